@@ -9,8 +9,12 @@ resident in HBM before the timed region.  `value` = radiance rays actually trace
 with depth > 0, counted by the kernels themselves; deterministic and partition-independent).  SURVEY.md 8d's closed form
 W*H*S*sum N^k is the full-tree upper bound and is reported beside it as `nominal_rays`.
 
-  python bench.py [--config 2|3|4|5] [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--config 2|3|4|5] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+--dump-outputs DIR writes, after the timed steps, the frame the last timed step handed its caller (rank 0's u8 RGB image) as
+DIR/frame.npy in float32: [H, W, 3] whole, or past 2^22 pixels (48 MB) a fixed seeded sample of 2^22 of them, [n, 3] in ascending pixel order.
+The inputs are fixed by the configuration (scene, size, options, seed), so two builds can be compared output for output.
 
 --config picks the workload (BASELINE.json `configs`, 1-based as SURVEY.md 8d numbers them; default 3 = the headline):
   2  spheres2.scn 1920x1080 --jsample 5 --shadow            3  spheres2.scn 1920x1080 --gillum 16 --shadow
@@ -87,6 +91,55 @@ def measured_traffic(config, variant):
     if tj.get("sources") != source_hashes():
         return None, "stale: the kernel sources have changed since the PMC passes (git blob hashes differ)"
     return tj, None
+
+
+DUMP_MAX_PIXELS = 1 << 22  # 48 MB of float32 RGB: --dump-outputs stays under 64 MB
+
+
+def hip_runtime():
+    """The HIP runtime already in this process (the one torch loaded), so that a copy runs on the same device context."""
+    import ctypes
+    with open("/proc/self/maps") as f:
+        path = next((ln.split()[-1] for ln in f if "/libamdhip64.so" in ln), None)
+    if path is None:
+        raise RuntimeError("no HIP runtime mapped into this process")
+    hip = ctypes.CDLL(path)
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    return hip
+
+
+def frame_to_host(frame, w, h):
+    """A frame a step handed back (a torch tensor, or the device address of a W*H*3 buffer libskr owns) -> numpy u8 [h, w, 3].
+    The caller has drained the device."""
+    import numpy as np
+    if frame is None:
+        raise RuntimeError("the last timed step handed back no frame")
+    if hasattr(frame, "cpu"):
+        out = frame.cpu().numpy()
+    else:
+        out = np.empty((h, w, 3), np.uint8)
+        rc = hip_runtime().hipMemcpy(out.ctypes.data, frame, out.nbytes, 2)  # 2 = hipMemcpyDeviceToHost
+        if rc != 0:
+            raise RuntimeError("hipMemcpy of the frame failed (hipError_t %d)" % rc)
+    assert out.shape == (h, w, 3) and out.dtype == np.uint8, (out.shape, out.dtype)
+    return out
+
+
+def dump_outputs(out_dir, rgb):
+    """DIR/frame.npy (float32): the whole frame, or past DUMP_MAX_PIXELS a fixed seeded sample of its pixels in ascending order."""
+    import numpy as np
+    px = rgb.reshape(-1, 3).astype(np.float32)
+    note = "whole frame [%d, %d, 3]" % rgb.shape[:2]
+    if px.shape[0] > DUMP_MAX_PIXELS:
+        n = DUMP_MAX_PIXELS
+        idx = np.sort(np.random.default_rng(SEED).choice(px.shape[0], n, replace=False))
+        px = px[idx]
+        note = "%d of the frame's %d pixels [n, 3] (numpy default_rng(%d) choice without replacement, sorted)" % (n, rgb.shape[0] * rgb.shape[1], SEED)
+    else:
+        px = px.reshape(rgb.shape)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), px)
+    return {"dir": out_dir, "frame.npy": note}
 
 
 def reference_sample(orc, cfg):
@@ -171,12 +224,15 @@ def main():
     ap.add_argument("--sync-frames", action="store_true", help="libskr's frame step with the collective on the render stream (skr_comm_render_frame) instead of pipelined behind the next frame")
     ap.add_argument("--no-side-pass", action="store_true", help="do not time the other frame step beside the timed one (profiling runs: a trace of --sync-frames --no-side-pass holds serial frames only)")
     ap.add_argument("--torch-gather", action="store_true", help="the round-1 frame step (torch.distributed all_gather + torch de-interleave) instead of libskr's")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame the last one computed to DIR/frame.npy (float32; see the module docstring)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     if args.steps is None:
         args.steps = cfg["steps"]
     if args.warmup is None:
         args.warmup = cfg["warmup"]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     W, H, KW = cfg["w"], cfg["h"], dict(cfg["kw"], seed=SEED)
     SCENE = os.path.join(SCENES, cfg["scene"])
 
@@ -266,15 +322,16 @@ def main():
     pipelined = comm is not None and not args.sync_frames
 
     frames_enqueued = [0]  # every frame this process asks the device for, timed or not (tools/pmc_traffic.py divides a profiled run's counters by it)
+    last_frame = [None]    # what the last step handed its caller (rank 0): a device address libskr owns, or the sharder's tensor
 
     def step():
         frames_enqueued[0] += 1
         if pipelined:  # frame f's all-gather + de-interleave on the communicator's stream while this stream renders frame f + 1
             comm.render_frame_async(opt, TILE_ROWS, stream.cuda_stream, want_previous=False)
         elif comm is not None:
-            comm.render_frame(opt, TILE_ROWS, stream.cuda_stream)
+            last_frame[0] = comm.render_frame(opt, TILE_ROWS, stream.cuda_stream)
         else:
-            sharder.step(lambda buf: r.render_tiles_into(opt, TILE_ROWS, rank, world, buf.data_ptr(), None, stream.cuda_stream))
+            last_frame[0] = sharder.step(lambda buf: r.render_tiles_into(opt, TILE_ROWS, rank, world, buf.data_ptr(), None, stream.cuda_stream))
 
     if pipelined:
         # one pipelined frame before anything is timed: it either works on every rank or the run is not the one that was asked for
@@ -295,7 +352,7 @@ def main():
 
     def sync():
         if pipelined:
-            comm.flush(stream.cuda_stream)  # the last frame's collective is part of the timed region
+            last_frame[0] = comm.flush(stream.cuda_stream)  # the last frame's collective is part of the timed region
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(dev)
@@ -311,6 +368,8 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     cnt = r.work(reset=True)
+    # the last timed frame, before any pass below reuses its buffers
+    dumped = dump_outputs(args.dump_outputs, frame_to_host(last_frame[0], W, H)) if args.dump_outputs and rank == 0 else None
 
     # the other frame step of the library beside the timed one, over a short pass of its own (outside the timed region): the serial step
     # (collective on the render stream) when the pipelined one was timed and the other way round — so that a run on G GPUs shows what
@@ -482,6 +541,8 @@ def main():
                              "level0_nodes": queued, "level1_records": level1,
                              "note": "north_star's requested figure — SURVEY.md 8(d): algorithmic bytes = W*H*3 + scene per frame, over ms_per_step; this path is not HBM-bound"},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
             out["config"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
