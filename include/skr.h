@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SKR_ABI_VERSION 3 /* 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
+#define SKR_ABI_VERSION 4 /* 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
 
 typedef enum {
 	SKR_OK = 0,
@@ -103,6 +103,15 @@ int skr_scene_create_from_scn(const char *path, int echo, skr_scene **out);
  * and shaded by the reference's own loops (blinn_phong.h:77-85,122-131; shadow test utils.h:60-76).  film_resolution and
  * max_depth are reported in skr_scene_info either way; --strict-scn makes the CLI honour them. */
 #define SKR_SCN_STRICT 1u
+/* SKR_SCN_FOG (`raytracer --scn-fog`; combines with SKR_SCN_STRICT): `spherical_fog x y z radius r g b scattering [absorption]` lines
+ * are parsed in the field order of the reference's sscanf (scene.cpp:210; a missing absorption is 0) and kept, in file order; a line with
+ * fewer than 8 numbers is still warned about, skipped and counted in n_fog_skipped.  Without the flag every fog line is skipped (the
+ * reference's parse is undefined behaviour).  A scene with fog volumes is shaded with the fog term of blinn_phong.h:19-43 (DESIGN.md
+ * "Spherical fog": for every lit point light at a sphere hit, the term of every fog volume instead of the diffuse and again instead of
+ * the specular term, the reference's rand() replaced by the counter RNG) on the general level pipeline; it cannot be combined with
+ * skr_options.legacy_reflect or shade_triangles (SKR_ERR_UNSUPPORTED). */
+#define SKR_SCN_FOG 2u
+#define SKR_FOG_MAX_VOLUMES 64
 int skr_scene_create_from_scn_ex(const char *path, int echo, uint32_t flags, skr_scene **out);
 /* Build a scene from arrays (synthetic tests): spheres[n][14] = centre(3) radius
  * ambient(3) diffuse(3) specular(3) power; triangles[n][9] = v0 v1 v2;
@@ -110,6 +119,11 @@ int skr_scene_create_from_scn_ex(const char *path, int echo, uint32_t flags, skr
 int skr_scene_create_from_arrays(const float *spheres, int32_t n_spheres, const float *triangles, int32_t n_triangles,
 								 const float *point_lights, int32_t n_point_lights, const float camera[9],
 								 const float background[3], const float ambient[3], skr_scene **out);
+/* The fog volumes of a scene, rows[n][9] = centre(3) radius albedo(3) scattering absorption, in file order (at most
+ * SKR_FOG_MAX_VOLUMES).  get: *n = their number, rows (if not NULL) receives them.  set: replaces them (n = 0: no fog) — scenes made
+ * from arrays, and tests that choose scattering and absorption; a renderer takes the volumes the scene has when it is created. */
+int skr_scene_get_fog(const skr_scene *scene, float *rows, int32_t *n);
+int skr_scene_set_fog(skr_scene *scene, const float *rows, int32_t n);
 void skr_scene_destroy(skr_scene *scene);
 int skr_scene_get_info(const skr_scene *scene, skr_scene_info *info);
 /* Copy the parsed arrays back out in the skr_scene_create_from_arrays layouts
@@ -309,7 +323,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  * 3 smallest_root(a,b,c), 4 triangle test (o,d,v0,v1,v2 -> hit,t),
  * 5 quantise(c -> u8 as u32), 6 basis(n -> nt,nb), 7 (a,b -> sqrtf(a), a/b), 8 philox at 10 rounds (op 0: the 7 the draws use),
  * 9 (hi16 -> mismatch counts of the short exact sqrt, 1/x, x/pi, x/pdf forms against the correctly rounded expansions over the
- * 65536 binary32 values with those high 16 bits).  in/out are DEVICE pointers
+ * 65536 binary32 values with those high 16 bits), 10 exp_spec (binary64 x as lo, hi words -> exp(x) likewise), 11 the fog term
+ * (40 words: [0..2] radius absorption scattering, [4..6] albedo, [8..10] L, [11] intensity, [12..14] light colour, [15] pass
+ * (0 diffuse, 1 specular), [16..18] sphere centre, [19] fog index, [20..22] light position, [23] light index, [24..26] kd, [27] pixel,
+ * [28..30] N, [31] node, [32] aa, [33..34] seed lo, hi; the rest 0 -> colour(3), no-interaction probability).  in/out are DEVICE pointers
  * to n records of the op's input/output width in 32-bit words. */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 

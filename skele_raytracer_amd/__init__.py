@@ -11,8 +11,8 @@ device memory, streams and torch.distributed.
 There is no CPU fallback: every render entry point raises if libskr.so or a
 gfx950 device is missing.
 """
-from .binding import (Options, Renderer, Scene, SkrError, lib, lib_path, parse_scene, radiance_ray_count,
+from .binding import (Options, Renderer, Scene, SkrError, lib, lib_path, parse_scene, scene_fov, radiance_ray_count,
                       write_ppm, write_png, write_pfm, EXPORTED_SYMBOLS)
 
-__all__ = ["Options", "Renderer", "Scene", "SkrError", "lib", "lib_path", "parse_scene", "radiance_ray_count",
+__all__ = ["Options", "Renderer", "Scene", "SkrError", "lib", "lib_path", "parse_scene", "scene_fov", "radiance_ray_count",
            "write_ppm", "write_png", "write_pfm", "EXPORTED_SYMBOLS"]

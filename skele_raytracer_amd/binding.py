@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -70,6 +70,8 @@ def lib():
     L.skr_scene_create_from_arrays.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, C.POINTER(vp)]
     L.skr_scene_set_triangle_materials.argtypes = [vp, vp]
     L.skr_scene_set_sphere_ior.argtypes = [vp, vp]
+    L.skr_scene_get_fog.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.skr_scene_set_fog.argtypes = [vp, vp, C.c_int32]
     L.skr_scene_destroy.argtypes = [vp]
     L.skr_scene_destroy.restype = None
     L.skr_scene_get_info.argtypes = [vp, C.POINTER(CSceneInfo)]
@@ -149,9 +151,12 @@ class Options:
     """Reference struct Options (utils.h:26-34) with the reference's defaults, plus the
     width/height/use_shadows main() folds in (main.cpp:393-396) and the RNG seed."""
 
-    def __init__(self, width=1920, height=1080, fov=60.0, gillum=None, jsample=0, depth=3, shadow=False, seed=1, shade_triangles=False, progressive=1, legacy_reflect=False):
+    def __init__(self, width=1920, height=1080, fov=None, gillum=None, jsample=0, depth=3, shadow=False, seed=1, shade_triangles=False, progressive=1, legacy_reflect=False,
+                 scn_fov=None):
         c = COptions()
         lib().skr_options_default(C.byref(c))
+        if fov is None:  # --scn-fov: fov = 2 x the camera line's half_height_angle (a Scene in scn_fov) unless --fov is given; else utils.h:30
+            fov = scene_fov(scn_fov) if scn_fov is not None else 60.0
         c.width, c.height, c.fov = width, height, fov
         if gillum is not None:  # main.cpp:252-253: --gillum N sets monte_carlo and num_path_traces
             c.monte_carlo, c.num_path_traces = 1, gillum
@@ -217,6 +222,20 @@ class Scene:
                "skr_scene_get_culling")
         return cs.value, tris, sph, links, ch
 
+    @property
+    def fog(self):
+        """The fog volumes [n, 9] = centre(3) radius albedo(3) scattering absorption, in file order (include/skr.h skr_scene_get_fog)."""
+        n = C.c_int32()
+        _check(lib().skr_scene_get_fog(self.h, None, C.byref(n)), "skr_scene_get_fog")
+        rows = np.zeros((n.value, 9), np.float32)
+        _check(lib().skr_scene_get_fog(self.h, rows.ctypes.data, C.byref(n)), "skr_scene_get_fog")
+        return rows
+
+    def set_fog(self, rows):
+        """Replace the fog volumes (rows [n, 9] as `fog` returns them; n = 0: none).  A renderer takes those the scene has when it is made."""
+        r = np.ascontiguousarray(rows, np.float32).reshape(-1, 9)
+        _check(lib().skr_scene_set_fog(self.h, r.ctypes.data, len(r)), "skr_scene_set_fog")
+
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
@@ -239,11 +258,22 @@ class Scene:
         return sc
 
 
-def parse_scene(path, echo=False, strict=False):
-    """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept)."""
+SCN_STRICT, SCN_FOG = 1, 2  # include/skr.h SKR_SCN_*
+FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
+
+
+def parse_scene(path, echo=False, strict=False, fog=False):
+    """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept),
+    fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded)."""
     h = C.c_void_p()
-    _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), 1 if strict else 0, C.byref(h)), "skr_scene_create_from_scn_ex")
+    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0)
+    _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), flags, C.byref(h)), "skr_scene_create_from_scn_ex")
     return Scene(h.value)
+
+
+def scene_fov(scene):
+    """--scn-fov: the field of view the camera line asks for, 2 x half_height_angle (exact in binary32)."""
+    return float(np.float32(2) * np.float32(scene.info.camera[12]))
 
 
 def write_ppm(path, rgb):

@@ -47,6 +47,8 @@ struct skr_renderer {
 	float4 *d_camec = nullptr; // per sphere {cam_pos - centre, |.|^2 - r^2} (render_wave.hip skr_camec_kernel), + 16 rows of padding
 	bool is_clone = false;    // skr_renderer_clone: the scene blob and the work counters belong to the renderer it was cloned from
 	size_t off_amb = 0, off_kd = 0, off_ks = 0, off_lights = 0, off_tris = 0, off_chunks = 0, off_tri_mats = 0;
+	size_t off_fog = 0;       // --scn-fog: 2 rows per fog volume (render_params.h RenderParams::fog_row)
+	int n_fog = 0;
 	int n_chunks = 0, chunk_size = 0, cones = 0;
 	size_t chunk_stride = 0;
 	unsigned long long *d_counters = nullptr;
@@ -140,7 +142,17 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	r->n_chunks = scene->info.n_triangles ? scene->tri_node_count : 0; // nodes of the chunk tree (scene_host.h)
 	const size_t ntm = scene->tri_mats.size();
 	r->off_tri_mats = 4 * ns + nl2 + nt3 + nch;
-	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm;
+	// the fog volumes (skr_scene raw_fog, SKR_SCN_FOG / skr_scene_set_fog): [radius absorption scattering 0] [albedo 0]
+	const size_t nfog = scene->raw_fog.size() / 9;
+	if(nfog > SKR_FOG_MAX_VOLUMES)
+	{
+		skr_set_error("scene has %zu fog volumes; at most %d are supported", nfog, SKR_FOG_MAX_VOLUMES);
+		delete r;
+		return SKR_ERR_UNSUPPORTED;
+	}
+	r->off_fog = 4 * ns + nl2 + nt3 + nch + ntm;
+	r->n_fog = (int) nfog;
+	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog;
 	std::vector<skr_f4> blob(total + 16); // (+ 16 rows: the sphere loops ask for the rows of a trip ahead without a bounds test, shade_common.h sphere_rows)
 	if(ns)
 	{
@@ -162,6 +174,12 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	if(nt3) memcpy(&blob[r->off_tris], scene->tris.data(), nt3 * 16);
 	if(nch) memcpy(&blob[r->off_chunks], scene->tri_chunks.data(), nch * 16);
 	if(ntm) memcpy(&blob[r->off_tri_mats], scene->tri_mats.data(), ntm * 16);
+	for(size_t j = 0; j < nfog; j++)
+	{
+		const float *f = &scene->raw_fog[9 * j]; // x y z radius r g b scattering absorption
+		blob[r->off_fog + 2 * j] = {f[3], f[8], f[7], 0.0f};
+		blob[r->off_fog + 2 * j + 1] = {f[4], f[5], f[6], 0.0f};
+	}
 	r->blob_bytes = blob.size() * 16;
 	hipError_t e = hipMalloc((void **) &r->d_blob, blob.size() * 16);
 	if(e == hipSuccess) e = hipMemcpy(r->d_blob, blob.data(), blob.size() * 16, hipMemcpyHostToDevice);
@@ -213,6 +231,7 @@ int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 	r->is_clone = true;
 	r->off_amb = src->off_amb; r->off_kd = src->off_kd; r->off_ks = src->off_ks; r->off_lights = src->off_lights;
 	r->off_tris = src->off_tris; r->off_chunks = src->off_chunks; r->off_tri_mats = src->off_tri_mats;
+	r->off_fog = src->off_fog; r->n_fog = src->n_fog;
 	r->n_chunks = src->n_chunks; r->chunk_size = src->chunk_size; r->cones = src->cones; r->chunk_stride = src->chunk_stride;
 	r->d_counters = src->d_counters;
 	r->d_tri_work = src->d_tri_work;
@@ -372,6 +391,14 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 			skr_set_error("gillum %d at depth %d needs more than 2^32 tree nodes per sample", p.num_path_traces, p.max_depth);
 			return SKR_ERR_UNSUPPORTED;
 		}
+	}
+	// --scn-fog: a scene with fog volumes renders on the general level pipeline (render_kernel.hip skr_generic_selected)
+	p.n_fog = r->n_fog;
+	p.fog_row = (uint32_t) r->off_fog;
+	if(p.n_fog > 0 && (opt->legacy_reflect || opt->shade_triangles))
+	{
+		skr_set_error("fog volumes (--scn-fog) cannot be combined with --legacy-reflect or --shade-triangles");
+		return SKR_ERR_UNSUPPORTED;
 	}
 	p.seed_lo = (uint32_t) opt->seed;
 	p.seed_hi = (uint32_t) (opt->seed >> 32);

@@ -192,6 +192,15 @@ SKR_DEV void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint
 // applies to rand() (raytrace.h:119-120, main.cpp:146); float(RAND_MAX) == 2^31.
 SKR_DEV float u31_to_unit(uint32_t w) { return (float) (w >> 1) * 4.656612873077392578125e-10f; } // * 2^-31 is exact
 
+// The fog draws (--scn-fog, DESIGN.md "Spherical fog"): ONE call per (node, point light l, fog j, diffuse / specular pass) stands for the
+// four rand() calls of blinn_phong.h:28 and utils.h:219-221.  Counter (pixel, aa, node, fog_ctr3(l, j, pass)): bit 31 set, so it is
+// disjoint from the hemisphere draws (ctr[3] = child >> 1 < 2^30) and from the jitter (ctr[3] = 0xFFFFFFFF, never formed here: l < 2^22,
+// j < 64 leave bits 7 of ctr[3] clear).  u0 = u31(out[0]) (float(rand()) / float(RAND_MAX)), and x, y, z = -1 + u30(out[1..3]) with
+// u30(w) = float(w >> 1) / float(RAND_MAX / 2) = float(w >> 1) * 2^-30 (utils.h:219-221: RAND_MAX / (1 + 1) is an integer divide).
+#define SKR_FOG_MAX 64 // == SKR_FOG_MAX_VOLUMES (include/skr.h)
+SKR_DEV uint32_t fog_ctr3(uint32_t light, uint32_t fog, uint32_t pass) { return 0x80000000u | (light << 8) | (fog << 1) | pass; }
+SKR_DEV float u31_to_pm1(uint32_t w) { return -1.0f + (float) (w >> 1) * 9.31322574615478515625e-10f; } // * 2^-30 is exact
+
 // ------------------------------------------------------- shared math ----
 typedef float f2 __attribute__((ext_vector_type(2)));
 SKR_DEV f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); } // v_pk_fma_f32: two IEEE fmaf
@@ -235,6 +244,39 @@ SKR_DEV void sincos_spec(float phi, float &s, float &c)
 	sincos_spec2(splat2(phi), s2, c2);
 	s = s2.x;
 	c = c2.x;
+}
+
+// exp() of binary64, the function the reference's unqualified exp(float) binds to (blinn_phong.h:27; --scn-fog only), restated so that
+// host and device agree bit for bit: libm and the device library are not bound to the same last bit.  k = rint(x / ln 2); two-term
+// Cody-Waite reduction r = x - k ln2 (fdlibm's split: k * LN2_HI is exact for |k| < 2^21; one fma each step); exp(r) by its Taylor
+// series to r^13 (|r| <= 0.347: truncation 4e-18 relative) in Horner form with fma; 2^k applied as two exact powers of two, so that a
+// result near the overflow / underflow edges rounds once, in the last multiply.  Every step is one IEEE binary64 operation.  Error against
+// exp correctly rounded: DESIGN.md "Spherical fog" (tools/exp_exhaustive.c).
+SKR_DEV double exp_spec(double x)
+{
+	if(x != x) return x;
+	if(x > 710.0) return __builtin_inf();
+	if(x < -746.0) return 0.0;
+	const double k = __builtin_rint(x * 0x1.71547652b82fep+0);
+	double r = __builtin_fma(-k, 0x1.62e42feep-1, x);
+	r = __builtin_fma(-k, 0x1.a39ef35793c76p-33, r);
+	double q = 0x1.6124613a86d09p-33; // 1/13!, then 1/12! .. 1/2!, 1, 1
+	q = __builtin_fma(q, r, 0x1.1eed8eff8d898p-29);
+	q = __builtin_fma(q, r, 0x1.ae64567f544e4p-26);
+	q = __builtin_fma(q, r, 0x1.27e4fb7789f5cp-22);
+	q = __builtin_fma(q, r, 0x1.71de3a556c734p-19);
+	q = __builtin_fma(q, r, 0x1.a01a01a01a01ap-16);
+	q = __builtin_fma(q, r, 0x1.a01a01a01a01ap-13);
+	q = __builtin_fma(q, r, 0x1.6c16c16c16c17p-10);
+	q = __builtin_fma(q, r, 0x1.1111111111111p-7);
+	q = __builtin_fma(q, r, 0x1.5555555555555p-5);
+	q = __builtin_fma(q, r, 0x1.5555555555555p-3);
+	q = __builtin_fma(q, r, 0.5);
+	q = __builtin_fma(q, r, 1.0);
+	q = __builtin_fma(q, r, 1.0);
+	const int ki = (int) k, k1 = ki >> 1, k2 = ki - k1;
+	const double s1 = __longlong_as_double((long long) (k1 + 1023) << 52), s2 = __longlong_as_double((long long) (k2 + 1023) << 52);
+	return (q * s1) * s2;
 }
 
 // General (non-integer exponent) branch of powf_spec: 2^(p log2 x) in binary64.  Cold for every

@@ -5,7 +5,7 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --shade-triangles, --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm.
+// --scn-fog, --scn-fov, --shade-triangles, --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm.
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +24,7 @@ int main(int argc, char *argv[])
 	bool quiet = false;
 	int device = 0, gpus = 1;
 	bool strict_scn = false, width_given = false, height_given = false, depth_given = false; // --strict-scn (new)
+	bool scn_fog = false, scn_fov = false, fov_given = false; // --scn-fog, --scn-fov (new: DESIGN.md "Spherical fog", "Camera half-angle")
 	bool sharded = false; // --gpus given (even --gpus 1): the frame goes through the multi-GPU path
 	uint32_t tile_rows = 8;
 	uint32_t progressive_every = 0; // --progressive-every M: the output file is rewritten after every M passes (the headless "viewer")
@@ -49,6 +50,7 @@ int main(int argc, char *argv[])
 				return 0;
 			}
 			option.fov = (float) atof(argv[i + 1]);
+			fov_given = true;
 		}
 		if(!strcmp(argv[i], "--jsample"))
 		{
@@ -119,6 +121,8 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--tile-rows") && has_next) tile_rows = (uint32_t) (atoi(argv[i + 1]) > 0 ? atoi(argv[i + 1]) : 8);
 		if(!strcmp(argv[i], "--quiet")) quiet = true;
 		if(!strcmp(argv[i], "--strict-scn")) strict_scn = true;
+		if(!strcmp(argv[i], "--scn-fog")) scn_fog = true;                   // new: spherical_fog lines parsed and shaded (include/skr.h SKR_SCN_FOG)
+		if(!strcmp(argv[i], "--scn-fov")) scn_fov = true;                   // new: fov = 2 x the camera line's half_height_angle unless --fov is given
 		if(!strcmp(argv[i], "--shade-triangles")) option.shade_triangles = 1; // new: triangles as surfaces (include/skr.h skr_options)
 		if(!strcmp(argv[i], "--legacy-reflect")) option.legacy_reflect = 1;   // new: the reflection / refraction code behind raytrace.h:44's early return
 		if(!strcmp(argv[i], "--progressive") && has_next) option.progressive_passes = atoi(argv[i + 1]) > 1 ? atoi(argv[i + 1]) : 1; // new: mean of K frames, seeds seed..seed+K-1
@@ -137,7 +141,7 @@ int main(int argc, char *argv[])
 	}
 
 	skr_scene *scene = nullptr;
-	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, strict_scn ? SKR_SCN_STRICT : 0u, &scene) != SKR_OK)
+	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u), &scene) != SKR_OK)
 	{
 		printf("%s\n", skr_last_error()); // scene.cpp:24-25: message, exit(0)
 		return 0;
@@ -150,6 +154,12 @@ int main(int argc, char *argv[])
 		if(!width_given && info.film_width > 0) option.width = info.film_width;
 		if(!height_given && info.film_height > 0) option.height = info.film_height;
 		if(!depth_given && info.max_depth_parsed > 0) option.max_depth = info.max_depth_parsed;
+	}
+	if(scn_fov && !fov_given)
+	{ // camera.h:14 halfHeightAngle, parsed and never used by the reference: the .scn holds for what argv leaves open (2 h is exact)
+		skr_scene_info info;
+		skr_scene_get_info(scene, &info);
+		option.fov = 2.0f * info.camera[12];
 	}
 	// utils.h:35-38 Options::to_string
 	printf("\n\nMonte carlo: %d\nvisual display: %d\nfov: %f\nnum paths traced: %d\nsupersample grid size: %d\nmax depth: %d\n",

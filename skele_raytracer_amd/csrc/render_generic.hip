@@ -8,7 +8,8 @@
 //     test the triangle they start on;
 //   * --legacy-reflect: every shaded sphere hit has, besides its N --gillum children, two children per light —
 //     the refraction and the reflection ray of raytrace.h:54-99 — from the hit point itself;
-//   * --gillum beyond 256 children per node.
+//   * --gillum beyond 256 children per node;
+//   * scenes with fog volumes (--scn-fog, DESIGN.md "Spherical fog"): the fog term of every lit point light at a sphere hit.
 //
 // Levels.  Level 0 is the camera: one root per pixel of the band with ONE child, the primary ray (main.cpp:140-182).  A hit of level k
 // (k >= 1) is a node of level k; it is shaded when its record is activated and, while k < --depth, its A = N + 2 L children are
@@ -263,6 +264,8 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 
 } // namespace
 
+// FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
+template <bool FOG>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
 	extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -319,7 +322,8 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		}
 		else n.N = normalize3(n.P - ld3(sv.geom[surf])); // :205
 		cn.hits++;
-		n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn);
+		if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn);
+		else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn);
 		n.fr = (p.legacy_reflect && !(surf & SURF_TRI)) ? legacy_fresnel(n.d, n.N, ks4.w) : 0.0f; // :46
 		if(p.g_last)
 		{ // its children are shade(depth 0) == (0,0,0): the node is finished
@@ -505,7 +509,8 @@ hipError_t skr_launch_generic(const RenderParams &p_in, hipStream_t stream, cons
 				p.g_nodes_dst = L < D ? reinterpret_cast<float4 *>(base + pl.off_nodes[L]) : nullptr;
 				p.res_out = reinterpret_cast<float *>(base + pl.off_res[L]);
 				const unsigned grid_a = SKR_P1_REGIONS * ((pl.cap[L] + 255u) / 256u);
-				hipLaunchKernelGGL(skr_gactivate_kernel, dim3(grid_a), dim3(256), lds, stream, p);
+				if(p.n_fog > 0) hipLaunchKernelGGL(skr_gactivate_kernel<true>, dim3(grid_a), dim3(256), lds, stream, p);
+				else hipLaunchKernelGGL(skr_gactivate_kernel<false>, dim3(grid_a), dim3(256), lds, stream, p);
 			}
 			for(int L = D - 1; L >= 0; L--)
 			{ // sums, deepest level first; level 0 writes the pixels

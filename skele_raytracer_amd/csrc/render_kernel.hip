@@ -5,7 +5,7 @@
 //   * the node pipeline (render_nodes.hip: sibling-pair kernels, persistent leaf kernel) for --gillum trees over sphere scenes
 //     (and scenes with a handful of triangles) — the headline path;
 //   * the general level pipeline (render_generic.hip: one lane per ray) for meshes under --gillum, --shade-triangles,
-//     --legacy-reflect and more than 256 children per node.
+//     --legacy-reflect, fog volumes (--scn-fog) and more than 256 children per node.
 // Rounds 1-2 also had a lane-per-pixel kernel with the recursion depth as a template parameter (--depth <= 6) here; the level
 // pipelines take any depth.
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@ static bool has_tree(const RenderParams &p) { return p.max_depth > 1; }
 bool skr_generic_selected(const RenderParams &p)
 {
 	if(p.sw.pipeline == SKR_PIPE_GENERIC) return true;
-	if(p.shade_triangles || p.legacy_reflect) return true;
+	if(p.shade_triangles || p.legacy_reflect || p.n_fog > 0) return true;
 	return has_tree(p) && !skr_nodes_selected(p);
 }
 
@@ -144,6 +144,27 @@ __global__ void skr_debug_kernel(int op, const uint32_t *in, uint32_t *out, uint
 		case 7: { // binary32 sqrt and divide must be the correctly rounded forms
 			out[2 * i] = U(sk_sqrtf(F(in[2 * i])));
 			out[2 * i + 1] = U(sk_divf(F(in[2 * i]), F(in[2 * i + 1])));
+			break;
+		}
+		case 10: { // exp_spec (binary64 in, binary64 out: lo, hi words)
+			const double x = __hiloint2double((int) in[2 * i + 1], (int) in[2 * i]);
+			const double y = exp_spec(x);
+			out[2 * i] = (uint32_t) __double2loint(y);
+			out[2 * i + 1] = (uint32_t) __double2hiint(y);
+			break;
+		}
+		case 11: { // fog_term: 40 words in (include/skr.h), {colour, no-interaction probability} out
+			const uint32_t *r = in + 40 * i;
+			auto v3 = [&](int k) { return mk3(F(r[k]), F(r[k + 1]), F(r[k + 2])); };
+			const float4 a = make_float4(F(r[0]), F(r[1]), F(r[2]), 0.0f), alb = make_float4(F(r[4]), F(r[5]), F(r[6]), 0.0f);
+			LightTerm t;
+			t.L = v3(8);
+			t.intensity = F(r[11]);
+			t.lc = v3(12);
+			const uint32_t ctr[4] = {r[27], r[32], r[31], fog_ctr3(r[23], r[19], r[15])};
+			float pni = 0.0f;
+			const f3 c = fog_term(a, alb, t, v3(16), v3(20), v3(24), v3(28), ctr, r[33], r[34], &pni);
+			out[4 * i] = U(c.x); out[4 * i + 1] = U(c.y); out[4 * i + 2] = U(c.z); out[4 * i + 3] = U(pni);
 			break;
 		}
 		default: break;

@@ -59,6 +59,11 @@ struct RenderParams {
 	uint32_t *qctr;     // [0] the number of level-0 nodes skr_primary_kernel appended
 	float *acc;         // float3 per output pixel: the running `image[y][x] += shade(...)` of main.cpp:162 (AA under --gillum: one pass per sample)
 	uint32_t aa_index;  // which AA sample this launch traces
+	// --scn-fog (DESIGN.md "Spherical fog"; general level pipeline): the fog volumes in file order, 2 float4 each — [radius absorption
+	// scattering 0] [albedo 0] —, at row fog_row of the scene blob (sph_geom + fog_row; HBM, never written by a kernel); n_fog of them
+	// (<= SKR_FOG_MAX, device_math.h; 0 = no fog).  Both sit in alignment holes: the struct keeps its size and every other field its
+	// offset, so the kernels that never read them compile to the same code.
+	uint32_t fog_row;
 	// node pipeline (render_nodes.hip): the --gillum tree cut at every level.  A node is a shaded sphere hit; level 0 = the
 	// primary hits.  A node is two rows of two float4 in two arrays, so that every kernel reads only the half it needs:
 	//   geometry (tracing its children): [co.xyz N.x] [N.yz pixel node-id]                       (node id 0 at level 0)
@@ -84,6 +89,7 @@ struct RenderParams {
 	uint32_t g_level;         // the level a launch works on (trace / activate: the rays' level, 1 = primary; finalize: the nodes' level, 0 = the camera)
 	uint32_t g_arity;         // children per node of the level whose children are traced / summed (1 at the camera level); activate: the tree's arity (node ids)
 	uint32_t g_last;          // activate: the hits of the last level (their children are shade(depth 0) == 0) are finished at once
+	int32_t n_fog;            // (see fog_row)
 	const float4 *g_nodes_src; // nodes of the level above (trace, activate) / of the level being summed (finalize): 5 float4 each
 	float4 *g_nodes_dst;      // nodes being written (activate)
 };

@@ -473,8 +473,9 @@ static void set_camera(skr_scene_info &info, const float p[3], const float d[3],
 	info.camera[12] = ha;
 }
 
-int skr_parse_scn(const std::string &path, bool echo, bool strict, skr_scene &sc)
+int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene &sc)
 {
+	const bool strict = (flags & SKR_SCN_STRICT) != 0, fog = (flags & SKR_SCN_FOG) != 0;
 	FILE *fp = fopen(path.c_str(), "r");
 	if(!fp)
 	{
@@ -637,8 +638,20 @@ int skr_parse_scn(const std::string &path, bool echo, bool strict, skr_scene &sc
 		{
 			// scene.cpp:207-212 pushes a fog volume built from uninitialised floats
 			// (sscanf "fog ..." never matches): undefined behaviour, pinned as "ignored".
-			fprintf(stderr, "WARNING. spherical_fog is not reproducible in the reference (uninitialised data): line skipped\n");
-			info.n_fog_skipped++;
+			// SKR_SCN_FOG: the fields in the order of that sscanf, x y z radius r g b scattering [absorption = 0]
+			float v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+			const int got = fog ? read_floats(args, v, 9) : 0;
+			if(got >= 8)
+			{
+				if(echo) printf("spherical fog at (%f, %f, %f), radius %f, albedo (%f, %f, %f), scattering %f, absorption %f\n", v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]);
+				sc.raw_fog.insert(sc.raw_fog.end(), v, v + 9);
+			}
+			else
+			{
+				fprintf(stderr, fog ? "WARNING. spherical_fog needs at least 8 numbers (x y z radius r g b scattering [absorption]): line skipped\n"
+				                    : "WARNING. spherical_fog is not reproducible in the reference (uninitialised data): line skipped\n");
+				info.n_fog_skipped++;
+			}
 		}
 		else
 		{
@@ -663,7 +676,7 @@ int skr_scene_create_from_scn_ex(const char *path, int echo, uint32_t flags, skr
 		return SKR_ERR_ARG;
 	}
 	skr_scene *sc = new skr_scene();
-	int rc = skr_parse_scn(path, echo != 0, (flags & SKR_SCN_STRICT) != 0, *sc);
+	int rc = skr_parse_scn(path, echo != 0, flags, *sc);
 	if(rc != SKR_OK)
 	{
 		delete sc;
@@ -723,6 +736,25 @@ int skr_scene_set_sphere_ior(skr_scene *scene, const float *ior)
 	}
 	scene->raw_sphere_ior.assign(ior, ior + scene->info.n_spheres);
 	for(int i = 0; i < scene->info.n_spheres; i++) scene->sph_ks[i].w = ior[i];
+	return SKR_OK;
+}
+
+int skr_scene_set_fog(skr_scene *scene, const float *rows, int32_t n)
+{
+	if(!scene || n < 0 || n > SKR_FOG_MAX_VOLUMES || (n && !rows))
+	{
+		skr_set_error("skr_scene_set_fog: bad argument (at most %d fog volumes)", SKR_FOG_MAX_VOLUMES);
+		return SKR_ERR_ARG;
+	}
+	scene->raw_fog.assign(rows, rows + (size_t) n * 9);
+	return SKR_OK;
+}
+
+int skr_scene_get_fog(const skr_scene *scene, float *rows, int32_t *n)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(n) *n = (int32_t) (scene->raw_fog.size() / 9);
+	if(rows && !scene->raw_fog.empty()) memcpy(rows, scene->raw_fog.data(), scene->raw_fog.size() * 4);
 	return SKR_OK;
 }
 

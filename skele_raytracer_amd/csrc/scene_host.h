@@ -25,6 +25,7 @@ struct skr_scene {
 	                                     //         (read by --shade-triangles only; shorter than n = the default material, material.h:9-17)
 	std::vector<float> raw_point_lights; // [n][6]  position colour
 	std::vector<float> raw_directional_lights; // [n][6] direction colour — --strict-scn only (scene.cpp:139-163 drops them)
+	std::vector<float> raw_fog;          // [n][9] centre radius albedo scattering absorption — SKR_SCN_FOG / skr_scene_set_fog only (file order)
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	skr_scene_info info{};
 
@@ -55,6 +56,6 @@ struct skr_scene {
 };
 
 // scene.cpp:12-227 replacement.  Returns SKR_OK or SKR_ERR_IO.
-int skr_parse_scn(const std::string &path, bool echo, bool strict, skr_scene &out);
+int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene &out);
 
 void skr_set_error(const char *fmt, ...);

@@ -458,6 +458,73 @@ SKR_DEV f3 direct_light(const SceneView &sv, const RenderParams &p, int sph, f3 
 	return direct_light_of<COHERENT>(sv, p, ld3(sv.kd[sph]), ld3(sv.ks[sph]), sv.amb[sph], P, N, cn);
 }
 
+// ---- --scn-fog (DESIGN.md "Spherical fog"; general level pipeline only): blinn_phong.h:19-43 as written, rand() replaced ----
+// One fog term (blinn_phong.h:19-43 with utils.h:216-225 inlined) for the lit point light t at `lpos` and a hit on the sphere at `centre`;
+// the fog's rows a = [radius absorption scattering -], alb = [albedo -] (RenderParams::fog).  ctr: the counter of its one Philox call.
+SKR_DEV f3 fog_term(float4 a, float4 alb, const LightTerm &t, f3 centre, f3 lpos, f3 kd, f3 N, const uint32_t ctr[4], uint32_t k0, uint32_t k1,
+					float *no_interaction_out = nullptr)
+{
+	float distance = length3(centre - lpos); // :22 (the sphere's centre, not the hit point)
+	if(distance > 2 * a.x) distance = 2 * a.x;
+	const float no_interaction = (float) exp_spec((double) ((-1.0f * distance) * (a.y + a.z))); // :27, binary64 exp
+	if(no_interaction_out) *no_interaction_out = no_interaction;
+	uint32_t rnd[4];
+	philox4x32(ctr[0], ctr[1], ctr[2], ctr[3], k0, k1, rnd);
+	if(u31_to_unit(rnd[0]) > no_interaction) return ((kd * t.lc) * t.intensity) * max0(dot3(N, t.L)); // :30-38, the plain diffuse term
+	// :41-42 + utils.h:219-224: the direction is not re-normalised, no intensity factor
+	const f3 nd = mk3(t.L.x + u31_to_pm1(rnd[1]) * a.z, t.L.y + u31_to_pm1(rnd[2]) * a.z, t.L.z + u31_to_pm1(rnd[3]) * a.z);
+	return (ld3(alb) * t.lc) * max0(dot3(N, nd));
+}
+
+// direct_light_of() for a sphere hit of a scene with fog (blinn_phong.h:47-134): every lit point light adds the fog term of every fog
+// volume, in file order, INSTEAD of its diffuse term, and again instead of its specular term; directional lights and the ambient term
+// are unchanged.  (pixel, node): the node's counter words (DESIGN.md "Counter RNG").
+SKR_DEV f3 direct_light_fog(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, f3 centre, uint32_t pixel,
+							uint32_t node, Counters &cn)
+{
+	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
+	const f3 view = normalize3(p.cam_pos - P);
+	for(int i = 0; i < sv.nl; i += 2)
+	{
+		const bool second = i + 1 < sv.nl;
+		const LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
+		bool occ0 = false, occ1 = false;
+		if(p.use_shadows)
+		{
+			cn.shadow_rays += second ? 2u : 1u;
+			occluded_pair<false>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests);
+		}
+		auto add_light = [&](const LightTerm &t, int l, bool lit)
+		{
+			if(!lit) return;
+			const float4 lp4 = sv.lights[2 * l];
+			if(lp4.w == 0.0f)
+			{ // a point light: blinn_phong.h:62-64, :106-108
+				for(uint32_t pass = 0; pass < 2; pass++)
+					for(int j = 0; j < p.n_fog; j++)
+					{
+						const uint32_t ctr[4] = {pixel, p.aa_index, node, fog_ctr3((uint32_t) l, (uint32_t) j, pass)};
+						const f3 f = fog_term(load_const4(p.sph_geom + p.fog_row, 2 * j), load_const4(p.sph_geom + p.fog_row, 2 * j + 1), t, centre, ld3(lp4), kd, N, ctr, p.seed_lo, p.seed_hi);
+						if(pass == 0) diffuse = diffuse + f;
+						else specular = specular + f;
+					}
+				return;
+			}
+			diffuse = diffuse + ((kd * t.lc) * t.intensity) * max0(dot3(N, t.L));
+			const f3 vl = view + t.L;
+			const f3 H = vl / length3(vl);
+			specular = specular + ((ks * t.lc) * t.intensity) * powf_spec(max0(dot3(N, H)), ambp.w, p.pow_steps);
+		};
+		add_light(t0, i, !occ0);
+		add_light(t1, i + 1, second && !occ1);
+	}
+	f3 total = mk3(0, 0, 0);
+	total = total + ld3(ambp);
+	total = total + diffuse;
+	total = total + specular;
+	return total;
+}
+
 // raytrace.h:22-30 + :117-125: hemisphere sample and the reference's basis mix
 // (perp_to_both.y/.z where perp_to_normal.y/.z belongs — kept), for the two sibling rays of a pair at once in packed binary32
 // (every component is the one-ray expression: v_pk_* round each half like the scalar instruction).

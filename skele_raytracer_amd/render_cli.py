@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--shade-triangles] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm]
+           [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
            --gillum 64 --jsample 5 --shadow            # BASELINE config 5
@@ -60,6 +60,7 @@ def _parse(argv):
             given.add("height")
         elif a == "--fov":
             opt["fov"] = value(i, _atof, "fov takes a float (degrees) after flag for the field of view")
+            given.add("fov")
         elif a == "--gillum":
             if i + 1 < len(argv):  # main.cpp:250-253: monte_carlo = true, num_path_traces = atoi(next) — 0 for a non-number
                 opt["gillum"] = _atoi(argv[i + 1])
@@ -76,6 +77,10 @@ def _parse(argv):
             opt["shadow"] = True
         elif a == "--strict-scn":
             opt["strict_scn"] = True
+        elif a == "--scn-fog":
+            opt["scn_fog"] = True
+        elif a == "--scn-fov":
+            opt["scn_fov"] = True
         elif a == "--shade-triangles":
             opt["shade_triangles"] = True
         elif a == "--legacy-reflect":
@@ -94,7 +99,7 @@ def _parse(argv):
         raise ValueError("tile-rows takes a positive int")
     if opt.get("format", "ppm") not in ("ppm", "png", "pfm"):
         raise ValueError("format takes ppm, png or pfm")
-    if opt.get("strict_scn"):
+    if opt.get("strict_scn") or opt.get("scn_fov"):
         opt["_given"] = given
     if opt["path"] is None:
         raise ValueError("no scene file was passed. Pass with --path path_to_scn")
@@ -136,7 +141,7 @@ def main(argv=None):
         else:
             dist.init_process_group("nccl", device_id=dev)  # RCCL over xGMI
     try:
-        scene = skr.parse_scene(o["path"], strict=bool(o.get("strict_scn")))
+        scene = skr.parse_scene(o["path"], strict=bool(o.get("strict_scn")), fog=bool(o.get("scn_fog")))
     except skr.SkrError as e:
         if rank == 0:
             print(str(e))  # scene.cpp:24: "Can't open file" on stdout, exit(0)
@@ -151,6 +156,8 @@ def main(argv=None):
             o["height"] = info.film_height
         if "depth" not in o["_given"] and info.max_depth_parsed > 0:
             o["depth"] = info.max_depth_parsed
+    if o.get("scn_fov") and "fov" not in o["_given"]:  # as bin/raytracer --scn-fov: 2 x the camera line's half_height_angle unless --fov is given
+        o["fov"] = skr.scene_fov(scene)
     r = skr.Renderer(scene, local_rank)
     kw = dict(fov=o["fov"], depth=o["depth"], shadow=o["shadow"], seed=o["seed"], shade_triangles=bool(o.get("shade_triangles")), progressive=o.get("progressive", 1), legacy_reflect=bool(o.get("legacy_reflect")))
     if o["gillum"] is not None:
