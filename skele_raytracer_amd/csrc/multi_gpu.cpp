@@ -10,6 +10,11 @@
 //   skr_comm_*    one process PER device (torchrun, mpirun): the same frame step on a communicator made with
 //                 ncclCommInitRank from an id the caller broadcasts by whatever transport it has.  What bench.py uses.
 //
+// Each has a serial step (the collective on the render stream) and a pipelined one (the collective on a stream of its own, two buffer
+// sets).  All four are made of the same per-device parts: a Rank is what one device owns, render_rank its frame up to the collective,
+// finish_rank what follows the collective.  Only the collective is the shape's own: one ncclAllGather per process (skr_comm) against
+// one grouped call over every device (skr_multi).
+//
 // Tile t belongs to rank t mod G (cost is very non-uniform vertically); random numbers are keyed by the global pixel
 // index, so the image does not depend on G.  RCCL is bound at run time (dlopen): libskr.so loads, and renders on one
 // GPU, on a box without it, and inside a process that already carries an RCCL (PyTorch ships one) it uses that one.
@@ -31,6 +36,7 @@
 #include "../../include/skr.h"
 
 void skr_set_error(const char *fmt, ...);
+void skr_copy_switches(skr_renderer *dst, const skr_renderer *src); // api.cpp
 
 namespace {
 
@@ -169,13 +175,27 @@ hipError_t launch_deinterleave(const uint8_t *gathered, uint8_t *frame, int32_t 
 	return hipGetLastError();
 }
 
+// What one rank's map and buffers of a frame are made for.  A frame whose key differs from the last frame's is a change of frame
+// geometry: the map is rebuilt (and, unless SKR_SHARD=interleave, the tile costs probed again) and the buffers resized.
+struct FrameKey {
+	const skr_renderer *r = nullptr;
+	int32_t width = 0, height = 0;
+	float fov = 0;
+	uint32_t tile_rows = 0, world = 0, rank = 0;
+	int32_t monte_carlo = 0, gillum = 0, depth = 0;
+	bool operator==(const FrameKey &o) const
+	{
+		return r == o.r && width == o.width && height == o.height && fov == o.fov && tile_rows == o.tile_rows && world == o.world && rank == o.rank &&
+			   monte_carlo == o.monte_carlo && gillum == o.gillum && depth == o.depth;
+	}
+	bool operator!=(const FrameKey &o) const { return !(*this == o); }
+};
+
 // The map of one frame geometry on one device: host copy, and on the device the rank's own tile list (what skr_render_tile_list
 // takes) and slot_of_tile (what the de-interleave takes).  Rebuilt when the geometry, the tree or the scene behind it changes.
 struct ShardMap {
-	const skr_renderer *r = nullptr;
-	int32_t width = 0, height = 0, monte_carlo = 0, gillum = 0, depth = 0;
-	float fov = 0;
-	uint32_t tile_rows = 0, world = 0, rank = 0, T = 0, k_max = 0;
+	FrameKey key;
+	uint32_t T = 0, k_max = 0;
 	std::vector<uint32_t> slot_of_tile;
 	uint32_t *d_tiles = nullptr;        // k_max entries: the tiles of `rank` in slot order (0xFFFFFFFF: an empty slot)
 	uint32_t *d_slot_of_tile = nullptr; // T entries
@@ -240,35 +260,23 @@ void free_map(ShardMap &m)
 }
 
 // `shared`: a map already computed for this geometry on another device of the same process (skr_multi): only uploaded here
-int ensure_map(ShardMap &m, skr_renderer *r, const skr_options *opt, uint32_t tile_rows, uint32_t world, uint32_t rank, const std::vector<uint32_t> *shared)
+int ensure_map(ShardMap &m, skr_renderer *r, const skr_options *opt, const FrameKey &key, const std::vector<uint32_t> *shared)
 {
-	const bool same = m.r == r && m.width == opt->width && m.height == opt->height && m.fov == opt->fov && m.tile_rows == tile_rows && m.world == world && m.rank == rank &&
-					  m.monte_carlo == opt->monte_carlo && m.gillum == opt->num_path_traces && m.depth == opt->max_depth && m.d_tiles;
-	if(same && !shared) return SKR_OK;
-	if(same && shared && *shared == m.slot_of_tile) return SKR_OK;
+	if(m.d_tiles && m.key == key && (!shared || *shared == m.slot_of_tile)) return SKR_OK;
 	free_map(m);
-	m.r = r;
-	m.width = opt->width;
-	m.height = opt->height;
-	m.fov = opt->fov;
-	m.monte_carlo = opt->monte_carlo;
-	m.gillum = opt->num_path_traces;
-	m.depth = opt->max_depth;
-	m.tile_rows = tile_rows;
-	m.world = world;
-	m.rank = rank;
-	m.T = tiles_total(opt->height, tile_rows);
-	m.k_max = tiles_per_rank(opt->height, tile_rows, world);
+	m.key = key;
+	m.T = tiles_total(key.height, key.tile_rows);
+	m.k_max = tiles_per_rank(key.height, key.tile_rows, key.world);
 	if(shared) m.slot_of_tile = *shared;
 	else
 	{
 		m.slot_of_tile.assign(m.T, 0);
-		const int rc = plan_map(r, opt, tile_rows, world, m.slot_of_tile.data());
+		const int rc = plan_map(r, opt, key.tile_rows, key.world, m.slot_of_tile.data());
 		if(rc != SKR_OK) return rc;
 	}
 	std::vector<uint32_t> mine(m.k_max, 0xFFFFFFFFu);
 	for(uint32_t t = 0; t < m.T; t++)
-		if(m.slot_of_tile[t] / m.k_max == rank) mine[m.slot_of_tile[t] % m.k_max] = t;
+		if(m.slot_of_tile[t] / m.k_max == key.rank) mine[m.slot_of_tile[t] % m.k_max] = t;
 	SKR_HIP(hipMalloc((void **) &m.d_tiles, (size_t) m.k_max * sizeof(uint32_t)));
 	SKR_HIP(hipMalloc((void **) &m.d_slot_of_tile, (size_t) m.T * sizeof(uint32_t)));
 	SKR_HIP(hipMemcpy(m.d_tiles, mine.data(), (size_t) m.k_max * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -278,28 +286,23 @@ int ensure_map(ShardMap &m, skr_renderer *r, const skr_options *opt, uint32_t ti
 
 // one rank's buffers for one frame geometry
 struct RankBuffers {
-	int32_t width = 0, height = 0;
-	uint32_t tile_rows = 0, world = 0, k_max = 0;
+	FrameKey key;
 	size_t chunk = 0;           // bytes one rank contributes: k_max * tile_rows * width * 3
 	uint8_t *d_gather = nullptr; // [world][chunk]; this rank renders into slot `rank`
 	uint8_t *d_frame = nullptr;  // root only: the de-interleaved frame
 };
 
-int size_buffers(RankBuffers &b, const skr_options *opt, uint32_t tile_rows, uint32_t world, bool root)
+int size_buffers(RankBuffers &b, const FrameKey &key, bool root)
 {
-	if(b.d_gather && b.width == opt->width && b.height == opt->height && b.tile_rows == tile_rows && b.world == world) return SKR_OK;
+	if(b.d_gather && b.key == key) return SKR_OK;
 	if(b.d_gather) SKR_HIP(hipFree(b.d_gather));
 	if(b.d_frame) SKR_HIP(hipFree(b.d_frame));
 	b.d_gather = b.d_frame = nullptr;
-	b.width = opt->width;
-	b.height = opt->height;
-	b.tile_rows = tile_rows;
-	b.world = world;
-	b.k_max = tiles_per_rank(opt->height, tile_rows, world);
-	b.chunk = (size_t) b.k_max * tile_rows * (size_t) opt->width * 3;
-	SKR_HIP(hipMalloc((void **) &b.d_gather, b.chunk * world));
-	SKR_HIP(hipMemset(b.d_gather, 0, b.chunk * world)); // the padding rows of a last partial tile travel too
-	if(root) SKR_HIP(hipMalloc((void **) &b.d_frame, (size_t) opt->width * opt->height * 3));
+	b.key = key;
+	b.chunk = (size_t) tiles_per_rank(key.height, key.tile_rows, key.world) * key.tile_rows * (size_t) key.width * 3;
+	SKR_HIP(hipMalloc((void **) &b.d_gather, b.chunk * key.world));
+	SKR_HIP(hipMemset(b.d_gather, 0, b.chunk * key.world)); // the padding rows of a last partial tile travel too
+	if(root) SKR_HIP(hipMalloc((void **) &b.d_frame, (size_t) key.width * key.height * 3));
 	return SKR_OK;
 }
 
@@ -320,40 +323,188 @@ int check_frame_args(const skr_options *opt, uint32_t tile_rows)
 	return SKR_OK;
 }
 
+// A rank's share of a frame is eight short dependent kernels (DESIGN.md 7): two frames in flight on two streams fill each other's ramps and
+// tails — 1/8 of the headline frame 0.258 -> 0.217 ms per frame, 1/4 0.454 -> 0.427, 1/2 0.836 -> 0.800 (tools/inflight.py); a whole frame
+// through this step, with the de-interleave behind it, 1.570 -> 1.513 ms.  So a run of frames alternates between the renderer and a clone of
+// it (a second set of tables: 1.7 GB for the headline frame); SKR_INFLIGHT=1 keeps it to one.
+bool two_in_flight()
+{
+	if(const char *e = getenv("SKR_INFLIGHT")) return atoi(e) >= 2;
+	return true;
+}
+
+constexpr int SERIAL = -1; // the buffer set of the serial frame step (the pipelined step's are 0 and 1)
+
+// Everything one device owns for the frame steps, in either shape.  Complete from creation, but for the clone: the pipelined step makes
+// it on the first odd frame of a run.
+struct Rank {
+	int device = 0, rank = 0, world = 1;
+	ncclComm_t comm = nullptr; // nullptr: a world of one without RCCL
+	skr_renderer *r = nullptr;
+	bool owns_r = false;         // skr_multi makes its renderers, skr_comm borrows the caller's
+	hipStream_t rs = nullptr;    // skr_multi: the render stream (skr_comm renders on the caller's stream) ...
+	hipEvent_t called = nullptr; // ... skr_comm: the caller's stream as it stands at a call, which the clone's frames follow
+	bool two = false;            // two_in_flight(), read at creation: buffer set 1 belongs to a clone of r on a stream of its own
+	skr_renderer *r2 = nullptr;
+	hipStream_t rs2 = nullptr;
+	// the pipelined step: frame f's collective on cs while frame f + 1 is rendered into the other buffer set
+	hipStream_t cs = nullptr;
+	hipEvent_t rendered[2] = {nullptr, nullptr}, gathered[2] = {nullptr, nullptr};
+	bool in_flight[2] = {false, false}; // a collective of set s was enqueued: gathered[s] marks its end
+	RankBuffers buf, abuf[2];            // the serial step's buffer set; the pipelined step's two
+	ShardMap map;                        // the tile -> rank map of the frame geometry last rendered
+
+	FrameKey key(const skr_options *opt, uint32_t tile_rows) const
+	{
+		return {r, opt->width, opt->height, opt->fov, tile_rows, (uint32_t) world, (uint32_t) rank, opt->monte_carlo, opt->num_path_traces, opt->max_depth};
+	}
+	RankBuffers &buffers(int set) { return set == SERIAL ? buf : abuf[set]; }
+};
+
+// the streams and events of a rank, on its device (own_stream: skr_multi's, which render on a stream of their own)
+int open_rank(Rank &k, bool own_stream)
+{
+	k.two = two_in_flight();
+	SKR_HIP(hipSetDevice(k.device));
+	if(own_stream) SKR_HIP(hipStreamCreateWithFlags(&k.rs, hipStreamNonBlocking));
+	else SKR_HIP(hipEventCreateWithFlags(&k.called, hipEventDisableTiming));
+	SKR_HIP(hipStreamCreateWithFlags(&k.cs, hipStreamNonBlocking));
+	for(int s = 0; s < 2; s++)
+	{
+		SKR_HIP(hipEventCreateWithFlags(&k.rendered[s], hipEventDisableTiming));
+		SKR_HIP(hipEventCreateWithFlags(&k.gathered[s], hipEventDisableTiming));
+	}
+	return SKR_OK;
+}
+
+void free_rank(Rank &k)
+{
+	(void) hipSetDevice(k.device);
+	for(hipStream_t s : {k.rs, k.rs2, k.cs})
+		if(s) (void) hipStreamSynchronize(s);
+	free_buffers(k.buf);
+	for(int s = 0; s < 2; s++)
+	{
+		free_buffers(k.abuf[s]);
+		if(k.rendered[s]) (void) hipEventDestroy(k.rendered[s]);
+		if(k.gathered[s]) (void) hipEventDestroy(k.gathered[s]);
+	}
+	free_map(k.map);
+	if(k.called) (void) hipEventDestroy(k.called);
+	for(hipStream_t s : {k.rs, k.rs2, k.cs})
+		if(s) (void) hipStreamDestroy(s);
+	if(k.r2) skr_renderer_destroy(k.r2);
+	if(k.comm) (void) rccl().CommDestroy(k.comm);
+	if(k.owns_r && k.r) skr_renderer_destroy(k.r);
+}
+
+// on the host, until the collective of every buffer set in flight on these ranks has ended
+int wait_in_flight(Rank *ranks, int n)
+{
+	for(int i = 0; i < n; i++)
+		for(int s = 0; s < 2; s++)
+			if(ranks[i].in_flight[s]) SKR_HIP(hipEventSynchronize(ranks[i].gathered[s]));
+	return SKR_OK;
+}
+
+// The pipelined steps' rule for a change of frame geometry: this frame resizes buffers and rebuilds the map that a collective still in
+// flight may read, so every set in flight is waited for on the host first.  Both sets stay in flight: the previous frame's buffers are
+// not the ones this frame resizes, and it is handed back as usual.
+int settle(Rank *ranks, int n, const skr_options *opt, uint32_t tile_rows)
+{
+	for(int i = 0; i < n; i++)
+		if((ranks[i].in_flight[0] || ranks[i].in_flight[1]) && ranks[i].map.key != ranks[i].key(opt, tile_rows)) return wait_in_flight(ranks, n);
+	return SKR_OK;
+}
+
+// One device's frame up to the collective, into buffer set `set` (SERIAL, or 0 / 1 of the pipelined step): the renderer and the stream,
+// the wait for the set's last collective, the buffers and the map, the render into this rank's slot of the gather buffer.  `rs`: the
+// render stream (skr_comm: the caller's).  `shared`: device 0's map, for skr_multi's other devices to upload.  `start`: an event recorded
+// just before the render (skr_multi's serial step, device 0).
+//
+// The order of a pipelined frame f on one device, set s = f mod 2:
+//   - set 1 with two frames in flight: the clone renders, on rs2; under skr_comm rs2 first waits for `called`, recorded on the caller's
+//     stream;
+//   - the render stream waits for gathered[s] if set s is in flight (the collective of frame f - 2 read these buffers);
+//   - the render, then rendered[s]; cs waits for rendered[s];
+//   - the caller then enqueues on cs the all-gather, and finish_rank the de-interleave (root only) and gathered[s].
+// The previous frame is handed back by each shape: skr_comm makes the caller's stream wait for gathered[prev], skr_multi waits for it on
+// the host.  The serial step keeps the collective and the de-interleave on the render stream, with no events.
+int render_rank(Rank &k, int set, const skr_options *opt, uint32_t tile_rows, hipStream_t rs, const std::vector<uint32_t> *shared, hipEvent_t start)
+{
+	SKR_HIP(hipSetDevice(k.device));
+	skr_renderer *rr = k.r;
+	if(set == 1 && k.two)
+	{ // (the clone and its stream are made by this device's own thread, once)
+		if(!k.r2)
+		{
+			const int rc = skr_renderer_clone(k.r, &k.r2);
+			if(rc != SKR_OK) return rc;
+			SKR_HIP(hipStreamCreateWithFlags(&k.rs2, hipStreamNonBlocking));
+		}
+		skr_copy_switches(k.r2, k.r);
+		if(k.called)
+		{
+			SKR_HIP(hipEventRecord(k.called, rs));
+			SKR_HIP(hipStreamWaitEvent(k.rs2, k.called, 0));
+		}
+		rs = k.rs2;
+		rr = k.r2;
+	}
+	if(set != SERIAL && k.in_flight[set]) SKR_HIP(hipStreamWaitEvent(rs, k.gathered[set], 0));
+	RankBuffers &b = k.buffers(set);
+	const FrameKey key = k.key(opt, tile_rows);
+	int rc = size_buffers(b, key, k.rank == 0);
+	if(rc != SKR_OK) return rc;
+	rc = ensure_map(k.map, k.r, opt, key, shared);
+	if(rc != SKR_OK) return rc;
+	if(start) SKR_HIP(hipEventRecord(start, rs));
+	rc = skr_render_tile_list(rr, opt, tile_rows, k.map.d_tiles, k.map.k_max, b.d_gather + (size_t) k.rank * b.chunk, nullptr, rs);
+	if(rc != SKR_OK) return rc;
+	if(set != SERIAL)
+	{
+		SKR_HIP(hipEventRecord(k.rendered[set], rs));
+		SKR_HIP(hipStreamWaitEvent(k.cs, k.rendered[set], 0));
+	}
+	return SKR_OK;
+}
+
+// this rank's slot of the set's gather buffer to every rank, in place (slot `rank` is the send buffer)
+ncclResult_t all_gather(Rank &k, int set, hipStream_t on)
+{
+	RankBuffers &b = k.buffers(set);
+	return rccl().AllGather(b.d_gather + (size_t) k.rank * b.chunk, b.d_gather, b.chunk, ncclUint8, k.comm, on);
+}
+
+// behind the all-gather on `on`: the root's de-interleave, then (pipelined) gathered[set], what the next user of the set waits for
+int finish_rank(Rank &k, int set, hipStream_t on)
+{
+	RankBuffers &b = k.buffers(set);
+	if(k.rank == 0) SKR_HIP(launch_deinterleave(b.d_gather, b.d_frame, b.key.width, b.key.height, b.key.tile_rows, k.map.d_slot_of_tile, on));
+	if(set != SERIAL)
+	{
+		SKR_HIP(hipEventRecord(k.gathered[set], on));
+		k.in_flight[set] = true;
+	}
+	return SKR_OK;
+}
+
+// skr_comm's collective: one all-gather per process (none in a world of one without RCCL), then finish_rank
+int comm_collect(Rank &k, int set, hipStream_t on)
+{
+	if(k.comm) SKR_NCCL(all_gather(k, set, on));
+	return finish_rank(k, set, on);
+}
+
 } // namespace
 
 // =====================================================================================================================
 // one process per device
 // =====================================================================================================================
 struct skr_comm {
-	skr_renderer *r = nullptr; // not owned
-	int device = 0, rank = 0, world = 1;
-	ncclComm_t comm = nullptr;
-	RankBuffers buf;
-	ShardMap map; // the tile -> rank map of the frame geometry last rendered
-	// pipelined frames (skr_comm_render_frame_async): two buffer sets, the collective on a stream of its own
-	RankBuffers abuf[2];
-	hipStream_t cs = nullptr;
-	hipEvent_t rendered[2] = {nullptr, nullptr}, gathered[2] = {nullptr, nullptr};
-	bool in_flight[2] = {false, false};
+	Rank k; // the renderer is the caller's
 	uint64_t async_frames = 0;
-	// two frames in flight: odd frames of a run are rendered by a clone of the renderer (its own tables) on a stream of the communicator's
-	skr_renderer *r2 = nullptr;
-	hipStream_t rs2 = nullptr;
-	hipEvent_t called = nullptr;
 };
-
-void skr_copy_switches(skr_renderer *dst, const skr_renderer *src); // api.cpp
-
-// A rank's share of a frame is eight short dependent kernels (DESIGN.md 7): two frames in flight on two streams fill each other's ramps and
-// tails — 1/8 of the headline frame 0.258 -> 0.217 ms per frame, 1/4 0.454 -> 0.427, 1/2 0.836 -> 0.800 (tools/inflight.py); a whole frame
-// through this step, with the de-interleave behind it, 1.570 -> 1.513 ms.  So a run of frames alternates between the renderer and a clone of
-// it (a second set of tables: 1.7 GB for the headline frame); SKR_INFLIGHT=1 keeps it to one.
-static bool two_in_flight()
-{
-	if(const char *e = getenv("SKR_INFLIGHT")) return atoi(e) >= 2;
-	return true;
-}
 
 extern "C" {
 
@@ -382,29 +533,35 @@ int skr_comm_create(skr_renderer *r, int device, const uint8_t id[SKR_COMM_ID_BY
 		return SKR_ERR_ARG;
 	}
 	*out = nullptr;
+	const bool with_rccl = world > 1 || id; // (a world of one still goes through RCCL when the caller hands an id: how the path is exercised on a one-GPU box)
+	if(with_rccl && !rccl().ok)
+	{
+		skr_set_error("RCCL (librccl.so.1) is not loadable in this process");
+		return SKR_ERR_UNSUPPORTED;
+	}
 	skr_comm *c = new skr_comm();
-	c->r = r;
-	c->device = device;
-	c->rank = rank;
-	c->world = world;
-	if(world > 1 || id)
-	{ // (a world of one still goes through RCCL when the caller hands an id: how the path is exercised on a one-GPU box)
-		if(!rccl().ok)
-		{
-			delete c;
-			skr_set_error("RCCL (librccl.so.1) is not loadable in this process");
-			return SKR_ERR_UNSUPPORTED;
-		}
-		hipError_t e = hipSetDevice(device);
+	Rank &k = c->k;
+	k.r = r;
+	k.device = device;
+	k.rank = rank;
+	k.world = world;
+	int rc = open_rank(k, false);
+	if(rc == SKR_OK && with_rccl)
+	{
 		ncclUniqueId u;
 		memcpy(u.internal, id, SKR_COMM_ID_BYTES);
-		ncclResult_t ne = e == hipSuccess ? rccl().CommInitRank(&c->comm, world, u, rank) : ncclUnhandledCudaError;
+		const ncclResult_t ne = rccl().CommInitRank(&k.comm, world, u, rank);
 		if(ne != ncclSuccess)
 		{
-			skr_set_error("ncclCommInitRank(rank %d of %d, device %d) failed: %s", rank, world, device, e == hipSuccess ? rccl().GetErrorString(ne) : hipGetErrorString(e));
-			delete c;
-			return SKR_ERR_HIP;
+			skr_set_error("ncclCommInitRank(rank %d of %d, device %d) failed: %s", rank, world, device, rccl().GetErrorString(ne));
+			k.comm = nullptr;
+			rc = SKR_ERR_HIP;
 		}
+	}
+	if(rc != SKR_OK)
+	{
+		skr_comm_destroy(c);
+		return rc;
 	}
 	*out = c;
 	return SKR_OK;
@@ -413,22 +570,7 @@ int skr_comm_create(skr_renderer *r, int device, const uint8_t id[SKR_COMM_ID_BY
 void skr_comm_destroy(skr_comm *c)
 {
 	if(!c) return;
-	(void) hipSetDevice(c->device);
-	if(c->cs) (void) hipStreamSynchronize(c->cs);
-	free_buffers(c->buf);
-	free_map(c->map);
-	for(int k = 0; k < 2; k++)
-	{
-		free_buffers(c->abuf[k]);
-		if(c->rendered[k]) (void) hipEventDestroy(c->rendered[k]);
-		if(c->gathered[k]) (void) hipEventDestroy(c->gathered[k]);
-	}
-	if(c->cs) (void) hipStreamDestroy(c->cs);
-	if(c->rs2) (void) hipStreamSynchronize(c->rs2);
-	if(c->r2) skr_renderer_destroy(c->r2);
-	if(c->rs2) (void) hipStreamDestroy(c->rs2);
-	if(c->called) (void) hipEventDestroy(c->called);
-	if(c->comm) (void) rccl().CommDestroy(c->comm);
+	free_rank(c->k);
 	delete c;
 }
 
@@ -439,18 +581,11 @@ int skr_comm_render_frame(skr_comm *c, const skr_options *opt, uint32_t tile_row
 	if(!c) return SKR_ERR_ARG;
 	int rc = check_frame_args(opt, tile_rows);
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(c->device));
-	rc = size_buffers(c->buf, opt, tile_rows, (uint32_t) c->world, c->rank == 0);
+	rc = render_rank(c->k, SERIAL, opt, tile_rows, (hipStream_t) stream, nullptr, nullptr);
 	if(rc != SKR_OK) return rc;
-	rc = ensure_map(c->map, c->r, opt, tile_rows, (uint32_t) c->world, (uint32_t) c->rank, nullptr);
+	rc = comm_collect(c->k, SERIAL, (hipStream_t) stream);
 	if(rc != SKR_OK) return rc;
-	RankBuffers &b = c->buf;
-	uint8_t *mine = b.d_gather + (size_t) c->rank * b.chunk;
-	rc = skr_render_tile_list(c->r, opt, tile_rows, c->map.d_tiles, c->map.k_max, mine, nullptr, stream);
-	if(rc != SKR_OK) return rc;
-	if(c->comm) SKR_NCCL(rccl().AllGather(mine, b.d_gather, b.chunk, ncclUint8, c->comm, (hipStream_t) stream)); // in place: slot `rank` is the send buffer
-	if(c->rank == 0) SKR_HIP(launch_deinterleave(b.d_gather, b.d_frame, opt->width, opt->height, tile_rows, c->map.d_slot_of_tile, (hipStream_t) stream));
-	if(d_frame) *d_frame = c->rank == 0 ? b.d_frame : nullptr;
+	if(d_frame) *d_frame = c->k.rank == 0 ? c->k.buf.d_frame : nullptr;
 	return SKR_OK;
 }
 
@@ -464,65 +599,22 @@ int skr_comm_render_frame_async(skr_comm *c, const skr_options *opt, uint32_t ti
 	if(!c) return SKR_ERR_ARG;
 	int rc = check_frame_args(opt, tile_rows);
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(c->device));
-	if(!c->cs)
-	{
-		SKR_HIP(hipStreamCreateWithFlags(&c->cs, hipStreamNonBlocking));
-		for(int k = 0; k < 2; k++)
-		{
-			SKR_HIP(hipEventCreateWithFlags(&c->rendered[k], hipEventDisableTiming));
-			SKR_HIP(hipEventCreateWithFlags(&c->gathered[k], hipEventDisableTiming));
-		}
-	}
+	Rank &k = c->k;
 	const int s = (int) (c->async_frames & 1u), prev = s ^ 1;
-	hipStream_t rs = (hipStream_t) stream; // the stream this frame is rendered on
-	skr_renderer *rr = c->r;
-	if(s == 1 && two_in_flight())
-	{ // odd frames: the clone, on the communicator's second render stream, behind whatever the caller's stream holds at this call
-		if(!c->r2)
-		{
-			rc = skr_renderer_clone(c->r, &c->r2);
-			if(rc != SKR_OK) return rc;
-			SKR_HIP(hipStreamCreateWithFlags(&c->rs2, hipStreamNonBlocking));
-			SKR_HIP(hipEventCreateWithFlags(&c->called, hipEventDisableTiming));
-		}
-		skr_copy_switches(c->r2, c->r);
-		SKR_HIP(hipEventRecord(c->called, (hipStream_t) stream));
-		SKR_HIP(hipStreamWaitEvent(c->rs2, c->called, 0));
-		rs = c->rs2;
-		rr = c->r2;
-	}
-	RankBuffers &b = c->abuf[s];
-	if(c->in_flight[s])
-	{ // the collective of frame f - 2 read these buffers (a change of geometry frees them: wait on the host then)
-		if(b.d_gather && (b.width != opt->width || b.height != opt->height || b.tile_rows != tile_rows)) SKR_HIP(hipEventSynchronize(c->gathered[s]));
-		else SKR_HIP(hipStreamWaitEvent(rs, c->gathered[s], 0));
-		c->in_flight[s] = false;
-	}
-	rc = size_buffers(b, opt, tile_rows, (uint32_t) c->world, c->rank == 0);
+	rc = settle(&k, 1, opt, tile_rows);
 	if(rc != SKR_OK) return rc;
-	if(c->map.d_tiles && (c->map.width != opt->width || c->map.height != opt->height || c->map.tile_rows != tile_rows || c->map.fov != opt->fov ||
-						  c->map.gillum != opt->num_path_traces || c->map.depth != opt->max_depth || c->map.monte_carlo != opt->monte_carlo))
-		SKR_HIP(hipStreamSynchronize(c->cs)); // (a de-interleave in flight still reads the old map)
-	rc = ensure_map(c->map, c->r, opt, tile_rows, (uint32_t) c->world, (uint32_t) c->rank, nullptr);
+	rc = render_rank(k, s, opt, tile_rows, (hipStream_t) stream, nullptr, nullptr);
 	if(rc != SKR_OK) return rc;
-	uint8_t *mine = b.d_gather + (size_t) c->rank * b.chunk;
-	rc = skr_render_tile_list(rr, opt, tile_rows, c->map.d_tiles, c->map.k_max, mine, nullptr, rs);
+	rc = comm_collect(k, s, k.cs);
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipEventRecord(c->rendered[s], rs));
-	SKR_HIP(hipStreamWaitEvent(c->cs, c->rendered[s], 0));
-	if(c->comm) SKR_NCCL(rccl().AllGather(mine, b.d_gather, b.chunk, ncclUint8, c->comm, c->cs));
-	if(c->rank == 0) SKR_HIP(launch_deinterleave(b.d_gather, b.d_frame, opt->width, opt->height, tile_rows, c->map.d_slot_of_tile, c->cs));
-	SKR_HIP(hipEventRecord(c->gathered[s], c->cs));
-	c->in_flight[s] = true;
 	c->async_frames++;
 	if(d_prev_frame)
 	{ // the previous frame: whatever `stream` does from here on sees it whole (a caller that passes NULL does not look, and saves the wait)
 		*d_prev_frame = nullptr;
-		if(c->in_flight[prev])
+		if(k.in_flight[prev])
 		{
-			SKR_HIP(hipStreamWaitEvent((hipStream_t) stream, c->gathered[prev], 0));
-			if(c->rank == 0) *d_prev_frame = c->abuf[prev].d_frame;
+			SKR_HIP(hipStreamWaitEvent((hipStream_t) stream, k.gathered[prev], 0));
+			if(k.rank == 0) *d_prev_frame = k.abuf[prev].d_frame;
 		}
 	}
 	return SKR_OK;
@@ -534,25 +626,26 @@ int skr_comm_flush(skr_comm *c, uint8_t **d_frame, void *stream)
 	if(!c) return SKR_ERR_ARG;
 	if(d_frame) *d_frame = nullptr;
 	if(c->async_frames == 0) return SKR_OK;
-	SKR_HIP(hipSetDevice(c->device));
-	const int last = (int) ((c->async_frames - 1) & 1u);
-	for(int k = 0; k < 2; k++)
-		if(c->in_flight[k]) SKR_HIP(hipStreamWaitEvent((hipStream_t) stream, c->gathered[k], 0));
-	if(d_frame && c->rank == 0) *d_frame = c->abuf[last].d_frame;
+	Rank &k = c->k;
+	SKR_HIP(hipSetDevice(k.device));
+	for(int s = 0; s < 2; s++)
+		if(k.in_flight[s]) SKR_HIP(hipStreamWaitEvent((hipStream_t) stream, k.gathered[s], 0));
+	if(d_frame && k.rank == 0) *d_frame = k.abuf[(c->async_frames - 1) & 1u].d_frame;
 	return SKR_OK;
 }
 
 // Rank 0: waits for `stream` and copies the frame of the last skr_comm_render_frame to host memory (W*H*3 bytes).
 int skr_comm_frame_to_host(skr_comm *c, uint8_t *h_rgb, void *stream)
 {
-	if(!c || !h_rgb || c->rank != 0 || !c->buf.d_frame)
+	if(!c || !h_rgb || c->k.rank != 0 || !c->k.buf.d_frame)
 	{
 		skr_set_error("skr_comm_frame_to_host: rank 0 only, after skr_comm_render_frame");
 		return SKR_ERR_ARG;
 	}
-	SKR_HIP(hipSetDevice(c->device));
+	const RankBuffers &b = c->k.buf;
+	SKR_HIP(hipSetDevice(c->k.device));
 	SKR_HIP(hipStreamSynchronize((hipStream_t) stream));
-	SKR_HIP(hipMemcpy(h_rgb, c->buf.d_frame, (size_t) c->buf.width * c->buf.height * 3, hipMemcpyDeviceToHost));
+	SKR_HIP(hipMemcpy(h_rgb, b.d_frame, (size_t) b.key.width * b.key.height * 3, hipMemcpyDeviceToHost));
 	return SKR_OK;
 }
 
@@ -563,21 +656,8 @@ int skr_comm_frame_to_host(skr_comm *c, uint8_t *h_rgb, void *stream)
 // =====================================================================================================================
 struct skr_multi {
 	int n = 0;
-	std::vector<int> devices;
-	std::vector<skr_renderer *> renderers;
-	std::vector<hipStream_t> streams;
-	std::vector<ncclComm_t> comms;
-	std::vector<RankBuffers> bufs;
-	std::vector<ShardMap> maps; // the tile -> rank map, computed on device 0 and uploaded to every device
-	// pipelined frames (skr_multi_render_frame_async): two buffer sets per device, the collective on a stream of its own per device
-	std::vector<RankBuffers> abufs[2];
-	std::vector<hipStream_t> cstreams;
-	std::vector<hipEvent_t> rendered[2], gathered[2];
-	bool in_flight[2] = {false, false};
+	std::vector<Rank> ranks; // device 0's map is computed there and uploaded to every other device
 	uint64_t async_frames = 0;
-	int async_set = -1; // >= 0: the workers render into abufs[async_set] (and order themselves behind its last collective)
-	std::vector<skr_renderer *> renderers2; // two frames in flight (two_in_flight above): the odd frames of a run on a clone per device ...
-	std::vector<hipStream_t> streams2;      // ... and a second stream
 	hipEvent_t e0 = nullptr, e1 = nullptr; // root stream: frame time
 	// one worker thread per device (a single thread would enqueue 8 devices' launch sequences one after the other)
 	std::vector<std::thread> workers;
@@ -586,8 +666,11 @@ struct skr_multi {
 	uint64_t generation = 0;
 	int pending = 0;
 	bool quit = false;
-	const skr_options *opt = nullptr;
-	uint32_t tile_rows = 0;
+	struct Job {
+		const skr_options *opt;
+		uint32_t tile_rows;
+		int set; // the buffer set every device renders into
+	} job = {nullptr, 0, SERIAL}; // what the workers are woken with
 	std::vector<int> status;
 	std::vector<std::string> errors;
 };
@@ -595,56 +678,27 @@ struct skr_multi {
 namespace {
 
 // what one device does for a frame: its tiles into its slot of its gather buffer (the collective follows, grouped, from the caller)
-int multi_render_rank(skr_multi *m, int i)
+int multi_render_rank(skr_multi *m, int i, const skr_multi::Job &job)
 {
-	SKR_HIP(hipSetDevice(m->devices[i]));
-	const int set = m->async_set;
-	RankBuffers &b = set >= 0 ? m->abufs[set][i] : m->bufs[i];
-	int rc = SKR_OK;
-	skr_renderer *rr = m->renderers[i];
-	hipStream_t rs = m->streams[i];
-	if(set == 1 && two_in_flight())
-	{ // buffer set 1 always belongs to the clone and its stream (made by this device's own thread, once)
-		if(!m->renderers2[i])
-		{
-			rc = skr_renderer_clone(m->renderers[i], &m->renderers2[i]);
-			if(rc != SKR_OK) return rc;
-			SKR_HIP(hipStreamCreateWithFlags(&m->streams2[i], hipStreamNonBlocking));
-		}
-		skr_copy_switches(m->renderers2[i], m->renderers[i]);
-		rr = m->renderers2[i];
-		rs = m->streams2[i];
-	}
-	if(set >= 0 && m->in_flight[set]) SKR_HIP(hipStreamWaitEvent(rs, m->gathered[set][i], 0)); // the collective of frame f - 2 read these buffers
-	rc = size_buffers(b, m->opt, m->tile_rows, (uint32_t) m->n, i == 0);
-	if(rc != SKR_OK) return rc;
-	if(i != 0)
-	{ // (device 0's map was made by the caller before the workers were woken: here it is only uploaded)
-		rc = ensure_map(m->maps[i], m->renderers[i], m->opt, m->tile_rows, (uint32_t) m->n, (uint32_t) i, &m->maps[0].slot_of_tile);
-		if(rc != SKR_OK) return rc;
-	}
-	if(i == 0 && set < 0) SKR_HIP(hipEventRecord(m->e0, m->streams[0]));
-	rc = skr_render_tile_list(rr, m->opt, m->tile_rows, m->maps[i].d_tiles, m->maps[i].k_max, b.d_gather + (size_t) i * b.chunk, nullptr, rs);
-	if(rc != SKR_OK) return rc;
-	if(set >= 0) SKR_HIP(hipEventRecord(m->rendered[set][i], rs));
-	return SKR_OK;
+	Rank &k = m->ranks[i];
+	return render_rank(k, job.set, job.opt, job.tile_rows, k.rs, i != 0 ? &m->ranks[0].map.slot_of_tile : nullptr, i == 0 && job.set == SERIAL ? m->e0 : nullptr);
 }
 
 // every device renders its tiles of one frame (the calling thread drives device 0, the workers the others); returns when all are enqueued
-int multi_render_all(skr_multi *m, const skr_options *opt, uint32_t tile_rows)
+int multi_render_all(skr_multi *m, const skr_options *opt, uint32_t tile_rows, int set)
 {
-	SKR_HIP(hipSetDevice(m->devices[0]));
-	int rc = ensure_map(m->maps[0], m->renderers[0], opt, tile_rows, (uint32_t) m->n, 0u, nullptr);
+	Rank &k0 = m->ranks[0];
+	SKR_HIP(hipSetDevice(k0.device));
+	int rc = ensure_map(k0.map, k0.r, opt, k0.key(opt, tile_rows), nullptr); // (before the workers upload it)
 	if(rc != SKR_OK) return rc;
 	{
 		std::lock_guard<std::mutex> lk(m->mu);
-		m->opt = opt;
-		m->tile_rows = tile_rows;
+		m->job = {opt, tile_rows, set};
 		m->pending = m->n - 1;
 		m->generation++;
 	}
 	m->cv_go.notify_all();
-	m->status[0] = multi_render_rank(m, 0);
+	m->status[0] = multi_render_rank(m, 0, m->job);
 	if(m->status[0] != SKR_OK) m->errors[0] = skr_last_error();
 	{
 		std::unique_lock<std::mutex> lk(m->mu);
@@ -653,33 +707,38 @@ int multi_render_all(skr_multi *m, const skr_options *opt, uint32_t tile_rows)
 	for(int i = 0; i < m->n; i++)
 		if(m->status[i] != SKR_OK)
 		{
-			skr_set_error("device %d: %s", m->devices[i], m->errors[i].c_str());
+			skr_set_error("device %d: %s", m->ranks[i].device, m->errors[i].c_str());
 			return m->status[i];
 		}
 	return SKR_OK;
 }
 
-// one grouped all-gather of every device's chunk, each on the stream given for its device, then the root's de-interleave
-int multi_collect(skr_multi *m, std::vector<RankBuffers> &bufs, const std::vector<hipStream_t> &on, const skr_options *opt, uint32_t tile_rows)
+// one grouped all-gather of every device's chunk, each on its device's collective stream (the render stream in the serial step), then
+// the rest of the frame on every device
+int multi_collect(skr_multi *m, int set)
 {
-	if(m->comms[0])
+	auto on = [set](const Rank &k) { return set == SERIAL ? k.rs : k.cs; };
+	if(m->ranks[0].comm)
 	{
 		SKR_NCCL(rccl().GroupStart());
-		for(int i = 0; i < m->n; i++)
+		for(Rank &k : m->ranks)
 		{
-			RankBuffers &b = bufs[i];
-			const ncclResult_t ne = rccl().AllGather(b.d_gather + (size_t) i * b.chunk, b.d_gather, b.chunk, ncclUint8, m->comms[i], on[i]);
+			const ncclResult_t ne = all_gather(k, set, on(k));
 			if(ne != ncclSuccess)
 			{
 				(void) rccl().GroupEnd();
-				skr_set_error("ncclAllGather(rank %d) failed: %s", i, rccl().GetErrorString(ne));
+				skr_set_error("ncclAllGather(rank %d) failed: %s", k.rank, rccl().GetErrorString(ne));
 				return SKR_ERR_HIP;
 			}
 		}
 		SKR_NCCL(rccl().GroupEnd());
 	}
-	SKR_HIP(hipSetDevice(m->devices[0]));
-	SKR_HIP(launch_deinterleave(bufs[0].d_gather, bufs[0].d_frame, opt->width, opt->height, tile_rows, m->maps[0].d_slot_of_tile, on[0]));
+	for(Rank &k : m->ranks)
+	{
+		SKR_HIP(hipSetDevice(k.device));
+		const int rc = finish_rank(k, set, on(k));
+		if(rc != SKR_OK) return rc;
+	}
 	return SKR_OK;
 }
 
@@ -688,13 +747,15 @@ void worker_main(skr_multi *m, int i)
 	uint64_t seen = 0;
 	for(;;)
 	{
+		skr_multi::Job job;
 		{
 			std::unique_lock<std::mutex> lk(m->mu);
 			m->cv_go.wait(lk, [&] { return m->quit || m->generation != seen; });
 			if(m->quit) return;
 			seen = m->generation;
+			job = m->job;
 		}
-		const int rc = multi_render_rank(m, i);
+		const int rc = multi_render_rank(m, i, job);
 		{
 			std::lock_guard<std::mutex> lk(m->mu);
 			m->status[i] = rc;
@@ -729,38 +790,34 @@ int skr_multi_create(const skr_scene *scene, int n_devices, const int *devices, 
 	}
 	skr_multi *m = new skr_multi();
 	m->n = n_devices;
-	m->devices.resize(n_devices);
-	for(int i = 0; i < n_devices; i++) m->devices[i] = devices ? devices[i] : i;
-	m->renderers.assign(n_devices, nullptr);
-	m->streams.assign(n_devices, nullptr);
-	m->renderers2.assign(n_devices, nullptr);
-	m->streams2.assign(n_devices, nullptr);
-	m->comms.assign(n_devices, nullptr);
-	m->bufs.resize(n_devices);
-	m->maps.resize(n_devices);
+	m->ranks.resize(n_devices);
 	m->status.assign(n_devices, SKR_OK);
 	m->errors.resize(n_devices);
+	std::vector<int> ids(n_devices);
 	int rc = SKR_OK;
 	for(int i = 0; i < n_devices && rc == SKR_OK; i++)
 	{ // the scene is uploaded to every device from the host: <= 0.5 MB, no collective needed
-		rc = skr_renderer_create(scene, m->devices[i], &m->renderers[i]);
-		if(rc == SKR_OK && (hipSetDevice(m->devices[i]) != hipSuccess || hipStreamCreateWithFlags(&m->streams[i], hipStreamNonBlocking) != hipSuccess))
-		{
-			skr_set_error("stream creation failed on device %d", m->devices[i]);
-			rc = SKR_ERR_HIP;
-		}
+		Rank &k = m->ranks[i];
+		k.device = ids[i] = devices ? devices[i] : i;
+		k.rank = i;
+		k.world = n_devices;
+		k.owns_r = true;
+		rc = skr_renderer_create(scene, k.device, &k.r);
+		if(rc == SKR_OK) rc = open_rank(k, true);
 	}
 	if(rc == SKR_OK && rccl().ok)
 	{ // (one device too, when RCCL is there: the same frame step, and the path that a one-GPU box can test)
-		const ncclResult_t ne = rccl().CommInitAll(m->comms.data(), n_devices, m->devices.data());
+		std::vector<ncclComm_t> comms(n_devices, nullptr);
+		const ncclResult_t ne = rccl().CommInitAll(comms.data(), n_devices, ids.data());
 		if(ne != ncclSuccess)
 		{
 			skr_set_error("ncclCommInitAll(%d devices) failed: %s", n_devices, rccl().GetErrorString(ne));
-			m->comms.assign(n_devices, nullptr);
 			rc = SKR_ERR_HIP;
 		}
+		else
+			for(int i = 0; i < n_devices; i++) m->ranks[i].comm = comms[i];
 	}
-	if(rc == SKR_OK && (hipSetDevice(m->devices[0]) != hipSuccess || hipEventCreate(&m->e0) != hipSuccess || hipEventCreate(&m->e1) != hipSuccess))
+	if(rc == SKR_OK && (hipSetDevice(ids[0]) != hipSuccess || hipEventCreate(&m->e0) != hipSuccess || hipEventCreate(&m->e1) != hipSuccess))
 	{
 		skr_set_error("event creation failed");
 		rc = SKR_ERR_HIP;
@@ -784,27 +841,7 @@ void skr_multi_destroy(skr_multi *m)
 	}
 	m->cv_go.notify_all();
 	for(std::thread &t : m->workers) t.join();
-	for(int i = 0; i < m->n; i++)
-	{
-		(void) hipSetDevice(m->devices[i]);
-		if(m->streams[i]) (void) hipStreamSynchronize(m->streams[i]);
-		if(i < (int) m->cstreams.size() && m->cstreams[i]) (void) hipStreamSynchronize(m->cstreams[i]);
-		free_buffers(m->bufs[i]);
-		if(i < (int) m->maps.size()) free_map(m->maps[i]);
-		for(int k = 0; k < 2; k++)
-		{
-			if(i < (int) m->abufs[k].size()) free_buffers(m->abufs[k][i]);
-			if(i < (int) m->rendered[k].size() && m->rendered[k][i]) (void) hipEventDestroy(m->rendered[k][i]);
-			if(i < (int) m->gathered[k].size() && m->gathered[k][i]) (void) hipEventDestroy(m->gathered[k][i]);
-		}
-		if(i < (int) m->cstreams.size() && m->cstreams[i]) (void) hipStreamDestroy(m->cstreams[i]);
-		if(m->comms[i]) (void) rccl().CommDestroy(m->comms[i]);
-		if(i < (int) m->streams2.size() && m->streams2[i]) (void) hipStreamSynchronize(m->streams2[i]);
-		if(i < (int) m->renderers2.size() && m->renderers2[i]) skr_renderer_destroy(m->renderers2[i]);
-		if(i < (int) m->streams2.size() && m->streams2[i]) (void) hipStreamDestroy(m->streams2[i]);
-		if(m->streams[i]) (void) hipStreamDestroy(m->streams[i]);
-		if(m->renderers[i]) skr_renderer_destroy(m->renderers[i]);
-	}
+	for(Rank &k : m->ranks) free_rank(k);
 	if(m->e0) (void) hipEventDestroy(m->e0);
 	if(m->e1) (void) hipEventDestroy(m->e1);
 	delete m;
@@ -812,7 +849,7 @@ void skr_multi_destroy(skr_multi *m)
 
 int skr_multi_device_count(const skr_multi *m) { return m ? m->n : 0; }
 
-skr_renderer *skr_multi_renderer(skr_multi *m, int i) { return (m && i >= 0 && i < m->n) ? m->renderers[i] : nullptr; }
+skr_renderer *skr_multi_renderer(skr_multi *m, int i) { return (m && i >= 0 && i < m->n) ? m->ranks[i].r : nullptr; }
 
 // The whole frame: every device its tiles, one grouped all-gather, the root's de-interleave; synchronous.  *d_frame is the
 // W x H x 3 frame in device 0's memory (owned by m, valid until the next call); frame_ms = first launch to de-interleaved
@@ -822,19 +859,20 @@ int skr_multi_render_frame(skr_multi *m, const skr_options *opt, uint32_t tile_r
 	if(!m) return SKR_ERR_ARG;
 	int rc = check_frame_args(opt, tile_rows);
 	if(rc != SKR_OK) return rc;
-	m->async_set = -1;
-	rc = multi_render_all(m, opt, tile_rows);
+	rc = multi_render_all(m, opt, tile_rows, SERIAL);
 	if(rc != SKR_OK) return rc;
-	rc = multi_collect(m, m->bufs, m->streams, opt, tile_rows); // every rank's chunk to every rank (the root is the one that uses it), each on its rank's stream behind its kernels
+	rc = multi_collect(m, SERIAL); // every rank's chunk to every rank (the root is the one that uses it), each on its rank's stream behind its kernels
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipEventRecord(m->e1, m->streams[0]));
+	const Rank &k0 = m->ranks[0];
+	SKR_HIP(hipSetDevice(k0.device));
+	SKR_HIP(hipEventRecord(m->e1, k0.rs));
 	for(int i = m->n - 1; i >= 0; i--)
 	{
-		SKR_HIP(hipSetDevice(m->devices[i]));
-		SKR_HIP(hipStreamSynchronize(m->streams[i]));
+		SKR_HIP(hipSetDevice(m->ranks[i].device));
+		SKR_HIP(hipStreamSynchronize(m->ranks[i].rs));
 	}
 	if(frame_ms) SKR_HIP(hipEventElapsedTime(frame_ms, m->e0, m->e1));
-	if(d_frame) *d_frame = m->bufs[0].d_frame;
+	if(d_frame) *d_frame = k0.buf.d_frame;
 	return SKR_OK;
 }
 
@@ -847,64 +885,22 @@ int skr_multi_render_frame_async(skr_multi *m, const skr_options *opt, uint32_t 
 	if(!m) return SKR_ERR_ARG;
 	int rc = check_frame_args(opt, tile_rows);
 	if(rc != SKR_OK) return rc;
-	if(m->cstreams.empty())
-	{
-		m->cstreams.assign(m->n, nullptr);
-		for(int k = 0; k < 2; k++)
-		{
-			m->abufs[k].resize(m->n);
-			m->rendered[k].assign(m->n, nullptr);
-			m->gathered[k].assign(m->n, nullptr);
-		}
-		for(int i = 0; i < m->n; i++)
-		{
-			SKR_HIP(hipSetDevice(m->devices[i]));
-			SKR_HIP(hipStreamCreateWithFlags(&m->cstreams[i], hipStreamNonBlocking));
-			for(int k = 0; k < 2; k++)
-			{
-				SKR_HIP(hipEventCreateWithFlags(&m->rendered[k][i], hipEventDisableTiming));
-				SKR_HIP(hipEventCreateWithFlags(&m->gathered[k][i], hipEventDisableTiming));
-			}
-		}
-	}
 	const int s = (int) (m->async_frames & 1u), prev = s ^ 1;
-	if(m->in_flight[s])
-	{ // a change of geometry frees the buffers and the map the collective of frame f - 2 may still read: wait for it on the host then
-		const RankBuffers &b = m->abufs[s][0];
-		const ShardMap &mp = m->maps[0];
-		if(b.width != opt->width || b.height != opt->height || b.tile_rows != tile_rows || mp.fov != opt->fov || mp.gillum != opt->num_path_traces ||
-		   mp.depth != opt->max_depth || mp.monte_carlo != opt->monte_carlo)
-		{
-			for(int k = 0; k < 2; k++)
-				for(int i = 0; i < m->n && m->in_flight[k]; i++) SKR_HIP(hipEventSynchronize(m->gathered[k][i]));
-			m->in_flight[prev] = false; // (its frame is handed back below only if still in flight: it is gone with the old geometry)
-		}
-	}
-	m->async_set = s;
-	rc = multi_render_all(m, opt, tile_rows);
-	m->async_set = -1;
+	rc = settle(m->ranks.data(), m->n, opt, tile_rows);
 	if(rc != SKR_OK) return rc;
-	for(int i = 0; i < m->n; i++)
-	{
-		SKR_HIP(hipSetDevice(m->devices[i]));
-		SKR_HIP(hipStreamWaitEvent(m->cstreams[i], m->rendered[s][i], 0));
-	}
-	rc = multi_collect(m, m->abufs[s], m->cstreams, opt, tile_rows);
+	rc = multi_render_all(m, opt, tile_rows, s);
 	if(rc != SKR_OK) return rc;
-	for(int i = 0; i < m->n; i++)
-	{
-		SKR_HIP(hipSetDevice(m->devices[i]));
-		SKR_HIP(hipEventRecord(m->gathered[s][i], m->cstreams[i]));
-	}
-	m->in_flight[s] = true;
+	rc = multi_collect(m, s);
+	if(rc != SKR_OK) return rc;
 	m->async_frames++;
 	if(d_prev_frame)
 	{
+		const Rank &k0 = m->ranks[0];
 		*d_prev_frame = nullptr;
-		if(m->in_flight[prev])
+		if(k0.in_flight[prev])
 		{
-			SKR_HIP(hipEventSynchronize(m->gathered[prev][0]));
-			*d_prev_frame = m->abufs[prev][0].d_frame;
+			SKR_HIP(hipEventSynchronize(k0.gathered[prev]));
+			*d_prev_frame = k0.abuf[prev].d_frame;
 		}
 	}
 	return SKR_OK;
@@ -916,9 +912,9 @@ int skr_multi_flush(skr_multi *m, uint8_t **d_frame)
 	if(!m) return SKR_ERR_ARG;
 	if(d_frame) *d_frame = nullptr;
 	if(m->async_frames == 0) return SKR_OK;
-	for(int k = 0; k < 2; k++)
-		for(int i = 0; i < m->n && m->in_flight[k]; i++) SKR_HIP(hipEventSynchronize(m->gathered[k][i]));
-	if(d_frame) *d_frame = m->abufs[(m->async_frames - 1) & 1u][0].d_frame;
+	const int rc = wait_in_flight(m->ranks.data(), m->n);
+	if(rc != SKR_OK) return rc;
+	if(d_frame) *d_frame = m->ranks[0].abuf[(m->async_frames - 1) & 1u].d_frame;
 	return SKR_OK;
 }
 

@@ -779,7 +779,7 @@ def test_a_clone_renders_the_same_frames_on_its_own_stream(gpu):
     assert gpu.equal(again, want_a)  # (the source outlives its clone)
 
 
-def test_native_frame_step_on_one_gpu(gpu, tmp_path):
+def test_native_frame_step_on_one_gpu(gpu, tmp_path, monkeypatch):
     """The multi-GPU frame step that lives inside libskr (include/skr.h "multi-GPU": tiles into the gather buffer, ONE
     ncclAllGather, de-interleave kernel), as far as a one-GPU box can run it: a world of one with a real RCCL communicator
     (skr_comm_*: what bench.py uses under torchrun), the single-process form on one device (skr_multi_*: what
@@ -805,25 +805,36 @@ def test_native_frame_step_on_one_gpu(gpu, tmp_path):
     got, ms = m.render_frame_host(opt, 8)
     assert np.array_equal(got, want) and ms > 0
     assert m.counters()["radiance_rays"] > 0
-    # the pipelined form: three frames under three seeds, each handed back one call late (the last by skr_multi_flush)
+    m.close()
+    # the pipelined form: six frames under six seeds, with a change of geometry in between, each handed back one call late (the last by
+    # skr_multi_flush) — the frame just before the change too; with one and with two frames in flight (a clone per device)
     import ctypes as C
     hip = C.CDLL("libamdhip64.so")
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
 
-    def fetch(addr):
-        out = np.zeros((h, w, 3), np.uint8)
+    def fetch(addr, fw, fh):
+        out = np.zeros((fh, fw, 3), np.uint8)
         assert hip.hipMemcpy(out.ctypes.data, addr, out.nbytes, 2) == 0  # hipMemcpyDeviceToHost
         return out
-    seeds = (5, 6, 7)
-    wants = [r.render(skr.Options(w, h, gillum=4, jsample=2, shadow=True, seed=sd))[0].cpu().numpy() for sd in seeds]
-    back = []
-    for sd in seeds:
-        prev = m.render_frame_async(skr.Options(w, h, gillum=4, jsample=2, shadow=True, seed=sd), 8)
-        if prev:
-            back.append(fetch(prev))
-    back.append(fetch(m.flush()))
-    assert len(back) == 3 and all(np.array_equal(a, b) for a, b in zip(back, wants))
-    m.close()
+    shapes = [(w, h, 8)] * 3 + [(200, 113, 16)] * 3
+    opts = [skr.Options(fw, fh, gillum=4, jsample=2, shadow=True, seed=5 + k) for k, (fw, fh, _) in enumerate(shapes)]
+    wants = [r.render(o)[0].cpu().numpy() for o in opts]
+    for inflight in ("1", "2"):
+        monkeypatch.setenv("SKR_INFLIGHT", inflight)
+        m = binding.Multi(renderer("spheres2.scn").scene, 1)
+        back = []
+        for k, (o, (_, _, tile_rows)) in enumerate(zip(opts, shapes)):
+            prev = m.render_frame_async(o, tile_rows)
+            if k == 0:
+                assert not prev
+            else:
+                assert prev, (inflight, k)
+                back.append(fetch(prev, *shapes[k - 1][:2]))
+        back.append(fetch(m.flush(), *shapes[-1][:2]))
+        assert len(back) == 6
+        for k in range(6):
+            assert np.array_equal(back[k], wants[k]), (inflight, k)
+        m.close()
     exe = os.path.join(ROOT, "bin", "raytracer")
     args = ["--path", scene_path("spheres2.scn"), "--width", str(w), "--height", str(h), "--gillum", "4", "--jsample", "2", "--shadow", "--seed", "5", "--quiet"]
     a, b = str(tmp_path / "one.ppm"), str(tmp_path / "sharded.ppm")
