@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "device_math.h"
+#include "launch.h"
 
 // acc = frame (first pass) or acc + frame, element by element
 __global__ __launch_bounds__(256) void skr_accumulate_kernel(float *__restrict__ acc, const float *__restrict__ frame, size_t n, int first)

@@ -9,22 +9,8 @@
 #include <cstring>
 #include <vector>
 
-#include "render_params.h"
+#include "launch.h"
 #include "scene_host.h"
-
-hipError_t skr_launch_render(const RenderParams &p, hipStream_t stream, const char **variant, const SkrTimingHook *hook);
-hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream);
-// accumulate.hip
-hipError_t skr_launch_accumulate(float *acc, const float *frame, size_t n, int first, hipStream_t stream);
-hipError_t skr_launch_resolve_accumulated(const float *acc, uint32_t passes, uint32_t width, uint32_t out_rows, uint32_t height, uint32_t tile_rows,
-										  uint32_t first_tile, uint32_t tile_stride, const uint32_t *tile_table, uint8_t *rgb, float *rgbf, hipStream_t stream);
-size_t skr_render_lds_bytes(const RenderParams &p);
-bool skr_nodes_selected(const RenderParams &p);
-size_t skr_nodes_scratch_bytes(const RenderParams &p);
-bool skr_generic_selected(const RenderParams &p);   // render_kernel.hip
-bool skr_generic_supported(const RenderParams &p);  // render_generic.hip
-size_t skr_generic_scratch_bytes(const RenderParams &p);
-bool skr_nodes_counter_layout(const RenderParams &p, size_t *off_ctr, size_t *level_words, int *levels);
 
 static thread_local const char *g_variant = "none";
 
@@ -57,7 +43,7 @@ struct skr_renderer {
 	int lds_limit = 0;
 	int pow_steps = 11; // bit length of the largest integer phong exponent in [1, 1024] among the scene's materials (device_math.h powf_spec)
 	// scratch, grown on demand and kept
-	void *d_nodes = nullptr;  // node pipeline: every table of one band (render_nodes.hip NodePlan)
+	void *d_nodes = nullptr;  // level pipelines: every table of one band (launch.h NodePlan, GPlan)
 	size_t nodes_cap = 0;
 	float *d_acc = nullptr;
 	size_t acc_cap = 0;
@@ -68,8 +54,8 @@ struct skr_renderer {
 	hipEvent_t frame_e0 = nullptr, frame_e1 = nullptr;
 	// skr_renderer_kernel_ms: event pairs around the dominant kernel of recent launches
 	SkrSwitches sw; // the SKR_* development switches, read once (load_switches)
-	RenderParams last_p{}; // the launch last enqueued (skr_renderer_last_*_count)
-	bool last_nodes = false;
+	size_t last_off_ctr = 0; // the node-pipeline counters of the launch last enqueued (skr_renderer_last_*_count): where in d_nodes ...
+	int last_levels = 0;     // ... and how many levels they count (0: the launch took another path)
 	bool timing = false;
 	bool count_tri = false; // skr_renderer_count_triangle_work
 	std::vector<SkrTimingHook> timed;
@@ -86,8 +72,6 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_LEVELS_BUDGET_MB")) sw.budget_mb = atoi(e) > 0 ? atoi(e) : 1;
 	if(const char *e = getenv("SKR_FLAT")) sw.flat = atoi(e) > 0 ? 1 : -1;
 }
-
-hipError_t skr_launch_camec(const float4 *geom, int ns, f3 cam_pos, float4 *out, hipStream_t stream); // render_wave.hip
 
 // (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
 void skr_copy_switches(skr_renderer *dst, const skr_renderer *src) { dst->sw = src->sw; }
@@ -384,7 +368,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	if(p.max_depth > 1)
 	{ // tree node ids are 32-bit RNG counter words: need N^(depth-1) < 2^32
 		double nodes = 1;
-		const double arity = (double) (p.monte_carlo ? p.num_path_traces : 0) + (p.legacy_reflect ? 2.0 * p.n_lights : 0.0); // children per node
+		const double arity = skr_tree_arity(p);
 		for(int k = 1; k < p.max_depth && nodes < 4294967296.0; k++) nodes = nodes * arity + 1;
 		if(nodes >= 4294967296.0)
 		{
@@ -392,7 +376,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 			return SKR_ERR_UNSUPPORTED;
 		}
 	}
-	// --scn-fog: a scene with fog volumes renders on the general level pipeline (render_kernel.hip skr_generic_selected)
+	// --scn-fog: a scene with fog volumes renders on the general level pipeline (render_kernel.hip skr_plan_launch)
 	p.n_fog = r->n_fog;
 	p.fog_row = (uint32_t) r->off_fog;
 	if(p.n_fog > 0 && (opt->legacy_reflect || opt->shade_triangles))
@@ -407,42 +391,33 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.counters = r->d_counters;
 	p.tri_work = r->count_tri ? r->d_tri_work : nullptr;
 	p.qctr = reinterpret_cast<uint32_t *>(r->d_counters + (size_t) SKR_COUNTER_SHARDS * 4 + 8);
-	const bool generic_path = skr_generic_selected(p);
-	const bool nodes_path = !generic_path && skr_nodes_selected(p);
-	if(generic_path && !skr_generic_supported(p))
+	LaunchPlan lp;
+	if(!skr_plan_launch(p, lp))
 	{
 		skr_set_error("--depth %d with %d children per node: the tables of one output row exceed the scratch budget (SKR_LEVELS_BUDGET_MB)", p.max_depth, p.num_path_traces + (p.legacy_reflect ? 2 * p.n_lights : 0));
 		return SKR_ERR_UNSUPPORTED;
 	}
-	if(nodes_path || generic_path)
+	if(lp.scratch_bytes > r->nodes_cap)
 	{
-		const size_t need = nodes_path ? skr_nodes_scratch_bytes(p) : skr_generic_scratch_bytes(p);
-		if(need > r->nodes_cap)
-		{
-			if(r->d_nodes) SKR_HIP(hipFree(r->d_nodes));
-			r->d_nodes = nullptr;
-			r->nodes_cap = 0;
-			SKR_HIP(hipMalloc(&r->d_nodes, need));
-			r->nodes_cap = need;
-		}
-		p.node_scratch = r->d_nodes;
-		if(p.grid_size > 0)
-		{
-			const size_t need_acc = (size_t) p.width * p.out_rows * 12;
-			if(need_acc > r->acc_cap)
-			{
-				if(r->d_acc) SKR_HIP(hipFree(r->d_acc));
-				r->d_acc = nullptr;
-				r->acc_cap = 0;
-				SKR_HIP(hipMalloc((void **) &r->d_acc, need_acc));
-				r->acc_cap = need_acc;
-			}
-			p.acc = r->d_acc;
-		}
+		if(r->d_nodes) SKR_HIP(hipFree(r->d_nodes));
+		r->d_nodes = nullptr;
+		r->nodes_cap = 0;
+		SKR_HIP(hipMalloc(&r->d_nodes, lp.scratch_bytes));
+		r->nodes_cap = lp.scratch_bytes;
 	}
-	if(skr_render_lds_bytes(p) > (size_t) r->lds_limit)
+	if(lp.path != SKR_PATH_DIRECT) p.node_scratch = r->d_nodes;
+	if(lp.acc_bytes > r->acc_cap)
 	{
-		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", skr_render_lds_bytes(p),
+		if(r->d_acc) SKR_HIP(hipFree(r->d_acc));
+		r->d_acc = nullptr;
+		r->acc_cap = 0;
+		SKR_HIP(hipMalloc((void **) &r->d_acc, lp.acc_bytes));
+		r->acc_cap = lp.acc_bytes;
+	}
+	if(lp.acc_bytes) p.acc = r->d_acc;
+	if(lp.lds_bytes > (size_t) r->lds_limit)
+	{
+		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", lp.lds_bytes,
 					  p.n_spheres, p.n_lights, r->lds_limit);
 		return SKR_ERR_UNSUPPORTED;
 	}
@@ -467,9 +442,10 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 		hook.snap = r->d_snap;
 		hook.counters = r->d_counters;
 	}
-	r->last_p = p;
-	r->last_nodes = nodes_path;
-	SKR_HIP(skr_launch_render(p, (hipStream_t) stream, &g_variant, r->timing ? &hook : nullptr));
+	r->last_off_ctr = lp.off_ctr;
+	r->last_levels = lp.levels;
+	g_variant = lp.variant;
+	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
 	if(r->timing) r->timed.push_back(hook);
 	return SKR_OK;
 }
@@ -671,41 +647,16 @@ int skr_renderer_kernel_ms(skr_renderer *r, float *mean_ms, int32_t *launches)
 // node pipeline: records of level `level` in the band last rendered (level 0: its level-0 nodes)
 static int nodes_level_count(skr_renderer *r, int level, uint32_t *n)
 {
-	size_t off = 0, words = 0;
-	int levels = 0;
-	*n = 0;
-	if(!skr_nodes_counter_layout(r->last_p, &off, &words, &levels) || level >= levels) return SKR_OK;
-	const uint32_t *ctr = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(r->d_nodes) + off);
-	if(level == 0)
-	{
-		SKR_HIP(hipMemcpy(n, ctr, sizeof(uint32_t), hipMemcpyDeviceToHost));
-		return SKR_OK;
-	}
-	std::vector<uint32_t> h((size_t) SKR_P1_REGIONS * SKR_PULL_STRIDE);
-	SKR_HIP(hipMemcpy(h.data(), ctr + SKR_PULL_STRIDE + words * (size_t) level, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	uint64_t total = 0;
-	for(uint32_t k = 0; k < SKR_P1_REGIONS; k++) total += h[(size_t) SKR_PULL_STRIDE * k];
-	*n = (uint32_t) total;
-	return SKR_OK;
-}
-
-int skr_renderer_last_parent_count(skr_renderer *r, uint32_t *n)
-{
 	if(!r || !n) return SKR_ERR_ARG;
 	SKR_HIP(hipSetDevice(r->device));
 	*n = 0;
-	if(r->last_nodes) return nodes_level_count(r, 0, n); // (only the node pipeline has level tables of this layout)
+	if(level < r->last_levels) SKR_HIP(skr_nodes_level_count(r->d_nodes, r->last_off_ctr, level, n)); // (only the node pipeline has level tables of this layout)
 	return SKR_OK;
 }
 
-int skr_renderer_last_level1_count(skr_renderer *r, uint32_t *n)
-{
-	if(!r || !n) return SKR_ERR_ARG;
-	SKR_HIP(hipSetDevice(r->device));
-	*n = 0;
-	if(r->last_nodes) return nodes_level_count(r, 1, n);
-	return SKR_OK;
-}
+int skr_renderer_last_parent_count(skr_renderer *r, uint32_t *n) { return nodes_level_count(r, 0, n); }
+
+int skr_renderer_last_level1_count(skr_renderer *r, uint32_t *n) { return nodes_level_count(r, 1, n); }
 
 static int read_work(skr_renderer *r, uint64_t *out, int n_out, int reset)
 {

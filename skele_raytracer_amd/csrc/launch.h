@@ -1,0 +1,98 @@
+// Host side of a render launch, shared by the translation units of libskr: the launch entry points, and the plan that decides once
+// per launch which kernels render it and how the scratch of a level pipeline is cut (skr_plan_launch, render_kernel.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "render_params.h"
+
+// The plan of one band of the node pipeline (render_nodes.hip): table sizes for the worst case, every pixel a node, every child a hit.
+constexpr int SKR_NODE_LEVELS_MAX = 33;
+struct NodePlan {
+	bool flat = false;       // the flat schedule (render_nodes.hip nodes_flat_wanted): the leaves' hits are a record level of their own
+	int levels = 0;          // node / record levels 0 .. max_depth - 2 (flat: .. max_depth - 1)
+	uint32_t band_nblk = 0;  // 16x16 pixel blocks per band
+	uint64_t nodes_max[SKR_NODE_LEVELS_MAX] = {};
+	uint32_t cap[SKR_NODE_LEVELS_MAX] = {};
+	size_t off_nodes[SKR_NODE_LEVELS_MAX] = {}, off_shade[SKR_NODE_LEVELS_MAX] = {}, off_recs[SKR_NODE_LEVELS_MAX] = {}, off_res[SKR_NODE_LEVELS_MAX] = {}, off_ixh[SKR_NODE_LEVELS_MAX] = {};
+	size_t off_ctr = 0, ctr_bytes = 0, total = 0, banded = 0;
+	size_t lds_leaf = 0;     // the leaf kernel's workgroup LDS: the scene + the per-wave rings and windows
+};
+
+// The plan of one band of the general level pipeline (render_generic.hip).
+constexpr int SKR_GLEVELS_MAX = 64;
+struct GPlan {
+	int levels = 0;            // traced levels 1 .. levels (= --depth)
+	uint32_t band_rows = 0;    // output rows per band
+	uint64_t nodes_max[SKR_GLEVELS_MAX + 1] = {}; // worst case: roots of the band; then every ray of the level above a hit
+	uint32_t cap[SKR_GLEVELS_MAX + 1] = {};       // records per region
+	size_t off_nodes[SKR_GLEVELS_MAX + 1] = {}, off_recs[SKR_GLEVELS_MAX + 1] = {}, off_res[SKR_GLEVELS_MAX + 1] = {}, off_hdr[SKR_GLEVELS_MAX + 1] = {};
+	size_t off_ctr = 0, ctr_bytes = 0, total = 0;
+};
+
+enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
+
+// Everything render_pass (api.cpp) sizes and checks and the launchers follow, computed once per launch.
+struct LaunchPlan {
+	SkrPath path = SKR_PATH_DIRECT;
+	const char *variant = "direct_v3"; // what skr_kernel_variant() reports
+	size_t scratch_bytes = 0;          // the level pipeline's one allocation (RenderParams::node_scratch)
+	size_t acc_bytes = 0;              // its AA accumulation image (RenderParams::acc)
+	size_t lds_bytes = 0;              // the largest workgroup LDS among the launch's kernels
+	size_t off_ctr = 0;                // node pipeline: where the counter block sits in the scratch ...
+	int levels = 0;                    // ... and how many node / record levels it counts (0 on the other paths)
+	NodePlan nodes;                    // (path == SKR_PATH_NODES)
+	GPlan generic;                     // (path == SKR_PATH_GENERIC)
+};
+
+// the scene SoA every kernel stages into LDS (wave_common.h stage_scene): 4 rows per sphere, a zero row, 2 rows per light
+static inline size_t skr_scene_lds_bytes(const RenderParams &p) { return ((size_t) 4 * p.n_spheres + 1 + 2 * p.n_lights) * 16; }
+
+// children per node of the --gillum tree: N --gillum rays, and under --legacy-reflect 2 per light (the arity of the counter RNG's
+// node ids, include/skr.h)
+static inline uint32_t skr_tree_arity(const RenderParams &p) { return (uint32_t) (p.monte_carlo ? p.num_path_traces : 0) + (p.legacy_reflect ? 2u * (uint32_t) p.n_lights : 0u); }
+
+// the scratch tables of a level pipeline, one after the other on 256-byte boundaries
+struct ScratchLayout {
+	size_t off = 0;
+	size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t) 255; return o; }
+};
+
+// the largest band in [1, all] whose worst-case tables fit the budget (`fits`: they grow with the band); 0: not even a band of 1
+template <class Fits>
+static uint32_t skr_largest_band(uint32_t all, Fits fits)
+{
+	if(fits(all)) return all;
+	uint32_t lo = 1, hi = all;
+	if(!fits(lo)) return 0;
+	while(hi - lo > 1)
+	{
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if(fits(mid)) lo = mid;
+		else hi = mid;
+	}
+	return lo;
+}
+
+// render_kernel.hip
+bool skr_plan_launch(const RenderParams &p, LaunchPlan &lp); // false: the launch takes a level pipeline and not one band of it fits the budget
+hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook);
+hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream);
+// render_nodes.hip
+bool skr_nodes_plan(const RenderParams &p, NodePlan &pl); // false: the node pipeline does not take this launch
+hipError_t skr_launch_nodes(const RenderParams &p, const NodePlan &pl, hipStream_t stream, const SkrTimingHook *hook);
+hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level, uint32_t *n);
+// render_generic.hip
+bool skr_generic_plan(const RenderParams &p, GPlan &pl); // false: not one band fits the budget
+hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook);
+// render_wave.hip
+hipError_t skr_launch_wave(const RenderParams &p, size_t lds, hipStream_t stream);
+hipError_t skr_launch_primary(const RenderParams &p, dim3 grid, size_t lds, hipStream_t stream);
+hipError_t skr_launch_resolve(const RenderParams &p, hipStream_t stream);
+hipError_t skr_launch_camec(const float4 *geom, int ns, f3 cam_pos, float4 *out, hipStream_t stream);
+// accumulate.hip
+hipError_t skr_launch_accumulate(float *acc, const float *frame, size_t n, int first, hipStream_t stream);
+hipError_t skr_launch_resolve_accumulated(const float *acc, uint32_t passes, uint32_t width, uint32_t out_rows, uint32_t height, uint32_t tile_rows,
+										  uint32_t first_tile, uint32_t tile_stride, const uint32_t *tile_table, uint8_t *rgb, float *rgbf, hipStream_t stream);

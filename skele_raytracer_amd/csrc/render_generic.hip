@@ -33,6 +33,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "launch.h"
 #include "wave_common.h"
 
 namespace {
@@ -384,33 +385,16 @@ __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-hipError_t skr_launch_resolve(const RenderParams &p, hipStream_t stream); // render_wave.hip
-
-constexpr int SKR_GLEVELS_MAX = 64;
-struct GPlan {
-	int levels = 0;            // traced levels 1 .. levels (= --depth)
-	uint32_t band_rows = 0;    // output rows per band
-	uint64_t nodes_max[SKR_GLEVELS_MAX + 1] = {}; // worst case: roots of the band; then every ray of the level above a hit
-	uint32_t cap[SKR_GLEVELS_MAX + 1] = {};       // records per region
-	size_t off_nodes[SKR_GLEVELS_MAX + 1] = {}, off_recs[SKR_GLEVELS_MAX + 1] = {}, off_res[SKR_GLEVELS_MAX + 1] = {}, off_hdr[SKR_GLEVELS_MAX + 1] = {};
-	size_t off_ctr = 0, ctr_bytes = 0, total = 0;
-};
-static const size_t G_LVL_CTR_WORDS = (size_t) SKR_PULL_STRIDE * (2u * SKR_P1_REGIONS + 2u);
-static uint32_t *g_prefix_host(uint32_t *ctr) { return ctr + SKR_PULL_STRIDE * (2u * SKR_P1_REGIONS + 1u) + 64; } // the level's record count (region_prefix)
-
-static uint32_t g_arity(const RenderParams &p) { return (uint32_t) (p.monte_carlo ? p.num_path_traces : 0) + (p.legacy_reflect ? 2u * (uint32_t) p.n_lights : 0u); }
-
 static bool gplan_for(const RenderParams &p, uint32_t rows, GPlan &pl)
 {
-	const uint64_t A = g_arity(p);
+	const uint64_t A = skr_tree_arity(p);
 	pl.levels = (A == 0) ? 1 : p.max_depth;
 	if(pl.levels < 1 || pl.levels > SKR_GLEVELS_MAX) return false;
 	pl.band_rows = rows;
 	pl.nodes_max[0] = (uint64_t) rows * (uint64_t) p.width;
-	size_t off = 0;
-	auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t) 255; return o; };
-	pl.ctr_bytes = (SKR_PULL_STRIDE + G_LVL_CTR_WORDS * (size_t) (pl.levels + 1)) * sizeof(uint32_t);
-	pl.off_ctr = take(pl.ctr_bytes);
+	ScratchLayout s;
+	pl.ctr_bytes = (SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) (pl.levels + 1)) * sizeof(uint32_t);
+	pl.off_ctr = s.take(pl.ctr_bytes);
 	for(int L = 1; L <= pl.levels; L++)
 	{ // a region receives at most 64 hits from each of its trace waves (64 rays): `cap` record slots per region; the level cannot hold
 	  // more hits than it has rays, which bounds the next level's rays (a band of one row would otherwise be sized for 64 x 64 nodes)
@@ -421,60 +405,36 @@ static bool gplan_for(const RenderParams &p, uint32_t rows, GPlan &pl)
 		const uint64_t slots = cap * SKR_P1_REGIONS;
 		pl.cap[L] = (uint32_t) cap;
 		pl.nodes_max[L] = slots < rays ? slots : rays;
-		pl.off_hdr[L] = take((chunks + 4) * GHDR_ROWS * 16);
-		pl.off_recs[L] = take((size_t) slots * GREC_ROWS * 16);
-		pl.off_res[L] = take((size_t) slots * 12 + 16);
-		if(L < pl.levels) pl.off_nodes[L] = take((size_t) pl.nodes_max[L] * GNODE_ROWS * 16);
-		if(off > ((size_t) 1 << 40)) return false;
+		pl.off_hdr[L] = s.take((chunks + 4) * GHDR_ROWS * 16);
+		pl.off_recs[L] = s.take((size_t) slots * GREC_ROWS * 16);
+		pl.off_res[L] = s.take((size_t) slots * 12 + 16);
+		if(L < pl.levels) pl.off_nodes[L] = s.take((size_t) pl.nodes_max[L] * GNODE_ROWS * 16);
+		if(s.off > ((size_t) 1 << 40)) return false;
 	}
-	pl.total = off;
+	pl.total = s.off;
 	return true;
 }
 
 static uint64_t g_budget(const RenderParams &p) { return p.sw.budget_mb ? (uint64_t) p.sw.budget_mb << 20 : 6ull << 30; }
 
-// the largest band (whole tile rows of 8 output rows) whose worst-case tables fit the budget
-static bool gplan(const RenderParams &p, GPlan &pl)
-{
-	const uint32_t rows_all = p.out_rows;
-	if(gplan_for(p, rows_all, pl) && pl.total <= g_budget(p)) return true;
-	uint32_t lo = 1, hi = rows_all;
-	if(!gplan_for(p, lo, pl) || pl.total > g_budget(p)) return false;
-	while(hi - lo > 1)
-	{
-		const uint32_t mid = lo + (hi - lo) / 2;
-		if(gplan_for(p, mid, pl) && pl.total <= g_budget(p)) lo = mid;
-		else hi = mid;
-	}
-	return gplan_for(p, lo, pl);
-}
-
-bool skr_generic_supported(const RenderParams &p)
+// the largest band of output rows whose worst-case tables fit the budget (< 65536 spheres, < 2^30 triangles); false: not even one row
+bool skr_generic_plan(const RenderParams &p, GPlan &pl)
 {
 	if(p.n_spheres >= 65536 || p.n_tris >= (1 << 30)) return false;
-	GPlan pl;
-	return gplan(p, pl);
+	const uint64_t budget = g_budget(p);
+	const uint32_t rows = skr_largest_band(p.out_rows, [&](uint32_t r) { return gplan_for(p, r, pl) && pl.total <= budget; });
+	return rows > 0 && gplan_for(p, rows, pl);
 }
 
-size_t skr_generic_scratch_bytes(const RenderParams &p)
-{
-	GPlan pl;
-	return gplan(p, pl) ? pl.total : 0;
-}
-
-size_t skr_generic_lds_bytes(const RenderParams &p) { return ((size_t) 4 * p.n_spheres + 1 + 2 * p.n_lights) * 16 + 32; }
-
-hipError_t skr_launch_generic(const RenderParams &p_in, hipStream_t stream, const SkrTimingHook *hook)
+hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook)
 {
 	RenderParams p = p_in;
-	GPlan pl;
-	if(!p.node_scratch || !gplan(p, pl)) return hipErrorInvalidValue;
 	char *base = reinterpret_cast<char *>(p.node_scratch);
 	uint32_t *ctr0 = reinterpret_cast<uint32_t *>(base + pl.off_ctr);
-	auto lvl_ctr = [&](int L) { return ctr0 + SKR_PULL_STRIDE + G_LVL_CTR_WORDS * (size_t) L; };
+	auto lvl_ctr = [&](int L) { return ctr0 + SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) L; };
 	const int nsamp = p.grid_size > 0 ? p.grid_size * p.grid_size : 1;
-	const size_t lds = skr_generic_lds_bytes(p);
-	const uint32_t A = g_arity(p);
+	const size_t lds = skr_scene_lds_bytes(p) + 32;
+	const uint32_t A = skr_tree_arity(p);
 	const int D = pl.levels;
 	hipError_t e = hipSuccess;
 	for(int s = 0; s < nsamp; s++)
@@ -496,7 +456,7 @@ hipError_t skr_launch_generic(const RenderParams &p_in, hipStream_t stream, cons
 				p.g_level = (uint32_t) L;
 				p.g_arity = L == 1 ? 1u : A;
 				p.g_last = L == D ? 1u : 0u;
-				p.nd_count = L == 1 ? ctr0 : g_prefix_host(lvl_ctr(L - 1));
+				p.nd_count = L == 1 ? ctr0 : lc_prefix_host(lvl_ctr(L - 1));
 				p.g_nodes_src = L == 1 ? nullptr : reinterpret_cast<const float4 *>(base + pl.off_nodes[L - 1]);
 				p.rc = reinterpret_cast<float4 *>(base + pl.off_recs[L]);
 				p.rc_cap = pl.cap[L];
@@ -516,7 +476,7 @@ hipError_t skr_launch_generic(const RenderParams &p_in, hipStream_t stream, cons
 			{ // sums, deepest level first; level 0 writes the pixels
 				p.g_level = (uint32_t) L;
 				p.g_arity = L == 0 ? 1u : A;
-				p.nd_count = L == 0 ? ctr0 : g_prefix_host(lvl_ctr(L));
+				p.nd_count = L == 0 ? ctr0 : lc_prefix_host(lvl_ctr(L));
 				p.g_nodes_src = L == 0 ? nullptr : reinterpret_cast<const float4 *>(base + pl.off_nodes[L]);
 				p.ixh = reinterpret_cast<uint4 *>(base + pl.off_hdr[L + 1]);
 				p.res_in = reinterpret_cast<const float *>(base + pl.off_res[L + 1]);

@@ -8,63 +8,74 @@
 //     --legacy-reflect, fog volumes (--scn-fog) and more than 256 children per node.
 // Rounds 1-2 also had a lane-per-pixel kernel with the recursion depth as a template parameter (--depth <= 6) here; the level
 // pipelines take any depth.
+//
+// skr_plan_launch picks the path once per launch and sizes its scratch and LDS (launch.h LaunchPlan); render_pass (api.cpp) allocates
+// and checks from that plan, and skr_launch_render and the pipelines' launchers follow it without planning again.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include "launch.h"
 #include "shade_common.h"
 
-// render_wave.hip
-size_t skr_wave_lds_bytes(const RenderParams &p);
-bool skr_wave_supported(const RenderParams &p);
-hipError_t skr_launch_wave(const RenderParams &p, hipStream_t stream);
-// render_nodes.hip
-bool skr_nodes_selected(const RenderParams &p);
-bool skr_nodes_flat(const RenderParams &p);
-size_t skr_nodes_lds_bytes(const RenderParams &p);
-hipError_t skr_launch_nodes(const RenderParams &p, hipStream_t stream, const SkrTimingHook *hook);
-// render_generic.hip
-size_t skr_generic_lds_bytes(const RenderParams &p);
-hipError_t skr_launch_generic(const RenderParams &p, hipStream_t stream, const SkrTimingHook *hook);
-
-// does shade() recurse at all in this launch (api.cpp folds --depth to 1 where it cannot: raytrace.h:208-218)
-static bool has_tree(const RenderParams &p) { return p.max_depth > 1; }
-
-// The general level pipeline takes every tree the pair kernels of the node pipeline do not, and the two modes only it knows.
-// SKR_PIPELINE=generic forces it for every launch, SKR_PIPELINE=nodes keeps triangle meshes on the node pipeline (tests, A/B runs).
-bool skr_generic_selected(const RenderParams &p)
+// The direct kernel's workgroup: the scene + 4 x 192 bytes of tile — and, for a scene that is all mesh (every lane's time is the triangle
+// walk, whose scalar loads go through a 16 KB cache that more waves only thrash), padding up to a third of the CU's LDS: dragon.scn
+// runs 1.18 / 1.24 / 1.26 ms at 3 / 4 / 5 waves per SIMD.  A mesh among spheres wants the fourth wave to hide the shading's latencies:
+// test.scn (1800 triangles, 4 spheres) 0.556 / 0.485 ms at 3 / 4.
+#ifndef SKR_MESH_LDS_PAD
+#define SKR_MESH_LDS_PAD 53248 // 3 x 53 248 B are co-resident on a CU (1280-byte granules), 4 are not
+#endif
+static size_t direct_lds_bytes(const RenderParams &p)
 {
-	if(p.sw.pipeline == SKR_PIPE_GENERIC) return true;
-	if(p.shade_triangles || p.legacy_reflect || p.n_fog > 0) return true;
-	return has_tree(p) && !skr_nodes_selected(p);
+	const size_t need = skr_scene_lds_bytes(p) + 4 * 192; // scene | tile bytes
+	return (p.n_tris > 0 && p.n_spheres == 0 && need < SKR_MESH_LDS_PAD) ? SKR_MESH_LDS_PAD : need;
 }
 
-size_t skr_render_lds_bytes(const RenderParams &p)
+// Which kernels render this launch, and what they need.  In this order:
+//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, and every tree
+//     (shade() recurses: max_depth > 1; api.cpp folds --depth to 1 where it cannot, raytrace.h:208-218) the node pipeline does not;
+//   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget;
+//   * the direct kernel takes the rest.
+// SKR_PIPELINE=generic forces the general pipeline for every launch, SKR_PIPELINE=nodes keeps triangle meshes on the node pipeline
+// (tests, A/B runs).
+bool skr_plan_launch(const RenderParams &p, LaunchPlan &lp)
 {
-	if(skr_generic_selected(p)) return skr_generic_lds_bytes(p);
-	if(skr_nodes_selected(p)) return skr_nodes_lds_bytes(p);
-	return skr_wave_lds_bytes(p);
+	lp = LaunchPlan();
+	const bool generic_only = p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0;
+	if(!generic_only && skr_nodes_plan(p, lp.nodes))
+	{
+		lp.path = SKR_PATH_NODES;
+		lp.variant = lp.nodes.flat ? "node_levels_v5_flat" : "node_levels_v5";
+		lp.scratch_bytes = lp.nodes.total;
+		lp.lds_bytes = lp.nodes.lds_leaf;
+		lp.off_ctr = lp.nodes.off_ctr;
+		lp.levels = lp.nodes.levels;
+	}
+	else if(generic_only || p.max_depth > 1)
+	{
+		lp.path = SKR_PATH_GENERIC;
+		lp.variant = "level_pipeline_g1";
+		if(!skr_generic_plan(p, lp.generic)) return false;
+		lp.scratch_bytes = lp.generic.total;
+		lp.lds_bytes = skr_scene_lds_bytes(p) + 32;
+	}
+	else
+	{
+		lp.lds_bytes = direct_lds_bytes(p);
+		return true;
+	}
+	if(p.grid_size > 0) lp.acc_bytes = (size_t) p.width * p.out_rows * 12; // AA under --gillum: one pass per sample, summed here
+	return true;
 }
 
-hipError_t skr_launch_render(const RenderParams &p, hipStream_t stream, const char **variant, const SkrTimingHook *hook)
+hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)
 {
-	if(skr_generic_selected(p))
-	{
-		if(!p.node_scratch) return hipErrorInvalidValue;
-		*variant = "level_pipeline_g1";
-		return skr_launch_generic(p, stream, hook);
-	}
-	if(skr_nodes_selected(p))
-	{
-		if(!p.node_scratch) return hipErrorInvalidValue;
-		*variant = skr_nodes_flat(p) ? "node_levels_v5_flat" : "node_levels_v5";
-		return skr_launch_nodes(p, stream, hook);
-	}
-	if(!skr_wave_supported(p)) return hipErrorInvalidValue;
-	*variant = "direct_v3";
+	if(lp.path == SKR_PATH_GENERIC) return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook) : hipErrorInvalidValue;
+	if(lp.path == SKR_PATH_NODES) return p.node_scratch ? skr_launch_nodes(p, lp.nodes, stream, hook) : hipErrorInvalidValue;
+	if(p.n_spheres >= 65536) return hipErrorInvalidValue; // (one launch, no tree: any scene the LDS holds)
 	skr_hook_start(hook, stream);
-	const hipError_t e = skr_launch_wave(p, stream);
+	const hipError_t e = skr_launch_wave(p, lp.lds_bytes, stream);
 	skr_hook_stop(hook, stream);
 	return e;
 }

@@ -33,6 +33,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <vector>
+
+#include "launch.h"
 #include "wave_common.h"
 
 namespace {
@@ -283,7 +286,7 @@ __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_shade_leaf_kernel(cons
 		const Activated a = activate_record(sv, p, act, rec, cn);
 		if(act)
 		{
-			const f3 tot = mk3(0, 0, 0); // (0,0,0) / N with N >= 1 (skr_nodes_supported): +0 in every component, no division needed
+			const f3 tot = mk3(0, 0, 0); // (0,0,0) / N with N >= 1 (skr_nodes_plan): +0 in every component, no division needed
 			const f3 colour = (div3_const(a.direct, SKR_DIV_PI) + tot * 2.0f) * ld3(sv.kd[a.sph]);
 			store3(p.res_out + (size_t) rec * 3, div3_const(colour * a.r1, SKR_DIV_PDF));
 		}
@@ -350,7 +353,7 @@ SKR_DEV void leaf_batch(const SceneView &sv, const RenderParams &p, Ring &q, flo
 		const f3 Nn = normalize3(P - ld3(sv.geom[sph]));
 		cn.hits++;
 		const f3 direct = direct_light<false>(sv, p, sph, P, Nn, cn);
-		const f3 total = mk3(0, 0, 0); // (0,0,0) / N with N >= 1 (skr_nodes_supported): +0 in every component, no division needed
+		const f3 total = mk3(0, 0, 0); // (0,0,0) / N with N >= 1 (skr_nodes_plan): +0 in every component, no division needed
 		const f3 colour = (div3_const(direct, SKR_DIV_PI) + total * 2.0f) * ld3(sv.kd[sph]);
 		const f3 c = div3_const(colour * r1, SKR_DIV_PDF);
 		float *s = slots + (int) ((ids >> 23) & (NWIN - 1)) * WIN_FLOATS + (int) ((ids >> 22) & 1u) * 192 + kl; // [round][child][component][lane]
@@ -731,28 +734,13 @@ __global__ __launch_bounds__(256) void skr_finalize_kernel2(const RenderParams p
 // =====================================================================================================================
 // host side: the plan of one band (table sizes for the worst case: every pixel a node, every child a hit), selection, launch
 // =====================================================================================================================
-hipError_t skr_launch_primary(const RenderParams &p, dim3 grid, size_t lds, hipStream_t stream); // render_wave.hip
-hipError_t skr_launch_resolve(const RenderParams &p, hipStream_t stream);
-
-constexpr int SKR_NODE_LEVELS_MAX = 33;
 #ifndef SKR_TRACE_GRID_MAX
 #define SKR_TRACE_GRID_MAX 49152u // workgroups of skr_trace_kernel at most (it strides over the blocks of 256 pairs)
 #endif
 #ifndef SKR_FLAT_BELOW
 #define SKR_FLAT_BELOW 1.2e7 // worst-case records of the last-but-one level (W x rows x N^(depth-2): what the persistent kernel cuts into units of 64 for its 4096 waves) below which a launch takes the flat schedule — a quarter of the headline frame: 0.83e7, a half: 1.66e7: tools/ab_nodes.py, tools/ab_flat.py, DESIGN.md 5.0n
 #endif
-struct NodePlan {
-	bool flat = false;       // the flat schedule (below): the leaves' hits are a record level of their own
-	int levels = 0;          // node / record levels 0 .. max_depth - 2 (flat: .. max_depth - 1)
-	uint32_t band_nblk = 0;  // 16x16 pixel blocks per band
-	uint64_t nodes_max[SKR_NODE_LEVELS_MAX] = {};
-	uint32_t cap[SKR_NODE_LEVELS_MAX] = {};
-	size_t off_nodes[SKR_NODE_LEVELS_MAX] = {}, off_shade[SKR_NODE_LEVELS_MAX] = {}, off_recs[SKR_NODE_LEVELS_MAX] = {}, off_res[SKR_NODE_LEVELS_MAX] = {}, off_ixh[SKR_NODE_LEVELS_MAX] = {};
-	size_t off_ctr = 0, ctr_bytes = 0, total = 0, banded = 0;
-};
-static uint32_t *lc_prefix_host(uint32_t *ctr) { return ctr + SKR_PULL_STRIDE * (2u * SKR_P1_REGIONS + 1u) + 64; } // the level's record count (region_prefix, published by skr_activate_kernel's first workgroup)
 static const uint32_t LEAF2_GRID = 256u * SKR_LEAF2_OCC;                   // every workgroup resident: 256 CUs x 4 workgroups of 4 waves
-static const size_t LVL_CTR_WORDS = (size_t) SKR_PULL_STRIDE * (2u * SKR_P1_REGIONS + 2u); // counts, taken, mask, prefix
 
 // Small launches (a rank's share of a frame cut over 4 or 8 GPUs; a full frame with a small tree) take the FLAT schedule: the last
 // level too is traced by skr_trace_kernel into records, which skr_shade_leaf_kernel shades — every kernel a plain grid, nothing
@@ -785,30 +773,29 @@ static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, NodePlan &
 		pl.cap[L] = (uint32_t) cap;
 		pl.nodes_max[L] = cap * SKR_P1_REGIONS;
 	}
-	size_t off = 0;
-	auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t) 255; return o; };
+	ScratchLayout s;
 	pl.ctr_bytes = (SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) pl.levels) * sizeof(uint32_t); // [0] = level-0 node count, then one block per level
-	pl.off_ctr = take(pl.ctr_bytes);
+	pl.off_ctr = s.take(pl.ctr_bytes);
 	for(int L = 0; L < pl.levels; L++)
 	{
 		const size_t n = (size_t) pl.nodes_max[L];
 		if(L > 0)
 		{
-			pl.off_recs[L] = take(n * 16);
-			pl.off_res[L] = take(n * 12 + 16);
+			pl.off_recs[L] = s.take(n * 16);
+			pl.off_res[L] = s.take(n * 12 + 16);
 		}
 		if(L < pl.levels - 1 || pl.levels == 1)
 		{ // levels whose nodes exist (the last record level is only shaded): geometry rows and shading rows, 32 bytes each per node
-			pl.off_nodes[L] = take(n * 32);
-			pl.off_shade[L] = take(n * 32);
+			pl.off_nodes[L] = s.take(n * 32);
+			pl.off_shade[L] = s.take(n * 32);
 		}
 		if(L < pl.levels - 1)
 		{ // the children of level L: a 48-byte header per trace wave (64 sibling pairs)
-			pl.off_ixh[L] = take(((n * PP + 63) / 64 + 4) * IXH_ROWS * 16);
+			pl.off_ixh[L] = s.take(((n * PP + 63) / 64 + 4) * IXH_ROWS * 16);
 		}
 	}
-	pl.total = off;
-	pl.banded = off - (pl.off_nodes[0]); // what grows with the band; the counters are fixed
+	pl.total = s.off;
+	pl.banded = s.off - (pl.off_nodes[0]); // what grows with the band; the counters are fixed
 	return true;
 }
 
@@ -823,21 +810,25 @@ static bool plan_bands(const RenderParams &p, bool flat, NodePlan &pl)
 {
 	const uint32_t bx = (uint32_t) (p.width + 15) / 16, by = (p.out_rows + 15) / 16;
 	const uint64_t budget = nodes_budget(p, flat);
-	uint32_t lo = 1, hi = bx * by;
-	if(!plan_for(p, lo, flat, pl) || pl.banded > budget) return false;
-	if(plan_for(p, hi, flat, pl) && pl.banded <= budget) return true;
-	while(hi - lo > 1)
-	{ // plan size grows with the block count
-		const uint32_t mid = lo + (hi - lo) / 2;
-		if(plan_for(p, mid, flat, pl) && pl.banded <= budget) lo = mid;
-		else hi = mid;
-	}
-	if(lo > bx) lo = lo / bx * bx; // whole block rows where possible
-	return plan_for(p, lo, flat, pl);
+	uint32_t nblk = skr_largest_band(bx * by, [&](uint32_t n) { return plan_for(p, n, flat, pl) && pl.banded <= budget; });
+	if(nblk == 0) return false;
+	if(nblk > bx) nblk = nblk / bx * bx; // whole block rows where possible
+	return plan_for(p, nblk, flat, pl);
 }
 
-static bool skr_nodes_plan(const RenderParams &p, NodePlan &pl)
+// The node pipeline covers --gillum trees of any depth >= 2 on sphere scenes (<= 256 children per node, < 65536 spheres) whose tables
+// fit the budget in bands.  SKR_PIPELINE=nodes forces it wherever it applies; other values of SKR_PIPELINE exclude it.  Triangle meshes
+// go to the general level pipeline (render_generic.hip: one lane per ray, one walk of the culling tree per 64 rays; test.scn 640x360
+// --gillum 4: 1.18 ms there against 2.15 ms here, where a lane walks the tree once per sibling); a handful of triangles (spheres1.scn
+// has two) are tested in line by the pair kernels.
+bool skr_nodes_plan(const RenderParams &p, NodePlan &pl)
 {
+	const bool forced = p.sw.pipeline == SKR_PIPE_NODES;
+	if(p.sw.pipeline != SKR_PIPE_AUTO && !forced) return false;
+	if(p.shade_triangles || p.legacy_reflect) return false; // (render_generic.hip)
+	if(!(p.monte_carlo && p.n_spheres > 0 && p.n_spheres < 65536 && p.max_depth >= 2 && p.num_path_traces > 0 && p.num_path_traces <= 256)) return false;
+	if(!forced && p.n_tris > 64) return false;
+	pl.lds_leaf = skr_scene_lds_bytes(p) + 32 + (size_t) 4 * LEAF2_WAVE_FLOATS * sizeof(float);
 	if(nodes_flat_wanted(p))
 	{ // flat only in one piece (SKR_FLAT=1: wherever it fits at all): in bands the persistent kernel is the better schedule
 		const uint32_t all = (uint32_t) ((p.width + 15) / 16) * ((p.out_rows + 15) / 16);
@@ -846,53 +837,20 @@ static bool skr_nodes_plan(const RenderParams &p, NodePlan &pl)
 	return plan_bands(p, false, pl);
 }
 
-// The node pipeline covers --gillum trees of any depth >= 2 on sphere scenes (<= 256 children per node, < 65536 spheres).
-// SKR_PIPELINE=nodes forces it wherever it applies; other values of SKR_PIPELINE exclude it.
-bool skr_nodes_supported(const RenderParams &p)
+// records of level `level` in the band last rendered (level 0: its level-0 nodes), from its counter block at off_ctr in the scratch:
+// [0] = level-0 nodes, then per level 64 region counts
+hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level, uint32_t *n)
 {
-	if(p.shade_triangles || p.legacy_reflect) return false; // (render_generic.hip)
-	if(!(p.monte_carlo && p.n_spheres > 0 && p.n_spheres < 65536 && p.max_depth >= 2 && p.num_path_traces > 0 && p.num_path_traces <= 256)) return false;
-	NodePlan pl;
-	return skr_nodes_plan(p, pl);
+	const uint32_t *ctr = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(scratch) + off_ctr);
+	if(level == 0) return hipMemcpy(n, ctr, sizeof(uint32_t), hipMemcpyDeviceToHost);
+	std::vector<uint32_t> h((size_t) SKR_P1_REGIONS * SKR_PULL_STRIDE);
+	const hipError_t e = hipMemcpy(h.data(), ctr + SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) level, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+	if(e != hipSuccess) return e;
+	uint64_t total = 0;
+	for(uint32_t k = 0; k < SKR_P1_REGIONS; k++) total += h[(size_t) SKR_PULL_STRIDE * k];
+	*n = (uint32_t) total;
+	return hipSuccess;
 }
-
-bool skr_nodes_selected(const RenderParams &p)
-{
-	const bool forced = p.sw.pipeline == SKR_PIPE_NODES;
-	if(p.sw.pipeline != SKR_PIPE_AUTO && !forced) return false;
-	if(!skr_nodes_supported(p)) return false;
-	if(forced) return true;
-	// triangle meshes go to the general level pipeline (render_generic.hip: one lane per ray, one walk of the culling tree per 64
-	// rays; test.scn 640x360 --gillum 4: 1.18 ms there against 2.15 ms here, where a lane walks the tree once per sibling);
-	// a handful of triangles (spheres1.scn has two) are tested in line by the pair kernels
-	return p.n_tris <= 64;
-}
-
-// the schedule this launch takes: the flat one (small launches) or the persistent leaf kernel
-bool skr_nodes_flat(const RenderParams &p)
-{
-	NodePlan pl;
-	return skr_nodes_plan(p, pl) && pl.flat;
-}
-
-size_t skr_nodes_scratch_bytes(const RenderParams &p)
-{
-	NodePlan pl;
-	return skr_nodes_plan(p, pl) ? pl.total : 0;
-}
-
-// where the counters of the band last rendered sit in the scratch: [0] = level-0 nodes, then per level 64 region counts
-bool skr_nodes_counter_layout(const RenderParams &p, size_t *off_ctr, size_t *level_words, int *levels)
-{
-	NodePlan pl;
-	if(!skr_nodes_plan(p, pl)) return false;
-	*off_ctr = pl.off_ctr;
-	*level_words = LVL_CTR_WORDS;
-	*levels = pl.levels;
-	return true;
-}
-
-size_t skr_nodes_lds_bytes(const RenderParams &p) { return ((size_t) 4 * p.n_spheres + 1 + 2 * p.n_lights) * 16 + 32 + (size_t) 4 * LEAF2_WAVE_FLOATS * sizeof(float); }
 
 template <bool FIRST>
 static hipError_t launch_leaf2(const RenderParams &p, size_t lds, hipStream_t stream)
@@ -905,19 +863,16 @@ static hipError_t launch_leaf2(const RenderParams &p, size_t lds, hipStream_t st
 	return hipGetLastError();
 }
 
-hipError_t skr_launch_nodes(const RenderParams &p_in, hipStream_t stream, const SkrTimingHook *hook)
+hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStream_t stream, const SkrTimingHook *hook)
 {
 	RenderParams p = p_in;
-	NodePlan pl;
-	if(!p.node_scratch || !skr_nodes_plan(p, pl)) return hipErrorInvalidValue;
 	char *base = reinterpret_cast<char *>(p.node_scratch);
 	uint32_t *ctr0 = reinterpret_cast<uint32_t *>(base + pl.off_ctr);
 	auto lvl_ctr = [&](int L) { return ctr0 + SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) L; };
 	auto nodes = [&](int L) { return reinterpret_cast<float4 *>(base + pl.off_nodes[L]); };   // geometry rows
 	auto shade = [&](int L) { return reinterpret_cast<float4 *>(base + pl.off_shade[L]); };   // shading rows
 	const int nsamp = p.grid_size > 0 ? p.grid_size * p.grid_size : 1;
-	const size_t lds_scene = ((size_t) 4 * p.n_spheres + 1 + 2 * p.n_lights) * 16 + 32;
-	const size_t lds_leaf = skr_nodes_lds_bytes(p);
+	const size_t lds_scene = skr_scene_lds_bytes(p) + 32;
 	const bool tris = p.n_tris > 0;
 	const bool flat = pl.flat;
 	const int D = p.max_depth, last = flat ? D - 1 : D - 2; // record levels 1 .. last; the leaf kernel (flat: skr_shade_leaf_kernel) works on level `last`
@@ -947,7 +902,7 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, hipStream_t stream, const 
 				p.nd_count = ctr0;
 				p.rc_ctr = lvl_ctr(0);
 				if(timed) skr_hook_start(hook, stream);
-				e = launch_leaf2<true>(p, lds_leaf, stream);
+				e = launch_leaf2<true>(p, pl.lds_leaf, stream);
 				if(timed) skr_hook_stop(hook, stream);
 				if(e != hipSuccess) return e;
 				continue;
@@ -988,7 +943,7 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, hipStream_t stream, const 
 			else
 			{ // leaf kernel: the records of the last level (their parents: level last - 1), results into res[last]
 				if(timed) skr_hook_start(hook, stream);
-				e = launch_leaf2<false>(p, lds_leaf, stream);
+				e = launch_leaf2<false>(p, pl.lds_leaf, stream);
 				if(timed) skr_hook_stop(hook, stream);
 				if(e != hipSuccess) return e;
 			}

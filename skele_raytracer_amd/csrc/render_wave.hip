@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "launch.h"
 #include "wave_common.h"
 
 // One workgroup = 4 independent waves; wave w of block (bx, by) owns the 8x8 pixel tile (2*bx + (w&1), 2*by + (w>>1)).
@@ -256,27 +257,10 @@ __global__ __launch_bounds__(256) void skr_resolve_kernel(const RenderParams p)
 	}
 }
 
-// the direct kernel's workgroup: the scene + 4 x 192 bytes of tile — and, for a scene that is all mesh (every lane's time is the triangle
-// walk, whose scalar loads go through a 16 KB cache that more waves only thrash), padding up to a third of the CU's LDS: dragon.scn
-// runs 1.18 / 1.24 / 1.26 ms at 3 / 4 / 5 waves per SIMD.  A mesh among spheres wants the fourth wave to hide the shading's latencies:
-// test.scn (1800 triangles, 4 spheres) 0.556 / 0.485 ms at 3 / 4.
-size_t skr_wave_lds_bytes(const RenderParams &p)
-{
-	const size_t need = ((size_t) 4 * p.n_spheres + 1 + 2 * p.n_lights) * 16 + 4 * 192; // scene | tile bytes
-#ifndef SKR_MESH_LDS_PAD
-#define SKR_MESH_LDS_PAD 53248 // 3 x 53 248 B are co-resident on a CU (1280-byte granules), 4 are not
-#endif
-	const size_t third = SKR_MESH_LDS_PAD;
-	return (p.n_tris > 0 && p.n_spheres == 0 && need < third) ? third : need;
-}
-
-// one launch, no tree: any scene the LDS holds
-bool skr_wave_supported(const RenderParams &p) { return p.n_spheres < 65536; }
-
-hipError_t skr_launch_wave(const RenderParams &p, hipStream_t stream)
+// lds: the workgroup's LDS (render_kernel.hip direct_lds_bytes)
+hipError_t skr_launch_wave(const RenderParams &p, size_t lds, hipStream_t stream)
 {
 	const dim3 grid((p.width + 15) / 16, (p.out_rows + 15) / 16);
-	const size_t lds = skr_wave_lds_bytes(p);
 	const bool tris = p.n_tris > 0, sph = p.n_spheres > 0;
 	const void *fn = tris ? (sph ? reinterpret_cast<const void *>(skr_direct_kernel<true, true>) : reinterpret_cast<const void *>(skr_direct_kernel<true, false>))
 	                      : (sph ? reinterpret_cast<const void *>(skr_direct_kernel<false, true>) : reinterpret_cast<const void *>(skr_direct_kernel<false, false>));
