@@ -12,7 +12,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-
             -fno-fast-math -Wall -Wno-unused-function -Wno-pass-failed -Iinclude
 KERNEL_SRCS := $(CSRC)/render_kernel.hip $(CSRC)/render_wave.hip $(CSRC)/render_nodes.hip $(CSRC)/render_generic.hip $(CSRC)/accumulate.hip
 HOST_SRCS   := $(CSRC)/api.cpp $(CSRC)/scene_host.cpp $(CSRC)/multi_gpu.cpp
-HDRS        := include/skr.h $(CSRC)/launch.h $(CSRC)/device_math.h $(CSRC)/shade_common.h $(CSRC)/render_params.h $(CSRC)/scene_host.h $(CSRC)/tri_chunks.h $(CSRC)/wave_common.h
+HDRS        := include/skr.h $(CSRC)/launch.h $(CSRC)/device_math.h $(CSRC)/shade_common.h $(CSRC)/render_params.h $(CSRC)/scene_host.h $(CSRC)/shadow_cells.h $(CSRC)/tri_chunks.h $(CSRC)/wave_common.h
 
 all: lib cli oracle
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SKR_ABI_VERSION 4 /* 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
+#define SKR_ABI_VERSION 5 /* 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
 
 typedef enum {
 	SKR_OK = 0,
@@ -140,6 +140,12 @@ int skr_scene_get_arrays(const skr_scene *scene, float *spheres, float *triangle
  * tests. */
 int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks,
 						  float *device_tris, float *node_spheres, int32_t *node_links, float *chunk_spheres);
+/* The shadow masks the level pipelines' shadow walk runs on (DESIGN.md "Shadow masks"), as uploaded: per point light a cube map of
+ * 6 x cells x cells uint32_t, masks[light][face][i][j], face = 2 axis + (negative), bit k = sphere k may stop a shadow ray of that light
+ * whose direction from the shading point towards the light falls in the cell; they hold for shading points P with
+ * fl(|Lp - P|^2) <= *reach2.  *n_lights = 0 where the scene has none (no sphere, more than 32, a directional light).  Any pointer may be
+ * NULL; the counts are returned first so the caller can size the array.  Used by the host-logic tests. */
+int skr_scene_get_shadow_masks(const skr_scene *scene, int32_t *n_lights, int32_t *cells, float *reach2, uint32_t *masks);
 
 /* Materials of the triangles of a scene built from arrays, materials[n_triangles][10] = ambient(3) diffuse(3) specular(3)
  * phong power — what the `material` line in force gives a `triangle` line in a .scn file (scene.cpp:110-137; the reference

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
     "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_destroy", "skr_scene_get_info",
-    "skr_scene_get_arrays", "skr_scene_get_culling", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
+    "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_shadow_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
     "skr_kernel_variant", "skr_debug_eval",
@@ -77,6 +77,7 @@ def lib():
     L.skr_scene_get_info.argtypes = [vp, C.POINTER(CSceneInfo)]
     L.skr_scene_get_arrays.argtypes = [vp, vp, vp, vp]
     L.skr_scene_get_culling.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp]
+    L.skr_scene_get_shadow_masks.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), vp]
     L.skr_options_default.argtypes = [C.POINTER(COptions)]
     L.skr_options_default.restype = None
     L.skr_radiance_ray_count.argtypes = [C.POINTER(COptions)]
@@ -221,6 +222,14 @@ class Scene:
         _check(lib().skr_scene_get_culling(self.h, level, None, None, None, tris.ctypes.data, sph.ctypes.data, links.ctypes.data, ch.ctypes.data),
                "skr_scene_get_culling")
         return cs.value, tris, sph, links, ch
+
+    def shadow_masks(self):
+        """(masks [n_lights, 6, cells, cells] uint32, reach2) — include/skr.h skr_scene_get_shadow_masks; n_lights = 0: the scene has none."""
+        nl, cells, reach2 = C.c_int32(), C.c_int32(), C.c_float()
+        _check(lib().skr_scene_get_shadow_masks(self.h, C.byref(nl), C.byref(cells), C.byref(reach2), None), "skr_scene_get_shadow_masks")
+        m = np.zeros((nl.value, 6, cells.value, cells.value), np.uint32)
+        _check(lib().skr_scene_get_shadow_masks(self.h, None, None, None, m.ctypes.data), "skr_scene_get_shadow_masks")
+        return m, reach2.value
 
     @property
     def fog(self):

@@ -35,6 +35,8 @@ struct skr_renderer {
 	size_t off_amb = 0, off_kd = 0, off_ks = 0, off_lights = 0, off_tris = 0, off_chunks = 0, off_tri_mats = 0;
 	size_t off_fog = 0;       // --scn-fog: 2 rows per fog volume (render_params.h RenderParams::fog_row)
 	int n_fog = 0;
+	size_t off_smask = 0;     // the shadow masks (skr_scene::shadow_masks, 4 per row), 0 = none
+	float shadow_reach2 = 0.0f;
 	int n_chunks = 0, chunk_size = 0, cones = 0;
 	size_t chunk_stride = 0;
 	unsigned long long *d_counters = nullptr;
@@ -71,6 +73,7 @@ static void load_switches(SkrSwitches &sw)
 	sw.no_cull = getenv("SKR_NO_CULL") != nullptr;
 	if(const char *e = getenv("SKR_LEVELS_BUDGET_MB")) sw.budget_mb = atoi(e) > 0 ? atoi(e) : 1;
 	if(const char *e = getenv("SKR_FLAT")) sw.flat = atoi(e) > 0 ? 1 : -1;
+	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = atoi(e) > 0 ? 1 : 0;
 }
 
 // (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
@@ -136,7 +139,10 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	}
 	r->off_fog = 4 * ns + nl2 + nt3 + nch + ntm;
 	r->n_fog = (int) nfog;
-	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog;
+	const size_t nsm = (scene->shadow_masks.size() + 3) / 4; // rows of the shadow masks
+	r->off_smask = nsm ? r->off_fog + 2 * nfog : 0;
+	r->shadow_reach2 = scene->shadow_reach2;
+	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog + nsm;
 	std::vector<skr_f4> blob(total + 16); // (+ 16 rows: the sphere loops ask for the rows of a trip ahead without a bounds test, shade_common.h sphere_rows)
 	if(ns)
 	{
@@ -164,6 +170,7 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		blob[r->off_fog + 2 * j] = {f[3], f[8], f[7], 0.0f};
 		blob[r->off_fog + 2 * j + 1] = {f[4], f[5], f[6], 0.0f};
 	}
+	if(nsm) memcpy(&blob[r->off_smask], scene->shadow_masks.data(), scene->shadow_masks.size() * 4);
 	r->blob_bytes = blob.size() * 16;
 	hipError_t e = hipMalloc((void **) &r->d_blob, blob.size() * 16);
 	if(e == hipSuccess) e = hipMemcpy(r->d_blob, blob.data(), blob.size() * 16, hipMemcpyHostToDevice);
@@ -216,6 +223,7 @@ int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 	r->off_amb = src->off_amb; r->off_kd = src->off_kd; r->off_ks = src->off_ks; r->off_lights = src->off_lights;
 	r->off_tris = src->off_tris; r->off_chunks = src->off_chunks; r->off_tri_mats = src->off_tri_mats;
 	r->off_fog = src->off_fog; r->n_fog = src->n_fog;
+	r->off_smask = src->off_smask; r->shadow_reach2 = src->shadow_reach2;
 	r->n_chunks = src->n_chunks; r->chunk_size = src->chunk_size; r->cones = src->cones; r->chunk_stride = src->chunk_stride;
 	r->d_counters = src->d_counters;
 	r->d_tri_work = src->d_tri_work;
@@ -337,6 +345,12 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.tri_chunks = r->d_blob + r->off_chunks;
 	p.tri_chunk_size = r->chunk_size;
 	p.tri_cones = (r->cones && !r->sw.no_cones) ? 1 : 0;
+	if(r->off_smask && r->sw.shadow_mask)
+	{ // the level pipelines' shadow walk visits only the spheres a lane's masks name (shade_common.h occluded_pair)
+		p.shadow_masks = reinterpret_cast<const uint32_t *>(r->d_blob + r->off_smask);
+		p.shadow_reach2 = r->shadow_reach2;
+		p.shadow_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
+	}
 	{ // pick the tightest set of chunk spheres whose |d| bound covers this frame's camera rays (GI children stay below 4,
 	  // the smallest bound): primary directions are dir + u right + v up (main.cpp:154-155)
 		auto len3 = [](const float *v) { return std::sqrt((double) v[0] * v[0] + (double) v[1] * v[1] + (double) v[2] * v[2]); };

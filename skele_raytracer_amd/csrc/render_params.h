@@ -23,9 +23,11 @@ struct f3 {
 enum SkrPipeline { SKR_PIPE_AUTO = 0, SKR_PIPE_NODES, SKR_PIPE_GENERIC, SKR_PIPE_OTHER };
 struct SkrSwitches {
 	int32_t pipeline = SKR_PIPE_AUTO; // SKR_PIPELINE = nodes | generic: which level pipeline takes a --gillum tree (tests, A/B runs)
-	int32_t no_cones = 0, no_cull = 0; // SKR_NO_CONES, SKR_NO_CULL: triangle-walk culling off
+	int16_t no_cones = 0, no_cull = 0; // SKR_NO_CONES, SKR_NO_CULL: triangle-walk culling off  (two halves of one word: the struct stays 20 bytes, so that
+	                                   // every field of RenderParams behind it keeps its offset and the kernels that never read the switches their code)
 	int32_t budget_mb = 0;            // SKR_LEVELS_BUDGET_MB: scratch budget of the level pipelines (0 = default)
 	int32_t flat = 0;                 // SKR_FLAT = 1 | 0: the node pipeline's flat schedule forced on (+1) / off (-1); unset: by launch size
+	int32_t shadow_mask = 1;          // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
 };
 
 struct RenderParams {
@@ -92,6 +94,12 @@ struct RenderParams {
 	int32_t n_fog;            // (see fog_row)
 	const float4 *g_nodes_src; // nodes of the level above (trace, activate) / of the level being summed (finalize): 5 float4 each
 	float4 *g_nodes_dst;      // nodes being written (activate)
+	// the shadow masks (shadow_cells.h; the level pipelines' shadow walk, shade_common.h occluded_pair): SKR_SHADOW_TABLE_WORDS per point light,
+	// in the scene blob (HBM, never written by a kernel); null = every shadow ray tests every sphere.  They hold for shading points P with
+	// fl(|Lp - P|^2) <= shadow_reach2; shadow_all = the mask of every sphere.
+	const uint32_t *shadow_masks;
+	float shadow_reach2;
+	uint32_t shadow_all;
 };
 
 // Optional timing of the dominant kernel of a launch (skr_renderer_kernel_ms): the launcher records the

@@ -138,6 +138,7 @@ void skr_scene::finalize()
 	tri_order = order;
 	build_triangle_materials();
 	build_triangle_chunks();
+	build_shadow_masks();
 }
 
 void skr_scene::build_triangle_materials()
@@ -156,6 +157,102 @@ void skr_scene::build_triangle_materials()
 		tri_mats[3 * i + 1] = {kd[0], kd[1], kd[2], 0.0f};
 		tri_mats[3 * i + 2] = {ks[0], ks[1], ks[2], 0.0f};
 	}
+}
+
+// The shadow masks (shadow_cells.h; DESIGN.md "Shadow masks" derives every margin below).  Every shadow ray of a point light runs along
+// a line through (almost) the light's position Lp, so whether sphere k can stop it depends only on the ray's direction as seen from Lp:
+// bit k of a cell is set when the line through Lp along the cell's centre direction, taken in both senses, passes within R of the
+// centre of sphere k, where R grows the radius by
+//   * the slack of the binary32 discriminant, which can come out >= 0 for a line that just misses the sphere (grazing),
+//   * how far the ray's line lies from the ideal line through Lp: the 1e-6 offset of its origin and the error of L = normalize(Lp - P),
+//     which grows with the distance from Lp (bounded through `reach`, the farthest shading point the device lets use a mask),
+//   * the cell's angular radius (every corner; the cell widened to absorb the device's rounding of its face coordinates) times the
+//     distance from Lp.
+// A light inside the grown sphere sets the bit in every cell.  All in binary64.
+void skr_scene::build_shadow_masks()
+{
+	shadow_masks.clear();
+	shadow_reach2 = 0.0f;
+	const int ns = info.n_spheres, nl = info.n_point_lights, nt = info.n_triangles;
+	if(ns < 1 || ns > SKR_SHADOW_MAX_SPHERES || nl < 1 || !raw_directional_lights.empty()) return;
+	// reach: the farthest point of the scene (spheres, triangles with their accept regions v0 - e1, v0 + e2) from any light.  The device
+	// checks fl(|Lp - P|^2) <= reach^2 per lane, so a shading point outside it only costs that lane the plain walk.
+	double reach = 0.0;
+	for(int l = 0; l < nl; l++)
+	{
+		const double lp[3] = {raw_point_lights[6 * l], raw_point_lights[6 * l + 1], raw_point_lights[6 * l + 2]};
+		auto dist = [&](double x, double y, double z) { return std::sqrt((x - lp[0]) * (x - lp[0]) + (y - lp[1]) * (y - lp[1]) + (z - lp[2]) * (z - lp[2])); };
+		for(int k = 0; k < ns; k++)
+			reach = std::max(reach, dist(sph_geom[k].x, sph_geom[k].y, sph_geom[k].z) + std::sqrt((double) sph_geom[k].w));
+		for(int t = 0; t < nt; t++)
+		{
+			const float *v = &raw_triangles[(size_t) t * 9];
+			for(int c = 0; c < 3; c++) reach = std::max(reach, dist(v[3 * c], v[3 * c + 1], v[3 * c + 2]));
+			const double e1[3] = {(double) v[3] - v[0], (double) v[4] - v[1], (double) v[5] - v[2]}, e2[3] = {(double) v[6] - v[0], (double) v[7] - v[1], (double) v[8] - v[2]};
+			reach = std::max(reach, dist(v[0] - e1[0], v[1] - e1[1], v[2] - e1[2]));
+			reach = std::max(reach, dist(v[0] + e2[0], v[1] + e2[1], v[2] + e2[2]));
+		}
+	}
+	reach *= 1.0 + 0x1p-10;
+	if(!(reach > 0.0) || !(reach * reach < 1e36)) return; // (NaN, inf, or beyond binary32: no masks)
+	const float reach2 = std::nextafter((float) (reach * reach), INFINITY);
+	const double D = std::sqrt((double) reach2) * (1.0 + 0x1p-16); // bounds |Lp - P| of every lane that passes fl(|Lp - P|^2) <= reach2
+	const double eta = 0x1p-16;                                  // bounds |L - (Lp - P) / |Lp - P||, L the device's binary32 normalize
+	const int N = SKR_SHADOW_CELLS;
+	// every cell's centre direction and angular radius: the same for every light
+	std::vector<double> cell_dir((size_t) SKR_SHADOW_TABLE_WORDS * 3), cell_theta(SKR_SHADOW_TABLE_WORDS);
+	for(int f = 0; f < 6; f++)
+		for(int i = 0; i < N; i++)
+			for(int j = 0; j < N; j++)
+			{
+				const int ax = f >> 1, o1 = ax == 0 ? 1 : 0, o2 = ax == 2 ? 1 : 2;
+				const double sg = (f & 1) ? -1.0 : 1.0, wid = 2.0 / N, pad = 0x1p-12; // pad: the device's face coordinates are within 2^-20 of v's
+				auto dir = [&](double a, double b, double *w) {
+					w[ax] = sg;
+					w[o1] = a;
+					w[o2] = b;
+					const double n = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+					for(int c = 0; c < 3; c++) w[c] /= n;
+				};
+				const double a0 = -1.0 + i * wid, b0 = -1.0 + j * wid;
+				double *wc = &cell_dir[3 * ((size_t) (f * N + i) * N + j)];
+				dir(a0 + 0.5 * wid, b0 + 0.5 * wid, wc);
+				double theta = 0.0;
+				for(int corner = 0; corner < 4; corner++)
+				{ // the cell is a convex spherical quadrilateral: its farthest point from the centre direction is a corner
+					double w[3];
+					dir((corner & 1) ? a0 + wid + pad : a0 - pad, (corner & 2) ? b0 + wid + pad : b0 - pad, w);
+					const double cx = wc[1] * w[2] - wc[2] * w[1], cy = wc[2] * w[0] - wc[0] * w[2], cz = wc[0] * w[1] - wc[1] * w[0];
+					theta = std::max(theta, std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), wc[0] * w[0] + wc[1] * w[1] + wc[2] * w[2]));
+				}
+				cell_theta[(size_t) (f * N + i) * N + j] = theta * (1.0 + 0x1p-20) + 0x1p-16; // + the angle between fl(Lp - P) and Lp - P
+			}
+	std::vector<uint32_t> masks((size_t) nl * SKR_SHADOW_TABLE_WORDS, 0u);
+	for(int l = 0; l < nl; l++)
+	{
+		const double lp[3] = {raw_point_lights[6 * l], raw_point_lights[6 * l + 1], raw_point_lights[6 * l + 2]};
+		const double lmax = std::max(std::fabs(lp[0]), std::max(std::fabs(lp[1]), std::fabs(lp[2])));
+		// |o - P| for o = fl(P + 1e-6f) per component, |P| <= |Lp| + D (twice over)
+		const double eps_o = 2.0 * std::sqrt(3.0) * (1e-6 + 0x1p-23 * (lmax + D + 1e-6));
+		for(int k = 0; k < ns; k++)
+		{
+			const double q[3] = {sph_geom[k].x - lp[0], sph_geom[k].y - lp[1], sph_geom[k].z - lp[2]};
+			const double r2 = sph_geom[k].w, qq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2], qn = std::sqrt(qq);
+			const double E = (qn + D + eps_o) * (1.0 + 0x1p-20); // bounds |e| = |o - C| of the device's test
+			const double rk = std::sqrt(r2 + 0x1p-16 * (E * E + r2)) + 0x1p-20 * E; // discriminant slack (16x), the rounding of e
+			const double S = qn + rk;                                               // farthest point of the grown sphere from Lp
+			const double base = rk + eps_o + eta * (S + D + eps_o) / (1.0 - eta) + 0x1p-30 * qn;
+			for(int c = 0; c < SKR_SHADOW_TABLE_WORDS; c++)
+			{
+				const double *wc = &cell_dir[3 * (size_t) c];
+				const double s = q[0] * wc[0] + q[1] * wc[1] + q[2] * wc[2];
+				const double dist = std::sqrt(std::max(0.0, qq - s * s));
+				if(dist <= base + cell_theta[c] * S) masks[(size_t) l * SKR_SHADOW_TABLE_WORDS + c] |= 1u << k;
+			}
+		}
+	}
+	shadow_masks.swap(masks);
+	shadow_reach2 = reach2;
 }
 
 // Exact-preserving culling data for the triangle walk (DESIGN.md "Triangle chunks").
@@ -793,6 +890,16 @@ int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_
 		if(node_links) memcpy(node_links + 4 * (size_t) i, base + 3 * (size_t) i + 2, 16);
 	}
 	if(chunk_spheres && nc) memcpy(chunk_spheres, base + 3 * ((size_t) nn + 1), (size_t) nc * 32);
+	return SKR_OK;
+}
+
+int skr_scene_get_shadow_masks(const skr_scene *scene, int32_t *n_lights, int32_t *cells, float *reach2, uint32_t *masks)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(n_lights) *n_lights = (int32_t) (scene->shadow_masks.size() / SKR_SHADOW_TABLE_WORDS);
+	if(cells) *cells = SKR_SHADOW_CELLS;
+	if(reach2) *reach2 = scene->shadow_reach2;
+	if(masks && !scene->shadow_masks.empty()) memcpy(masks, scene->shadow_masks.data(), scene->shadow_masks.size() * 4);
 	return SKR_OK;
 }
 

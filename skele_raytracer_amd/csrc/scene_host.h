@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/skr.h"
+#include "shadow_cells.h"
 #include "tri_chunks.h"
 
 
@@ -53,6 +54,11 @@ struct skr_scene {
 	std::vector<int> tri_order; // tris[3*i] holds triangle tri_order[i] of the file
 	void build_triangle_materials();
 	void build_triangle_chunk_level(double d_max, std::vector<skr_f4> &out);
+	// the shadow masks of the level pipelines' shadow walk (shadow_cells.h, DESIGN.md "Shadow masks"): SKR_SHADOW_TABLE_WORDS per point
+	// light, in light order; empty where the walk keeps its plain loop (no sphere, more than SKR_SHADOW_MAX_SPHERES, a directional light)
+	std::vector<uint32_t> shadow_masks;
+	float shadow_reach2 = 0.0f; // the masks hold for shading points P with fl(|Lp - P|^2) <= shadow_reach2 (every light); other lanes test every sphere
+	void build_shadow_masks();
 };
 
 // scene.cpp:12-227 replacement.  Returns SKR_OK or SKR_ERR_IO.

@@ -4,6 +4,7 @@
 
 #include "device_math.h"
 #include "render_params.h"
+#include "shadow_cells.h"
 #include "tri_chunks.h"
 
 namespace {
@@ -26,6 +27,9 @@ struct SceneView {
 	int cones;            // some entry carries a tight radius for non-grazing rays
 	unsigned long long *tri_work; // HBM, or null (not counting): SKR_TRI_WORK_SHARDS x {culling-sphere tests, triangle tests} the walks executed (lanes that needed them)
 	const float4 *geom_u; // HBM: the same rows as `geom`, for the loops that walk the spheres in order with a wave-uniform index (sphere_rows)
+	const uint32_t *smask; // HBM, or null: the shadow masks (RenderParams::shadow_masks; shadow_mask_of)
+	float smask_reach2;
+	uint32_t smask_all;
 };
 typedef float skr_v4f __attribute__((ext_vector_type(4)));
 // One aligned 16-byte row of a table that no kernel writes, at a wave-uniform index, through the constant address space: that is what
@@ -338,6 +342,25 @@ SKR_DEV bool any_triangle_closer(const SceneView &sv, const RayConst &r, float t
 	return hit;
 }
 
+// The spheres that may stop the shadow ray of point light l from P (v = Lp - P, the subtraction light_term makes): the cell of v's
+// direction in the light's table (shadow_cells.h; DESIGN.md "Shadow masks").  A lane whose P lies beyond the reach the table was built
+// for, or whose v is not a vector of normal length (zero, NaN, inf), gets every sphere.  The index is in bounds whatever v holds.
+SKR_DEV uint32_t shadow_mask_of(const SceneView &sv, int l, f3 v)
+{
+	const float vv = sqr3(v);
+	const bool ok = (vv <= sv.smask_reach2) && (vv >= 0x1p-98f);
+	const float ax = __builtin_fabsf(v.x), ay = __builtin_fabsf(v.y), az = __builtin_fabsf(v.z);
+	const bool fx = (ax >= ay) && (ax >= az), fy = !fx && (ay >= az);
+	const float m = fx ? ax : (fy ? ay : az), lead = fx ? v.x : (fy ? v.y : v.z);
+	const float a = fx ? v.y : v.x, b = fy || fx ? v.z : v.y;
+	const int face = (fx ? 0 : (fy ? 2 : 4)) + (lead < 0.0f ? 1 : 0);
+	const float inv = __builtin_amdgcn_rcpf(m), h = 0.5f * (float) SKR_SHADOW_CELLS, top = (float) (SKR_SHADOW_CELLS - 1);
+	const int i = (int) __builtin_fminf(__builtin_fmaxf((a * inv) * h + h, 0.0f), top); // (NaN -> 0)
+	const int j = (int) __builtin_fminf(__builtin_fmaxf((b * inv) * h + h, 0.0f), top);
+	const uint32_t mask = sv.smask[(l * 6 + face) * (SKR_SHADOW_CELLS * SKR_SHADOW_CELLS) + i * SKR_SHADOW_CELLS + j];
+	return ok ? mask : sv.smask_all;
+}
+
 // utils.h:42-58: any sphere with 1 < t < inf along the (unbounded) shadow ray; two lights at a
 // time, because both shadow rays start at the same point and share e and c per sphere.
 // COHERENT: the lanes of the wave are neighbouring pixels (the direct kernel's 8x8 tiles), where a whole wave in one shadow is common
@@ -347,8 +370,11 @@ SKR_DEV bool any_triangle_closer(const SceneView &sv, const RayConst &r, float t
 #ifndef SKR_COHERENT_TRIP
 #define SKR_COHERENT_TRIP 4 // spheres per trip of the coherent shadow loop (the wave-wide exit is looked at once per trip)
 #endif
+// With shadow masks (the level pipelines, !COHERENT): `cand` = the union of the lane's two masks (shadow_mask_of).  A sphere outside a
+// ray's mask provably fails the test below (its D < 0), so each lane walks only its own candidates, lowest index first: the first
+// occluder it finds is the one the loop over every sphere finds, and every decision and count is the same.
 template <bool COHERENT>
-SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second, bool &occ0, bool &occ1, uint32_t &tests)
+SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second, bool &occ0, bool &occ1, uint32_t &tests, uint32_t cand = 0u)
 {
 	const f3 o = add_scalar(P, 0.000001f);
 	const RayPair rp = make_pair(L0, L1);
@@ -384,10 +410,48 @@ SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second,
 		}
 	};
 	if(COHERENT) table_rows<SKR_COHERENT_TRIP>(sv.geom_u, sv.ns, test, [&] { return !__all(occ0 && occ1); }); // (the wave-wide exit, once per trip)
+	else if(sv.smask)
+	{
+#if defined(SKR_DIAG) && SKR_DIAG
+		{ // the gate of DESIGN.md "Shadow masks": spheres the wave's lanes name together, the most one lane names, the sum over lanes
+			uint32_t any = 0, most = 0, sum = 0;
+			for(int k = 0; k < 32; k++)
+			{
+				const unsigned long long bk = __ballot((cand >> k) & 1u);
+				any += bk ? 1u : 0u;
+				sum += (uint32_t) __popcll(bk);
+			}
+			for(uint32_t c = 1; c <= 32; c++) most += __any((uint32_t) __popc(cand) >= c) ? 1u : 0u;
+			DIAG_WAVE(19, 1);
+			DIAG_WAVE(20, any);
+			DIAG_WAVE(21, most);
+			DIAG_WAVE(22, sv.ns);
+			DIAG_WAVE(23, sum);
+			DIAG_LANES(24);
+		}
+#endif
+		uint32_t rest = cand;
+		while(rest)
+		{
+			const int i = __builtin_ctz(rest);
+			test(sv.geom[i], i); // (the lanes' rows differ: LDS)
+			rest &= rest - 1u;
+		}
+	}
 	else sphere_rows(sv, test);
 	if(!occ0) tests += (uint32_t) sv.ns;
 	if(second && !occ1) tests += (uint32_t) sv.ns;
 	if(!second) occ1 = false;
+}
+
+// The union of the shadow masks of lights i and (second) i + 1 at P, for occluded_pair; 0 where it walks every sphere.  (The masks
+// exist only for scenes whose lights are all point lights.)
+template <bool COHERENT>
+SKR_DEV uint32_t shadow_cands(const SceneView &sv, const RenderParams &p, int i, bool second, f3 P)
+{
+	if(COHERENT || !sv.smask || !p.use_shadows) return 0u;
+	const uint32_t m0 = shadow_mask_of(sv, i, ld3(sv.lights[2 * i]) - P);
+	return second ? m0 | shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P) : m0;
 }
 
 struct LightTerm { // the per-light quantities of blinn_phong.h:67-72 / :100-117
@@ -425,12 +489,13 @@ SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3
 	for(int i = 0; i < sv.nl; i += 2)
 	{
 		const bool second = i + 1 < sv.nl;
+		const uint32_t cand = shadow_cands<COHERENT>(sv, p, i, second, P); // (asked for ahead of the light terms)
 		const LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
 		bool occ0 = false, occ1 = false;
 		if(p.use_shadows)
 		{
 			cn.shadow_rays += second ? 2u : 1u;
-			occluded_pair<COHERENT>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests);
+			occluded_pair<COHERENT>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
 		}
 		auto add_light = [&](const LightTerm &t, bool lit)
 		{
@@ -487,12 +552,13 @@ SKR_DEV f3 direct_light_fog(const SceneView &sv, const RenderParams &p, f3 kd, f
 	for(int i = 0; i < sv.nl; i += 2)
 	{
 		const bool second = i + 1 < sv.nl;
+		const uint32_t cand = shadow_cands<false>(sv, p, i, second, P);
 		const LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
 		bool occ0 = false, occ1 = false;
 		if(p.use_shadows)
 		{
 			cn.shadow_rays += second ? 2u : 1u;
-			occluded_pair<false>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests);
+			occluded_pair<false>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
 		}
 		auto add_light = [&](const LightTerm &t, int l, bool lit)
 		{
