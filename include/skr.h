@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SKR_ABI_VERSION 5 /* 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
+#define SKR_ABI_VERSION 6 /* 6: skr_scene_get_gi_masks; 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
 
 typedef enum {
 	SKR_OK = 0,
@@ -146,6 +146,12 @@ int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_
  * fl(|Lp - P|^2) <= *reach2.  *n_lights = 0 where the scene has none (no sphere, more than 32, a directional light).  Any pointer may be
  * NULL; the counts are returned first so the caller can size the array.  Used by the host-logic tests. */
 int skr_scene_get_shadow_masks(const skr_scene *scene, int32_t *n_lights, int32_t *cells, float *reach2, uint32_t *masks);
+/* The GI masks the node pipeline's closest-hit walk of GI children runs on (DESIGN.md "GI masks"), as uploaded: *n_words uint32_t words
+ * (0 = the scene has none: no sphere, more than 32, triangles); the masks start at word *mask_word, uint16_t entries (uint32_t where
+ * *wide), 6 x dir_cells x dir_cells of them per origin cell, addressed like the shadow masks.  grids[2][8] = the fine and the coarse
+ * origin grid: lo.xyz, 1 / cell edge, the cell counts n.xyz and the grid's first index word (as floats); index word
+ * base + (k n1 + j) n0 + i = the origin cell's row of masks, -1 = none.  Any pointer may be NULL.  Used by the host-logic tests. */
+int skr_scene_get_gi_masks(const skr_scene *scene, int32_t *n_words, int32_t *mask_word, int32_t *wide, int32_t *dir_cells, float *grids, uint32_t *table);
 
 /* Materials of the triangles of a scene built from arrays, materials[n_triangles][10] = ambient(3) diffuse(3) specular(3)
  * phong power — what the `material` line in force gives a `triangle` line in a .scn file (scene.cpp:110-137; the reference

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
     "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_destroy", "skr_scene_get_info",
-    "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_shadow_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
+    "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
     "skr_kernel_variant", "skr_debug_eval",
@@ -78,6 +78,7 @@ def lib():
     L.skr_scene_get_arrays.argtypes = [vp, vp, vp, vp]
     L.skr_scene_get_culling.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp]
     L.skr_scene_get_shadow_masks.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), vp]
+    L.skr_scene_get_gi_masks.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
     L.skr_options_default.argtypes = [C.POINTER(COptions)]
     L.skr_options_default.restype = None
     L.skr_radiance_ray_count.argtypes = [C.POINTER(COptions)]
@@ -230,6 +231,15 @@ class Scene:
         m = np.zeros((nl.value, 6, cells.value, cells.value), np.uint32)
         _check(lib().skr_scene_get_shadow_masks(self.h, None, None, None, m.ctypes.data), "skr_scene_get_shadow_masks")
         return m, reach2.value
+
+    def gi_masks(self):
+        """(table uint32 words, mask_word, wide, dir_cells, grids [2, 8] float32) — include/skr.h skr_scene_get_gi_masks; an empty table: the scene has none."""
+        nw, mw, wide, dc = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        grids = np.zeros((2, 8), np.float32)
+        _check(lib().skr_scene_get_gi_masks(self.h, C.byref(nw), C.byref(mw), C.byref(wide), C.byref(dc), grids.ctypes.data, None), "skr_scene_get_gi_masks")
+        t = np.zeros(nw.value, np.uint32)
+        _check(lib().skr_scene_get_gi_masks(self.h, None, None, None, None, None, t.ctypes.data), "skr_scene_get_gi_masks")
+        return t, mw.value, wide.value, dc.value, grids
 
     @property
     def fog(self):

@@ -37,6 +37,10 @@ struct skr_renderer {
 	int n_fog = 0;
 	size_t off_smask = 0;     // the shadow masks (skr_scene::shadow_masks, 4 per row), 0 = none
 	float shadow_reach2 = 0.0f;
+	size_t off_gi = 0;        // the GI masks (skr_scene::gi_table, 4 words per row), 0 = none
+	SkrGiGrid gi_grid[2] = {};
+	uint32_t gi_mask_word = 0;
+	int gi_wide = 0;
 	int n_chunks = 0, chunk_size = 0, cones = 0;
 	size_t chunk_stride = 0;
 	unsigned long long *d_counters = nullptr;
@@ -74,6 +78,7 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_LEVELS_BUDGET_MB")) sw.budget_mb = atoi(e) > 0 ? atoi(e) : 1;
 	if(const char *e = getenv("SKR_FLAT")) sw.flat = atoi(e) > 0 ? 1 : -1;
 	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = atoi(e) > 0 ? 1 : 0;
+	if(const char *e = getenv("SKR_GI_MASK")) sw.gi_mask = atoi(e) > 0 ? 1 : 0;
 }
 
 // (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
@@ -142,7 +147,13 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	const size_t nsm = (scene->shadow_masks.size() + 3) / 4; // rows of the shadow masks
 	r->off_smask = nsm ? r->off_fog + 2 * nfog : 0;
 	r->shadow_reach2 = scene->shadow_reach2;
-	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog + nsm;
+	const size_t ngi = scene->gi_table.size() / 4; // rows of the GI masks (whole rows: scene_host.cpp build_gi_masks)
+	r->off_gi = ngi ? r->off_fog + 2 * nfog + nsm : 0;
+	r->gi_grid[0] = scene->gi_grid[0];
+	r->gi_grid[1] = scene->gi_grid[1];
+	r->gi_mask_word = scene->gi_mask_word;
+	r->gi_wide = scene->gi_wide;
+	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog + nsm + ngi;
 	std::vector<skr_f4> blob(total + 16); // (+ 16 rows: the sphere loops ask for the rows of a trip ahead without a bounds test, shade_common.h sphere_rows)
 	if(ns)
 	{
@@ -171,6 +182,7 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		blob[r->off_fog + 2 * j + 1] = {f[4], f[5], f[6], 0.0f};
 	}
 	if(nsm) memcpy(&blob[r->off_smask], scene->shadow_masks.data(), scene->shadow_masks.size() * 4);
+	if(ngi) memcpy(&blob[r->off_gi], scene->gi_table.data(), scene->gi_table.size() * 4);
 	r->blob_bytes = blob.size() * 16;
 	hipError_t e = hipMalloc((void **) &r->d_blob, blob.size() * 16);
 	if(e == hipSuccess) e = hipMemcpy(r->d_blob, blob.data(), blob.size() * 16, hipMemcpyHostToDevice);
@@ -224,6 +236,7 @@ int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 	r->off_tris = src->off_tris; r->off_chunks = src->off_chunks; r->off_tri_mats = src->off_tri_mats;
 	r->off_fog = src->off_fog; r->n_fog = src->n_fog;
 	r->off_smask = src->off_smask; r->shadow_reach2 = src->shadow_reach2;
+	r->off_gi = src->off_gi; r->gi_grid[0] = src->gi_grid[0]; r->gi_grid[1] = src->gi_grid[1]; r->gi_mask_word = src->gi_mask_word; r->gi_wide = src->gi_wide;
 	r->n_chunks = src->n_chunks; r->chunk_size = src->chunk_size; r->cones = src->cones; r->chunk_stride = src->chunk_stride;
 	r->d_counters = src->d_counters;
 	r->d_tri_work = src->d_tri_work;
@@ -350,6 +363,15 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 		p.shadow_masks = reinterpret_cast<const uint32_t *>(r->d_blob + r->off_smask);
 		p.shadow_reach2 = r->shadow_reach2;
 		p.shadow_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
+	}
+	if(r->off_gi && r->sw.gi_mask)
+	{ // the node pipeline's closest-hit walk of a GI child visits only the spheres its masks name (wave_common.h closest_pair)
+		p.gi_index = reinterpret_cast<const int32_t *>(r->d_blob + r->off_gi);
+		p.gi_masks = reinterpret_cast<const uint32_t *>(r->d_blob + r->off_gi) + r->gi_mask_word;
+		p.gi_grid[0] = r->gi_grid[0];
+		p.gi_grid[1] = r->gi_grid[1];
+		p.gi_wide = r->gi_wide;
+		p.gi_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
 	}
 	{ // pick the tightest set of chunk spheres whose |d| bound covers this frame's camera rays (GI children stay below 4,
 	  // the smallest bound): primary directions are dir + u right + v up (main.cpp:154-155)

@@ -89,7 +89,8 @@ SKR_DEV bool classify_child(const SceneView &sv, f3 co, f3 d, float two_a, float
 #else
 #define SKR_TRACE_ATTR
 #endif
-template <bool TRIS>
+// GIM: GI masks (sphere-only scenes, p.gi_index set; wave_common.h closest_pair); the kernels without them are compiled without the walk
+template <bool TRIS, bool GIM>
 __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams p)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 		cn.rays += second ? 2u : 1u;
 		const RayPair rp = make_pair(d0, d1);
 		BestState s0, s1;
-		closest_pair(sv, co, d0, d1, second, rp, s0, s1);
+		closest_pair<GIM>(sv, p, GIM ? gi_origin_row(p, co) : -1, co, d0, d1, second, rp, s0, s1);
 		hit0 = classify_child(sv, co, d0, rp.two_a.x, rp.four_a.x, s0, black0);
 		rec0 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s0.best & 0xffff) | ((2u * j) << 16)), q1a, q2a);
 		if(second)
@@ -401,7 +402,7 @@ extern "C" void skr_leaf2_times_read(unsigned long long *out)
 #ifndef SKR_LEAF2_OCC
 #define SKR_LEAF2_OCC 4 // waves per SIMD the register allocation aims at (A/B builds)
 #endif
-template <bool TRIS, bool FIRST>
+template <bool TRIS, bool FIRST, bool GIM>
 __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const RenderParams p)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -507,6 +508,7 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 		const bool act = act0;
 		f3 nt, nb;
 		tangent_basis(Nn, nt, nb);
+		const int gi_row = GIM ? gi_origin_row(p, co) : -1; // (the lane's origin row of GI masks: one per unit, every round's children start at co)
 		// (r1 and the sphere are only needed when the unit is finished: they are read again from the record / node row then)
 		STAMP(1);
 		// ---- rounds: children 2j, 2j+1 of every lane's node
@@ -543,7 +545,7 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 				cn.rays += second ? 2u : 1u;
 				const RayPair rp = make_pair(d0, d1);
 				BestState s0, s1;
-				closest_pair(sv, co, d0, d1, second, rp, s0, s1);
+				closest_pair<GIM>(sv, p, gi_row, co, d0, d1, second, rp, s0, s1);
 				bool black;
 				hit0 = classify_child(sv, co, d0, rp.two_a.x, rp.four_a.x, s0, black);
 				if(!hit0)
@@ -854,12 +856,16 @@ hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level,
 
 template <bool FIRST>
 static hipError_t launch_leaf2(const RenderParams &p, size_t lds, hipStream_t stream)
-{
-	const void *fn = p.n_tris > 0 ? reinterpret_cast<const void *>(skr_leaf_kernel2<true, FIRST>) : reinterpret_cast<const void *>(skr_leaf_kernel2<false, FIRST>);
+{ // (GI masks exist for sphere-only scenes alone: scene_host.cpp build_gi_masks)
+	const bool gim = p.n_tris == 0 && p.gi_index != nullptr;
+	const void *fn = p.n_tris > 0 ? reinterpret_cast<const void *>(skr_leaf_kernel2<true, FIRST, false>)
+					 : gim        ? reinterpret_cast<const void *>(skr_leaf_kernel2<false, FIRST, true>)
+								  : reinterpret_cast<const void *>(skr_leaf_kernel2<false, FIRST, false>);
 	hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 	if(e != hipSuccess) return e;
-	if(p.n_tris > 0) hipLaunchKernelGGL((skr_leaf_kernel2<true, FIRST>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
-	else hipLaunchKernelGGL((skr_leaf_kernel2<false, FIRST>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
+	if(p.n_tris > 0) hipLaunchKernelGGL((skr_leaf_kernel2<true, FIRST, false>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
+	else if(gim) hipLaunchKernelGGL((skr_leaf_kernel2<false, FIRST, true>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
+	else hipLaunchKernelGGL((skr_leaf_kernel2<false, FIRST, false>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
 	return hipGetLastError();
 }
 
@@ -920,8 +926,9 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStr
 				const uint64_t wg_t = (pl.nodes_max[L - 1] * (uint64_t) ((p.num_path_traces + 1) >> 1) + 255) / 256;
 				const unsigned grid_t = (unsigned) (wg_t < SKR_TRACE_GRID_MAX ? wg_t : SKR_TRACE_GRID_MAX);
 				if(flat && L == last && timed) skr_hook_start(hook, stream); // (flat: the last level's trace + shading are the dominant pair)
-				if(tris) hipLaunchKernelGGL(skr_trace_kernel<true>, dim3(grid_t), dim3(256), lds_scene, stream, p);
-				else hipLaunchKernelGGL(skr_trace_kernel<false>, dim3(grid_t), dim3(256), lds_scene, stream, p);
+				if(tris) hipLaunchKernelGGL((skr_trace_kernel<true, false>), dim3(grid_t), dim3(256), lds_scene, stream, p);
+				else if(p.gi_index) hipLaunchKernelGGL((skr_trace_kernel<false, true>), dim3(grid_t), dim3(256), lds_scene, stream, p);
+				else hipLaunchKernelGGL((skr_trace_kernel<false, false>), dim3(grid_t), dim3(256), lds_scene, stream, p);
 				if(L < last)
 				{ // its records become the nodes of level L
 					p.nd_dst = nodes(L);

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "shadow_cells.h"
+
 struct f3 {
 	float x, y, z;
 };
@@ -27,7 +29,8 @@ struct SkrSwitches {
 	                                   // every field of RenderParams behind it keeps its offset and the kernels that never read the switches their code)
 	int32_t budget_mb = 0;            // SKR_LEVELS_BUDGET_MB: scratch budget of the level pipelines (0 = default)
 	int32_t flat = 0;                 // SKR_FLAT = 1 | 0: the node pipeline's flat schedule forced on (+1) / off (-1); unset: by launch size
-	int32_t shadow_mask = 1;          // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
+	int16_t shadow_mask = 1;          // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
+	int16_t gi_mask = 1;              // SKR_GI_MASK = 1 | 0: the same for the closest-hit walk of the node pipeline's GI children  (two halves of one word, as above)
 };
 
 struct RenderParams {
@@ -100,6 +103,14 @@ struct RenderParams {
 	const uint32_t *shadow_masks;
 	float shadow_reach2;
 	uint32_t shadow_all;
+	// the GI masks (shadow_cells.h; the node pipeline's closest-hit walk of GI children, wave_common.h closest_pair), in the scene blob:
+	// gi_index = the index words of both grids, gi_masks = the rows of masks (uint16_t entries, uint32_t where gi_wide); null = every
+	// GI child tests every sphere.  gi_all = the mask of every sphere.
+	const int32_t *gi_index;
+	const uint32_t *gi_masks;
+	SkrGiGrid gi_grid[2];
+	int32_t gi_wide;
+	uint32_t gi_all;
 };
 
 // Optional timing of the dominant kernel of a launch (skr_renderer_kernel_ms): the launcher records the

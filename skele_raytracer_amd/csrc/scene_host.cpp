@@ -139,6 +139,7 @@ void skr_scene::finalize()
 	build_triangle_materials();
 	build_triangle_chunks();
 	build_shadow_masks();
+	build_gi_masks();
 }
 
 void skr_scene::build_triangle_materials()
@@ -157,6 +158,41 @@ void skr_scene::build_triangle_materials()
 		tri_mats[3 * i + 1] = {kd[0], kd[1], kd[2], 0.0f};
 		tri_mats[3 * i + 2] = {ks[0], ks[1], ks[2], 0.0f};
 	}
+}
+
+// The cells of a cube map of N x N cells per face (shadow_cells.h addressing): every cell's centre direction (unit, 3 doubles) and
+// angular radius, taken at its farthest corner (a cube-map cell is a convex spherical quadrilateral) with the cell widened by 2^-12 in
+// face coordinates: the device's v_rcp_f32 face coordinates are within 2^-20 of v's.
+static void cube_cells(int N, std::vector<double> &cell_dir, std::vector<double> &cell_theta)
+{
+	cell_dir.assign((size_t) 6 * N * N * 3, 0.0);
+	cell_theta.assign((size_t) 6 * N * N, 0.0);
+	for(int f = 0; f < 6; f++)
+		for(int i = 0; i < N; i++)
+			for(int j = 0; j < N; j++)
+			{
+				const int ax = f >> 1, o1 = ax == 0 ? 1 : 0, o2 = ax == 2 ? 1 : 2;
+				const double sg = (f & 1) ? -1.0 : 1.0, wid = 2.0 / N, pad = 0x1p-12;
+				auto dir = [&](double a, double b, double *w) {
+					w[ax] = sg;
+					w[o1] = a;
+					w[o2] = b;
+					const double n = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+					for(int c = 0; c < 3; c++) w[c] /= n;
+				};
+				const double a0 = -1.0 + i * wid, b0 = -1.0 + j * wid;
+				double *wc = &cell_dir[3 * ((size_t) (f * N + i) * N + j)];
+				dir(a0 + 0.5 * wid, b0 + 0.5 * wid, wc);
+				double theta = 0.0;
+				for(int corner = 0; corner < 4; corner++)
+				{
+					double w[3];
+					dir((corner & 1) ? a0 + wid + pad : a0 - pad, (corner & 2) ? b0 + wid + pad : b0 - pad, w);
+					const double cx = wc[1] * w[2] - wc[2] * w[1], cy = wc[2] * w[0] - wc[0] * w[2], cz = wc[0] * w[1] - wc[1] * w[0];
+					theta = std::max(theta, std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), wc[0] * w[0] + wc[1] * w[1] + wc[2] * w[2]));
+				}
+				cell_theta[(size_t) (f * N + i) * N + j] = theta;
+			}
 }
 
 // The shadow masks (shadow_cells.h; DESIGN.md "Shadow masks" derives every margin below).  Every shadow ray of a point light runs along
@@ -198,35 +234,10 @@ void skr_scene::build_shadow_masks()
 	const float reach2 = std::nextafter((float) (reach * reach), INFINITY);
 	const double D = std::sqrt((double) reach2) * (1.0 + 0x1p-16); // bounds |Lp - P| of every lane that passes fl(|Lp - P|^2) <= reach2
 	const double eta = 0x1p-16;                                  // bounds |L - (Lp - P) / |Lp - P||, L the device's binary32 normalize
-	const int N = SKR_SHADOW_CELLS;
 	// every cell's centre direction and angular radius: the same for every light
-	std::vector<double> cell_dir((size_t) SKR_SHADOW_TABLE_WORDS * 3), cell_theta(SKR_SHADOW_TABLE_WORDS);
-	for(int f = 0; f < 6; f++)
-		for(int i = 0; i < N; i++)
-			for(int j = 0; j < N; j++)
-			{
-				const int ax = f >> 1, o1 = ax == 0 ? 1 : 0, o2 = ax == 2 ? 1 : 2;
-				const double sg = (f & 1) ? -1.0 : 1.0, wid = 2.0 / N, pad = 0x1p-12; // pad: the device's face coordinates are within 2^-20 of v's
-				auto dir = [&](double a, double b, double *w) {
-					w[ax] = sg;
-					w[o1] = a;
-					w[o2] = b;
-					const double n = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-					for(int c = 0; c < 3; c++) w[c] /= n;
-				};
-				const double a0 = -1.0 + i * wid, b0 = -1.0 + j * wid;
-				double *wc = &cell_dir[3 * ((size_t) (f * N + i) * N + j)];
-				dir(a0 + 0.5 * wid, b0 + 0.5 * wid, wc);
-				double theta = 0.0;
-				for(int corner = 0; corner < 4; corner++)
-				{ // the cell is a convex spherical quadrilateral: its farthest point from the centre direction is a corner
-					double w[3];
-					dir((corner & 1) ? a0 + wid + pad : a0 - pad, (corner & 2) ? b0 + wid + pad : b0 - pad, w);
-					const double cx = wc[1] * w[2] - wc[2] * w[1], cy = wc[2] * w[0] - wc[0] * w[2], cz = wc[0] * w[1] - wc[1] * w[0];
-					theta = std::max(theta, std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), wc[0] * w[0] + wc[1] * w[1] + wc[2] * w[2]));
-				}
-				cell_theta[(size_t) (f * N + i) * N + j] = theta * (1.0 + 0x1p-20) + 0x1p-16; // + the angle between fl(Lp - P) and Lp - P
-			}
+	std::vector<double> cell_dir, cell_theta;
+	cube_cells(SKR_SHADOW_CELLS, cell_dir, cell_theta);
+	for(double &t : cell_theta) t = t * (1.0 + 0x1p-20) + 0x1p-16; // + the angle between fl(Lp - P) and Lp - P
 	std::vector<uint32_t> masks((size_t) nl * SKR_SHADOW_TABLE_WORDS, 0u);
 	for(int l = 0; l < nl; l++)
 	{
@@ -253,6 +264,187 @@ void skr_scene::build_shadow_masks()
 	}
 	shadow_masks.swap(masks);
 	shadow_reach2 = reach2;
+}
+
+// The GI masks (shadow_cells.h; DESIGN.md "GI masks" derives every margin below).  A GI child ray starts at its node's hit point o
+// and runs along d (not of unit length: the basis mix of shade_common.h gi_direction_pair); the device's closest-hit walk counts
+// sphere k as a candidate when its binary32 D >= 0 and b < 0.  For a cell of origins — a ball of centre q and radius rho — and a cell
+// of directions — a cone of axis w and half-angle theta — bit k is set unless, for every origin and every direction of the two cells,
+//   * the line misses the sphere grown to r' (the slack of the binary32 discriminant, as for the shadow masks): the distance from C to
+//     the line is at least |C - q| sin(psi) - rho, psi the angle between C - q and the direction, psi in [phi - theta, phi + theta],
+//   * or the sphere lies behind the origin: (C - o).d/|d| <= |C - q| cos(max(0, phi - theta)) + rho < -(the rounding of b), so b > 0.
+// All in binary64.  Origins are looked up in a fine grid over the small spheres (radius <= 4 x the median), grown by twice the largest
+// of them, then in a coarse grid over every sphere's bounds, cut to the fine grid's box grown by its extent; only cells near some
+// sphere's surface (where hit points lie) get masks.  The cells grow until the whole table fits SKR_GI_MAX_BYTES.  A device lane whose
+// origin lies in no stored cell, or whose direction is degenerate, walks every sphere.
+void skr_scene::build_gi_masks()
+{
+	gi_table.clear();
+	gi_grid[0] = gi_grid[1] = SkrGiGrid{};
+	gi_mask_word = 0;
+	gi_wide = 0;
+	const int ns = info.n_spheres;
+	if(ns < 1 || ns > SKR_GI_MAX_SPHERES || info.n_triangles > 0) return;
+	std::vector<double> C((size_t) 3 * ns), r2(ns), rad(ns);
+	for(int k = 0; k < ns; k++)
+	{
+		C[3 * k] = sph_geom[k].x;
+		C[3 * k + 1] = sph_geom[k].y;
+		C[3 * k + 2] = sph_geom[k].z;
+		r2[k] = sph_geom[k].w;
+		rad[k] = std::sqrt(r2[k]);
+		for(int c = 0; c < 3; c++)
+			if(!(std::fabs(C[3 * k + c]) < 1e6)) return;
+		if(!(rad[k] < 1e6)) return; // (NaN, inf, out of the range the margins are derived for: no masks)
+	}
+	std::vector<double> sorted(rad);
+	std::sort(sorted.begin(), sorted.end());
+	const double small = 4.0 * sorted[ns / 2];
+	double flo[3] = {INFINITY, INFINITY, INFINITY}, fhi[3] = {-INFINITY, -INFINITY, -INFINITY}, alo[3] = {INFINITY, INFINITY, INFINITY},
+		   ahi[3] = {-INFINITY, -INFINITY, -INFINITY}, rsmall = 0.0;
+	for(int k = 0; k < ns; k++)
+		for(int c = 0; c < 3; c++)
+		{
+			alo[c] = std::min(alo[c], C[3 * k + c] - rad[k]);
+			ahi[c] = std::max(ahi[c], C[3 * k + c] + rad[k]);
+			if(rad[k] <= small)
+			{
+				flo[c] = std::min(flo[c], C[3 * k + c] - rad[k]);
+				fhi[c] = std::max(fhi[c], C[3 * k + c] + rad[k]);
+				rsmall = std::max(rsmall, rad[k]);
+			}
+		}
+	double ext_f = 0.0;
+	for(int c = 0; c < 3; c++)
+	{
+		flo[c] -= 2.0 * rsmall;
+		fhi[c] += 2.0 * rsmall;
+		ext_f = std::max(ext_f, fhi[c] - flo[c]);
+	}
+	if(!(ext_f > 1e-6)) return;
+	double clo[3], chi[3], ext_c = 0.0;
+	for(int c = 0; c < 3; c++)
+	{
+		clo[c] = std::min(flo[c], std::max(alo[c], flo[c] - ext_f));
+		chi[c] = std::max(fhi[c], std::min(ahi[c], fhi[c] + ext_f));
+		ext_c = std::max(ext_c, chi[c] - clo[c]);
+	}
+	gi_wide = ns > 16 ? 1 : 0;
+	const size_t row_bytes = (size_t) SKR_GI_ROW_ENTRIES * (gi_wide ? 4 : 2);
+	struct Cell {
+		double q[3], rho;
+	};
+	std::vector<Cell> cells;
+	std::vector<int32_t> index;
+	double hh[2] = {0.0, 0.0};
+	bool fits = false;
+	for(int attempt = 0; attempt < 64 && !fits; attempt++)
+	{
+		const double grow = std::pow(1.15, attempt);
+		cells.clear();
+		index.clear();
+		for(int g = 0; g < 2; g++)
+		{
+			SkrGiGrid &G = gi_grid[g];
+			const double *lo = g ? clo : flo, *hi = g ? chi : fhi;
+			G.inv = (float) (1.0 / ((g ? ext_c / 16.0 : ext_f / 32.0) * grow));
+			hh[g] = 1.0 / (double) G.inv; // the cell edge the device's (o - lo) * inv cuts at
+			for(int c = 0; c < 3; c++)
+			{
+				float l = (float) lo[c];
+				if((double) l > lo[c]) l = std::nextafter(l, -INFINITY);
+				G.lo[c] = l;
+				G.n[c] = std::max(1, std::min(256, (int) std::ceil((hi[c] - (double) l) / hh[g])));
+				G.n_f[c] = (float) G.n[c];
+			}
+			G.base = (int32_t) index.size();
+			const int n0 = G.n[0], n1 = G.n[1], n2 = G.n[2];
+			// the device's cell of o is within 2^-22 (i + 1) hh of o's: pad every cell by 2^-18 n hh
+			const double pad = 0x1p-18 * std::max(n0, std::max(n1, n2)) * hh[g];
+			const double rho = std::sqrt(3.0) * (0.5 * hh[g] + pad) * (1.0 + 0x1p-20);
+			for(int k = 0; k < n2; k++)
+				for(int j = 0; j < n1; j++)
+					for(int i = 0; i < n0; i++)
+					{
+						const int ijk[3] = {i, j, k};
+						Cell cl;
+						bool inside_fine = g == 1;
+						for(int c = 0; c < 3; c++)
+						{
+							cl.q[c] = (double) G.lo[c] + (ijk[c] + 0.5) * hh[g];
+							const double f0 = (double) gi_grid[0].lo[c], f1 = f0 + gi_grid[0].n[c] * hh[0];
+							inside_fine = inside_fine && cl.q[c] - 0.5 * hh[g] >= f0 && cl.q[c] + 0.5 * hh[g] <= f1;
+						}
+						cl.rho = rho;
+						bool near = false; // (which cells are stored decides only the speed: hit points lie near some sphere's surface)
+						for(int s = 0; s < ns && !near && !inside_fine; s++)
+						{
+							const double dx = C[3 * s] - cl.q[0], dy = C[3 * s + 1] - cl.q[1], dz = C[3 * s + 2] - cl.q[2];
+							const double dist = std::sqrt(dx * dx + dy * dy + dz * dz);
+							near = std::fabs(dist - rad[s]) <= rho + 1e-4 + 0x1p-16 * (dist + rad[s]);
+						}
+						index.push_back(near ? (int32_t) cells.size() : -1);
+						if(near) cells.push_back(cl);
+					}
+		}
+		fits = ((index.size() + 1) & ~(size_t) 1) * 4 + cells.size() * row_bytes <= SKR_GI_MAX_BYTES;
+	}
+	if(!fits || cells.empty()) return;
+	std::vector<double> cell_dir, cell_theta;
+	cube_cells(SKR_GI_DIR_CELLS, cell_dir, cell_theta);
+	std::vector<double> cth(SKR_GI_ROW_ENTRIES), sth(SKR_GI_ROW_ENTRIES);
+	for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++)
+	{
+		const double t = cell_theta[e] * (1.0 + 0x1p-20) + 0x1p-40;
+		cth[e] = std::cos(t);
+		sth[e] = std::sin(t);
+	}
+	std::vector<uint32_t> masks(cells.size() * SKR_GI_ROW_ENTRIES, 0u);
+	for(size_t ci = 0; ci < cells.size(); ci++)
+	{
+		const Cell &cl = cells[ci];
+		uint32_t *row = &masks[ci * SKR_GI_ROW_ENTRIES];
+		for(int k = 0; k < ns; k++)
+		{
+			const double v[3] = {C[3 * k] - cl.q[0], C[3 * k + 1] - cl.q[1], C[3 * k + 2] - cl.q[2]};
+			const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+			const double E = (dist + cl.rho) * (1.0 + 0x1p-20); // bounds |e| = |o - C| of the device's test
+			const double rk = std::sqrt(r2[k] + 0x1p-16 * (E * E + r2[k])) + 0x1p-20 * E; // discriminant slack (16x), the rounding of e
+			const double tol = 0x1p-30 * (dist + cl.rho + rk);                             // (this function's own rounding)
+			const double behind = cl.rho + 0x1p-16 * E + tol;                               // b < 0 needs (C - o).d > -2^-22 |e| |d|
+			const double reach = rk + cl.rho + tol;
+			const uint32_t bit = 1u << k;
+			if(dist <= reach)
+			{ // the grown sphere meets the cell: every direction
+				for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++) row[e] |= bit;
+				continue;
+			}
+			for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++)
+			{
+				const double *w = &cell_dir[3 * (size_t) e];
+				const double cp = (v[0] * w[0] + v[1] * w[1] + v[2] * w[2]) / dist;
+				const double x = v[1] * w[2] - v[2] * w[1], y = v[2] * w[0] - v[0] * w[2], z = v[0] * w[1] - v[1] * w[0];
+				const double sp = std::sqrt(x * x + y * y + z * z) / dist;
+				const double ct = cth[e], st = sth[e];
+				const bool lo0 = cp >= ct;   // phi <= theta
+				const bool hipi = cp <= -ct; // phi + theta >= pi
+				const double cos_lo = lo0 ? 1.0 : cp * ct + sp * st;
+				const double sin_lo = lo0 ? 0.0 : sp * ct - cp * st;
+				const double sin_hi = hipi ? 0.0 : sp * ct + cp * st;
+				const double min_sin = std::max(0.0, std::min(sin_lo, sin_hi));
+				if(dist * cos_lo + behind >= 0.0 && dist * min_sin <= reach) row[e] |= bit;
+			}
+		}
+	}
+	const size_t n_index = (index.size() + 1) & ~(size_t) 1;
+	const size_t n_mask_words = gi_wide ? masks.size() : masks.size() / 2;
+	std::vector<uint32_t> table((n_index + n_mask_words + 3) & ~(size_t) 3, 0u);
+	memcpy(table.data(), index.data(), index.size() * 4);
+	if(gi_wide) memcpy(&table[n_index], masks.data(), masks.size() * 4);
+	else
+		for(size_t e = 0; e < masks.size(); e += 2) table[n_index + e / 2] = masks[e] | masks[e + 1] << 16; // (uint16_t entries, little-endian)
+	gi_mask_word = (uint32_t) n_index;
+	gi_table.swap(table);
 }
 
 // Exact-preserving culling data for the triangle walk (DESIGN.md "Triangle chunks").
@@ -900,6 +1092,24 @@ int skr_scene_get_shadow_masks(const skr_scene *scene, int32_t *n_lights, int32_
 	if(cells) *cells = SKR_SHADOW_CELLS;
 	if(reach2) *reach2 = scene->shadow_reach2;
 	if(masks && !scene->shadow_masks.empty()) memcpy(masks, scene->shadow_masks.data(), scene->shadow_masks.size() * 4);
+	return SKR_OK;
+}
+
+int skr_scene_get_gi_masks(const skr_scene *scene, int32_t *n_words, int32_t *mask_word, int32_t *wide, int32_t *dir_cells, float *grids, uint32_t *table)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(n_words) *n_words = (int32_t) scene->gi_table.size();
+	if(mask_word) *mask_word = (int32_t) scene->gi_mask_word;
+	if(wide) *wide = scene->gi_wide;
+	if(dir_cells) *dir_cells = SKR_GI_DIR_CELLS;
+	if(grids)
+		for(int g = 0; g < 2; g++)
+		{
+			const SkrGiGrid &G = scene->gi_grid[g];
+			const float row[8] = {G.lo[0], G.lo[1], G.lo[2], G.inv, (float) G.n[0], (float) G.n[1], (float) G.n[2], (float) G.base};
+			memcpy(grids + 8 * g, row, sizeof(row));
+		}
+	if(table && !scene->gi_table.empty()) memcpy(table, scene->gi_table.data(), scene->gi_table.size() * 4);
 	return SKR_OK;
 }
 

@@ -59,6 +59,14 @@ struct skr_scene {
 	std::vector<uint32_t> shadow_masks;
 	float shadow_reach2 = 0.0f; // the masks hold for shading points P with fl(|Lp - P|^2) <= shadow_reach2 (every light); other lanes test every sphere
 	void build_shadow_masks();
+	// the GI masks of the node pipeline's closest-hit walk (shadow_cells.h, DESIGN.md "GI masks"): the index words of both grids, then
+	// the masks (uint16_t, or uint32_t where gi_wide), padded to whole 16-byte rows; empty where the walk keeps its plain loop
+	// (no sphere, more than SKR_GI_MAX_SPHERES, triangles)
+	std::vector<uint32_t> gi_table;
+	SkrGiGrid gi_grid[2] = {}; // fine, coarse
+	uint32_t gi_mask_word = 0; // the first word of the masks in gi_table
+	int gi_wide = 0;
+	void build_gi_masks();
 };
 
 // scene.cpp:12-227 replacement.  Returns SKR_OK or SKR_ERR_IO.

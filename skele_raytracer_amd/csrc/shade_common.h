@@ -342,6 +342,25 @@ SKR_DEV bool any_triangle_closer(const SceneView &sv, const RayConst &r, float t
 	return hit;
 }
 
+// The cell (face, i, j) of direction v in a cube map of N x N cells per face (shadow_cells.h addressing), in bounds whatever v holds
+// (NaN -> 0).
+struct CubeCell {
+	int face, i, j;
+};
+template <int N>
+SKR_DEV CubeCell cube_cell(f3 v)
+{
+	const float ax = __builtin_fabsf(v.x), ay = __builtin_fabsf(v.y), az = __builtin_fabsf(v.z);
+	const bool fx = (ax >= ay) && (ax >= az), fy = !fx && (ay >= az);
+	const float m = fx ? ax : (fy ? ay : az), lead = fx ? v.x : (fy ? v.y : v.z);
+	const float a = fx ? v.y : v.x, b = fy || fx ? v.z : v.y;
+	const int face = (fx ? 0 : (fy ? 2 : 4)) + (lead < 0.0f ? 1 : 0);
+	const float inv = __builtin_amdgcn_rcpf(m), h = 0.5f * (float) N, top = (float) (N - 1);
+	const int i = (int) __builtin_fminf(__builtin_fmaxf((a * inv) * h + h, 0.0f), top); // (NaN -> 0)
+	const int j = (int) __builtin_fminf(__builtin_fmaxf((b * inv) * h + h, 0.0f), top);
+	return CubeCell{face, i, j};
+}
+
 // The spheres that may stop the shadow ray of point light l from P (v = Lp - P, the subtraction light_term makes): the cell of v's
 // direction in the light's table (shadow_cells.h; DESIGN.md "Shadow masks").  A lane whose P lies beyond the reach the table was built
 // for, or whose v is not a vector of normal length (zero, NaN, inf), gets every sphere.  The index is in bounds whatever v holds.
@@ -349,16 +368,42 @@ SKR_DEV uint32_t shadow_mask_of(const SceneView &sv, int l, f3 v)
 {
 	const float vv = sqr3(v);
 	const bool ok = (vv <= sv.smask_reach2) && (vv >= 0x1p-98f);
-	const float ax = __builtin_fabsf(v.x), ay = __builtin_fabsf(v.y), az = __builtin_fabsf(v.z);
-	const bool fx = (ax >= ay) && (ax >= az), fy = !fx && (ay >= az);
-	const float m = fx ? ax : (fy ? ay : az), lead = fx ? v.x : (fy ? v.y : v.z);
-	const float a = fx ? v.y : v.x, b = fy || fx ? v.z : v.y;
-	const int face = (fx ? 0 : (fy ? 2 : 4)) + (lead < 0.0f ? 1 : 0);
-	const float inv = __builtin_amdgcn_rcpf(m), h = 0.5f * (float) SKR_SHADOW_CELLS, top = (float) (SKR_SHADOW_CELLS - 1);
-	const int i = (int) __builtin_fminf(__builtin_fmaxf((a * inv) * h + h, 0.0f), top); // (NaN -> 0)
-	const int j = (int) __builtin_fminf(__builtin_fmaxf((b * inv) * h + h, 0.0f), top);
-	const uint32_t mask = sv.smask[(l * 6 + face) * (SKR_SHADOW_CELLS * SKR_SHADOW_CELLS) + i * SKR_SHADOW_CELLS + j];
+	const CubeCell c = cube_cell<SKR_SHADOW_CELLS>(v);
+	const uint32_t mask = sv.smask[(l * 6 + c.face) * (SKR_SHADOW_CELLS * SKR_SHADOW_CELLS) + c.i * SKR_SHADOW_CELLS + c.j];
 	return ok ? mask : sv.smask_all;
+}
+
+// ---- GI masks (shadow_cells.h; DESIGN.md "GI masks"): the spheres a GI child ray may have as candidates ----
+// The row of masks of origin o: its cell in the fine grid, else in the coarse one; -1 = none (outside both, or not finite).  Only a lane
+// inside a grid reads its index word.
+SKR_DEV int gi_grid_cell(const int32_t *index, const SkrGiGrid &g, f3 o)
+{
+	const float fx = (o.x - g.lo[0]) * g.inv, fy = (o.y - g.lo[1]) * g.inv, fz = (o.z - g.lo[2]) * g.inv;
+	const bool in = (fx >= 0.0f) && (fx < g.n_f[0]) && (fy >= 0.0f) && (fy < g.n_f[1]) && (fz >= 0.0f) && (fz < g.n_f[2]); // (NaN: out)
+	int row = -1;
+	if(in) row = index[g.base + ((int) fz * g.n[1] + (int) fy) * g.n[0] + (int) fx];
+	return row;
+}
+SKR_DEV int gi_origin_row(const RenderParams &p, f3 o)
+{
+	int row = gi_grid_cell(p.gi_index, p.gi_grid[0], o);
+	if(row < 0) row = gi_grid_cell(p.gi_index, p.gi_grid[1], o); // (the coarse grid only where the fine one has no row)
+	return row;
+}
+// The union of the masks of children d0 and (second) d1 from origin row `row`; every sphere where the row is -1 or a direction is not a
+// vector of moderate length (zero, tiny, huge, NaN, inf: the margins are derived for |d|^2 in [2^-40, 2^40]).
+SKR_DEV uint32_t gi_cands(const RenderParams &p, int row, f3 d0, f3 d1, bool second)
+{
+	const float a0 = sqr3(d0), a1 = sqr3(d1);
+	const bool ok = (row >= 0) && (a0 >= 0x1p-40f) && (a0 <= 0x1p40f) && (!second || ((a1 >= 0x1p-40f) && (a1 <= 0x1p40f)));
+	const uint32_t base = ok ? (uint32_t) row * SKR_GI_ROW_ENTRIES : 0u;
+	const CubeCell c0 = cube_cell<SKR_GI_DIR_CELLS>(d0), c1 = cube_cell<SKR_GI_DIR_CELLS>(d1);
+	const uint32_t e0 = base + (uint32_t) ((c0.face * SKR_GI_DIR_CELLS + c0.i) * SKR_GI_DIR_CELLS + c0.j);
+	const uint32_t e1 = base + (uint32_t) ((c1.face * SKR_GI_DIR_CELLS + c1.i) * SKR_GI_DIR_CELLS + c1.j);
+	const uint16_t *m16 = reinterpret_cast<const uint16_t *>(p.gi_masks);
+	uint32_t m = p.gi_wide ? p.gi_masks[e0] : (uint32_t) m16[e0];
+	if(second) m |= p.gi_wide ? p.gi_masks[e1] : (uint32_t) m16[e1]; // (no second child: no second load)
+	return ok ? m : p.gi_all;
 }
 
 // utils.h:42-58: any sphere with 1 < t < inf along the (unbounded) shadow ray; two lights at a

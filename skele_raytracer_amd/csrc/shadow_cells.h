@@ -2,6 +2,8 @@
 // (shade_common.h shadow_mask_of).  DESIGN.md "Shadow masks" has the derivation of the margins.
 #pragma once
 
+#include <stdint.h>
+
 /* Cells per edge of one cube face: a light's table has 6 x N x N cells of one uint32_t each (N = 32: 6144 cells, 24 KB).  Cell
  * (face, i, j) of a direction v: the face is the axis of v's largest |component| (ties: x before y before z) and its sign,
  * face = 2 axis + (v[axis] < 0); (i, j) = the cells of v's other two components in axis order, divided by |v[axis]|, on
@@ -12,3 +14,21 @@
 #endif
 #define SKR_SHADOW_TABLE_WORDS (6 * SKR_SHADOW_CELLS * SKR_SHADOW_CELLS) /* per light */
 #define SKR_SHADOW_MAX_SPHERES 32 /* one bit per sphere; more spheres keep the plain loop */
+
+/* GI masks (DESIGN.md "GI masks"): the node pipeline's closest-hit walk of a GI child ray visits only the spheres named by the mask
+ * of (the cell of its origin, the cell of its direction).  Origins are looked up in a fine grid over the small spheres, then in a
+ * coarse grid around it (SkrGiGrid: cubic cells, cell (i, j, k) of a point o = the integer parts of (o - lo) * inv, each in [0, n);
+ * index[base + (k n1 + j) n0 + i] = the cell's row of masks, -1 = none).  A row holds the masks of 6 x G x G direction cells, G =
+ * SKR_GI_DIR_CELLS, addressed like a light's shadow table; uint16_t masks where the scene has at most 16 spheres, else uint32_t.
+ * Bit k: a ray from any origin of the cell along any direction of the direction cell may have D >= 0 and b < 0 for sphere k. */
+#ifndef SKR_GI_DIR_CELLS
+#define SKR_GI_DIR_CELLS 16
+#endif
+#define SKR_GI_ROW_ENTRIES (6 * SKR_GI_DIR_CELLS * SKR_GI_DIR_CELLS) /* masks per origin cell */
+#define SKR_GI_MAX_SPHERES 32
+#define SKR_GI_MAX_BYTES (2u << 20) /* the whole table (index and masks): small enough to stay in L2 */
+struct SkrGiGrid {
+	float lo[3], inv; /* lo: the grid's corner; inv: 1 / the cell's edge */
+	float n_f[3];     /* n as floats (the device's range test) */
+	int32_t n[3], base;
+};

@@ -75,7 +75,14 @@ SKR_DEV void best_resolve(const SceneView &sv, f3 o, f3 d, float four_a, BestSta
 	}
 }
 
-SKR_DEV void closest_pair_deferred(const SceneView &sv, f3 o, f3 d0, f3 d1, bool second, const RayPair &rp, BestState &s0, BestState &s1)
+// With GI masks (`masked`, wave-uniform): `cand` = the union of the lane's two masks (shade_common.h gi_cands).  A sphere outside a
+// ray's mask provably fails the candidate test below (its D < 0 or b >= 0), so each lane walks only its own candidates, lowest index
+// first, rows from LDS: best_update sees the same candidates in the same order, and every decision is the one of the loop over every
+// sphere.  A wave with a lane that names every sphere (no mask for it) takes that loop.  GIM = false: the loop over every sphere only,
+// compiled without any of the masked walk (kernels that run without masks keep their code).
+template <bool GIM>
+SKR_DEV void closest_pair_deferred(const SceneView &sv, f3 o, f3 d0, f3 d1, bool second, const RayPair &rp, BestState &s0, BestState &s1,
+								   uint32_t cand, uint32_t all)
 {
 	s0 = BestState{-1, __builtin_inff(), __builtin_inff(), __builtin_inff(), 0.0f, 0.0f};
 	s1 = s0;
@@ -101,15 +108,53 @@ SKR_DEV void closest_pair_deferred(const SceneView &sv, f3 o, f3 d0, f3 d1, bool
 			best_update(s1, acc1, i, l1, h1, b.y, D.y);
 		}
 	};
-	sphere_rows(sv, test);
+	bool masked = GIM;
+	if constexpr(GIM)
+	{
+#if defined(SKR_DIAG) && SKR_DIAG
+		{ // the gate of DESIGN.md "GI masks": spheres the wave's lanes name together, the most one lane names, the sum over lanes
+			uint32_t any = 0, most = 0, sum = 0;
+			for(int k = 0; k < 32; k++)
+			{
+				const unsigned long long bk = __ballot((cand >> k) & 1u);
+				any += bk ? 1u : 0u;
+				sum += (uint32_t) __popcll(bk);
+			}
+			for(uint32_t c = 1; c <= 32; c++) most += __any((uint32_t) __popc(cand) >= c) ? 1u : 0u;
+			DIAG_WAVE(25, 1);
+			DIAG_WAVE(26, any);
+			DIAG_WAVE(27, most);
+			DIAG_WAVE(28, sv.ns);
+			DIAG_WAVE(29, sum);
+			DIAG_LANES(30);
+			DIAG_WAVE(31, __any(cand == all) ? 1u : 0u);
+		}
+#endif
+		masked = !__any(cand == all);
+	}
+	if(GIM && masked)
+	{
+		uint32_t rest = cand;
+		while(rest)
+		{
+			const int i = __builtin_ctz(rest);
+			test(sv.geom[i], i); // (the lanes' rows differ: LDS)
+			rest &= rest - 1u;
+		}
+	}
+	else sphere_rows(sv, test);
 	best_resolve(sv, o, d0, rp.four_a.x, s0);
 	if(second) best_resolve(sv, o, d1, rp.four_a.y, s1);
 }
 
 
-SKR_DEV void closest_pair(const SceneView &sv, f3 o, f3 d0, f3 d1, bool second, const RayPair &rp, BestState &s0, BestState &s1)
+// GIM: the kernel runs with GI masks (p.gi_index set; the launcher picks it); `row` = the lane's origin row (shade_common.h
+// gi_origin_row), -1 = none
+template <bool GIM>
+SKR_DEV void closest_pair(const SceneView &sv, const RenderParams &p, int row, f3 o, f3 d0, f3 d1, bool second, const RayPair &rp, BestState &s0, BestState &s1)
 {
-	closest_pair_deferred(sv, o, d0, d1, second, rp, s0, s1);
+	const uint32_t cand = GIM ? gi_cands(p, row, d0, d1, second) : 0u;
+	closest_pair_deferred<GIM>(sv, o, d0, d1, second, rp, s0, s1, cand, p.gi_all);
 }
 
 // the image row of row `orow` of the compact output (include/skr.h skr_render_tiles / skr_render_tile_list); >= height: no such row

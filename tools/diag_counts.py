@@ -21,10 +21,15 @@ names = ["closest-pair iterations", "closest-pair candidate paths", "  lanes in 
          "  lanes in them", "exact-root fallbacks (wave events)", "bracket overlaps -> exact loop (wave events)", "leaf shading batches", "  hits in them",
          "activation batches", "  records in them", "closest-pair candidate RAYS", "  accepted", "shadow candidate RAYS", "  occluders found", "  closest-pair candidates a t2 <= 1 pre-test rejects", "  closest-pair candidate paths left with it",
          "masked shadow-pair calls (wave events)", "  (a) spheres named by some lane, summed", "  (b) most spheres one lane names, summed", "  ns, summed",
-         "  spheres named, summed over lanes", "  lanes in them"] + ["counter %d" % i for i in range(25, 32)]
+         "  spheres named, summed over lanes", "  lanes in them",
+         "masked closest-pair calls (wave events)", "  (a) spheres named by some lane, summed", "  (b) most spheres one lane names, summed", "  ns, summed",
+         "  spheres named, summed over lanes", "  lanes in them", "  calls with a lane that names every sphere"]
 print(r.kernel_variant())
 for n, v in zip(names, out):
     if v: print("%-48s %d" % (n, v))
 if out[19]:  # the gate of DESIGN.md "Shadow masks": per masked shadow-pair call of a wave, against ns
     print("per masked shadow-pair call: (a) %.2f  (b) %.2f  lane mean %.2f  of ns = %.2f"
           % (out[20] / out[19], out[21] / out[19], out[23] / max(out[24], 1), out[22] / out[19]))
+if out[25]:  # the gate of DESIGN.md "GI masks": per masked closest-pair call of a wave, against ns
+    print("per masked closest-pair call: (a) %.2f  (b) %.2f  lane mean %.2f  of ns = %.2f; waves walking every sphere %.1f %%"
+          % (out[26] / out[25], out[27] / out[25], out[29] / max(out[30], 1), out[28] / out[25], 100.0 * out[31] / out[25]))
