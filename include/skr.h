@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SKR_ABI_VERSION 6 /* 6: skr_scene_get_gi_masks; 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
+#define SKR_ABI_VERSION 7 /* 7: skr_ray, skr_hit, skr_trace_rays, skr_camera_rays (ray queries); 6: skr_scene_get_gi_masks; 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
 
 typedef enum {
 	SKR_OK = 0,
@@ -318,6 +318,43 @@ int skr_shard_lpt(const uint64_t *cost, uint32_t n_tiles, uint32_t world, uint32
 int skr_shard_by_cost(const uint64_t *cost, uint32_t n_tiles, uint32_t world, uint32_t *slot_of_tile);
 int skr_shard_plan(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, uint32_t world, uint32_t *slot_of_tile);
 int skr_shard_deinterleave_map_host(const uint8_t *gathered, uint8_t *frame, int32_t width, int32_t height, uint32_t tile_rows, const uint32_t *slot_of_tile);
+
+/* ---- ray queries (new; DESIGN.md "Ray queries"): caller-supplied rays traced against a renderer's scene ----
+ * The hit rule is the renderer's own closest hit under skr_options.shade_triangles:
+ *   - a sphere is accepted when 1 < t < inf (raytrace.h:152-165); t is the binary64 near root the renderer computes (utils.h:87-110);
+ *   - a triangle is accepted when utils.h:181-213 passes with t > 0 and its file index is not the ray's ignore_triangle;
+ *   - the smallest t wins; a triangle wins against a sphere only with a strictly smaller t; among triangles with equal t the lower
+ *     file index wins;
+ *   - a winner with t >= tmax makes the result a miss; fog volumes are not surfaces.
+ * n is the shading normal of the general level pipeline: normalize(P - C) with P = o + d t (sphere), normalize(cross(v1 - v0, v2 - v0))
+ * turned against d (triangle).  Rays with a non-finite or zero-length direction get an unspecified result; they never change
+ * the results of other rays.  Neither call changes anything a render or a counter reads (work counters, kernel timing,
+ * skr_kernel_variant). */
+typedef struct {              /* 32 bytes, two float4; DEVICE arrays of it are 16-byte aligned */
+	float o[3];
+	float tmax;               /* hits with t >= tmax are ignored; +inf = no limit */
+	float d[3];               /* need not be unit length; t is in units of d, as in the renderer */
+	int32_t ignore_triangle;  /* file index of a triangle this ray may not hit (the surface it leaves), -1 = none */
+} skr_ray;
+
+typedef struct {              /* 32 bytes */
+	float t;                  /* +inf on a miss */
+	int32_t kind;             /* 0 miss, 1 sphere, 2 triangle */
+	int32_t index;            /* sphere index / triangle file index, -1 on a miss */
+	float n[3];               /* shading normal of the hit (see above); 0 on a miss */
+	int32_t reserved[2];      /* 0 */
+} skr_hit;
+
+#define SKR_TRACE_ANY_HIT 1u
+/* Trace n rays (DEVICE array) against the renderer's scene, asynchronously on `stream` (a hipStream_t, NULL = default stream).
+ * flags = 0: d_out is a DEVICE skr_hit[n] (16-byte aligned).  SKR_TRACE_ANY_HIT: d_out is a DEVICE int32_t[n]: 1 exactly where the
+ * closest-hit result would not be a miss, else 0.  n == 0: SKR_OK, nothing is launched.  Null pointers, misaligned arrays and
+ * unknown flags: SKR_ERR_ARG. */
+int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t flags, void *d_out, void *stream);
+/* The primary rays of sample `sample` of a frame with options `opt` (the AA index, < grid_size^2; 0 with grid_size == 0, the pixel
+ * centres) into a DEVICE skr_ray[height][width]: o = the camera position, d = bit for bit the direction the renderer traces for that
+ * pixel and sample (main.cpp:140-182), tmax = +inf, ignore_triangle = -1.  Asynchronous on `stream`. */
+int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, skr_ray *d_rays, void *stream);
 
 /* ---- image file: replaces the inline writer main.cpp:199-211 ---- */
 int skr_write_ppm(const char *path, uint32_t width, uint32_t height, const uint8_t *rgb);

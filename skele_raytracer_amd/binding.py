@@ -16,6 +16,7 @@ EXPORTED_SYMBOLS = [
     "skr_rccl_available", "skr_multi_create", "skr_multi_destroy", "skr_multi_device_count", "skr_multi_renderer", "skr_multi_render_frame",
     "skr_multi_render_frame_host", "skr_comm_unique_id", "skr_comm_create", "skr_comm_destroy", "skr_comm_render_frame", "skr_comm_render_frame_async", "skr_comm_flush", "skr_comm_frame_to_host",
     "skr_shard_tiles_per_rank", "skr_shard_deinterleave_host", "skr_shard_lpt", "skr_shard_by_cost", "skr_shard_plan", "skr_shard_deinterleave_map_host", "skr_multi_render_frame_async", "skr_multi_flush",
+    "skr_trace_rays", "skr_camera_rays",
 ]
 
 
@@ -140,6 +141,8 @@ def lib():
     L.skr_shard_tiles_per_rank.argtypes = [C.c_int32, C.c_uint32, C.c_uint32]
     L.skr_shard_tiles_per_rank.restype = C.c_uint32
     L.skr_shard_deinterleave_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32]
+    L.skr_trace_rays.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.skr_camera_rays.argtypes = [vp, C.POINTER(COptions), C.c_uint32, vp, vp]
     _lib = L
     return L
 
@@ -477,6 +480,75 @@ class Renderer:
     @staticmethod
     def kernel_variant():
         return (lib().skr_kernel_variant() or b"").decode()
+
+    def trace(self, rays, any_hit=False):
+        """Trace rays (float32 [n, 8] on this device, the include/skr.h skr_ray layout: make_rays) against the scene, on torch's
+        current stream (include/skr.h skr_trace_rays).  Returns Hits(t, kind, index, normal): views of one float32 [n, 8] buffer in the
+        skr_hit layout (t float32 [n], kind and index int32 [n], normal float32 [n, 3]); any_hit=True: int32 [n], 1 where the closest
+        hit would not be a miss."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or rays.device != dev:
+            raise SkrError("trace: rays must be a float32 [n, 8] tensor on %s (make_rays)" % dev)
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        if n >= 1 << 32:
+            raise SkrError("trace: at most 2^32 - 1 rays per call")
+        out = torch.empty(n, dtype=torch.int32, device=dev) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=dev)
+        if n == 0:  # (an empty tensor has no address to pass)
+            return out if any_hit else Hits(out[:, 0], out.view(torch.int32)[:, 1], out.view(torch.int32)[:, 2], out[:, 3:6], out)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib().skr_trace_rays(self.h, rays.data_ptr(), n, TRACE_ANY_HIT if any_hit else 0, out.data_ptr(), stream), "skr_trace_rays")
+        if any_hit:
+            return out
+        ints = out.view(torch.int32)
+        return Hits(out[:, 0], ints[:, 1], ints[:, 2], out[:, 3:6], out)
+
+    def camera_rays(self, opt, sample=0):
+        """The primary rays of AA sample `sample` of a frame with options opt (include/skr.h skr_camera_rays): float32 [h, w, 8] on this
+        device, on torch's current stream.  trace(camera_rays(opt).view(-1, 8)) gives the frame's depth, id and normal buffers."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((opt.height, opt.width, 8), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib().skr_camera_rays(self.h, C.byref(opt.c), sample, out.data_ptr(), stream), "skr_camera_rays")
+        return out
+
+
+TRACE_ANY_HIT = 1  # include/skr.h SKR_TRACE_ANY_HIT
+
+
+class Hits:
+    """The result of Renderer.trace: views of one float32 [n, 8] buffer `raw` in the include/skr.h skr_hit layout."""
+
+    def __init__(self, t, kind, index, normal, raw):
+        self.t, self.kind, self.index, self.normal, self.raw = t, kind, index, normal, raw
+
+    def __iter__(self):
+        return iter((self.t, self.kind, self.index, self.normal))
+
+
+def make_rays(origins, directions, tmax=None, ignore_triangle=None, device=None):
+    """Pack rays into a CUDA float32 [n, 8] tensor in the include/skr.h skr_ray layout: origins and directions [n, 3] (tensors or
+    arrays); tmax (scalar or [n]; None = +inf: no limit); ignore_triangle (scalar or [n] file indices; None = -1: none).  The tensor
+    lives on `device` (default: the origins' CUDA device, else the current one)."""
+    import torch
+    if device is None:
+        device = origins.device if isinstance(origins, torch.Tensor) and origins.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    o = torch.as_tensor(origins, dtype=torch.float32, device=device).reshape(-1, 3)
+    d = torch.as_tensor(directions, dtype=torch.float32, device=device).reshape(-1, 3)
+    n = o.shape[0]
+    if d.shape[0] != n:
+        raise SkrError("make_rays: %d origins and %d directions" % (n, d.shape[0]))
+    rays = torch.empty((n, 8), dtype=torch.float32, device=device)
+    rays[:, 0:3] = o
+    rays[:, 3] = float("inf") if tmax is None else torch.as_tensor(tmax, dtype=torch.float32, device=device).expand(n)
+    rays[:, 4:7] = d
+    ign = -1 if ignore_triangle is None else torch.as_tensor(ignore_triangle, dtype=torch.int32, device=device).expand(n)
+    rays.view(torch.int32)[:, 7] = ign
+    return rays
 
 
 COMM_ID_BYTES = 128

@@ -43,6 +43,9 @@ struct skr_renderer {
 	int gi_wide = 0;
 	int n_chunks = 0, chunk_size = 0, cones = 0;
 	size_t chunk_stride = 0;
+	size_t off_trace = 0;     // the ray queries' tree (skr_scene::trace_chunks, SKR_CULL_LEVELS sets of chunk_stride rows), 0 = none
+	float trace_ball[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+	int trace_cones = 0;
 	unsigned long long *d_counters = nullptr;
 	unsigned long long *d_snap = nullptr; // skr_renderer_kernel_work: the work counters in front of and behind the dominant kernel of the last timed launch
 	unsigned long long *d_tri_work = nullptr; // 256 x {culling-sphere tests, triangle tests} executed by the triangle walks (skr_renderer_read_triangle_work)
@@ -153,7 +156,11 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	r->gi_grid[1] = scene->gi_grid[1];
 	r->gi_mask_word = scene->gi_mask_word;
 	r->gi_wide = scene->gi_wide;
-	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog + nsm + ngi;
+	const size_t ntc = scene->info.n_triangles ? scene->trace_chunks.size() : 0; // rows of the ray queries' tree
+	r->off_trace = ntc ? r->off_fog + 2 * nfog + nsm + ngi : 0;
+	memcpy(r->trace_ball, scene->trace_ball, sizeof r->trace_ball);
+	r->trace_cones = scene->trace_any_cone ? 1 : 0;
+	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog + nsm + ngi + ntc;
 	std::vector<skr_f4> blob(total + 16); // (+ 16 rows: the sphere loops ask for the rows of a trip ahead without a bounds test, shade_common.h sphere_rows)
 	if(ns)
 	{
@@ -183,6 +190,7 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	}
 	if(nsm) memcpy(&blob[r->off_smask], scene->shadow_masks.data(), scene->shadow_masks.size() * 4);
 	if(ngi) memcpy(&blob[r->off_gi], scene->gi_table.data(), scene->gi_table.size() * 4);
+	if(ntc) memcpy(&blob[r->off_trace], scene->trace_chunks.data(), ntc * 16);
 	r->blob_bytes = blob.size() * 16;
 	hipError_t e = hipMalloc((void **) &r->d_blob, blob.size() * 16);
 	if(e == hipSuccess) e = hipMemcpy(r->d_blob, blob.data(), blob.size() * 16, hipMemcpyHostToDevice);
@@ -238,6 +246,7 @@ int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 	r->off_smask = src->off_smask; r->shadow_reach2 = src->shadow_reach2;
 	r->off_gi = src->off_gi; r->gi_grid[0] = src->gi_grid[0]; r->gi_grid[1] = src->gi_grid[1]; r->gi_mask_word = src->gi_mask_word; r->gi_wide = src->gi_wide;
 	r->n_chunks = src->n_chunks; r->chunk_size = src->chunk_size; r->cones = src->cones; r->chunk_stride = src->chunk_stride;
+	r->off_trace = src->off_trace; memcpy(r->trace_ball, src->trace_ball, sizeof r->trace_ball); r->trace_cones = src->trace_cones;
 	r->d_counters = src->d_counters;
 	r->d_tri_work = src->d_tri_work;
 	r->lds_limit = src->lds_limit;
@@ -295,6 +304,20 @@ static int check_options(const skr_options *opt)
 	return SKR_OK;
 }
 
+// main.cpp:134-137, hoisted: identical float/double expressions evaluated once; the camera of camera.h:8-32 (what primary_ray() reads)
+static void camera_invariants(const skr_renderer *r, const skr_options *opt, RenderParams &p)
+{
+	p.inv_width = 1 / float(opt->width);
+	p.inv_height = 1 / float(opt->height);
+	p.aspect = opt->width / float(opt->height);
+	p.angle = (float) tan(M_PI * 0.5 * opt->fov / 180.);
+	const float *c = r->info.camera;
+	p.cam_pos = f3{c[0], c[1], c[2]};
+	p.cam_dir = f3{c[3], c[4], c[5]};
+	p.cam_up = f3{c[6], c[7], c[8]};
+	p.cam_right = f3{c[9], c[10], c[11]};
+}
+
 // one frame (one pass of a progressive render) of the tiles first_tile, first_tile + tile_stride, ...
 // the tiles of a launch: first, first + stride, ... (table == nullptr) or the n_slots entries of a device table (skr_render_tile_list)
 struct TileSel {
@@ -334,16 +357,8 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.out_rows = n_tiles * tile_rows;
 	p.band_row0 = 0;
 	p.band_rows = p.out_rows;
-	// main.cpp:134-137, hoisted: identical float/double expressions evaluated once
-	p.inv_width = 1 / float(opt->width);
-	p.inv_height = 1 / float(opt->height);
-	p.aspect = opt->width / float(opt->height);
-	p.angle = (float) tan(M_PI * 0.5 * opt->fov / 180.);
+	camera_invariants(r, opt, p);
 	const float *c = r->info.camera;
-	p.cam_pos = f3{c[0], c[1], c[2]};
-	p.cam_dir = f3{c[3], c[4], c[5]};
-	p.cam_up = f3{c[6], c[7], c[8]};
-	p.cam_right = f3{c[9], c[10], c[11]};
 	p.background = f3{r->info.background[0], r->info.background[1], r->info.background[2]};
 	p.n_spheres = r->info.n_spheres;
 	p.n_tris = r->info.n_triangles;
@@ -845,6 +860,59 @@ int skr_render_frame_host(skr_renderer *r, const skr_options *opt, uint8_t *h_rg
 }
 
 const char *skr_kernel_variant(void) { return g_variant; }
+
+// ---- ray queries (trace_rays.hip): they read the scene blob and write only the caller's arrays ----
+int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t flags, void *d_out, void *stream)
+{
+	const bool any_hit = (flags & SKR_TRACE_ANY_HIT) != 0;
+	if(!r || !d_rays || !d_out || (flags & ~SKR_TRACE_ANY_HIT) || ((uintptr_t) d_rays & 15) || ((uintptr_t) d_out & (any_hit ? 3 : 15)))
+	{
+		skr_set_error("skr_trace_rays: bad argument (null or misaligned array, or unknown flags 0x%x)", flags);
+		return SKR_ERR_ARG;
+	}
+	if(n == 0) return SKR_OK;
+	SKR_HIP(hipSetDevice(r->device));
+	TraceScene s{};
+	s.geom = r->d_blob;
+	s.tris = r->d_blob + r->off_tris;
+	s.ns = r->info.n_spheres;
+	s.nt = r->info.n_triangles;
+	s.chunk = r->chunk_size;
+	s.stride = r->chunk_stride;
+	s.nchunks = (r->off_trace && !r->sw.no_cull) ? r->n_chunks : 0;
+	s.chunks = r->off_trace ? r->d_blob + r->off_trace : r->d_blob;
+	s.cones = (r->trace_cones && !r->sw.no_cones) ? 1 : 0;
+	s.ball = make_float4(r->trace_ball[0], r->trace_ball[1], r->trace_ball[2], r->trace_ball[3]);
+	SKR_HIP(skr_launch_trace(s, reinterpret_cast<const float4 *>(d_rays), n, any_hit, d_out, (hipStream_t) stream));
+	return SKR_OK;
+}
+
+int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, skr_ray *d_rays, void *stream)
+{
+	if(!r || !opt || !d_rays || ((uintptr_t) d_rays & 15))
+	{
+		skr_set_error("skr_camera_rays: bad argument (null or misaligned array)");
+		return SKR_ERR_ARG;
+	}
+	int rc = check_options(opt);
+	if(rc != SKR_OK) return rc;
+	if(sample >= (uint32_t) (opt->grid_size > 0 ? opt->grid_size * opt->grid_size : 1))
+	{
+		skr_set_error("skr_camera_rays: sample %u of a frame with %d AA samples", sample, opt->grid_size > 0 ? opt->grid_size * opt->grid_size : 1);
+		return SKR_ERR_ARG;
+	}
+	SKR_HIP(hipSetDevice(r->device));
+	RenderParams p{};
+	p.width = opt->width;
+	p.height = opt->height;
+	camera_invariants(r, opt, p);
+	p.grid_size = opt->grid_size;
+	p.seed_lo = (uint32_t) opt->seed;
+	p.seed_hi = (uint32_t) (opt->seed >> 32);
+	p.aa_index = sample;
+	SKR_HIP(skr_launch_camera_rays(p, reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream));
+	return SKR_OK;
+}
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {

@@ -92,6 +92,17 @@ hipError_t skr_launch_wave(const RenderParams &p, size_t lds, hipStream_t stream
 hipError_t skr_launch_primary(const RenderParams &p, dim3 grid, size_t lds, hipStream_t stream);
 hipError_t skr_launch_resolve(const RenderParams &p, hipStream_t stream);
 hipError_t skr_launch_camec(const float4 *geom, int ns, f3 cam_pos, float4 *out, hipStream_t stream);
+// trace_rays.hip: the ray queries (include/skr.h skr_trace_rays, skr_camera_rays).  Not a render: no plan, no counters, no timing.
+struct TraceScene {
+	const float4 *geom;   // sphere rows {centre, r^2} (HBM; the rows behind them are readable: the blob's padding)
+	const float4 *tris;   // device triangles, 3 float4 each (scene_host.h)
+	const float4 *chunks; // the trace tree (scene_host.h trace_chunks): SKR_CULL_LEVELS sets of `stride` float4
+	size_t stride;
+	int32_t ns, nt, nchunks, chunk, cones;
+	float4 ball;          // {centre, radius}: the tree holds for rays that start in it
+};
+hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream);
+hipError_t skr_launch_camera_rays(const RenderParams &p, float4 *rays, hipStream_t stream);
 // accumulate.hip
 hipError_t skr_launch_accumulate(float *acc, const float *frame, size_t n, int first, hipStream_t stream);
 hipError_t skr_launch_resolve_accumulated(const float *acc, uint32_t passes, uint32_t width, uint32_t out_rows, uint32_t height, uint32_t tile_rows,

@@ -473,6 +473,43 @@ void skr_scene::build_triangle_chunks()
 		tri_chunk_stride = one.size();
 		tri_chunks.insert(tri_chunks.end(), one.begin(), one.end());
 	}
+	// the ray queries' ball: around the bounding box of every point a renderer's ray can start at or hit, twice that box's half diagonal
+	double lo[3] = {info.camera[0], info.camera[1], info.camera[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+	auto grow = [&](double x, double y, double z, double r) {
+		const double p[3] = {x, y, z};
+		for(int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
+	};
+	for(int i = 0; i < info.n_spheres; i++)
+	{
+		const float *s = &raw_spheres[(size_t) i * 14];
+		grow(s[0], s[1], s[2], std::fabs((double) s[3]));
+	}
+	for(int i = 0; i < info.n_triangles; i++)
+	{ // the accept region (v0, v0 - e1, v0 + e2)
+		const skr_f4 v0 = tris[3 * i], e1 = tris[3 * i + 1], e2 = tris[3 * i + 2];
+		grow(v0.x, v0.y, v0.z, 0);
+		grow((double) v0.x - e1.x, (double) v0.y - e1.y, (double) v0.z - e1.z, 0);
+		grow((double) v0.x + e2.x, (double) v0.y + e2.y, (double) v0.z + e2.z, 0);
+	}
+	const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]), cz = 0.5 * (lo[2] + hi[2]);
+	const double half = 0.5 * std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+	trace_ball[0] = (float) cx;
+	trace_ball[1] = (float) cy;
+	trace_ball[2] = (float) cz;
+	trace_ball[3] = (float) (2 * half + 1e-3);
+	// the device tests fl(|o - c|^2) <= fl(r)^2 against the float centre: the tree is built for a ball wider by far more than that rounding
+	const double ball[4] = {trace_ball[0], trace_ball[1], trace_ball[2], (double) trace_ball[3] * 1.001 + 1e-3};
+	trace_chunks.clear();
+	const bool render_cone = tri_any_cone; // (the flag the builder raises belongs to the renderer's tree)
+	tri_any_cone = false;
+	for(int level = 0; level < SKR_CULL_LEVELS; level++)
+	{
+		std::vector<skr_f4> one;
+		build_triangle_chunk_level(dmax[level], one, ball);
+		trace_chunks.insert(trace_chunks.end(), one.begin(), one.end());
+	}
+	trace_any_cone = tri_any_cone;
+	tri_any_cone = render_cone;
 }
 
 // Grazing rays are what makes the slack above large: |det| = |d . (e1 x e2)| may be as small as 1e-5.  Where a
@@ -519,7 +556,7 @@ void ball_entries(const Ball &b, skr_f4 &A, skr_f4 &B)
 }
 } // namespace
 
-void skr_scene::build_triangle_chunk_level(double d_max, std::vector<skr_f4> &out)
+void skr_scene::build_triangle_chunk_level(double d_max, std::vector<skr_f4> &out, const double *origin_ball)
 {
 	const int nt = info.n_triangles;
 	const double eps = 5.9604644775390625e-08; // 2^-24
@@ -527,8 +564,9 @@ void skr_scene::build_triangle_chunk_level(double d_max, std::vector<skr_f4> &ou
 	// where rays can start: the camera, or on a sphere (GI children, raytrace.h:128)
 	struct Org { double x, y, z, r; };
 	std::vector<Org> orgs;
-	orgs.push_back({info.camera[0], info.camera[1], info.camera[2], 1e-3});
-	for(int i = 0; i < info.n_spheres; i++)
+	if(origin_ball) orgs.push_back({origin_ball[0], origin_ball[1], origin_ball[2], origin_ball[3]});
+	else orgs.push_back({info.camera[0], info.camera[1], info.camera[2], 1e-3});
+	for(int i = 0; i < info.n_spheres && !origin_ball; i++)
 	{
 		const float *s = &raw_spheres[(size_t) i * 14];
 		orgs.push_back({s[0], s[1], s[2], std::fabs((double) s[3]) + 1e-3});

@@ -53,7 +53,14 @@ struct skr_scene {
 	void build_triangle_chunks();
 	std::vector<int> tri_order; // tris[3*i] holds triangle tri_order[i] of the file
 	void build_triangle_materials();
-	void build_triangle_chunk_level(double d_max, std::vector<skr_f4> &out);
+	// origin_ball (x, y, z, radius) or null: the rays start anywhere in that ball instead of at the camera or on a sphere
+	void build_triangle_chunk_level(double d_max, std::vector<skr_f4> &out, const double *origin_ball = nullptr);
+	// the same tree for the ray queries (skr_trace_rays): SKR_CULL_LEVELS sets of tri_chunk_stride entries that hold for rays starting
+	// anywhere in the ball trace_ball = {centre, radius} (twice the radius of a ball around the camera, the spheres and the triangles'
+	// accept regions); the kernel walks them for a wave whose rays all start inside it, and every triangle otherwise
+	std::vector<skr_f4> trace_chunks;
+	float trace_ball[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+	bool trace_any_cone = false;
 	// the shadow masks of the level pipelines' shadow walk (shadow_cells.h, DESIGN.md "Shadow masks"): SKR_SHADOW_TABLE_WORDS per point
 	// light, in light order; empty where the walk keeps its plain loop (no sphere, more than SKR_SHADOW_MAX_SPHERES, a directional light)
 	std::vector<uint32_t> shadow_masks;
