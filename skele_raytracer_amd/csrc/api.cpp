@@ -41,6 +41,7 @@ struct skr_renderer {
 	SkrGiGrid gi_grid[2] = {};
 	uint32_t gi_mask_word = 0;
 	int gi_wide = 0;
+	size_t gi_surface_word = 0; // the surface patches' headers (skr_scene::gi_surface), in words from off_gi; 0 = none
 	int n_chunks = 0, chunk_size = 0, cones = 0;
 	size_t chunk_stride = 0;
 	size_t off_trace = 0;     // the ray queries' tree (skr_scene::trace_chunks, SKR_CULL_LEVELS sets of chunk_stride rows), 0 = none
@@ -82,6 +83,7 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_FLAT")) sw.flat = atoi(e) > 0 ? 1 : -1;
 	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_GI_MASK")) sw.gi_mask = atoi(e) > 0 ? 1 : 0;
+	if(const char *e = getenv("SKR_GI_SURFACE")) sw.gi_surface = atoi(e) > 0 ? 1 : 0;
 }
 
 // (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
@@ -150,7 +152,11 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	const size_t nsm = (scene->shadow_masks.size() + 3) / 4; // rows of the shadow masks
 	r->off_smask = nsm ? r->off_fog + 2 * nfog : 0;
 	r->shadow_reach2 = scene->shadow_reach2;
-	const size_t ngi = scene->gi_table.size() / 4; // rows of the GI masks (whole rows: scene_host.cpp build_gi_masks)
+	// rows of the GI masks (whole rows: scene_host.cpp build_gi_masks), with the surface patches' masks right behind the grids'
+	// masks (their rows continue the grids' rows), then the patches' headers and index
+	const size_t gi_patch_word = scene->gi_mask_word + (size_t) scene->gi_rows * (SKR_GI_ROW_ENTRIES * (scene->gi_wide ? 4 : 2) / 4);
+	const size_t ngi = scene->gi_table.empty() ? 0 : (std::max(scene->gi_table.size(), scene->gi_surface.empty() ? 0 : gi_patch_word + scene->gi_surface.size()) + 3) / 4;
+	r->gi_surface_word = scene->gi_table.empty() || scene->gi_surface.empty() ? 0 : gi_patch_word + scene->gi_surface_head;
 	r->off_gi = ngi ? r->off_fog + 2 * nfog + nsm : 0;
 	r->gi_grid[0] = scene->gi_grid[0];
 	r->gi_grid[1] = scene->gi_grid[1];
@@ -189,7 +195,11 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		blob[r->off_fog + 2 * j + 1] = {f[4], f[5], f[6], 0.0f};
 	}
 	if(nsm) memcpy(&blob[r->off_smask], scene->shadow_masks.data(), scene->shadow_masks.size() * 4);
-	if(ngi) memcpy(&blob[r->off_gi], scene->gi_table.data(), scene->gi_table.size() * 4);
+	if(ngi)
+	{
+		memcpy(&blob[r->off_gi], scene->gi_table.data(), scene->gi_table.size() * 4);
+		if(r->gi_surface_word) memcpy(reinterpret_cast<uint32_t *>(&blob[r->off_gi]) + gi_patch_word, scene->gi_surface.data(), scene->gi_surface.size() * 4);
+	}
 	if(ntc) memcpy(&blob[r->off_trace], scene->trace_chunks.data(), ntc * 16);
 	r->blob_bytes = blob.size() * 16;
 	hipError_t e = hipMalloc((void **) &r->d_blob, blob.size() * 16);
@@ -245,6 +255,7 @@ int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 	r->off_fog = src->off_fog; r->n_fog = src->n_fog;
 	r->off_smask = src->off_smask; r->shadow_reach2 = src->shadow_reach2;
 	r->off_gi = src->off_gi; r->gi_grid[0] = src->gi_grid[0]; r->gi_grid[1] = src->gi_grid[1]; r->gi_mask_word = src->gi_mask_word; r->gi_wide = src->gi_wide;
+	r->gi_surface_word = src->gi_surface_word;
 	r->n_chunks = src->n_chunks; r->chunk_size = src->chunk_size; r->cones = src->cones; r->chunk_stride = src->chunk_stride;
 	r->off_trace = src->off_trace; memcpy(r->trace_ball, src->trace_ball, sizeof r->trace_ball); r->trace_cones = src->trace_cones;
 	r->d_counters = src->d_counters;
@@ -387,6 +398,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 		p.gi_grid[1] = r->gi_grid[1];
 		p.gi_wide = r->gi_wide;
 		p.gi_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
+		if(r->gi_surface_word && r->sw.gi_surface) p.gi_surface = reinterpret_cast<const uint32_t *>(r->d_blob + r->off_gi) + r->gi_surface_word;
 	}
 	{ // pick the tightest set of chunk spheres whose |d| bound covers this frame's camera rays (GI children stay below 4,
 	  // the smallest bound): primary directions are dir + u right + v up (main.cpp:154-155)

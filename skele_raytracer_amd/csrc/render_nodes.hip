@@ -129,6 +129,7 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 		cn.rays += second ? 2u : 1u;
 		const RayPair rp = make_pair(d0, d1);
 		BestState s0, s1;
+		// (the grids' row: the surface patches, with the node's sphere from its shading row, made this kernel slower — DESIGN.md §5.8)
 		closest_pair<GIM>(sv, p, GIM ? gi_origin_row(p, co) : -1, co, d0, d1, second, rp, s0, s1);
 		hit0 = classify_child(sv, co, d0, rp.two_a.x, rp.four_a.x, s0, black0);
 		rec0 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s0.best & 0xffff) | ((2u * j) << 16)), q1a, q2a);
@@ -482,8 +483,10 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 		const bool act0 = lane < m; // the lane that shades record `lane` of the unit and writes its result
 		f3 co = mk3(0, 0, 1), Nn = mk3(0, 0, 1), direct1 = mk3(0, 0, 0);
 		uint32_t pixel = 0, node_id = 0, out_idx = 0; // out_idx: output pixel (FIRST) or this record's index
+		int gi_row = -1; // the lane's row of GI masks: one per unit, every round's children start at co (shade_common.h gi_surface_row)
 		if(FIRST)
 		{
+			uint32_t sph0 = ~0u;
 			if(act0)
 			{
 				const size_t nn = (size_t) (first + (uint32_t) lane);
@@ -493,7 +496,9 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 				direct1 = mk3(b0.x, b0.y, b0.z);
 				pixel = __float_as_uint(a1.z);
 				out_idx = __float_as_uint(b1.y);
+				sph0 = __float_as_uint(b0.w); // (the shading row's sphere: the one co lies on)
 			}
+			if(GIM) gi_row = gi_surface_row(p, sv, (int) sph0, co);
 		}
 		else
 		{
@@ -504,11 +509,11 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 			direct1 = a.direct;
 			pixel = a.pixel;
 			node_id = a.node_id;
+			if(GIM) gi_row = gi_surface_row(p, sv, (int) a.sph, co);
 		}
 		const bool act = act0;
 		f3 nt, nb;
 		tangent_basis(Nn, nt, nb);
-		const int gi_row = GIM ? gi_origin_row(p, co) : -1; // (the lane's origin row of GI masks: one per unit, every round's children start at co)
 		// (r1 and the sphere are only needed when the unit is finished: they are read again from the record / node row then)
 		STAMP(1);
 		// ---- rounds: children 2j, 2j+1 of every lane's node

@@ -29,8 +29,10 @@ struct SkrSwitches {
 	                                   // every field of RenderParams behind it keeps its offset and the kernels that never read the switches their code)
 	int32_t budget_mb = 0;            // SKR_LEVELS_BUDGET_MB: scratch budget of the level pipelines (0 = default)
 	int32_t flat = 0;                 // SKR_FLAT = 1 | 0: the node pipeline's flat schedule forced on (+1) / off (-1); unset: by launch size
-	int16_t shadow_mask = 1;          // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
-	int16_t gi_mask = 1;              // SKR_GI_MASK = 1 | 0: the same for the closest-hit walk of the node pipeline's GI children  (two halves of one word, as above)
+	int8_t shadow_mask = 1;           // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
+	int8_t gi_mask = 1;               // SKR_GI_MASK = 1 | 0: the same for the closest-hit walk of the node pipeline's GI children
+	int8_t gi_surface = 1;            // SKR_GI_SURFACE = 1 | 0: GI origins on a sphere take their row of masks from the surface patches / the 3D grids only
+	int8_t pad_switch = 0;            // (four quarters of one word, as above)
 };
 
 struct RenderParams {
@@ -111,6 +113,10 @@ struct RenderParams {
 	SkrGiGrid gi_grid[2];
 	int32_t gi_wide;
 	uint32_t gi_all;
+	// the surface patches of the GI masks (shadow_cells.h; shade_common.h gi_surface_row), in the scene blob behind the grids' rows:
+	// SKR_GI_SURFACE_HEAD words per sphere, then the patch index words; their rows continue the grids' rows of gi_masks.  null = the
+	// grids only.
+	const uint32_t *gi_surface;
 };
 
 // Optional timing of the dominant kernel of a launch (skr_renderer_kernel_ms): the launcher records the

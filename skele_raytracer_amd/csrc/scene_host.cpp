@@ -140,6 +140,7 @@ void skr_scene::finalize()
 	build_triangle_chunks();
 	build_shadow_masks();
 	build_gi_masks();
+	build_gi_surface();
 }
 
 void skr_scene::build_triangle_materials()
@@ -264,6 +265,40 @@ void skr_scene::build_shadow_masks()
 	}
 	shadow_masks.swap(masks);
 	shadow_reach2 = reach2;
+}
+
+// Bit `bit` (sphere of centre C, squared radius r2) of every direction cell of a GI mask row, for origins in the ball (q, rho)
+// (build_gi_masks' margins; cth, sth: the cosine and sine of each direction cell's padded angular radius).  All in binary64.
+static void gi_ball_bits(const double *q, double rho, const double *C, double r2, uint32_t bit, const std::vector<double> &cell_dir,
+						 const std::vector<double> &cth, const std::vector<double> &sth, uint32_t *row)
+{
+	const double v[3] = {C[0] - q[0], C[1] - q[1], C[2] - q[2]};
+	const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+	const double E = (dist + rho) * (1.0 + 0x1p-20); // bounds |e| = |o - C| of the device's test
+	const double rk = std::sqrt(r2 + 0x1p-16 * (E * E + r2)) + 0x1p-20 * E; // discriminant slack (16x), the rounding of e
+	const double tol = 0x1p-30 * (dist + rho + rk);                         // (this function's own rounding)
+	const double behind = rho + 0x1p-16 * E + tol;                           // b < 0 needs (C - o).d > -2^-22 |e| |d|
+	const double reach = rk + rho + tol;
+	if(dist <= reach)
+	{ // the grown sphere meets the cell: every direction
+		for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++) row[e] |= bit;
+		return;
+	}
+	for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++)
+	{
+		const double *w = &cell_dir[3 * (size_t) e];
+		const double cp = (v[0] * w[0] + v[1] * w[1] + v[2] * w[2]) / dist;
+		const double x = v[1] * w[2] - v[2] * w[1], y = v[2] * w[0] - v[0] * w[2], z = v[0] * w[1] - v[1] * w[0];
+		const double sp = std::sqrt(x * x + y * y + z * z) / dist;
+		const double ct = cth[e], st = sth[e];
+		const bool lo0 = cp >= ct;   // phi <= theta
+		const bool hipi = cp <= -ct; // phi + theta >= pi
+		const double cos_lo = lo0 ? 1.0 : cp * ct + sp * st;
+		const double sin_lo = lo0 ? 0.0 : sp * ct - cp * st;
+		const double sin_hi = hipi ? 0.0 : sp * ct + cp * st;
+		const double min_sin = std::max(0.0, std::min(sin_lo, sin_hi));
+		if(dist * cos_lo + behind >= 0.0 && dist * min_sin <= reach) row[e] |= bit;
+	}
 }
 
 // The GI masks (shadow_cells.h; DESIGN.md "GI masks" derives every margin below).  A GI child ray starts at its node's hit point o
@@ -401,41 +436,7 @@ void skr_scene::build_gi_masks()
 	}
 	std::vector<uint32_t> masks(cells.size() * SKR_GI_ROW_ENTRIES, 0u);
 	for(size_t ci = 0; ci < cells.size(); ci++)
-	{
-		const Cell &cl = cells[ci];
-		uint32_t *row = &masks[ci * SKR_GI_ROW_ENTRIES];
-		for(int k = 0; k < ns; k++)
-		{
-			const double v[3] = {C[3 * k] - cl.q[0], C[3 * k + 1] - cl.q[1], C[3 * k + 2] - cl.q[2]};
-			const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-			const double E = (dist + cl.rho) * (1.0 + 0x1p-20); // bounds |e| = |o - C| of the device's test
-			const double rk = std::sqrt(r2[k] + 0x1p-16 * (E * E + r2[k])) + 0x1p-20 * E; // discriminant slack (16x), the rounding of e
-			const double tol = 0x1p-30 * (dist + cl.rho + rk);                             // (this function's own rounding)
-			const double behind = cl.rho + 0x1p-16 * E + tol;                               // b < 0 needs (C - o).d > -2^-22 |e| |d|
-			const double reach = rk + cl.rho + tol;
-			const uint32_t bit = 1u << k;
-			if(dist <= reach)
-			{ // the grown sphere meets the cell: every direction
-				for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++) row[e] |= bit;
-				continue;
-			}
-			for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++)
-			{
-				const double *w = &cell_dir[3 * (size_t) e];
-				const double cp = (v[0] * w[0] + v[1] * w[1] + v[2] * w[2]) / dist;
-				const double x = v[1] * w[2] - v[2] * w[1], y = v[2] * w[0] - v[0] * w[2], z = v[0] * w[1] - v[1] * w[0];
-				const double sp = std::sqrt(x * x + y * y + z * z) / dist;
-				const double ct = cth[e], st = sth[e];
-				const bool lo0 = cp >= ct;   // phi <= theta
-				const bool hipi = cp <= -ct; // phi + theta >= pi
-				const double cos_lo = lo0 ? 1.0 : cp * ct + sp * st;
-				const double sin_lo = lo0 ? 0.0 : sp * ct - cp * st;
-				const double sin_hi = hipi ? 0.0 : sp * ct + cp * st;
-				const double min_sin = std::max(0.0, std::min(sin_lo, sin_hi));
-				if(dist * cos_lo + behind >= 0.0 && dist * min_sin <= reach) row[e] |= bit;
-			}
-		}
-	}
+		for(int k = 0; k < ns; k++) gi_ball_bits(cells[ci].q, cells[ci].rho, &C[3 * k], r2[k], 1u << k, cell_dir, cth, sth, &masks[ci * SKR_GI_ROW_ENTRIES]);
 	const size_t n_index = (index.size() + 1) & ~(size_t) 1;
 	const size_t n_mask_words = gi_wide ? masks.size() : masks.size() / 2;
 	std::vector<uint32_t> table((n_index + n_mask_words + 3) & ~(size_t) 3, 0u);
@@ -445,6 +446,158 @@ void skr_scene::build_gi_masks()
 		for(size_t e = 0; e < masks.size(); e += 2) table[n_index + e / 2] = masks[e] | masks[e + 1] << 16; // (uint16_t entries, little-endian)
 	gi_mask_word = (uint32_t) n_index;
 	gi_table.swap(table);
+}
+
+// The surface patches of the GI masks (shadow_cells.h; DESIGN.md "GI surface patches" derives every margin below).  A GI origin is a
+// hit point of some sphere s, so the device keys it to the cell of e = o - C_s in a cube map on that sphere, once fl(|e|^2) - r_s^2
+// is within the sphere's radial slack tau_s: every such origin lies in the shell R_lo <= |o - C_s| <= R_hi, in the directions of
+// the cell padded like every cube-map cell.  A patch is that piece of the shell; its origins lie in a ball (q, rho) around the
+// point at r_s cos(theta) along the cell's centre direction, and its row holds build_gi_masks' masks of that ball, except for
+// sphere s itself: an origin on the patch sees it only behind its surface, so its bit is set only for the directions that some
+// origin of the patch may see at an angle of 90 degrees or more from its own e (b >= 0 otherwise).  Patches are stored where their
+// ball meets the fine grid's box (the small spheres and the ground under them); the cells grow by 1.15x until the whole table
+// fits SKR_GI_MAX_BYTES.  A device lane off every stored patch takes the grids' row (shade_common.h gi_surface_row).  All in binary64.
+void skr_scene::build_gi_surface()
+{
+	gi_surface.clear();
+	gi_surface_head = 0;
+	gi_rows = 0;
+	if(gi_table.empty()) return;
+	const int ns = info.n_spheres;
+	const size_t row_words = (size_t) SKR_GI_ROW_ENTRIES * (gi_wide ? 4 : 2) / 4;
+	gi_rows = (uint32_t) ((gi_table.size() - gi_mask_word) / row_words); // (the table's padding is below one row)
+	std::vector<double> C((size_t) 3 * ns), r2(ns), rad(ns), R_lo(ns), R_hi(ns);
+	std::vector<float> tau(ns);
+	for(int k = 0; k < ns; k++)
+	{
+		C[3 * k] = sph_geom[k].x;
+		C[3 * k + 1] = sph_geom[k].y;
+		C[3 * k + 2] = sph_geom[k].z;
+		r2[k] = sph_geom[k].w;
+		rad[k] = std::sqrt(r2[k]);
+		// the radial slack: |fl(|e|^2) - r^2| <= tau gives (r^2 - tau)(1 - 2^-20) <= |fl(e)|^2 <= (r^2 + tau)(1 + 2^-20) (the dot product's
+		// and the difference's rounding), and |e| is within 2^-23 |e| of |fl(e)|
+		tau[k] = rad[k] > 1e-3 ? (float) (r2[k] * 0x1p-7) : -1.0f; // (|o - C| within about r / 256 of r; tiny spheres: no patches)
+		R_lo[k] = std::sqrt(std::max(0.0, (r2[k] - tau[k]) * (1.0 - 0x1p-20))) * (1.0 - 0x1p-22);
+		R_hi[k] = std::sqrt((r2[k] + std::max(0.0f, tau[k])) * (1.0 + 0x1p-20)) * (1.0 + 0x1p-22);
+	}
+	double blo[3], bhi[3]; // the fine grid's box
+	for(int c = 0; c < 3; c++)
+	{
+		blo[c] = gi_grid[0].lo[c];
+		bhi[c] = blo[c] + gi_grid[0].n[c] / (double) gi_grid[0].inv;
+	}
+	struct Patch {
+		int s, cell;
+		double q[3], rho;
+	};
+	std::vector<Patch> patches;
+	std::vector<int> G(ns, 0);
+	std::vector<std::vector<double>> cdir(ns), cth(ns); // per sphere: its cells' centre directions and padded angular radii
+	size_t n_index = 0;
+	bool fits = false;
+	// the first edge tried: half the one at which the small spheres' patches alone (about 24 r^2 / edge^2 each) fill the table
+	std::vector<double> sorted(rad);
+	std::sort(sorted.begin(), sorted.end());
+	double small_area = 0.0;
+	for(int k = 0; k < ns; k++)
+		if(rad[k] <= 4.0 * sorted[ns / 2]) small_area += 24.0 * r2[k];
+	double edge = std::max(1e-6, 0.5 * std::sqrt(small_area / std::max(1.0, (double) SKR_GI_MAX_BYTES / (row_words * 4))));
+	for(int attempt = 0; attempt < 200 && !fits; attempt++, edge *= 1.15)
+	{
+		patches.clear();
+		n_index = 0;
+		for(int k = 0; k < ns; k++)
+		{
+			const int g = tau[k] < 0.0f ? 0 : (int) std::min((double) SKR_GI_SURFACE_MAX_CELLS, std::max(1.0, std::ceil(2.0 * rad[k] / edge)));
+			if(g != G[k])
+			{
+				G[k] = g;
+				cdir[k].clear();
+				cth[k].clear();
+				if(g) cube_cells(g, cdir[k], cth[k]);
+				// + the angle between e and fl(e) (2^-23 of each component)
+				for(double &t : cth[k]) t = t * (1.0 + 0x1p-20) + 0x1p-20;
+			}
+			n_index += (size_t) 6 * g * g;
+			for(int cell = 0; cell < 6 * g * g; cell++)
+			{
+				const double *w = &cdir[k][3 * (size_t) cell];
+				const double th = cth[k][cell], h = rad[k] * std::cos(th);
+				Patch pt;
+				pt.s = k;
+				pt.cell = cell;
+				for(int c = 0; c < 3; c++) pt.q[c] = C[3 * k + c] + h * w[c];
+				// the farthest point of the patch from q: |o - q|^2 = R^2 + h^2 - 2 R h cos(phi) grows with phi and is convex in R
+				double far = 0.0;
+				for(double R : {R_lo[k], R_hi[k]}) far = std::max(far, std::sqrt(std::max(0.0, R * R + h * h - 2.0 * R * h * std::cos(th))));
+				double cmax = 0.0;
+				for(int c = 0; c < 3; c++) cmax = std::max(cmax, std::fabs(C[3 * k + c]));
+				pt.rho = far * (1.0 + 0x1p-20) + 0x1p-30 * (cmax + rad[k]);
+				double gap2 = 0.0; // from q to the box
+				for(int c = 0; c < 3; c++)
+				{
+					const double o = std::max(0.0, std::max(blo[c] - pt.q[c], pt.q[c] - bhi[c]));
+					gap2 += o * o;
+				}
+				if(gap2 <= pt.rho * pt.rho) patches.push_back(pt);
+			}
+		}
+		fits = (SKR_GI_SURFACE_HEAD * (size_t) ns + n_index) * 4 + patches.size() * row_words * 4 <= SKR_GI_MAX_BYTES;
+	}
+	if(!fits || patches.empty()) return;
+	std::vector<double> cell_dir, cell_theta;
+	cube_cells(SKR_GI_DIR_CELLS, cell_dir, cell_theta);
+	std::vector<double> dth(SKR_GI_ROW_ENTRIES), dct(SKR_GI_ROW_ENTRIES), dst(SKR_GI_ROW_ENTRIES);
+	for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++)
+	{
+		dth[e] = cell_theta[e] * (1.0 + 0x1p-20) + 0x1p-40;
+		dct[e] = std::cos(dth[e]);
+		dst[e] = std::sin(dth[e]);
+	}
+	std::vector<uint32_t> masks(patches.size() * SKR_GI_ROW_ENTRIES, 0u);
+	for(size_t pi = 0; pi < patches.size(); pi++)
+	{
+		const Patch &pt = patches[pi];
+		uint32_t *row = &masks[pi * SKR_GI_ROW_ENTRIES];
+		for(int k = 0; k < ns; k++)
+			if(k != pt.s) gi_ball_bits(pt.q, pt.rho, &C[3 * k], r2[k], 1u << k, cell_dir, dct, dst, row);
+		// sphere s: (C - o).d / |d| = -R cos(angle(e, d)) with R >= R_lo, and that angle is at most psi + theta_patch + theta_dir;
+		// below 90 degrees b < 0 needs R_lo cos(.) < 2^-16 E (the rounding of b, as in build_gi_masks)
+		const int s = pt.s;
+		const double *wp = &cdir[s][3 * (size_t) pt.cell];
+		const double E = R_hi[s] * (1.0 + 0x1p-20), behind = 0x1p-16 * E + 0x1p-30 * R_hi[s];
+		for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++)
+		{
+			const double *w = &cell_dir[3 * (size_t) e];
+			const double x = wp[1] * w[2] - wp[2] * w[1], y = wp[2] * w[0] - wp[0] * w[2], z = wp[0] * w[1] - wp[1] * w[0];
+			const double psi = std::atan2(std::sqrt(x * x + y * y + z * z), wp[0] * w[0] + wp[1] * w[1] + wp[2] * w[2]);
+			const double ang = psi + cth[s][pt.cell] + dth[e] + 0x1p-30;
+			if(!(ang < 0.5 * M_PI && R_lo[s] * std::cos(ang) > behind)) row[e] |= 1u << s;
+		}
+	}
+	// masks (rows gi_rows + pi), headers, index
+	const size_t n_mask_words = gi_wide ? masks.size() : masks.size() / 2;
+	std::vector<uint32_t> table(n_mask_words + SKR_GI_SURFACE_HEAD * (size_t) ns + n_index, 0u);
+	if(gi_wide) memcpy(table.data(), masks.data(), masks.size() * 4);
+	else
+		for(size_t e = 0; e < masks.size(); e += 2) table[e / 2] = masks[e] | masks[e + 1] << 16; // (uint16_t entries, little-endian)
+	uint32_t *head = &table[n_mask_words];
+	int32_t *index = reinterpret_cast<int32_t *>(head + SKR_GI_SURFACE_HEAD * ns);
+	size_t at = SKR_GI_SURFACE_HEAD * (size_t) ns;
+	for(int k = 0; k < ns; k++)
+	{
+		head[SKR_GI_SURFACE_HEAD * k] = (uint32_t) at;
+		head[SKR_GI_SURFACE_HEAD * k + 1] = (uint32_t) G[k];
+		const float t = G[k] ? tau[k] : -1.0f;
+		memcpy(&head[SKR_GI_SURFACE_HEAD * k + 2], &t, 4);
+		for(int c = 0; c < 6 * G[k] * G[k]; c++) head[at + c] = 0xffffffffu; // -1 = none
+		at += (size_t) 6 * G[k] * G[k];
+	}
+	for(size_t pi = 0; pi < patches.size(); pi++)
+		index[head[SKR_GI_SURFACE_HEAD * patches[pi].s] - SKR_GI_SURFACE_HEAD * ns + patches[pi].cell] = (int32_t) (gi_rows + pi);
+	gi_surface_head = (uint32_t) n_mask_words;
+	gi_surface.swap(table);
 }
 
 // Exact-preserving culling data for the triangle walk (DESIGN.md "Triangle chunks").
@@ -1148,6 +1301,18 @@ int skr_scene_get_gi_masks(const skr_scene *scene, int32_t *n_words, int32_t *ma
 			memcpy(grids + 8 * g, row, sizeof(row));
 		}
 	if(table && !scene->gi_table.empty()) memcpy(table, scene->gi_table.data(), scene->gi_table.size() * 4);
+	return SKR_OK;
+}
+
+// Internal (not in include/skr.h: tests only): the surface patches of the GI masks (skr_scene::gi_surface).  first_row: the row
+// number of the first patch (the grids' rows come first on the device).
+int skr_scene_get_gi_surface(const skr_scene *scene, int32_t *n_words, int32_t *head_word, int32_t *first_row, uint32_t *table)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(n_words) *n_words = (int32_t) scene->gi_surface.size();
+	if(head_word) *head_word = (int32_t) scene->gi_surface_head;
+	if(first_row) *first_row = (int32_t) scene->gi_rows;
+	if(table && !scene->gi_surface.empty()) memcpy(table, scene->gi_surface.data(), scene->gi_surface.size() * 4);
 	return SKR_OK;
 }
 

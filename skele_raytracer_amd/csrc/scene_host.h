@@ -74,6 +74,13 @@ struct skr_scene {
 	uint32_t gi_mask_word = 0; // the first word of the masks in gi_table
 	int gi_wide = 0;
 	void build_gi_masks();
+	// the surface patches of the GI masks (shadow_cells.h, DESIGN.md "GI surface patches"): the patches' masks (rows gi_rows,
+	// gi_rows + 1, ... of the device's table, which are laid behind the grids' rows), then SKR_GI_SURFACE_HEAD words per sphere from
+	// word gi_surface_head, then the index words; empty where there are no GI masks
+	std::vector<uint32_t> gi_surface;
+	uint32_t gi_surface_head = 0;
+	uint32_t gi_rows = 0; // rows of masks of the grids in gi_table
+	void build_gi_surface();
 };
 
 // scene.cpp:12-227 replacement.  Returns SKR_OK or SKR_ERR_IO.

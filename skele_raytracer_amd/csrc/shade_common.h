@@ -347,8 +347,7 @@ SKR_DEV bool any_triangle_closer(const SceneView &sv, const RayConst &r, float t
 struct CubeCell {
 	int face, i, j;
 };
-template <int N>
-SKR_DEV CubeCell cube_cell(f3 v)
+SKR_DEV CubeCell cube_cell_n(f3 v, int N)
 {
 	const float ax = __builtin_fabsf(v.x), ay = __builtin_fabsf(v.y), az = __builtin_fabsf(v.z);
 	const bool fx = (ax >= ay) && (ax >= az), fy = !fx && (ay >= az);
@@ -359,6 +358,11 @@ SKR_DEV CubeCell cube_cell(f3 v)
 	const int i = (int) __builtin_fminf(__builtin_fmaxf((a * inv) * h + h, 0.0f), top); // (NaN -> 0)
 	const int j = (int) __builtin_fminf(__builtin_fmaxf((b * inv) * h + h, 0.0f), top);
 	return CubeCell{face, i, j};
+}
+template <int N>
+SKR_DEV CubeCell cube_cell(f3 v)
+{
+	return cube_cell_n(v, N);
 }
 
 // The spheres that may stop the shadow ray of point light l from P (v = Lp - P, the subtraction light_term makes): the cell of v's
@@ -388,6 +392,28 @@ SKR_DEV int gi_origin_row(const RenderParams &p, f3 o)
 {
 	int row = gi_grid_cell(p.gi_index, p.gi_grid[0], o);
 	if(row < 0) row = gi_grid_cell(p.gi_index, p.gi_grid[1], o); // (the coarse grid only where the fine one has no row)
+	return row;
+}
+// The row of masks of GI origin o, a hit point of sphere s (DESIGN.md "GI surface patches"): the patch of e = o - C_s on sphere s,
+// where fl(|e|^2) - r_s^2 is within the sphere's radial slack and the patch is stored; else the grids' row (gi_origin_row).  s
+// outside [0, ns) (the sphere is not known) or no patches (SKR_GI_SURFACE=0): the grids' row.  The index is in bounds whatever o holds.
+SKR_DEV int gi_surface_row(const RenderParams &p, const SceneView &sv, int s, f3 o)
+{
+	int row = -1;
+	if(p.gi_surface != nullptr && (uint32_t) s < (uint32_t) sv.ns)
+	{
+		const uint32_t *h = p.gi_surface + SKR_GI_SURFACE_HEAD * s;
+		const uint32_t at = h[0], n = h[1];
+		const float4 g = sv.geom[s];
+		const f3 e = o - ld3(g);
+		const float c = dot3(e, e) - g.w;
+		if(__builtin_fabsf(c) <= __uint_as_float(h[2])) // (NaN: no; a sphere without patches has a negative slack)
+		{
+			const CubeCell cc = cube_cell_n(e, (int) n);
+			row = (int) p.gi_surface[at + ((uint32_t) cc.face * n + (uint32_t) cc.i) * n + (uint32_t) cc.j];
+		}
+	}
+	if(row < 0) row = gi_origin_row(p, o);
 	return row;
 }
 // The union of the masks of children d0 and (second) d1 from origin row `row`; every sphere where the row is -1 or a direction is not a

@@ -32,3 +32,11 @@ struct SkrGiGrid {
 	float n_f[3];     /* n as floats (the device's range test) */
 	int32_t n[3], base;
 };
+
+/* Surface patches of the GI masks (DESIGN.md "GI surface patches"): a GI origin is a hit point of sphere s, so its row can be keyed
+ * to the cell of e = o - C_s in a cube map of G_s x G_s cells per face on that sphere (the addressing above, G_s per sphere), where
+ * the device's fl(|e|^2) - r_s^2 is within the sphere's radial slack tau_s.  Per sphere SKR_GI_SURFACE_HEAD words: the first index
+ * word (from the start of the headers), G_s, tau_s (binary32 bits; negative: no patches), 0.  Index word (f G_s + i) G_s + j = the
+ * patch's row of masks (numbered after the grids' rows), -1 = none. */
+#define SKR_GI_SURFACE_HEAD 4
+#define SKR_GI_SURFACE_MAX_CELLS 128 /* G_s at most: the ground-like spheres' index stays small */
