@@ -25,7 +25,9 @@
 extern "C" {
 #endif
 
-#define SKR_ABI_VERSION 7 /* 7: skr_ray, skr_hit, skr_trace_rays, skr_camera_rays (ray queries); 6: skr_scene_get_gi_masks; 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
+#define SKR_ABI_VERSION 7 /* 7: skr_ray, skr_hit, skr_trace_rays, skr_camera_rays (ray queries), then skr_shade_rays (shading queries: an addition that leaves every
+                            * existing entry point and struct as it was; SKR_HAS_SHADE_RAYS tells a caller it is there); 6: skr_scene_get_gi_masks; 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
+#define SKR_HAS_SHADE_RAYS 1
 
 typedef enum {
 	SKR_OK = 0,
@@ -355,6 +357,32 @@ int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t 
  * centres) into a DEVICE skr_ray[height][width]: o = the camera position, d = bit for bit the direction the renderer traces for that
  * pixel and sample (main.cpp:140-182), tmax = +inf, ignore_triangle = -1.  Asynchronous on `stream`. */
 int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, skr_ray *d_rays, void *stream);
+
+/* ---- shading queries (new): the radiance of caller-supplied rays, what shade() returns for them ----
+ * Radiance of n caller-supplied rays (DEVICE skr_ray[n], 16-byte aligned) under options opt, asynchronously on `stream`.
+ * d_rgbf: DEVICE float[n][3], the unquantised value shade() returns for each ray (what a 1-spp frame's float output holds).
+ * d_keys: DEVICE uint32_t[n] or NULL (= ray index): the counter RNG's pixel word for each ray; `sample` is its AA word.
+ *   - Shading rule: the renderer's own, for opt's monte_carlo, num_path_traces, max_depth, use_shadows, seed, shade_triangles and
+ *     legacy_reflect, and for the scene's fog volumes.  The result does not depend on width, height, fov, grid_size or
+ *     progressive_passes.
+ *   - Specular view: as everywhere in the renderer (blinn_phong.h), the view vector of the specular term points to the SCENE CAMERA,
+ *     not to the ray's origin.
+ *   - Counter RNG: ray i is keyed (pixel = d_keys ? d_keys[i] : i, aa = sample, node 0); its GI and fog draws are then exactly those of
+ *     frame pixel `key` at AA sample `sample`.  So skr_camera_rays(opt, s) with keys y * width + x reproduces the frame's sample s,
+ *     bit for bit.
+ *   - tmax: the winner the frame's rule picks for the first segment is found first — the closest sphere at 1 < t, or a triangle that
+ *     blackens (shade_triangles = 0) or is shaded (shade_triangles = 1) under the mode's own triangle rule.  If its t is >= tmax the
+ *     ray is a miss and returns the background.  With tmax = +inf this is exactly the frame's rule.  tmax does not apply to child rays.
+ *   - ignore_triangle: honoured under shade_triangles, as the from_triangle of the first segment (what a --gillum child has).
+ *     Without shade_triangles it is not read: no ray the renderer traces in that mode carries one.
+ *   - Counters: the work counters (skr_renderer_read_counters: rays, hits, shadow rays) advance exactly as a render of those rays
+ *     would.  Nothing a later render reads is changed.  skr_kernel_variant() names the shading path.
+ *   - Errors: n == 0: SKR_OK, nothing is launched.  SKR_ERR_ARG: null or misaligned arrays, bad options.  As skr_render_tiles
+ *     returns them: a tree over 2^32 node ids, fog with legacy_reflect or shade_triangles, tables over the scratch budget
+ *     (SKR_ERR_UNSUPPORTED).  Rays with a non-finite or zero direction get an unspecified result for that ray only; they never
+ *     fault and never change another ray's result. */
+int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_rays, uint32_t n, uint32_t sample, const uint32_t *d_keys, float *d_rgbf,
+                   void *stream);
 
 /* ---- image file: replaces the inline writer main.cpp:199-211 ---- */
 int skr_write_ppm(const char *path, uint32_t width, uint32_t height, const uint8_t *rgb);

@@ -16,7 +16,7 @@ EXPORTED_SYMBOLS = [
     "skr_rccl_available", "skr_multi_create", "skr_multi_destroy", "skr_multi_device_count", "skr_multi_renderer", "skr_multi_render_frame",
     "skr_multi_render_frame_host", "skr_comm_unique_id", "skr_comm_create", "skr_comm_destroy", "skr_comm_render_frame", "skr_comm_render_frame_async", "skr_comm_flush", "skr_comm_frame_to_host",
     "skr_shard_tiles_per_rank", "skr_shard_deinterleave_host", "skr_shard_lpt", "skr_shard_by_cost", "skr_shard_plan", "skr_shard_deinterleave_map_host", "skr_multi_render_frame_async", "skr_multi_flush",
-    "skr_trace_rays", "skr_camera_rays",
+    "skr_trace_rays", "skr_camera_rays", "skr_shade_rays",
 ]
 
 
@@ -143,6 +143,7 @@ def lib():
     L.skr_shard_deinterleave_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32]
     L.skr_trace_rays.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.skr_camera_rays.argtypes = [vp, C.POINTER(COptions), C.c_uint32, vp, vp]
+    L.skr_shade_rays.argtypes = [vp, C.POINTER(COptions), vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     _lib = L
     return L
 
@@ -514,6 +515,35 @@ class Renderer:
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             _check(lib().skr_camera_rays(self.h, C.byref(opt.c), sample, out.data_ptr(), stream), "skr_camera_rays")
+        return out
+
+    def shade(self, rays, opt, sample=0, keys=None):
+        """The radiance of rays (float32 [n, 8] on this device, the include/skr.h skr_ray layout: make_rays, camera_rays) under options
+        opt, on torch's current stream (include/skr.h skr_shade_rays): float32 [n, 3], what shade() returns for each ray.  keys (int32 or
+        uint32 [n] on this device; None = the ray index) and sample are the counter RNG's pixel and AA words of each ray, so
+        shade(camera_rays(opt, s).view(-1, 8), opt, s, keys=y * width + x) is the frame's sample s, bit for bit."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or rays.device != dev:
+            raise SkrError("shade: rays must be a float32 [n, 8] tensor on %s (make_rays)" % dev)
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        if n >= 1 << 32:
+            raise SkrError("shade: at most 2^32 - 1 rays per call")
+        if keys is not None:
+            if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 1 or keys.shape[0] != n or keys.device != dev:
+                raise SkrError("shade: keys must be an int32 or uint32 [%d] tensor on %s" % (n, dev))
+            keys = keys.contiguous()
+        if not 0 <= int(sample) < 1 << 32:
+            raise SkrError("shade: sample must fit 32 bits")
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        if n == 0:  # (an empty tensor has no address to pass)
+            return out
+        self._sync_switches()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib().skr_shade_rays(self.h, C.byref(opt.c), rays.data_ptr(), n, int(sample), None if keys is None else keys.data_ptr(),
+                                        out.data_ptr(), stream), "skr_shade_rays")
         return out
 
 

@@ -343,31 +343,11 @@ static uint32_t sel_tiles(const skr_options *opt, uint32_t tile_rows, const Tile
 	return n > ts.max_tiles ? ts.max_tiles : n;
 }
 
-static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
+// Everything of a launch that is not its output: the scene, the switches and masks, the camera, and the options folded and checked —
+// the depth fold, the node-id bound, the fog exclusions.  render_pass and skr_shade_rays both start from it.
+static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &p)
 {
-	const uint32_t first_tile = ts.first, tile_stride = ts.stride;
-	if(!r || !opt || (!d_rgb && !d_rgbf) || tile_rows == 0 || tile_stride == 0)
-	{
-		skr_set_error("skr_render_tiles: bad argument");
-		return SKR_ERR_ARG;
-	}
-	int rc = check_options(opt);
-	if(rc != SKR_OK) return rc;
-	const uint32_t n_tiles = sel_tiles(opt, tile_rows, ts);
-	if(n_tiles == 0) return SKR_OK;
-	SKR_HIP(hipSetDevice(r->device));
-
-	RenderParams p{};
 	p.sw = r->sw;
-	p.width = opt->width;
-	p.height = opt->height;
-	p.tile_rows = tile_rows;
-	p.first_tile = first_tile;
-	p.tile_table = ts.d_table;
-	p.tile_stride = tile_stride;
-	p.out_rows = n_tiles * tile_rows;
-	p.band_row0 = 0;
-	p.band_rows = p.out_rows;
 	camera_invariants(r, opt, p);
 	const float *c = r->info.camera;
 	p.background = f3{r->info.background[0], r->info.background[1], r->info.background[2]};
@@ -449,25 +429,62 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	}
 	p.seed_lo = (uint32_t) opt->seed;
 	p.seed_hi = (uint32_t) (opt->seed >> 32);
-	p.rgb = d_rgb;
-	p.rgbf = d_rgbf;
 	p.counters = r->d_counters;
 	p.tri_work = r->count_tri ? r->d_tri_work : nullptr;
 	p.qctr = reinterpret_cast<uint32_t *>(r->d_counters + (size_t) SKR_COUNTER_SHARDS * 4 + 8);
+	return SKR_OK;
+}
+
+// grows the level pipelines' scratch (kept between launches) to `bytes`
+static int ensure_level_scratch(skr_renderer *r, size_t bytes)
+{
+	if(bytes > r->nodes_cap)
+	{
+		if(r->d_nodes) SKR_HIP(hipFree(r->d_nodes));
+		r->d_nodes = nullptr;
+		r->nodes_cap = 0;
+		SKR_HIP(hipMalloc(&r->d_nodes, bytes));
+		r->nodes_cap = bytes;
+	}
+	return SKR_OK;
+}
+
+static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
+{
+	const uint32_t first_tile = ts.first, tile_stride = ts.stride;
+	if(!r || !opt || (!d_rgb && !d_rgbf) || tile_rows == 0 || tile_stride == 0)
+	{
+		skr_set_error("skr_render_tiles: bad argument");
+		return SKR_ERR_ARG;
+	}
+	int rc = check_options(opt);
+	if(rc != SKR_OK) return rc;
+	const uint32_t n_tiles = sel_tiles(opt, tile_rows, ts);
+	if(n_tiles == 0) return SKR_OK;
+	SKR_HIP(hipSetDevice(r->device));
+
+	RenderParams p{};
+	p.width = opt->width;
+	p.height = opt->height;
+	p.tile_rows = tile_rows;
+	p.first_tile = first_tile;
+	p.tile_table = ts.d_table;
+	p.tile_stride = tile_stride;
+	p.out_rows = n_tiles * tile_rows;
+	p.band_row0 = 0;
+	p.band_rows = p.out_rows;
+	rc = launch_params(r, opt, p);
+	if(rc != SKR_OK) return rc;
+	p.rgb = d_rgb;
+	p.rgbf = d_rgbf;
 	LaunchPlan lp;
 	if(!skr_plan_launch(p, lp))
 	{
 		skr_set_error("--depth %d with %d children per node: the tables of one output row exceed the scratch budget (SKR_LEVELS_BUDGET_MB)", p.max_depth, p.num_path_traces + (p.legacy_reflect ? 2 * p.n_lights : 0));
 		return SKR_ERR_UNSUPPORTED;
 	}
-	if(lp.scratch_bytes > r->nodes_cap)
-	{
-		if(r->d_nodes) SKR_HIP(hipFree(r->d_nodes));
-		r->d_nodes = nullptr;
-		r->nodes_cap = 0;
-		SKR_HIP(hipMalloc(&r->d_nodes, lp.scratch_bytes));
-		r->nodes_cap = lp.scratch_bytes;
-	}
+	rc = ensure_level_scratch(r, lp.scratch_bytes);
+	if(rc != SKR_OK) return rc;
 	if(lp.path != SKR_PATH_DIRECT) p.node_scratch = r->d_nodes;
 	if(lp.acc_bytes > r->acc_cap)
 	{
@@ -923,6 +940,64 @@ int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, sk
 	p.seed_hi = (uint32_t) (opt->seed >> 32);
 	p.aa_index = sample;
 	SKR_HIP(skr_launch_camera_rays(p, reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream));
+	return SKR_OK;
+}
+
+// ---- shading queries (render_generic.hip): the radiance of caller-supplied rays on the general level pipeline ----
+int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_rays, uint32_t n, uint32_t sample, const uint32_t *d_keys, float *d_rgbf,
+				   void *stream)
+{
+	if(!r || !opt || !d_rays || !d_rgbf || ((uintptr_t) d_rays & 15) || ((uintptr_t) d_rgbf & 3) || ((uintptr_t) d_keys & 3))
+	{
+		skr_set_error("skr_shade_rays: bad argument (null or misaligned array)");
+		return SKR_ERR_ARG;
+	}
+	int rc = check_options(opt);
+	if(rc != SKR_OK) return rc;
+	if(n == 0) return SKR_OK;
+	SKR_HIP(hipSetDevice(r->device));
+	RenderParams p{};
+	p.width = (int32_t) SKR_SHADE_ROW; // the plan's rows: SKR_SHADE_ROW rays each, the last one partial
+	p.height = opt->height;
+	p.tile_rows = 1;
+	p.tile_stride = 1;
+	p.out_rows = (uint32_t) (((uint64_t) n + SKR_SHADE_ROW - 1) / SKR_SHADE_ROW);
+	p.band_rows = p.out_rows;
+	rc = launch_params(r, opt, p);
+	if(rc != SKR_OK) return rc;
+	p.grid_size = 0; // (one sample: `sample`)
+	p.aa_index = sample;
+	GPlan pl;
+	if(!skr_generic_plan(p, pl))
+	{
+		skr_set_error("--depth %d with %d children per node: the tables of %u rays exceed the scratch budget (SKR_LEVELS_BUDGET_MB)", p.max_depth,
+					  p.num_path_traces + (p.legacy_reflect ? 2 * p.n_lights : 0), SKR_SHADE_ROW);
+		return SKR_ERR_UNSUPPORTED;
+	}
+	rc = ensure_level_scratch(r, pl.total);
+	if(rc != SKR_OK) return rc;
+	p.node_scratch = r->d_nodes;
+	if(skr_scene_lds_bytes(p) + 32 > (size_t) r->lds_limit)
+	{
+		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", skr_scene_lds_bytes(p) + 32,
+					  p.n_spheres, p.n_lights, r->lds_limit);
+		return SKR_ERR_UNSUPPORTED;
+	}
+	ShadeRays q{};
+	q.rays = reinterpret_cast<const float4 *>(d_rays);
+	q.keys = d_keys;
+	q.out = d_rgbf;
+	q.n = n;
+	q.tree = r->d_blob + r->off_chunks;
+	q.trace = r->off_trace ? r->d_blob + r->off_trace : nullptr;
+	q.stride = (uint32_t) r->chunk_stride;
+	q.nchunks = r->sw.no_cull ? 0 : r->n_chunks;
+	q.cones = (r->cones && !r->sw.no_cones) ? 1 : 0;
+	q.trace_cones = (r->trace_cones && !r->sw.no_cones) ? 1 : 0;
+	q.ball = make_float4(r->trace_ball[0], r->trace_ball[1], r->trace_ball[2], r->trace_ball[3]);
+	r->last_levels = 0; // (the scratch no longer holds the node pipeline's tables of the last render)
+	g_variant = "shade_rays_g1";
+	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q));
 	return SKR_OK;
 }
 

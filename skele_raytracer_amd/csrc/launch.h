@@ -32,6 +32,23 @@ struct GPlan {
 	size_t off_ctr = 0, ctr_bytes = 0, total = 0;
 };
 
+// A shading query (include/skr.h skr_shade_rays) on the general level pipeline: the rays are its roots, as rows of RenderParams::width
+// rays (the last row partial), banded like a frame's rows.  The kernels' second argument (render_generic.hip).
+struct ShadeRays {
+	const float4 *rays;   // the caller's skr_ray[n]: {o, tmax} {d, ignore_triangle}
+	const uint32_t *keys; // the counter RNG's pixel word of each ray, or null (= the ray's index)
+	float *out;           // float[n][3]
+	uint32_t n, ray0;     // rays in all; the first ray of the band being launched
+	const float4 *tree;   // the renderer's chunk tree, its first set (SKR_CULL_LEVELS sets of `stride` rows)
+	const float4 *trace;  // the trace tree (skr_scene::trace_chunks), its first set; null: none
+	uint32_t stride;
+	int32_t nchunks;      // nodes of either tree; 0 = every triangle (no mesh, SKR_NO_CULL)
+	int32_t cones, trace_cones;
+	float4 ball;          // {centre, radius}: the trace tree holds for rays that start in it
+};
+// the rays of one row of a shading query's plan
+constexpr uint32_t SKR_SHADE_ROW = 1024;
+
 enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
 
 // Everything render_pass (api.cpp) sizes and checks and the launchers follow, computed once per launch.
@@ -86,7 +103,8 @@ hipError_t skr_launch_nodes(const RenderParams &p, const NodePlan &pl, hipStream
 hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level, uint32_t *n);
 // render_generic.hip
 bool skr_generic_plan(const RenderParams &p, GPlan &pl); // false: not one band fits the budget
-hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook);
+// q: a shading query (p.width = SKR_SHADE_ROW, p.out_rows its rows, p.aa_index its sample); null: a frame
+hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q = nullptr);
 // render_wave.hip
 hipError_t skr_launch_wave(const RenderParams &p, size_t lds, hipStream_t stream);
 hipError_t skr_launch_primary(const RenderParams &p, dim3 grid, size_t lds, hipStream_t stream);

@@ -28,6 +28,11 @@
 //
 // Every float operation and every order of summation is the reference's; the image is bit-identical to the oracle's
 // (tests/test_gpu_parity.py, test_shade_triangles.py, test_legacy_reflect.py run every mode through it).
+//
+// Shading queries (include/skr.h skr_shade_rays).  The ray source of level 1 and the sink of level 0 are a compile-time
+// parameter of the three kernels: an empty pack `Q...` is the camera and the image (frames), one ShadeRays the caller's rays and
+// their float[n][3] values.  The empty pack leaves a frame instance's argument block, and so its code, as it was.  Every level below
+// level 1 works on any ray unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -131,13 +136,50 @@ SKR_DEV GChild child_of(const SceneView &sv, const RenderParams &p, const GNode 
 	return ch;
 }
 
+// the query of an instance with a ShadeRays argument (the frame instances never call it)
+SKR_DEV ShadeRays query_of(const ShadeRays &q) { return q; }
+SKR_DEV ShadeRays query_of() { return ShadeRays{}; }
+
+// The tree a wave of query rays walks.  The bound is the smallest of SKR_CULL_DMAX_LIST above every live lane's
+// |d| (0.2 % short of it: room for the rounding of d.d; NaN and inf: none).  Then (a) level 1, every lane at the scene camera bit for
+// bit, or a level below (its rays start on surfaces): the renderer's tree, which holds for such origins; (b) level 1, every lane inside
+// the trace ball: the trace tree; (c) otherwise no tree: every triangle.  All three give the same answers.
+SKR_DEV void query_tree(SceneView &sv, const RenderParams &p, const ShadeRays &q, bool live, f3 o, f3 d)
+{
+	sv.nchunks = 0;
+	if(sv.nt == 0 || q.nchunks == 0) return;
+	constexpr float lim[SKR_CULL_LEVELS] = {(float) (4.0 * 4.0 * 0.998), (float) (32.0 * 32.0 * 0.998), (float) (256.0 * 256.0 * 0.998)};
+	const float dd = dot3(d, d);
+	int level = 0;
+	while(level < SKR_CULL_LEVELS && !__all(!live || dd < lim[level])) level++;
+	if(level == SKR_CULL_LEVELS) return;
+	const bool at_cam = __float_as_uint(o.x) == __float_as_uint(p.cam_pos.x) && __float_as_uint(o.y) == __float_as_uint(p.cam_pos.y) &&
+						__float_as_uint(o.z) == __float_as_uint(p.cam_pos.z);
+	const f3 e = o - mk3(q.ball.x, q.ball.y, q.ball.z);
+	if(p.g_level != 1 || __all(!live || at_cam))
+	{
+		sv.chunks = q.tree + (size_t) level * q.stride;
+		sv.cones = q.cones;
+		sv.nchunks = q.nchunks;
+	}
+	else if(q.trace && __all(!live || dot3(e, e) <= q.ball.w * q.ball.w))
+	{
+		sv.chunks = q.trace + (size_t) level * q.stride;
+		sv.cones = q.trace_cones;
+		sv.nchunks = q.nchunks;
+	}
+}
+
 } // namespace
 
 // =====================================================================================================================
 // trace: one lane per child ray of the level above (level 1: the primary rays)
 // =====================================================================================================================
-__global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p)
+template <typename... Q>
+__global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, const Q... qs)
 {
+	constexpr bool RAYS = sizeof...(Q) > 0;
+	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t A = p.g_arity; // children per node of the level above (1 at the camera level)
@@ -156,21 +198,36 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p)
 		ch.exists = false;
 		ch.o = ch.d = mk3(0, 0, 1);
 		ch.from_tri = -1;
+		float tmax = __builtin_inff();
 		if(valid)
 		{
 			if(p.g_level == 1)
-			{ // the camera: root `node` is pixel (x, row) of the band, its one child the primary ray (main.cpp:140-182)
-				const uint32_t bw = (uint32_t) p.width, row = p.band_row0 + node / bw, x = node - (node / bw) * bw;
-				const uint32_t y = image_row(p, row);
-				ch.exists = y < (uint32_t) p.height;
-				if(ch.exists)
-				{
-					ch.o = p.cam_pos;
-					primary_ray(p, (int) x, y, y * bw + x, p.aa_index, ch.d);
+			{
+				if constexpr(RAYS)
+				{ // the caller's ray {o, tmax} {d, ignore_triangle} (include/skr.h skr_ray); ignore_triangle only where a ray can carry one
+					const float4 ra = q.rays[2 * (size_t) (q.ray0 + node)], rb = q.rays[2 * (size_t) (q.ray0 + node) + 1];
+					ch.exists = true;
+					ch.o = mk3(ra.x, ra.y, ra.z);
+					ch.d = mk3(rb.x, rb.y, rb.z);
+					ch.from_tri = p.shade_triangles ? __float_as_int(rb.w) : -1;
+					tmax = ra.w;
+				}
+				else
+				{ // the camera: root `node` is pixel (x, row) of the band, its one child the primary ray (main.cpp:140-182)
+					const uint32_t bw = (uint32_t) p.width, row = p.band_row0 + node / bw, x = node - (node / bw) * bw;
+					const uint32_t y = image_row(p, row);
+					ch.exists = y < (uint32_t) p.height;
+					if(ch.exists)
+					{
+						ch.o = p.cam_pos;
+						primary_ray(p, (int) x, y, y * bw + x, p.aa_index, ch.d);
+					}
 				}
 			}
 			else ch = child_of(sv, p, load_node(p.g_nodes_src + (size_t) node * GNODE_ROWS), c);
 		}
+		SceneView svw = sv;
+		if constexpr(RAYS) query_tree(svw, p, q, ch.exists, ch.o, ch.d);
 		bool hit = false, black = false;
 		uint32_t surf = 0;
 		float t = 0.0f;
@@ -179,18 +236,24 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p)
 			cn.rays++;
 			const RayConst r = make_ray(ch.o, ch.d);
 			float tmin;
-			const int sph = closest_sphere(sv, r, tmin); // raytrace.h:152-165
+			int sph = closest_sphere(sv, r, tmin); // raytrace.h:152-165
+			float tcut = tmin;
+			if constexpr(RAYS)
+			{ // include/skr.h skr_shade_rays `tmax`: the winner is cut where it lies at or beyond tmax (a triangle only wins below the cut)
+				tcut = tmin < tmax ? tmin : tmax;
+				if(!(tmin < tmax)) sph = -1;
+			}
 			if(p.shade_triangles)
 			{
-				TriBest b{tmin, -1, -1};
-				if(sv.nt > 0) closest_triangle(sv, r, ch.from_tri, b);
+				TriBest b{tcut, -1, -1};
+				if(svw.nt > 0) closest_triangle(svw, r, ch.from_tri, b);
 				hit = sph >= 0 || b.slot >= 0;
 				surf = b.slot >= 0 ? (SURF_TRI | (uint32_t) b.slot) : (uint32_t) sph;
 				t = b.t;
 			}
 			else
 			{
-				black = sv.nt > 0 && any_triangle_closer(sv, r, tmin); // raytrace.h:171-186, :221-224
+				black = svw.nt > 0 && any_triangle_closer(svw, r, tcut); // raytrace.h:171-186, :221-224
 				hit = !black && sph >= 0;
 				surf = (uint32_t) sph;
 				t = tmin;
@@ -266,9 +329,11 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 } // namespace
 
 // FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
-template <bool FOG>
-__global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p)
+template <bool FOG, typename... Q>
+__global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
+	constexpr bool RAYS = sizeof...(Q) > 0;
+	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t per_region = (p.rc_cap + 255u) / 256u;
@@ -296,11 +361,22 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		f3 o;
 		if(p.g_level == 1)
 		{
-			const uint32_t bw = (uint32_t) p.width, row = p.band_row0 + parent / bw, x = parent - (parent / bw) * bw;
-			const uint32_t y = image_row(p, row);
-			n.pixel = y * bw + x;
-			n.node_id = 0u;
-			o = p.cam_pos;
+			if constexpr(RAYS)
+			{ // the counter RNG's pixel word: the ray's key
+				const uint32_t ray = q.ray0 + parent;
+				const float4 ra = q.rays[2 * (size_t) ray];
+				n.pixel = q.keys ? q.keys[ray] : ray;
+				n.node_id = 0u;
+				o = mk3(ra.x, ra.y, ra.z);
+			}
+			else
+			{
+				const uint32_t bw = (uint32_t) p.width, row = p.band_row0 + parent / bw, x = parent - (parent / bw) * bw;
+				const uint32_t y = image_row(p, row);
+				n.pixel = y * bw + x;
+				n.node_id = 0u;
+				o = p.cam_pos;
+			}
 		}
 		else
 		{
@@ -346,8 +422,11 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 // =====================================================================================================================
 // finalize: one lane per node of a level (level 0: per pixel of the band)
 // =====================================================================================================================
-__global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p)
+template <typename... Q>
+__global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p, const Q... qs)
 {
+	constexpr bool RAYS = sizeof...(Q) > 0;
+	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t n_nodes = *p.nd_count;
@@ -371,7 +450,13 @@ __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p
 		return ((mb >> bit) & 1ull) ? mk3(0, 0, 0) : p.background;
 	};
 	if(p.g_level == 0)
-	{ // the camera level: the pixel is its primary ray's value (rows outside the image have no ray and no pixel)
+	{
+		if constexpr(RAYS)
+		{ // the caller's ray: its value, unquantised
+			store3(q.out + (size_t) (q.ray0 + node) * 3, value_of(0u));
+			return;
+		}
+		// the camera level: the pixel is its primary ray's value (rows outside the image have no ray and no pixel)
 		const uint32_t bw = (uint32_t) p.width, row = p.band_row0 + node / bw, x = node - (node / bw) * bw;
 		if(image_row(p, row) < (uint32_t) p.height) emit_sample(p, row * bw + x, value_of(0u));
 		return;
@@ -426,29 +511,36 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl)
 	return rows > 0 && gplan_for(p, rows, pl);
 }
 
-hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook)
+hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q_in)
 {
 	RenderParams p = p_in;
 	char *base = reinterpret_cast<char *>(p.node_scratch);
 	uint32_t *ctr0 = reinterpret_cast<uint32_t *>(base + pl.off_ctr);
 	auto lvl_ctr = [&](int L) { return ctr0 + SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) L; };
-	const int nsamp = p.grid_size > 0 ? p.grid_size * p.grid_size : 1;
+	const int nsamp = (p.grid_size > 0 && !q_in) ? p.grid_size * p.grid_size : 1; // (a query: the one sample p.aa_index)
+	ShadeRays q = q_in ? *q_in : ShadeRays{};
 	const size_t lds = skr_scene_lds_bytes(p) + 32;
 	const uint32_t A = skr_tree_arity(p);
 	const int D = pl.levels;
 	hipError_t e = hipSuccess;
 	for(int s = 0; s < nsamp; s++)
 	{
-		p.aa_index = (uint32_t) s;
+		if(!q_in) p.aa_index = (uint32_t) s;
 		for(uint32_t row0 = 0; row0 < p.out_rows; row0 += pl.band_rows)
 		{ // every band is a complete pass
 			const uint32_t rows = p.out_rows - row0 < pl.band_rows ? p.out_rows - row0 : pl.band_rows;
 			const bool timed = hook && s == nsamp - 1 && row0 == 0; // (the first band of the last sample: a full-size band)
 			p.band_row0 = row0;
 			p.band_rows = rows;
+			uint32_t roots = rows * (uint32_t) p.width;
+			if(q_in)
+			{ // a query's band: its rays [ray0, ray0 + roots), the last row partial
+				q.ray0 = row0 * (uint32_t) p.width;
+				roots = q.n - q.ray0 < roots ? q.n - q.ray0 : roots;
+			}
 			e = hipMemsetAsync(ctr0, 0, pl.ctr_bytes, stream);
 			if(e != hipSuccess) return e;
-			e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctr0), (int) (rows * (uint32_t) p.width), 1, stream); // [0]: the band's roots
+			e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctr0), (int) roots, 1, stream); // [0]: the band's roots
 			if(e != hipSuccess) return e;
 			if(timed) skr_hook_start(hook, stream);
 			for(int L = 1; L <= D; L++)
@@ -464,12 +556,15 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.ixh = reinterpret_cast<uint4 *>(base + pl.off_hdr[L]);
 				const uint64_t wg_t = (pl.nodes_max[L - 1] * (uint64_t) p.g_arity + 255) / 256;
 				const unsigned grid_t = (unsigned) (wg_t < 49152u ? wg_t : 49152u);
-				hipLaunchKernelGGL(skr_gtrace_kernel, dim3(grid_t), dim3(256), lds, stream, p);
+				if(q_in) hipLaunchKernelGGL(skr_gtrace_kernel<ShadeRays>, dim3(grid_t), dim3(256), lds, stream, p, q);
+				else hipLaunchKernelGGL(skr_gtrace_kernel<>, dim3(grid_t), dim3(256), lds, stream, p);
 				p.g_arity = A; // (node ids of this level's hits: parent id * A + child + 1)
 				p.g_nodes_dst = L < D ? reinterpret_cast<float4 *>(base + pl.off_nodes[L]) : nullptr;
 				p.res_out = reinterpret_cast<float *>(base + pl.off_res[L]);
 				const unsigned grid_a = SKR_P1_REGIONS * ((pl.cap[L] + 255u) / 256u);
-				if(p.n_fog > 0) hipLaunchKernelGGL(skr_gactivate_kernel<true>, dim3(grid_a), dim3(256), lds, stream, p);
+				if(q_in && p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
+				else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
+				else if(p.n_fog > 0) hipLaunchKernelGGL(skr_gactivate_kernel<true>, dim3(grid_a), dim3(256), lds, stream, p);
 				else hipLaunchKernelGGL(skr_gactivate_kernel<false>, dim3(grid_a), dim3(256), lds, stream, p);
 			}
 			for(int L = D - 1; L >= 0; L--)
@@ -481,13 +576,15 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.ixh = reinterpret_cast<uint4 *>(base + pl.off_hdr[L + 1]);
 				p.res_in = reinterpret_cast<const float *>(base + pl.off_res[L + 1]);
 				p.res_out = L == 0 ? nullptr : reinterpret_cast<float *>(base + pl.off_res[L]);
-				hipLaunchKernelGGL(skr_gfinalize_kernel, dim3((unsigned) ((pl.nodes_max[L] + 255) / 256)), dim3(256), lds, stream, p);
+				const dim3 grid_f((unsigned) ((pl.nodes_max[L] + 255) / 256));
+				if(q_in) hipLaunchKernelGGL(skr_gfinalize_kernel<ShadeRays>, grid_f, dim3(256), lds, stream, p, q);
+				else hipLaunchKernelGGL(skr_gfinalize_kernel<>, grid_f, dim3(256), lds, stream, p);
 			}
 			if(timed) skr_hook_stop(hook, stream);
 			e = hipGetLastError();
 			if(e != hipSuccess) return e;
 		}
 	}
-	if(p.grid_size > 0) return skr_launch_resolve(p, stream);
+	if(p.grid_size > 0 && !q_in) return skr_launch_resolve(p, stream);
 	return hipSuccess;
 }
