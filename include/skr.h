@@ -28,6 +28,7 @@ extern "C" {
 #define SKR_ABI_VERSION 7 /* 7: skr_ray, skr_hit, skr_trace_rays, skr_camera_rays (ray queries), then skr_shade_rays (shading queries: an addition that leaves every
                             * existing entry point and struct as it was; SKR_HAS_SHADE_RAYS tells a caller it is there); 6: skr_scene_get_gi_masks; 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
 #define SKR_HAS_SHADE_RAYS 1
+#define SKR_HAS_DENOISE 1    /* skr_denoise, skr_render_denoised_host: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
 	SKR_OK = 0,
@@ -383,6 +384,40 @@ int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, sk
  *     fault and never change another ray's result. */
 int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_rays, uint32_t n, uint32_t sample, const uint32_t *d_keys, float *d_rgbf,
                    void *stream);
+
+/* ---- denoiser (new): an edge-aware filter for Monte-Carlo frames ----
+ * A spatial a-trous wavelet filter with edge-stopping weights (Dammertz 2010) and SVGF's luminance-variance guidance (Schied 2017)
+ * without its temporal part.  All arithmetic is binary32 + - * / max, not contracted, divide correctly rounded, taps summed in order:
+ *   - Guides: skr_hit[height][width], the first hits of the pixel-centre camera rays of the frame's options (grid_size = 0, sample 0)
+ *     traced by skr_trace_rays.  Class of a pixel: a miss is one class, each sphere index one, all triangles together one.
+ *   - Luminance l = 0.2126 r + 0.7152 g + 0.0722 b, left to right.
+ *   - Init: var_p = max(0, m2 - m1 * m1), m1 and m2 the means of l and l * l over the same-class in-image pixels of the 3x3 window
+ *     (row-major).
+ *   - Iteration i = 0 .. iterations - 1, s = 2^i: over the taps (dy, dx) in {-2..2}^2, row-major, q = p + s (dx, dy) in the image:
+ *     w = 0 where q's class differs from p's, else w = h * wn * wz * wl in that order, with h = k[dx+2] * k[dy+2],
+ *     k = {1/16, 1/4, 3/8, 1/4, 1/16}; wn = max(0, n_p . n_q)^128 (seven squarings); wz = D / (D + |t_p - t_q|) with
+ *     D = SIGMA_Z * t_p * (s * max(|dx|, |dy|)), 1 at the centre tap; wn = wz = 1 for a miss; wl = V / (V + (l_p - l_q)^2) with
+ *     V = SIGMA_L^2 * var_p + EPS.  c'_p = sum w c_q / sum w per channel, var'_p = sum w^2 var_q / (sum w)^2; a pixel whose weights
+ *     sum to no positive number (non-finite input) keeps its colour and variance.
+ *   - Output: the float frame after the last iteration and its bytes, quantised exactly as a frame is.
+ */
+#define SKR_DENOISE_SIGMA_L 4.0f
+#define SKR_DENOISE_SIGMA_Z 0.05f
+#define SKR_DENOISE_EPS 1e-6f
+#define SKR_DENOISE_ITERATIONS 5       /* the default of the CLIs and of Renderer.denoise */
+#define SKR_DENOISE_MAX_ITERATIONS 16
+/* Filter the DEVICE float frame d_rgbf[height][width][3] guided by the DEVICE d_hits[height][width] (16-byte aligned) into
+ * d_out_rgbf (float[height][width][3]) and / or d_out_rgb (uint8_t[height][width][3]): either may be NULL, not both.  Asynchronous
+ * on `stream`.  iterations 0 .. SKR_DENOISE_MAX_ITERATIONS; 0: the output is the input, bit for bit.  No whole-frame neighbours, no
+ * filter: there is no tiled or multi-GPU form.  Scratch (4 x 16 + 4 bytes a pixel) is the renderer's, grown on demand and kept.
+ * SKR_ERR_ARG: null or misaligned arrays, an output that overlaps an input or the other output, a size outside 1 .. 65536, iterations
+ * out of range.  Touches no work counter, no kernel timing and not skr_kernel_variant(). */
+int skr_denoise(skr_renderer *r, uint32_t width, uint32_t height, const float *d_rgbf, const skr_hit *d_hits, uint32_t iterations, float *d_out_rgbf,
+                uint8_t *d_out_rgb, void *stream);
+/* The whole frame, denoised, into HOST memory (h_rgb W*H*3 bytes and / or h_rgbf W*H*3 floats; either may be NULL, not both):
+ * the frame's float output (the mean of opt->progressive_passes passes), the guides skr_trace_rays(skr_camera_rays(opt with
+ * grid_size = 0, sample 0)), then skr_denoise.  Synchronous.  kernel_ms: device time of the whole sequence. */
+int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf, float *kernel_ms);
 
 /* ---- image file: replaces the inline writer main.cpp:199-211 ---- */
 int skr_write_ppm(const char *path, uint32_t width, uint32_t height, const uint8_t *rgb);

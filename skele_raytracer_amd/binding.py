@@ -16,8 +16,10 @@ EXPORTED_SYMBOLS = [
     "skr_rccl_available", "skr_multi_create", "skr_multi_destroy", "skr_multi_device_count", "skr_multi_renderer", "skr_multi_render_frame",
     "skr_multi_render_frame_host", "skr_comm_unique_id", "skr_comm_create", "skr_comm_destroy", "skr_comm_render_frame", "skr_comm_render_frame_async", "skr_comm_flush", "skr_comm_frame_to_host",
     "skr_shard_tiles_per_rank", "skr_shard_deinterleave_host", "skr_shard_lpt", "skr_shard_by_cost", "skr_shard_plan", "skr_shard_deinterleave_map_host", "skr_multi_render_frame_async", "skr_multi_flush",
-    "skr_trace_rays", "skr_camera_rays", "skr_shade_rays",
+    "skr_trace_rays", "skr_camera_rays", "skr_shade_rays", "skr_denoise", "skr_render_denoised_host",
 ]
+
+DENOISE_ITERATIONS = 5  # include/skr.h SKR_DENOISE_ITERATIONS: Renderer.denoise's default
 
 
 class SkrError(RuntimeError):
@@ -144,6 +146,8 @@ def lib():
     L.skr_trace_rays.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.skr_camera_rays.argtypes = [vp, C.POINTER(COptions), C.c_uint32, vp, vp]
     L.skr_shade_rays.argtypes = [vp, C.POINTER(COptions), vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.skr_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp]
+    L.skr_render_denoised_host.argtypes = [vp, C.POINTER(COptions), C.c_uint32, vp, vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -545,6 +549,39 @@ class Renderer:
             _check(lib().skr_shade_rays(self.h, C.byref(opt.c), rays.data_ptr(), n, int(sample), None if keys is None else keys.data_ptr(),
                                         out.data_ptr(), stream), "skr_shade_rays")
         return out
+
+    def denoise(self, rgbf, hits, iterations=DENOISE_ITERATIONS):
+        """The edge-aware denoiser (include/skr.h skr_denoise) on torch's current stream: rgbf float32 [H, W, 3] on this device, hits the
+        guides — a Hits or its float32 raw buffer ([H * W, 8] or [H, W, 8]) of the pixel-centre camera rays of the frame's options:
+        r.trace(r.camera_rays(opt_with_grid_0).view(-1, 8)), with opt_with_grid_0 = opt with jsample 0.  Returns (rgb uint8 [H, W, 3],
+        rgbf float32 [H, W, 3]) device tensors; iterations 0 .. 16, 0 = the input itself."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if rgbf.dtype != torch.float32 or rgbf.dim() != 3 or rgbf.shape[2] != 3 or rgbf.device != dev:
+            raise SkrError("denoise: rgbf must be a float32 [H, W, 3] tensor on %s" % dev)
+        h, w = int(rgbf.shape[0]), int(rgbf.shape[1])
+        raw = hits.raw if isinstance(hits, Hits) else hits
+        if raw.dtype != torch.float32 or raw.device != dev or raw.numel() != h * w * 8:
+            raise SkrError("denoise: hits must be the [%d, 8] float32 guides of the frame on %s (Renderer.trace)" % (h * w, dev))
+        rgbf, raw = rgbf.contiguous(), raw.contiguous()
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib().skr_denoise(self.h, w, h, rgbf.data_ptr(), raw.data_ptr(), int(iterations), out.data_ptr(), rgb.data_ptr(), stream), "skr_denoise")
+        return rgb, out
+
+    def render_denoised(self, opt, iterations=DENOISE_ITERATIONS, want_float=False):
+        """include/skr.h skr_render_denoised_host: the whole frame (the mean of opt's progressive passes), its guides and the denoiser,
+        into host arrays.  Returns (rgb uint8 [H, W, 3], rgbf float32 or None, device ms); the same bits as render(opt, want_float=True),
+        then denoise(rgbf, trace(camera_rays(opt with jsample 0).view(-1, 8)), iterations)."""
+        self._sync_switches()
+        rgb = np.zeros((opt.height, opt.width, 3), np.uint8)
+        rgbf = np.zeros((opt.height, opt.width, 3), np.float32) if want_float else None
+        ms = C.c_float()
+        _check(lib().skr_render_denoised_host(self.h, C.byref(opt.c), int(iterations), rgb.ctypes.data, rgbf.ctypes.data if want_float else None,
+                                              C.byref(ms)), "skr_render_denoised_host")
+        return rgb, rgbf, ms.value
 
 
 TRACE_ANY_HIT = 1  # include/skr.h SKR_TRACE_ANY_HIT

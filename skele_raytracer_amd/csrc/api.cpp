@@ -61,6 +61,10 @@ struct skr_renderer {
 	size_t prog_cap = 0;
 	uint8_t *d_frame = nullptr; // skr_render_frame_host
 	size_t frame_cap = 0;
+	void *d_dn = nullptr;     // skr_denoise: the ping-pong images, the guides and the classes (launch.h DenoiseScratch)
+	size_t dn_pixels = 0;
+	void *d_dnframe = nullptr; // skr_render_denoised_host: the frame, its camera rays and guides, the filtered frame and its bytes
+	size_t dnframe_pixels = 0;
 	hipEvent_t frame_e0 = nullptr, frame_e1 = nullptr;
 	// skr_renderer_kernel_ms: event pairs around the dominant kernel of recent launches
 	SkrSwitches sw; // the SKR_* development switches, read once (load_switches)
@@ -280,6 +284,8 @@ void skr_renderer_destroy(skr_renderer *r)
 	if(r->d_acc) (void) hipFree(r->d_acc);
 	if(r->d_prog) (void) hipFree(r->d_prog);
 	if(r->d_frame) (void) hipFree(r->d_frame);
+	if(r->d_dn) (void) hipFree(r->d_dn);
+	if(r->d_dnframe) (void) hipFree(r->d_dnframe);
 	if(r->frame_e0) (void) hipEventDestroy(r->frame_e0);
 	if(r->frame_e1) (void) hipEventDestroy(r->frame_e1);
 	for(SkrTimingHook &h : r->timed) { (void) hipEventDestroy(h.start); (void) hipEventDestroy(h.stop); }
@@ -908,10 +914,13 @@ int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t 
 	s.nt = r->info.n_triangles;
 	s.chunk = r->chunk_size;
 	s.stride = r->chunk_stride;
-	s.nchunks = (r->off_trace && !r->sw.no_cull) ? r->n_chunks : 0;
-	s.chunks = r->off_trace ? r->d_blob + r->off_trace : r->d_blob;
+	s.nchunks = r->sw.no_cull ? 0 : r->n_chunks;
+	s.tree = r->d_blob + r->off_chunks;
+	s.tree_cones = (r->cones && !r->sw.no_cones) ? 1 : 0;
+	s.chunks = r->off_trace ? r->d_blob + r->off_trace : nullptr;
 	s.cones = (r->trace_cones && !r->sw.no_cones) ? 1 : 0;
 	s.ball = make_float4(r->trace_ball[0], r->trace_ball[1], r->trace_ball[2], r->trace_ball[3]);
+	s.cam = f3{r->info.camera[0], r->info.camera[1], r->info.camera[2]};
 	SKR_HIP(skr_launch_trace(s, reinterpret_cast<const float4 *>(d_rays), n, any_hit, d_out, (hipStream_t) stream));
 	return SKR_OK;
 }
@@ -998,6 +1007,100 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	r->last_levels = 0; // (the scratch no longer holds the node pipeline's tables of the last render)
 	g_variant = "shade_rays_g1";
 	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q));
+	return SKR_OK;
+}
+
+// ---- the denoiser (denoise.hip): reads the caller's frame and guides, writes only the caller's outputs ----
+static bool overlaps(const void *a, size_t na, const void *b, size_t nb)
+{
+	if(!a || !b) return false;
+	const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+	return x < y + nb && y < x + na;
+}
+
+int skr_denoise(skr_renderer *r, uint32_t width, uint32_t height, const float *d_rgbf, const skr_hit *d_hits, uint32_t iterations, float *d_out_rgbf,
+				uint8_t *d_out_rgb, void *stream)
+{
+	if(!r || !d_rgbf || !d_hits || (!d_out_rgbf && !d_out_rgb) || ((uintptr_t) d_rgbf & 3) || ((uintptr_t) d_hits & 15) || ((uintptr_t) d_out_rgbf & 3))
+	{
+		skr_set_error("skr_denoise: bad argument (null or misaligned array, or no output)");
+		return SKR_ERR_ARG;
+	}
+	if(width == 0 || height == 0 || width > 65536 || height > 65536 || iterations > SKR_DENOISE_MAX_ITERATIONS)
+	{
+		skr_set_error("skr_denoise: bad size %ux%u or iterations %u (0 .. %d)", width, height, iterations, SKR_DENOISE_MAX_ITERATIONS);
+		return SKR_ERR_ARG;
+	}
+	const size_t n = (size_t) width * height;
+	if(overlaps(d_out_rgbf, n * 12, d_rgbf, n * 12) || overlaps(d_out_rgbf, n * 12, d_hits, n * sizeof(skr_hit)) || overlaps(d_out_rgb, n * 3, d_rgbf, n * 12) ||
+	   overlaps(d_out_rgb, n * 3, d_hits, n * sizeof(skr_hit)) || overlaps(d_out_rgbf, n * 12, d_out_rgb, n * 3))
+	{
+		skr_set_error("skr_denoise: an output overlaps an input or the other output");
+		return SKR_ERR_ARG;
+	}
+	SKR_HIP(hipSetDevice(r->device));
+	if(n > r->dn_pixels)
+	{
+		if(r->d_dn) SKR_HIP(hipFree(r->d_dn));
+		r->d_dn = nullptr;
+		r->dn_pixels = 0;
+		SKR_HIP(hipMalloc(&r->d_dn, n * (3 * sizeof(float4) + sizeof(uint32_t))));
+		r->dn_pixels = n;
+	}
+	DenoiseScratch b;
+	b.img[0] = reinterpret_cast<float4 *>(r->d_dn);
+	b.img[1] = b.img[0] + n;
+	b.guide = b.img[1] + n;
+	b.cls = reinterpret_cast<uint32_t *>(b.guide + n);
+	SKR_HIP(skr_launch_denoise(b, width, height, d_rgbf, reinterpret_cast<const float4 *>(d_hits), (int) iterations, d_out_rgbf, d_out_rgb, (hipStream_t) stream));
+	return SKR_OK;
+}
+
+int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf, float *kernel_ms)
+{
+	if(!r || !opt || (!h_rgb && !h_rgbf) || iterations > SKR_DENOISE_MAX_ITERATIONS)
+	{
+		skr_set_error("skr_render_denoised_host: bad argument");
+		return SKR_ERR_ARG;
+	}
+	int rc = check_options(opt); // before anything is sized from width x height
+	if(rc != SKR_OK) return rc;
+	SKR_HIP(hipSetDevice(r->device));
+	const size_t n = (size_t) opt->width * opt->height;
+	if(n > r->dnframe_pixels)
+	{ // 12 (frame) + 32 (rays) + 32 (guides) + 12 (filtered) + 3 (bytes) per pixel; every part starts 16-byte aligned
+		if(r->d_dnframe) SKR_HIP(hipFree(r->d_dnframe));
+		r->d_dnframe = nullptr;
+		r->dnframe_pixels = 0;
+		SKR_HIP(hipMalloc(&r->d_dnframe, n * 91 + 64));
+		r->dnframe_pixels = n;
+	}
+	auto at = [&](size_t off) { return reinterpret_cast<char *>(r->d_dnframe) + off; };
+	const size_t o_frame = 0, o_rays = (o_frame + n * 12 + 15) & ~(size_t) 15, o_hits = o_rays + n * 32, o_out = o_hits + n * 32, o_rgb = o_out + n * 12;
+	float *frame = reinterpret_cast<float *>(at(o_frame)), *out = reinterpret_cast<float *>(at(o_out));
+	skr_ray *rays = reinterpret_cast<skr_ray *>(at(o_rays));
+	skr_hit *hits = reinterpret_cast<skr_hit *>(at(o_hits));
+	uint8_t *rgb = reinterpret_cast<uint8_t *>(at(o_rgb));
+	if(!r->frame_e0) SKR_HIP(hipEventCreate(&r->frame_e0));
+	if(!r->frame_e1) SKR_HIP(hipEventCreate(&r->frame_e1));
+	SKR_HIP(hipEventRecord(r->frame_e0, nullptr));
+	rc = skr_render_tiles(r, opt, (uint32_t) opt->height, 0, 1, nullptr, frame, nullptr); // (the K-pass mean under progressive_passes)
+	if(rc != SKR_OK) return rc;
+	skr_options guide_opt = *opt;
+	guide_opt.grid_size = 0; // the pixel centres
+	rc = skr_camera_rays(r, &guide_opt, 0, rays, nullptr);
+	if(rc != SKR_OK) return rc;
+	rc = skr_trace_rays(r, rays, (uint32_t) n, 0, hits, nullptr);
+	if(rc != SKR_OK) return rc;
+	rc = skr_denoise(r, (uint32_t) opt->width, (uint32_t) opt->height, frame, hits, iterations, h_rgbf ? out : nullptr, h_rgb ? rgb : nullptr, nullptr);
+	if(rc != SKR_OK) return rc;
+	SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
+	if(h_rgb) SKR_HIP(hipMemcpy(h_rgb, rgb, n * 3, hipMemcpyDeviceToHost));
+	if(h_rgbf) SKR_HIP(hipMemcpy(h_rgbf, out, n * 12, hipMemcpyDeviceToHost));
+	float ms = 0;
+	SKR_HIP(hipEventSynchronize(r->frame_e1));
+	SKR_HIP(hipEventElapsedTime(&ms, r->frame_e0, r->frame_e1));
+	if(kernel_ms) *kernel_ms = ms;
 	return SKR_OK;
 }
 

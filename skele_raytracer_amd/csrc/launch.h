@@ -114,13 +114,23 @@ hipError_t skr_launch_camec(const float4 *geom, int ns, f3 cam_pos, float4 *out,
 struct TraceScene {
 	const float4 *geom;   // sphere rows {centre, r^2} (HBM; the rows behind them are readable: the blob's padding)
 	const float4 *tris;   // device triangles, 3 float4 each (scene_host.h)
-	const float4 *chunks; // the trace tree (scene_host.h trace_chunks): SKR_CULL_LEVELS sets of `stride` float4
+	const float4 *tree;   // the renderer's chunk tree, its first set (SKR_CULL_LEVELS sets of `stride` float4): waves of camera rays
+	const float4 *chunks; // the trace tree (scene_host.h trace_chunks), its first set; null: none
 	size_t stride;
-	int32_t ns, nt, nchunks, chunk, cones;
-	float4 ball;          // {centre, radius}: the tree holds for rays that start in it
+	int32_t ns, nt, nchunks, chunk, cones, tree_cones; // nchunks: nodes of either tree, 0 = every triangle; cones: the trace tree's
+	float4 ball;          // {centre, radius}: the trace tree holds for rays that start in it
+	f3 cam;               // the scene camera: the renderer's tree holds for rays that start there
 };
 hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream);
 hipError_t skr_launch_camera_rays(const RenderParams &p, float4 *rays, hipStream_t stream);
+// denoise.hip: the denoiser (include/skr.h skr_denoise).  Not a render: no plan, no counters, no timing.
+struct DenoiseScratch {
+	float4 *img[2]; // the {r, g, b, var} ping-pong images (img[1] first holds {r, g, b, l})
+	float4 *guide;  // {n, t} of every pixel's guide hit
+	uint32_t *cls;  // its class: the sphere index, 0xFFFFFFFE for every triangle, 0xFFFFFFFF for a miss
+};
+hipError_t skr_launch_denoise(const DenoiseScratch &b, uint32_t w, uint32_t h, const float *rgbf, const float4 *hits, int iterations, float *out_rgbf,
+							  uint8_t *out_rgb, hipStream_t stream);
 // accumulate.hip
 hipError_t skr_launch_accumulate(float *acc, const float *frame, size_t n, int first, hipStream_t stream);
 hipError_t skr_launch_resolve_accumulated(const float *acc, uint32_t passes, uint32_t width, uint32_t out_rows, uint32_t height, uint32_t tile_rows,

@@ -5,7 +5,7 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --scn-fog, --scn-fov, --shade-triangles, --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm.
+// --scn-fog, --scn-fov, --shade-triangles, --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L.
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +27,8 @@ int main(int argc, char *argv[])
 	bool scn_fog = false, scn_fov = false, fov_given = false; // --scn-fog, --scn-fov (new: DESIGN.md "Spherical fog", "Camera half-angle")
 	bool sharded = false; // --gpus given (even --gpus 1): the frame goes through the multi-GPU path
 	uint32_t tile_rows = 8;
+	int denoise = 0;  // --denoise L: the frame filtered by L iterations of the denoiser (include/skr.h skr_render_denoised_host)
+	bool denoised = false;
 	uint32_t progressive_every = 0; // --progressive-every M: the output file is rewritten after every M passes (the headless "viewer")
 	const char *format = "ppm";     // --format ppm | png | pfm (new; the reference writes P6 whatever the name says)
 
@@ -128,6 +130,7 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--progressive") && has_next) option.progressive_passes = atoi(argv[i + 1]) > 1 ? atoi(argv[i + 1]) : 1; // new: mean of K frames, seeds seed..seed+K-1
 		if(!strcmp(argv[i], "--progressive-every") && has_next) progressive_every = (uint32_t) (atoi(argv[i + 1]) > 0 ? atoi(argv[i + 1]) : 0);
 		if(!strcmp(argv[i], "--format") && has_next) format = argv[i + 1];
+		if(!strcmp(argv[i], "--denoise") && has_next) { denoise = atoi(argv[i + 1]); denoised = true; } // new: edge-aware denoiser, L iterations
 	}
 	if(!path)
 	{
@@ -181,6 +184,12 @@ int main(int argc, char *argv[])
 		std::cerr << "raytracer: --format pfm and --progressive-every need the single-device path (drop --gpus)" << std::endl;
 		return SKR_ERR_ARG;
 	}
+	if(denoised && ((sharded && gpus > 1) || progressive_every || denoise < 0 || denoise > SKR_DENOISE_MAX_ITERATIONS))
+	{ // the filter needs whole-frame neighbours (the ranks exchange quantised tiles) and filters the finished mean only
+		std::cerr << "raytracer: --denoise takes 0 .. " << SKR_DENOISE_MAX_ITERATIONS << " iterations on the single-device path (no --gpus N > 1, no --progressive-every)" << std::endl;
+		return SKR_ERR_ARG;
+	}
+	if(denoised) sharded = false; // (--gpus 1: the one device)
 	std::vector<uint8_t> rgb((size_t) option.width * option.height * 3);
 	std::vector<float> rgbf(want_pfm ? rgb.size() : 0);
 	struct Out {
@@ -227,7 +236,9 @@ int main(int argc, char *argv[])
 			return 0;
 		};
 		rc = skr_renderer_create(scene, device, &renderer);
-		if(rc == SKR_OK)
+		if(rc == SKR_OK && denoised)
+			rc = skr_render_denoised_host(renderer, &option, (uint32_t) denoise, want_pfm ? nullptr : rgb.data(), want_pfm ? rgbf.data() : nullptr, &ms);
+		else if(rc == SKR_OK)
 			rc = skr_render_progressive_host(renderer, &option, progressive_every, want_pfm ? nullptr : rgb.data(), want_pfm ? rgbf.data() : nullptr,
 											 progressive_every ? progress : nullptr, &show, &ms);
 		if(rc != SKR_OK)

@@ -140,34 +140,13 @@ SKR_DEV GChild child_of(const SceneView &sv, const RenderParams &p, const GNode 
 SKR_DEV ShadeRays query_of(const ShadeRays &q) { return q; }
 SKR_DEV ShadeRays query_of() { return ShadeRays{}; }
 
-// The tree a wave of query rays walks.  The bound is the smallest of SKR_CULL_DMAX_LIST above every live lane's
-// |d| (0.2 % short of it: room for the rounding of d.d; NaN and inf: none).  Then (a) level 1, every lane at the scene camera bit for
-// bit, or a level below (its rays start on surfaces): the renderer's tree, which holds for such origins; (b) level 1, every lane inside
-// the trace ball: the trace tree; (c) otherwise no tree: every triangle.  All three give the same answers.
+// The tree a wave of query rays walks (wave_common.h pick_query_tree): at level 1 the renderer's tree where every lane
+// starts at the scene camera, else the trace tree where every lane starts in its ball; at a level below (origins on surfaces) the
+// renderer's tree.
 SKR_DEV void query_tree(SceneView &sv, const RenderParams &p, const ShadeRays &q, bool live, f3 o, f3 d)
 {
-	sv.nchunks = 0;
-	if(sv.nt == 0 || q.nchunks == 0) return;
-	constexpr float lim[SKR_CULL_LEVELS] = {(float) (4.0 * 4.0 * 0.998), (float) (32.0 * 32.0 * 0.998), (float) (256.0 * 256.0 * 0.998)};
-	const float dd = dot3(d, d);
-	int level = 0;
-	while(level < SKR_CULL_LEVELS && !__all(!live || dd < lim[level])) level++;
-	if(level == SKR_CULL_LEVELS) return;
-	const bool at_cam = __float_as_uint(o.x) == __float_as_uint(p.cam_pos.x) && __float_as_uint(o.y) == __float_as_uint(p.cam_pos.y) &&
-						__float_as_uint(o.z) == __float_as_uint(p.cam_pos.z);
-	const f3 e = o - mk3(q.ball.x, q.ball.y, q.ball.z);
-	if(p.g_level != 1 || __all(!live || at_cam))
-	{
-		sv.chunks = q.tree + (size_t) level * q.stride;
-		sv.cones = q.cones;
-		sv.nchunks = q.nchunks;
-	}
-	else if(q.trace && __all(!live || dot3(e, e) <= q.ball.w * q.ball.w))
-	{
-		sv.chunks = q.trace + (size_t) level * q.stride;
-		sv.cones = q.trace_cones;
-		sv.nchunks = q.nchunks;
-	}
+	const QueryTrees t{q.tree, q.trace, q.stride, q.nchunks, q.cones, q.trace_cones, p.cam_pos, q.ball};
+	pick_query_tree(sv, t, p.g_level != 1, live, o, d);
 }
 
 } // namespace

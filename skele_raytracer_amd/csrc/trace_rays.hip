@@ -6,8 +6,9 @@
 //
 // Culling.  The renderer's chunk tree holds for rays that start at the camera or on a sphere.  Query rays start anywhere, so the
 // scene carries a second tree built for rays that start anywhere in a ball around the scene (scene_host.cpp trace_chunks), one set
-// per bound on |d| like the renderer's.  A wave whose 64 rays all start inside the ball walks the set of the smallest bound above
-// every lane's |d|; any other wave tests every triangle.  Either way every lane gets the exact answer.
+// per bound on |d| like the renderer's.  A wave whose live rays all start at the scene camera bit for bit walks the renderer's set
+// of the smallest bound above every lane's |d| (as a shading query's camera wave does); one whose live rays all start
+// inside the ball walks the trace tree's; any other wave tests every triangle.  Either way every lane gets the exact answer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -16,9 +17,10 @@
 
 namespace {
 
-// The scene view of one wave: the trace tree where it holds for every lane (wave-uniform decision), else no tree.
+// The scene view of one wave: the tree pick_query_tree chooses for it (wave-uniform decision) — the renderer's where every live lane
+// starts at the scene camera, else the trace tree where every live lane starts in its ball — or no tree.
 template <bool TRI>
-SKR_DEV SceneView trace_view(const TraceScene &s, f3 o, f3 d)
+SKR_DEV SceneView trace_view(const TraceScene &s, bool live, f3 o, f3 d)
 {
 	SceneView sv{};
 	sv.geom = s.geom; // (closest_sphere_exact's rows: HBM here)
@@ -26,29 +28,15 @@ SKR_DEV SceneView trace_view(const TraceScene &s, f3 o, f3 d)
 	sv.ns = s.ns;
 	sv.tris = s.tris;
 	sv.nt = TRI ? s.nt : 0;
-	sv.chunks = s.chunks;
+	sv.chunks = s.tree;
 	sv.nchunks = 0;
 	sv.chunk = s.chunk;
 	sv.cones = s.cones;
 	sv.tri_work = nullptr; // a query counts nothing
-	if(TRI && s.nchunks > 0)
+	if(TRI)
 	{
-		const f3 e = o - mk3(s.ball.x, s.ball.y, s.ball.z);
-		const float dd = dot3(d, d);
-		// the bounds of SKR_CULL_DMAX_LIST squared, 0.2 % short of them: room for the rounding of dd (NaN and inf: no tree)
-		constexpr float lim[SKR_CULL_LEVELS] = {(float) (4.0 * 4.0 * 0.998), (float) (32.0 * 32.0 * 0.998), (float) (256.0 * 256.0 * 0.998)};
-		if(__all(dot3(e, e) <= s.ball.w * s.ball.w))
-		{
-			for(int level = 0; level < SKR_CULL_LEVELS; level++)
-			{
-				if(__all(dd < lim[level]))
-				{
-					sv.nchunks = s.nchunks;
-					sv.chunks = s.chunks + (size_t) level * s.stride;
-					break;
-				}
-			}
-		}
+		const QueryTrees q{s.tree, s.chunks, s.stride, s.nchunks, s.tree_cones, s.cones, s.cam, s.ball};
+		pick_query_tree(sv, q, false, live, o, d);
 	}
 	return sv;
 }
@@ -151,7 +139,7 @@ __global__ __launch_bounds__(256) void skr_ray_query_kernel(const TraceScene s, 
 	const float tmax = ra.w;
 	const int ignore = __float_as_int(rb.w);
 	const RayConst r = make_ray(o, d);
-	const SceneView sv = trace_view<TRI>(s, o, d);
+	const SceneView sv = trace_view<TRI>(s, valid, o, d);
 	if constexpr(ANY)
 	{
 		bool occ = false;

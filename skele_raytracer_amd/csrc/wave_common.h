@@ -286,4 +286,44 @@ SKR_DEV void region_prefix(const RenderParams &p, uint32_t *s_pre, bool publish)
 	__syncthreads();
 }
 
+// The trees a wave of query rays may walk: the renderer's chunk tree and the trace tree (null: none), each
+// SKR_CULL_LEVELS sets of `stride` rows of `nchunks` nodes.
+struct QueryTrees {
+	const float4 *tree, *trace;
+	size_t stride;
+	int nchunks, cones, trace_cones;
+	f3 cam;     // the scene camera
+	float4 ball; // {centre, radius}: the trace tree holds for rays that start in it
+};
+
+// The tree a wave of query rays walks, into sv.chunks / cones / nchunks (nchunks = 0: every triangle).  The bound is
+// the smallest of SKR_CULL_DMAX_LIST above every live lane's |d| (0.2 % short of it: room for the rounding of d.d; NaN and inf: none).
+// Then (a) every live lane at the scene camera bit for bit, or `surface` (the rays start on surfaces): the renderer's tree, which holds
+// for such origins; (b) every live lane inside the trace ball: the trace tree; (c) otherwise no tree.  All three give the same answers.
+SKR_DEV void pick_query_tree(SceneView &sv, const QueryTrees &q, bool surface, bool live, f3 o, f3 d)
+{
+	sv.nchunks = 0;
+	if(sv.nt == 0 || q.nchunks == 0) return;
+	constexpr float lim[SKR_CULL_LEVELS] = {(float) (4.0 * 4.0 * 0.998), (float) (32.0 * 32.0 * 0.998), (float) (256.0 * 256.0 * 0.998)};
+	const float dd = dot3(d, d);
+	int level = 0;
+	while(level < SKR_CULL_LEVELS && !__all(!live || dd < lim[level])) level++;
+	if(level == SKR_CULL_LEVELS) return;
+	const bool at_cam = __float_as_uint(o.x) == __float_as_uint(q.cam.x) && __float_as_uint(o.y) == __float_as_uint(q.cam.y) &&
+						__float_as_uint(o.z) == __float_as_uint(q.cam.z);
+	const f3 e = o - mk3(q.ball.x, q.ball.y, q.ball.z);
+	if(surface || __all(!live || at_cam))
+	{
+		sv.chunks = q.tree + (size_t) level * q.stride;
+		sv.cones = q.cones;
+		sv.nchunks = q.nchunks;
+	}
+	else if(q.trace && __all(!live || dot3(e, e) <= q.ball.w * q.ball.w))
+	{
+		sv.chunks = q.trace + (size_t) level * q.stride;
+		sv.cones = q.trace_cones;
+		sv.nchunks = q.nchunks;
+	}
+}
+
 } // namespace

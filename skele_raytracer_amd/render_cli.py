@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm]
+           [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
            --gillum 64 --jsample 5 --shadow            # BASELINE config 5
@@ -91,6 +91,8 @@ def _parse(argv):
             opt["progressive_every"] = max(0, value(i, _atoi, "progressive-every takes a number of passes"))
         elif a == "--format":
             opt["format"] = value(i, str, "format takes ppm, png or pfm")
+        elif a == "--denoise":
+            opt["denoise"] = value(i, _atoi, "denoise takes a number of iterations")
         elif a == "--seed":
             opt["seed"] = value(i, _atoi, "seed takes an int")
         elif a == "--tile-rows":
@@ -172,6 +174,23 @@ def main(argv=None):
             print("raytracer: --format pfm and --progressive-every need the single-device path", file=sys.stderr)
         dist.destroy_process_group()
         return 2
+    denoise = o.get("denoise")
+    if denoise is not None and (world > 1 or every or not 0 <= denoise <= 16):
+        # the filter needs whole-frame neighbours (the ranks exchange quantised tiles) and filters the finished mean only
+        if rank == 0:
+            print("raytracer: --denoise takes 0 .. 16 iterations on the single-device path (no world > 1, no --progressive-every)", file=sys.stderr)
+        if world > 1:
+            dist.destroy_process_group()
+        return 2
+    if denoise is not None:
+        rgb, rgbf, ms = r.render_denoised(opt, denoise, want_float=(fmt == "pfm"))
+        if fmt == "pfm":
+            skr.write_pfm(o["output"], rgbf)
+        else:
+            (skr.write_png if fmt == "png" else skr.write_ppm)(o["output"], rgb)
+        print("***\nWROTE TO PPM\n***")  # main.cpp:213
+        print("1 GPU(s), %dx%d, %.3f ms (device, denoised), kernel %s" % (o["width"], o["height"], ms, r.kernel_variant()), file=sys.stderr)
+        return 0
     if fmt == "pfm" or every:
         # the file is the window (main.cpp:183-197 redraws its SDL window as rows finish): rewritten with the mean so far
         def write(rgb, rgbf):
