@@ -484,7 +484,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.rgb = d_rgb;
 	p.rgbf = d_rgbf;
 	LaunchPlan lp;
-	if(!skr_plan_launch(p, lp))
+	if(!skr_plan_launch(p, (size_t) r->lds_limit, lp))
 	{
 		skr_set_error("--depth %d with %d children per node: the tables of one output row exceed the scratch budget (SKR_LEVELS_BUDGET_MB)", p.max_depth, p.num_path_traces + (p.legacy_reflect ? 2 * p.n_lights : 0));
 		return SKR_ERR_UNSUPPORTED;
@@ -986,9 +986,9 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	rc = ensure_level_scratch(r, pl.total);
 	if(rc != SKR_OK) return rc;
 	p.node_scratch = r->d_nodes;
-	if(skr_scene_lds_bytes(p) + 32 > (size_t) r->lds_limit)
+	if(skr_scene_kernels_lds(p) > (size_t) r->lds_limit)
 	{
-		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", skr_scene_lds_bytes(p) + 32,
+		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", skr_scene_kernels_lds(p),
 					  p.n_spheres, p.n_lights, r->lds_limit);
 		return SKR_ERR_UNSUPPORTED;
 	}

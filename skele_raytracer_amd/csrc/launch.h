@@ -19,6 +19,7 @@ struct NodePlan {
 	size_t off_nodes[SKR_NODE_LEVELS_MAX] = {}, off_shade[SKR_NODE_LEVELS_MAX] = {}, off_recs[SKR_NODE_LEVELS_MAX] = {}, off_res[SKR_NODE_LEVELS_MAX] = {}, off_ixh[SKR_NODE_LEVELS_MAX] = {};
 	size_t off_ctr = 0, ctr_bytes = 0, total = 0, banded = 0;
 	size_t lds_leaf = 0;     // the leaf kernel's workgroup LDS: the scene + the per-wave rings and windows
+	size_t lds = 0;          // the largest workgroup LDS among the schedule's kernels (flat: skr_scene_kernels_lds; persistent: lds_leaf)
 };
 
 // The plan of one band of the general level pipeline (render_generic.hip).
@@ -67,6 +68,14 @@ struct LaunchPlan {
 // the scene SoA every kernel stages into LDS (wave_common.h stage_scene): 4 rows per sphere, a zero row, 2 rows per light
 static inline size_t skr_scene_lds_bytes(const RenderParams &p) { return ((size_t) 4 * p.n_spheres + 1 + 2 * p.n_lights) * 16; }
 
+// The workgroup LDS of the kernels that keep only the scene there: the node pipeline's primary, trace, activate and flat shade-leaf
+// kernels and the general level pipeline's.  Their dynamic LDS is the scene + 32 bytes; the activate and shade-leaf kernels add the
+// prefix sums (SKR_PREFIX_WORDS words of static LDS, ahead of the dynamic LDS on a 16-byte boundary).  The runtime does not refuse a
+// launch whose static + dynamic LDS exceeds the device's: on gfx950 such a launch (2 558 spheres under fog: 163 792 + 272 bytes) ran
+// and faulted.  So the plans count both.
+constexpr size_t SKR_PREFIX_LDS = ((size_t) SKR_PREFIX_WORDS * sizeof(uint32_t) + 15) & ~(size_t) 15;
+static inline size_t skr_scene_kernels_lds(const RenderParams &p) { return skr_scene_lds_bytes(p) + 32 + SKR_PREFIX_LDS; }
+
 // children per node of the --gillum tree: N --gillum rays, and under --legacy-reflect 2 per light (the arity of the counter RNG's
 // node ids, include/skr.h)
 static inline uint32_t skr_tree_arity(const RenderParams &p) { return (uint32_t) (p.monte_carlo ? p.num_path_traces : 0) + (p.legacy_reflect ? 2u * (uint32_t) p.n_lights : 0u); }
@@ -94,11 +103,12 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 }
 
 // render_kernel.hip
-bool skr_plan_launch(const RenderParams &p, LaunchPlan &lp); // false: the launch takes a level pipeline and not one band of it fits the budget
+// lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp); // false: the launch takes a level pipeline and not one band of it fits the budget
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook);
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream);
 // render_nodes.hip
-bool skr_nodes_plan(const RenderParams &p, NodePlan &pl); // false: the node pipeline does not take this launch
+bool skr_nodes_plan(const RenderParams &p, size_t lds_limit, NodePlan &pl); // false: the node pipeline does not take this launch
 hipError_t skr_launch_nodes(const RenderParams &p, const NodePlan &pl, hipStream_t stream, const SkrTimingHook *hook);
 hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level, uint32_t *n);
 // render_generic.hip

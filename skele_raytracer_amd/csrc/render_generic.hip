@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 	const uint32_t region = (uint32_t) blockIdx.x / per_region, pos0 = ((uint32_t) blockIdx.x % per_region) * 256u;
 	const uint32_t cnt = *lc_count(p.rc_ctr, region);
 	if(pos0 >= cnt && blockIdx.x != 0) return;
-	__shared__ uint32_t s_pre[65];
+	__shared__ uint32_t s_pre[SKR_PREFIX_WORDS];
 	region_prefix(p, s_pre, blockIdx.x == 0); // (workgroup 0 leaves the level's record count for the kernels that follow)
 	if(pos0 >= cnt) return;
 	const SceneView sv = stage_scene(p, lds4, true);

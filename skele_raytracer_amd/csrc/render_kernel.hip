@@ -35,30 +35,32 @@ static size_t direct_lds_bytes(const RenderParams &p)
 // Which kernels render this launch, and what they need.  In this order:
 //   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, and every tree
 //     (shade() recurses: max_depth > 1; api.cpp folds --depth to 1 where it cannot, raytrace.h:208-218) the node pipeline does not;
-//   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget;
-//   * the direct kernel takes the rest.
+//   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget and its kernels
+//     fit the device's LDS;
+//   * the direct kernel takes the rest, unless the scene leaves it no room for its tile: then the general pipeline does.
+// A launch is refused (api.cpp render_pass: lp.lds_bytes > the device's LDS) only where no path fits.
 // SKR_PIPELINE=generic forces the general pipeline for every launch, SKR_PIPELINE=nodes keeps triangle meshes on the node pipeline
 // (tests, A/B runs).
-bool skr_plan_launch(const RenderParams &p, LaunchPlan &lp)
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp)
 {
 	lp = LaunchPlan();
 	const bool generic_only = p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0;
-	if(!generic_only && skr_nodes_plan(p, lp.nodes))
+	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
 		lp.path = SKR_PATH_NODES;
 		lp.variant = lp.nodes.flat ? "node_levels_v5_flat" : "node_levels_v5";
 		lp.scratch_bytes = lp.nodes.total;
-		lp.lds_bytes = lp.nodes.lds_leaf;
+		lp.lds_bytes = lp.nodes.lds;
 		lp.off_ctr = lp.nodes.off_ctr;
 		lp.levels = lp.nodes.levels;
 	}
-	else if(generic_only || p.max_depth > 1)
-	{
+	else if(generic_only || p.max_depth > 1 || direct_lds_bytes(p) > lds_limit)
+	{ // (a frame without a tree whose scene leaves the direct kernel no room for its tile: the general pipeline renders it as well)
 		lp.path = SKR_PATH_GENERIC;
 		lp.variant = "level_pipeline_g1";
 		if(!skr_generic_plan(p, lp.generic)) return false;
 		lp.scratch_bytes = lp.generic.total;
-		lp.lds_bytes = skr_scene_lds_bytes(p) + 32;
+		lp.lds_bytes = skr_scene_kernels_lds(p);
 	}
 	else
 	{

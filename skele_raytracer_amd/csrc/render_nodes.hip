@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_activate_kernel(const 
 	const uint32_t region = (uint32_t) blockIdx.x / per_region, pos0 = ((uint32_t) blockIdx.x % per_region) * 256u;
 	const uint32_t cnt = *lc_count(p.rc_ctr, region);
 	if(pos0 >= cnt && blockIdx.x != 0) return;
-	__shared__ uint32_t s_pre[65];
+	__shared__ uint32_t s_pre[SKR_PREFIX_WORDS];
 	region_prefix(p, s_pre, blockIdx.x == 0); // (workgroup 0 leaves the level's record count for the kernels that follow)
 	if(pos0 >= cnt) return;
 	const SceneView sv = stage_scene(p, lds4, TRIS);
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_shade_leaf_kernel(cons
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
-	__shared__ uint32_t prefix[65];
+	__shared__ uint32_t prefix[SKR_PREFIX_WORDS];
 	region_prefix(p, prefix, false);
 	const uint32_t total = prefix[64];
 	if((uint32_t) blockIdx.x * 256u >= total) return; // (uniform per workgroup)
@@ -827,8 +827,9 @@ static bool plan_bands(const RenderParams &p, bool flat, NodePlan &pl)
 // fit the budget in bands.  SKR_PIPELINE=nodes forces it wherever it applies; other values of SKR_PIPELINE exclude it.  Triangle meshes
 // go to the general level pipeline (render_generic.hip: one lane per ray, one walk of the culling tree per 64 rays; test.scn 640x360
 // --gillum 4: 1.18 ms there against 2.15 ms here, where a lane walks the tree once per sibling); a handful of triangles (spheres1.scn
-// has two) are tested in line by the pair kernels.
-bool skr_nodes_plan(const RenderParams &p, NodePlan &pl)
+// has two) are tested in line by the pair kernels.  A scene whose table leaves no room in the device's LDS (lds_limit) for the leaf
+// kernel's rings takes the flat schedule, SKR_FLAT=0 or not; one that leaves no room for the flat schedule's kernels either is not taken.
+bool skr_nodes_plan(const RenderParams &p, size_t lds_limit, NodePlan &pl)
 {
 	const bool forced = p.sw.pipeline == SKR_PIPE_NODES;
 	if(p.sw.pipeline != SKR_PIPE_AUTO && !forced) return false;
@@ -836,12 +837,20 @@ bool skr_nodes_plan(const RenderParams &p, NodePlan &pl)
 	if(!(p.monte_carlo && p.n_spheres > 0 && p.n_spheres < 65536 && p.max_depth >= 2 && p.num_path_traces > 0 && p.num_path_traces <= 256)) return false;
 	if(!forced && p.n_tris > 64) return false;
 	pl.lds_leaf = skr_scene_lds_bytes(p) + 32 + (size_t) 4 * LEAF2_WAVE_FLOATS * sizeof(float);
-	if(nodes_flat_wanted(p))
-	{ // flat only in one piece (SKR_FLAT=1: wherever it fits at all): in bands the persistent kernel is the better schedule
+	if(skr_scene_kernels_lds(p) > lds_limit) return false;
+	const bool leaf_fits = pl.lds_leaf <= lds_limit;
+	if(nodes_flat_wanted(p) || !leaf_fits)
+	{ // flat only in one piece (SKR_FLAT=1, or no room for the leaf kernel: wherever it fits at all): in bands the persistent kernel is
+	  // the better schedule
 		const uint32_t all = (uint32_t) ((p.width + 15) / 16) * ((p.out_rows + 15) / 16);
-		if(plan_bands(p, true, pl) && (p.sw.flat > 0 || pl.band_nblk >= all)) return true;
+		if(plan_bands(p, true, pl) && (p.sw.flat > 0 || !leaf_fits || pl.band_nblk >= all))
+		{
+			pl.lds = skr_scene_kernels_lds(p);
+			return true;
+		}
 	}
-	return plan_bands(p, false, pl);
+	pl.lds = pl.lds_leaf;
+	return leaf_fits && plan_bands(p, false, pl);
 }
 
 // records of level `level` in the band last rendered (level 0: its level-0 nodes), from its counter block at off_ctr in the scratch:

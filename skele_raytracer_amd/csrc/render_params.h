@@ -19,6 +19,8 @@ struct f3 {
 #define SKR_PULL_STRIDE 256u
 // the level pipelines append the hit records of a level to SKR_P1_REGIONS regions, one counter each
 #define SKR_P1_REGIONS 64u
+// the regions' prefix sums (wave_common.h region_prefix), kept in static LDS by the kernels that number a level's records densely
+#define SKR_PREFIX_WORDS (SKR_P1_REGIONS + 1u)
 
 // The SKR_* development switches (A/B runs, tests), read from the environment ONCE per renderer (skr_renderer_create,
 // skr_renderer_reload_switches) — the launch path never calls getenv.

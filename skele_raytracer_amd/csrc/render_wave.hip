@@ -265,7 +265,10 @@ hipError_t skr_launch_wave(const RenderParams &p, size_t lds, hipStream_t stream
 	const bool tris = p.n_tris > 0, sph = p.n_spheres > 0;
 	const void *fn = tris ? (sph ? reinterpret_cast<const void *>(skr_direct_kernel<true, true>) : reinterpret_cast<const void *>(skr_direct_kernel<true, false>))
 	                      : (sph ? reinterpret_cast<const void *>(skr_direct_kernel<false, true>) : reinterpret_cast<const void *>(skr_direct_kernel<false, false>));
-	hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); // > 64 KiB of dynamic LDS per workgroup has to be opted into
+	// (on gfx950 the runtime launches more than 64 KiB of dynamic LDS without this opt-in as well: the scene kernels of the level
+	// pipelines never set it and run with up to 160 KiB, tests/test_scene_size_gpu.py.  What it does not check is static + dynamic
+	// LDS against the device: launch.h skr_scene_kernels_lds.)
+	hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 	if(e != hipSuccess) return e;
 	if(tris && sph) hipLaunchKernelGGL((skr_direct_kernel<true, true>), grid, dim3(256), lds, stream, p);
 	else if(tris) hipLaunchKernelGGL((skr_direct_kernel<true, false>), grid, dim3(256), lds, stream, p);
