@@ -29,6 +29,7 @@ extern "C" {
                             * existing entry point and struct as it was; SKR_HAS_SHADE_RAYS tells a caller it is there); 6: skr_scene_get_gi_masks; 5: skr_scene_get_shadow_masks; 4: SKR_SCN_FOG, skr_scene_get_fog, skr_scene_set_fog (spherical fog; skr_options unchanged); 3: skr_options grew by shade_triangles, progressive_passes and legacy_reflect (56 bytes); 2: multi-GPU entry points, skr_scene_info.n_directional_lights */
 #define SKR_HAS_SHADE_RAYS 1
 #define SKR_HAS_DENOISE 1    /* skr_denoise, skr_render_denoised_host: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_ADAPTIVE 1   /* skr_adaptive, skr_render_adaptive(_host): an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
 	SKR_OK = 0,
@@ -418,6 +419,45 @@ int skr_denoise(skr_renderer *r, uint32_t width, uint32_t height, const float *d
  * the frame's float output (the mean of opt->progressive_passes passes), the guides skr_trace_rays(skr_camera_rays(opt with
  * grid_size = 0, sample 0)), then skr_denoise.  Synchronous.  kernel_ms: device time of the whole sequence. */
 int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf, float *kernel_ms);
+
+/* ---- adaptive sampling (adaptive.hip): extra passes only for the pixels whose estimate is still noisy ----
+ * The rule (normative):
+ *   - Pass k of pixel p (k = 0, 1, ...): v_k, the float frame pixel of opt with seed = opt->seed + k (uint64 wrap-around); with
+ *     grid_size g > 0 the frame's own value, its g^2 AA samples summed in sample order and divided by (float) g^2.
+ *   - Luminance l_k = 0.2126f * r + 0.7152f * g + 0.0722f * b, left to right (the denoiser's).
+ *   - Running sums in binary32, in pass order, not contracted: C = v_0, then C + v_k per channel (skr_accumulate's order);
+ *     S1 = sum l_k and S2 = sum (l_k * l_k) in the same order.
+ *   - Convergence after n passes, tested only when n >= max(2, min_passes) and threshold >= 0: nf = (float) n, m = S1 / nf,
+ *     d = S2 / nf - m * m, var = d > 0 ? d : 0, e2 = var / (nf - 1), b = threshold * (m > SKR_ADAPTIVE_LUM_FLOOR ? m :
+ *     SKR_ADAPTIVE_LUM_FLOOR); converged iff e2 <= b * b.  Divides are correctly rounded.  A negative threshold: nothing converges.
+ *   - Pixel p gets pass n iff n < min_passes, or n < max_passes and it has not converged after n passes (a pixel the test has not
+ *     run on counts as not converged; a converged pixel never resumes).  So its pass count n_p lies in [min_passes, max_passes].
+ *   - Outputs: mean_p = C / (float) n_p per channel (as skr_resolve_accumulated divides), its bytes quantised as a frame's are,
+ *     passes[p] = n_p.
+ *   - min_passes == max_passes == K is opt->progressive_passes = K bit for bit; a negative threshold is K = max_passes.
+ * Limits: 1 <= min_passes <= max_passes <= SKR_ADAPTIVE_PASS_LIMIT, threshold not NaN (+inf: every pixel stops at
+ * max(2, min_passes)), reserved 0; anything else SKR_ERR_ARG. */
+#define SKR_ADAPTIVE_LUM_FLOOR 0.00390625f /* 2^-8: dark pixels stop on absolute noise */
+#define SKR_ADAPTIVE_MIN_PASSES 8          /* the defaults of skr_adaptive_default, the CLIs and Renderer.render_adaptive */
+#define SKR_ADAPTIVE_MAX_PASSES 64
+#define SKR_ADAPTIVE_THRESHOLD 0.05f
+#define SKR_ADAPTIVE_PASS_LIMIT 65535      /* the largest max_passes */
+typedef struct {
+	int32_t min_passes, max_passes;
+	float threshold;  /* relative standard error of a pixel's mean luminance at which it stops */
+	int32_t reserved; /* 0 */
+} skr_adaptive;
+void skr_adaptive_default(skr_adaptive *a);
+/* The whole frame under the rule above into DEVICE outputs: d_rgb uint8_t[H][W][3], d_rgbf float[H][W][3] (the means),
+ * d_passes uint32_t[H][W] (n_p); any may be NULL, not all three.  opt->progressive_passes must be <= 1 (SKR_ERR_ARG).  The option
+ * errors of skr_render_tiles apply.  SYNCHRONOUS: after the first min_passes whole frames it reads back one 4-byte count of the
+ * still-active pixels per round (at most max_passes - min_passes rounds), so it cannot be captured in a graph.  Each round gives
+ * the active pixels one more pass, as a whole frame or as shading queries of just those pixels, whichever costs less; both give the
+ * same bits.  The work counters advance by the work done.  Scratch is the renderer's, grown on demand and kept. */
+int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes, void *stream);
+/* The same into HOST memory (h_rgb W*H*3 bytes, h_rgbf W*H*3 floats, h_passes W*H uint32; any may be NULL, not all three).
+ * kernel_ms: device time of the whole sequence, as skr_render_progressive_host reports it. */
+int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *h_rgb, float *h_rgbf, uint32_t *h_passes, float *kernel_ms);
 
 /* ---- image file: replaces the inline writer main.cpp:199-211 ---- */
 int skr_write_ppm(const char *path, uint32_t width, uint32_t height, const uint8_t *rgb);

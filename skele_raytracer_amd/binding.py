@@ -17,9 +17,16 @@ EXPORTED_SYMBOLS = [
     "skr_multi_render_frame_host", "skr_comm_unique_id", "skr_comm_create", "skr_comm_destroy", "skr_comm_render_frame", "skr_comm_render_frame_async", "skr_comm_flush", "skr_comm_frame_to_host",
     "skr_shard_tiles_per_rank", "skr_shard_deinterleave_host", "skr_shard_lpt", "skr_shard_by_cost", "skr_shard_plan", "skr_shard_deinterleave_map_host", "skr_multi_render_frame_async", "skr_multi_flush",
     "skr_trace_rays", "skr_camera_rays", "skr_shade_rays", "skr_denoise", "skr_render_denoised_host",
+    "skr_adaptive_default", "skr_render_adaptive", "skr_render_adaptive_host",
 ]
 
 DENOISE_ITERATIONS = 5  # include/skr.h SKR_DENOISE_ITERATIONS: Renderer.denoise's default
+# include/skr.h SKR_ADAPTIVE_*: Renderer.render_adaptive's defaults, the luminance floor of the rule and the largest max_passes
+ADAPTIVE_MIN_PASSES = 8
+ADAPTIVE_MAX_PASSES = 64
+ADAPTIVE_THRESHOLD = 0.05
+ADAPTIVE_LUM_FLOOR = 0.00390625
+ADAPTIVE_PASS_LIMIT = 65535
 
 
 class SkrError(RuntimeError):
@@ -148,8 +155,27 @@ def lib():
     L.skr_shade_rays.argtypes = [vp, C.POINTER(COptions), vp, C.c_uint32, C.c_uint32, vp, vp, vp]
     L.skr_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp]
     L.skr_render_denoised_host.argtypes = [vp, C.POINTER(COptions), C.c_uint32, vp, vp, C.POINTER(C.c_float)]
+    L.skr_adaptive_default.argtypes = [C.POINTER(CAdaptive)]
+    L.skr_adaptive_default.restype = None
+    L.skr_render_adaptive.argtypes = [vp, C.POINTER(COptions), C.POINTER(CAdaptive), vp, vp, vp, vp]
+    L.skr_render_adaptive_host.argtypes = [vp, C.POINTER(COptions), C.POINTER(CAdaptive), vp, vp, vp, C.POINTER(C.c_float)]
     _lib = L
     return L
+
+
+class CAdaptive(C.Structure):
+    """include/skr.h skr_adaptive"""
+    _fields_ = [("min_passes", C.c_int32), ("max_passes", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32)]
+
+
+def adaptive_params(threshold=ADAPTIVE_THRESHOLD, min_passes=ADAPTIVE_MIN_PASSES, max_passes=ADAPTIVE_MAX_PASSES):
+    """An include/skr.h skr_adaptive; libskr checks the limits (SKR_ERR_ARG)."""
+    a = CAdaptive()
+    lo, hi = -(1 << 31), (1 << 31) - 1
+    a.min_passes = min(max(int(min_passes), lo), hi)
+    a.max_passes = min(max(int(max_passes), lo), hi)
+    a.threshold = float(threshold)
+    return a
 
 
 def _check(rc, what):
@@ -570,6 +596,37 @@ class Renderer:
             stream = torch.cuda.current_stream(dev).cuda_stream
             _check(lib().skr_denoise(self.h, w, h, rgbf.data_ptr(), raw.data_ptr(), int(iterations), out.data_ptr(), rgb.data_ptr(), stream), "skr_denoise")
         return rgb, out
+
+    def render_adaptive(self, opt, threshold=ADAPTIVE_THRESHOLD, min_passes=ADAPTIVE_MIN_PASSES, max_passes=ADAPTIVE_MAX_PASSES, want_float=False):
+        """Adaptive sampling (include/skr.h skr_render_adaptive): every pixel gets min_passes passes of opt (seeds seed, seed+1, ...) and
+        more, up to max_passes, while the standard error of its mean luminance exceeds threshold x that mean.  Returns (rgb uint8
+        [H, W, 3], rgbf float32 [H, W, 3] or None, passes uint32 [H, W]) device tensors, written on torch's current stream; the call
+        itself is synchronous (one 4-byte count is read back per round).  min_passes == max_passes == K is render(opt with progressive=K)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        a = adaptive_params(threshold, min_passes, max_passes)
+        rgb = torch.zeros((opt.height, opt.width, 3), dtype=torch.uint8, device=dev)
+        rgbf = torch.zeros((opt.height, opt.width, 3), dtype=torch.float32, device=dev) if want_float else None
+        passes = torch.empty((opt.height, opt.width), dtype=torch.uint32, device=dev)  # (every word is written)
+        self._sync_switches()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib().skr_render_adaptive(self.h, C.byref(opt.c), C.byref(a), rgb.data_ptr(), rgbf.data_ptr() if want_float else None,
+                                             passes.data_ptr(), stream), "skr_render_adaptive")
+        return rgb, rgbf, passes
+
+    def render_adaptive_host(self, opt, threshold=ADAPTIVE_THRESHOLD, min_passes=ADAPTIVE_MIN_PASSES, max_passes=ADAPTIVE_MAX_PASSES, want_float=False):
+        """render_adaptive into host arrays (include/skr.h skr_render_adaptive_host).  Returns (rgb uint8 [H, W, 3], rgbf float32 or
+        None, passes uint32 [H, W], device ms)."""
+        a = adaptive_params(threshold, min_passes, max_passes)
+        self._sync_switches()
+        rgb = np.zeros((opt.height, opt.width, 3), np.uint8)
+        rgbf = np.zeros((opt.height, opt.width, 3), np.float32) if want_float else None
+        passes = np.zeros((opt.height, opt.width), np.uint32)
+        ms = C.c_float()
+        _check(lib().skr_render_adaptive_host(self.h, C.byref(opt.c), C.byref(a), rgb.ctypes.data, rgbf.ctypes.data if want_float else None,
+                                              passes.ctypes.data, C.byref(ms)), "skr_render_adaptive_host")
+        return rgb, rgbf, passes, ms.value
 
     def render_denoised(self, opt, iterations=DENOISE_ITERATIONS, want_float=False):
         """include/skr.h skr_render_denoised_host: the whole frame (the mean of opt's progressive passes), its guides and the denoiser,

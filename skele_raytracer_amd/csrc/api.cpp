@@ -65,6 +65,9 @@ struct skr_renderer {
 	size_t dn_pixels = 0;
 	void *d_dnframe = nullptr; // skr_render_denoised_host: the frame, its camera rays and guides, the filtered frame and its bytes
 	size_t dnframe_pixels = 0;
+	void *d_ad = nullptr;     // skr_render_adaptive: the per-pixel statistics, the active lists and the query path's rays (launch.h AdaptiveScratch)
+	size_t ad_pixels = 0;
+	uint32_t *h_count = nullptr; // skr_render_adaptive: the pinned word each round's active count is read back into
 	hipEvent_t frame_e0 = nullptr, frame_e1 = nullptr;
 	// skr_renderer_kernel_ms: event pairs around the dominant kernel of recent launches
 	SkrSwitches sw; // the SKR_* development switches, read once (load_switches)
@@ -88,6 +91,7 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_GI_MASK")) sw.gi_mask = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_GI_SURFACE")) sw.gi_surface = atoi(e) > 0 ? 1 : 0;
+	if(const char *e = getenv("SKR_ADAPTIVE_PATH")) sw.adaptive_path = !strcmp(e, "frame") ? 1 : !strcmp(e, "query") ? 2 : 0;
 }
 
 // (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
@@ -286,6 +290,8 @@ void skr_renderer_destroy(skr_renderer *r)
 	if(r->d_frame) (void) hipFree(r->d_frame);
 	if(r->d_dn) (void) hipFree(r->d_dn);
 	if(r->d_dnframe) (void) hipFree(r->d_dnframe);
+	if(r->d_ad) (void) hipFree(r->d_ad);
+	if(r->h_count) (void) hipHostFree(r->h_count);
 	if(r->frame_e0) (void) hipEventDestroy(r->frame_e0);
 	if(r->frame_e1) (void) hipEventDestroy(r->frame_e1);
 	for(SkrTimingHook &h : r->timed) { (void) hipEventDestroy(h.start); (void) hipEventDestroy(h.stop); }
@@ -1097,6 +1103,156 @@ int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t i
 	SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
 	if(h_rgb) SKR_HIP(hipMemcpy(h_rgb, rgb, n * 3, hipMemcpyDeviceToHost));
 	if(h_rgbf) SKR_HIP(hipMemcpy(h_rgbf, out, n * 12, hipMemcpyDeviceToHost));
+	float ms = 0;
+	SKR_HIP(hipEventSynchronize(r->frame_e1));
+	SKR_HIP(hipEventElapsedTime(&ms, r->frame_e0, r->frame_e1));
+	if(kernel_ms) *kernel_ms = ms;
+	return SKR_OK;
+}
+
+// ---- adaptive sampling (adaptive.hip): extra passes only for the pixels whose estimate is still noisy ----
+void skr_adaptive_default(skr_adaptive *a)
+{
+	if(!a) return;
+	a->min_passes = SKR_ADAPTIVE_MIN_PASSES;
+	a->max_passes = SKR_ADAPTIVE_MAX_PASSES;
+	a->threshold = SKR_ADAPTIVE_THRESHOLD;
+	a->reserved = 0;
+}
+
+static int check_adaptive(const skr_options *opt, const skr_adaptive *a, const char *who)
+{
+	if(opt->progressive_passes > 1)
+	{
+		skr_set_error("%s: progressive_passes %d: adaptive sampling chooses the passes itself (leave it at 1)", who, opt->progressive_passes);
+		return SKR_ERR_ARG;
+	}
+	if(a->min_passes < 1 || a->max_passes < a->min_passes || a->max_passes > SKR_ADAPTIVE_PASS_LIMIT || std::isnan(a->threshold) || a->reserved != 0)
+	{
+		skr_set_error("%s: need 1 <= min_passes <= max_passes <= %d and a threshold that is not NaN (got %d, %d, %g)", who, SKR_ADAPTIVE_PASS_LIMIT,
+					  a->min_passes, a->max_passes, (double) a->threshold);
+		return SKR_ERR_ARG;
+	}
+	int rc = check_options(opt);
+	if(rc != SKR_OK) return rc;
+	if((uint64_t) opt->width * (uint64_t) opt->height > 0xFFFFFFFFull)
+	{
+		skr_set_error("%s: %dx%d pixels do not fit the 32-bit pixel lists", who, opt->width, opt->height);
+		return SKR_ERR_ARG;
+	}
+	return SKR_OK;
+}
+
+int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes, void *stream)
+{
+	if(!r || !opt || !a || (!d_rgb && !d_rgbf && !d_passes) || ((uintptr_t) d_rgbf & 3) || ((uintptr_t) d_passes & 3))
+	{
+		skr_set_error("skr_render_adaptive: bad argument (null or misaligned array, or no output)");
+		return SKR_ERR_ARG;
+	}
+	int rc = check_adaptive(opt, a, "skr_render_adaptive");
+	if(rc != SKR_OK) return rc;
+	SKR_HIP(hipSetDevice(r->device));
+	const hipStream_t st = (hipStream_t) stream;
+	const uint64_t pixels = (uint64_t) opt->width * (uint64_t) opt->height;
+	rc = ensure_progressive_scratch(r, (size_t) pixels * 3);
+	if(rc != SKR_OK) return rc;
+	if(pixels > r->ad_pixels)
+	{
+		if(r->d_ad) SKR_HIP(hipFree(r->d_ad));
+		r->d_ad = nullptr;
+		r->ad_pixels = 0;
+		SKR_HIP(hipMalloc(&r->d_ad, skr_adaptive_scratch_bytes(pixels)));
+		r->ad_pixels = (size_t) pixels;
+	}
+	if(!r->h_count) SKR_HIP(hipHostMalloc((void **) &r->h_count, sizeof(uint32_t), hipHostMallocDefault));
+	const AdaptiveScratch s = skr_adaptive_carve(r->d_ad, pixels);
+	float *frame = r->d_prog;
+	skr_options pass = *opt;
+	pass.progressive_passes = 1;
+	// the first min_passes passes: whole frames
+	for(int32_t k = 0; k < a->min_passes; k++)
+	{
+		pass.seed = opt->seed + (uint64_t) k;
+		rc = render_pass(r, &pass, (uint32_t) opt->height, TileSel(), nullptr, frame, stream);
+		if(rc != SKR_OK) return rc;
+		SKR_HIP(skr_launch_adaptive_fold(s, frame, nullptr, (uint32_t) pixels, k == 0, st));
+	}
+	// then one round per pass index n while pixels are active: select (the first list is every pixel), read the count back, one pass
+	const AdaptiveRule rule{(uint32_t) a->min_passes, (uint32_t) a->max_passes, a->threshold};
+	const uint32_t samples = opt->grid_size > 0 ? (uint32_t) (opt->grid_size * opt->grid_size) : 0u;
+	const uint32_t *in = nullptr;
+	uint32_t m = (uint32_t) pixels;
+	for(uint32_t n = (uint32_t) a->min_passes, cur = 0; n < (uint32_t) a->max_passes; n++, cur ^= 1)
+	{
+		uint32_t *out = s.list[cur];
+		SKR_HIP(skr_launch_adaptive_select(s, rule, in, m, out, st));
+		SKR_HIP(hipMemcpyAsync(r->h_count, s.count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+		SKR_HIP(hipStreamSynchronize(st));
+		m = *r->h_count;
+		in = out;
+		if(m == 0) break;
+		pass.seed = opt->seed + (uint64_t) n;
+		const bool whole = r->sw.adaptive_path == 1 || (r->sw.adaptive_path == 0 && (double) m >= (double) SKR_ADAPTIVE_CROSSOVER * (double) pixels);
+		if(whole)
+		{ // frame path: the whole frame, its listed pixels gathered
+			rc = render_pass(r, &pass, (uint32_t) opt->height, TileSel(), nullptr, frame, stream);
+			if(rc != SKR_OK) return rc;
+			SKR_HIP(skr_launch_adaptive_fold(s, frame, in, m, 0, st));
+			continue;
+		}
+		// query path: per AA sample the listed pixels' camera rays, shaded with the pixel words as keys (skr_shade_rays)
+		RenderParams p{};
+		p.width = opt->width;
+		p.height = opt->height;
+		camera_invariants(r, opt, p);
+		p.grid_size = opt->grid_size;
+		p.seed_lo = (uint32_t) pass.seed;
+		p.seed_hi = (uint32_t) (pass.seed >> 32);
+		for(uint32_t aa = 0; aa < (samples ? samples : 1u); aa++)
+		{
+			p.aa_index = aa;
+			SKR_HIP(skr_launch_adaptive_rays(p, in, m, s.rays, st));
+			rc = skr_shade_rays(r, &pass, reinterpret_cast<const skr_ray *>(s.rays), m, aa, in, s.shade, stream);
+			if(rc != SKR_OK) return rc;
+			SKR_HIP(skr_launch_adaptive_sample(s, in, m, aa, samples, st));
+		}
+	}
+	SKR_HIP(skr_launch_adaptive_resolve(s, pixels, d_rgb, d_rgbf, d_passes, st));
+	return SKR_OK;
+}
+
+int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *h_rgb, float *h_rgbf, uint32_t *h_passes, float *kernel_ms)
+{
+	if(!r || !opt || !a || (!h_rgb && !h_rgbf && !h_passes))
+	{
+		skr_set_error("skr_render_adaptive_host: bad argument");
+		return SKR_ERR_ARG;
+	}
+	int rc = check_adaptive(opt, a, "skr_render_adaptive_host"); // before anything is sized from width x height
+	if(rc != SKR_OK) return rc;
+	SKR_HIP(hipSetDevice(r->device));
+	const size_t pixels = (size_t) opt->width * opt->height, bytes = pixels * 3, need = ((bytes + 15) & ~(size_t) 15) + pixels * 12 + pixels * 4;
+	if(need > r->frame_cap)
+	{ // the device frame (u8, float, passes) lives in the renderer, as skr_render_progressive_host's does
+		if(r->d_frame) SKR_HIP(hipFree(r->d_frame));
+		r->d_frame = nullptr;
+		r->frame_cap = 0;
+		SKR_HIP(hipMalloc((void **) &r->d_frame, need));
+		r->frame_cap = need;
+	}
+	uint8_t *d_rgb = h_rgb ? r->d_frame : nullptr;
+	float *d_rgbf = h_rgbf ? reinterpret_cast<float *>(r->d_frame + ((bytes + 15) & ~(size_t) 15)) : nullptr;
+	uint32_t *d_passes = h_passes ? reinterpret_cast<uint32_t *>(r->d_frame + ((bytes + 15) & ~(size_t) 15) + pixels * 12) : nullptr;
+	if(!r->frame_e0) SKR_HIP(hipEventCreate(&r->frame_e0));
+	if(!r->frame_e1) SKR_HIP(hipEventCreate(&r->frame_e1));
+	SKR_HIP(hipEventRecord(r->frame_e0, nullptr));
+	rc = skr_render_adaptive(r, opt, a, d_rgb, d_rgbf, d_passes, nullptr);
+	if(rc != SKR_OK) return rc;
+	SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
+	if(h_rgb) SKR_HIP(hipMemcpy(h_rgb, d_rgb, bytes, hipMemcpyDeviceToHost));
+	if(h_rgbf) SKR_HIP(hipMemcpy(h_rgbf, d_rgbf, pixels * 12, hipMemcpyDeviceToHost));
+	if(h_passes) SKR_HIP(hipMemcpy(h_passes, d_passes, pixels * 4, hipMemcpyDeviceToHost));
 	float ms = 0;
 	SKR_HIP(hipEventSynchronize(r->frame_e1));
 	SKR_HIP(hipEventElapsedTime(&ms, r->frame_e0, r->frame_e1));

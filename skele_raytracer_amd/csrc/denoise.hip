@@ -22,7 +22,6 @@ constexpr int DN_TILE = 16;
 constexpr float DN_SIGMA_L2 = SKR_DENOISE_SIGMA_L * SKR_DENOISE_SIGMA_L; // (16: exact)
 
 // l = 0.2126 r + 0.7152 g + 0.0722 b, left to right
-SKR_DEV float dn_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 SKR_DEV float dn_max0(float x) { return x > 0.0f ? x : 0.0f; }
 // h = k[dx + 2] * k[dy + 2] with k = {1/16, 1/4, 3/8, 1/4, 1/16}: every product is exact, so it folds to a constant
 constexpr float dn_k(int i) { return i == 0 || i == 4 ? 1.0f / 16 : i == 1 || i == 3 ? 0.25f : 0.375f; }
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(256) void skr_dn_pack_kernel(const float *__restric
 	cls[i] = kind == 1 ? (uint32_t) __float_as_int(h0.z) : kind == 2 ? DN_MESH : DN_MISS;
 	guide[i] = make_float4(h0.w, h1.x, h1.y, h0.x);
 	const float r = rgbf[3 * i], g = rgbf[3 * i + 1], b = rgbf[3 * i + 2];
-	col[i] = make_float4(r, g, b, dn_lum(r, g, b));
+	col[i] = make_float4(r, g, b, sk_lum(r, g, b));
 }
 
 // var_p = max(0, m2 - m1 * m1), m1 and m2 the means of l and l * l over the same-class in-image pixels of the 3x3 window (row-major)
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(256) void skr_dn_iter_kernel(const float4 *__restri
 	const uint32_t cp = cls[i];
 	const float4 gp = guide[i], cpx = in[i];
 	const bool miss = cp == DN_MISS;
-	const float lp = dn_lum(cpx.x, cpx.y, cpx.z);
+	const float lp = sk_lum(cpx.x, cpx.y, cpx.z);
 	const float V = DN_SIGMA_L2 * cpx.w + SKR_DENOISE_EPS;
 	const float zt = SKR_DENOISE_SIGMA_Z * gp.w;
 	const float D1 = zt * (float) s, D2 = zt * (float) (2 * s); // D = sigma_z * t_p * (s * max(|dx|, |dy|))
@@ -126,7 +125,7 @@ __global__ __launch_bounds__(256) void skr_dn_iter_kernel(const float4 *__restri
 					wz = D / (D + fabsf(gp.w - gq.w));
 				}
 			}
-			const float dl = lp - dn_lum(q.x, q.y, q.z);
+			const float dl = lp - sk_lum(q.x, q.y, q.z);
 			const float wl = V / (V + dl * dl);
 			const float hk = dn_k(dx + 2) * dn_k(dy + 2);
 			const float wt = hk * wn * wz * wl;

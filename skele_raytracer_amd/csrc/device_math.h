@@ -601,6 +601,9 @@ SKR_DEV void tangent_basis(f3 n, f3 &nt, f3 &nb)
 	nb = cross3(n, nt);
 }
 
+// luminance, left to right: the denoiser's edge weight and the adaptive sampler's statistic (include/skr.h)
+SKR_DEV float sk_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+
 // main.cpp:205: (unsigned char)(std::min(float(1), c) * 255); NaN -> 255
 SKR_DEV uint32_t quantise(float c)
 {

@@ -145,3 +145,27 @@ hipError_t skr_launch_denoise(const DenoiseScratch &b, uint32_t w, uint32_t h, c
 hipError_t skr_launch_accumulate(float *acc, const float *frame, size_t n, int first, hipStream_t stream);
 hipError_t skr_launch_resolve_accumulated(const float *acc, uint32_t passes, uint32_t width, uint32_t out_rows, uint32_t height, uint32_t tile_rows,
 										  uint32_t first_tile, uint32_t tile_stride, const uint32_t *tile_table, uint8_t *rgb, float *rgbf, hipStream_t stream);
+// adaptive.hip: the adaptive sampler's kernels (include/skr.h skr_render_adaptive)
+struct AdaptiveScratch {
+	float4 *st;        // per pixel {C.r, C.g, C.b, S1}
+	uint2 *st2;        // per pixel {S2 (bits), n}
+	uint32_t *list[2]; // the active lists, ping-pong: pixel indices in ascending order
+	uint32_t *blocks;  // per workgroup of a selection: its survivors, then their offset
+	uint32_t *count;   // the survivors of the last selection (one word)
+	float4 *rays;      // the query path: the camera rays of the listed pixels (skr_ray)
+	float *shade;      // their radiance at one AA sample [m][3]
+	float *sacc;       // the running sum of their AA samples [m][3]
+};
+struct AdaptiveRule {
+	uint32_t min_passes, max_passes;
+	float threshold;
+};
+// an active share at or above this gives the round a whole frame; below it, shading queries of the active pixels
+constexpr float SKR_ADAPTIVE_CROSSOVER = 0.5f;
+size_t skr_adaptive_scratch_bytes(uint64_t pixels);
+AdaptiveScratch skr_adaptive_carve(void *base, uint64_t pixels);
+hipError_t skr_launch_adaptive_fold(const AdaptiveScratch &s, const float *frame, const uint32_t *list, uint32_t m, int first, hipStream_t stream);
+hipError_t skr_launch_adaptive_select(const AdaptiveScratch &s, const AdaptiveRule &rule, const uint32_t *in, uint32_t m, uint32_t *out, hipStream_t stream);
+hipError_t skr_launch_adaptive_rays(const RenderParams &p, const uint32_t *list, uint32_t m, float4 *rays, hipStream_t stream);
+hipError_t skr_launch_adaptive_sample(const AdaptiveScratch &s, const uint32_t *list, uint32_t m, uint32_t sample, uint32_t samples, hipStream_t stream);
+hipError_t skr_launch_adaptive_resolve(const AdaptiveScratch &s, uint64_t pixels, uint8_t *rgb, float *rgbf, uint32_t *passes, hipStream_t stream);

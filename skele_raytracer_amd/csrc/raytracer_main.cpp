@@ -5,7 +5,8 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --scn-fog, --scn-fov, --shade-triangles, --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L.
+// --scn-fog, --scn-fov, --shade-triangles, --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
+// --adaptive T [--adaptive-min K] [--adaptive-max N].
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cstdio>
 #include <cstdlib>
@@ -29,6 +30,9 @@ int main(int argc, char *argv[])
 	uint32_t tile_rows = 8;
 	int denoise = 0;  // --denoise L: the frame filtered by L iterations of the denoiser (include/skr.h skr_render_denoised_host)
 	bool denoised = false;
+	bool adaptive = false; // --adaptive T [--adaptive-min K] [--adaptive-max N]: passes per pixel while it is still noisy (include/skr.h skr_render_adaptive)
+	skr_adaptive adapt;
+	skr_adaptive_default(&adapt);
 	uint32_t progressive_every = 0; // --progressive-every M: the output file is rewritten after every M passes (the headless "viewer")
 	const char *format = "ppm";     // --format ppm | png | pfm (new; the reference writes P6 whatever the name says)
 
@@ -131,6 +135,9 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--progressive-every") && has_next) progressive_every = (uint32_t) (atoi(argv[i + 1]) > 0 ? atoi(argv[i + 1]) : 0);
 		if(!strcmp(argv[i], "--format") && has_next) format = argv[i + 1];
 		if(!strcmp(argv[i], "--denoise") && has_next) { denoise = atoi(argv[i + 1]); denoised = true; } // new: edge-aware denoiser, L iterations
+		if(!strcmp(argv[i], "--adaptive") && has_next) { adapt.threshold = strtof(argv[i + 1], nullptr); adaptive = true; } // new: adaptive sampling
+		if(!strcmp(argv[i], "--adaptive-min") && has_next) adapt.min_passes = atoi(argv[i + 1]);
+		if(!strcmp(argv[i], "--adaptive-max") && has_next) adapt.max_passes = atoi(argv[i + 1]);
 	}
 	if(!path)
 	{
@@ -189,7 +196,12 @@ int main(int argc, char *argv[])
 		std::cerr << "raytracer: --denoise takes 0 .. " << SKR_DENOISE_MAX_ITERATIONS << " iterations on the single-device path (no --gpus N > 1, no --progressive-every)" << std::endl;
 		return SKR_ERR_ARG;
 	}
-	if(denoised) sharded = false; // (--gpus 1: the one device)
+	if(adaptive && (option.progressive_passes > 1 || progressive_every || (sharded && gpus > 1) || denoised))
+	{ // the passes are chosen per pixel on one device; the denoiser does not take the per-pixel means (yet)
+		std::cerr << "raytracer: --adaptive cannot be combined with --progressive K > 1, --progressive-every, --gpus N > 1 or --denoise" << std::endl;
+		return SKR_ERR_ARG;
+	}
+	if(denoised || adaptive) sharded = false; // (--gpus 1: the one device)
 	std::vector<uint8_t> rgb((size_t) option.width * option.height * 3);
 	std::vector<float> rgbf(want_pfm ? rgb.size() : 0);
 	struct Out {
@@ -236,7 +248,23 @@ int main(int argc, char *argv[])
 			return 0;
 		};
 		rc = skr_renderer_create(scene, device, &renderer);
-		if(rc == SKR_OK && denoised)
+		std::vector<uint32_t> passes(adaptive ? (size_t) option.width * option.height : 0);
+		if(rc == SKR_OK && adaptive)
+		{
+			rc = skr_render_adaptive_host(renderer, &option, &adapt, want_pfm ? nullptr : rgb.data(), want_pfm ? rgbf.data() : nullptr, passes.data(), &ms);
+			if(rc == SKR_OK)
+			{ // the mean passes per pixel and the share of pixels that reached max_passes
+				uint64_t sum = 0, at_max = 0;
+				for(uint32_t n : passes)
+				{
+					sum += n;
+					at_max += n == (uint32_t) adapt.max_passes;
+				}
+				fprintf(stderr, "adaptive: %.3f passes per pixel (min %d, max %d, threshold %g), %.2f %% of the pixels at max\n", (double) sum / passes.size(),
+						adapt.min_passes, adapt.max_passes, (double) adapt.threshold, 100.0 * (double) at_max / passes.size());
+			}
+		}
+		else if(rc == SKR_OK && denoised)
 			rc = skr_render_denoised_host(renderer, &option, (uint32_t) denoise, want_pfm ? nullptr : rgb.data(), want_pfm ? rgbf.data() : nullptr, &ms);
 		else if(rc == SKR_OK)
 			rc = skr_render_progressive_host(renderer, &option, progressive_every, want_pfm ? nullptr : rgb.data(), want_pfm ? rgbf.data() : nullptr,

@@ -34,7 +34,7 @@ struct SkrSwitches {
 	int8_t shadow_mask = 1;           // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
 	int8_t gi_mask = 1;               // SKR_GI_MASK = 1 | 0: the same for the closest-hit walk of the node pipeline's GI children
 	int8_t gi_surface = 1;            // SKR_GI_SURFACE = 1 | 0: GI origins on a sphere take their row of masks from the surface patches / the 3D grids only
-	int8_t pad_switch = 0;            // (four quarters of one word, as above)
+	int8_t adaptive_path = 0;         // SKR_ADAPTIVE_PATH = frame | query: the path of every adaptive round (+1 / +2); unset: by active share (four quarters of one word, as above)
 };
 
 struct RenderParams {

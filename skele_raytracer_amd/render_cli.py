@@ -4,6 +4,7 @@ per GPU.
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
            [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--adaptive T [--adaptive-min K] [--adaptive-max N]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
            --gillum 64 --jsample 5 --shadow            # BASELINE config 5
@@ -17,6 +18,8 @@ print the reference's messages and exit with status 0 (main.cpp:381-391).  There
 import os
 import sys
 import time
+
+import numpy as np
 
 
 def _atoi(s):
@@ -93,6 +96,12 @@ def _parse(argv):
             opt["format"] = value(i, str, "format takes ppm, png or pfm")
         elif a == "--denoise":
             opt["denoise"] = value(i, _atoi, "denoise takes a number of iterations")
+        elif a == "--adaptive":
+            opt["adaptive"] = value(i, _atof, "adaptive takes a float (the relative standard error at which a pixel stops)")
+        elif a == "--adaptive-min":
+            opt["adaptive_min"] = value(i, _atoi, "adaptive-min takes the number of passes every pixel gets")
+        elif a == "--adaptive-max":
+            opt["adaptive_max"] = value(i, _atoi, "adaptive-max takes the largest number of passes of a pixel")
         elif a == "--seed":
             opt["seed"] = value(i, _atoi, "seed takes an int")
         elif a == "--tile-rows":
@@ -182,6 +191,31 @@ def main(argv=None):
         if world > 1:
             dist.destroy_process_group()
         return 2
+    adaptive = o.get("adaptive")
+    if adaptive is not None and (o.get("progressive", 1) > 1 or every or world > 1 or denoise is not None):
+        # the passes are chosen per pixel on one device; the denoiser does not take the per-pixel means (yet)
+        if rank == 0:
+            print("raytracer: --adaptive cannot be combined with --progressive K > 1, --progressive-every, --gpus N > 1 or --denoise", file=sys.stderr)
+        if world > 1:
+            dist.destroy_process_group()
+        return 2
+    if adaptive is not None:
+        try:
+            rgb, rgbf, passes, ms = r.render_adaptive_host(opt, adaptive, o.get("adaptive_min", skr.ADAPTIVE_MIN_PASSES), o.get("adaptive_max", skr.ADAPTIVE_MAX_PASSES),
+                                                           want_float=(fmt == "pfm"))
+        except skr.SkrError as e:
+            print("raytracer: %s" % e, file=sys.stderr)
+            return 2
+        if fmt == "pfm":
+            skr.write_pfm(o["output"], rgbf)
+        else:
+            (skr.write_png if fmt == "png" else skr.write_ppm)(o["output"], rgb)
+        print("***\nWROTE TO PPM\n***")  # main.cpp:213
+        nmax = o.get("adaptive_max", skr.ADAPTIVE_MAX_PASSES)
+        print("adaptive: %.3f passes per pixel, %.2f %% of the pixels at max (%d)" % (float(passes.mean(dtype=np.float64)), 100.0 * float((passes == nmax).mean()), nmax),
+              file=sys.stderr)
+        print("1 GPU(s), %dx%d, %.3f ms (device, adaptive), kernel %s" % (o["width"], o["height"], ms, r.kernel_variant()), file=sys.stderr)
+        return 0
     if denoise is not None:
         rgb, rgbf, ms = r.render_denoised(opt, denoise, want_float=(fmt == "pfm"))
         if fmt == "pfm":
