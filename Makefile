@@ -48,6 +48,8 @@ asm: $(KERNEL_SRCS) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o build/render_wave.s $(CSRC)/render_wave.hip -Rpass-analysis=kernel-resource-usage 2>> build/resource_usage.txt
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o build/render_nodes.s $(CSRC)/render_nodes.hip -Rpass-analysis=kernel-resource-usage 2>> build/resource_usage.txt
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o build/render_generic.s $(CSRC)/render_generic.hip -Rpass-analysis=kernel-resource-usage 2>> build/resource_usage.txt
+	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o build/accumulate.s $(CSRC)/accumulate.hip -Rpass-analysis=kernel-resource-usage 2>> build/resource_usage.txt
+	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o build/trace_rays.s $(CSRC)/trace_rays.hip -Rpass-analysis=kernel-resource-usage 2>> build/resource_usage.txt
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o build/denoise.s $(CSRC)/denoise.hip -Rpass-analysis=kernel-resource-usage 2>> build/resource_usage.txt
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o build/adaptive.s $(CSRC)/adaptive.hip -Rpass-analysis=kernel-resource-usage 2>> build/resource_usage.txt
 

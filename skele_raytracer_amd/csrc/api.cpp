@@ -7,6 +7,8 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <vector>
 
 #include "launch.h"
@@ -25,13 +27,18 @@ static thread_local const char *g_variant = "none";
 		}                                                                                                  \
 	} while(0)
 
-struct skr_renderer {
+// The uploaded scene and what the launches take with it: shared by a renderer and its clones (skr_renderer_clone), freed by the last
+// of them.  The section offsets count 16-byte rows of the blob (pack_scene).
+struct DeviceScene {
 	int device = 0;
 	skr_scene_info info{};
-	float4 *d_blob = nullptr; // one allocation: geom | amb | kd | ks | lights | tris | chunk trees | triangle materials
+	int lds_limit = 0;
+	int pow_steps = 11; // bit length of the largest integer phong exponent in [1, 1024] among the scene's materials (device_math.h powf_spec)
+	float4 *d_blob = nullptr; // one allocation: the sections of pack_scene
 	size_t blob_bytes = 0;
 	float4 *d_camec = nullptr; // per sphere {cam_pos - centre, |.|^2 - r^2} (render_wave.hip skr_camec_kernel), + 16 rows of padding
-	bool is_clone = false;    // skr_renderer_clone: the scene blob and the work counters belong to the renderer it was cloned from
+	unsigned long long *d_counters = nullptr;
+	unsigned long long *d_tri_work = nullptr; // 256 x {culling-sphere tests, triangle tests} executed by the triangle walks (skr_renderer_read_triangle_work)
 	size_t off_amb = 0, off_kd = 0, off_ks = 0, off_lights = 0, off_tris = 0, off_chunks = 0, off_tri_mats = 0;
 	size_t off_fog = 0;       // --scn-fog: 2 rows per fog volume (render_params.h RenderParams::fog_row)
 	int n_fog = 0;
@@ -45,36 +52,61 @@ struct skr_renderer {
 	int n_chunks = 0, chunk_size = 0, cones = 0;
 	size_t chunk_stride = 0;
 	size_t off_trace = 0;     // the ray queries' tree (skr_scene::trace_chunks, SKR_CULL_LEVELS sets of chunk_stride rows), 0 = none
-	float trace_ball[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+	float4 trace_ball{};
 	int trace_cones = 0;
-	unsigned long long *d_counters = nullptr;
-	unsigned long long *d_snap = nullptr; // skr_renderer_kernel_work: the work counters in front of and behind the dominant kernel of the last timed launch
-	unsigned long long *d_tri_work = nullptr; // 256 x {culling-sphere tests, triangle tests} executed by the triangle walks (skr_renderer_read_triangle_work)
-	int lds_limit = 0;
-	int pow_steps = 11; // bit length of the largest integer phong exponent in [1, 1024] among the scene's materials (device_math.h powf_spec)
-	// scratch, grown on demand and kept
-	void *d_nodes = nullptr;  // level pipelines: every table of one band (launch.h NodePlan, GPlan)
-	size_t nodes_cap = 0;
-	float *d_acc = nullptr;
-	size_t acc_cap = 0;
-	float *d_prog = nullptr; // progressive accumulation: this pass's float frame | the running sum
-	size_t prog_cap = 0;
-	uint8_t *d_frame = nullptr; // skr_render_frame_host
-	size_t frame_cap = 0;
-	void *d_dn = nullptr;     // skr_denoise: the ping-pong images, the guides and the classes (launch.h DenoiseScratch)
-	size_t dn_pixels = 0;
-	void *d_dnframe = nullptr; // skr_render_denoised_host: the frame, its camera rays and guides, the filtered frame and its bytes
-	size_t dnframe_pixels = 0;
-	void *d_ad = nullptr;     // skr_render_adaptive: the per-pixel statistics, the active lists and the query path's rays (launch.h AdaptiveScratch)
-	size_t ad_pixels = 0;
-	uint32_t *h_count = nullptr; // skr_render_adaptive: the pinned word each round's active count is read back into
-	hipEvent_t frame_e0 = nullptr, frame_e1 = nullptr;
-	// skr_renderer_kernel_ms: event pairs around the dominant kernel of recent launches
+
+	DeviceScene() = default;
+	DeviceScene(const DeviceScene &) = delete;
+	DeviceScene &operator=(const DeviceScene &) = delete;
+	~DeviceScene()
+	{
+		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work})
+			if(p) (void) hipFree(p);
+	}
+};
+
+// A device buffer grown on demand and kept.  grow() frees the old buffer first (hipFree waits for the launches that may still read
+// it), then allocates exactly `need` bytes.
+struct Scratch {
+	void *p = nullptr;
+	size_t bytes = 0;
+
+	int grow(size_t need)
+	{
+		if(need <= bytes) return SKR_OK;
+		if(p) SKR_HIP(hipFree(p));
+		p = nullptr;
+		bytes = 0;
+		SKR_HIP(hipMalloc(&p, need));
+		bytes = need;
+		return SKR_OK;
+	}
+	template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(static_cast<char *>(p) + off); }
+	Scratch() = default;
+	Scratch(const Scratch &) = delete;
+	Scratch &operator=(const Scratch &) = delete;
+	~Scratch() { if(p) (void) hipFree(p); }
+};
+
+struct skr_renderer {
+	std::shared_ptr<const DeviceScene> scene;
 	SkrSwitches sw; // the SKR_* development switches, read once (load_switches)
-	size_t last_off_ctr = 0; // the node-pipeline counters of the launch last enqueued (skr_renderer_last_*_count): where in d_nodes ...
+	// scratch (Scratch)
+	Scratch nodes;   // level pipelines: every table of one band (launch.h NodePlan, GPlan)
+	Scratch acc;     // their AA accumulation image (LaunchPlan::acc_bytes)
+	Scratch prog;    // progressive accumulation: this pass's float frame | the running sum (progressive_scratch)
+	Scratch frame;   // the *_host entries' device frame (host_frame)
+	Scratch dn;      // skr_denoise: the ping-pong images, the guides and the classes (launch.h DenoiseScratch)
+	Scratch dnframe; // skr_render_denoised_host: the frame, its camera rays and guides, the filtered frame and its bytes
+	Scratch ad;      // skr_render_adaptive: the per-pixel statistics, the active lists and the query path's rays (launch.h AdaptiveScratch)
+	unsigned long long *d_snap = nullptr; // skr_renderer_kernel_work: the work counters in front of and behind the dominant kernel of the last timed launch
+	uint32_t *h_count = nullptr; // skr_render_adaptive: the pinned word each round's active count is read back into
+	hipEvent_t frame_e0 = nullptr, frame_e1 = nullptr; // the *_host entries' timing (timed_host)
+	size_t last_off_ctr = 0; // the node-pipeline counters of the launch last enqueued (skr_renderer_last_*_count): where in `nodes` ...
 	int last_levels = 0;     // ... and how many levels they count (0: the launch took another path)
 	bool timing = false;
 	bool count_tri = false; // skr_renderer_count_triangle_work
+	// skr_renderer_kernel_ms: event pairs around the dominant kernel of recent launches
 	std::vector<SkrTimingHook> timed;
 	std::vector<SkrTimingHook> free_pairs;
 };
@@ -96,6 +128,113 @@ static void load_switches(SkrSwitches &sw)
 
 // (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
 void skr_copy_switches(skr_renderer *dst, const skr_renderer *src) { dst->sw = src->sw; }
+
+// The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | shadow
+// masks | GI masks | trace tree, then 16 rows of padding (the sphere loops ask for the rows of a trip ahead without a bounds test,
+// shade_common.h sphere_rows).  Sets the offsets and the scalars of `d` that go with the sections; host only, nothing is uploaded.
+static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
+{
+	std::vector<skr_f4> rows;
+	auto put = [&](const void *src, size_t bytes) { // `bytes` of `src` (null: zeros) as whole rows; returns the first
+		const size_t at = rows.size();
+		rows.resize(at + (bytes + 15) / 16, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
+		if(src && bytes) memcpy(&rows[at], src, bytes);
+		return at;
+	};
+	auto put4 = [&](const std::vector<skr_f4> &v) { return put(v.data(), v.size() * 16); };
+	put4(s.sph_geom);
+	d.off_amb = put4(s.sph_amb);
+	d.off_kd = put4(s.sph_kd);
+	d.off_ks = put4(s.sph_ks);
+	d.off_lights = put4(s.lights);
+	d.off_tris = put4(s.tris);
+	d.off_chunks = put4(s.tri_chunks);
+	d.chunk_size = s.tri_chunk_size;
+	d.chunk_stride = s.tri_chunk_stride;
+	d.cones = s.tri_any_cone ? 1 : 0;
+	d.n_chunks = s.info.n_triangles ? s.tri_node_count : 0; // nodes of the chunk tree (scene_host.h)
+	d.off_tri_mats = put4(s.tri_mats);
+	// the fog volumes (skr_scene raw_fog, SKR_SCN_FOG / skr_scene_set_fog): [radius absorption scattering 0] [albedo 0]
+	d.off_fog = rows.size();
+	d.n_fog = (int) (s.raw_fog.size() / 9);
+	for(int j = 0; j < d.n_fog; j++)
+	{
+		const float *f = &s.raw_fog[9 * j]; // x y z radius r g b scattering absorption
+		rows.push_back({f[3], f[8], f[7], 0.0f});
+		rows.push_back({f[4], f[5], f[6], 0.0f});
+	}
+	if(!s.shadow_masks.empty()) d.off_smask = put(s.shadow_masks.data(), s.shadow_masks.size() * 4);
+	d.shadow_reach2 = s.shadow_reach2;
+	if(!s.gi_table.empty())
+	{ // the GI masks (whole rows: scene_host.cpp build_gi_masks), with the surface patches' masks right behind the grids' masks (their
+	  // rows continue the grids' rows), then the patches' headers and index
+		const size_t patch_word = s.gi_mask_word + (size_t) s.gi_rows * (SKR_GI_ROW_ENTRIES * (s.gi_wide ? 4 : 2) / 4);
+		d.gi_surface_word = s.gi_surface.empty() ? 0 : patch_word + s.gi_surface_head;
+		d.off_gi = put(nullptr, std::max(s.gi_table.size(), s.gi_surface.empty() ? 0 : patch_word + s.gi_surface.size()) * 4);
+		uint32_t *words = reinterpret_cast<uint32_t *>(&rows[d.off_gi]);
+		memcpy(words, s.gi_table.data(), s.gi_table.size() * 4);
+		if(d.gi_surface_word) memcpy(words + patch_word, s.gi_surface.data(), s.gi_surface.size() * 4);
+	}
+	d.gi_grid[0] = s.gi_grid[0];
+	d.gi_grid[1] = s.gi_grid[1];
+	d.gi_mask_word = s.gi_mask_word;
+	d.gi_wide = s.gi_wide;
+	if(s.info.n_triangles && !s.trace_chunks.empty()) d.off_trace = put4(s.trace_chunks);
+	d.trace_ball = make_float4(s.trace_ball[0], s.trace_ball[1], s.trace_ball[2], s.trace_ball[3]);
+	d.trace_cones = s.trace_any_cone ? 1 : 0;
+	rows.resize(rows.size() + 16, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
+	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
+		float top = 1.0f;
+		auto look = [&](float pw) { if(pw >= 1.0f && pw <= 1024.0f && pw == rintf(pw) && pw > top) top = pw; };
+		for(const skr_f4 &a : s.sph_amb) look(a.w);
+		for(size_t i = 0; i + 2 < s.tri_mats.size(); i += 3) look(s.tri_mats[i].w);
+		int bits = 0;
+		for(unsigned v = (unsigned) top; v; v >>= 1) bits++;
+		d.pow_steps = bits < 1 ? 1 : bits;
+	}
+	return rows;
+}
+
+// The device frame of a *_host entry, kept in the renderer: its bytes, its floats and, with `passes`, the adaptive sampler's pass counts
+struct HostFrame {
+	uint8_t *rgb;
+	float *rgbf;
+	uint32_t *passes;
+};
+static int host_frame(skr_renderer *r, size_t pixels, bool passes, HostFrame &f)
+{
+	ScratchLayout L;
+	const size_t o_rgb = L.take(pixels * 3), o_rgbf = L.take(pixels * 12), o_passes = passes ? L.take(pixels * 4) : 0;
+	const int rc = r->frame.grow(L.off);
+	if(rc != SKR_OK) return rc;
+	f = {r->frame.at<uint8_t>(o_rgb), r->frame.at<float>(o_rgbf), passes ? r->frame.at<uint32_t>(o_passes) : nullptr};
+	return SKR_OK;
+}
+
+// A *_host entry's device work on the null stream, timed by the renderer's event pair: `run` enqueues it, then every output with a
+// host array is copied back, and the elapsed milliseconds go to *ms (if not null).
+struct HostCopy {
+	void *host; // null: not wanted
+	const void *device;
+	size_t bytes;
+};
+template <class Run>
+static int timed_host(skr_renderer *r, Run run, std::initializer_list<HostCopy> copies, float *ms)
+{
+	if(!r->frame_e0) SKR_HIP(hipEventCreate(&r->frame_e0));
+	if(!r->frame_e1) SKR_HIP(hipEventCreate(&r->frame_e1));
+	SKR_HIP(hipEventRecord(r->frame_e0, nullptr));
+	const int rc = run();
+	if(rc != SKR_OK) return rc;
+	SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
+	for(const HostCopy &c : copies)
+		if(c.host) SKR_HIP(hipMemcpy(c.host, c.device, c.bytes, hipMemcpyDeviceToHost));
+	float t = 0;
+	SKR_HIP(hipEventSynchronize(r->frame_e1));
+	SKR_HIP(hipEventElapsedTime(&t, r->frame_e0, r->frame_e1));
+	if(ms) *ms = t;
+	return SKR_OK;
+}
 
 extern "C" {
 
@@ -128,120 +267,49 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		skr_set_error("device %d is %s; libskr is built for gfx950 (MI355X) only", device, prop.gcnArchName);
 		return SKR_ERR_NO_DEVICE;
 	}
-	skr_renderer *r = new skr_renderer();
-	load_switches(r->sw);
-	r->device = device;
-	r->info = scene->info;
-	r->lds_limit = (int) prop.sharedMemPerBlock;
-	const size_t ns = scene->sph_geom.size(), nl2 = scene->lights.size(), nt3 = scene->tris.size();
-	r->off_amb = ns;
-	r->off_kd = 2 * ns;
-	r->off_ks = 3 * ns;
-	r->off_lights = 4 * ns;
-	r->off_tris = 4 * ns + nl2;
-	const size_t nch = scene->tri_chunks.size();
-	r->off_chunks = 4 * ns + nl2 + nt3;
-	r->chunk_size = scene->tri_chunk_size;
-	r->chunk_stride = scene->tri_chunk_stride;
-	r->cones = scene->tri_any_cone ? 1 : 0;
-	r->n_chunks = scene->info.n_triangles ? scene->tri_node_count : 0; // nodes of the chunk tree (scene_host.h)
-	const size_t ntm = scene->tri_mats.size();
-	r->off_tri_mats = 4 * ns + nl2 + nt3 + nch;
-	// the fog volumes (skr_scene raw_fog, SKR_SCN_FOG / skr_scene_set_fog): [radius absorption scattering 0] [albedo 0]
-	const size_t nfog = scene->raw_fog.size() / 9;
-	if(nfog > SKR_FOG_MAX_VOLUMES)
+	if(scene->raw_fog.size() / 9 > SKR_FOG_MAX_VOLUMES)
 	{
-		skr_set_error("scene has %zu fog volumes; at most %d are supported", nfog, SKR_FOG_MAX_VOLUMES);
-		delete r;
+		skr_set_error("scene has %zu fog volumes; at most %d are supported", scene->raw_fog.size() / 9, SKR_FOG_MAX_VOLUMES);
 		return SKR_ERR_UNSUPPORTED;
 	}
-	r->off_fog = 4 * ns + nl2 + nt3 + nch + ntm;
-	r->n_fog = (int) nfog;
-	const size_t nsm = (scene->shadow_masks.size() + 3) / 4; // rows of the shadow masks
-	r->off_smask = nsm ? r->off_fog + 2 * nfog : 0;
-	r->shadow_reach2 = scene->shadow_reach2;
-	// rows of the GI masks (whole rows: scene_host.cpp build_gi_masks), with the surface patches' masks right behind the grids'
-	// masks (their rows continue the grids' rows), then the patches' headers and index
-	const size_t gi_patch_word = scene->gi_mask_word + (size_t) scene->gi_rows * (SKR_GI_ROW_ENTRIES * (scene->gi_wide ? 4 : 2) / 4);
-	const size_t ngi = scene->gi_table.empty() ? 0 : (std::max(scene->gi_table.size(), scene->gi_surface.empty() ? 0 : gi_patch_word + scene->gi_surface.size()) + 3) / 4;
-	r->gi_surface_word = scene->gi_table.empty() || scene->gi_surface.empty() ? 0 : gi_patch_word + scene->gi_surface_head;
-	r->off_gi = ngi ? r->off_fog + 2 * nfog + nsm : 0;
-	r->gi_grid[0] = scene->gi_grid[0];
-	r->gi_grid[1] = scene->gi_grid[1];
-	r->gi_mask_word = scene->gi_mask_word;
-	r->gi_wide = scene->gi_wide;
-	const size_t ntc = scene->info.n_triangles ? scene->trace_chunks.size() : 0; // rows of the ray queries' tree
-	r->off_trace = ntc ? r->off_fog + 2 * nfog + nsm + ngi : 0;
-	memcpy(r->trace_ball, scene->trace_ball, sizeof r->trace_ball);
-	r->trace_cones = scene->trace_any_cone ? 1 : 0;
-	const size_t total = 4 * ns + nl2 + nt3 + nch + ntm + 2 * nfog + nsm + ngi + ntc;
-	std::vector<skr_f4> blob(total + 16); // (+ 16 rows: the sphere loops ask for the rows of a trip ahead without a bounds test, shade_common.h sphere_rows)
-	if(ns)
-	{
-		memcpy(&blob[0], scene->sph_geom.data(), ns * 16);
-		memcpy(&blob[r->off_amb], scene->sph_amb.data(), ns * 16);
-		memcpy(&blob[r->off_kd], scene->sph_kd.data(), ns * 16);
-		memcpy(&blob[r->off_ks], scene->sph_ks.data(), ns * 16);
-	}
-	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
-		float top = 1.0f;
-		auto look = [&](float pw) { if(pw >= 1.0f && pw <= 1024.0f && pw == rintf(pw) && pw > top) top = pw; };
-		for(size_t i = 0; i < ns; i++) look(scene->sph_amb[i].w);
-		for(size_t i = 0; i + 2 < scene->tri_mats.size(); i += 3) look(scene->tri_mats[i].w);
-		int bits = 0;
-		for(unsigned v = (unsigned) top; v; v >>= 1) bits++;
-		r->pow_steps = bits < 1 ? 1 : bits;
-	}
-	if(nl2) memcpy(&blob[r->off_lights], scene->lights.data(), nl2 * 16);
-	if(nt3) memcpy(&blob[r->off_tris], scene->tris.data(), nt3 * 16);
-	if(nch) memcpy(&blob[r->off_chunks], scene->tri_chunks.data(), nch * 16);
-	if(ntm) memcpy(&blob[r->off_tri_mats], scene->tri_mats.data(), ntm * 16);
-	for(size_t j = 0; j < nfog; j++)
-	{
-		const float *f = &scene->raw_fog[9 * j]; // x y z radius r g b scattering absorption
-		blob[r->off_fog + 2 * j] = {f[3], f[8], f[7], 0.0f};
-		blob[r->off_fog + 2 * j + 1] = {f[4], f[5], f[6], 0.0f};
-	}
-	if(nsm) memcpy(&blob[r->off_smask], scene->shadow_masks.data(), scene->shadow_masks.size() * 4);
-	if(ngi)
-	{
-		memcpy(&blob[r->off_gi], scene->gi_table.data(), scene->gi_table.size() * 4);
-		if(r->gi_surface_word) memcpy(reinterpret_cast<uint32_t *>(&blob[r->off_gi]) + gi_patch_word, scene->gi_surface.data(), scene->gi_surface.size() * 4);
-	}
-	if(ntc) memcpy(&blob[r->off_trace], scene->trace_chunks.data(), ntc * 16);
-	r->blob_bytes = blob.size() * 16;
-	hipError_t e = hipMalloc((void **) &r->d_blob, blob.size() * 16);
-	if(e == hipSuccess) e = hipMemcpy(r->d_blob, blob.data(), blob.size() * 16, hipMemcpyHostToDevice);
-	if(e == hipSuccess) e = hipMalloc((void **) &r->d_counters, (SKR_COUNTER_SHARDS * 4 + 16) * sizeof(unsigned long long) + (SKR_PULL_QUEUES + 2 + 2 * SKR_P1_REGIONS) * SKR_PULL_STRIDE * sizeof(uint32_t));
-	if(e == hipSuccess) e = hipMemset(r->d_counters, 0, (SKR_COUNTER_SHARDS * 4 + 16) * sizeof(unsigned long long) + (SKR_PULL_QUEUES + 2 + 2 * SKR_P1_REGIONS) * SKR_PULL_STRIDE * sizeof(uint32_t));
-	if(e == hipSuccess) e = hipMalloc((void **) &r->d_tri_work, 256 * 2 * sizeof(unsigned long long));
-	if(e == hipSuccess) e = hipMemset(r->d_tri_work, 0, 256 * 2 * sizeof(unsigned long long));
-	if(e == hipSuccess) e = hipMalloc((void **) &r->d_camec, (ns + 16) * 16);
-	if(e == hipSuccess) e = hipMemset(r->d_camec, 0, (ns + 16) * 16);
+	auto s = std::make_shared<DeviceScene>(); // (frees what was allocated if the upload fails)
+	s->device = device;
+	s->info = scene->info;
+	s->lds_limit = (int) prop.sharedMemPerBlock;
+	const std::vector<skr_f4> blob = pack_scene(*scene, *s);
+	s->blob_bytes = blob.size() * 16;
+	const size_t ns = scene->sph_geom.size();
+	const size_t counter_bytes = (SKR_COUNTER_SHARDS * 4 + 16) * sizeof(unsigned long long) + (SKR_PULL_QUEUES + 2 + 2 * SKR_P1_REGIONS) * SKR_PULL_STRIDE * sizeof(uint32_t);
+	hipError_t e = hipMalloc((void **) &s->d_blob, s->blob_bytes);
+	if(e == hipSuccess) e = hipMemcpy(s->d_blob, blob.data(), s->blob_bytes, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMalloc((void **) &s->d_counters, counter_bytes);
+	if(e == hipSuccess) e = hipMemset(s->d_counters, 0, counter_bytes);
+	if(e == hipSuccess) e = hipMalloc((void **) &s->d_tri_work, 256 * 2 * sizeof(unsigned long long));
+	if(e == hipSuccess) e = hipMemset(s->d_tri_work, 0, 256 * 2 * sizeof(unsigned long long));
+	if(e == hipSuccess) e = hipMalloc((void **) &s->d_camec, (ns + 16) * 16);
+	if(e == hipSuccess) e = hipMemset(s->d_camec, 0, (ns + 16) * 16);
 	if(e == hipSuccess)
 	{ // the camera belongs to the scene: its (e, c) rows are formed once, on the device, by the operations every ray would perform
 		const float *c = scene->info.camera;
-		e = skr_launch_camec(r->d_blob, (int) ns, f3{c[0], c[1], c[2]}, r->d_camec, nullptr);
+		e = skr_launch_camec(s->d_blob, (int) ns, f3{c[0], c[1], c[2]}, s->d_camec, nullptr);
 		if(e == hipSuccess) e = hipDeviceSynchronize();
 	}
 	if(e != hipSuccess)
 	{
 		skr_set_error("scene upload failed: %s", hipGetErrorString(e));
-		if(r->d_camec) (void) hipFree(r->d_camec);
-		if(r->d_blob) (void) hipFree(r->d_blob);
-		if(r->d_counters) (void) hipFree(r->d_counters);
-		if(r->d_tri_work) (void) hipFree(r->d_tri_work);
-		delete r;
 		return SKR_ERR_HIP;
 	}
+	skr_renderer *r = new skr_renderer();
+	r->scene = std::move(s);
+	load_switches(r->sw);
 	*out = r;
 	return SKR_OK;
 }
 
 // A second renderer for the same scene on the same device with its own scratch (tables, accumulation buffers, timing events) — what a
 // second frame in flight needs (multi_gpu.cpp: consecutive frames of a run alternate between a renderer and its clone on two streams).
-// The scene blob (read-only) and the work counters (atomics) are SHARED with `src`, which must outlive the clone: rays counted by
-// either are read through either.
+// The scene blob (read-only) and the work counters (atomics) are SHARED with `src` (DeviceScene): rays counted by either are read
+// through either.
 int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 {
 	if(!src || !out)
@@ -250,26 +318,9 @@ int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 		return SKR_ERR_ARG;
 	}
 	*out = nullptr;
-	SKR_HIP(hipSetDevice(src->device));
+	SKR_HIP(hipSetDevice(src->scene->device));
 	skr_renderer *r = new skr_renderer();
-	r->device = src->device;
-	r->info = src->info;
-	r->d_blob = src->d_blob;
-	r->blob_bytes = src->blob_bytes;
-	r->d_camec = src->d_camec;
-	r->is_clone = true;
-	r->off_amb = src->off_amb; r->off_kd = src->off_kd; r->off_ks = src->off_ks; r->off_lights = src->off_lights;
-	r->off_tris = src->off_tris; r->off_chunks = src->off_chunks; r->off_tri_mats = src->off_tri_mats;
-	r->off_fog = src->off_fog; r->n_fog = src->n_fog;
-	r->off_smask = src->off_smask; r->shadow_reach2 = src->shadow_reach2;
-	r->off_gi = src->off_gi; r->gi_grid[0] = src->gi_grid[0]; r->gi_grid[1] = src->gi_grid[1]; r->gi_mask_word = src->gi_mask_word; r->gi_wide = src->gi_wide;
-	r->gi_surface_word = src->gi_surface_word;
-	r->n_chunks = src->n_chunks; r->chunk_size = src->chunk_size; r->cones = src->cones; r->chunk_stride = src->chunk_stride;
-	r->off_trace = src->off_trace; memcpy(r->trace_ball, src->trace_ball, sizeof r->trace_ball); r->trace_cones = src->trace_cones;
-	r->d_counters = src->d_counters;
-	r->d_tri_work = src->d_tri_work;
-	r->lds_limit = src->lds_limit;
-	r->pow_steps = src->pow_steps;
+	r->scene = src->scene;
 	r->sw = src->sw;
 	*out = r;
 	return SKR_OK;
@@ -278,25 +329,14 @@ int skr_renderer_clone(const skr_renderer *src, skr_renderer **out)
 void skr_renderer_destroy(skr_renderer *r)
 {
 	if(!r) return;
-	(void) hipSetDevice(r->device);
-	if(r->d_blob && !r->is_clone) (void) hipFree(r->d_blob);
-	if(r->d_camec && !r->is_clone) (void) hipFree(r->d_camec);
-	if(r->d_counters && !r->is_clone) (void) hipFree(r->d_counters);
-	if(r->d_tri_work && !r->is_clone) (void) hipFree(r->d_tri_work);
+	(void) hipSetDevice(r->scene->device);
 	if(r->d_snap) (void) hipFree(r->d_snap);
-	if(r->d_nodes) (void) hipFree(r->d_nodes);
-	if(r->d_acc) (void) hipFree(r->d_acc);
-	if(r->d_prog) (void) hipFree(r->d_prog);
-	if(r->d_frame) (void) hipFree(r->d_frame);
-	if(r->d_dn) (void) hipFree(r->d_dn);
-	if(r->d_dnframe) (void) hipFree(r->d_dnframe);
-	if(r->d_ad) (void) hipFree(r->d_ad);
 	if(r->h_count) (void) hipHostFree(r->h_count);
 	if(r->frame_e0) (void) hipEventDestroy(r->frame_e0);
 	if(r->frame_e1) (void) hipEventDestroy(r->frame_e1);
 	for(SkrTimingHook &h : r->timed) { (void) hipEventDestroy(h.start); (void) hipEventDestroy(h.stop); }
 	for(SkrTimingHook &h : r->free_pairs) { (void) hipEventDestroy(h.start); (void) hipEventDestroy(h.stop); }
-	delete r;
+	delete r; // (the scratch, and the scene with the last renderer that holds it)
 }
 
 uint32_t skr_tile_count(const skr_options *opt, uint32_t tile_rows, uint32_t first_tile, uint32_t tile_stride)
@@ -327,18 +367,28 @@ static int check_options(const skr_options *opt)
 	return SKR_OK;
 }
 
-// main.cpp:134-137, hoisted: identical float/double expressions evaluated once; the camera of camera.h:8-32 (what primary_ray() reads)
-static void camera_invariants(const skr_renderer *r, const skr_options *opt, RenderParams &p)
+// What every launch starts from, and all the camera rays need (skr_launch_camera_rays, skr_launch_adaptive_rays): the size of the frame
+// of opt, AA sample `sample` of it under `seed`, and the camera of camera.h:8-32 (what primary_ray() reads) with main.cpp:134-137
+// hoisted (identical float/double expressions evaluated once)
+static RenderParams camera_params(const skr_renderer *r, const skr_options *opt, uint64_t seed, uint32_t sample)
 {
+	RenderParams p{};
+	p.width = opt->width;
+	p.height = opt->height;
+	p.grid_size = opt->grid_size;
+	p.seed_lo = (uint32_t) seed;
+	p.seed_hi = (uint32_t) (seed >> 32);
+	p.aa_index = sample;
 	p.inv_width = 1 / float(opt->width);
 	p.inv_height = 1 / float(opt->height);
 	p.aspect = opt->width / float(opt->height);
 	p.angle = (float) tan(M_PI * 0.5 * opt->fov / 180.);
-	const float *c = r->info.camera;
+	const float *c = r->scene->info.camera;
 	p.cam_pos = f3{c[0], c[1], c[2]};
 	p.cam_dir = f3{c[3], c[4], c[5]};
 	p.cam_up = f3{c[6], c[7], c[8]};
 	p.cam_right = f3{c[9], c[10], c[11]};
+	return p;
 }
 
 // one frame (one pass of a progressive render) of the tiles first_tile, first_tile + tile_stride, ...
@@ -355,42 +405,42 @@ static uint32_t sel_tiles(const skr_options *opt, uint32_t tile_rows, const Tile
 	return n > ts.max_tiles ? ts.max_tiles : n;
 }
 
-// Everything of a launch that is not its output: the scene, the switches and masks, the camera, and the options folded and checked —
-// the depth fold, the node-id bound, the fog exclusions.  render_pass and skr_shade_rays both start from it.
+// Everything of a launch beyond camera_params that is not its output: the scene, the switches and masks, and the options folded and
+// checked — the depth fold, the node-id bound, the fog exclusions.  render_pass and skr_shade_rays both take it.
 static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &p)
 {
+	const DeviceScene &s = *r->scene;
 	p.sw = r->sw;
-	camera_invariants(r, opt, p);
-	const float *c = r->info.camera;
-	p.background = f3{r->info.background[0], r->info.background[1], r->info.background[2]};
-	p.n_spheres = r->info.n_spheres;
-	p.n_tris = r->info.n_triangles;
-	p.n_lights = r->info.n_point_lights + r->info.n_directional_lights; // (directional ones only under --strict-scn)
-	p.sph_geom = r->d_blob;
-	p.cam_ec = r->d_camec;
-	p.sph_amb = r->d_blob + r->off_amb;
-	p.sph_kd = r->d_blob + r->off_kd;
-	p.sph_ks = r->d_blob + r->off_ks;
-	p.lights = r->d_blob + r->off_lights;
-	p.tris = r->d_blob + r->off_tris;
-	p.tri_chunks = r->d_blob + r->off_chunks;
-	p.tri_chunk_size = r->chunk_size;
-	p.tri_cones = (r->cones && !r->sw.no_cones) ? 1 : 0;
-	if(r->off_smask && r->sw.shadow_mask)
+	const float *c = s.info.camera;
+	p.background = f3{s.info.background[0], s.info.background[1], s.info.background[2]};
+	p.n_spheres = s.info.n_spheres;
+	p.n_tris = s.info.n_triangles;
+	p.n_lights = s.info.n_point_lights + s.info.n_directional_lights; // (directional ones only under --strict-scn)
+	p.sph_geom = s.d_blob;
+	p.cam_ec = s.d_camec;
+	p.sph_amb = s.d_blob + s.off_amb;
+	p.sph_kd = s.d_blob + s.off_kd;
+	p.sph_ks = s.d_blob + s.off_ks;
+	p.lights = s.d_blob + s.off_lights;
+	p.tris = s.d_blob + s.off_tris;
+	p.tri_chunks = s.d_blob + s.off_chunks;
+	p.tri_chunk_size = s.chunk_size;
+	p.tri_cones = (s.cones && !r->sw.no_cones) ? 1 : 0;
+	if(s.off_smask && r->sw.shadow_mask)
 	{ // the level pipelines' shadow walk visits only the spheres a lane's masks name (shade_common.h occluded_pair)
-		p.shadow_masks = reinterpret_cast<const uint32_t *>(r->d_blob + r->off_smask);
-		p.shadow_reach2 = r->shadow_reach2;
+		p.shadow_masks = reinterpret_cast<const uint32_t *>(s.d_blob + s.off_smask);
+		p.shadow_reach2 = s.shadow_reach2;
 		p.shadow_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
 	}
-	if(r->off_gi && r->sw.gi_mask)
+	if(s.off_gi && r->sw.gi_mask)
 	{ // the node pipeline's closest-hit walk of a GI child visits only the spheres its masks name (wave_common.h closest_pair)
-		p.gi_index = reinterpret_cast<const int32_t *>(r->d_blob + r->off_gi);
-		p.gi_masks = reinterpret_cast<const uint32_t *>(r->d_blob + r->off_gi) + r->gi_mask_word;
-		p.gi_grid[0] = r->gi_grid[0];
-		p.gi_grid[1] = r->gi_grid[1];
-		p.gi_wide = r->gi_wide;
+		p.gi_index = reinterpret_cast<const int32_t *>(s.d_blob + s.off_gi);
+		p.gi_masks = reinterpret_cast<const uint32_t *>(s.d_blob + s.off_gi) + s.gi_mask_word;
+		p.gi_grid[0] = s.gi_grid[0];
+		p.gi_grid[1] = s.gi_grid[1];
+		p.gi_wide = s.gi_wide;
 		p.gi_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
-		if(r->gi_surface_word && r->sw.gi_surface) p.gi_surface = reinterpret_cast<const uint32_t *>(r->d_blob + r->off_gi) + r->gi_surface_word;
+		if(s.gi_surface_word && r->sw.gi_surface) p.gi_surface = reinterpret_cast<const uint32_t *>(s.d_blob + s.off_gi) + s.gi_surface_word;
 	}
 	{ // pick the tightest set of chunk spheres whose |d| bound covers this frame's camera rays (GI children stay below 4,
 	  // the smallest bound): primary directions are dir + u right + v up (main.cpp:154-155)
@@ -400,20 +450,19 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 		const double bound[SKR_CULL_LEVELS] = SKR_CULL_DMAX_LIST;
 		int level = 0;
 		while(level < SKR_CULL_LEVELS && !(dmax < bound[level])) level++;
-		p.n_tri_chunks = (level < SKR_CULL_LEVELS && !r->sw.no_cull) ? r->n_chunks : 0;
-		if(p.n_tri_chunks) p.tri_chunks += (size_t) level * r->chunk_stride;
+		p.n_tri_chunks = (level < SKR_CULL_LEVELS && !r->sw.no_cull) ? s.n_chunks : 0;
+		if(p.n_tri_chunks) p.tri_chunks += (size_t) level * s.chunk_stride;
 	}
 	p.monte_carlo = opt->monte_carlo ? 1 : 0;
 	p.num_path_traces = opt->num_path_traces;
-	p.grid_size = opt->grid_size;
 	p.max_depth = opt->max_depth;
 	p.use_shadows = opt->use_shadows ? 1 : 0;
-	p.pow_steps = r->pow_steps;
+	p.pow_steps = s.pow_steps;
 	// shade() only recurses under --gillum and only below a sphere hit (raytrace.h:208-218), and with N = 0 there is no
 	// child to recurse into: every --depth is then the depth-1 image
 	// (--shade-triangles: a triangle hit recurses too)
 	p.shade_triangles = (opt->shade_triangles && p.n_tris > 0) ? 1 : 0;
-	p.tri_mats = r->d_blob + r->off_tri_mats;
+	p.tri_mats = s.d_blob + s.off_tri_mats;
 	// Only a sphere hit has the terms of raytrace.h:45-103, so a scene without spheres has nothing to add — but the flag also sets the
 	// arity of the counter RNG's node ids (N + 2 L, include/skr.h), and a tree over triangle surfaces (--shade-triangles --gillum) has
 	// nodes whatever the scene holds: there the flag stays, the legacy children simply never exist (found by tests/fuzz_parity.py:
@@ -432,87 +481,63 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 		}
 	}
 	// --scn-fog: a scene with fog volumes renders on the general level pipeline (render_kernel.hip skr_plan_launch)
-	p.n_fog = r->n_fog;
-	p.fog_row = (uint32_t) r->off_fog;
+	p.n_fog = s.n_fog;
+	p.fog_row = (uint32_t) s.off_fog;
 	if(p.n_fog > 0 && (opt->legacy_reflect || opt->shade_triangles))
 	{
 		skr_set_error("fog volumes (--scn-fog) cannot be combined with --legacy-reflect or --shade-triangles");
 		return SKR_ERR_UNSUPPORTED;
 	}
-	p.seed_lo = (uint32_t) opt->seed;
-	p.seed_hi = (uint32_t) (opt->seed >> 32);
-	p.counters = r->d_counters;
-	p.tri_work = r->count_tri ? r->d_tri_work : nullptr;
-	p.qctr = reinterpret_cast<uint32_t *>(r->d_counters + (size_t) SKR_COUNTER_SHARDS * 4 + 8);
+	p.counters = s.d_counters;
+	p.tri_work = r->count_tri ? s.d_tri_work : nullptr;
+	p.qctr = reinterpret_cast<uint32_t *>(s.d_counters + (size_t) SKR_COUNTER_SHARDS * 4 + 8);
 	return SKR_OK;
 }
 
-// grows the level pipelines' scratch (kept between launches) to `bytes`
-static int ensure_level_scratch(skr_renderer *r, size_t bytes)
+// A launch the device cannot take: not one band of its tables fits the scratch budget (a band holds at least one output row, or the
+// `rays` of one row of a shading query), or its kernels need `lds` bytes of LDS, more than a workgroup has
+static int check_plan(const skr_renderer *r, const RenderParams &p, bool fits, size_t lds, uint32_t rays)
 {
-	if(bytes > r->nodes_cap)
+	if(!fits)
 	{
-		if(r->d_nodes) SKR_HIP(hipFree(r->d_nodes));
-		r->d_nodes = nullptr;
-		r->nodes_cap = 0;
-		SKR_HIP(hipMalloc(&r->d_nodes, bytes));
-		r->nodes_cap = bytes;
+		char band[32] = "one output row";
+		if(rays) snprintf(band, sizeof band, "%u rays", rays);
+		skr_set_error("--depth %d with %d children per node: the tables of %s exceed the scratch budget (SKR_LEVELS_BUDGET_MB)", p.max_depth,
+					  p.num_path_traces + (p.legacy_reflect ? 2 * p.n_lights : 0), band);
+		return SKR_ERR_UNSUPPORTED;
+	}
+	if(lds > (size_t) r->scene->lds_limit)
+	{
+		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", lds, p.n_spheres, p.n_lights,
+					  r->scene->lds_limit);
+		return SKR_ERR_UNSUPPORTED;
 	}
 	return SKR_OK;
 }
 
+// one pass of the tiles `ts` selects (render_impl has checked the arguments and set the device)
 static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
 {
-	const uint32_t first_tile = ts.first, tile_stride = ts.stride;
-	if(!r || !opt || (!d_rgb && !d_rgbf) || tile_rows == 0 || tile_stride == 0)
-	{
-		skr_set_error("skr_render_tiles: bad argument");
-		return SKR_ERR_ARG;
-	}
-	int rc = check_options(opt);
-	if(rc != SKR_OK) return rc;
-	const uint32_t n_tiles = sel_tiles(opt, tile_rows, ts);
-	if(n_tiles == 0) return SKR_OK;
-	SKR_HIP(hipSetDevice(r->device));
-
-	RenderParams p{};
-	p.width = opt->width;
-	p.height = opt->height;
+	RenderParams p = camera_params(r, opt, opt->seed, 0);
 	p.tile_rows = tile_rows;
-	p.first_tile = first_tile;
+	p.first_tile = ts.first;
 	p.tile_table = ts.d_table;
-	p.tile_stride = tile_stride;
-	p.out_rows = n_tiles * tile_rows;
+	p.tile_stride = ts.stride;
+	p.out_rows = sel_tiles(opt, tile_rows, ts) * tile_rows;
 	p.band_row0 = 0;
 	p.band_rows = p.out_rows;
-	rc = launch_params(r, opt, p);
+	int rc = launch_params(r, opt, p);
 	if(rc != SKR_OK) return rc;
 	p.rgb = d_rgb;
 	p.rgbf = d_rgbf;
 	LaunchPlan lp;
-	if(!skr_plan_launch(p, (size_t) r->lds_limit, lp))
-	{
-		skr_set_error("--depth %d with %d children per node: the tables of one output row exceed the scratch budget (SKR_LEVELS_BUDGET_MB)", p.max_depth, p.num_path_traces + (p.legacy_reflect ? 2 * p.n_lights : 0));
-		return SKR_ERR_UNSUPPORTED;
-	}
-	rc = ensure_level_scratch(r, lp.scratch_bytes);
+	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp);
+	rc = check_plan(r, p, fits, lp.lds_bytes, 0);
+	if(rc == SKR_OK) rc = r->nodes.grow(lp.scratch_bytes);
+	if(rc == SKR_OK) rc = r->acc.grow(lp.acc_bytes);
 	if(rc != SKR_OK) return rc;
-	if(lp.path != SKR_PATH_DIRECT) p.node_scratch = r->d_nodes;
-	if(lp.acc_bytes > r->acc_cap)
-	{
-		if(r->d_acc) SKR_HIP(hipFree(r->d_acc));
-		r->d_acc = nullptr;
-		r->acc_cap = 0;
-		SKR_HIP(hipMalloc((void **) &r->d_acc, lp.acc_bytes));
-		r->acc_cap = lp.acc_bytes;
-	}
-	if(lp.acc_bytes) p.acc = r->d_acc;
-	if(lp.lds_bytes > (size_t) r->lds_limit)
-	{
-		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", lp.lds_bytes,
-					  p.n_spheres, p.n_lights, r->lds_limit);
-		return SKR_ERR_UNSUPPORTED;
-	}
+	if(lp.path != SKR_PATH_DIRECT) p.node_scratch = r->nodes.p;
+	if(lp.acc_bytes) p.acc = static_cast<float *>(r->acc.p);
 	SkrTimingHook hook;
 	if(r->timing)
 	{
@@ -532,7 +557,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 			SKR_HIP(hipMemset(r->d_snap, 0, (size_t) 2 * SKR_COUNTER_SHARDS * 4 * sizeof(unsigned long long)));
 		}
 		hook.snap = r->d_snap;
-		hook.counters = r->d_counters;
+		hook.counters = r->scene->d_counters;
 	}
 	r->last_off_ctr = lp.off_ctr;
 	r->last_levels = lp.levels;
@@ -542,26 +567,20 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	return SKR_OK;
 }
 
-// grows the renderer's progressive scratch to 2 x n floats: this pass's frame | the running sum
-static int ensure_progressive_scratch(skr_renderer *r, size_t n)
+// the progressive passes' scratch for frames of n floats: this pass's frame | the running sum
+static int progressive_scratch(skr_renderer *r, size_t n, float *&frame, float *&acc)
 {
-	if(2 * n * sizeof(float) > r->prog_cap)
-	{
-		if(r->d_prog) SKR_HIP(hipFree(r->d_prog));
-		r->d_prog = nullptr;
-		r->prog_cap = 0;
-		SKR_HIP(hipMalloc((void **) &r->d_prog, 2 * n * sizeof(float)));
-		r->prog_cap = 2 * n * sizeof(float);
-	}
-	return SKR_OK;
+	const int rc = r->prog.grow(2 * n * sizeof(float));
+	frame = static_cast<float *>(r->prog.p);
+	acc = frame + n;
+	return rc;
 }
 
 // skr_options.progressive_passes: K frames under the seeds s, s+1, ..., s+K-1, summed in binary32 in pass
 // order, divided by K once and quantised like a single frame (accumulate.hip).  K <= 1 is the single frame itself.
 static int render_impl(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
 {
-	if(!opt || opt->progressive_passes <= 1) return render_pass(r, opt, tile_rows, ts, d_rgb, d_rgbf, stream);
-	if(!r || (!d_rgb && !d_rgbf) || tile_rows == 0 || ts.stride == 0)
+	if(!r || !opt || (!d_rgb && !d_rgbf) || tile_rows == 0 || ts.stride == 0)
 	{
 		skr_set_error("skr_render_tiles: bad argument");
 		return SKR_ERR_ARG;
@@ -570,12 +589,13 @@ static int render_impl(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	if(rc != SKR_OK) return rc;
 	const uint32_t n_tiles = sel_tiles(opt, tile_rows, ts);
 	if(n_tiles == 0) return SKR_OK;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
+	if(opt->progressive_passes <= 1) return render_pass(r, opt, tile_rows, ts, d_rgb, d_rgbf, stream);
 	const uint32_t out_rows = n_tiles * tile_rows;
 	const size_t n = (size_t) opt->width * out_rows * 3;
-	rc = ensure_progressive_scratch(r, n);
+	float *frame, *acc;
+	rc = progressive_scratch(r, n, frame, acc);
 	if(rc != SKR_OK) return rc;
-	float *frame = r->d_prog, *acc = r->d_prog + n;
 	skr_options pass = *opt;
 	pass.progressive_passes = 1;
 	for(int32_t k = 0; k < opt->progressive_passes; k++)
@@ -622,12 +642,12 @@ int skr_tile_costs(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, 
 	if(!r || !opt || !h_cost || tile_rows == 0) return SKR_ERR_ARG;
 	int rc = check_options(opt);
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	const uint32_t T = ((uint32_t) opt->height + tile_rows - 1) / tile_rows;
 	SKR_HIP(hipDeviceSynchronize()); // (frames still in flight on other streams add to the counters this probe borrows)
 	std::vector<unsigned long long> saved((size_t) SKR_COUNTER_SHARDS * 4 + 8);
-	SKR_HIP(hipMemcpy(saved.data(), r->d_counters, saved.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-	SKR_HIP(hipMemset(r->d_counters, 0, saved.size() * sizeof(unsigned long long)));
+	SKR_HIP(hipMemcpy(saved.data(), r->scene->d_counters, saved.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	SKR_HIP(hipMemset(r->scene->d_counters, 0, saved.size() * sizeof(unsigned long long)));
 	std::vector<uint32_t> tiles(T);
 	for(uint32_t t = 0; t < T; t++) tiles[t] = t;
 	uint32_t *d_tiles = nullptr;
@@ -642,13 +662,13 @@ int skr_tile_costs(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, 
 		rc = skr_render_tile_list(r, opt, tile_rows, d_tiles + t, 1, d_rgb, nullptr, nullptr);
 		uint64_t w[4] = {0, 0, 0, 0};
 		if(rc == SKR_OK) rc = skr_renderer_read_work(r, w, 1);
-		const uint64_t mesh = r->info.n_triangles > 64 ? (uint64_t) (6 * 19 + 5 * 46) : (uint64_t) r->info.n_triangles * 46;
+		const uint64_t mesh = r->scene->info.n_triangles > 64 ? (uint64_t) (6 * 19 + 5 * 46) : (uint64_t) r->scene->info.n_triangles * 46;
 		h_cost[t] = 34 * w[3] + 150 * w[1] + (20 + mesh) * (w[0] + w[2]);
 	}
 	r->count_tri = was_timing;
 	if(d_tiles) (void) hipFree(d_tiles);
 	if(d_rgb) (void) hipFree(d_rgb);
-	if(e == hipSuccess) e = hipMemcpy(r->d_counters, saved.data(), saved.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(r->scene->d_counters, saved.data(), saved.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
 	if(e != hipSuccess)
 	{
 		skr_set_error("skr_tile_costs: %s", hipGetErrorString(e));
@@ -718,7 +738,7 @@ int skr_renderer_kernel_timing(skr_renderer *r, int enable)
 int skr_renderer_kernel_ms(skr_renderer *r, float *mean_ms, int32_t *launches)
 {
 	if(!r || !mean_ms) return SKR_ERR_ARG;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	double sum = 0;
 	int n = 0;
 	for(SkrTimingHook &h : r->timed)
@@ -740,9 +760,9 @@ int skr_renderer_kernel_ms(skr_renderer *r, float *mean_ms, int32_t *launches)
 static int nodes_level_count(skr_renderer *r, int level, uint32_t *n)
 {
 	if(!r || !n) return SKR_ERR_ARG;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	*n = 0;
-	if(level < r->last_levels) SKR_HIP(skr_nodes_level_count(r->d_nodes, r->last_off_ctr, level, n)); // (only the node pipeline has level tables of this layout)
+	if(level < r->last_levels) SKR_HIP(skr_nodes_level_count(r->nodes.p, r->last_off_ctr, level, n)); // (only the node pipeline has level tables of this layout)
 	return SKR_OK;
 }
 
@@ -753,10 +773,10 @@ int skr_renderer_last_level1_count(skr_renderer *r, uint32_t *n) { return nodes_
 static int read_work(skr_renderer *r, uint64_t *out, int n_out, int reset)
 {
 	if(!r || !out) return SKR_ERR_ARG;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	// the work counters and (diagnostic builds) the 8 phase stamps behind them; the queue counters that follow are not touched
 	std::vector<unsigned long long> h((size_t) SKR_COUNTER_SHARDS * 4 + 8);
-	SKR_HIP(hipMemcpy(h.data(), r->d_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost)); // synchronises with prior launches
+	SKR_HIP(hipMemcpy(h.data(), r->scene->d_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost)); // synchronises with prior launches
 	for(int k = 0; k < n_out; k++) out[k] = 0;
 	for(size_t s = 0; s < SKR_COUNTER_SHARDS; s++)
 		for(int k = 0; k < n_out; k++) out[k] += h[4 * s + k];
@@ -765,7 +785,7 @@ static int read_work(skr_renderer *r, uint64_t *out, int n_out, int reset)
 		for(int k = 0; k < 8; k++) fprintf(stderr, "stamp[%d] = %llu\n", k, h[(size_t) SKR_COUNTER_SHARDS * 4 + k]);
 	}
 	// (null stream: callers read the counters between frames, after synchronising their render stream)
-	if(reset) SKR_HIP(hipMemset(r->d_counters, 0, h.size() * sizeof(unsigned long long)));
+	if(reset) SKR_HIP(hipMemset(r->scene->d_counters, 0, h.size() * sizeof(unsigned long long)));
 	return SKR_OK;
 }
 
@@ -776,7 +796,7 @@ int skr_renderer_read_work(skr_renderer *r, uint64_t out[4], int reset)
 	const int rc = read_work(r, out, 4, reset);
 	if(rc != SKR_OK) return rc;
 	// every radiance ray tests every sphere (raytrace.h:152-165); a shadow ray stops at its first occluder (utils.h:52-55)
-	out[3] += out[0] * (uint64_t) r->info.n_spheres;
+	out[3] += out[0] * (uint64_t) r->scene->info.n_spheres;
 	return SKR_OK;
 }
 
@@ -792,22 +812,22 @@ int skr_renderer_kernel_work(skr_renderer *r, uint64_t out[4])
 	if(!r || !out) return SKR_ERR_ARG;
 	for(int k = 0; k < 4; k++) out[k] = 0;
 	if(!r->d_snap) return SKR_OK;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	std::vector<unsigned long long> h((size_t) 2 * SKR_COUNTER_SHARDS * 4);
 	SKR_HIP(hipMemcpy(h.data(), r->d_snap, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost)); // synchronises with prior launches
 	const size_t half = (size_t) SKR_COUNTER_SHARDS * 4;
 	for(size_t s = 0; s < SKR_COUNTER_SHARDS; s++)
 		for(int k = 0; k < 4; k++) out[k] += h[half + 4 * s + k] - h[4 * s + k];
-	out[3] += out[0] * (uint64_t) r->info.n_spheres; // (as skr_renderer_read_work)
+	out[3] += out[0] * (uint64_t) r->scene->info.n_spheres; // (as skr_renderer_read_work)
 	return SKR_OK;
 }
 
 int skr_renderer_read_triangle_work(skr_renderer *r, uint64_t out[3], int reset)
 {
 	if(!r || !out) return SKR_ERR_ARG;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	unsigned long long h[256 * 2];
-	SKR_HIP(hipMemcpy(h, r->d_tri_work, sizeof(h), hipMemcpyDeviceToHost)); // synchronises with prior launches
+	SKR_HIP(hipMemcpy(h, r->scene->d_tri_work, sizeof(h), hipMemcpyDeviceToHost)); // synchronises with prior launches
 	out[0] = out[1] = 0;
 	for(int s = 0; s < 256; s++)
 	{
@@ -817,8 +837,8 @@ int skr_renderer_read_triangle_work(skr_renderer *r, uint64_t out[3], int reset)
 	uint64_t w[4];
 	const int rc = read_work(r, w, 4, 0);
 	if(rc != SKR_OK) return rc;
-	out[2] = w[0] * (uint64_t) r->info.n_triangles; // raytrace.h:171-186: every radiance ray tests every triangle
-	if(reset) SKR_HIP(hipMemset(r->d_tri_work, 0, sizeof(h)));
+	out[2] = w[0] * (uint64_t) r->scene->info.n_triangles; // raytrace.h:171-186: every radiance ray tests every triangle
+	if(reset) SKR_HIP(hipMemset(r->scene->d_tri_work, 0, sizeof(h)));
 	return SKR_OK;
 }
 
@@ -832,61 +852,42 @@ int skr_render_progressive_host(skr_renderer *r, const skr_options *opt, uint32_
 	}
 	int rc = check_options(opt); // before anything is sized from width x height
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(r->device));
-	const size_t pixels = (size_t) opt->width * opt->height, bytes = pixels * 3, fbytes = h_rgbf ? pixels * 12 : 0;
-	if(bytes + fbytes > r->frame_cap)
-	{ // the device frame (u8, then float) and the two events live in the renderer: nothing to leak on an early return
-		if(r->d_frame) SKR_HIP(hipFree(r->d_frame));
-		r->d_frame = nullptr;
-		r->frame_cap = 0;
-		SKR_HIP(hipMalloc((void **) &r->d_frame, ((bytes + 15) & ~(size_t) 15) + pixels * 12));
-		r->frame_cap = bytes + pixels * 12;
-	}
-	uint8_t *d_rgb = r->d_frame;
-	float *d_rgbf = h_rgbf ? reinterpret_cast<float *>(r->d_frame + ((bytes + 15) & ~(size_t) 15)) : nullptr;
-	if(!r->frame_e0) SKR_HIP(hipEventCreate(&r->frame_e0));
-	if(!r->frame_e1) SKR_HIP(hipEventCreate(&r->frame_e1));
+	SKR_HIP(hipSetDevice(r->scene->device));
+	const size_t n = (size_t) opt->width * opt->height * 3; // (the frame's bytes, its floats)
+	HostFrame f;
+	rc = host_frame(r, n / 3, false, f);
+	if(rc != SKR_OK) return rc;
+	float *d_rgbf = h_rgbf ? f.rgbf : nullptr;
 	const uint32_t passes = opt->progressive_passes > 1 ? (uint32_t) opt->progressive_passes : 1u;
-	float total_ms = 0;
 	if(!progress || every == 0 || every >= passes)
 	{ // nobody looks before the end: the frame (or the K-pass mean) in one launch sequence
-		SKR_HIP(hipEventRecord(r->frame_e0, nullptr));
-		rc = skr_render_tiles(r, opt, (uint32_t) opt->height, 0, 1, d_rgb, d_rgbf, nullptr);
-		if(rc != SKR_OK) return rc;
-		SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
-		if(h_rgb) SKR_HIP(hipMemcpy(h_rgb, d_rgb, bytes, hipMemcpyDeviceToHost));
-		if(h_rgbf) SKR_HIP(hipMemcpy(h_rgbf, d_rgbf, fbytes, hipMemcpyDeviceToHost));
-		SKR_HIP(hipEventElapsedTime(&total_ms, r->frame_e0, r->frame_e1));
-		if(progress) (void) progress(user, passes, passes, h_rgb, h_rgbf);
-		if(kernel_ms) *kernel_ms = total_ms;
-		return SKR_OK;
+		rc = timed_host(r, [&] { return skr_render_tiles(r, opt, (uint32_t) opt->height, 0, 1, f.rgb, d_rgbf, nullptr); },
+						{{h_rgb, f.rgb, n}, {h_rgbf, d_rgbf, n * 4}}, kernel_ms);
+		if(rc == SKR_OK && progress) (void) progress(user, passes, passes, h_rgb, h_rgbf);
+		return rc;
 	}
 	// the mean is shown while it forms: after every `every` passes (and after the last) it is resolved, copied out and handed to
 	// the callback — where the SDL viewer of main.cpp:183-197 would blit.  The final mean is the one-launch result, bit for bit.
-	const size_t n = pixels * 3;
-	rc = ensure_progressive_scratch(r, n);
+	float *frame, *acc;
+	rc = progressive_scratch(r, n, frame, acc);
 	if(rc != SKR_OK) return rc;
-	float *frame = r->d_prog, *acc = r->d_prog + n;
 	skr_options pass = *opt;
 	pass.progressive_passes = 1;
+	float total_ms = 0;
 	for(uint32_t k = 0; k < passes; k++)
 	{
 		pass.seed = opt->seed + (uint64_t) k;
-		SKR_HIP(hipEventRecord(r->frame_e0, nullptr));
-		rc = render_pass(r, &pass, (uint32_t) opt->height, TileSel(), nullptr, frame, nullptr);
-		if(rc != SKR_OK) return rc;
-		SKR_HIP(skr_launch_accumulate(acc, frame, n, k == 0, nullptr));
 		const bool show = (k + 1) % every == 0 || k + 1 == passes;
-		if(show) SKR_HIP(skr_launch_resolve_accumulated(acc, k + 1, (uint32_t) opt->width, (uint32_t) opt->height, (uint32_t) opt->height, (uint32_t) opt->height, 0, 1, nullptr, d_rgb, d_rgbf, nullptr));
-		SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
-		if(show)
-		{
-			if(h_rgb) SKR_HIP(hipMemcpy(h_rgb, d_rgb, bytes, hipMemcpyDeviceToHost));
-			if(h_rgbf) SKR_HIP(hipMemcpy(h_rgbf, d_rgbf, fbytes, hipMemcpyDeviceToHost));
-		}
-		else SKR_HIP(hipEventSynchronize(r->frame_e1));
+		const uint32_t h = (uint32_t) opt->height;
 		float ms = 0;
-		SKR_HIP(hipEventElapsedTime(&ms, r->frame_e0, r->frame_e1));
+		rc = timed_host(r, [&]() -> int {
+			const int e = render_pass(r, &pass, h, TileSel(), nullptr, frame, nullptr);
+			if(e != SKR_OK) return e;
+			SKR_HIP(skr_launch_accumulate(acc, frame, n, k == 0, nullptr));
+			if(show) SKR_HIP(skr_launch_resolve_accumulated(acc, k + 1, (uint32_t) opt->width, h, h, h, 0, 1, nullptr, f.rgb, d_rgbf, nullptr));
+			return SKR_OK;
+		}, {{show ? h_rgb : nullptr, f.rgb, n}, {show ? h_rgbf : nullptr, d_rgbf, n * 4}}, &ms);
+		if(rc != SKR_OK) return rc;
 		total_ms += ms;
 		if(show && progress(user, k + 1, passes, h_rgb, h_rgbf) != 0) break; // the viewer was closed: what is in the buffers is the mean so far
 	}
@@ -903,6 +904,21 @@ int skr_render_frame_host(skr_renderer *r, const skr_options *opt, uint8_t *h_rg
 const char *skr_kernel_variant(void) { return g_variant; }
 
 // ---- ray queries (trace_rays.hip): they read the scene blob and write only the caller's arrays ----
+// the trees a query may walk under the renderer's switches (launch.h QueryTrees)
+static QueryTrees query_trees(const skr_renderer *r)
+{
+	const DeviceScene &s = *r->scene;
+	QueryTrees q{};
+	q.tree = s.d_blob + s.off_chunks;
+	q.trace = s.off_trace ? s.d_blob + s.off_trace : nullptr;
+	q.stride = (uint32_t) s.chunk_stride;
+	q.nchunks = r->sw.no_cull ? 0 : s.n_chunks;
+	q.cones = (s.cones && !r->sw.no_cones) ? 1 : 0;
+	q.trace_cones = (s.trace_cones && !r->sw.no_cones) ? 1 : 0;
+	q.ball = s.trace_ball;
+	return q;
+}
+
 int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t flags, void *d_out, void *stream)
 {
 	const bool any_hit = (flags & SKR_TRACE_ANY_HIT) != 0;
@@ -912,21 +928,16 @@ int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t 
 		return SKR_ERR_ARG;
 	}
 	if(n == 0) return SKR_OK;
-	SKR_HIP(hipSetDevice(r->device));
+	const DeviceScene &sc = *r->scene;
+	SKR_HIP(hipSetDevice(sc.device));
 	TraceScene s{};
-	s.geom = r->d_blob;
-	s.tris = r->d_blob + r->off_tris;
-	s.ns = r->info.n_spheres;
-	s.nt = r->info.n_triangles;
-	s.chunk = r->chunk_size;
-	s.stride = r->chunk_stride;
-	s.nchunks = r->sw.no_cull ? 0 : r->n_chunks;
-	s.tree = r->d_blob + r->off_chunks;
-	s.tree_cones = (r->cones && !r->sw.no_cones) ? 1 : 0;
-	s.chunks = r->off_trace ? r->d_blob + r->off_trace : nullptr;
-	s.cones = (r->trace_cones && !r->sw.no_cones) ? 1 : 0;
-	s.ball = make_float4(r->trace_ball[0], r->trace_ball[1], r->trace_ball[2], r->trace_ball[3]);
-	s.cam = f3{r->info.camera[0], r->info.camera[1], r->info.camera[2]};
+	s.geom = sc.d_blob;
+	s.tris = sc.d_blob + sc.off_tris;
+	s.ns = sc.info.n_spheres;
+	s.nt = sc.info.n_triangles;
+	s.chunk = sc.chunk_size;
+	s.cam = f3{sc.info.camera[0], sc.info.camera[1], sc.info.camera[2]};
+	s.trees = query_trees(r);
 	SKR_HIP(skr_launch_trace(s, reinterpret_cast<const float4 *>(d_rays), n, any_hit, d_out, (hipStream_t) stream));
 	return SKR_OK;
 }
@@ -945,16 +956,8 @@ int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, sk
 		skr_set_error("skr_camera_rays: sample %u of a frame with %d AA samples", sample, opt->grid_size > 0 ? opt->grid_size * opt->grid_size : 1);
 		return SKR_ERR_ARG;
 	}
-	SKR_HIP(hipSetDevice(r->device));
-	RenderParams p{};
-	p.width = opt->width;
-	p.height = opt->height;
-	camera_invariants(r, opt, p);
-	p.grid_size = opt->grid_size;
-	p.seed_lo = (uint32_t) opt->seed;
-	p.seed_hi = (uint32_t) (opt->seed >> 32);
-	p.aa_index = sample;
-	SKR_HIP(skr_launch_camera_rays(p, reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream));
+	SKR_HIP(hipSetDevice(r->scene->device));
+	SKR_HIP(skr_launch_camera_rays(camera_params(r, opt, opt->seed, sample), reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream));
 	return SKR_OK;
 }
 
@@ -970,10 +973,9 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	int rc = check_options(opt);
 	if(rc != SKR_OK) return rc;
 	if(n == 0) return SKR_OK;
-	SKR_HIP(hipSetDevice(r->device));
-	RenderParams p{};
+	SKR_HIP(hipSetDevice(r->scene->device));
+	RenderParams p = camera_params(r, opt, opt->seed, sample);
 	p.width = (int32_t) SKR_SHADE_ROW; // the plan's rows: SKR_SHADE_ROW rays each, the last one partial
-	p.height = opt->height;
 	p.tile_rows = 1;
 	p.tile_stride = 1;
 	p.out_rows = (uint32_t) (((uint64_t) n + SKR_SHADE_ROW - 1) / SKR_SHADE_ROW);
@@ -981,35 +983,18 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	rc = launch_params(r, opt, p);
 	if(rc != SKR_OK) return rc;
 	p.grid_size = 0; // (one sample: `sample`)
-	p.aa_index = sample;
 	GPlan pl;
-	if(!skr_generic_plan(p, pl))
-	{
-		skr_set_error("--depth %d with %d children per node: the tables of %u rays exceed the scratch budget (SKR_LEVELS_BUDGET_MB)", p.max_depth,
-					  p.num_path_traces + (p.legacy_reflect ? 2 * p.n_lights : 0), SKR_SHADE_ROW);
-		return SKR_ERR_UNSUPPORTED;
-	}
-	rc = ensure_level_scratch(r, pl.total);
+	const bool fits = skr_generic_plan(p, pl);
+	rc = check_plan(r, p, fits, skr_scene_kernels_lds(p), SKR_SHADE_ROW);
+	if(rc == SKR_OK) rc = r->nodes.grow(pl.total);
 	if(rc != SKR_OK) return rc;
-	p.node_scratch = r->d_nodes;
-	if(skr_scene_kernels_lds(p) > (size_t) r->lds_limit)
-	{
-		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", skr_scene_kernels_lds(p),
-					  p.n_spheres, p.n_lights, r->lds_limit);
-		return SKR_ERR_UNSUPPORTED;
-	}
+	p.node_scratch = r->nodes.p;
 	ShadeRays q{};
 	q.rays = reinterpret_cast<const float4 *>(d_rays);
 	q.keys = d_keys;
 	q.out = d_rgbf;
 	q.n = n;
-	q.tree = r->d_blob + r->off_chunks;
-	q.trace = r->off_trace ? r->d_blob + r->off_trace : nullptr;
-	q.stride = (uint32_t) r->chunk_stride;
-	q.nchunks = r->sw.no_cull ? 0 : r->n_chunks;
-	q.cones = (r->cones && !r->sw.no_cones) ? 1 : 0;
-	q.trace_cones = (r->trace_cones && !r->sw.no_cones) ? 1 : 0;
-	q.ball = make_float4(r->trace_ball[0], r->trace_ball[1], r->trace_ball[2], r->trace_ball[3]);
+	q.trees = query_trees(r);
 	r->last_levels = 0; // (the scratch no longer holds the node pipeline's tables of the last render)
 	g_variant = "shade_rays_g1";
 	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q));
@@ -1044,20 +1029,12 @@ int skr_denoise(skr_renderer *r, uint32_t width, uint32_t height, const float *d
 		skr_set_error("skr_denoise: an output overlaps an input or the other output");
 		return SKR_ERR_ARG;
 	}
-	SKR_HIP(hipSetDevice(r->device));
-	if(n > r->dn_pixels)
-	{
-		if(r->d_dn) SKR_HIP(hipFree(r->d_dn));
-		r->d_dn = nullptr;
-		r->dn_pixels = 0;
-		SKR_HIP(hipMalloc(&r->d_dn, n * (3 * sizeof(float4) + sizeof(uint32_t))));
-		r->dn_pixels = n;
-	}
-	DenoiseScratch b;
-	b.img[0] = reinterpret_cast<float4 *>(r->d_dn);
-	b.img[1] = b.img[0] + n;
-	b.guide = b.img[1] + n;
-	b.cls = reinterpret_cast<uint32_t *>(b.guide + n);
+	SKR_HIP(hipSetDevice(r->scene->device));
+	ScratchLayout L;
+	const size_t o_img0 = L.take(n * sizeof(float4)), o_img1 = L.take(n * sizeof(float4)), o_guide = L.take(n * sizeof(float4)), o_cls = L.take(n * sizeof(uint32_t));
+	const int rc = r->dn.grow(L.off);
+	if(rc != SKR_OK) return rc;
+	const DenoiseScratch b{{r->dn.at<float4>(o_img0), r->dn.at<float4>(o_img1)}, r->dn.at<float4>(o_guide), r->dn.at<uint32_t>(o_cls)};
 	SKR_HIP(skr_launch_denoise(b, width, height, d_rgbf, reinterpret_cast<const float4 *>(d_hits), (int) iterations, d_out_rgbf, d_out_rgb, (hipStream_t) stream));
 	return SKR_OK;
 }
@@ -1071,43 +1048,25 @@ int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t i
 	}
 	int rc = check_options(opt); // before anything is sized from width x height
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	const size_t n = (size_t) opt->width * opt->height;
-	if(n > r->dnframe_pixels)
-	{ // 12 (frame) + 32 (rays) + 32 (guides) + 12 (filtered) + 3 (bytes) per pixel; every part starts 16-byte aligned
-		if(r->d_dnframe) SKR_HIP(hipFree(r->d_dnframe));
-		r->d_dnframe = nullptr;
-		r->dnframe_pixels = 0;
-		SKR_HIP(hipMalloc(&r->d_dnframe, n * 91 + 64));
-		r->dnframe_pixels = n;
-	}
-	auto at = [&](size_t off) { return reinterpret_cast<char *>(r->d_dnframe) + off; };
-	const size_t o_frame = 0, o_rays = (o_frame + n * 12 + 15) & ~(size_t) 15, o_hits = o_rays + n * 32, o_out = o_hits + n * 32, o_rgb = o_out + n * 12;
-	float *frame = reinterpret_cast<float *>(at(o_frame)), *out = reinterpret_cast<float *>(at(o_out));
-	skr_ray *rays = reinterpret_cast<skr_ray *>(at(o_rays));
-	skr_hit *hits = reinterpret_cast<skr_hit *>(at(o_hits));
-	uint8_t *rgb = reinterpret_cast<uint8_t *>(at(o_rgb));
-	if(!r->frame_e0) SKR_HIP(hipEventCreate(&r->frame_e0));
-	if(!r->frame_e1) SKR_HIP(hipEventCreate(&r->frame_e1));
-	SKR_HIP(hipEventRecord(r->frame_e0, nullptr));
-	rc = skr_render_tiles(r, opt, (uint32_t) opt->height, 0, 1, nullptr, frame, nullptr); // (the K-pass mean under progressive_passes)
+	ScratchLayout L; // the frame, its camera rays and guides, the filtered frame and its bytes
+	const size_t o_frame = L.take(n * 12), o_rays = L.take(n * sizeof(skr_ray)), o_hits = L.take(n * sizeof(skr_hit)), o_out = L.take(n * 12), o_rgb = L.take(n * 3);
+	rc = r->dnframe.grow(L.off);
 	if(rc != SKR_OK) return rc;
+	float *frame = r->dnframe.at<float>(o_frame), *out = r->dnframe.at<float>(o_out);
+	skr_ray *rays = r->dnframe.at<skr_ray>(o_rays);
+	skr_hit *hits = r->dnframe.at<skr_hit>(o_hits);
+	uint8_t *rgb = r->dnframe.at<uint8_t>(o_rgb);
 	skr_options guide_opt = *opt;
 	guide_opt.grid_size = 0; // the pixel centres
-	rc = skr_camera_rays(r, &guide_opt, 0, rays, nullptr);
-	if(rc != SKR_OK) return rc;
-	rc = skr_trace_rays(r, rays, (uint32_t) n, 0, hits, nullptr);
-	if(rc != SKR_OK) return rc;
-	rc = skr_denoise(r, (uint32_t) opt->width, (uint32_t) opt->height, frame, hits, iterations, h_rgbf ? out : nullptr, h_rgb ? rgb : nullptr, nullptr);
-	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
-	if(h_rgb) SKR_HIP(hipMemcpy(h_rgb, rgb, n * 3, hipMemcpyDeviceToHost));
-	if(h_rgbf) SKR_HIP(hipMemcpy(h_rgbf, out, n * 12, hipMemcpyDeviceToHost));
-	float ms = 0;
-	SKR_HIP(hipEventSynchronize(r->frame_e1));
-	SKR_HIP(hipEventElapsedTime(&ms, r->frame_e0, r->frame_e1));
-	if(kernel_ms) *kernel_ms = ms;
-	return SKR_OK;
+	return timed_host(r, [&]() -> int {
+		int e = skr_render_tiles(r, opt, (uint32_t) opt->height, 0, 1, nullptr, frame, nullptr); // (the K-pass mean under progressive_passes)
+		if(e == SKR_OK) e = skr_camera_rays(r, &guide_opt, 0, rays, nullptr);
+		if(e == SKR_OK) e = skr_trace_rays(r, rays, (uint32_t) n, 0, hits, nullptr);
+		if(e == SKR_OK) e = skr_denoise(r, (uint32_t) opt->width, (uint32_t) opt->height, frame, hits, iterations, h_rgbf ? out : nullptr, h_rgb ? rgb : nullptr, nullptr);
+		return e;
+	}, {{h_rgb, rgb, n * 3}, {h_rgbf, out, n * 12}}, kernel_ms);
 }
 
 // ---- adaptive sampling (adaptive.hip): extra passes only for the pixels whose estimate is still noisy ----
@@ -1152,22 +1111,15 @@ int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adapt
 	}
 	int rc = check_adaptive(opt, a, "skr_render_adaptive");
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(r->device));
+	SKR_HIP(hipSetDevice(r->scene->device));
 	const hipStream_t st = (hipStream_t) stream;
 	const uint64_t pixels = (uint64_t) opt->width * (uint64_t) opt->height;
-	rc = ensure_progressive_scratch(r, (size_t) pixels * 3);
+	float *frame, *acc; // (the passes are folded into the statistics: the running sum is not used)
+	rc = progressive_scratch(r, (size_t) pixels * 3, frame, acc);
+	if(rc == SKR_OK) rc = r->ad.grow(skr_adaptive_scratch_bytes(pixels));
 	if(rc != SKR_OK) return rc;
-	if(pixels > r->ad_pixels)
-	{
-		if(r->d_ad) SKR_HIP(hipFree(r->d_ad));
-		r->d_ad = nullptr;
-		r->ad_pixels = 0;
-		SKR_HIP(hipMalloc(&r->d_ad, skr_adaptive_scratch_bytes(pixels)));
-		r->ad_pixels = (size_t) pixels;
-	}
 	if(!r->h_count) SKR_HIP(hipHostMalloc((void **) &r->h_count, sizeof(uint32_t), hipHostMallocDefault));
-	const AdaptiveScratch s = skr_adaptive_carve(r->d_ad, pixels);
-	float *frame = r->d_prog;
+	const AdaptiveScratch s = skr_adaptive_carve(r->ad.p, pixels);
 	skr_options pass = *opt;
 	pass.progressive_passes = 1;
 	// the first min_passes passes: whole frames
@@ -1202,13 +1154,7 @@ int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adapt
 			continue;
 		}
 		// query path: per AA sample the listed pixels' camera rays, shaded with the pixel words as keys (skr_shade_rays)
-		RenderParams p{};
-		p.width = opt->width;
-		p.height = opt->height;
-		camera_invariants(r, opt, p);
-		p.grid_size = opt->grid_size;
-		p.seed_lo = (uint32_t) pass.seed;
-		p.seed_hi = (uint32_t) (pass.seed >> 32);
+		RenderParams p = camera_params(r, opt, pass.seed, 0);
 		for(uint32_t aa = 0; aa < (samples ? samples : 1u); aa++)
 		{
 			p.aa_index = aa;
@@ -1231,33 +1177,16 @@ int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_
 	}
 	int rc = check_adaptive(opt, a, "skr_render_adaptive_host"); // before anything is sized from width x height
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(r->device));
-	const size_t pixels = (size_t) opt->width * opt->height, bytes = pixels * 3, need = ((bytes + 15) & ~(size_t) 15) + pixels * 12 + pixels * 4;
-	if(need > r->frame_cap)
-	{ // the device frame (u8, float, passes) lives in the renderer, as skr_render_progressive_host's does
-		if(r->d_frame) SKR_HIP(hipFree(r->d_frame));
-		r->d_frame = nullptr;
-		r->frame_cap = 0;
-		SKR_HIP(hipMalloc((void **) &r->d_frame, need));
-		r->frame_cap = need;
-	}
-	uint8_t *d_rgb = h_rgb ? r->d_frame : nullptr;
-	float *d_rgbf = h_rgbf ? reinterpret_cast<float *>(r->d_frame + ((bytes + 15) & ~(size_t) 15)) : nullptr;
-	uint32_t *d_passes = h_passes ? reinterpret_cast<uint32_t *>(r->d_frame + ((bytes + 15) & ~(size_t) 15) + pixels * 12) : nullptr;
-	if(!r->frame_e0) SKR_HIP(hipEventCreate(&r->frame_e0));
-	if(!r->frame_e1) SKR_HIP(hipEventCreate(&r->frame_e1));
-	SKR_HIP(hipEventRecord(r->frame_e0, nullptr));
-	rc = skr_render_adaptive(r, opt, a, d_rgb, d_rgbf, d_passes, nullptr);
+	SKR_HIP(hipSetDevice(r->scene->device));
+	const size_t pixels = (size_t) opt->width * opt->height;
+	HostFrame f;
+	rc = host_frame(r, pixels, true, f);
 	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipEventRecord(r->frame_e1, nullptr));
-	if(h_rgb) SKR_HIP(hipMemcpy(h_rgb, d_rgb, bytes, hipMemcpyDeviceToHost));
-	if(h_rgbf) SKR_HIP(hipMemcpy(h_rgbf, d_rgbf, pixels * 12, hipMemcpyDeviceToHost));
-	if(h_passes) SKR_HIP(hipMemcpy(h_passes, d_passes, pixels * 4, hipMemcpyDeviceToHost));
-	float ms = 0;
-	SKR_HIP(hipEventSynchronize(r->frame_e1));
-	SKR_HIP(hipEventElapsedTime(&ms, r->frame_e0, r->frame_e1));
-	if(kernel_ms) *kernel_ms = ms;
-	return SKR_OK;
+	uint8_t *d_rgb = h_rgb ? f.rgb : nullptr;
+	float *d_rgbf = h_rgbf ? f.rgbf : nullptr;
+	uint32_t *d_passes = h_passes ? f.passes : nullptr;
+	return timed_host(r, [&] { return skr_render_adaptive(r, opt, a, d_rgb, d_rgbf, d_passes, nullptr); },
+					  {{h_rgb, d_rgb, pixels * 3}, {h_rgbf, d_rgbf, pixels * 12}, {h_passes, d_passes, pixels * 4}}, kernel_ms);
 }
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)

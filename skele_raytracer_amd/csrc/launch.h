@@ -33,6 +33,17 @@ struct GPlan {
 	size_t off_ctr = 0, ctr_bytes = 0, total = 0;
 };
 
+// The trees a wave of query rays may walk (wave_common.h pick_query_tree), under the renderer's switches (api.cpp
+// query_trees).  Both trees are SKR_CULL_LEVELS sets of `stride` rows.
+struct QueryTrees {
+	const float4 *tree;  // the renderer's chunk tree, its first set: it holds for rays that start at the scene camera or on a surface
+	const float4 *trace; // the trace tree (skr_scene::trace_chunks), its first set; null: none
+	uint32_t stride;
+	int32_t nchunks;     // nodes of either tree; 0 = every triangle (no mesh, SKR_NO_CULL)
+	int32_t cones, trace_cones; // the renderer tree's and the trace tree's
+	float4 ball;         // {centre, radius}: the trace tree holds for rays that start in it
+};
+
 // A shading query (include/skr.h skr_shade_rays) on the general level pipeline: the rays are its roots, as rows of RenderParams::width
 // rays (the last row partial), banded like a frame's rows.  The kernels' second argument (render_generic.hip).
 struct ShadeRays {
@@ -40,12 +51,7 @@ struct ShadeRays {
 	const uint32_t *keys; // the counter RNG's pixel word of each ray, or null (= the ray's index)
 	float *out;           // float[n][3]
 	uint32_t n, ray0;     // rays in all; the first ray of the band being launched
-	const float4 *tree;   // the renderer's chunk tree, its first set (SKR_CULL_LEVELS sets of `stride` rows)
-	const float4 *trace;  // the trace tree (skr_scene::trace_chunks), its first set; null: none
-	uint32_t stride;
-	int32_t nchunks;      // nodes of either tree; 0 = every triangle (no mesh, SKR_NO_CULL)
-	int32_t cones, trace_cones;
-	float4 ball;          // {centre, radius}: the trace tree holds for rays that start in it
+	QueryTrees trees;
 };
 // the rays of one row of a shading query's plan
 constexpr uint32_t SKR_SHADE_ROW = 1024;
@@ -124,11 +130,8 @@ hipError_t skr_launch_camec(const float4 *geom, int ns, f3 cam_pos, float4 *out,
 struct TraceScene {
 	const float4 *geom;   // sphere rows {centre, r^2} (HBM; the rows behind them are readable: the blob's padding)
 	const float4 *tris;   // device triangles, 3 float4 each (scene_host.h)
-	const float4 *tree;   // the renderer's chunk tree, its first set (SKR_CULL_LEVELS sets of `stride` float4): waves of camera rays
-	const float4 *chunks; // the trace tree (scene_host.h trace_chunks), its first set; null: none
-	size_t stride;
-	int32_t ns, nt, nchunks, chunk, cones, tree_cones; // nchunks: nodes of either tree, 0 = every triangle; cones: the trace tree's
-	float4 ball;          // {centre, radius}: the trace tree holds for rays that start in it
+	QueryTrees trees;
+	int32_t ns, nt, chunk;
 	f3 cam;               // the scene camera: the renderer's tree holds for rays that start there
 };
 hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream);

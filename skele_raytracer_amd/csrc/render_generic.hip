@@ -145,8 +145,7 @@ SKR_DEV ShadeRays query_of() { return ShadeRays{}; }
 // renderer's tree.
 SKR_DEV void query_tree(SceneView &sv, const RenderParams &p, const ShadeRays &q, bool live, f3 o, f3 d)
 {
-	const QueryTrees t{q.tree, q.trace, q.stride, q.nchunks, q.cones, q.trace_cones, p.cam_pos, q.ball};
-	pick_query_tree(sv, t, p.g_level != 1, live, o, d);
+	pick_query_tree(sv, q.trees, p.cam_pos, p.g_level != 1, live, o, d);
 }
 
 } // namespace

@@ -28,16 +28,12 @@ SKR_DEV SceneView trace_view(const TraceScene &s, bool live, f3 o, f3 d)
 	sv.ns = s.ns;
 	sv.tris = s.tris;
 	sv.nt = TRI ? s.nt : 0;
-	sv.chunks = s.tree;
+	sv.chunks = s.trees.tree;
 	sv.nchunks = 0;
 	sv.chunk = s.chunk;
-	sv.cones = s.cones;
+	sv.cones = s.trees.trace_cones;
 	sv.tri_work = nullptr; // a query counts nothing
-	if(TRI)
-	{
-		const QueryTrees q{s.tree, s.chunks, s.stride, s.nchunks, s.tree_cones, s.cones, s.cam, s.ball};
-		pick_query_tree(sv, q, false, live, o, d);
-	}
+	if(TRI) pick_query_tree(sv, s.trees, s.cam, false, live, o, d);
 	return sv;
 }
 
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(256) void skr_ray_query_kernel(const TraceScene s, 
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	const bool valid = i < n;
-	float4 ra = make_float4(s.ball.x, s.ball.y, s.ball.z, -__builtin_inff()), rb = make_float4(0.0f, 0.0f, 1.0f, __int_as_float(-1));
+	float4 ra = make_float4(s.trees.ball.x, s.trees.ball.y, s.trees.ball.z, -__builtin_inff()), rb = make_float4(0.0f, 0.0f, 1.0f, __int_as_float(-1));
 	if(valid)
 	{
 		ra = rays[2 * (size_t) i];
