@@ -818,13 +818,14 @@ def shard_deinterleave_host(gathered, width, height, tile_rows, world):
     return out
 
 
-def debug_eval(op, inp, out_words_per_record, device=0):
-    """Run the arithmetic-spec debug kernel on n records (uint32 words)."""
+def debug_eval(op, inp, out_words_per_record, device=0, n=None):
+    """Run the arithmetic-spec debug kernel on n records (uint32 words).  n: the record count where the input is not one row per
+    record (ops 15 and 16 of include/skr.h: a scene, then the records); by default the rows of `inp`."""
     import torch
     dev = torch.device("cuda", device)
     a = torch.from_numpy(np.ascontiguousarray(inp).view(np.uint32).astype(np.int64)).to(torch.int64)
     a = a.to(dev).to(torch.int32).contiguous()  # same bits as uint32
-    n = a.shape[0]
+    n = a.shape[0] if n is None else int(n)
     o = torch.zeros((n, out_words_per_record), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _check(lib().skr_debug_eval(op, a.data_ptr(), o.data_ptr(), n, torch.cuda.current_stream(dev).cuda_stream),

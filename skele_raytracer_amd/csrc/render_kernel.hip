@@ -18,6 +18,7 @@
 
 #include "launch.h"
 #include "shade_common.h"
+#include "wave_common.h"
 
 // The direct kernel's workgroup: the scene + 4 x 192 bytes of tile — and, for a scene that is all mesh (every lane's time is the triangle
 // walk, whose scalar loads go through a 16 KB cache that more waves only thrash), padding up to a third of the CU's LDS: dragon.scn
@@ -85,12 +86,170 @@ hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStr
 // ------------------------------------------------------------ debug eval ----
 // Device-side evaluation of the arithmetic spec, one record per thread
 // (skr_debug_eval in include/skr.h).
-__global__ void skr_debug_kernel(int op, const uint32_t *in, uint32_t *out, uint32_t n)
+// Ops 12..16 (include/skr.h): the filtered predicates of device_math.h and the selection code on top of them, through the functions the
+// render kernels call.  `i` = the lane's record, `live` = it may write.
+#define SKR_DEBUG_TABLE_ROWS 80u // ops 15, 16: rows of the sphere table in the input (<= 64 spheres, the pad row, the rows table_rows asks for behind it)
+#define SKR_DEBUG_EC_PAD 8u      // ops 15, 16: rows behind the ns rows of a record's ec table
+SKR_DEV void skr_debug_predicates(int op, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t i, bool live)
 {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if(i >= n) return;
 	auto F = [](uint32_t u) { return __uint_as_float(u); };
 	auto U = [](float f) { return __float_as_uint(f); };
+	auto v3 = [&](const uint32_t *r) { return mk3(F(r[0]), F(r[1]), F(r[2])); };
+	auto v4 = [&](const uint32_t *r) { return make_float4(F(r[0]), F(r[1]), F(r[2]), F(r[3])); };
+	const float nan = __builtin_nanf("");
+	switch(op)
+	{
+		case 12: { // one ray, one sphere: sphere_bracket, and bracket_from_ec on the row skr_camec_kernel forms
+			const uint32_t *r = in + 10 * i;
+			const f3 o = v3(r), d = v3(r + 3);
+			const float4 g = v4(r + 6);
+			const RayFilt f = make_filt(d);
+			float lo = nan, hi = nan, b = nan, D = nan;
+			const bool acc = sphere_bracket(o, d, f, g, lo, hi, b, D);
+			const float4 q = camec_row(g, o);
+			float lo2 = nan, hi2 = nan, b2 = nan, D2 = nan;
+			const bool acc2 = bracket_from_ec(ld3(q), q.w, d, f, lo2, hi2, b2, D2);
+			if(live)
+			{
+				uint32_t *w = out + 10 * i;
+				w[0] = acc; w[1] = U(lo); w[2] = U(hi); w[3] = U(b); w[4] = U(D);
+				w[5] = acc2; w[6] = U(lo2); w[7] = U(hi2); w[8] = U(b2); w[9] = U(D2);
+			}
+			break;
+		}
+		case 13: { // two rays with one origin, one sphere: the test of closest_pair_deferred (wave_common.h), both slots
+			const uint32_t *r = in + 13 * i;
+			const f3 o = v3(r), d0 = v3(r + 3), d1 = v3(r + 6);
+			const float4 g = v4(r + 9);
+			const RayPair rp = make_pair(d0, d1);
+			const f3 e = o - ld3(g);
+			const float c = dot3(e, e) - g.w;
+			f2 b, D;
+			pair_bD(rp, e, c, b, D);
+			const bool cand0 = (D.x >= 0.0f) && (b.x < 0.0f);
+			const bool cand1 = (D.y >= 0.0f) && (b.y < 0.0f);
+			float l0 = nan, h0 = nan, l1 = nan, h1 = nan;
+			bool acc0 = false, acc1 = false;
+			if(cand0 || cand1)
+			{
+				f2 lo, hi;
+				pair_bracket(rp, b, D, lo, hi);
+				l0 = lo.x; h0 = hi.x; l1 = lo.y; h1 = hi.y;
+				acc0 = cand0 && bracket_decide(rp.sane0, rp.two_a.x, b.x, D.x, l0, h0);
+				acc1 = cand1 && bracket_decide(rp.sane1, rp.two_a.y, b.y, D.y, l1, h1);
+			}
+			if(live)
+			{
+				uint32_t *w = out + 12 * i;
+				w[0] = cand0; w[1] = acc0; w[2] = U(l0); w[3] = U(h0); w[4] = U(b.x); w[5] = U(D.x);
+				w[6] = cand1; w[7] = acc1; w[8] = U(l1); w[9] = U(h1); w[10] = U(b.y); w[11] = U(D.y);
+			}
+			break;
+		}
+		case 14: { // two shadow rays from one point P, one sphere: the test of occluded_pair (shade_common.h), both slots
+			const uint32_t *r = in + 13 * i;
+			const f3 o = add_scalar(v3(r), 0.000001f), L0 = v3(r + 3), L1 = v3(r + 6);
+			const float4 g = v4(r + 9);
+			const RayPair rp = make_pair(L0, L1);
+			const PairAny pa{rp.two_a, rp.two_a * 0.25f, rp.sane0, rp.sane1};
+			const f3 e = o - ld3(g);
+			const float c = dot3(e, e) - g.w;
+			f2 b, D;
+			pair_bD(rp, e, c, b, D);
+			const bool cand0 = (D.x >= 0.0f) && (b.x < 0.0f);
+			const bool cand1 = (D.y >= 0.0f) && (b.y < 0.0f);
+			bool occ0 = false, occ1 = false;
+			if(cand0 || cand1)
+			{
+				f2 m, al, rl;
+				pair_any_m(pa, b, m, al, rl);
+				if(cand0) occ0 = any_decide(pa.sane0, pa.two_a.x, pa.quarter.x, b.x, D.x, m.x, al.x, rl.x);
+				if(cand1) occ1 = any_decide(pa.sane1, pa.two_a.y, pa.quarter.y, b.y, D.y, m.y, al.y, rl.y);
+			}
+			if(live)
+			{
+				uint32_t *w = out + 4 * i;
+				w[0] = cand0; w[1] = occ0; w[2] = cand1; w[3] = occ1;
+			}
+			break;
+		}
+		case 15: { // the ec table (skr_camec_kernel's rows) of each record's origin over the scene at the head of the input
+			const uint32_t ns = in[0] <= 64u ? in[0] : 64u;
+			const float4 *table = (const float4 *) (in + 4);
+			const uint32_t *r = in + 4u + 4u * SKR_DEBUG_TABLE_ROWS + 9u * i;
+			const f3 o = v3(r);
+			if(live)
+				for(uint32_t k = 0; k < ns; k++)
+				{
+					const float4 q = camec_row(table[k], o);
+					uint32_t *w = out + ((size_t) i * (ns + SKR_DEBUG_EC_PAD) + k) * 4u;
+					w[0] = U(q.x); w[1] = U(q.y); w[2] = U(q.z); w[3] = U(q.w);
+				}
+			break;
+		}
+		case 16: { // the selection code over that scene: every closest-hit and any-hit form, both rays of the record
+			const uint32_t ns = in[0] <= 64u ? in[0] : 64u;
+			const uint32_t rec0 = 4u + 4u * SKR_DEBUG_TABLE_ROWS;
+			const uint32_t *r = in + rec0 + 9u * i;
+			// (each lane has its own ec table, so closest_sphere_from's rows come by vector loads with per-lane addresses here, not the
+			// scalar loads of the primary kernels' one table; the scalar path of table_rows runs on geom_u below.  Same arithmetic.)
+			const float4 *ec = (const float4 *) (in + rec0 + ((9u * n + 3u) & ~3u)) + (size_t) i * (ns + SKR_DEBUG_EC_PAD);
+			const f3 o = v3(r), d0 = v3(r + 3), d1 = v3(r + 6);
+			SceneView sv{}; // as trace_view (trace_rays.hip) builds one: every table in HBM, no mesh, no masks
+			sv.geom = (const float4 *) (in + 4);
+			sv.geom_u = sv.geom;
+			sv.ns = (int) ns;
+			sv.smask = nullptr;
+			const RayConst r0 = make_ray(o, d0), r1 = make_ray(o, d1);
+			int idx[8];
+			float t[8];
+			idx[0] = closest_sphere(sv, r0, t[0]);
+			idx[1] = closest_sphere(sv, r1, t[1]);
+			idx[2] = closest_sphere_from(sv, ec, r0, t[2]);
+			idx[3] = closest_sphere_from(sv, ec, r1, t[3]);
+			const RayPair rp = make_pair(d0, d1);
+			BestState s0, s1;
+			closest_pair_deferred<false>(sv, o, d0, d1, true, rp, s0, s1, 0u, 0u);
+			idx[4] = s0.best;
+			t[4] = s0.best >= 0 ? near_root_exact(rp.two_a.x, s0.b, s0.D) : __builtin_inff();
+			idx[5] = s1.best;
+			t[5] = s1.best >= 0 ? near_root_exact(rp.two_a.y, s1.b, s1.D) : __builtin_inff();
+			idx[6] = closest_sphere_exact(sv, r0, t[6]);
+			idx[7] = closest_sphere_exact(sv, r1, t[7]);
+			bool a0, a1, c0, c1;
+			uint32_t ta = 0, tc = 0;
+			occluded_pair<false>(sv, o, d0, d1, true, a0, a1, ta); // (its origin is o + 1e-6, utils.h:45)
+			occluded_pair<true>(sv, o, d0, d1, true, c0, c1, tc);
+			if(live)
+			{
+				uint32_t *w = out + 22 * i;
+				for(int k = 0; k < 8; k++)
+				{
+					w[2 * k] = (uint32_t) idx[k];
+					w[2 * k + 1] = U(t[k]);
+				}
+				w[16] = a0; w[17] = a1; w[18] = ta;
+				w[19] = c0; w[20] = c1; w[21] = tc;
+			}
+			break;
+		}
+		default: break;
+	}
+}
+
+__global__ void skr_debug_kernel(int op, const uint32_t *in, uint32_t *out, uint32_t n)
+{
+	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	auto F = [](uint32_t u) { return __uint_as_float(u); };
+	auto U = [](float f) { return __float_as_uint(f); };
+	if(op >= 12)
+	{ // the predicate ops run whole waves (occluded_pair<true> and table_rows vote wave-wide): a lane past the end evaluates the last record and writes nothing
+		const bool live = i < n;
+		if(!live) i = n - 1u;
+		skr_debug_predicates(op, in, out, n, i, live);
+		return;
+	}
+	if(i >= n) return;
 	switch(op)
 	{
 		case 0: {

@@ -224,9 +224,7 @@ __global__ void skr_camec_kernel(const float4 *geom, int ns, f3 cam_pos, float4 
 {
 	const int i = (int) (blockIdx.x * blockDim.x + threadIdx.x);
 	if(i >= ns) return;
-	const float4 g = geom[i];
-	const f3 e = cam_pos - ld3(g);
-	out[i] = make_float4(e.x, e.y, e.z, dot3(e, e) - g.w);
+	out[i] = camec_row(geom[i], cam_pos);
 }
 hipError_t skr_launch_camec(const float4 *geom, int ns, f3 cam_pos, float4 *out, hipStream_t stream)
 {

@@ -197,6 +197,11 @@ SKR_DEV int closest_sphere(const SceneView &sv, const RayConst &r, float &tmin)
 // formed once per sphere and renderer (ec[i] = {e.xyz, c}: the same subtractions, products and sums in the same order, on the device, so the
 // same floats: skr_camec_kernel, render_wave.hip) instead of once per ray: 9 of the ~17 instructions a sphere costs a ray.  The rows are
 // read like the sphere rows of the level pipelines: scalar loads, several per trip (table_rows).
+SKR_DEV float4 camec_row(float4 g, f3 o)
+{ // row i of the ec table of rays that start at o (skr_camec_kernel; the debug ops of render_kernel.hip)
+	const f3 e = o - ld3(g);
+	return make_float4(e.x, e.y, e.z, dot3(e, e) - g.w);
+}
 #ifndef SKR_CAMERA_TRIP
 #define SKR_CAMERA_TRIP 4 // spheres per trip of closest_sphere_from: config 2 (15 spheres) 1.312 / 1.284 / 1.19 ms at 1 / 2 / 4 (with the shadow loop at the same count), bear.scn (31) 0.518 / 0.500 / 0.451
 #endif
