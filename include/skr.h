@@ -487,10 +487,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  * 12 bracket: (o(3), d(3), row(4)) -> sphere_bracket {accept, lo, hi, b, D}, then the same five words of bracket_from_ec on the row
  *    {e, c} skr_camec_kernel forms for origin o.  lo, hi are NaN for a non-candidate (D < 0, b >= 0, NaN), the binary32 bracket
  *    where binary32 decided (also for a certain reject), lo == hi == t2 where the exact form decided and accepted.
- * 13 pair bracket: (o(3), d0(3), d1(3), row(4)) -> per slot {candidate, accept, lo, hi, b, D}: make_pair, pair_bD, pair_bracket and
- *    bracket_decide as the sphere test of closest_pair_deferred runs them.
- * 14 pair any-hit: (P(3), L0(3), L1(3), row(4)) -> per slot {candidate, occluded}: pair_bD, pair_any_m, any_decide as the sphere
- *    test of occluded_pair runs them; the rays start at P + 1e-6 (utils.h:45), which the op adds.
+ * 13 pair bracket: (o(3), d0(3), d1(3), row(4)) -> per slot {candidate, accept, lo, hi, b, D}: pair_closest_step, the per-sphere
+ *    body of closest_pair_deferred (make_pair, pair_bD, pair_bracket, bracket_decide, best_update), on one sphere.
+ * 14 pair any-hit: (P(3), L0(3), L1(3), row(4)) -> per slot {candidate, occluded}: pair_any_step, the per-sphere body of
+ *    occluded_pair (pair_bD, pair_any_m, any_decide), on one sphere; the rays start at P + 1e-6 (utils.h:45), which the op adds.
  * 15, 16 take a scene at the head of the input: [0] ns (<= 64), [1..3] 0, then 80 rows of 4 words (the ns spheres, the rest 0:
  *    the pad rows the sphere loops ask for), then n records (o(3), d0(3), d1(3)).
  * 15 ec tables: -> per record ns + 8 rows {o - centre, |o - centre|^2 - r*r} (skr_camec_kernel's rows for a camera at o; the
@@ -500,10 +500,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  *    slot 1 (t = near_root_exact of the slot's b, D), closest_sphere_exact(d0), (d1); then {occ0, occ1, tests} of occluded_pair<false>
  *    and of occluded_pair<true> from P = o.  index -1, t +inf: no sphere accepted.  The scene view is the one trace_rays.hip builds:
  *    every table in global memory, no masks.
- * Ops 13 and 14 restate the few lines of glue around those calls (the candidate tests, which `sane` flag goes to which slot): they
- * cover the predicates, not the two loops' own bodies.  The loops themselves run in op 16 (closest_pair_deferred<false>, both
- * occluded_pair forms, with rays on either side of `sane` in the two slots) and in the frames of the same test file; the masked
- * walks (closest_pair_deferred<true>, occluded_pair with shadow masks) run only in those frames. */
+ * Ops 13 and 14 call the very functions the two loops call per sphere, with `second` set and neither ray occluded yet.  The loops
+ * themselves run in op 16 (closest_pair_deferred<false>, both occluded_pair forms, with rays on either side of `sane` in the two
+ * slots) and in the frames of the same test file; the masked walks (closest_pair_deferred<true>, occluded_pair with shadow masks:
+ * masked_rows) run only in those frames. */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

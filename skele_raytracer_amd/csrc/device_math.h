@@ -25,6 +25,27 @@ static __device__ unsigned long long skr_diag[32 * 64];
 #define DIAG_WAVE(i, v)
 #define DIAG_LANES(i)
 #endif
+// The gate of a masked sphere walk (DESIGN.md "Shadow masks": slots 19.., "GI masks": slots 25..) into six slots from `slot`: calls,
+// spheres the wave's lanes name together, the most one lane names, ns, the sum over lanes, lanes.
+SKR_DEV void diag_mask_gate(int slot, uint32_t cand, int ns)
+{
+#if defined(SKR_DIAG) && SKR_DIAG
+	uint32_t any = 0, most = 0, sum = 0;
+	for(int k = 0; k < 32; k++)
+	{
+		const unsigned long long bk = __ballot((cand >> k) & 1u);
+		any += bk ? 1u : 0u;
+		sum += (uint32_t) __popcll(bk);
+	}
+	for(uint32_t c = 1; c <= 32; c++) most += __any((uint32_t) __popc(cand) >= c) ? 1u : 0u;
+	DIAG_WAVE(slot, 1);
+	DIAG_WAVE(slot + 1, any);
+	DIAG_WAVE(slot + 2, most);
+	DIAG_WAVE(slot + 3, ns);
+	DIAG_WAVE(slot + 4, sum);
+	DIAG_LANES(slot + 5);
+#endif
+}
 
 
 // Correctly rounded binary32 sqrt and divide.  NOT __fsqrt_rn/__fdiv_rn: in this ROCm's
@@ -435,6 +456,8 @@ struct RayFilt {
 	bool sane;           // a in a range where the relative bounds hold
 };
 
+SKR_DEV bool sane_a(float a) { return (a > 1e-18f) && (a < 1e18f); }
+
 SKR_DEV RayFilt make_filt(f3 d)
 {
 	const float a = dot3(d, d);
@@ -443,9 +466,31 @@ SKR_DEV RayFilt make_filt(f3 d)
 	f.four_a = 4 * a;
 	f.inv2a = __builtin_amdgcn_rcpf(f.two_a);
 	f.k_err = f.inv2a * 0x1p-20f;
-	f.sane = (a > 1e-18f) && (a < 1e18f);
+	f.sane = sane_a(a);
 	return f;
 }
+
+// The decision on one bracket [lo, hi] of a candidate (D >= 0, b < 0): returns accept; lo = hi = t2 where the exact form had to decide
+// and accepted.  Every bracket test, scalar and packed, ends here.  (The DIAG lines count the exact-root fallbacks of both in a
+// diagnostic build: slots 3 and 7 of tools/diag_counts.py.)
+SKR_DEV bool bracket_decide(bool sane, float two_a, float b, float D, float &lo, float &hi)
+{
+	const bool normal = sane && (D > 1e-30f) && (b < -1e-15f);
+	const bool certain_accept = normal && (lo > 1.0f) && (hi < 3.0e38f);
+	const bool certain_reject = normal && (hi < 1.0f);
+	if(certain_reject) return false;
+	if(!certain_accept)
+	{ // too close to call in binary32: the exact form decides
+		DIAG_WAVE(7, 1);
+		DIAG_LANES(3);
+		const float t = near_root_exact(two_a, b, D);
+		if(!accept_distance(t)) return false;
+		lo = hi = t;
+	}
+	return true;
+}
+// The exact t2 of an accepted bracket, from the b, D kept with it: already there where the exact form decided.
+SKR_DEV float bracket_t(float two_a, float lo, float hi, float b, float D) { return (lo == hi) ? lo : near_root_exact(two_a, b, D); }
 
 // One sphere against one ray.  Returns false for a certain miss.  Otherwise
 // [lo, hi] brackets t2 (lo == hi when it had to be resolved exactly) and b, D
@@ -464,17 +509,39 @@ SKR_DEV bool bracket_from_ec(f3 e, float c, f3 d, const RayFilt &f, float &lo, f
 	const float E = __builtin_fmaf(__builtin_fabsf(ta), 0x1p-22f, (s + __builtin_fabsf(num)) * f.k_err);
 	lo = ta - E;
 	hi = ta + E;
-	const bool normal = f.sane && (D > 1e-30f) && (b < -1e-15f);
-	const bool certain_accept = normal && (lo > 1.0f) && (hi < 3.0e38f);
-	const bool certain_reject = normal && (hi < 1.0f);
-	if(certain_reject) return false;
-	if(!certain_accept)
-	{ // too close to call in binary32: the exact form decides
-		const float t = near_root_exact(f.two_a, b, D);
-		if(!accept_distance(t)) return false;
-		lo = hi = t;
+	return bracket_decide(f.sane, f.two_a, b, D, lo, hi);
+}
+SKR_DEV bool sphere_bracket(f3 o, f3 d, const RayFilt &f, float4 sph, float &lo, float &hi, float &b, float &D)
+{
+	const f3 e = o - ld3(sph);
+	const float c = dot3(e, e) - sph.w;
+	return bracket_from_ec(e, c, d, f, lo, hi, b, D);
+}
+
+// ---- closest hit: the selection over the accepted brackets of one ray ----
+// The winner is known as soon as its bracket lies strictly below every other accepted sphere's (others_lo > hi); its b, D are kept
+// for its exact t2.  Strict <: the first index wins a tie of equal `hi`, and such a tie is an overlap, which the exact loop settles.
+struct BestState {
+	int best;
+	float lo, hi, others_lo, b, D;
+};
+SKR_DEV BestState best_none() { return BestState{-1, __builtin_inff(), __builtin_inff(), __builtin_inff(), 0.0f, 0.0f}; }
+SKR_DEV void best_update(float &s_hi, float &s_others_lo, float &s_lo, int &s_best, float &s_b, float &s_D, int i, float lo, float hi, float b, float D)
+{ // (on the fields one by one: the scalar loops keep them in locals, see closest_of_rows)
+	if(hi < s_hi)
+	{
+		s_others_lo = __builtin_fminf(s_others_lo, s_lo);
+		s_lo = lo;
+		s_hi = hi;
+		s_best = i;
+		s_b = b;
+		s_D = D;
 	}
-	return true;
+	else s_others_lo = __builtin_fminf(s_others_lo, lo);
+}
+SKR_DEV void best_update(BestState &s, bool acc, int i, float lo, float hi, float b, float D)
+{
+	if(acc) best_update(s.hi, s.others_lo, s.lo, s.best, s.b, s.D, i, lo, hi, b, D);
 }
 
 // ---- two rays with a common origin, evaluated with packed binary32 arithmetic ----
@@ -498,8 +565,8 @@ SKR_DEV RayPair make_pair(f3 d0, f3 d1)
 	r.four_a = 4.0f * a;
 	r.inv2a = f2{__builtin_amdgcn_rcpf(r.two_a.x), __builtin_amdgcn_rcpf(r.two_a.y)};
 	r.k_err = r.inv2a * 0x1p-20f;
-	r.sane0 = (a.x > 1e-18f) && (a.x < 1e18f);
-	r.sane1 = (a.y > 1e-18f) && (a.y < 1e18f);
+	r.sane0 = sane_a(a.x);
+	r.sane1 = sane_a(a.y);
 	return r;
 }
 
@@ -523,22 +590,38 @@ SKR_DEV void pair_bracket(const RayPair &r, f2 b, f2 D, f2 &lo, f2 &hi)
 	hi = ta + E;
 }
 
-// Classify one component: returns accept; *resolved_t is set (and lo = hi = t) when the exact form had to decide.
-SKR_DEV bool bracket_decide(bool sane, float two_a, float b, float D, float &lo, float &hi)
+// The closest-hit step of one sphere row g (index i) for both rays from o (`second`: ray 1 exists): the whole per-sphere body of
+// closest_pair_deferred, selection included.  Returns what debug op 13 records (brackets NaN where neither slot is a candidate).
+struct PairHit {
+	bool cand0, cand1, acc0, acc1;
+	float lo0, hi0, lo1, hi1;
+	f2 b, D;
+};
+SKR_DEV PairHit pair_closest_step(const RayPair &rp, const f3 &o, bool second, const float4 &g, int i, BestState &s0, BestState &s1)
 {
-	const bool normal = sane && (D > 1e-30f) && (b < -1e-15f);
-	const bool certain_accept = normal && (lo > 1.0f) && (hi < 3.0e38f);
-	const bool certain_reject = normal && (hi < 1.0f);
-	if(certain_reject) return false;
-	if(!certain_accept)
+	const f3 e = o - ld3(g);
+	const float c = dot3(e, e) - g.w;
+	f2 b, D;
+	pair_bD(rp, e, c, b, D);
+	const bool cand0 = (D.x >= 0.0f) && (b.x < 0.0f);
+	const bool cand1 = second && (D.y >= 0.0f) && (b.y < 0.0f);
+	bool acc0 = false, acc1 = false;
+	float l0, h0, l1, h1;
+	l0 = h0 = l1 = h1 = __builtin_nanf("");
+	DIAG_WAVE(0, 1);
+	if(cand0 || cand1)
 	{
-		DIAG_WAVE(7, 1);
-		DIAG_LANES(3);
-		const float t = near_root_exact(two_a, b, D);
-		if(!accept_distance(t)) return false;
-		lo = hi = t;
+		DIAG_WAVE(1, 1);
+		DIAG_LANES(2);
+		f2 lo, hi;
+		pair_bracket(rp, b, D, lo, hi);
+		l0 = lo.x; h0 = hi.x; l1 = lo.y; h1 = hi.y;
+		acc0 = cand0 && bracket_decide(rp.sane0, rp.two_a.x, b.x, D.x, l0, h0);
+		acc1 = cand1 && bracket_decide(rp.sane1, rp.two_a.y, b.y, D.y, l1, h1);
+		best_update(s0, acc0, i, l0, h0, b.x, D.x);
+		best_update(s1, acc1, i, l1, h1, b.y, D.y);
 	}
-	return true;
+	return PairHit{cand0, cand1, acc0, acc1, l0, h0, l1, h1, b, D};
 }
 
 // The any-hit form (shadow rays, utils.h:42-58) needs no bracket, only "is t2 > 1": with m = fl(-b - 2a) — one rounding
@@ -567,12 +650,39 @@ SKR_DEV bool any_decide(bool sane, float two_a, float quarter, float b, float D,
 	DIAG_WAVE(7, 1);
 	return accept_distance(near_root_exact(two_a, b, D));
 }
-
-SKR_DEV bool sphere_bracket(f3 o, f3 d, const RayFilt &f, float4 sph, float &lo, float &hi, float &b, float &D)
+SKR_DEV PairAny make_pair_any(const RayPair &rp) { return PairAny{rp.two_a, rp.two_a * 0.25f, rp.sane0, rp.sane1}; }
+// The any-hit step of one sphere row g (index i) for both shadow rays from o: the whole per-sphere body of occluded_pair.  A ray that
+// is occluded already is not tested; `tests` counts as the reference's loop, which returns at the first occluder (utils.h:52-55).
+// Returns the candidate flags (debug op 14 records them and occ0, occ1).
+struct PairCand { bool cand0, cand1; };
+SKR_DEV PairCand pair_any_step(const RayPair &rp, const PairAny &pa, const f3 &o, const float4 &g, int i, bool &occ0, bool &occ1, uint32_t &tests)
 {
-	const f3 e = o - ld3(sph);
-	const float c = dot3(e, e) - sph.w;
-	return bracket_from_ec(e, c, d, f, lo, hi, b, D);
+	const f3 e = o - ld3(g);
+	const float c = dot3(e, e) - g.w;
+	f2 b, D;
+	pair_bD(rp, e, c, b, D);
+	// b >= 0 or D < 0 (or NaN): certain miss for that ray
+	const bool cand0 = !occ0 && (D.x >= 0.0f) && (b.x < 0.0f);
+	const bool cand1 = !occ1 && (D.y >= 0.0f) && (b.y < 0.0f);
+	DIAG_WAVE(4, 1);
+	if(cand0 || cand1)
+	{
+		DIAG_WAVE(5, 1);
+		DIAG_LANES(6);
+		f2 m, al, rl;
+		pair_any_m(pa, b, m, al, rl);
+		if(cand0)
+		{
+			occ0 = any_decide(pa.sane0, pa.two_a.x, pa.quarter.x, b.x, D.x, m.x, al.x, rl.x);
+			if(occ0) tests += (uint32_t) i + 1u;
+		}
+		if(cand1)
+		{
+			occ1 = any_decide(pa.sane1, pa.two_a.y, pa.quarter.y, b.y, D.y, m.y, al.y, rl.y);
+			if(occ1) tests += (uint32_t) i + 1u;
+		}
+	}
+	return PairCand{cand0, cand1};
 }
 
 // utils.h:181-213 with the edges e1 = v1-v0, e2 = v2-v0 precomputed on the host

@@ -117,59 +117,30 @@ SKR_DEV void skr_debug_predicates(int op, const uint32_t *in, uint32_t *out, uin
 			}
 			break;
 		}
-		case 13: { // two rays with one origin, one sphere: the test of closest_pair_deferred (wave_common.h), both slots
+		case 13: { // two rays with one origin, one sphere: pair_closest_step, the test of closest_pair_deferred (wave_common.h), both slots
 			const uint32_t *r = in + 13 * i;
 			const f3 o = v3(r), d0 = v3(r + 3), d1 = v3(r + 6);
-			const float4 g = v4(r + 9);
-			const RayPair rp = make_pair(d0, d1);
-			const f3 e = o - ld3(g);
-			const float c = dot3(e, e) - g.w;
-			f2 b, D;
-			pair_bD(rp, e, c, b, D);
-			const bool cand0 = (D.x >= 0.0f) && (b.x < 0.0f);
-			const bool cand1 = (D.y >= 0.0f) && (b.y < 0.0f);
-			float l0 = nan, h0 = nan, l1 = nan, h1 = nan;
-			bool acc0 = false, acc1 = false;
-			if(cand0 || cand1)
-			{
-				f2 lo, hi;
-				pair_bracket(rp, b, D, lo, hi);
-				l0 = lo.x; h0 = hi.x; l1 = lo.y; h1 = hi.y;
-				acc0 = cand0 && bracket_decide(rp.sane0, rp.two_a.x, b.x, D.x, l0, h0);
-				acc1 = cand1 && bracket_decide(rp.sane1, rp.two_a.y, b.y, D.y, l1, h1);
-			}
+			BestState s0 = best_none(), s1 = s0;
+			const PairHit h = pair_closest_step(make_pair(d0, d1), o, true, v4(r + 9), 0, s0, s1);
 			if(live)
 			{
 				uint32_t *w = out + 12 * i;
-				w[0] = cand0; w[1] = acc0; w[2] = U(l0); w[3] = U(h0); w[4] = U(b.x); w[5] = U(D.x);
-				w[6] = cand1; w[7] = acc1; w[8] = U(l1); w[9] = U(h1); w[10] = U(b.y); w[11] = U(D.y);
+				w[0] = h.cand0; w[1] = h.acc0; w[2] = U(h.lo0); w[3] = U(h.hi0); w[4] = U(h.b.x); w[5] = U(h.D.x);
+				w[6] = h.cand1; w[7] = h.acc1; w[8] = U(h.lo1); w[9] = U(h.hi1); w[10] = U(h.b.y); w[11] = U(h.D.y);
 			}
 			break;
 		}
-		case 14: { // two shadow rays from one point P, one sphere: the test of occluded_pair (shade_common.h), both slots
+		case 14: { // two shadow rays from one point P, one sphere: pair_any_step, the test of occluded_pair (shade_common.h), both slots
 			const uint32_t *r = in + 13 * i;
 			const f3 o = add_scalar(v3(r), 0.000001f), L0 = v3(r + 3), L1 = v3(r + 6);
-			const float4 g = v4(r + 9);
 			const RayPair rp = make_pair(L0, L1);
-			const PairAny pa{rp.two_a, rp.two_a * 0.25f, rp.sane0, rp.sane1};
-			const f3 e = o - ld3(g);
-			const float c = dot3(e, e) - g.w;
-			f2 b, D;
-			pair_bD(rp, e, c, b, D);
-			const bool cand0 = (D.x >= 0.0f) && (b.x < 0.0f);
-			const bool cand1 = (D.y >= 0.0f) && (b.y < 0.0f);
 			bool occ0 = false, occ1 = false;
-			if(cand0 || cand1)
-			{
-				f2 m, al, rl;
-				pair_any_m(pa, b, m, al, rl);
-				if(cand0) occ0 = any_decide(pa.sane0, pa.two_a.x, pa.quarter.x, b.x, D.x, m.x, al.x, rl.x);
-				if(cand1) occ1 = any_decide(pa.sane1, pa.two_a.y, pa.quarter.y, b.y, D.y, m.y, al.y, rl.y);
-			}
+			uint32_t tests = 0;
+			const PairCand h = pair_any_step(rp, make_pair_any(rp), o, v4(r + 9), 0, occ0, occ1, tests);
 			if(live)
 			{
 				uint32_t *w = out + 4 * i;
-				w[0] = cand0; w[1] = occ0; w[2] = cand1; w[3] = occ1;
+				w[0] = h.cand0; w[1] = occ0; w[2] = h.cand1; w[3] = occ1;
 			}
 			break;
 		}

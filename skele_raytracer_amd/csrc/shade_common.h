@@ -83,6 +83,18 @@ SKR_DEV void sphere_rows(const SceneView &sv, F test)
 {
 	table_rows<SKR_SPHERE_TRIP>(sv.geom_u, sv.ns, test, [] { return true; });
 }
+// `test(row, index)` for the spheres a lane's candidate mask names, lowest index first (the lanes' rows differ: LDS)
+template <typename F>
+SKR_DEV void masked_rows(const SceneView &sv, uint32_t cand, F test)
+{
+	uint32_t rest = cand;
+	while(rest)
+	{
+		const int i = __builtin_ctz(rest);
+		test(sv.geom[i], i);
+		rest &= rest - 1u;
+	}
+}
 
 // Row i of the mesh tables (triangles, culling data: HBM, never written by a kernel), i wave-uniform: one s_load_dwordx4 into SGPRs.
 // Through the plain pointer the compiler issues a VECTOR load with a uniform address (it cannot prove that no store of the kernel
@@ -160,37 +172,31 @@ SKR_DEV int closest_sphere_exact(const SceneView &sv, const RayConst &r, float &
 // known as soon as its bracket lies strictly below every other accepted
 // sphere's; its exact t2 is then formed once.  Overlapping brackets (two
 // surfaces within ~1e-6 relative of each other along the ray) fall back to the
-// exact loop for that lane.
-SKR_DEV int closest_sphere(const SceneView &sv, const RayConst &r, float &tmin)
+// exact loop for that lane.  The rows of `table`, K per trip; `bracket(row, f, lo, hi, b, D)` is the test of one row.
+template <int K, typename B>
+SKR_DEV int closest_of_rows(const SceneView &sv, const float4 *table, const RayConst &r, float &tmin, B bracket)
 {
 	const RayFilt f = make_filt(r.d);
 	int best = -1;
 	float best_lo = __builtin_inff(), best_hi = __builtin_inff(), others_lo = __builtin_inff();
 	float best_b = 0.0f, best_D = 0.0f;
-	sphere_rows(sv, [&](const float4 g, int i)
+	table_rows<K>(table, sv.ns, [&](const float4 row, int i)
 	{
 		float lo, hi, b, D;
-		if(sphere_bracket(r.o, r.d, f, g, lo, hi, b, D))
-		{
-			if(hi < best_hi)
-			{
-				others_lo = __builtin_fminf(others_lo, best_lo);
-				best_lo = lo;
-				best_hi = hi;
-				best = i;
-				best_b = b;
-				best_D = D;
-			}
-			else others_lo = __builtin_fminf(others_lo, lo);
-		}
-	});
+		if(bracket(row, f, lo, hi, b, D)) best_update(best_hi, others_lo, best_lo, best, best_b, best_D, i, lo, hi, b, D);
+	}, [] { return true; });
 	tmin = __builtin_inff();
 	if(best >= 0)
 	{
-		if(others_lo > best_hi) tmin = (best_lo == best_hi) ? best_lo : near_root_exact(f.two_a, best_b, best_D);
+		if(others_lo > best_hi) tmin = bracket_t(f.two_a, best_lo, best_hi, best_b, best_D);
 		else best = closest_sphere_exact(sv, r, tmin);
 	}
 	return best;
+}
+SKR_DEV int closest_sphere(const SceneView &sv, const RayConst &r, float &tmin)
+{
+	return closest_of_rows<SKR_SPHERE_TRIP>(sv, sv.geom_u, r, tmin, // (the rows of sphere_rows)
+		[&](const float4 g, const RayFilt &f, float &lo, float &hi, float &b, float &D) { return sphere_bracket(r.o, r.d, f, g, lo, hi, b, D); });
 }
 
 // closest_sphere() for rays that all start at ONE point (the camera: main.cpp:140-182), with e = o - C and c = e.e - r^2 of utils.h:115-118
@@ -207,34 +213,25 @@ SKR_DEV float4 camec_row(float4 g, f3 o)
 #endif
 SKR_DEV int closest_sphere_from(const SceneView &sv, const float4 *ec, const RayConst &r, float &tmin)
 {
-	const RayFilt f = make_filt(r.d);
-	int best = -1;
-	float best_lo = __builtin_inff(), best_hi = __builtin_inff(), others_lo = __builtin_inff();
-	float best_b = 0.0f, best_D = 0.0f;
-	table_rows<SKR_CAMERA_TRIP>(ec, sv.ns, [&](const float4 q, int i)
+	return closest_of_rows<SKR_CAMERA_TRIP>(sv, ec, r, tmin,
+		[&](const float4 q, const RayFilt &f, float &lo, float &hi, float &b, float &D) { return bracket_from_ec(ld3(q), q.w, r.d, f, lo, hi, b, D); });
+}
+
+// closest_pair_deferred's end for one slot: where the brackets overlap the exact loop names the winner, and its b, D are formed again
+// (b, D and not t: classify_child, render_nodes.hip, forms t only on mesh scenes).
+SKR_DEV void best_resolve(const SceneView &sv, f3 o, f3 d, float four_a, BestState &s)
+{
+	if(s.best >= 0 && !(s.others_lo > s.hi))
 	{
-		float lo, hi, b, D;
-		if(bracket_from_ec(ld3(q), q.w, r.d, f, lo, hi, b, D))
-		{
-			if(hi < best_hi)
-			{
-				others_lo = __builtin_fminf(others_lo, best_lo);
-				best_lo = lo;
-				best_hi = hi;
-				best = i;
-				best_b = b;
-				best_D = D;
-			}
-			else others_lo = __builtin_fminf(others_lo, lo);
-		}
-	}, [] { return true; });
-	tmin = __builtin_inff();
-	if(best >= 0)
-	{
-		if(others_lo > best_hi) tmin = (best_lo == best_hi) ? best_lo : near_root_exact(f.two_a, best_b, best_D);
-		else best = closest_sphere_exact(sv, r, tmin);
+		DIAG_WAVE(8, 1);
+		float tmin;
+		const RayConst r = make_ray(o, d);
+		s.best = closest_sphere_exact(sv, r, tmin);
+		const f3 e = o - ld3(sv.geom[s.best]);
+		s.b = 2 * dot3(d, e);
+		const float c = dot3(e, e) - sv.geom[s.best].w;
+		s.D = s.b * s.b - four_a * c;
 	}
-	return best;
 }
 
 // The conservative line-sphere test of the culling data (scene_host.cpp build_triangle_chunks): false only where
@@ -447,72 +444,22 @@ SKR_DEV uint32_t gi_cands(const RenderParams &p, int row, f3 d0, f3 d1, bool sec
 #define SKR_COHERENT_TRIP 4 // spheres per trip of the coherent shadow loop (the wave-wide exit is looked at once per trip)
 #endif
 // With shadow masks (the level pipelines, !COHERENT): `cand` = the union of the lane's two masks (shadow_mask_of).  A sphere outside a
-// ray's mask provably fails the test below (its D < 0), so each lane walks only its own candidates, lowest index first: the first
+// ray's mask provably fails pair_any_step's candidate test (its D < 0), so each lane walks only its own candidates, lowest index first: the first
 // occluder it finds is the one the loop over every sphere finds, and every decision and count is the same.
 template <bool COHERENT>
 SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second, bool &occ0, bool &occ1, uint32_t &tests, uint32_t cand = 0u)
 {
 	const f3 o = add_scalar(P, 0.000001f);
 	const RayPair rp = make_pair(L0, L1);
-	const PairAny pa{rp.two_a, rp.two_a * 0.25f, rp.sane0, rp.sane1};
+	const PairAny pa = make_pair_any(rp);
 	occ0 = false;
 	occ1 = !second;
-	auto test = [&](const float4 g, int i)
-	{
-		const f3 e = o - ld3(g);
-		const float c = dot3(e, e) - g.w;
-		f2 b, D;
-		pair_bD(rp, e, c, b, D);
-		// b >= 0 or D < 0 (or NaN): certain miss for that ray
-		const bool cand0 = !occ0 && (D.x >= 0.0f) && (b.x < 0.0f);
-		const bool cand1 = !occ1 && (D.y >= 0.0f) && (b.y < 0.0f);
-		DIAG_WAVE(4, 1);
-		if(cand0 || cand1)
-		{
-			DIAG_WAVE(5, 1);
-			DIAG_LANES(6);
-			f2 m, al, rl;
-			pair_any_m(pa, b, m, al, rl);
-			if(cand0)
-			{
-				occ0 = any_decide(pa.sane0, pa.two_a.x, pa.quarter.x, b.x, D.x, m.x, al.x, rl.x);
-				if(occ0) tests += (uint32_t) i + 1u; // the reference's loop returns here (utils.h:52-55)
-			}
-			if(cand1)
-			{
-				occ1 = any_decide(pa.sane1, pa.two_a.y, pa.quarter.y, b.y, D.y, m.y, al.y, rl.y);
-				if(occ1) tests += (uint32_t) i + 1u;
-			}
-		}
-	};
+	auto test = [&](const float4 g, int i) { pair_any_step(rp, pa, o, g, i, occ0, occ1, tests); };
 	if(COHERENT) table_rows<SKR_COHERENT_TRIP>(sv.geom_u, sv.ns, test, [&] { return !__all(occ0 && occ1); }); // (the wave-wide exit, once per trip)
 	else if(sv.smask)
 	{
-#if defined(SKR_DIAG) && SKR_DIAG
-		{ // the gate of DESIGN.md "Shadow masks": spheres the wave's lanes name together, the most one lane names, the sum over lanes
-			uint32_t any = 0, most = 0, sum = 0;
-			for(int k = 0; k < 32; k++)
-			{
-				const unsigned long long bk = __ballot((cand >> k) & 1u);
-				any += bk ? 1u : 0u;
-				sum += (uint32_t) __popcll(bk);
-			}
-			for(uint32_t c = 1; c <= 32; c++) most += __any((uint32_t) __popc(cand) >= c) ? 1u : 0u;
-			DIAG_WAVE(19, 1);
-			DIAG_WAVE(20, any);
-			DIAG_WAVE(21, most);
-			DIAG_WAVE(22, sv.ns);
-			DIAG_WAVE(23, sum);
-			DIAG_LANES(24);
-		}
-#endif
-		uint32_t rest = cand;
-		while(rest)
-		{
-			const int i = __builtin_ctz(rest);
-			test(sv.geom[i], i); // (the lanes' rows differ: LDS)
-			rest &= rest - 1u;
-		}
+		diag_mask_gate(19, cand, sv.ns);
+		masked_rows(sv, cand, test);
 	}
 	else sphere_rows(sv, test);
 	if(!occ0) tests += (uint32_t) sv.ns;

@@ -49,7 +49,7 @@ SKR_DEV bool any_sphere_before(const SceneView &sv, const RayConst &r, float tma
 		if(!occ && sphere_bracket(r.o, r.d, f, g, lo, hi, b, D))
 		{
 			if(hi < tmax) occ = true;
-			else if(lo < tmax) occ = ((lo == hi) ? lo : near_root_exact(f.two_a, b, D)) < tmax;
+			else if(lo < tmax) occ = bracket_t(f.two_a, lo, hi, b, D) < tmax;
 		}
 	}, [&] { return !__all(occ); });
 	return occ;

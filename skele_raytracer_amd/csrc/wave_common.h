@@ -39,45 +39,10 @@ SKR_DEV int lanes_below(unsigned long long m)
 // Children 2j and 2j+1 of a node share their origin (raytrace.h:128), one Philox call
 // (DESIGN.md "RNG") and, per sphere, e = o - C and c = e.e - r^2; the per-ray part runs in
 // packed binary32 (device_math.h RayPair).  Same values as child_round(), half the issue slots.
-struct BestState {
-	int best;
-	float lo, hi, others_lo, b, D;
-};
-
-SKR_DEV void best_update(BestState &s, bool acc, int i, float lo, float hi, float b, float D)
-{
-	if(acc)
-	{
-		if(hi < s.hi)
-		{
-			s.others_lo = __builtin_fminf(s.others_lo, s.lo);
-			s.lo = lo;
-			s.hi = hi;
-			s.best = i;
-			s.b = b;
-			s.D = D;
-		}
-		else s.others_lo = __builtin_fminf(s.others_lo, lo);
-	}
-}
-
-SKR_DEV void best_resolve(const SceneView &sv, f3 o, f3 d, float four_a, BestState &s)
-{
-	if(s.best >= 0 && !(s.others_lo > s.hi))
-	{ // brackets overlap: the exact loop names the winner; recompute its coefficients
-		DIAG_WAVE(8, 1);
-		float tmin;
-		const RayConst r = make_ray(o, d);
-		s.best = closest_sphere_exact(sv, r, tmin);
-		const f3 e = o - ld3(sv.geom[s.best]);
-		s.b = 2 * dot3(d, e);
-		const float c = dot3(e, e) - sv.geom[s.best].w;
-		s.D = s.b * s.b - four_a * c;
-	}
-}
+// (The selection state and its update: device_math.h BestState; the end of a slot: shade_common.h best_resolve.)
 
 // With GI masks (`masked`, wave-uniform): `cand` = the union of the lane's two masks (shade_common.h gi_cands).  A sphere outside a
-// ray's mask provably fails the candidate test below (its D < 0 or b >= 0), so each lane walks only its own candidates, lowest index
+// ray's mask provably fails pair_closest_step's candidate test (its D < 0 or b >= 0), so each lane walks only its own candidates, lowest index
 // first, rows from LDS: best_update sees the same candidates in the same order, and every decision is the one of the loop over every
 // sphere.  A wave with a lane that names every sphere (no mask for it) takes that loop.  GIM = false: the loop over every sphere only,
 // compiled without any of the masked walk (kernels that run without masks keep their code).
@@ -85,64 +50,16 @@ template <bool GIM>
 SKR_DEV void closest_pair_deferred(const SceneView &sv, f3 o, f3 d0, f3 d1, bool second, const RayPair &rp, BestState &s0, BestState &s1,
 								   uint32_t cand, uint32_t all)
 {
-	s0 = BestState{-1, __builtin_inff(), __builtin_inff(), __builtin_inff(), 0.0f, 0.0f};
-	s1 = s0;
-	auto test = [&](const float4 g, int i)
-	{
-		const f3 e = o - ld3(g);
-		const float c = dot3(e, e) - g.w;
-		f2 b, D;
-		pair_bD(rp, e, c, b, D);
-		const bool cand0 = (D.x >= 0.0f) && (b.x < 0.0f);
-		const bool cand1 = second && (D.y >= 0.0f) && (b.y < 0.0f);
-		DIAG_WAVE(0, 1);
-		if(cand0 || cand1)
-		{
-			DIAG_WAVE(1, 1);
-			DIAG_LANES(2);
-			f2 lo, hi;
-			pair_bracket(rp, b, D, lo, hi);
-			float l0 = lo.x, h0 = hi.x, l1 = lo.y, h1 = hi.y;
-			const bool acc0 = cand0 && bracket_decide(rp.sane0, rp.two_a.x, b.x, D.x, l0, h0);
-			const bool acc1 = cand1 && bracket_decide(rp.sane1, rp.two_a.y, b.y, D.y, l1, h1);
-			best_update(s0, acc0, i, l0, h0, b.x, D.x);
-			best_update(s1, acc1, i, l1, h1, b.y, D.y);
-		}
-	};
+	s0 = s1 = best_none();
+	auto test = [&](const float4 g, int i) { pair_closest_step(rp, o, second, g, i, s0, s1); };
 	bool masked = GIM;
 	if constexpr(GIM)
 	{
-#if defined(SKR_DIAG) && SKR_DIAG
-		{ // the gate of DESIGN.md "GI masks": spheres the wave's lanes name together, the most one lane names, the sum over lanes
-			uint32_t any = 0, most = 0, sum = 0;
-			for(int k = 0; k < 32; k++)
-			{
-				const unsigned long long bk = __ballot((cand >> k) & 1u);
-				any += bk ? 1u : 0u;
-				sum += (uint32_t) __popcll(bk);
-			}
-			for(uint32_t c = 1; c <= 32; c++) most += __any((uint32_t) __popc(cand) >= c) ? 1u : 0u;
-			DIAG_WAVE(25, 1);
-			DIAG_WAVE(26, any);
-			DIAG_WAVE(27, most);
-			DIAG_WAVE(28, sv.ns);
-			DIAG_WAVE(29, sum);
-			DIAG_LANES(30);
-			DIAG_WAVE(31, __any(cand == all) ? 1u : 0u);
-		}
-#endif
+		diag_mask_gate(25, cand, sv.ns);
+		DIAG_WAVE(31, __any(cand == all) ? 1u : 0u);
 		masked = !__any(cand == all);
 	}
-	if(GIM && masked)
-	{
-		uint32_t rest = cand;
-		while(rest)
-		{
-			const int i = __builtin_ctz(rest);
-			test(sv.geom[i], i); // (the lanes' rows differ: LDS)
-			rest &= rest - 1u;
-		}
-	}
+	if(GIM && masked) masked_rows(sv, cand, test);
 	else sphere_rows(sv, test);
 	best_resolve(sv, o, d0, rp.four_a.x, s0);
 	if(second) best_resolve(sv, o, d1, rp.four_a.y, s1);

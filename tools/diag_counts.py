@@ -17,8 +17,8 @@ L.skr_diag_read_nodes(C.c_void_p(out.ctypes.data), 1)
 r.render(opt); torch.cuda.synchronize()
 L.skr_diag_read_nodes(C.c_void_p(out.ctypes.data), 1)
 # (the counters of render_nodes.hip's translation unit: the trace, leaf and finalize kernels of the node pipeline)
-names = ["closest-pair iterations", "closest-pair candidate paths", "  lanes in them", "exact-root fallbacks (lanes)", "shadow-pair iterations", "shadow candidate paths",
-         "  lanes in them", "exact-root fallbacks (wave events)", "bracket overlaps -> exact loop (wave events)", "leaf shading batches", "  hits in them",
+names = ["closest-pair iterations", "closest-pair candidate paths", "  lanes in them", "exact-root fallbacks of bracket tests, pair and scalar (lanes)", "shadow-pair iterations", "shadow candidate paths",
+         "  lanes in them", "exact-root fallbacks, bracket (pair and scalar) and any-hit tests (wave events)", "bracket overlaps -> exact loop (wave events)", "leaf shading batches", "  hits in them",
          "activation batches", "  records in them", "closest-pair candidate RAYS", "  accepted", "shadow candidate RAYS", "  occluders found", "  closest-pair candidates a t2 <= 1 pre-test rejects", "  closest-pair candidate paths left with it",
          "masked shadow-pair calls (wave events)", "  (a) spheres named by some lane, summed", "  (b) most spheres one lane names, summed", "  ns, summed",
          "  spheres named, summed over lanes", "  lanes in them",
