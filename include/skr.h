@@ -251,6 +251,13 @@ int skr_renderer_last_parent_count(skr_renderer *r, uint32_t *n);
 /* Number of level-1 sphere hit records the last launch (its last band) queued (node pipeline;
  * 0 for the other kernel variants and at depth 2); synchronous. */
 int skr_renderer_last_level1_count(skr_renderer *r, uint32_t *n);
+/* Frames of one camera share their primary stage: where a --gillum frame takes the node pipeline without --jsample, the primary hits,
+ * the pixels of the rays that hit no sphere and their counted work depend on the scene, the camera, the image and the tile selection
+ * but not on the seed, so a renderer keeps them from one frame and the next frame under the same options (another seed, another
+ * pass of a progressive or adaptive render) starts behind them.  Images and work counters are what they are without it.  This
+ * returns how many frames of `r` built that stage and how many reused it (either pointer may be null); SKR_PRIMARY_CACHE=0 turns
+ * the reuse off.  A tile table in caller memory (skr_render_tile_list) is never assumed unchanged: such frames always build. */
+int skr_renderer_primary_cache_stats(skr_renderer *r, uint64_t *builds, uint64_t *replays);
 /* Whole frame into HOST memory (W*H*3 bytes), synchronous; what the CLI uses. */
 int skr_render_frame_host(skr_renderer *r, const skr_options *opt, uint8_t *h_rgb, float *kernel_ms);
 /* The same with the float frame as a second output (h_rgb or h_rgbf may be NULL, not both) and — under

@@ -106,10 +106,27 @@ struct skr_renderer {
 	int last_levels = 0;     // ... and how many levels they count (0: the launch took another path)
 	bool timing = false;
 	bool count_tri = false; // skr_renderer_count_triangle_work
+	// the node pipeline's level-0 stage kept in `nodes` (launch.h PrimaryKey, take_node_scratch)
+	PrimaryKey level0_key{};
+	bool level0_kept = false;
+	uint64_t level0_builds = 0, level0_replays = 0; // skr_renderer_primary_cache_stats
 	// skr_renderer_kernel_ms: event pairs around the dominant kernel of recent launches
 	std::vector<SkrTimingHook> timed;
 	std::vector<SkrTimingHook> free_pairs;
 };
+
+// The level pipelines' scratch of `need` bytes, for a launch that will overwrite it.  Whoever takes `nodes` takes it here: the level-0
+// stage a node-pipeline frame may have left in it (launch.h PrimaryKey) is forgotten, and only render_pass, which knows what it
+// launches, keeps one again.  *kept: the stage was still there, in an allocation that did not move.
+static int take_node_scratch(skr_renderer *r, size_t need, bool *kept = nullptr)
+{
+	const size_t had = r->nodes.bytes;
+	const bool was_kept = r->level0_kept;
+	r->level0_kept = false;
+	const int rc = r->nodes.grow(need);
+	if(kept) *kept = rc == SKR_OK && was_kept && r->nodes.bytes == had;
+	return rc;
+}
 
 static void load_switches(SkrSwitches &sw)
 {
@@ -123,11 +140,15 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_GI_MASK")) sw.gi_mask = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_GI_SURFACE")) sw.gi_surface = atoi(e) > 0 ? 1 : 0;
+	if(const char *e = getenv("SKR_PRIMARY_CACHE")) sw.primary_cache = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_ADAPTIVE_PATH")) sw.adaptive_path = !strcmp(e, "frame") ? 1 : !strcmp(e, "query") ? 2 : 0;
 }
 
 // (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
 void skr_copy_switches(skr_renderer *dst, const skr_renderer *src) { dst->sw = src->sw; }
+// (multi_gpu.cpp) skr_render_tile_list for a table the caller owns and never rewrites in place: table_id (not 0) names its contents
+int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
+							   float *d_rgbf, void *stream);
 
 // The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | shadow
 // masks | GI masks | trace tree, then 16 rows of padding (the sphere loops ask for the rows of a trip ahead without a bounds test,
@@ -397,6 +418,7 @@ struct TileSel {
 	uint32_t first = 0, stride = 1, max_tiles = 0xffffffffu;
 	const uint32_t *d_table = nullptr;
 	uint32_t n_slots = 0;
+	uint64_t table_id = 0; // what the owner of d_table calls its present contents (skr_render_tile_list_owned); 0: the caller's memory, contents unknown
 };
 static uint32_t sel_tiles(const skr_options *opt, uint32_t tile_rows, const TileSel &ts)
 {
@@ -533,10 +555,15 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	LaunchPlan lp;
 	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp);
 	rc = check_plan(r, p, fits, lp.lds_bytes, 0);
-	if(rc == SKR_OK) rc = r->nodes.grow(lp.scratch_bytes);
+	bool kept = false;
+	if(rc == SKR_OK && lp.path != SKR_PATH_DIRECT) rc = take_node_scratch(r, lp.scratch_bytes, &kept);
 	if(rc == SKR_OK) rc = r->acc.grow(lp.acc_bytes);
 	if(rc != SKR_OK) return rc;
 	if(lp.path != SKR_PATH_DIRECT) p.node_scratch = r->nodes.p;
+	// frames of one camera share the node pipeline's level-0 stage: replay it if the scratch still holds it under this launch's key
+	PrimaryKey key;
+	const bool keeps = lp.path == SKR_PATH_NODES && skr_primary_key(p, lp.nodes, ts.table_id, key);
+	if(keeps) lp.nodes.level0 = kept && !memcmp(&key, &r->level0_key, sizeof key) ? SKR_LEVEL0_REPLAY : SKR_LEVEL0_BUILD;
 	if(lp.acc_bytes) p.acc = static_cast<float *>(r->acc.p);
 	SkrTimingHook hook;
 	if(r->timing)
@@ -564,6 +591,12 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
 	if(r->timing) r->timed.push_back(hook);
+	if(keeps)
+	{ // (only behind a launch that went through)
+		r->level0_key = key;
+		r->level0_kept = true;
+		(lp.nodes.level0 == SKR_LEVEL0_REPLAY ? r->level0_replays : r->level0_builds)++;
+	}
 	return SKR_OK;
 }
 
@@ -619,7 +652,9 @@ int skr_render_tiles(skr_renderer *r, const skr_options *opt, uint32_t tile_rows
 	return render_impl(r, opt, tile_rows, ts, d_rgb, d_rgbf, stream);
 }
 
-int skr_render_tile_list(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint8_t *d_rgb, float *d_rgbf, void *stream)
+// table_id: the identity of the table's present contents, from its owner (0: unknown — such a launch never replays a level-0 stage)
+static int render_tile_list(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
+							float *d_rgbf, void *stream)
 {
 	if(!d_tiles)
 	{
@@ -629,7 +664,21 @@ int skr_render_tile_list(skr_renderer *r, const skr_options *opt, uint32_t tile_
 	TileSel ts;
 	ts.d_table = d_tiles;
 	ts.n_slots = n_slots;
+	ts.table_id = table_id;
 	return render_impl(r, opt, tile_rows, ts, d_rgb, d_rgbf, stream);
+}
+
+int skr_render_tile_list(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint8_t *d_rgb, float *d_rgbf, void *stream)
+{
+	return render_tile_list(r, opt, tile_rows, d_tiles, n_slots, 0, d_rgb, d_rgbf, stream);
+}
+
+int skr_renderer_primary_cache_stats(skr_renderer *r, uint64_t *builds, uint64_t *replays)
+{
+	if(!r) return SKR_ERR_ARG;
+	if(builds) *builds = r->level0_builds;
+	if(replays) *replays = r->level0_replays;
+	return SKR_OK;
 }
 
 // Per tile of `tile_rows` image rows: the work its pixels cost, counted — the tile is rendered on its own and the work counters read
@@ -986,7 +1035,7 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	GPlan pl;
 	const bool fits = skr_generic_plan(p, pl);
 	rc = check_plan(r, p, fits, skr_scene_kernels_lds(p), SKR_SHADE_ROW);
-	if(rc == SKR_OK) rc = r->nodes.grow(pl.total);
+	if(rc == SKR_OK) rc = take_node_scratch(r, pl.total);
 	if(rc != SKR_OK) return rc;
 	p.node_scratch = r->nodes.p;
 	ShadeRays q{};
@@ -1198,3 +1247,9 @@ int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stre
 }
 
 } // extern "C"
+
+int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
+							   float *d_rgbf, void *stream)
+{
+	return render_tile_list(r, opt, tile_rows, d_tiles, n_slots, table_id, d_rgb, d_rgbf, stream);
+}

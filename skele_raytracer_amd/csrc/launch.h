@@ -8,6 +8,16 @@
 
 #include "render_params.h"
 
+// The level-0 stage of the node pipeline (skr_primary_kernel: the primary hits as nodes, the final pixels of the rays that hit no sphere,
+// its share of the work counters) reads neither the seed nor the AA index where grid_size == 0, so frames of one camera share it:
+//   RUN     the primary kernel, nothing kept (several bands, --jsample, triangle work counted, SKR_PRIMARY_CACHE=0);
+//   BUILD   the primary kernel, which also records each output pixel's class and its counter sums in the scratch;
+//   REPLAY  no primary kernel: the level-0 tables and their count are still in the scratch, skr_primary_replay_kernel emits the pixels
+//           that are no node and adds the recorded sums.
+enum { SKR_LEVEL0_RUN = 0, SKR_LEVEL0_BUILD, SKR_LEVEL0_REPLAY };
+// the class of an output pixel (one byte each at NodePlan::off_cls)
+enum { SKR_PIX_NONE = 0, SKR_PIX_NODE, SKR_PIX_BACKGROUND, SKR_PIX_TRIANGLE }; // NONE: no pixel of the image (an empty tile slot, a row past the height)
+
 // The plan of one band of the node pipeline (render_nodes.hip): table sizes for the worst case, every pixel a node, every child a hit.
 constexpr int SKR_NODE_LEVELS_MAX = 33;
 struct NodePlan {
@@ -18,6 +28,9 @@ struct NodePlan {
 	uint32_t cap[SKR_NODE_LEVELS_MAX] = {};
 	size_t off_nodes[SKR_NODE_LEVELS_MAX] = {}, off_shade[SKR_NODE_LEVELS_MAX] = {}, off_recs[SKR_NODE_LEVELS_MAX] = {}, off_res[SKR_NODE_LEVELS_MAX] = {}, off_ixh[SKR_NODE_LEVELS_MAX] = {};
 	size_t off_ctr = 0, ctr_bytes = 0, total = 0, banded = 0;
+	size_t off_cls = 0, off_sums = 0; // the kept level-0 stage (PrimaryKey): a class byte per output pixel of the band; the primary kernel's work counters, shard by shard
+	size_t off_girow = 0;             // ... and a word per level-0 node: its row of GI masks (RenderParams::gi_row0)
+	int level0 = SKR_LEVEL0_RUN; // how this launch gets its level-0 nodes (api.cpp render_pass decides; the plan itself says SKR_LEVEL0_RUN)
 	size_t lds_leaf = 0;     // the leaf kernel's workgroup LDS: the scene + the per-wave rings and windows
 	size_t lds = 0;          // the largest workgroup LDS among the schedule's kernels (flat: skr_scene_kernels_lds; persistent: lds_leaf)
 };
@@ -122,8 +135,34 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl); // false: not one band 
 // q: a shading query (p.width = SKR_SHADE_ROW, p.out_rows its rows, p.aa_index its sample); null: a frame
 hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q = nullptr);
 // render_wave.hip
+// Every value the level-0 stage of a node-pipeline launch depends on, and where it is kept: what skr_primary_kernel and plan_for
+// (render_nodes.hip) read.  A frame replays the stage only if its key equals, byte for byte, the key the scratch was last built under
+// (api.cpp render_pass).  The outputs (rgb, rgbf) are not in it: the nodes carry output-pixel indices, and the replay kernel emits into
+// whatever the frame names.
+struct PrimaryKey {
+	int32_t width, height;
+	uint32_t tile_rows, first_tile, tile_stride, out_rows;
+	const uint32_t *tile_table; // the table's address says nothing about its contents: ...
+	uint64_t tile_table_id;     // ... the identity of its contents, from whoever owns it (multi_gpu.cpp ShardMap::generation)
+	float inv_width, inv_height, aspect, angle;
+	f3 cam_pos, cam_dir, cam_up, cam_right, background;
+	int32_t n_spheres, n_tris, n_lights;
+	const float4 *scene, *cam_ec, *tri_chunks; // the scene blob, the camera rows, the chunk tree's level
+	int32_t tri_chunk_size, tri_cones, n_tri_chunks;
+	int32_t use_shadows, pow_steps, num_path_traces, max_depth, flat, levels;
+	const void *gi_index, *gi_surface; // what the stored rows of GI masks were looked up in (null: SKR_GI_MASK=0 / SKR_GI_SURFACE=0)
+	uint32_t band_nblk;
+	const void *scratch;        // the renderer's allocation, and where the plan puts the stage in it
+	const void *counters;
+	size_t off_ctr, off_nodes0, off_shade0, off_cls, off_sums, off_girow, total;
+};
+// false: the launch does not keep its level-0 stage (see SKR_LEVEL0_RUN); tile_table_id: 0 = a table of unknown contents
+bool skr_primary_key(const RenderParams &p, const NodePlan &pl, uint64_t tile_table_id, PrimaryKey &key);
 hipError_t skr_launch_wave(const RenderParams &p, size_t lds, hipStream_t stream);
 hipError_t skr_launch_primary(const RenderParams &p, dim3 grid, size_t lds, hipStream_t stream);
+// the same, recording the stage: cls = a byte per output pixel, sums = SKR_COUNTER_SHARDS x 4 words, zeroed here; p.gi_row0 = a word per node
+hipError_t skr_launch_primary_build(const RenderParams &p, dim3 grid, size_t lds, uint8_t *cls, unsigned long long *sums, hipStream_t stream);
+hipError_t skr_launch_primary_replay(const RenderParams &p, const uint8_t *cls, const unsigned long long *sums, hipStream_t stream);
 hipError_t skr_launch_resolve(const RenderParams &p, hipStream_t stream);
 hipError_t skr_launch_camec(const float4 *geom, int ns, f3 cam_pos, float4 *out, hipStream_t stream);
 // trace_rays.hip: the ray queries (include/skr.h skr_trace_rays, skr_camera_rays).  Not a render: no plan, no counters, no timing.

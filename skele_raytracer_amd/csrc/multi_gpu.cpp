@@ -37,6 +37,8 @@
 
 void skr_set_error(const char *fmt, ...);
 void skr_copy_switches(skr_renderer *dst, const skr_renderer *src); // api.cpp
+int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
+							   float *d_rgbf, void *stream); // api.cpp
 
 namespace {
 
@@ -198,6 +200,7 @@ struct ShardMap {
 	uint32_t T = 0, k_max = 0;
 	std::vector<uint32_t> slot_of_tile;
 	uint32_t *d_tiles = nullptr;        // k_max entries: the tiles of `rank` in slot order (0xFFFFFFFF: an empty slot)
+	uint64_t generation = 0;            // names the contents of d_tiles: a new number, never 0, from next_generation() whenever the table is rebuilt
 	uint32_t *d_slot_of_tile = nullptr; // T entries
 };
 
@@ -252,6 +255,14 @@ int plan_map(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, uint32
 	return SKR_OK;
 }
 
+// One sequence for every map of the process: a renderer that kept its level-0 stage under one map's table (api.cpp render_pass) must not
+// take another map's table at the same address for it.
+uint64_t next_generation()
+{
+	static std::atomic<uint64_t> last{0};
+	return ++last;
+}
+
 void free_map(ShardMap &m)
 {
 	if(m.d_tiles) (void) hipFree(m.d_tiles);
@@ -280,6 +291,7 @@ int ensure_map(ShardMap &m, skr_renderer *r, const skr_options *opt, const Frame
 	SKR_HIP(hipMalloc((void **) &m.d_tiles, (size_t) m.k_max * sizeof(uint32_t)));
 	SKR_HIP(hipMalloc((void **) &m.d_slot_of_tile, (size_t) m.T * sizeof(uint32_t)));
 	SKR_HIP(hipMemcpy(m.d_tiles, mine.data(), (size_t) m.k_max * sizeof(uint32_t), hipMemcpyHostToDevice));
+	m.generation = next_generation();
 	SKR_HIP(hipMemcpy(m.d_slot_of_tile, m.slot_of_tile.data(), (size_t) m.T * sizeof(uint32_t), hipMemcpyHostToDevice));
 	return SKR_OK;
 }
@@ -459,7 +471,7 @@ int render_rank(Rank &k, int set, const skr_options *opt, uint32_t tile_rows, hi
 	rc = ensure_map(k.map, k.r, opt, key, shared);
 	if(rc != SKR_OK) return rc;
 	if(start) SKR_HIP(hipEventRecord(start, rs));
-	rc = skr_render_tile_list(rr, opt, tile_rows, k.map.d_tiles, k.map.k_max, b.d_gather + (size_t) k.rank * b.chunk, nullptr, rs);
+	rc = skr_render_tile_list_owned(rr, opt, tile_rows, k.map.d_tiles, k.map.k_max, k.map.generation, b.d_gather + (size_t) k.rank * b.chunk, nullptr, rs);
 	if(rc != SKR_OK) return rc;
 	if(set != SERIAL)
 	{

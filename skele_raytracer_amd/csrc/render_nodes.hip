@@ -129,8 +129,12 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 		cn.rays += second ? 2u : 1u;
 		const RayPair rp = make_pair(d0, d1);
 		BestState s0, s1;
-		// (the grids' row: the surface patches, with the node's sphere from its shading row, made this kernel slower — DESIGN.md §5.8)
-		closest_pair<GIM>(sv, p, GIM ? gi_origin_row(p, co) : -1, co, d0, d1, second, rp, s0, s1);
+		// the node's row of GI masks: stored with a level-0 node of a kept stage (p.gi_row0, wave-uniform: the patch row of its sphere's
+		// surface where there is one); else the grids' row, looked up here (the surface patches, with the node's sphere from its shading
+		// row, made this kernel slower — DESIGN.md §5.8)
+		int gi_row = -1;
+		if(GIM) gi_row = p.gi_row0 ? p.gi_row0[node] : gi_origin_row(p, co);
+		closest_pair<GIM>(sv, p, gi_row, co, d0, d1, second, rp, s0, s1);
 		hit0 = classify_child(sv, co, d0, rp.two_a.x, rp.four_a.x, s0, black0);
 		rec0 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s0.best & 0xffff) | ((2u * j) << 16)), q1a, q2a);
 		if(second)
@@ -801,8 +805,13 @@ static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, NodePlan &
 			pl.off_ixh[L] = s.take(((n * PP + 63) / 64 + 4) * IXH_ROWS * 16);
 		}
 	}
-	pl.total = s.off;
 	pl.banded = s.off - (pl.off_nodes[0]); // what grows with the band; the counters are fixed
+	// the kept level-0 stage (launch.h PrimaryKey), behind every table so that they keep their places: a class byte per output pixel of
+	// the band, and the primary kernel's share of the work counters
+	pl.off_cls = s.take((size_t) nblk * 256u);
+	pl.off_sums = s.take((size_t) SKR_COUNTER_SHARDS * 4 * sizeof(unsigned long long));
+	pl.off_girow = s.take((size_t) nblk * 256u * sizeof(int32_t));
+	pl.total = s.off;
 	return true;
 }
 
@@ -908,11 +917,24 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStr
 			const bool timed = hook && s == nsamp - 1 && blk0 == 0; // (the first band of the last sample: a full-size band)
 			p.band_blk0 = blk0;
 			p.band_nblk = blocks - blk0 < pl.band_nblk ? blocks - blk0 : pl.band_nblk;
-			e = hipMemsetAsync(ctr0, 0, pl.ctr_bytes, stream);
-			if(e != hipSuccess) return e;
 			p.nd_dst = nodes(0);
 			p.ns_dst = shade(0);
-			e = skr_launch_primary(p, dim3(p.band_nblk), lds_scene, stream);
+			uint8_t *cls = reinterpret_cast<uint8_t *>(base + pl.off_cls);
+			unsigned long long *sums = reinterpret_cast<unsigned long long *>(base + pl.off_sums);
+			int32_t *const gi_row0 = pl.level0 != SKR_LEVEL0_RUN ? reinterpret_cast<int32_t *>(base + pl.off_girow) : nullptr;
+			p.gi_row0 = gi_row0;
+			if(pl.level0 == SKR_LEVEL0_REPLAY)
+			{ // the level-0 tables and ctr0[0], their count, are the build frame's: only the level blocks behind it start from zero
+				e = hipMemsetAsync(ctr0 + SKR_PULL_STRIDE, 0, pl.ctr_bytes - SKR_PULL_STRIDE * sizeof(uint32_t), stream);
+				if(e == hipSuccess) e = skr_launch_primary_replay(p, cls, sums, stream);
+			}
+			else
+			{
+				e = hipMemsetAsync(ctr0, 0, pl.ctr_bytes, stream);
+				if(e == hipSuccess)
+					e = pl.level0 == SKR_LEVEL0_BUILD ? skr_launch_primary_build(p, dim3(p.band_nblk), lds_scene, cls, sums, stream)
+													  : skr_launch_primary(p, dim3(p.band_nblk), lds_scene, stream);
+			}
 			if(e != hipSuccess) return e;
 			if(D == 2 && !flat)
 			{ // the level-0 nodes' children are the leaves
@@ -932,6 +954,7 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStr
 				p.nd_src = nodes(L - 1);
 				p.ns_src = shade(L - 1);
 				p.nd_src_level0 = L == 1;
+				p.gi_row0 = L == 1 ? gi_row0 : nullptr; // (deeper levels' nodes have no stored rows)
 				p.nd_count = L == 1 ? ctr0 : lc_prefix_host(lvl_ctr(L - 1));
 				p.rc = reinterpret_cast<float4 *>(base + pl.off_recs[L]);
 				p.rc_cap = pl.cap[L];

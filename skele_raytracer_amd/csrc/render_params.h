@@ -27,8 +27,10 @@ struct f3 {
 enum SkrPipeline { SKR_PIPE_AUTO = 0, SKR_PIPE_NODES, SKR_PIPE_GENERIC, SKR_PIPE_OTHER };
 struct SkrSwitches {
 	int32_t pipeline = SKR_PIPE_AUTO; // SKR_PIPELINE = nodes | generic: which level pipeline takes a --gillum tree (tests, A/B runs)
-	int16_t no_cones = 0, no_cull = 0; // SKR_NO_CONES, SKR_NO_CULL: triangle-walk culling off  (two halves of one word: the struct stays 20 bytes, so that
+	int8_t no_cones = 0, no_cull = 0;  // SKR_NO_CONES, SKR_NO_CULL: triangle-walk culling off  (four quarters of one word: the struct stays 20 bytes, so that
 	                                   // every field of RenderParams behind it keeps its offset and the kernels that never read the switches their code)
+	int8_t primary_cache = 1;          // SKR_PRIMARY_CACHE = 1 | 0: frames of one camera replay the node pipeline's level-0 stage / every frame runs skr_primary_kernel
+	int8_t reserved = 0;
 	int32_t budget_mb = 0;            // SKR_LEVELS_BUDGET_MB: scratch budget of the level pipelines (0 = default)
 	int32_t flat = 0;                 // SKR_FLAT = 1 | 0: the node pipeline's flat schedule forced on (+1) / off (-1); unset: by launch size
 	int8_t shadow_mask = 1;           // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
@@ -36,6 +38,8 @@ struct SkrSwitches {
 	int8_t gi_surface = 1;            // SKR_GI_SURFACE = 1 | 0: GI origins on a sphere take their row of masks from the surface patches / the 3D grids only
 	int8_t adaptive_path = 0;         // SKR_ADAPTIVE_PATH = frame | query: the path of every adaptive round (+1 / +2); unset: by active share (four quarters of one word, as above)
 };
+
+static_assert(sizeof(SkrSwitches) == 20, "SkrSwitches keeps its 20 bytes");
 
 struct RenderParams {
 	SkrSwitches sw; // (host side only)
@@ -100,7 +104,13 @@ struct RenderParams {
 	uint32_t g_last;          // activate: the hits of the last level (their children are shade(depth 0) == 0) are finished at once
 	int32_t n_fog;            // (see fog_row)
 	const float4 *g_nodes_src; // nodes of the level above (trace, activate) / of the level being summed (finalize): 5 float4 each
-	float4 *g_nodes_dst;      // nodes being written (activate)
+	union {
+		float4 *g_nodes_dst;  // nodes being written (activate)
+		// node pipeline (it has no g_nodes_dst; one word for both, so that every field keeps its offset and every kernel that reads neither
+		// its code): the row of GI masks of every level-0 node (shade_common.h gi_surface_row), stored by skr_primary_build_kernel with the
+		// node and kept with it across frames (launch.h SKR_LEVEL0_BUILD); null = not stored, skr_trace_kernel looks its lanes' rows up itself
+		int32_t *gi_row0;
+	};
 	// the shadow masks (shadow_cells.h; the level pipelines' shadow walk, shade_common.h occluded_pair): SKR_SHADOW_TABLE_WORDS per point light,
 	// in the scene blob (HBM, never written by a kernel); null = every shadow ray tests every sphere.  They hold for shading points P with
 	// fl(|Lp - P|^2) <= shadow_reach2; shadow_all = the mask of every sphere.

@@ -122,8 +122,10 @@ __global__ __launch_bounds__(256) void skr_direct_kernel(const RenderParams p)
 #else
 #define SKR_PRIMARY_ATTR
 #endif
-template <bool TRIS>
-__global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_kernel(const RenderParams p)
+// BUILD: the launch keeps its level-0 stage (launch.h SKR_LEVEL0_BUILD): every lane with an output pixel also stores the pixel's class,
+// and the workgroup's counter sums go to `sums` as well, shard by shard as to p.counters.
+template <bool TRIS, bool BUILD>
+static __device__ __forceinline__ void primary_body(const RenderParams &p, uint8_t *cls, unsigned long long *sums)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_kernel(const
 
 	Counters cn{0, 0, 0};
 	f3 colour = mk3(0, 0, 0), co = mk3(0, 0, 0), N = mk3(0, 0, 1);
-	bool hit = false;
+	bool hit = false, is_bg = false;
 	int sph_hit = 0;
 	if(valid)
 	{
@@ -169,7 +171,11 @@ __global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_kernel(const
 		float tmin;
 		const int sph = closest_sphere_from(sv, p.cam_ec, r, tmin);
 		if(sv.nt > 0 && any_triangle_closer(sv, r, tmin)) colour = mk3(0, 0, 0);
-		else if(sph < 0) colour = p.background;
+		else if(sph < 0)
+		{
+			colour = p.background;
+			if(BUILD) is_bg = true;
+		}
 		else
 		{
 			hit = true;
@@ -191,6 +197,7 @@ __global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_kernel(const
 		s_cnt[4] = total ? atomicAdd(&p.qctr[0], total) : 0u;
 	}
 	__syncthreads();
+	if(BUILD && x < p.width && orow < p.out_rows) cls[out_pix] = (uint8_t) (hit ? SKR_PIX_NODE : !valid ? SKR_PIX_NONE : is_bg ? SKR_PIX_BACKGROUND : SKR_PIX_TRIANGLE);
 	if(hit)
 	{
 		uint32_t idx = s_cnt[4] + (uint32_t) lanes_below(M);
@@ -202,6 +209,9 @@ __global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_kernel(const
 		grow[1] = make_float4(N.y, N.z, __uint_as_float(pixel), __uint_as_float(0u));
 		srow[0] = make_float4(colour.x, colour.y, colour.z, __uint_as_float((uint32_t) sph_hit));
 		srow[1] = make_float4(0.0f, __uint_as_float(out_pix), __uint_as_float(pixel), __uint_as_float(0u));
+		// the node's row of GI masks, looked up once where the node is made: the level-1 trace kernel's lanes (N/2 per node) load it
+		// instead of walking the index themselves — which is what makes the surface patches' tighter rows affordable there
+		if(BUILD) p.gi_row0[idx] = p.gi_index ? gi_surface_row(p, sv, sph_hit, co) : -1;
 	}
 	else if(valid) emit_sample(p, out_pix, colour); // this sample of this pixel is final
 	if(p.counters)
@@ -215,8 +225,52 @@ __global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_kernel(const
 			atomicAdd(&c4[1], (unsigned long long) b);
 			atomicAdd(&c4[2], (unsigned long long) c);
 			atomicAdd(&c4[3], (unsigned long long) d4);
+			if(BUILD)
+			{
+				unsigned long long *k4 = sums + 4u * shard;
+				atomicAdd(&k4[0], (unsigned long long) a);
+				atomicAdd(&k4[1], (unsigned long long) b);
+				atomicAdd(&k4[2], (unsigned long long) c);
+				atomicAdd(&k4[3], (unsigned long long) d4);
+			}
 		}
 	}
+}
+template <bool TRIS>
+__global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_kernel(const RenderParams p)
+{
+	primary_body<TRIS, false>(p, nullptr, nullptr);
+}
+template <bool TRIS>
+__global__ __launch_bounds__(256) SKR_PRIMARY_ATTR void skr_primary_build_kernel(const RenderParams p, uint8_t *cls, unsigned long long *sums)
+{
+	primary_body<TRIS, true>(p, cls, sums);
+}
+
+// A frame that replays the level-0 stage (launch.h SKR_LEVEL0_REPLAY) runs this in place of the primary kernel: a lane per four output
+// pixels reads their classes and emits the ones no node will write — the background, or black where a triangle took the ray —, and the
+// first lanes add the work the primary kernel counted, shard by shard.  cls is read a word at a time: its table ends on a 256-byte
+// boundary (launch.h ScratchLayout).
+__global__ __launch_bounds__(256) void skr_primary_replay_kernel(const RenderParams p, const uint8_t *cls, const unsigned long long *sums)
+{
+	const uint32_t n = (uint32_t) p.width * p.out_rows; // (< 2^31: the plan's worst-case tables, render_nodes.hip plan_for)
+	const uint32_t gid = blockIdx.x * 256u + threadIdx.x, first = gid * 4u;
+	if(first < n)
+	{
+		const uint32_t w = reinterpret_cast<const uint32_t *>(cls)[gid];
+		for(uint32_t j = 0; j < 4u && first + j < n; j++)
+		{
+			const uint32_t c = (w >> (8u * j)) & 255u;
+			if(c == SKR_PIX_BACKGROUND) emit_sample(p, first + j, p.background);
+			else if(c == SKR_PIX_TRIANGLE) emit_sample(p, first + j, mk3(0, 0, 0));
+		}
+	}
+	if(p.counters)
+		for(uint32_t i = gid; i < SKR_COUNTER_SHARDS * 4u; i += gridDim.x * 256u)
+		{
+			const unsigned long long v = sums[i];
+			if(v) atomicAdd(&p.counters[i], v);
+		}
 }
 
 // Once per renderer: e = cam_pos - C and c = e.e - r^2 of utils.h:115-118 per sphere, for every ray that starts at the camera (closest_sphere_from).
@@ -282,6 +336,80 @@ hipError_t skr_launch_primary(const RenderParams &p, dim3 grid, size_t lds, hipS
 	else hipLaunchKernelGGL(skr_primary_kernel<false>, grid, dim3(256), lds, stream, p);
 	return hipGetLastError();
 }
+hipError_t skr_launch_primary_build(const RenderParams &p, dim3 grid, size_t lds, uint8_t *cls, unsigned long long *sums, hipStream_t stream)
+{
+	const hipError_t e = hipMemsetAsync(sums, 0, (size_t) SKR_COUNTER_SHARDS * 4 * sizeof(unsigned long long), stream);
+	if(e != hipSuccess) return e;
+	if(p.n_tris > 0) hipLaunchKernelGGL(skr_primary_build_kernel<true>, grid, dim3(256), lds, stream, p, cls, sums);
+	else hipLaunchKernelGGL(skr_primary_build_kernel<false>, grid, dim3(256), lds, stream, p, cls, sums);
+	return hipGetLastError();
+}
+hipError_t skr_launch_primary_replay(const RenderParams &p, const uint8_t *cls, const unsigned long long *sums, hipStream_t stream)
+{
+	const uint64_t lanes = ((uint64_t) p.width * p.out_rows + 3) / 4;
+	hipLaunchKernelGGL(skr_primary_replay_kernel, dim3((unsigned) ((lanes + 255) / 256)), dim3(256), 0, stream, p, cls, sums);
+	return hipGetLastError();
+}
+
+// Fills `key` for a node-pipeline launch under plan `pl`; false where the launch cannot keep its level-0 stage: --jsample (the primary
+// rays are jittered per sample), several bands (each band reuses the level-0 tables), triangle work counted (p.tri_work: a walk per
+// frame is what the caller asked to count), the switch off, a tile table whose contents nobody vouches for.
+// seed_lo / seed_hi and aa_index are deliberately NOT in the key: with grid_size == 0 primary_ray (wave_common.h) takes the pixel
+// centre and never draws a random number, and nothing behind it in the primary kernel — the closest sphere, P, N, direct_light<true>,
+// the shadow walks — reads them.  That is what lets frames that differ only in their seed share the stage.
+bool skr_primary_key(const RenderParams &p, const NodePlan &pl, uint64_t tile_table_id, PrimaryKey &key)
+{
+	const uint32_t blocks = (uint32_t) ((p.width + 15) / 16) * ((p.out_rows + 15) / 16);
+	if(!p.sw.primary_cache || p.grid_size != 0 || pl.band_nblk < blocks || p.tri_work) return false;
+	if(p.tile_table && tile_table_id == 0) return false;
+	memset(&key, 0, sizeof key); // (its padding too: keys are compared as bytes)
+	key.width = p.width;
+	key.height = p.height;
+	key.tile_rows = p.tile_rows;
+	key.first_tile = p.first_tile;
+	key.tile_stride = p.tile_stride;
+	key.out_rows = p.out_rows;
+	key.tile_table = p.tile_table;
+	key.tile_table_id = p.tile_table ? tile_table_id : 0;
+	key.inv_width = p.inv_width;
+	key.inv_height = p.inv_height;
+	key.aspect = p.aspect;
+	key.angle = p.angle;
+	key.cam_pos = p.cam_pos;
+	key.cam_dir = p.cam_dir;
+	key.cam_up = p.cam_up;
+	key.cam_right = p.cam_right;
+	key.background = p.background;
+	key.n_spheres = p.n_spheres;
+	key.n_tris = p.n_tris;
+	key.n_lights = p.n_lights;
+	key.scene = p.sph_geom;
+	key.cam_ec = p.cam_ec;
+	key.tri_chunks = p.tri_chunks;
+	key.tri_chunk_size = p.tri_chunk_size;
+	key.tri_cones = p.tri_cones;
+	key.n_tri_chunks = p.n_tri_chunks;
+	key.use_shadows = p.use_shadows;
+	key.pow_steps = p.pow_steps;
+	key.gi_index = p.gi_index;
+	key.gi_surface = p.gi_surface;
+	key.num_path_traces = p.num_path_traces;
+	key.max_depth = p.max_depth;
+	key.flat = pl.flat ? 1 : 0;
+	key.levels = pl.levels;
+	key.band_nblk = pl.band_nblk;
+	key.scratch = p.node_scratch;
+	key.counters = p.counters;
+	key.off_ctr = pl.off_ctr;
+	key.off_nodes0 = pl.off_nodes[0];
+	key.off_shade0 = pl.off_shade[0];
+	key.off_cls = pl.off_cls;
+	key.off_sums = pl.off_sums;
+	key.off_girow = pl.off_girow;
+	key.total = pl.total;
+	return true;
+}
+
 hipError_t skr_launch_resolve(const RenderParams &p, hipStream_t stream)
 {
 	const size_t n = (size_t) p.width * p.out_rows;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM traffic of one frame over ALL its kernels from two separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of
-`bench.py [--config C] --steps 2 --warmup 1 --no-cpu-baseline`, written with the git blob hashes of the kernel sources it was
+`bench.py [--config C] --steps 2 --warmup 1 --no-cpu-baseline` (or the frames PMC_STEPS names, as in tools/pmc_pass.sh), written with the git blob hashes of the kernel sources it was
 measured on (bench.py reports it only while those hashes match).  Every dispatch of every skr_ kernel is summed and divided by the
 frames that command asked the device for — bench.py counts them (config.frames_enqueued in its JSON line, found in the passes' logs: warm-up,
 timed frames, the other frame step's side pass, the kernel-timing pass, a mesh's counting frame) —, so configurations whose frame takes several
@@ -42,7 +42,7 @@ for k, cs in sorted(acc.items()):
     per_kernel[k.replace("void ", "").replace("(RenderParams)", "")] = {"fetch_kib": fetch, "write_kib": write, "bytes": b, "launches_per_frame": len(launches[(k, "FETCH_SIZE")]) / FRAMES}
     total += b
 json.dump({"variant": variant, "config": config,
-           "command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --output-format csv -- python3 bench.py --config %d --steps 2 --warmup 1 --no-cpu-baseline (separate passes: tools/pmc_pass.sh); per frame = all dispatches / %d frames" % (config, FRAMES),
+           "command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --output-format csv -- python3 bench.py --config %d %s --no-cpu-baseline (separate passes: tools/pmc_pass.sh); per frame = all dispatches / %d frames" % (config, os.environ.get("PMC_STEPS", "--steps 2 --warmup 1"), FRAMES),
            "correction": "MI355X_MICROARCH.md HBM: FETCH_SIZE doubled (gfx950 reports half of a coalesced read stream), WRITE_SIZE as is; KiB -> bytes",
            "per_kernel": per_kernel, "traffic_bytes_per_frame": total, "sources": bench.source_hashes()}, open(out, "w"), indent=1)
 print(json.dumps(per_kernel, indent=1)); print("total MB per frame: %.1f" % (total / 1e6))

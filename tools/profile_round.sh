@@ -9,6 +9,8 @@ export BENCH_ARGS="--config $CFG"
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 STEPS=$([ "$CFG" = 5 ] && echo "--steps 2 --warmup 1" || echo "--steps 20 --warmup 3")
+# the headline's frames are not all alike (the first frame of each renderer builds the level-0 stage): its PMC passes take the traces' frames
+[ "$CFG" = 3 ] && export PMC_STEPS="${PMC_STEPS:-$STEPS}"
 # two kernel traces: the serial frame step (--sync-frames: one frame at a time, every kernel alone on the device — the durations bench.py's
 # roofline.kernel_ms must agree with) and the default, pipelined one (two frames in flight: kernels of consecutive frames overlap and stretch each other)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py $BENCH_ARGS $STEPS --no-cpu-baseline --sync-frames --no-side-pass > $OUT/trace.log 2>&1
