@@ -30,6 +30,7 @@ extern "C" {
 #define SKR_HAS_SHADE_RAYS 1
 #define SKR_HAS_DENOISE 1    /* skr_denoise, skr_render_denoised_host: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ADAPTIVE 1   /* skr_adaptive, skr_render_adaptive(_host): an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
 	SKR_OK = 0,
@@ -64,7 +65,8 @@ typedef struct {
 	                           * strictly below the closest sphere's (equal t: lower index in the file); the hit is shaded as a
 	                           * sphere is (blinn_phong.h, raytrace.h:107-136,208-218) with the material in force on its
 	                           * `triangle` line and the geometric normal normalize(cross(v1-v0, v2-v0)) turned against the ray;
-	                           * shadow rays still test spheres only (utils.h:42-76); the child rays of a triangle hit start at
+	                           * shadow rays test spheres only (utils.h:42-76) unless the scene has triangle shadows switched on
+	                           * (skr_scene_set_triangle_shadows, below); the child rays of a triangle hit start at
 	                           * P + 1e-5 like a sphere's (raytrace.h:128).  No counterpart in the reference, so no reference output
 	                           * pins it (tests/test_shade_triangles.py).  Any --depth, with or without --gillum (the general level pipeline). */
 	int32_t progressive_passes; /* new, default 1 (`raytracer --progressive K`, SURVEY.md 8f-4: what the SDL viewer of main.cpp:183-197 is
@@ -116,6 +118,9 @@ int skr_scene_create_from_scn(const char *path, int echo, skr_scene **out);
  * skr_options.legacy_reflect or shade_triangles (SKR_ERR_UNSUPPORTED). */
 #define SKR_SCN_FOG 2u
 #define SKR_FOG_MAX_VOLUMES 64
+/* SKR_SCN_TRIANGLE_SHADOWS (`raytracer --triangle-shadows`; combines with the other two): the scene is created with triangle shadows
+ * switched on (skr_scene_set_triangle_shadows below states the rule). */
+#define SKR_SCN_TRIANGLE_SHADOWS 4u
 int skr_scene_create_from_scn_ex(const char *path, int echo, uint32_t flags, skr_scene **out);
 /* Build a scene from arrays (synthetic tests): spheres[n][14] = centre(3) radius
  * ambient(3) diffuse(3) specular(3) power; triangles[n][9] = v0 v1 v2;
@@ -128,6 +133,31 @@ int skr_scene_create_from_arrays(const float *spheres, int32_t n_spheres, const 
  * from arrays, and tests that choose scattering and absorption; a renderer takes the volumes the scene has when it is created. */
 int skr_scene_get_fog(const skr_scene *scene, float *rows, int32_t *n);
 int skr_scene_set_fog(skr_scene *scene, const float *rows, int32_t n);
+/* Triangle shadows (new, off by default; no counterpart in the reference, whose shadow rays test spheres only and whose triangles are
+ * no surfaces).  A switch of the scene; a renderer takes the scene's setting when it is created, as it takes the fog volumes (its
+ * clones and the multi-GPU frame steps with it).  The rule (normative):
+ *   - In force for a launch iff the renderer's scene has the switch on AND the launch's effective shade_triangles is 1 (the option is
+ *     set and the scene has triangles) AND use_shadows is set.  Otherwise the launch is what it is without the switch, bit for bit, with
+ *     the same kernels, skr_kernel_variant() and counters: without shade_triangles a triangle is a black hole, not a surface, and the
+ *     switch is a no-op.
+ *   - When in force, at every shaded hit (sphere or triangle surface; the hits of --gillum and legacy_reflect child rays are shaded
+ *     hits like any other) and for every light, in the reference's light order:
+ *     1. the sphere test runs first, exactly as without the switch (utils.h:42-76: origin o = P + 1e-6 added to every component,
+ *        direction L; the same shadow-ray and sphere-test counts).  If a sphere occludes, the light is dark and no triangle is looked at;
+ *     2. otherwise the triangles are tested with the same o and the same L (the bits the sphere test used).  Triangle i (file index)
+ *        occludes iff utils.h:181-213 accepts (o, L, triangle i) with distance t AND t > 0 AND i is not the file index of the triangle
+ *        being shaded (none at a sphere hit) AND, for a point light, t < dist with dist = sqrtf(to_l . to_l), to_l = Lp - P, the
+ *        correctly rounded binary32 value blinn_phong.h calls `distance`.  A directional light has no upper bound.  The outcome is
+ *        binary and does not depend on the order in which triangles are tried; the occluder is the accept region of the reference's
+ *        test (its mirrored triangle), the same surface that is rendered;
+ *     3. an occluded light adds neither its diffuse nor its specular term (as for a sphere occluder).  Nothing else changes: ambient,
+ *        the child rays, node ids and RNG draws are as they are.  Fog cannot be combined with shade_triangles and stays excluded.
+ *   - Counters: skr_renderer_read_counters / read_work advance exactly as without the switch (one shadow ray per light per hit; sphere
+ *     tests as the reference's loop runs them).  While skr_renderer_count_triangle_work is on, the culling-sphere and triangle tests the
+ *     shadow walk executes are added to out[0] / out[1] of skr_renderer_read_triangle_work; its out[2] (the reference's own loop) is
+ *     not advanced by shadow rays: the reference has no such loop. */
+int skr_scene_set_triangle_shadows(skr_scene *scene, int enable);
+int skr_scene_get_triangle_shadows(const skr_scene *scene, int *enabled);
 void skr_scene_destroy(skr_scene *scene);
 int skr_scene_get_info(const skr_scene *scene, skr_scene_info *info);
 /* Copy the parsed arrays back out in the skr_scene_create_from_arrays layouts
@@ -144,6 +174,10 @@ int skr_scene_get_arrays(const skr_scene *scene, float *spheres, float *triangle
  * tests. */
 int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks,
 						  float *device_tris, float *node_spheres, int32_t *node_links, float *chunk_spheres);
+/* The same arrays for the trace tree: the tree the ray queries and the triangle-shadow walk run on, built for rays that start anywhere
+ * in ball = {centre, radius} (device_tris and the counts are those of skr_scene_get_culling).  Used by the host-logic tests. */
+int skr_scene_get_trace_culling(const skr_scene *scene, int32_t level, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks,
+								float *device_tris, float *node_spheres, int32_t *node_links, float *chunk_spheres, float ball[4]);
 /* The shadow masks the level pipelines' shadow walk runs on (DESIGN.md "Shadow masks"), as uploaded: per point light a cube map of
  * 6 x cells x cells uint32_t, masks[light][face][i][j], face = 2 axis + (negative), bit k = sphere k may stop a shadow ray of that light
  * whose direction from the shading point towards the light falls in the cell; they hold for shading points P with
@@ -372,7 +406,7 @@ int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, sk
  * d_rgbf: DEVICE float[n][3], the unquantised value shade() returns for each ray (what a 1-spp frame's float output holds).
  * d_keys: DEVICE uint32_t[n] or NULL (= ray index): the counter RNG's pixel word for each ray; `sample` is its AA word.
  *   - Shading rule: the renderer's own, for opt's monte_carlo, num_path_traces, max_depth, use_shadows, seed, shade_triangles and
- *     legacy_reflect, and for the scene's fog volumes.  The result does not depend on width, height, fov, grid_size or
+ *     legacy_reflect, and for the scene's fog volumes and triangle-shadow switch as the renderer took them.  The result does not depend on width, height, fov, grid_size or
  *     progressive_passes.
  *   - Specular view: as everywhere in the renderer (blinn_phong.h), the view vector of the specular term points to the SCENE CAMERA,
  *     not to the ray's origin.

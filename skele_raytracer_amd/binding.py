@@ -8,8 +8,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_destroy", "skr_scene_get_info",
-    "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
     "skr_kernel_variant", "skr_debug_eval",
@@ -82,11 +82,14 @@ def lib():
     L.skr_scene_set_sphere_ior.argtypes = [vp, vp]
     L.skr_scene_get_fog.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_scene_set_fog.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
+    L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
     L.skr_scene_destroy.argtypes = [vp]
     L.skr_scene_destroy.restype = None
     L.skr_scene_get_info.argtypes = [vp, C.POINTER(CSceneInfo)]
     L.skr_scene_get_arrays.argtypes = [vp, vp, vp, vp]
     L.skr_scene_get_culling.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp]
+    L.skr_scene_get_trace_culling.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp, vp]
     L.skr_scene_get_shadow_masks.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), vp]
     L.skr_scene_get_gi_masks.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
     L.skr_options_default.argtypes = [C.POINTER(COptions)]
@@ -259,6 +262,20 @@ class Scene:
                "skr_scene_get_culling")
         return cs.value, tris, sph, links, ch
 
+    def trace_culling(self, level=0):
+        """culling() for the trace tree (the ray queries' and the triangle-shadow walk's), plus its ball (centre, radius) float32 [4] —
+        include/skr.h skr_scene_get_trace_culling."""
+        cs, nn, nc = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().skr_scene_get_trace_culling(self.h, level, C.byref(cs), C.byref(nn), C.byref(nc), None, None, None, None, None), "skr_scene_get_trace_culling")
+        tris = np.zeros((self.info.n_triangles, 3, 4), np.float32)
+        sph = np.zeros((nn.value, 8), np.float32)
+        links = np.zeros((nn.value, 4), np.int32)
+        ch = np.zeros((nc.value, 8), np.float32)
+        ball = np.zeros(4, np.float32)
+        _check(lib().skr_scene_get_trace_culling(self.h, level, None, None, None, tris.ctypes.data, sph.ctypes.data, links.ctypes.data, ch.ctypes.data,
+                                                 ball.ctypes.data), "skr_scene_get_trace_culling")
+        return cs.value, tris, sph, links, ch, ball
+
     def shadow_masks(self):
         """(masks [n_lights, 6, cells, cells] uint32, reach2) — include/skr.h skr_scene_get_shadow_masks; n_lights = 0: the scene has none."""
         nl, cells, reach2 = C.c_int32(), C.c_int32(), C.c_float()
@@ -290,8 +307,21 @@ class Scene:
         r = np.ascontiguousarray(rows, np.float32).reshape(-1, 9)
         _check(lib().skr_scene_set_fog(self.h, r.ctypes.data, len(r)), "skr_scene_set_fog")
 
+    @property
+    def triangle_shadows(self):
+        """The scene's triangle-shadow switch (include/skr.h skr_scene_set_triangle_shadows)."""
+        on = C.c_int()
+        _check(lib().skr_scene_get_triangle_shadows(self.h, C.byref(on)), "skr_scene_get_triangle_shadows")
+        return bool(on.value)
+
+    def set_triangle_shadows(self, enable):
+        """Triangles cast shadows in frames with shade_triangles and shadow (include/skr.h states the rule).  A renderer takes the
+        setting the scene has when it is made."""
+        _check(lib().skr_scene_set_triangle_shadows(self.h, int(bool(enable))), "skr_scene_set_triangle_shadows")
+
     @staticmethod
-    def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None):
+    def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
+                    triangle_shadows=False):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -309,18 +339,21 @@ class Scene:
         if sphere_ior is not None:  # [n_spheres] (--legacy-reflect)
             q = np.ascontiguousarray(sphere_ior, np.float32).reshape(len(s))
             _check(lib().skr_scene_set_sphere_ior(sc.h, q.ctypes.data), "skr_scene_set_sphere_ior")
+        if triangle_shadows:
+            sc.set_triangle_shadows(True)
         return sc
 
 
-SCN_STRICT, SCN_FOG = 1, 2  # include/skr.h SKR_SCN_*
+SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS = 1, 2, 4  # include/skr.h SKR_SCN_*
 FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
 
 
-def parse_scene(path, echo=False, strict=False, fog=False):
+def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False):
     """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept),
-    fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded)."""
+    fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded), triangle_shadows = SKR_SCN_TRIANGLE_SHADOWS
+    (--triangle-shadows: triangles cast shadows in frames with shade_triangles and shadow)."""
     h = C.c_void_p()
-    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0)
+    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0)
     _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), flags, C.byref(h)), "skr_scene_create_from_scn_ex")
     return Scene(h.value)
 

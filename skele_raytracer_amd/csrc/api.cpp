@@ -54,6 +54,7 @@ struct DeviceScene {
 	size_t off_trace = 0;     // the ray queries' tree (skr_scene::trace_chunks, SKR_CULL_LEVELS sets of chunk_stride rows), 0 = none
 	float4 trace_ball{};
 	int trace_cones = 0;
+	bool tri_shadows = false; // the scene's triangle-shadow switch when the renderer was made (include/skr.h skr_scene_set_triangle_shadows)
 
 	DeviceScene() = default;
 	DeviceScene(const DeviceScene &) = delete;
@@ -203,6 +204,7 @@ static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 	if(s.info.n_triangles && !s.trace_chunks.empty()) d.off_trace = put4(s.trace_chunks);
 	d.trace_ball = make_float4(s.trace_ball[0], s.trace_ball[1], s.trace_ball[2], s.trace_ball[3]);
 	d.trace_cones = s.trace_any_cone ? 1 : 0;
+	d.tri_shadows = s.triangle_shadows;
 	rows.resize(rows.size() + 16, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
 	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
 		float top = 1.0f;
@@ -537,6 +539,26 @@ static int check_plan(const skr_renderer *r, const RenderParams &p, bool fits, s
 	return SKR_OK;
 }
 
+// the trees a query may walk under the renderer's switches (launch.h QueryTrees)
+static QueryTrees query_trees(const skr_renderer *r)
+{
+	const DeviceScene &s = *r->scene;
+	QueryTrees q{};
+	q.tree = s.d_blob + s.off_chunks;
+	q.trace = s.off_trace ? s.d_blob + s.off_trace : nullptr;
+	q.stride = (uint32_t) s.chunk_stride;
+	q.nchunks = r->sw.no_cull ? 0 : s.n_chunks;
+	q.cones = (s.cones && !r->sw.no_cones) ? 1 : 0;
+	q.trace_cones = (s.trace_cones && !r->sw.no_cones) ? 1 : 0;
+	q.ball = s.trace_ball;
+	return q;
+}
+
+// Triangle shadows are in force for a launch iff the renderer's scene has them switched on, the launch shades triangles (the option is
+// set and the scene has some) and casts shadow rays (include/skr.h skr_scene_set_triangle_shadows).  Otherwise the launch is the one it
+// was without the switch: the same kernels, the same skr_kernel_variant().
+static bool tri_shadows_in_force(const skr_renderer *r, const RenderParams &p) { return r->scene->tri_shadows && p.shade_triangles && p.use_shadows; }
+
 // one pass of the tiles `ts` selects (render_impl has checked the arguments and set the device)
 static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
 {
@@ -588,6 +610,12 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	}
 	r->last_off_ctr = lp.off_ctr;
 	r->last_levels = lp.levels;
+	if(lp.path == SKR_PATH_GENERIC && tri_shadows_in_force(r, p))
+	{ // (shade_triangles: the general level pipeline)
+		lp.tri_shadows = true;
+		lp.shadows.trees = query_trees(r);
+		lp.variant = "level_pipeline_g1_tshadow";
+	}
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
 	if(r->timing) r->timed.push_back(hook);
@@ -953,21 +981,6 @@ int skr_render_frame_host(skr_renderer *r, const skr_options *opt, uint8_t *h_rg
 const char *skr_kernel_variant(void) { return g_variant; }
 
 // ---- ray queries (trace_rays.hip): they read the scene blob and write only the caller's arrays ----
-// the trees a query may walk under the renderer's switches (launch.h QueryTrees)
-static QueryTrees query_trees(const skr_renderer *r)
-{
-	const DeviceScene &s = *r->scene;
-	QueryTrees q{};
-	q.tree = s.d_blob + s.off_chunks;
-	q.trace = s.off_trace ? s.d_blob + s.off_trace : nullptr;
-	q.stride = (uint32_t) s.chunk_stride;
-	q.nchunks = r->sw.no_cull ? 0 : s.n_chunks;
-	q.cones = (s.cones && !r->sw.no_cones) ? 1 : 0;
-	q.trace_cones = (s.trace_cones && !r->sw.no_cones) ? 1 : 0;
-	q.ball = s.trace_ball;
-	return q;
-}
-
 int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t flags, void *d_out, void *stream)
 {
 	const bool any_hit = (flags & SKR_TRACE_ANY_HIT) != 0;
@@ -1045,8 +1058,11 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	q.n = n;
 	q.trees = query_trees(r);
 	r->last_levels = 0; // (the scratch no longer holds the node pipeline's tables of the last render)
-	g_variant = "shade_rays_g1";
-	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q));
+	TriShadows tsh{};
+	const bool tri_shadows = tri_shadows_in_force(r, p);
+	if(tri_shadows) tsh.trees = q.trees;
+	g_variant = tri_shadows ? "shade_rays_g1_tshadow" : "shade_rays_g1";
+	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr));
 	return SKR_OK;
 }
 

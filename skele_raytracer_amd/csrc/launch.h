@@ -69,6 +69,13 @@ struct ShadeRays {
 // the rays of one row of a shading query's plan
 constexpr uint32_t SKR_SHADE_ROW = 1024;
 
+// Triangle shadows (include/skr.h skr_scene_set_triangle_shadows): what the shadow walk of the activate kernel reads,
+// handed to the instances that have the walk in an argument of their own, behind a query's ShadeRays (render_generic.hip) — RenderParams,
+// and with it the code of every kernel that takes it, stays as it was.
+struct TriShadows {
+	QueryTrees trees; // the walk runs on the trace tree's first set (|L| = 1) for a wave whose shadow rays all start in the ball
+};
+
 enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
 
 // Everything render_pass (api.cpp) sizes and checks and the launchers follow, computed once per launch.
@@ -82,6 +89,8 @@ struct LaunchPlan {
 	int levels = 0;                    // ... and how many node / record levels it counts (0 on the other paths)
 	NodePlan nodes;                    // (path == SKR_PATH_NODES)
 	GPlan generic;                     // (path == SKR_PATH_GENERIC)
+	bool tri_shadows = false;          // triangle shadows are in force for this launch (api.cpp render_pass sets it and `shadows`; the plan itself says no)
+	TriShadows shadows{};
 };
 
 // the scene SoA every kernel stages into LDS (wave_common.h stage_scene): 4 rows per sphere, a zero row, 2 rows per light
@@ -133,7 +142,9 @@ hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level,
 // render_generic.hip
 bool skr_generic_plan(const RenderParams &p, GPlan &pl); // false: not one band fits the budget
 // q: a shading query (p.width = SKR_SHADE_ROW, p.out_rows its rows, p.aa_index its sample); null: a frame
-hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q = nullptr);
+// ts: triangle shadows are in force (the activate kernel's instances with the shadow walk); null: they are not
+hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q = nullptr,
+							  const TriShadows *ts = nullptr);
 // render_wave.hip
 // Every value the level-0 stage of a node-pipeline launch depends on, and where it is kept: what skr_primary_kernel and plan_for
 // (render_nodes.hip) read.  A frame replays the stage only if its key equals, byte for byte, the key the scratch was last built under

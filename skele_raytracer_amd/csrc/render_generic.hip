@@ -37,6 +37,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "launch.h"
 #include "wave_common.h"
@@ -139,6 +140,13 @@ SKR_DEV GChild child_of(const SceneView &sv, const RenderParams &p, const GNode 
 // the query of an instance with a ShadeRays argument (the frame instances never call it)
 SKR_DEV ShadeRays query_of(const ShadeRays &q) { return q; }
 SKR_DEV ShadeRays query_of() { return ShadeRays{}; }
+// the activate kernel's pack: [ShadeRays] [TriShadows]
+SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &) { return q; }
+SKR_DEV ShadeRays query_of(const TriShadows &) { return ShadeRays{}; }
+SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts) { return ts; }
+SKR_DEV TriShadows shadows_of(const TriShadows &ts) { return ts; }
+template <typename T, typename... Q>
+constexpr bool pack_has = (std::is_same<T, Q>::value || ...);
 
 // The tree a wave of query rays walks (wave_common.h pick_query_tree): at level 1 the renderer's tree where every lane
 // starts at the scene camera, else the trace tree where every lane starts in its ball; at a level below (origins on surfaces) the
@@ -147,6 +155,67 @@ SKR_DEV void query_tree(SceneView &sv, const RenderParams &p, const ShadeRays &q
 {
 	pick_query_tree(sv, q.trees, p.cam_pos, p.g_level != 1, live, o, d);
 }
+
+// Triangle shadows (include/skr.h skr_scene_set_triangle_shadows), what direct_light_of calls behind the sphere test of a
+// pair of lights: a light the spheres left lit is dark if a triangle other than the lane's own accepts the shadow ray (the sphere test's
+// o = P + 1e-6 and L) at 0 < t, for a point light also t < |Lp - P|.  The tree is the trace tree — shadow rays start on spheres AND
+// on triangles, an origin class the renderer's tree is not built for — where every lane that still has a ray to test starts inside its
+// ball (pick_query_tree's rule (b); |L| = 1: the first set); otherwise every triangle.
+#ifndef SKR_SHADOW_PAIR_WALK
+#define SKR_SHADOW_PAIR_WALK 1 // 1: one walk tests both rays of a pair of lights against every entry it loads; 0: one walk per light (DESIGN.md 8.9 has both times)
+#endif
+struct TriangleShadows {
+	static constexpr bool on = true;
+	const SceneView &sv;
+	const QueryTrees &trees;
+	int own; // file index of the triangle being shaded, -1 at a sphere hit
+
+	__device__ __forceinline__ float reach(int l, f3 P) const
+	{ // blinn_phong.h's `distance` = length(Lp - P); a directional light has no far end
+		const float4 lp4 = sv.lights[2 * l];
+		return lp4.w != 0.0f ? __builtin_inff() : length3(ld3(lp4) - P);
+	}
+	template <int NR>
+	__device__ __forceinline__ void walk(ShadowRays<NR> &s) const
+	{ // (every lane of the wave that shades a hit arrives here: the choice of the tree and the walk are wave-wide)
+		bool live = false, fits = true;
+		constexpr float lim = (float) (4.0 * 4.0 * 0.998); // pick_query_tree's first bound
+#pragma unroll
+		for(int k = 0; k < NR; k++)
+		{
+			live = live || s.live[k];
+			fits = fits && dot3(s.d[k], s.d[k]) < lim; // (NaN: no tree)
+		}
+		if(!__any(live)) return;
+		const f3 e = s.o - mk3(trees.ball.x, trees.ball.y, trees.ball.z);
+		SceneView w = sv;
+		w.nchunks = 0;
+		if(trees.trace && trees.nchunks > 0 && __all(!live || (fits && dot3(e, e) <= trees.ball.w * trees.ball.w)))
+		{
+			w.chunks = trees.trace;
+			w.cones = trees.trace_cones;
+			w.nchunks = trees.nchunks;
+		}
+		shadow_triangles<NR>(w, s);
+	}
+	__device__ __forceinline__ void operator()(f3 P, int i, bool second, f3 L0, f3 L1, bool &occ0, bool &occ1) const
+	{
+		const f3 o = add_scalar(P, 0.000001f);
+		const float far0 = reach(i, P), far1 = reach(second ? i + 1 : i, P);
+#if SKR_SHADOW_PAIR_WALK
+		ShadowRays<2> s{o, {L0, L1}, {far0, far1}, {!occ0, second && !occ1}, own};
+		walk(s);
+		occ0 = !s.live[0];
+		if(second) occ1 = !s.live[1];
+#else
+		ShadowRays<1> s0{o, {L0}, {far0}, {!occ0}, own}, s1{o, {L1}, {far1}, {second && !occ1}, own};
+		walk(s0);
+		walk(s1);
+		occ0 = !s0.live[0];
+		if(second) occ1 = !s1.live[0];
+#endif
+	}
+};
 
 } // namespace
 
@@ -307,10 +376,11 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 } // namespace
 
 // FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
+// Q: [ShadeRays: a shading query] [TriShadows: triangle shadows are in force — the instances with the shadow walk]
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
-	constexpr bool RAYS = sizeof...(Q) > 0;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>;
 	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -378,6 +448,11 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		else n.N = normalize3(n.P - ld3(sv.geom[surf])); // :205
 		cn.hits++;
 		if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn);
+		else if constexpr(TSHADOW)
+		{
+			const TriShadows ts = shadows_of(qs...);
+			n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, TriangleShadows{sv, ts.trees, n.file});
+		}
 		else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn);
 		n.fr = (p.legacy_reflect && !(surf & SURF_TRI)) ? legacy_fresnel(n.d, n.N, ks4.w) : 0.0f; // :46
 		if(p.g_last)
@@ -489,8 +564,9 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl)
 	return rows > 0 && gplan_for(p, rows, pl);
 }
 
-hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q_in)
+hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q_in, const TriShadows *ts_in)
 {
+	if(ts_in && p_in.n_fog > 0) return hipErrorInvalidValue; // (triangle shadows need shade_triangles, which fog excludes: api.cpp launch_params)
 	RenderParams p = p_in;
 	char *base = reinterpret_cast<char *>(p.node_scratch);
 	uint32_t *ctr0 = reinterpret_cast<uint32_t *>(base + pl.off_ctr);
@@ -540,7 +616,9 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.g_nodes_dst = L < D ? reinterpret_cast<float4 *>(base + pl.off_nodes[L]) : nullptr;
 				p.res_out = reinterpret_cast<float *>(base + pl.off_res[L]);
 				const unsigned grid_a = SKR_P1_REGIONS * ((pl.cap[L] + 255u) / 256u);
-				if(q_in && p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
+				if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in);
+				else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in);
+				else if(q_in && p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
 				else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
 				else if(p.n_fog > 0) hipLaunchKernelGGL(skr_gactivate_kernel<true>, dim3(grid_a), dim3(256), lds, stream, p);
 				else hipLaunchKernelGGL(skr_gactivate_kernel<false>, dim3(grid_a), dim3(256), lds, stream, p);

@@ -74,7 +74,7 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp)
 
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)
 {
-	if(lp.path == SKR_PATH_GENERIC) return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook) : hipErrorInvalidValue;
+	if(lp.path == SKR_PATH_GENERIC) return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook, nullptr, lp.tri_shadows ? &lp.shadows : nullptr) : hipErrorInvalidValue;
 	if(lp.path == SKR_PATH_NODES) return p.node_scratch ? skr_launch_nodes(p, lp.nodes, stream, hook) : hipErrorInvalidValue;
 	if(p.n_spheres >= 65536) return hipErrorInvalidValue; // (one launch, no tree: any scene the LDS holds)
 	skr_hook_start(hook, stream);

@@ -1163,6 +1163,7 @@ int skr_scene_create_from_scn_ex(const char *path, int echo, uint32_t flags, skr
 		*out = nullptr;
 		return rc;
 	}
+	sc->triangle_shadows = (flags & SKR_SCN_TRIANGLE_SHADOWS) != 0;
 	*out = sc;
 	return SKR_OK;
 }
@@ -1238,6 +1239,24 @@ int skr_scene_get_fog(const skr_scene *scene, float *rows, int32_t *n)
 	return SKR_OK;
 }
 
+int skr_scene_set_triangle_shadows(skr_scene *scene, int enable)
+{
+	if(!scene)
+	{
+		skr_set_error("skr_scene_set_triangle_shadows: null scene");
+		return SKR_ERR_ARG;
+	}
+	scene->triangle_shadows = enable != 0;
+	return SKR_OK;
+}
+
+int skr_scene_get_triangle_shadows(const skr_scene *scene, int *enabled)
+{
+	if(!scene || !enabled) return SKR_ERR_ARG;
+	*enabled = scene->triangle_shadows ? 1 : 0;
+	return SKR_OK;
+}
+
 void skr_scene_destroy(skr_scene *scene) { delete scene; }
 
 int skr_scene_get_info(const skr_scene *scene, skr_scene_info *info)
@@ -1256,8 +1275,9 @@ int skr_scene_get_arrays(const skr_scene *scene, float *spheres, float *triangle
 	return SKR_OK;
 }
 
-int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks,
-						  float *device_tris, float *node_spheres, int32_t *node_links, float *chunk_spheres)
+// one set of a tree (`sets`: the renderer's tri_chunks or the ray queries' trace_chunks) in the layout of skr_scene_get_culling
+static int get_culling_set(const skr_scene *scene, const std::vector<skr_f4> &sets, int32_t level, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks,
+						   float *device_tris, float *node_spheres, int32_t *node_links, float *chunk_spheres)
 {
 	if(!scene || level < 0 || level >= SKR_CULL_LEVELS) return SKR_ERR_ARG;
 	const int nt = scene->info.n_triangles, nn = nt ? scene->tri_node_count : 0, cs = scene->tri_chunk_size;
@@ -1266,7 +1286,7 @@ int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_
 	if(n_nodes) *n_nodes = nn;
 	if(n_chunks) *n_chunks = nc;
 	if(device_tris && nt) memcpy(device_tris, scene->tris.data(), (size_t) nt * 48);
-	const skr_f4 *base = scene->tri_chunks.data() + (size_t) level * scene->tri_chunk_stride;
+	const skr_f4 *base = sets.data() + (size_t) level * scene->tri_chunk_stride;
 	for(int i = 0; i < nn; i++)
 	{
 		if(node_spheres) memcpy(node_spheres + 8 * (size_t) i, base + 3 * (size_t) i, 32);
@@ -1274,6 +1294,19 @@ int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_
 	}
 	if(chunk_spheres && nc) memcpy(chunk_spheres, base + 3 * ((size_t) nn + 1), (size_t) nc * 32);
 	return SKR_OK;
+}
+
+int skr_scene_get_culling(const skr_scene *scene, int32_t level, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks,
+						  float *device_tris, float *node_spheres, int32_t *node_links, float *chunk_spheres)
+{
+	return get_culling_set(scene, scene ? scene->tri_chunks : std::vector<skr_f4>(), level, chunk_size, n_nodes, n_chunks, device_tris, node_spheres, node_links, chunk_spheres);
+}
+
+int skr_scene_get_trace_culling(const skr_scene *scene, int32_t level, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks,
+								float *device_tris, float *node_spheres, int32_t *node_links, float *chunk_spheres, float ball[4])
+{
+	if(scene && ball) memcpy(ball, scene->trace_ball, 16);
+	return get_culling_set(scene, scene ? scene->trace_chunks : std::vector<skr_f4>(), level, chunk_size, n_nodes, n_chunks, device_tris, node_spheres, node_links, chunk_spheres);
 }
 
 int skr_scene_get_shadow_masks(const skr_scene *scene, int32_t *n_lights, int32_t *cells, float *reach2, uint32_t *masks)

@@ -28,6 +28,7 @@ struct skr_scene {
 	std::vector<float> raw_directional_lights; // [n][6] direction colour — --strict-scn only (scene.cpp:139-163 drops them)
 	std::vector<float> raw_fog;          // [n][9] centre radius albedo scattering absorption — SKR_SCN_FOG / skr_scene_set_fog only (file order)
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
+	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
 	skr_scene_info info{};
 
 	// SoA arrays as uploaded (built by finalize())

@@ -501,11 +501,19 @@ SKR_DEV LightTerm light_term(const SceneView &sv, int i, f3 P)
 	return t;
 }
 
+// what direct_light_of does about triangles in the way of a light where triangle shadows are not in force: nothing, and no code
+struct NoTriangleShadows {
+	static constexpr bool on = false;
+};
+
 // raytrace.h:36-44 = bp::ambient (blinn_phong.h:13) + diffuse (:47) + specular (:90).
 // The reference casts the same shadow ray in diffuse and again in specular; one cast serves both.
 // (kd, ks, ambp = {La * ka, power}: the material rows of the surface hit)
-template <bool COHERENT>
-SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn)
+// TS: triangle shadows (include/skr.h skr_scene_set_triangle_shadows) — `tri_shadows(P, i, second, L0, L1, occ0, occ1)` darkens the lights of a
+// pair that the spheres left lit and a triangle occludes (render_generic.hip TriangleShadows); chosen at compile time, so that the
+// instances without it keep their code.
+template <bool COHERENT, typename TS = NoTriangleShadows>
+SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn, const TS &tri_shadows = TS())
 {
 	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
 	const f3 view = normalize3(p.cam_pos - P); // always the camera (blinn_phong.h:93)
@@ -519,6 +527,7 @@ SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3
 		{
 			cn.shadow_rays += second ? 2u : 1u;
 			occluded_pair<COHERENT>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
+			if constexpr(TS::on) tri_shadows(P, i, second, t0.L, t1.L, occ0, occ1);
 		}
 		auto add_light = [&](const LightTerm &t, bool lit)
 		{
@@ -741,6 +750,144 @@ SKR_DEV void closest_triangle(const SceneView &sv, const RayConst &r, int from_t
 		return;
 	}
 	for(int k = 0; k < sv.nt; k++) tri_consider(r, true, ld3(mesh_row(sv.tris, 3 * k)), mesh_row(sv.tris, 3 * k + 1), mesh_row(sv.tris, 3 * k + 2), k, from_tri, b);
+}
+
+// ---- triangle shadows (include/skr.h skr_scene_set_triangle_shadows): does a triangle stand between a hit and a light ----
+// The NR shadow rays of one lane (the lights of a pair): they start at the same o = P + 1e-6, the origin the sphere test used.
+template <int NR>
+struct ShadowRays {
+	f3 o;
+	f3 d[NR];       // L, the bits the sphere test used
+	float tmax[NR]; // |Lp - P| for a point light, +inf for a directional one
+	bool live[NR];  // the light is not yet known to be dark: the ray is still tested (false on return: a triangle occludes it, or it was dark before)
+	int own;        // file index of the triangle being shaded (it casts no shadow on itself), -1 at a sphere hit
+};
+
+// the rule for one (ray, triangle): utils.h:181-213 accepts, 0 < t < tmax, not the lane's own triangle (NaN t: no occluder)
+SKR_DEV bool shadow_triangle_hit(f3 o, f3 d, f3 v0, f3 e1, f3 e2, int file, int own, float tmax)
+{
+	float t;
+	return triangle_hit(o, d, v0, e1, e2, t) && t > 0.0f && t < tmax && file != own;
+}
+
+// tree_walk() for shadow rays: one wave-uniform index over the tree `sv.chunks`, every entry that is loaded is tested against all NR
+// rays of the lane (the walk is bound by its scalar loads, which the rays of a pair share).  A ray leaves at its first occluder, the
+// wave when no ray of any lane is live.  The line test only: the tree proves nothing about the segment between o and the light.
+template <int NR, bool CONES, bool COUNT>
+SKR_DEV void tree_walk_shadow(const SceneView &sv, ShadowRays<NR> &s)
+{
+	RayConst r[NR];
+	float dd[NR];
+#pragma unroll
+	for(int k = 0; k < NR; k++)
+	{
+		r[k] = make_ray(s.o, s.d[k]);
+		dd[k] = dot3(s.d[k], s.d[k]);
+	}
+	int i = 0;
+	uint32_t n_cull = 0, n_tri = 0; // (wave-uniform: scalar registers)
+	const float4 *chunk_ent = sv.chunks + 3 * (sv.nchunks + 1); // behind the nodes and their pad
+	float4 A = mesh_row(sv.chunks, 0), B = mesh_row(sv.chunks, 1), lk = mesh_row(sv.chunks, 2);
+	while(i < sv.nchunks)
+	{
+		const int i_out = __float_as_int(lk.x);
+		const float4 A_in = mesh_row(sv.chunks, 3 * i + 3), B_in = mesh_row(sv.chunks, 3 * i + 4), lk_in = mesh_row(sv.chunks, 3 * i + 5);
+		const float4 A_out = mesh_row(sv.chunks, 3 * i_out), B_out = mesh_row(sv.chunks, 3 * i_out + 1), lk_out = mesh_row(sv.chunks, 3 * i_out + 2);
+		bool touch = false;
+#pragma unroll
+		for(int k = 0; k < NR; k++)
+		{
+			if(COUNT) n_cull += (uint32_t) __popcll(__ballot(s.live[k]));
+			touch = touch || (s.live[k] && line_touches<CONES>(r[k], dd[k], A, B));
+		}
+		const bool enter = __any(touch);
+		const int count = __float_as_int(lk.z);
+		if(enter && count > 0)
+		{ // height 1: its chunk entries are contiguous
+			const int c0 = __float_as_int(lk.y), c1 = c0 + count;
+			float4 cA_next = mesh_row(chunk_ent, 2 * c0), cB_next = mesh_row(chunk_ent, 2 * c0 + 1);
+			for(int c = c0; c < c1; c++)
+			{
+				const float4 cA = cA_next, cB = cB_next;
+				cA_next = mesh_row(chunk_ent, 2 * c + 2);
+				cB_next = mesh_row(chunk_ent, 2 * c + 3);
+				bool mine[NR], some = false;
+#pragma unroll
+				for(int k = 0; k < NR; k++)
+				{
+					if(COUNT) n_cull += (uint32_t) __popcll(__ballot(s.live[k]));
+					mine[k] = s.live[k] && line_touches<CONES>(r[k], dd[k], cA, cB);
+					some = some || mine[k];
+				}
+				if(__any(some))
+				{
+					const int i0 = c * sv.chunk, i1 = (i0 + sv.chunk < sv.nt) ? i0 + sv.chunk : sv.nt;
+					float4 n0 = mesh_row(sv.tris, 3 * i0), n1 = mesh_row(sv.tris, 3 * i0 + 1), n2 = mesh_row(sv.tris, 3 * i0 + 2);
+					for(int t = i0; t < i1; t++)
+					{
+						const f3 v0 = ld3(n0), e1 = ld3(n1), e2 = ld3(n2);
+						const int file = __float_as_int(n1.w);
+						n0 = mesh_row(sv.tris, 3 * t + 3);
+						n1 = mesh_row(sv.tris, 3 * t + 4);
+						n2 = mesh_row(sv.tris, 3 * t + 5);
+#pragma unroll
+						for(int k = 0; k < NR; k++)
+						{
+							if(COUNT) n_tri += (uint32_t) __popcll(__ballot(mine[k] && s.live[k]));
+							if(mine[k] && s.live[k] && shadow_triangle_hit(s.o, s.d[k], v0, e1, e2, file, s.own, s.tmax[k])) s.live[k] = false;
+						}
+					}
+				}
+			}
+			bool some_live = false;
+#pragma unroll
+			for(int k = 0; k < NR; k++) some_live = some_live || s.live[k];
+			if(!__any(some_live)) break;
+		}
+		i = enter ? i + 1 : i_out;
+		A = enter ? A_in : A_out;
+		B = enter ? B_in : B_out;
+		lk = enter ? lk_in : lk_out;
+	}
+	if(COUNT) tri_work_add(sv, n_cull, n_tri);
+}
+
+// The shadow walk of a lane's NR rays: the tree in sv.chunks (sv.nchunks nodes), or every triangle where the wave has none
+// (sv.nchunks == 0: SKR_NO_CULL, a ray that starts outside the tree's ball).  Both give the same answers.
+template <int NR>
+SKR_DEV void shadow_triangles(const SceneView &sv, ShadowRays<NR> &s)
+{
+	if(sv.nchunks > 0)
+	{ // (the counting instantiation runs only while sv.tri_work is set, as in any_triangle_closer)
+		if(__builtin_expect(sv.tri_work != nullptr, 0))
+		{
+			if(sv.cones) tree_walk_shadow<NR, true, true>(sv, s);
+			else tree_walk_shadow<NR, false, true>(sv, s);
+		}
+		else if(sv.cones) tree_walk_shadow<NR, true, false>(sv, s);
+		else tree_walk_shadow<NR, false, false>(sv, s);
+		return;
+	}
+	uint32_t n_tri = 0;
+	float4 n0 = mesh_row(sv.tris, 0), n1 = mesh_row(sv.tris, 1), n2 = mesh_row(sv.tris, 2); // (tris[] carries one pad triangle)
+	for(int t = 0; t < sv.nt; t++)
+	{
+		const f3 v0 = ld3(n0), e1 = ld3(n1), e2 = ld3(n2);
+		const int file = __float_as_int(n1.w);
+		n0 = mesh_row(sv.tris, 3 * t + 3);
+		n1 = mesh_row(sv.tris, 3 * t + 4);
+		n2 = mesh_row(sv.tris, 3 * t + 5);
+		bool some_live = false;
+#pragma unroll
+		for(int k = 0; k < NR; k++)
+		{
+			if(sv.tri_work) n_tri += (uint32_t) __popcll(__ballot(s.live[k]));
+			if(s.live[k] && shadow_triangle_hit(s.o, s.d[k], v0, e1, e2, file, s.own, s.tmax[k])) s.live[k] = false;
+			some_live = some_live || s.live[k];
+		}
+		if((t & 7) == 7 && !__any(some_live)) break;
+	}
+	tri_work_add(sv, 0u, n_tri);
 }
 
 // ---- --legacy-reflect: the leaf functions of raytrace.h:45-103 ----
