@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle campaign (development aid; the committed tests hold fixed cases): random sphere / mesh scenes, random
-options over every mode the product has (--gillum at random N and depth through both schedules of the node pipeline and through the
+options over every mode the product has (cameras of the pose families of tests/camera_poses.py, --gillum at random N and depth through both schedules of the node pipeline and through the
 general level pipeline, --jsample, --shadow, --strict-scn, --shade-triangles, --legacy-reflect — also together, at any depth —,
 --progressive), small frames, bit-for-bit comparison of the float image,
 the bytes and the ray / hit / shadow-ray counts.
@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 import skele_raytracer_amd as skr  # noqa: E402
 from oracle import pyoracle as orc  # noqa: E402  (the checker: this is a test tool)
+from camera_poses import posed_text, random_camera  # noqa: E402
 from scenegen import write_random_mesh_scene  # noqa: E402
 
 
@@ -43,6 +44,10 @@ def generate(rng, cases, tmp):
         scn = os.path.join(tmp, "s%d.scn" % c)
         mesh = rng.random() < 0.35
         (write_random_mesh_scene if mesh else write_sphere_scene)(scn, rng)
+        if rng.random() < 0.5:  # a camera of the pose families of tests/camera_poses.py: rolled, long vectors, inside or next to a sphere, along an axis
+            text = open(scn).read()
+            balls = [tuple(float(t) for t in ln.split()[1:5]) for ln in text.split("\n") if ln.split()[:1] == ["sphere"]]
+            open(scn, "w").write(posed_text(text, random_camera(rng, (0, 1.5, 3), balls)))
         w, h = int(rng.integers(8, 97)), int(rng.integers(8, 65))
         kw = dict(seed=int(rng.integers(1, 2 ** 40)), shadow=bool(rng.random() < .6), fov=float(rng.choice([30, 60, 90, 140])))
         mode = rng.choice(["gi", "gi", "gi", "plain", "legacy", "surfaces"])

@@ -8,6 +8,8 @@ fixtures, with the exact command line and seed of each in manifest.json.
 Also copies the data inputs the tests need on the GPU box, where
 /root/reference does not exist: the .scn scene files (data, not source) and the
 reference's one pixel-exact fixture renders/testcpu.ppm.
+Then writes this project's own posed scenes (tests/camera_poses.py: the scenes above under other cameras) next to them and
+renders and dumps those through the same binary.
 
 Usage: python tools/make_golden.py        (needs /root/reference and gcc/g++)
 """
@@ -21,6 +23,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import camera_poses  # noqa: E402  (the pose catalogue: this project's own data)
+
 REF = "/root/reference"
 GOLD = os.path.join(ROOT, "tests", "golden")
 BIN = os.path.join(ROOT, "oracle", "_ref", "ref_render")
@@ -76,6 +81,15 @@ def gz_write(src, dst):
         g.write(f.read())
 
 
+def gz_keep_or_write(dst, payload):
+    """Write payload gzipped to dst unless dst already holds exactly that payload (another zlib packs the same bytes differently:
+    a fixture whose content did not change keeps its bytes)."""
+    if os.path.exists(dst) and gzip.decompress(open(dst, "rb").read()) == payload:
+        return
+    with open(dst, "wb") as f:
+        f.write(gzip.compress(payload, 9, mtime=0))
+
+
 def main():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/ref_render"])
     os.makedirs(os.path.join(GOLD, "scenes"), exist_ok=True)
@@ -106,6 +120,28 @@ def main():
         dst = os.path.join(GOLD, "scene_dump_%s.txt.gz" % scn[:-4])
         gz_write(d, dst)
         manifest["scene_dumps"][scn] = {"file": os.path.basename(dst), "sha256_uncompressed": sha(d)}
+    # the camera poses (tests/camera_poses.py): this project's own scenes, the base scenes above with another camera line, rendered and
+    # parsed by the reference like the others.  A degenerate pose gets a golden only if the reference agrees with itself on it.
+    camera_poses.write_all(os.path.join(GOLD, "scenes"))
+    tmp2 = "/tmp/golden_tmp2.ppm"
+    for name, scn, args in camera_poses.golden_cases():
+        cmd = [BIN, "--path", os.path.join(GOLD, "scenes", scn), "--output", tmp] + args
+        print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, stdout=subprocess.DEVNULL)
+        if name in camera_poses.DEGENERATE_GOLDENS:
+            subprocess.check_call(cmd[:4] + [tmp2] + args, stdout=subprocess.DEVNULL)
+            if open(tmp, "rb").read() != open(tmp2, "rb").read():
+                print("degenerate pose %s: two runs of the reference differ, no golden" % name)
+                continue
+        dst = os.path.join(GOLD, "ref_%s.ppm.gz" % name)
+        gz_write(tmp, dst)
+        manifest["cases"][name] = {"scene": scn, "args": args, "sha256_uncompressed": sha(tmp), "file": os.path.basename(dst)}
+    for pose in camera_poses.POSES:
+        scn = camera_poses.scene_file(pose)
+        d = "/tmp/golden_dump.txt"
+        subprocess.check_call([BIN, "--path", os.path.join(GOLD, "scenes", scn), "--dump-scene", d])
+        # (the dump repeats the base scene's but for its camera line: camera_poses.dump_lines puts it together again and checks the sha256)
+        manifest["scene_dumps"][scn] = {"base": pose.base, "camera": open(d).readline().rstrip("\n"), "sha256_uncompressed": sha(d)}
     # bp::fresnel / bp::refraction / bp::reflect_direction themselves on 10 000 triples (ref_driver.cpp --eval-legacy): 14 words per triple
     # [dir.xyz normal.xyz ior | fresnel | refraction.xyz | reflect_direction(normalize(dir), normal).xyz], kept as a uint32 array
     try:
@@ -117,8 +153,7 @@ def main():
         assert words.shape == (10000, 14)
         buf = io.BytesIO()
         np.save(buf, words)
-        with open(os.path.join(GOLD, "ref_legacy_eval.npy.gz"), "wb") as f:
-            f.write(gzip.compress(buf.getvalue(), 9, mtime=0))
+        gz_keep_or_write(os.path.join(GOLD, "ref_legacy_eval.npy.gz"), buf.getvalue())
         manifest["reference_fixture"]["ref_legacy_eval.npy.gz"] = {
             "source": "oracle/_ref/ref_render --eval-legacy", "sha256_text": sha(ev),
             "meaning": "the reference's bp::fresnel (blinn_phong.h:156), bp::refraction (:143), bp::reflect_direction (:137) on 10 000 (direction, normal, ior) triples"}
@@ -136,8 +171,7 @@ def main():
         small = im[:h4, :w4].reshape(h4 // 4, 4, w4 // 4, 4, 3).astype(np.float32).mean(axis=(1, 3)).round().astype(np.uint8)
         buf = io.BytesIO()
         np.save(buf, small)
-        with open(os.path.join(GOLD, "readme_bp_jsample5_parallel_shadows_quarter.npy.gz"), "wb") as f:
-            f.write(gzip.compress(buf.getvalue(), 9, mtime=0))
+        gz_keep_or_write(os.path.join(GOLD, "readme_bp_jsample5_parallel_shadows_quarter.npy.gz"), buf.getvalue())
         manifest["reference_fixture"]["readme_bp_jsample5_parallel_shadows_quarter.npy.gz"] = {
             "source": "renders/shadows/sample_pngs/bp_jsample5_parallel_shadows.png", "sha256_source": sha(src),
             "meaning": "README picture (1919x1003 screenshot of the 1920x1080 window), mean of 4x4 pixel blocks, uint8 [250, 479, 3]"}

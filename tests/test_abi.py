@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import skele_raytracer_amd as skr
+from camera_poses import dump_lines
 from conftest import GOLD, ROOT, manifest, read_ppm_bytes, scene_path
 
 
@@ -38,8 +39,7 @@ def _hex(v):
 
 @pytest.mark.parametrize("scn", ["spheres1.scn", "spheres2.scn", "bear.scn", "test.scn", "dragon.scn"])
 def test_loader_matches_reference_parseScene_dump(scn):
-    with gzip.open(os.path.join(GOLD, manifest()["scene_dumps"][scn]["file"]), "rt") as f:
-        lines = f.read().splitlines()
+    lines = dump_lines(manifest(), scn)
     sc = skr.parse_scene(scene_path(scn))
     info = sc.info
     s, t, l = sc.arrays()

@@ -94,7 +94,7 @@ def test_gpu_equals_checker_on_synthetic_guides(chk, h, w, L):
     assert_same(rgb, out, ref_rgb, ref_f, "%dx%d L=%d" % (h, w, L))
 
 
-@pytest.mark.parametrize("scn", ["dragon.scn", "test.scn"])
+@pytest.mark.parametrize("scn", ["dragon.scn", "test.scn", "pose_dragon_rolled.scn", "pose_dragon_inside.scn"])  # + a rolled and a mesh-interior pose (tests/camera_poses.py)
 def test_camera_guides_culled_equal_every_triangle_and_the_checker(scn):
     """Camera waves of skr_trace_rays walk the renderer's tree: the same bits as every triangle and as the ray-query checker."""
     import tempfile

@@ -140,9 +140,18 @@ def test_reference_fixture_testcpu_on_gpu(gpu):
 def test_partition_independence(gpu, tile_rows, G):
     """Row-tile interleaving over G 'ranks' reassembles to the single-launch frame, byte for byte
     (RNG keyed by global pixel index)."""
+    _partition_independence("spheres2.scn", tile_rows, G)
+
+
+def test_partition_independence_under_a_rolled_camera(gpu):
+    """The same under a camera whose right vector has three non-zero components (tests/camera_poses.py s2_rolled)."""
+    _partition_independence("pose_s2_rolled.scn", 16, 3)
+
+
+def _partition_independence(scn, tile_rows, G):
     w, h = 200, 117
     opt = skr.Options(w, h, gillum=4, shadow=True, seed=11)
-    r = renderer("spheres2.scn")
+    r = renderer(scn)
     full, _ = r.render(opt)
     full = full.cpu().numpy()
     out = np.zeros_like(full)

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from camera_poses import dump_lines
 from conftest import GOLD, args_to_kwargs, manifest, read_golden_ppm, scene_path
 
 CASES = sorted(manifest()["cases"].items())
@@ -56,8 +57,7 @@ def test_shared_math_stays_within_tolerance_of_libm(oracle, name):
 
 
 def _dump_lines(scn):
-    with gzip.open(os.path.join(GOLD, manifest()["scene_dumps"][scn]["file"]), "rt") as f:
-        return f.read().splitlines()
+    return dump_lines(manifest(), scn)
 
 
 def _hex(v):
