@@ -158,6 +158,41 @@ int skr_scene_set_fog(skr_scene *scene, const float *rows, int32_t n);
  *     not advanced by shadow rays: the reference has no such loop. */
 int skr_scene_set_triangle_shadows(skr_scene *scene, int enable);
 int skr_scene_get_triangle_shadows(const skr_scene *scene, int *enabled);
+/* The sphere tree (new, off by default: DESIGN.md 8.10).  A switch of the scene, as triangle shadows are: a renderer takes the scene's
+ * setting when it is created, its clones and the multi-GPU frame steps with it.  SKR_SCN_SPHERE_TREE (`raytracer --sphere-tree`;
+ * combines with the other scene flags) creates the scene with it switched on.  The rule (normative):
+ *   - Off: every launch is what it is without the switch, bit for bit: the same kernels, skr_kernel_variant(), counters, and the same
+ *     refusal of a scene whose sphere table does not fit a workgroup's LDS.
+ *   - On, for a scene with at least one sphere: every frame and every shading query renders on the general level pipeline, in every
+ *     mode it has; skr_kernel_variant() is "level_pipeline_g1_stree" ("level_pipeline_g1_stree_tshadow" where triangle shadows are in
+ *     force; shading queries: "shade_rays_g1_stree", "shade_rays_g1_stree_tshadow").  Sphere geometry and materials are read from HBM:
+ *     no kernel's LDS need depends on the sphere count, which is limited by memory and n < 2^31 only.  Lights stay in LDS.  The shadow
+ *     masks and GI masks are not consulted.
+ *   - Images (bytes and floats) and skr_renderer_read_work out[0..3] are what they are without the switch where both render the scene:
+ *     the closest hit is the sphere with the smallest t2, equal t2 going to the lower file index; out[3] counts n_spheres per radiance
+ *     ray and, per shadow ray, the spheres up to and including the first occluder in file order, as the reference's loops run.
+ *   - Culling is exactly conservative: no sphere whose binary32 discriminant makes it a candidate for a ray (D >= 0 and b < 0,
+ *     utils.h:113-121 in the reference's operation order) is skipped for that ray.  A wave with a ray that starts outside the tree's
+ *     ball, or whose direction is not finite or of extreme length, runs the loop over every sphere instead; so does every wave under
+ *     SKR_NO_SPHERE_CULL=1 (read like the other SKR_* switches).  The answers are the same.
+ *   - Ray queries (skr_trace_rays, closest and any-hit) walk the same tree under the same rule — a wave with a ray outside the ball or with
+ *     a direction that is not finite runs the loop over every sphere — and give the answers they give without the switch. */
+#define SKR_HAS_SPHERE_TREE 1
+#define SKR_SCN_SPHERE_TREE 8u
+int skr_scene_set_sphere_tree(skr_scene *scene, int enable);
+int skr_scene_get_sphere_tree(const skr_scene *scene, int *enabled);
+/* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
+ * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
+ * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device
+ * order, file_index[n_spheres] = their indices in the file; node_spheres[n_nodes][5] = {centre, R^2, kappa}: a line o + t d may hold a
+ * candidate below the node only if |(C - o) x d|^2 <= (R^2 + kappa |C - o|^2) |d|^2 in the device's binary32 (NaN: it may);
+ * node_links[n_nodes][4] = {skip, first chunk, chunk count (height-1 nodes only, else 0), smallest file index below};
+ * chunk_spheres[n_chunks][5] likewise (the always-tested chunks: R^2 = inf), chunk_links[n_chunks][3] = {smallest file index, first
+ * device sphere, sphere count}; ball = {centre, radius}.  Any pointer may be NULL; the counts are returned first so the caller can size
+ * the arrays.  Used by the host-logic tests. */
+int skr_scene_get_sphere_tree_data(const skr_scene *scene, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks, int32_t *n_always,
+								   float *device_spheres, int32_t *file_index, float *node_spheres, int32_t *node_links, float *chunk_spheres,
+								   int32_t *chunk_links, float ball[4]);
 void skr_scene_destroy(skr_scene *scene);
 int skr_scene_get_info(const skr_scene *scene, skr_scene_info *info);
 /* Copy the parsed arrays back out in the skr_scene_create_from_arrays layouts
@@ -271,6 +306,10 @@ int skr_renderer_count_triangle_work(skr_renderer *r, int enable);
  * themselves —, out[2] the ray-triangle tests the reference's loop runs for the same rays (raytrace.h:171-186: every triangle for
  * every radiance ray).  bench.py prices mesh scenes with out[0] and out[1]; out[2] / out[1] is what the exact culling saves. */
 int skr_renderer_read_triangle_work(skr_renderer *r, uint64_t out[3], int reset);
+/* The same for the sphere tree's walks (skr_scene_set_sphere_tree), counted only while skr_renderer_count_triangle_work is on: out[0]
+ * culling-sphere tests and out[1] ray-sphere tests the walks executed, lanes that needed the test (a pair of shadow rays counts each
+ * ray).  What the reference's loops run for the same rays is skr_renderer_read_work out[3]. */
+int skr_renderer_read_sphere_tree_work(skr_renderer *r, uint64_t out[2], int reset);
 /* The SKR_* development switches (kernel variant, budgets: DESIGN.md) are read from the environment
  * once, at skr_renderer_create; this reads them again (tests and A/B tools change them between frames). */
 int skr_renderer_reload_switches(skr_renderer *r);

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -84,6 +84,10 @@ def lib():
     L.skr_scene_set_fog.argtypes = [vp, vp, C.c_int32]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
+    L.skr_scene_set_sphere_tree.argtypes = [vp, C.c_int]
+    L.skr_scene_get_sphere_tree.argtypes = [vp, C.POINTER(C.c_int)]
+    L.skr_scene_get_sphere_tree_data.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp, vp, vp, vp, vp]
+    L.skr_renderer_read_sphere_tree_work.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.skr_scene_destroy.argtypes = [vp]
     L.skr_scene_destroy.restype = None
     L.skr_scene_get_info.argtypes = [vp, C.POINTER(CSceneInfo)]
@@ -319,9 +323,37 @@ class Scene:
         setting the scene has when it is made."""
         _check(lib().skr_scene_set_triangle_shadows(self.h, int(bool(enable))), "skr_scene_set_triangle_shadows")
 
+    def sphere_tree(self):
+        """The scene's sphere-tree switch (include/skr.h skr_scene_set_sphere_tree)."""
+        on = C.c_int()
+        _check(lib().skr_scene_get_sphere_tree(self.h, C.byref(on)), "skr_scene_get_sphere_tree")
+        return bool(on.value)
+
+    def set_sphere_tree(self, enable):
+        """Frames and shading queries render on the culled sphere walk, spheres in HBM (include/skr.h states the rule).  A renderer takes
+        the setting the scene has when it is made."""
+        _check(lib().skr_scene_set_sphere_tree(self.h, int(bool(enable))), "skr_scene_set_sphere_tree")
+
+    def sphere_tree_data(self):
+        """The sphere tree as a renderer uploads it (include/skr.h skr_scene_get_sphere_tree_data): a dict of chunk_size, n_always (chunks of
+        always-tested spheres at the front), spheres [n, 4] float32 in device order, file_index [n] int32, node_spheres [n_nodes, 5] float32
+        {centre, R^2, kappa}, node_links [n_nodes, 4] int32 {skip, first chunk, chunk count, smallest file index}, chunk_spheres
+        [n_chunks, 5], chunk_links [n_chunks, 3] int32 {smallest file index, first sphere, count}, ball [4]."""
+        cs, nn, nc, na = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().skr_scene_get_sphere_tree_data(self.h, C.byref(cs), C.byref(nn), C.byref(nc), C.byref(na), None, None, None, None, None, None, None),
+               "skr_scene_get_sphere_tree_data")
+        n = self.info.n_spheres
+        d = dict(chunk_size=cs.value, n_always=na.value, spheres=np.zeros((n, 4), np.float32), file_index=np.zeros(n, np.int32),
+                 node_spheres=np.zeros((nn.value, 5), np.float32), node_links=np.zeros((nn.value, 4), np.int32),
+                 chunk_spheres=np.zeros((nc.value, 5), np.float32), chunk_links=np.zeros((nc.value, 3), np.int32), ball=np.zeros(4, np.float32))
+        _check(lib().skr_scene_get_sphere_tree_data(self.h, None, None, None, None, d["spheres"].ctypes.data, d["file_index"].ctypes.data,
+                                                    d["node_spheres"].ctypes.data, d["node_links"].ctypes.data, d["chunk_spheres"].ctypes.data,
+                                                    d["chunk_links"].ctypes.data, d["ball"].ctypes.data), "skr_scene_get_sphere_tree_data")
+        return d
+
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
-                    triangle_shadows=False):
+                    triangle_shadows=False, sphere_tree=False):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -341,19 +373,22 @@ class Scene:
             _check(lib().skr_scene_set_sphere_ior(sc.h, q.ctypes.data), "skr_scene_set_sphere_ior")
         if triangle_shadows:
             sc.set_triangle_shadows(True)
+        if sphere_tree:
+            sc.set_sphere_tree(True)
         return sc
 
 
-SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS = 1, 2, 4  # include/skr.h SKR_SCN_*
+SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE = 1, 2, 4, 8  # include/skr.h SKR_SCN_*
 FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
 
 
-def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False):
+def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False):
     """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept),
     fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded), triangle_shadows = SKR_SCN_TRIANGLE_SHADOWS
-    (--triangle-shadows: triangles cast shadows in frames with shade_triangles and shadow)."""
+    (--triangle-shadows: triangles cast shadows in frames with shade_triangles and shadow), sphere_tree = SKR_SCN_SPHERE_TREE
+    (--sphere-tree: frames and shading queries on the culled sphere walk, any sphere count)."""
     h = C.c_void_p()
-    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0)
+    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0)
     _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), flags, C.byref(h)), "skr_scene_create_from_scn_ex")
     return Scene(h.value)
 
@@ -523,6 +558,12 @@ class Renderer:
         _check(lib().skr_renderer_read_triangle_work(self.h, out, int(reset)), "skr_renderer_read_triangle_work")
         return {"cull_tests": int(out[0]), "triangle_tests": int(out[1]), "reference_triangle_tests": int(out[2])}
 
+    def sphere_tree_work(self, reset=True):
+        """What the sphere tree's walks executed while count_triangle_work was on (include/skr.h skr_renderer_read_sphere_tree_work)."""
+        out = (C.c_uint64 * 2)()
+        _check(lib().skr_renderer_read_sphere_tree_work(self.h, out, int(reset)), "skr_renderer_read_sphere_tree_work")
+        return {"cull_tests": int(out[0]), "sphere_tests": int(out[1])}
+
     def kernel_timing(self, enable=True):
         _check(lib().skr_renderer_kernel_timing(self.h, int(enable)), "skr_renderer_kernel_timing")
 
@@ -568,6 +609,7 @@ class Renderer:
         out = torch.empty(n, dtype=torch.int32, device=dev) if any_hit else torch.empty((n, 8), dtype=torch.float32, device=dev)
         if n == 0:  # (an empty tensor has no address to pass)
             return out if any_hit else Hits(out[:, 0], out.view(torch.int32)[:, 1], out.view(torch.int32)[:, 2], out[:, 3:6], out)
+        self._sync_switches()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             _check(lib().skr_trace_rays(self.h, rays.data_ptr(), n, TRACE_ANY_HIT if any_hit else 0, out.data_ptr(), stream), "skr_trace_rays")

@@ -55,13 +55,19 @@ struct DeviceScene {
 	float4 trace_ball{};
 	int trace_cones = 0;
 	bool tri_shadows = false; // the scene's triangle-shadow switch when the renderer was made (include/skr.h skr_scene_set_triangle_shadows)
+	// the sphere tree (include/skr.h skr_scene_set_sphere_tree; render_params.h SphereTree), uploaded where the scene had the switch on
+	bool sphere_tree = false;
+	size_t off_st_rows = 0, off_st_chunks = 0, off_st_nodes = 0;
+	int st_nodes = 0, st_chunks = 0, st_always = 0;
+	float4 st_ball{};
+	unsigned long long *d_st_work = nullptr; // 256 x {culling-sphere tests, sphere tests} its walks executed (skr_renderer_read_sphere_tree_work)
 
 	DeviceScene() = default;
 	DeviceScene(const DeviceScene &) = delete;
 	DeviceScene &operator=(const DeviceScene &) = delete;
 	~DeviceScene()
 	{
-		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work})
+		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work})
 			if(p) (void) hipFree(p);
 	}
 };
@@ -136,6 +142,7 @@ static void load_switches(SkrSwitches &sw)
 		sw.pipeline = !strcmp(e, "nodes") ? SKR_PIPE_NODES : !strcmp(e, "generic") ? SKR_PIPE_GENERIC : SKR_PIPE_OTHER;
 	sw.no_cones = getenv("SKR_NO_CONES") != nullptr;
 	sw.no_cull = getenv("SKR_NO_CULL") != nullptr;
+	if(const char *e = getenv("SKR_NO_SPHERE_CULL")) sw.no_sphere_cull = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_LEVELS_BUDGET_MB")) sw.budget_mb = atoi(e) > 0 ? atoi(e) : 1;
 	if(const char *e = getenv("SKR_FLAT")) sw.flat = atoi(e) > 0 ? 1 : -1;
 	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = atoi(e) > 0 ? 1 : 0;
@@ -152,7 +159,7 @@ int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t
 							   float *d_rgbf, void *stream);
 
 // The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | shadow
-// masks | GI masks | trace tree, then 16 rows of padding (the sphere loops ask for the rows of a trip ahead without a bounds test,
+// masks | GI masks | trace tree | sphere tree (rows, chunks, nodes), then 16 rows of padding (the sphere loops ask for the rows of a trip ahead without a bounds test,
 // shade_common.h sphere_rows).  Sets the offsets and the scalars of `d` that go with the sections; host only, nothing is uploaded.
 static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 {
@@ -205,6 +212,19 @@ static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 	d.trace_ball = make_float4(s.trace_ball[0], s.trace_ball[1], s.trace_ball[2], s.trace_ball[3]);
 	d.trace_cones = s.trace_any_cone ? 1 : 0;
 	d.tri_shadows = s.triangle_shadows;
+	d.sphere_tree = s.sphere_tree && !s.sph_geom.empty();
+	if(d.sphere_tree)
+	{ // (the walk asks for the rows of a whole chunk, up to 3 behind the last sphere: the chunks follow)
+		SkrSphereTree t;
+		skr_build_sphere_tree(s, t);
+		d.off_st_rows = put4(t.rows);
+		d.off_st_chunks = put4(t.chunks);
+		d.off_st_nodes = put4(t.nodes);
+		d.st_nodes = t.n_nodes;
+		d.st_chunks = t.n_chunks;
+		d.st_always = t.n_always;
+		d.st_ball = make_float4(t.ball[0], t.ball[1], t.ball[2], t.ball[3]);
+	}
 	rows.resize(rows.size() + 16, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
 	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
 		float top = 1.0f;
@@ -309,6 +329,8 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	if(e == hipSuccess) e = hipMemset(s->d_counters, 0, counter_bytes);
 	if(e == hipSuccess) e = hipMalloc((void **) &s->d_tri_work, 256 * 2 * sizeof(unsigned long long));
 	if(e == hipSuccess) e = hipMemset(s->d_tri_work, 0, 256 * 2 * sizeof(unsigned long long));
+	if(e == hipSuccess && s->sphere_tree) e = hipMalloc((void **) &s->d_st_work, 256 * 2 * sizeof(unsigned long long));
+	if(e == hipSuccess && s->sphere_tree) e = hipMemset(s->d_st_work, 0, 256 * 2 * sizeof(unsigned long long));
 	if(e == hipSuccess) e = hipMalloc((void **) &s->d_camec, (ns + 16) * 16);
 	if(e == hipSuccess) e = hipMemset(s->d_camec, 0, (ns + 16) * 16);
 	if(e == hipSuccess)
@@ -532,8 +554,8 @@ static int check_plan(const skr_renderer *r, const RenderParams &p, bool fits, s
 	}
 	if(lds > (size_t) r->scene->lds_limit)
 	{
-		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup", lds, p.n_spheres, p.n_lights,
-					  r->scene->lds_limit);
+		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup%s", lds, p.n_spheres, p.n_lights,
+					  r->scene->lds_limit, r->scene->sphere_tree ? "" : " (the sphere tree, skr_scene_set_sphere_tree / --sphere-tree, keeps the spheres out of LDS)");
 		return SKR_ERR_UNSUPPORTED;
 	}
 	return SKR_OK;
@@ -559,6 +581,23 @@ static QueryTrees query_trees(const skr_renderer *r)
 // was without the switch: the same kernels, the same skr_kernel_variant().
 static bool tri_shadows_in_force(const skr_renderer *r, const RenderParams &p) { return r->scene->tri_shadows && p.shade_triangles && p.use_shadows; }
 
+// the sphere tree of a renderer whose scene had the switch on, under the renderer's switches (render_params.h SphereTree)
+static SphereTree sphere_tree_of(const skr_renderer *r)
+{
+	const DeviceScene &s = *r->scene;
+	SphereTree t{};
+	t.nodes = s.d_blob + s.off_st_nodes;
+	t.chunks = s.d_blob + s.off_st_chunks;
+	t.rows = s.d_blob + s.off_st_rows;
+	t.n_nodes = s.st_nodes;
+	t.n_chunks = s.st_chunks;
+	t.n_always = s.st_always;
+	t.cull = (r->sw.no_sphere_cull || !(s.st_ball.w >= 0.0f)) ? 0 : 1; // (a ball of radius -1: the tree's bounds do not hold, no wave walks it)
+	t.ball = s.st_ball;
+	t.work = r->count_tri ? s.d_st_work : nullptr;
+	return t;
+}
+
 // one pass of the tiles `ts` selects (render_impl has checked the arguments and set the device)
 static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
 {
@@ -575,7 +614,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.rgb = d_rgb;
 	p.rgbf = d_rgbf;
 	LaunchPlan lp;
-	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp);
+	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp, r->scene->sphere_tree);
 	rc = check_plan(r, p, fits, lp.lds_bytes, 0);
 	bool kept = false;
 	if(rc == SKR_OK && lp.path != SKR_PATH_DIRECT) rc = take_node_scratch(r, lp.scratch_bytes, &kept);
@@ -614,8 +653,9 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	{ // (shade_triangles: the general level pipeline)
 		lp.tri_shadows = true;
 		lp.shadows.trees = query_trees(r);
-		lp.variant = "level_pipeline_g1_tshadow";
+		lp.variant = lp.sphere_tree ? "level_pipeline_g1_stree_tshadow" : "level_pipeline_g1_tshadow";
 	}
+	if(lp.sphere_tree) lp.stree = sphere_tree_of(r);
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
 	if(r->timing) r->timed.push_back(hook);
@@ -919,6 +959,23 @@ int skr_renderer_read_triangle_work(skr_renderer *r, uint64_t out[3], int reset)
 	return SKR_OK;
 }
 
+int skr_renderer_read_sphere_tree_work(skr_renderer *r, uint64_t out[2], int reset)
+{
+	if(!r || !out) return SKR_ERR_ARG;
+	out[0] = out[1] = 0;
+	if(!r->scene->d_st_work) return SKR_OK; // (no sphere tree: no walks)
+	SKR_HIP(hipSetDevice(r->scene->device));
+	unsigned long long h[256 * 2];
+	SKR_HIP(hipMemcpy(h, r->scene->d_st_work, sizeof(h), hipMemcpyDeviceToHost)); // synchronises with prior launches
+	for(int s = 0; s < 256; s++)
+	{
+		out[0] += h[2 * s];
+		out[1] += h[2 * s + 1];
+	}
+	if(reset) SKR_HIP(hipMemset(r->scene->d_st_work, 0, sizeof(h)));
+	return SKR_OK;
+}
+
 int skr_render_progressive_host(skr_renderer *r, const skr_options *opt, uint32_t every, uint8_t *h_rgb, float *h_rgbf, skr_progress_fn progress, void *user,
 								float *kernel_ms)
 {
@@ -1000,7 +1057,13 @@ int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t 
 	s.chunk = sc.chunk_size;
 	s.cam = f3{sc.info.camera[0], sc.info.camera[1], sc.info.camera[2]};
 	s.trees = query_trees(r);
-	SKR_HIP(skr_launch_trace(s, reinterpret_cast<const float4 *>(d_rays), n, any_hit, d_out, (hipStream_t) stream));
+	SphereTree st{};
+	if(sc.sphere_tree)
+	{ // the sphere searches walk the tree (a query counts nothing)
+		st = sphere_tree_of(r);
+		st.work = nullptr;
+	}
+	SKR_HIP(skr_launch_trace(s, reinterpret_cast<const float4 *>(d_rays), n, any_hit, d_out, (hipStream_t) stream, sc.sphere_tree ? &st : nullptr));
 	return SKR_OK;
 }
 
@@ -1046,8 +1109,9 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	if(rc != SKR_OK) return rc;
 	p.grid_size = 0; // (one sample: `sample`)
 	GPlan pl;
-	const bool fits = skr_generic_plan(p, pl);
-	rc = check_plan(r, p, fits, skr_scene_kernels_lds(p), SKR_SHADE_ROW);
+	const bool stree = r->scene->sphere_tree;
+	const bool fits = skr_generic_plan(p, pl, stree);
+	rc = check_plan(r, p, fits, stree ? skr_lights_kernels_lds(p) : skr_scene_kernels_lds(p), SKR_SHADE_ROW);
 	if(rc == SKR_OK) rc = take_node_scratch(r, pl.total);
 	if(rc != SKR_OK) return rc;
 	p.node_scratch = r->nodes.p;
@@ -1061,8 +1125,10 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	TriShadows tsh{};
 	const bool tri_shadows = tri_shadows_in_force(r, p);
 	if(tri_shadows) tsh.trees = q.trees;
-	g_variant = tri_shadows ? "shade_rays_g1_tshadow" : "shade_rays_g1";
-	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr));
+	const SphereTree st = stree ? sphere_tree_of(r) : SphereTree{};
+	if(stree) g_variant = tri_shadows ? "shade_rays_g1_stree_tshadow" : "shade_rays_g1_stree";
+	else g_variant = tri_shadows ? "shade_rays_g1_tshadow" : "shade_rays_g1";
+	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr, stree ? &st : nullptr));
 	return SKR_OK;
 }
 

@@ -91,6 +91,8 @@ struct LaunchPlan {
 	GPlan generic;                     // (path == SKR_PATH_GENERIC)
 	bool tri_shadows = false;          // triangle shadows are in force for this launch (api.cpp render_pass sets it and `shadows`; the plan itself says no)
 	TriShadows shadows{};
+	bool sphere_tree = false;          // the launch renders on the sphere tree (skr_plan_launch's argument; api.cpp render_pass sets `stree`)
+	SphereTree stree{};
 };
 
 // the scene SoA every kernel stages into LDS (wave_common.h stage_scene): 4 rows per sphere, a zero row, 2 rows per light
@@ -103,6 +105,9 @@ static inline size_t skr_scene_lds_bytes(const RenderParams &p) { return ((size_
 // and faulted.  So the plans count both.
 constexpr size_t SKR_PREFIX_LDS = ((size_t) SKR_PREFIX_WORDS * sizeof(uint32_t) + 15) & ~(size_t) 15;
 static inline size_t skr_scene_kernels_lds(const RenderParams &p) { return skr_scene_lds_bytes(p) + 32 + SKR_PREFIX_LDS; }
+// the same for the general level pipeline's instances with the sphere tree: only the lights are staged
+static inline size_t skr_lights_lds_bytes(const RenderParams &p) { return ((size_t) 1 + 2 * p.n_lights) * 16; }
+static inline size_t skr_lights_kernels_lds(const RenderParams &p) { return skr_lights_lds_bytes(p) + 32 + SKR_PREFIX_LDS; }
 
 // children per node of the --gillum tree: N --gillum rays, and under --legacy-reflect 2 per light (the arity of the counter RNG's
 // node ids, include/skr.h)
@@ -132,7 +137,8 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
-bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp); // false: the launch takes a level pipeline and not one band of it fits the budget
+// sphere_tree: the renderer's scene has the sphere tree switched on and at least one sphere (include/skr.h skr_scene_set_sphere_tree)
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree = false); // false: the launch takes a level pipeline and not one band of it fits the budget
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook);
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream);
 // render_nodes.hip
@@ -140,11 +146,12 @@ bool skr_nodes_plan(const RenderParams &p, size_t lds_limit, NodePlan &pl); // f
 hipError_t skr_launch_nodes(const RenderParams &p, const NodePlan &pl, hipStream_t stream, const SkrTimingHook *hook);
 hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level, uint32_t *n);
 // render_generic.hip
-bool skr_generic_plan(const RenderParams &p, GPlan &pl); // false: not one band fits the budget
+bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree = false); // false: not one band fits the budget
 // q: a shading query (p.width = SKR_SHADE_ROW, p.out_rows its rows, p.aa_index its sample); null: a frame
 // ts: triangle shadows are in force (the activate kernel's instances with the shadow walk); null: they are not
+// st: the launch renders on the sphere tree (the instances with the sphere walks, which stage only the lights); null: it does not
 hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q = nullptr,
-							  const TriShadows *ts = nullptr);
+							  const TriShadows *ts = nullptr, const SphereTree *st = nullptr);
 // render_wave.hip
 // Every value the level-0 stage of a node-pipeline launch depends on, and where it is kept: what skr_primary_kernel and plan_for
 // (render_nodes.hip) read.  A frame replays the stage only if its key equals, byte for byte, the key the scratch was last built under
@@ -184,7 +191,8 @@ struct TraceScene {
 	int32_t ns, nt, chunk;
 	f3 cam;               // the scene camera: the renderer's tree holds for rays that start there
 };
-hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream);
+// st: the renderer's scene has the sphere tree switched on (the instances whose sphere searches are the tree's walks); null: it has not
+hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream, const SphereTree *st = nullptr);
 hipError_t skr_launch_camera_rays(const RenderParams &p, float4 *rays, hipStream_t stream);
 // denoise.hip: the denoiser (include/skr.h skr_denoise).  Not a render: no plan, no counters, no timing.
 struct DenoiseScratch {

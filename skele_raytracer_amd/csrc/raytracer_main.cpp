@@ -5,7 +5,7 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --scn-fog, --scn-fov, --shade-triangles, --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
+// --scn-fog, --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
 // --adaptive T [--adaptive-min K] [--adaptive-max N].
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cstdio>
@@ -27,6 +27,7 @@ int main(int argc, char *argv[])
 	bool strict_scn = false, width_given = false, height_given = false, depth_given = false; // --strict-scn (new)
 	bool scn_fog = false, scn_fov = false, fov_given = false; // --scn-fog, --scn-fov (new: DESIGN.md "Spherical fog", "Camera half-angle")
 	bool triangle_shadows = false; // --triangle-shadows (new: include/skr.h SKR_SCN_TRIANGLE_SHADOWS)
+	bool sphere_tree = false;      // --sphere-tree (new: include/skr.h SKR_SCN_SPHERE_TREE)
 	bool sharded = false; // --gpus given (even --gpus 1): the frame goes through the multi-GPU path
 	uint32_t tile_rows = 8;
 	int denoise = 0;  // --denoise L: the frame filtered by L iterations of the denoiser (include/skr.h skr_render_denoised_host)
@@ -131,6 +132,7 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--scn-fog")) scn_fog = true;                   // new: spherical_fog lines parsed and shaded (include/skr.h SKR_SCN_FOG)
 		if(!strcmp(argv[i], "--scn-fov")) scn_fov = true;                   // new: fov = 2 x the camera line's half_height_angle unless --fov is given
 		if(!strcmp(argv[i], "--shade-triangles")) option.shade_triangles = 1; // new: triangles as surfaces (include/skr.h skr_options)
+		if(!strcmp(argv[i], "--sphere-tree")) sphere_tree = true;              // new: the culled sphere walk, spheres in HBM: any sphere count, the same image
 		if(!strcmp(argv[i], "--triangle-shadows")) triangle_shadows = true;    // new: triangles cast shadows; needs --shade-triangles and --shadow to have an effect
 		if(!strcmp(argv[i], "--legacy-reflect")) option.legacy_reflect = 1;   // new: the reflection / refraction code behind raytrace.h:44's early return
 		if(!strcmp(argv[i], "--progressive") && has_next) option.progressive_passes = atoi(argv[i + 1]) > 1 ? atoi(argv[i + 1]) : 1; // new: mean of K frames, seeds seed..seed+K-1
@@ -153,7 +155,7 @@ int main(int argc, char *argv[])
 	}
 
 	skr_scene *scene = nullptr;
-	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u) | (triangle_shadows ? SKR_SCN_TRIANGLE_SHADOWS : 0u), &scene) != SKR_OK)
+	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u) | (triangle_shadows ? SKR_SCN_TRIANGLE_SHADOWS : 0u) | (sphere_tree ? SKR_SCN_SPHERE_TREE : 0u), &scene) != SKR_OK)
 	{
 		printf("%s\n", skr_last_error()); // scene.cpp:24-25: message, exit(0)
 		return 0;

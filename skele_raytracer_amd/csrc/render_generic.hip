@@ -145,8 +145,35 @@ SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &) { return q; }
 SKR_DEV ShadeRays query_of(const TriShadows &) { return ShadeRays{}; }
 SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts) { return ts; }
 SKR_DEV TriShadows shadows_of(const TriShadows &ts) { return ts; }
+// the packs of the instances with the sphere tree: [ShadeRays] [TriShadows] SphereTree
+SKR_DEV ShadeRays query_of(const ShadeRays &q, const SphereTree &) { return q; }
+SKR_DEV ShadeRays query_of(const SphereTree &) { return ShadeRays{}; }
+SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &, const SphereTree &) { return q; }
+SKR_DEV ShadeRays query_of(const TriShadows &, const SphereTree &) { return ShadeRays{}; }
+SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts, const SphereTree &) { return ts; }
+SKR_DEV TriShadows shadows_of(const TriShadows &ts, const SphereTree &) { return ts; }
+SKR_DEV const SphereTree &stree_of(const SphereTree &st) { return st; }
+template <typename U, typename... R>
+SKR_DEV const SphereTree &stree_of(const U &, const R &...rest) { return stree_of(rest...); }
 template <typename T, typename... Q>
 constexpr bool pack_has = (std::is_same<T, Q>::value || ...);
+
+// The scene of an instance with the sphere tree: the lights staged into LDS, the sphere rows and materials where they lie in HBM, in
+// file order (surface codes are file indices) — surface_material, child_of and the fog term read them by per-lane index, and the
+// loops over every sphere (a wave the tree does not hold for) by wave-uniform index.  No LDS need depends on the sphere count.
+SKR_DEV SceneView stage_lights(const RenderParams &p, float4 *lds4, bool tris)
+{
+	for(int i = threadIdx.x; i < 2 * p.n_lights; i += 256) lds4[i] = p.lights[i];
+	__syncthreads();
+	return SceneView{p.sph_geom, p.sph_amb, p.sph_kd, p.sph_ks, lds4, p.tris, p.n_spheres, tris ? p.n_tris : 0, p.n_lights, p.tri_chunks, p.n_tri_chunks, p.tri_chunk_size,
+					 p.tri_cones, p.tri_work, p.sph_geom, nullptr, 0.0f, 0u};
+}
+template <bool STREE>
+SKR_DEV SceneView stage_for(const RenderParams &p, float4 *lds4)
+{
+	if constexpr(STREE) return stage_lights(p, lds4, true);
+	else return stage_scene(p, lds4, true);
+}
 
 // The tree a wave of query rays walks (wave_common.h pick_query_tree): at level 1 the renderer's tree where every lane
 // starts at the scene camera, else the trace tree where every lane starts in its ball; at a level below (origins on surfaces) the
@@ -225,14 +252,14 @@ struct TriangleShadows {
 template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, const Q... qs)
 {
-	constexpr bool RAYS = sizeof...(Q) > 0;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>;
 	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t A = p.g_arity; // children per node of the level above (1 at the camera level)
 	const uint64_t n_rays = (uint64_t) *p.nd_count * A;
 	if((uint64_t) blockIdx.x * 256u >= n_rays) return; // (uniform per workgroup)
-	const SceneView sv = stage_scene(p, lds4, true);
+	const SceneView sv = stage_for<STREE>(p, lds4);
 	const int tid = threadIdx.x, lane = tid & 63;
 	Counters cn{0, 0, 0};
 	for(uint32_t blk = blockIdx.x; (uint64_t) blk * 256u < n_rays; blk += gridDim.x)
@@ -283,7 +310,9 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 			cn.rays++;
 			const RayConst r = make_ray(ch.o, ch.d);
 			float tmin;
-			int sph = closest_sphere(sv, r, tmin); // raytrace.h:152-165
+			int sph; // raytrace.h:152-165
+			if constexpr(STREE) sph = stree_closest(stree_of(qs...), sv, r, tmin);
+			else sph = closest_sphere(sv, r, tmin);
 			float tcut = tmin;
 			if constexpr(RAYS)
 			{ // include/skr.h skr_shade_rays `tmax`: the winner is cut where it lies at or beyond tmax (a triangle only wins below the cut)
@@ -380,7 +409,7 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
-	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>;
 	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -391,7 +420,7 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 	__shared__ uint32_t s_pre[SKR_PREFIX_WORDS];
 	region_prefix(p, s_pre, blockIdx.x == 0); // (workgroup 0 leaves the level's record count for the kernels that follow)
 	if(pos0 >= cnt) return;
-	const SceneView sv = stage_scene(p, lds4, true);
+	const SceneView sv = stage_for<STREE>(p, lds4);
 	const uint32_t pos = pos0 + threadIdx.x;
 	const bool act = pos < cnt;
 	const uint32_t rec = region * p.rc_cap + pos;
@@ -447,7 +476,18 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		}
 		else n.N = normalize3(n.P - ld3(sv.geom[surf])); // :205
 		cn.hits++;
-		if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn);
+		if constexpr(STREE)
+		{ // the sphere test of every pair of lights is the tree's pair walk
+			const SphereTreeShadows ss{stree_of(qs...)};
+			if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn, ss);
+			else if constexpr(TSHADOW)
+			{
+				const TriShadows ts = shadows_of(qs...);
+				n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, TriangleShadows{sv, ts.trees, n.file}, ss);
+			}
+			else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, NoTriangleShadows(), ss);
+		}
+		else if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn);
 		else if constexpr(TSHADOW)
 		{
 			const TriShadows ts = shadows_of(qs...);
@@ -478,13 +518,13 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p, const Q... qs)
 {
-	constexpr bool RAYS = sizeof...(Q) > 0;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>;
 	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t n_nodes = *p.nd_count;
 	if((uint32_t) blockIdx.x * 256u >= n_nodes) return;
-	const SceneView sv = stage_scene(p, lds4, true);
+	const SceneView sv = stage_for<STREE>(p, lds4);
 	const uint32_t node = (uint32_t) blockIdx.x * 256u + threadIdx.x;
 	if(node >= n_nodes) return;
 	const uint32_t A = p.g_arity;
@@ -556,15 +596,16 @@ static bool gplan_for(const RenderParams &p, uint32_t rows, GPlan &pl)
 static uint64_t g_budget(const RenderParams &p) { return p.sw.budget_mb ? (uint64_t) p.sw.budget_mb << 20 : 6ull << 30; }
 
 // the largest band of output rows whose worst-case tables fit the budget (< 65536 spheres, < 2^30 triangles); false: not even one row
-bool skr_generic_plan(const RenderParams &p, GPlan &pl)
-{
-	if(p.n_spheres >= 65536 || p.n_tris >= (1 << 30)) return false;
+bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
+{ // (with the sphere tree the surface code's 31 bits bound the sphere count: an int32_t holds no more)
+	if((p.n_spheres >= 65536 && !sphere_tree) || p.n_tris >= (1 << 30)) return false;
 	const uint64_t budget = g_budget(p);
 	const uint32_t rows = skr_largest_band(p.out_rows, [&](uint32_t r) { return gplan_for(p, r, pl) && pl.total <= budget; });
 	return rows > 0 && gplan_for(p, rows, pl);
 }
 
-hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q_in, const TriShadows *ts_in)
+hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q_in, const TriShadows *ts_in,
+							  const SphereTree *st_in)
 {
 	if(ts_in && p_in.n_fog > 0) return hipErrorInvalidValue; // (triangle shadows need shade_triangles, which fog excludes: api.cpp launch_params)
 	RenderParams p = p_in;
@@ -573,7 +614,7 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 	auto lvl_ctr = [&](int L) { return ctr0 + SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) L; };
 	const int nsamp = (p.grid_size > 0 && !q_in) ? p.grid_size * p.grid_size : 1; // (a query: the one sample p.aa_index)
 	ShadeRays q = q_in ? *q_in : ShadeRays{};
-	const size_t lds = skr_scene_lds_bytes(p) + 32;
+	const size_t lds = (st_in ? skr_lights_lds_bytes(p) : skr_scene_lds_bytes(p)) + 32;
 	const uint32_t A = skr_tree_arity(p);
 	const int D = pl.levels;
 	hipError_t e = hipSuccess;
@@ -610,13 +651,24 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.ixh = reinterpret_cast<uint4 *>(base + pl.off_hdr[L]);
 				const uint64_t wg_t = (pl.nodes_max[L - 1] * (uint64_t) p.g_arity + 255) / 256;
 				const unsigned grid_t = (unsigned) (wg_t < 49152u ? wg_t : 49152u);
-				if(q_in) hipLaunchKernelGGL(skr_gtrace_kernel<ShadeRays>, dim3(grid_t), dim3(256), lds, stream, p, q);
+				if(st_in && q_in) hipLaunchKernelGGL((skr_gtrace_kernel<ShadeRays, SphereTree>), dim3(grid_t), dim3(256), lds, stream, p, q, *st_in);
+				else if(st_in) hipLaunchKernelGGL(skr_gtrace_kernel<SphereTree>, dim3(grid_t), dim3(256), lds, stream, p, *st_in);
+				else if(q_in) hipLaunchKernelGGL(skr_gtrace_kernel<ShadeRays>, dim3(grid_t), dim3(256), lds, stream, p, q);
 				else hipLaunchKernelGGL(skr_gtrace_kernel<>, dim3(grid_t), dim3(256), lds, stream, p);
 				p.g_arity = A; // (node ids of this level's hits: parent id * A + child + 1)
 				p.g_nodes_dst = L < D ? reinterpret_cast<float4 *>(base + pl.off_nodes[L]) : nullptr;
 				p.res_out = reinterpret_cast<float *>(base + pl.off_res[L]);
 				const unsigned grid_a = SKR_P1_REGIONS * ((pl.cap[L] + 255u) / 256u);
-				if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in);
+				if(st_in)
+				{ // the instances with the sphere tree's pair walk
+					if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in, *st_in);
+					else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in, *st_in);
+					else if(q_in && p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, ShadeRays, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, q, *st_in);
+					else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, q, *st_in);
+					else if(p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *st_in);
+					else hipLaunchKernelGGL((skr_gactivate_kernel<false, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *st_in);
+				}
+				else if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in);
 				else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in);
 				else if(q_in && p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
 				else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
@@ -633,7 +685,9 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.res_in = reinterpret_cast<const float *>(base + pl.off_res[L + 1]);
 				p.res_out = L == 0 ? nullptr : reinterpret_cast<float *>(base + pl.off_res[L]);
 				const dim3 grid_f((unsigned) ((pl.nodes_max[L] + 255) / 256));
-				if(q_in) hipLaunchKernelGGL(skr_gfinalize_kernel<ShadeRays>, grid_f, dim3(256), lds, stream, p, q);
+				if(st_in && q_in) hipLaunchKernelGGL((skr_gfinalize_kernel<ShadeRays, SphereTree>), grid_f, dim3(256), lds, stream, p, q, *st_in);
+				else if(st_in) hipLaunchKernelGGL(skr_gfinalize_kernel<SphereTree>, grid_f, dim3(256), lds, stream, p, *st_in);
+				else if(q_in) hipLaunchKernelGGL(skr_gfinalize_kernel<ShadeRays>, grid_f, dim3(256), lds, stream, p, q);
 				else hipLaunchKernelGGL(skr_gfinalize_kernel<>, grid_f, dim3(256), lds, stream, p);
 			}
 			if(timed) skr_hook_stop(hook, stream);

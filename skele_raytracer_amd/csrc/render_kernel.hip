@@ -42,9 +42,20 @@ static size_t direct_lds_bytes(const RenderParams &p)
 // A launch is refused (api.cpp render_pass: lp.lds_bytes > the device's LDS) only where no path fits.
 // SKR_PIPELINE=generic forces the general pipeline for every launch, SKR_PIPELINE=nodes keeps triangle meshes on the node pipeline
 // (tests, A/B runs).
-bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp)
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree)
 {
 	lp = LaunchPlan();
+	if(sphere_tree)
+	{ // the sphere tree: every frame on the general level pipeline's instances with the sphere walks
+		lp.path = SKR_PATH_GENERIC;
+		lp.variant = "level_pipeline_g1_stree";
+		lp.sphere_tree = true;
+		if(!skr_generic_plan(p, lp.generic, true)) return false;
+		lp.scratch_bytes = lp.generic.total;
+		lp.lds_bytes = skr_lights_kernels_lds(p);
+		if(p.grid_size > 0) lp.acc_bytes = (size_t) p.width * p.out_rows * 12;
+		return true;
+	}
 	const bool generic_only = p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0;
 	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
@@ -74,7 +85,8 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp)
 
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)
 {
-	if(lp.path == SKR_PATH_GENERIC) return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook, nullptr, lp.tri_shadows ? &lp.shadows : nullptr) : hipErrorInvalidValue;
+	if(lp.path == SKR_PATH_GENERIC)
+		return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook, nullptr, lp.tri_shadows ? &lp.shadows : nullptr, lp.sphere_tree ? &lp.stree : nullptr) : hipErrorInvalidValue;
 	if(lp.path == SKR_PATH_NODES) return p.node_scratch ? skr_launch_nodes(p, lp.nodes, stream, hook) : hipErrorInvalidValue;
 	if(p.n_spheres >= 65536) return hipErrorInvalidValue; // (one launch, no tree: any scene the LDS holds)
 	skr_hook_start(hook, stream);

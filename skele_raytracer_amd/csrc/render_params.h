@@ -30,7 +30,7 @@ struct SkrSwitches {
 	int8_t no_cones = 0, no_cull = 0;  // SKR_NO_CONES, SKR_NO_CULL: triangle-walk culling off  (four quarters of one word: the struct stays 20 bytes, so that
 	                                   // every field of RenderParams behind it keeps its offset and the kernels that never read the switches their code)
 	int8_t primary_cache = 1;          // SKR_PRIMARY_CACHE = 1 | 0: frames of one camera replay the node pipeline's level-0 stage / every frame runs skr_primary_kernel
-	int8_t reserved = 0;
+	int8_t no_sphere_cull = 0;         // SKR_NO_SPHERE_CULL: a renderer on the sphere tree runs the loop over every sphere in every wave (the A/B arm of DESIGN.md 8.10)
 	int32_t budget_mb = 0;            // SKR_LEVELS_BUDGET_MB: scratch budget of the level pipelines (0 = default)
 	int32_t flat = 0;                 // SKR_FLAT = 1 | 0: the node pipeline's flat schedule forced on (+1) / off (-1); unset: by launch size
 	int8_t shadow_mask = 1;           // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
@@ -129,6 +129,21 @@ struct RenderParams {
 	// SKR_GI_SURFACE_HEAD words per sphere, then the patch index words; their rows continue the grids' rows of gi_masks.  null = the
 	// grids only.
 	const uint32_t *gi_surface;
+};
+
+// The sphere tree (include/skr.h skr_scene_set_sphere_tree): what the sphere walks of the general level pipeline read
+// (shade_common.h stree_walk), handed to the instances that have the walks in a kernel argument of their own — RenderParams, and with it
+// the code of every kernel that takes only it, stays as it was.  All tables sit in the scene blob (HBM, never written by a kernel).
+struct SphereTree {
+	const float4 *nodes;  // 2 rows per node, depth-first: {centre, R^2} {kappa, skip, first chunk (height 1: it has the next 8, or those left; else -1), smallest file index below}; + a pad node
+	const float4 *chunks; // 3 rows per chunk: {centre, R^2} {kappa, smallest file index, first sphere row, spheres} {their file indices}; + a pad chunk
+	const float4 *rows;   // the spheres {centre, r^2} in device order: the always-tested ones, then Morton order
+	int32_t n_nodes;      // nodes of the tree over the chunks behind the always-tested ones (0: there are none)
+	int32_t n_chunks;     // chunks in all
+	int32_t n_always;     // chunks at the front that every ray tests (no culling sphere holds them)
+	int32_t cull;         // 0: every wave runs the loop over all spheres in file order (SKR_NO_SPHERE_CULL)
+	float4 ball;          // {centre, radius}: the walk is taken by a wave whose rays all start in it
+	unsigned long long *work; // HBM, or null (not counting): SKR_TRI_WORK_SHARDS x {culling-sphere tests, sphere tests} the walks executed
 };
 
 // Optional timing of the dominant kernel of a launch (skr_renderer_kernel_ms): the launcher records the

@@ -937,6 +937,245 @@ void skr_scene::build_triangle_chunk_level(double d_max, std::vector<skr_f4> &ou
 	out.swap(nodes);
 }
 
+// Exact-preserving culling data for the sphere walks.
+//
+// A sphere {c, r^2} is a candidate for the ray (o, d) where the binary32 D = fl(b b - 4a c') of utils.h:113-121 is >= 0 (and b < 0), with
+// e = fl(o - c), b = 2 fl(d . e), c' = fl(fl(e . e) - r^2), a = fl(d . d).  In reals D = 4 (r^2 |d|^2 - |e x d|^2).  With u = 2^-24, every
+// three-term dot product within 3u of its sum of magnitudes and e within u of o - c, the two sides of the last (sign-exact) subtraction
+// are off by at most 9u |d|^2 |e|^2 (the square of b / 2) and u (10 |e|^2 + 5 r^2) |d|^2 (4a c'), so a candidate's line passes the
+// centre within rho, rho^2 <= r^2 (1 + 32u) + 32u |e|^2 (32 for 19 and 5: room for the second-order terms).  The slack grows with
+// |e|, the distance from the ray's origin, so it is carried to the device as a factor: an entry {C, R^2, kappa} is touched where
+//     |(C - o) x d|^2 <= (R^2 + kappa |C - o|^2) |d|^2.
+// For a member sphere at g = |C - c| with h^2 = r^2 (1 + 32u), |e| <= |C - o| + g gives |e|^2 <= 2 |C - o|^2 + 2 g^2 and the line's
+// distance from C is at most g + sqrt(h^2 + 32u |e|^2), whose square is at most
+//     (g + h)^2 + 64u (1 + g / h) g^2  +  64u (1 + g / h) |C - o|^2              (sqrt(h^2 + x) <= h + x / 2h), or
+//     (1 + s) (g + h)^2 + 2 (s + 32u) g^2  +  2 (s + 32u) |C - o|^2,  s = sqrt(32u)  (sqrt(h^2 + x) <= h + sqrt(x)),
+// whichever has the smaller factor; R^2 and kappa of an entry are the largest of its members'.  The device's own test forms the cross
+// product of rounded terms: its left side is within (1 + 3u) and 19u |C - o|^2 |d|^2 of the real one and its right side within 12u, so
+// kappa carries 19u more and both carry a relative 1e-4.  Anything that is not finite makes the radius infinite (never culled).
+namespace {
+struct SphereBound {
+	double x, y, z, R, kappa; // R: radius (before squaring); kappa: the factor of |C - o|^2
+	bool unbounded;
+};
+const double ST_U = 5.9604644775390625e-08; // 2^-24
+
+// the entry around device spheres [i0, i1) (rows: {centre, r^2})
+SphereBound sphere_bound(const std::vector<skr_f4> &rows, size_t i0, size_t i1)
+{
+	double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+	for(size_t i = i0; i < i1; i++)
+	{
+		const double r = std::sqrt((double) rows[i].w), c[3] = {rows[i].x, rows[i].y, rows[i].z};
+		for(int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], c[k] - r); hi[k] = std::max(hi[k], c[k] + r); }
+	}
+	SphereBound b{0, 0, 0, 0, 0, false};
+	// the centre is the float the device reads: every distance below is taken from it
+	b.x = (double) (float) (0.5 * (lo[0] + hi[0]));
+	b.y = (double) (float) (0.5 * (lo[1] + hi[1]));
+	b.z = (double) (float) (0.5 * (lo[2] + hi[2]));
+	const double s = std::sqrt(32 * ST_U);
+	double R2 = 0;
+	for(size_t i = i0; i < i1; i++)
+	{
+		const double dx = rows[i].x - b.x, dy = rows[i].y - b.y, dz = rows[i].z - b.z;
+		const double g = std::sqrt(dx * dx + dy * dy + dz * dz), h = std::sqrt((double) rows[i].w * (1 + 32 * ST_U));
+		const double ka = 64 * ST_U * (1 + g / h), kb = 2 * (s + 32 * ST_U);
+		double k, r2;
+		if(ka <= kb) { k = ka; r2 = (g + h) * (g + h) + ka * g * g; }
+		else { k = kb; r2 = (1 + s) * (g + h) * (g + h) + kb * g * g; }
+		if(!(r2 == r2) || !(k == k) || !(r2 < 1e300)) b.unbounded = true;
+		R2 = std::max(R2, r2);
+		b.kappa = std::max(b.kappa, k);
+	}
+	b.R = std::sqrt(R2);
+	if(!(b.x == b.x) || !(b.y == b.y) || !(b.z == b.z) || std::isinf(b.x) || std::isinf(b.y) || std::isinf(b.z)) b.unbounded = true;
+	return b;
+}
+void sphere_bound_rows(const SphereBound &b, skr_f4 &A, float &kappa)
+{
+	A = {(float) b.x, (float) b.y, (float) b.z, round_up_square(b.R * std::sqrt(1 + 1e-4), b.unbounded)};
+	const double k = (b.kappa + 19 * ST_U) * (1 + 1e-4);
+	kappa = (float) k;
+	if((double) kappa < k) kappa = std::nextafterf(kappa, INFINITY);
+	if(b.unbounded) { A.x = A.y = A.z = 0.0f; kappa = 0.0f; }
+}
+skr_f4 pack_row(float a, int32_t b, int32_t c, int32_t d)
+{
+	skr_f4 v;
+	v.x = a;
+	memcpy(&v.y, &b, 4); memcpy(&v.z, &c, 4); memcpy(&v.w, &d, 4);
+	return v;
+}
+uint64_t morton_spread(uint64_t v)
+{ // 21 bits, two zero bits between neighbours
+	v &= 0x1fffff;
+	v = (v | v << 32) & 0x1f00000000ffffull;
+	v = (v | v << 16) & 0x1f0000ff0000ffull;
+	v = (v | v << 8) & 0x100f00f00f00f00full;
+	v = (v | v << 4) & 0x10c30c30c30c30c3ull;
+	v = (v | v << 2) & 0x1249249249249249ull;
+	return v;
+}
+} // namespace
+
+void skr_build_sphere_tree(const skr_scene &sc, SkrSphereTree &t)
+{
+	t = SkrSphereTree();
+	const size_t n = sc.sph_geom.size();
+	// the ball: around the bounding box of the camera, the spheres and the mesh, twice that box's half diagonal (as the trace tree's)
+	double lo[3] = {sc.info.camera[0], sc.info.camera[1], sc.info.camera[2]}, hi[3] = {lo[0], lo[1], lo[2]};
+	auto grow = [&](double x, double y, double z, double r) {
+		const double p[3] = {x, y, z};
+		for(int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
+	};
+	for(size_t i = 0; i < n; i++) grow(sc.sph_geom[i].x, sc.sph_geom[i].y, sc.sph_geom[i].z, std::sqrt((double) sc.sph_geom[i].w));
+	for(size_t i = 0; i + 2 < sc.raw_triangles.size(); i += 3) grow(sc.raw_triangles[i], sc.raw_triangles[i + 1], sc.raw_triangles[i + 2], 0);
+	const double half = 0.5 * std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+	t.ball[0] = (float) (0.5 * (lo[0] + hi[0]));
+	t.ball[1] = (float) (0.5 * (lo[1] + hi[1]));
+	t.ball[2] = (float) (0.5 * (lo[2] + hi[2]));
+	t.ball[3] = (float) (2 * half + 1e-3);
+	// (the bounds above are relative: the ball only keeps |C - o|^2 |d|^2 far from the ends of binary32.  |d|^2 <= 2^44 on the device.)
+	if(!(t.ball[3] < 1e8f) || !(t.ball[0] == t.ball[0]) || !(t.ball[1] == t.ball[1]) || !(t.ball[2] == t.ball[2])) t.ball[3] = -1.0f; // no wave walks the tree (api.cpp sphere_tree_of: the device squares the radius, so the sign is read there)
+	// always tested: a sphere that is not finite or tiny (the relative bounds need normal numbers), and one that would blow up every
+	// entry above it — a radius beyond 8x the median radius (the 1000-radius ground spheres of the shipped scenes)
+	std::vector<double> radii(n);
+	for(size_t i = 0; i < n; i++) radii[i] = std::sqrt((double) sc.sph_geom[i].w);
+	double big = INFINITY;
+	if(n > 0)
+	{
+		std::vector<double> sorted(radii);
+		std::nth_element(sorted.begin(), sorted.begin() + n / 2, sorted.end());
+		big = 8 * sorted[n / 2];
+	}
+	std::vector<int32_t> always, rest;
+	for(size_t i = 0; i < n; i++)
+	{
+		const skr_f4 g = sc.sph_geom[i];
+		const bool finite = std::isfinite(g.x) && std::isfinite(g.y) && std::isfinite(g.z) && std::isfinite(g.w);
+		if(!finite || !(g.w >= 1e-30f) || !(radii[i] <= big)) always.push_back((int32_t) i);
+		else rest.push_back((int32_t) i);
+	}
+	{ // Morton order of the centres
+		double clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
+		for(int32_t i : rest)
+		{
+			const double c[3] = {sc.sph_geom[i].x, sc.sph_geom[i].y, sc.sph_geom[i].z};
+			for(int k = 0; k < 3; k++) { clo[k] = std::min(clo[k], c[k]); chi[k] = std::max(chi[k], c[k]); }
+		}
+		const double ext = std::max(chi[0] - clo[0], std::max(chi[1] - clo[1], chi[2] - clo[2]));
+		const double scale = ext > 0 ? 2097151.0 / ext : 0.0;
+		std::vector<std::pair<uint64_t, int32_t>> keyed;
+		keyed.reserve(rest.size());
+		for(int32_t i : rest)
+		{
+			const uint64_t x = (uint64_t) ((sc.sph_geom[i].x - clo[0]) * scale), y = (uint64_t) ((sc.sph_geom[i].y - clo[1]) * scale),
+						   z = (uint64_t) ((sc.sph_geom[i].z - clo[2]) * scale);
+			keyed.push_back({morton_spread(x) | morton_spread(y) << 1 | morton_spread(z) << 2, i});
+		}
+		std::sort(keyed.begin(), keyed.end()); // (equal codes: file order)
+		for(size_t k = 0; k < keyed.size(); k++) rest[k] = keyed[k].second;
+	}
+	for(int32_t i : always) { t.rows.push_back(sc.sph_geom[i]); t.file.push_back(i); }
+	for(int32_t i : rest) { t.rows.push_back(sc.sph_geom[i]); t.file.push_back(i); }
+	const size_t na = always.size(), CH = SKR_SPHERE_CHUNK;
+	t.n_always = (int) ((na + CH - 1) / CH);
+	const size_t n_reg = (rest.size() + CH - 1) / CH;
+	t.n_chunks = t.n_always + (int) n_reg;
+	// the chunks: rows [first, first + count), their smallest file index
+	struct Ent { SphereBound b; size_t first, last; int32_t min_index; skr_f4 A; float kappa; };
+	auto min_file = [&](size_t i0, size_t i1) { int32_t m = INT32_MAX; for(size_t i = i0; i < i1; i++) m = std::min(m, t.file[i]); return m; };
+	std::vector<Ent> chunk_ents;
+	for(int c = 0; c < t.n_chunks; c++)
+	{
+		const bool alw = c < t.n_always;
+		const size_t i0 = alw ? (size_t) c * CH : na + (size_t) (c - t.n_always) * CH, i1 = std::min(alw ? na : n, i0 + CH);
+		Ent e{};
+		e.first = i0;
+		e.last = i1;
+		e.min_index = min_file(i0, i1);
+		if(alw) e.b = SphereBound{0, 0, 0, 0, 0, true};
+		else e.b = sphere_bound(t.rows, i0, i1);
+		sphere_bound_rows(e.b, e.A, e.kappa);
+		chunk_ents.push_back(e);
+	}
+	for(const Ent &e : chunk_ents)
+	{
+		t.chunks.push_back(e.A);
+		t.chunks.push_back(pack_row(e.kappa, e.min_index, (int32_t) e.first, (int32_t) (e.last - e.first)));
+		skr_f4 f{0, 0, 0, 0};
+		int32_t fi[4] = {0, 0, 0, 0};
+		for(size_t i = e.first; i < e.last; i++) fi[i - e.first] = t.file[i];
+		memcpy(&f, fi, 16);
+		t.chunks.push_back(f);
+	}
+	t.chunks.push_back({0.0f, 0.0f, 0.0f, INFINITY});
+	t.chunks.push_back(pack_row(0.0f, INT32_MAX, 0, 0));
+	t.chunks.push_back({0.0f, 0.0f, 0.0f, 0.0f});
+	// the levels above the regular chunks: every entry bounds its own members (the slack does not pile up level by level) and holds its
+	// children's spheres
+	std::vector<std::vector<Ent>> levels(1);
+	levels[0].assign(chunk_ents.begin() + t.n_always, chunk_ents.end());
+	while(!levels[0].empty() && (levels.size() == 1 || levels.back().size() > 1))
+	{
+		const std::vector<Ent> &lo_l = levels.back();
+		std::vector<Ent> up;
+		for(size_t c0 = 0; c0 < lo_l.size(); c0 += SKR_SPHERE_SUPER)
+		{
+			const size_t c1 = std::min(lo_l.size(), c0 + SKR_SPHERE_SUPER);
+			Ent e{};
+			e.first = lo_l[c0].first;
+			e.last = lo_l[c1 - 1].last;
+			e.min_index = INT32_MAX;
+			e.b = sphere_bound(t.rows, e.first, e.last);
+			for(size_t c = c0; c < c1; c++)
+			{
+				const Ent &k = lo_l[c];
+				e.min_index = std::min(e.min_index, k.min_index);
+				e.b.unbounded = e.b.unbounded || k.b.unbounded;
+				if(!k.b.unbounded)
+				{
+					const double dx = (double) k.A.x - e.b.x, dy = (double) k.A.y - e.b.y, dz = (double) k.A.z - e.b.z;
+					e.b.R = std::max(e.b.R, (std::sqrt(dx * dx + dy * dy + dz * dz) + std::sqrt((double) k.A.w)) * (1 + 1e-6));
+				}
+				e.b.kappa = std::max(e.b.kappa, (double) k.kappa); // (not needed for exactness: a parent never culls harder than its child)
+			}
+			sphere_bound_rows(e.b, e.A, e.kappa);
+			up.push_back(e);
+		}
+		levels.push_back(up);
+	}
+	struct Emit {
+		const std::vector<std::vector<Ent>> &levels;
+		std::vector<skr_f4> &nodes;
+		int first_regular;
+		void run(int level, size_t idx)
+		{
+			const size_t me = nodes.size();
+			const Ent &e = levels[level][idx];
+			nodes.push_back(e.A);
+			nodes.push_back({0, 0, 0, 0});
+			int32_t fc = -1; // first chunk of a node of height 1 (it has the next SKR_SPHERE_SUPER chunks, or those that are left), else -1
+			if(level == 1) fc = first_regular + (int32_t) idx * SKR_SPHERE_SUPER;
+			else
+			{
+				const size_t c0 = idx * SKR_SPHERE_SUPER, c1 = std::min(levels[level - 1].size(), c0 + SKR_SPHERE_SUPER);
+				for(size_t c = c0; c < c1; c++) run(level - 1, c);
+			}
+			nodes[me + 1] = pack_row(e.kappa, (int32_t) (nodes.size() / 2), fc, e.min_index);
+		}
+	};
+	if(levels.size() > 1)
+	{
+		Emit emit{levels, t.nodes, t.n_always};
+		emit.run((int) levels.size() - 1, 0);
+	}
+	t.n_nodes = (int) (t.nodes.size() / 2);
+	t.nodes.push_back({0.0f, 0.0f, 0.0f, INFINITY});
+	t.nodes.push_back(pack_row(0.0f, t.n_nodes + 1, -1, INT32_MAX));
+}
+
 static void set_camera(skr_scene_info &info, const float p[3], const float d[3], const float u[3], float ha)
 {
 	for(int k = 0; k < 3; k++)
@@ -1164,6 +1403,7 @@ int skr_scene_create_from_scn_ex(const char *path, int echo, uint32_t flags, skr
 		return rc;
 	}
 	sc->triangle_shadows = (flags & SKR_SCN_TRIANGLE_SHADOWS) != 0;
+	sc->sphere_tree = (flags & SKR_SCN_SPHERE_TREE) != 0;
 	*out = sc;
 	return SKR_OK;
 }
@@ -1254,6 +1494,71 @@ int skr_scene_get_triangle_shadows(const skr_scene *scene, int *enabled)
 {
 	if(!scene || !enabled) return SKR_ERR_ARG;
 	*enabled = scene->triangle_shadows ? 1 : 0;
+	return SKR_OK;
+}
+
+int skr_scene_set_sphere_tree(skr_scene *scene, int enable)
+{
+	if(!scene)
+	{
+		skr_set_error("skr_scene_set_sphere_tree: null scene");
+		return SKR_ERR_ARG;
+	}
+	scene->sphere_tree = enable != 0;
+	return SKR_OK;
+}
+
+int skr_scene_get_sphere_tree(const skr_scene *scene, int *enabled)
+{
+	if(!scene || !enabled) return SKR_ERR_ARG;
+	*enabled = scene->sphere_tree ? 1 : 0;
+	return SKR_OK;
+}
+
+int skr_scene_get_sphere_tree_data(const skr_scene *scene, int32_t *chunk_size, int32_t *n_nodes, int32_t *n_chunks, int32_t *n_always,
+								   float *device_spheres, int32_t *file_index, float *node_spheres, int32_t *node_links, float *chunk_spheres,
+								   int32_t *chunk_links, float ball[4])
+{
+	if(!scene) return SKR_ERR_ARG;
+	SkrSphereTree t;
+	skr_build_sphere_tree(*scene, t);
+	if(chunk_size) *chunk_size = SKR_SPHERE_CHUNK;
+	if(n_nodes) *n_nodes = t.n_nodes;
+	if(n_chunks) *n_chunks = t.n_chunks;
+	if(n_always) *n_always = t.n_always;
+	if(ball) memcpy(ball, t.ball, 16);
+	if(device_spheres && !t.rows.empty()) memcpy(device_spheres, t.rows.data(), t.rows.size() * 16);
+	if(file_index && !t.file.empty()) memcpy(file_index, t.file.data(), t.file.size() * 4);
+	auto word = [](float f) { int32_t v; memcpy(&v, &f, 4); return v; };
+	for(int i = 0; i < t.n_nodes; i++)
+	{
+		const skr_f4 A = t.nodes[2 * (size_t) i], L = t.nodes[2 * (size_t) i + 1];
+		if(node_spheres)
+		{
+			const float row[5] = {A.x, A.y, A.z, A.w, L.x};
+			memcpy(node_spheres + 5 * (size_t) i, row, sizeof row);
+		}
+		if(node_links)
+		{
+			const int32_t fc = word(L.z), left = t.n_chunks - fc;
+			const int32_t row[4] = {word(L.y), fc < 0 ? 0 : fc, fc < 0 ? 0 : (left < SKR_SPHERE_SUPER ? left : SKR_SPHERE_SUPER), word(L.w)};
+			memcpy(node_links + 4 * (size_t) i, row, sizeof row);
+		}
+	}
+	for(int c = 0; c < t.n_chunks; c++)
+	{
+		const skr_f4 A = t.chunks[3 * (size_t) c], L = t.chunks[3 * (size_t) c + 1];
+		if(chunk_spheres)
+		{
+			const float row[5] = {A.x, A.y, A.z, A.w, L.x};
+			memcpy(chunk_spheres + 5 * (size_t) c, row, sizeof row);
+		}
+		if(chunk_links)
+		{
+			const int32_t row[3] = {word(L.y), word(L.z), word(L.w)};
+			memcpy(chunk_links + 3 * (size_t) c, row, sizeof row);
+		}
+	}
 	return SKR_OK;
 }
 

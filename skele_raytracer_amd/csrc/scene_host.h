@@ -29,6 +29,7 @@ struct skr_scene {
 	std::vector<float> raw_fog;          // [n][9] centre radius albedo scattering absorption — SKR_SCN_FOG / skr_scene_set_fog only (file order)
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
+	bool sphere_tree = false;            // SKR_SCN_SPHERE_TREE / skr_scene_set_sphere_tree: likewise
 	skr_scene_info info{};
 
 	// SoA arrays as uploaded (built by finalize())
@@ -83,6 +84,21 @@ struct skr_scene {
 	uint32_t gi_rows = 0; // rows of masks of the grids in gi_table
 	void build_gi_surface();
 };
+
+// The sphere tree (include/skr.h skr_scene_set_sphere_tree) in the layout of render_params.h SphereTree.  Built on
+// demand (a renderer of a scene with the switch on; skr_scene_get_sphere_tree_data), not by finalize(): a scene without the switch
+// does not pay for it.
+#define SKR_SPHERE_CHUNK 4 // spheres per chunk: the file indices of a chunk fill one row
+#define SKR_SPHERE_SUPER 8 // children per node
+struct SkrSphereTree {
+	int n_nodes = 0, n_chunks = 0, n_always = 0; // n_always: chunks of always-tested spheres, at the front
+	std::vector<skr_f4> rows;    // n_spheres rows {centre, r^2} in device order
+	std::vector<int32_t> file;   // their file indices
+	std::vector<skr_f4> nodes;   // 2 per node + a pad node
+	std::vector<skr_f4> chunks;  // 3 per chunk + a pad chunk
+	float ball[4] = {0.0f, 0.0f, 0.0f, -1.0f};
+};
+void skr_build_sphere_tree(const skr_scene &scene, SkrSphereTree &out);
 
 // scene.cpp:12-227 replacement.  Returns SKR_OK or SKR_ERR_IO.
 int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene &out);

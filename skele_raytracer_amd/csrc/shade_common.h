@@ -477,6 +477,213 @@ SKR_DEV uint32_t shadow_cands(const SceneView &sv, const RenderParams &p, int i,
 	return second ? m0 | shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P) : m0;
 }
 
+// ---- the sphere tree (include/skr.h skr_scene_set_sphere_tree; scene_host.cpp skr_build_sphere_tree) ----
+// The conservative line test of an entry {C, R^2} with its slack factor kappa: false only where no sphere below the entry can be a
+// candidate (binary32 D >= 0) of this lane's line.  The slack of D grows with the distance of the ray's origin, so it is a factor of
+// |C - o|^2 and not a part of the radius.  NaN anywhere => true.
+SKR_DEV bool sphere_entry_touched(f3 o, f3 d, float dd, float4 A, float kappa)
+{
+	const f3 e = ld3(A) - o;
+	const f3 cr = cross3(e, d);
+	return !(dot3(cr, cr) > (A.w + kappa * dot3(e, e)) * dd);
+}
+
+SKR_DEV void sphere_work_add(const SphereTree &st, uint32_t n_cull, uint32_t n_sph)
+{
+	if(st.work && (n_cull | n_sph))
+	{
+		const unsigned long long m = __ballot(true);
+		if(__builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u)) == 0)
+		{
+			unsigned long long *w = st.work + 2u * ((blockIdx.x * 4u + (threadIdx.x >> 6)) & (SKR_TRI_WORK_SHARDS - 1u));
+			atomicAdd(&w[0], (unsigned long long) n_cull);
+			atomicAdd(&w[1], (unsigned long long) n_sph);
+		}
+	}
+}
+// lanes x rays of a mask of up to two rays per lane (wave-uniform: scalar registers)
+SKR_DEV uint32_t lanes_of(uint32_t mask) { return (uint32_t) __popcll(__ballot((mask & 1u) != 0u)) + (uint32_t) __popcll(__ballot((mask & 2u) != 0u)); }
+
+// The walk of tree_walk() over the sphere tree: one wave-uniform index over the depth-first nodes, no stack, rows through the scalar
+// cache; both successors of a node are fetched while its culling sphere is tested.  `live()` = the rays of the lane (a bit each) that
+// still want tests; `touch(A, kappa, smallest file index below)` = those of them that want this entry: an entry is entered when any
+// lane wants it, and `sphere(row, file index, mine)` sees every sphere of a chunk some lane wants, with the bits of its own lane.
+// The always-tested chunks at the front come first, without a culling test.
+template <bool COUNT, typename V, typename T, typename S>
+SKR_DEV void stree_walk(const SphereTree &st, V live, T touch, S sphere)
+{
+	uint32_t n_cull = 0, n_sph = 0;
+	auto chunk_spheres = [&](int c, float4 cL, uint32_t mine)
+	{
+		const int i0 = __float_as_int(cL.z), cnt = __float_as_int(cL.w);
+		const float4 fi = mesh_row(st.chunks, 3 * c + 2);
+		const int file[4] = {__float_as_int(fi.x), __float_as_int(fi.y), __float_as_int(fi.z), __float_as_int(fi.w)};
+		float4 g[4];
+#pragma unroll
+		for(int k = 0; k < 4; k++) g[k] = mesh_row(st.rows, i0 + k); // (the rows behind the last sphere are the blob's: readable)
+#pragma unroll
+		for(int k = 0; k < 4; k++)
+			if(k < cnt)
+			{
+				if(COUNT) n_sph += lanes_of(mine);
+				sphere(g[k], file[k], mine);
+			}
+	};
+	for(int c = 0; c < st.n_always; c++) chunk_spheres(c, mesh_row(st.chunks, 3 * c + 1), live());
+	int i = 0;
+	float4 A = mesh_row(st.nodes, 0), L = mesh_row(st.nodes, 1);
+	while(i < st.n_nodes)
+	{
+		const int i_out = __float_as_int(L.y);
+		const float4 A_in = mesh_row(st.nodes, 2 * i + 2), L_in = mesh_row(st.nodes, 2 * i + 3);
+		const float4 A_out = mesh_row(st.nodes, 2 * i_out), L_out = mesh_row(st.nodes, 2 * i_out + 1);
+		if(COUNT) n_cull += lanes_of(live());
+		const bool enter = __any(touch(A, L.x, __float_as_int(L.w)) != 0u);
+		const int c0 = __float_as_int(L.z);
+		if(enter && c0 >= 0)
+		{ // height 1: its chunk entries are contiguous
+			const int c1 = c0 + 8 < st.n_chunks ? c0 + 8 : st.n_chunks;
+			float4 cA_next = mesh_row(st.chunks, 3 * c0), cL_next = mesh_row(st.chunks, 3 * c0 + 1);
+			for(int c = c0; c < c1; c++)
+			{
+				const float4 cA = cA_next, cL = cL_next;
+				cA_next = mesh_row(st.chunks, 3 * c + 3);
+				cL_next = mesh_row(st.chunks, 3 * c + 4);
+				if(COUNT) n_cull += lanes_of(live());
+				const uint32_t mine = touch(cA, cL.x, __float_as_int(cL.y));
+				if(__any(mine != 0u)) chunk_spheres(c, cL, mine);
+			}
+		}
+		i = enter ? i + 1 : i_out;
+		A = enter ? A_in : A_out;
+		L = enter ? L_in : L_out;
+	}
+	if(COUNT) sphere_work_add(st, n_cull, n_sph);
+}
+
+// does a wave whose lanes are all here walk the tree: every lane's origin in the ball, every direction of a length the bounds hold for
+SKR_DEV bool stree_lane_fits(const SphereTree &st, f3 o, float dd)
+{
+	const f3 e = o - mk3(st.ball.x, st.ball.y, st.ball.z);
+	return (dot3(e, e) <= st.ball.w * st.ball.w) && (dd >= 0x1p-44f) && (dd <= 0x1p44f); // (NaN: no)
+}
+
+// closest_sphere() on the tree (raytrace.h:152-165): the smallest t2 wins, equal t2 goes to the lower file index; the index returned is
+// the file's.  The brackets of the candidates the walk meets are selected as closest_of_rows selects them — the outcome does not
+// depend on the order where the winner's bracket lies strictly below every other's —; where brackets overlap a second walk evaluates the
+// exact form of every candidate of the lanes concerned (every accepted sphere is a candidate: t2 > 1 needs D >= 0 and b < 0).
+template <bool COUNT>
+SKR_DEV int stree_closest_walk(const SphereTree &st, const RayConst &r, float &tmin)
+{
+	const RayFilt f = make_filt(r.d);
+	const float dd = r.two_a * 0.5f; // dot(d, d)
+	int best = -1;
+	float best_lo = __builtin_inff(), best_hi = __builtin_inff(), others_lo = __builtin_inff();
+	float best_b = 0.0f, best_D = 0.0f;
+	stree_walk<COUNT>(st, [] { return 1u; },
+		[&](const float4 A, float kappa, int) { return sphere_entry_touched(r.o, r.d, dd, A, kappa) ? 1u : 0u; },
+		[&](const float4 g, int file, uint32_t mine)
+		{
+			float lo, hi, b, D;
+			if(mine && sphere_bracket(r.o, r.d, f, g, lo, hi, b, D)) best_update(best_hi, others_lo, best_lo, best, best_b, best_D, file, lo, hi, b, D);
+		});
+	tmin = __builtin_inff();
+	const bool unsure = best >= 0 && !(others_lo > best_hi);
+	if(best >= 0 && !unsure) tmin = bracket_t(f.two_a, best_lo, best_hi, best_b, best_D);
+	if(__any(unsure))
+	{
+		int eb = -1;
+		float et = __builtin_inff();
+		stree_walk<COUNT>(st, [&] { return unsure ? 1u : 0u; },
+			[&](const float4 A, float kappa, int) { return (unsure && sphere_entry_touched(r.o, r.d, dd, A, kappa)) ? 1u : 0u; },
+			[&](const float4 g, int file, uint32_t mine)
+			{
+				if(!mine) return;
+				const float t = sphere_distance(r.o, r.d, r.two_a, r.four_a, g);
+				if(accept_distance(t) && (t < et || (t == et && file < eb)))
+				{
+					et = t;
+					eb = file;
+				}
+			});
+		if(unsure)
+		{
+			best = eb;
+			tmin = et;
+		}
+	}
+	return best;
+}
+// (every lane of the wave that traces a ray arrives here: the choice between the walk and the loop is wave-wide)
+SKR_DEV int stree_closest(const SphereTree &st, const SceneView &sv, const RayConst &r, float &tmin)
+{
+	if(!st.cull || !__all(stree_lane_fits(st, r.o, r.two_a * 0.5f))) return closest_sphere(sv, r, tmin); // every row in file order, from HBM
+	if(__builtin_expect(st.work != nullptr, 0)) return stree_closest_walk<true>(st, r, tmin);
+	return stree_closest_walk<false>(st, r, tmin);
+}
+
+// occluded_pair() on the tree (utils.h:42-58).  The reference's loop stops at its first occluder in file order and `tests` counts the
+// spheres up to it, so the walk looks for the LOWEST file index among each ray's occluders: it cannot stop at the first one it meets,
+// but a ray wants neither a sphere nor an entry whose smallest file index is not below the best it has.
+template <bool COUNT>
+SKR_DEV void stree_occluded_walk(const SphereTree &st, f3 o, const RayPair &rp, f3 L0, f3 L1, bool second, int &idx0, int &idx1)
+{
+	const PairAny pa = make_pair_any(rp);
+	const float dd0 = rp.two_a.x * 0.5f, dd1 = rp.two_a.y * 0.5f;
+	constexpr int none = 0x7fffffff;
+	idx0 = none;
+	idx1 = second ? none : -1;
+	stree_walk<COUNT>(st, [&] { return (idx0 > 0 ? 1u : 0u) | (idx1 > 0 ? 2u : 0u); },
+		[&](const float4 A, float kappa, int low)
+		{
+			const uint32_t m0 = (low < idx0 && sphere_entry_touched(o, L0, dd0, A, kappa)) ? 1u : 0u;
+			const uint32_t m1 = (low < idx1 && sphere_entry_touched(o, L1, dd1, A, kappa)) ? 2u : 0u;
+			return m0 | m1;
+		},
+		[&](const float4 g, int file, uint32_t mine)
+		{
+			const bool w0 = (mine & 1u) && file < idx0, w1 = (mine & 2u) && file < idx1;
+			if(!(w0 || w1)) return;
+			const f3 e = o - ld3(g);
+			const float c = dot3(e, e) - g.w;
+			f2 b, D;
+			pair_bD(rp, e, c, b, D);
+			const bool cand0 = w0 && (D.x >= 0.0f) && (b.x < 0.0f), cand1 = w1 && (D.y >= 0.0f) && (b.y < 0.0f);
+			if(cand0 || cand1)
+			{
+				f2 m, al, rl;
+				pair_any_m(pa, b, m, al, rl);
+				if(cand0 && any_decide(pa.sane0, pa.two_a.x, pa.quarter.x, b.x, D.x, m.x, al.x, rl.x)) idx0 = file;
+				if(cand1 && any_decide(pa.sane1, pa.two_a.y, pa.quarter.y, b.y, D.y, m.y, al.y, rl.y)) idx1 = file;
+			}
+		});
+}
+
+// the sphere test of direct_light_of on the tree (SphereLoopShadows' counterpart); a wave with a lane the tree does not hold for runs
+// occluded_pair's loop over every row in file order, from HBM (the instances with the tree have no shadow masks)
+struct SphereTreeShadows {
+	const SphereTree &st;
+	static constexpr bool loops = false;
+	__device__ __forceinline__ void pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second, bool &occ0, bool &occ1, uint32_t &tests) const
+	{
+		const f3 o = add_scalar(P, 0.000001f);
+		const RayPair rp = make_pair(L0, L1);
+		const bool fits = stree_lane_fits(st, o, rp.two_a.x * 0.5f) && (!second || stree_lane_fits(st, o, rp.two_a.y * 0.5f));
+		if(!st.cull || !__all(fits))
+		{
+			occluded_pair<false>(sv, P, L0, L1, second, occ0, occ1, tests, 0u);
+			return;
+		}
+		int idx0, idx1;
+		if(__builtin_expect(st.work != nullptr, 0)) stree_occluded_walk<true>(st, o, rp, L0, L1, second, idx0, idx1);
+		else stree_occluded_walk<false>(st, o, rp, L0, L1, second, idx0, idx1);
+		occ0 = idx0 != 0x7fffffff;
+		occ1 = second && idx1 != 0x7fffffff;
+		tests += occ0 ? (uint32_t) idx0 + 1u : (uint32_t) sv.ns;
+		if(second) tests += occ1 ? (uint32_t) idx1 + 1u : (uint32_t) sv.ns;
+	}
+};
+
 struct LightTerm { // the per-light quantities of blinn_phong.h:67-72 / :100-117
 	f3 L, lc;
 	float intensity; // 1 / powf(|Lp - P|, 2) (== 1 / (d * d): SURVEY.md 8c); exactly 1 for a directional light
@@ -506,27 +713,36 @@ struct NoTriangleShadows {
 	static constexpr bool on = false;
 };
 
+// How direct_light_of tests the spheres against the shadow rays of a pair of lights: the loops over the sphere table (occluded_pair, with
+// the shadow masks where the launch has them), or the sphere tree's pair walk (SphereTreeShadows below).  Chosen at compile time, so
+// that the instances on the loops keep their code.
+struct SphereLoopShadows {
+	static constexpr bool loops = true;
+};
+
 // raytrace.h:36-44 = bp::ambient (blinn_phong.h:13) + diffuse (:47) + specular (:90).
 // The reference casts the same shadow ray in diffuse and again in specular; one cast serves both.
 // (kd, ks, ambp = {La * ka, power}: the material rows of the surface hit)
 // TS: triangle shadows (include/skr.h skr_scene_set_triangle_shadows) — `tri_shadows(P, i, second, L0, L1, occ0, occ1)` darkens the lights of a
 // pair that the spheres left lit and a triangle occludes (render_generic.hip TriangleShadows); chosen at compile time, so that the
 // instances without it keep their code.
-template <bool COHERENT, typename TS = NoTriangleShadows>
-SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn, const TS &tri_shadows = TS())
+template <bool COHERENT, typename TS = NoTriangleShadows, typename SS = SphereLoopShadows>
+SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn, const TS &tri_shadows = TS(),
+						   const SS &sphere_shadows = SS())
 {
 	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
 	const f3 view = normalize3(p.cam_pos - P); // always the camera (blinn_phong.h:93)
 	for(int i = 0; i < sv.nl; i += 2)
 	{
 		const bool second = i + 1 < sv.nl;
-		const uint32_t cand = shadow_cands<COHERENT>(sv, p, i, second, P); // (asked for ahead of the light terms)
+		const uint32_t cand = SS::loops ? shadow_cands<COHERENT>(sv, p, i, second, P) : 0u; // (asked for ahead of the light terms)
 		const LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
 		bool occ0 = false, occ1 = false;
 		if(p.use_shadows)
 		{
 			cn.shadow_rays += second ? 2u : 1u;
-			occluded_pair<COHERENT>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
+			if constexpr(SS::loops) occluded_pair<COHERENT>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
+			else sphere_shadows.pair(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests);
 			if constexpr(TS::on) tri_shadows(P, i, second, t0.L, t1.L, occ0, occ1);
 		}
 		auto add_light = [&](const LightTerm &t, bool lit)
@@ -576,21 +792,23 @@ SKR_DEV f3 fog_term(float4 a, float4 alb, const LightTerm &t, f3 centre, f3 lpos
 // direct_light_of() for a sphere hit of a scene with fog (blinn_phong.h:47-134): every lit point light adds the fog term of every fog
 // volume, in file order, INSTEAD of its diffuse term, and again instead of its specular term; directional lights and the ambient term
 // are unchanged.  (pixel, node): the node's counter words (DESIGN.md "Counter RNG").
+template <typename SS = SphereLoopShadows>
 SKR_DEV f3 direct_light_fog(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, f3 centre, uint32_t pixel,
-							uint32_t node, Counters &cn)
+							uint32_t node, Counters &cn, const SS &sphere_shadows = SS())
 {
 	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
 	const f3 view = normalize3(p.cam_pos - P);
 	for(int i = 0; i < sv.nl; i += 2)
 	{
 		const bool second = i + 1 < sv.nl;
-		const uint32_t cand = shadow_cands<false>(sv, p, i, second, P);
+		const uint32_t cand = SS::loops ? shadow_cands<false>(sv, p, i, second, P) : 0u;
 		const LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
 		bool occ0 = false, occ1 = false;
 		if(p.use_shadows)
 		{
 			cn.shadow_rays += second ? 2u : 1u;
-			occluded_pair<false>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
+			if constexpr(SS::loops) occluded_pair<false>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
+			else sphere_shadows.pair(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests);
 		}
 		auto add_light = [&](const LightTerm &t, int l, bool lit)
 		{

@@ -55,6 +55,31 @@ SKR_DEV bool any_sphere_before(const SceneView &sv, const RayConst &r, float tma
 	return occ;
 }
 
+SKR_DEV float4 sphere_ball_of(const SphereTree &st) { return st.ball; }
+
+// any_sphere_before() on the sphere tree: every sphere the lane's line may touch, in the tree's order — the answer is a
+// disjunction of per-sphere decisions, each of them exact, so the order does not matter.  A lane stops wanting entries once it is decided.
+// A wave with a lane the tree does not hold for (outside the ball, a direction that is not finite) runs the loop over every sphere.
+SKR_DEV bool any_sphere_before_tree(const SphereTree &st, const SceneView &sv, const RayConst &r, float tmax)
+{
+	const float dd = r.two_a * 0.5f;
+	if(!st.cull || !__all(stree_lane_fits(st, r.o, dd))) return any_sphere_before(sv, r, tmax);
+	const RayFilt f = make_filt(r.d);
+	bool occ = false;
+	stree_walk<false>(st, [&] { return occ ? 0u : 1u; },
+		[&](const float4 A, float kappa, int) { return (!occ && sphere_entry_touched(r.o, r.d, dd, A, kappa)) ? 1u : 0u; },
+		[&](const float4 g, int, uint32_t mine)
+		{
+			float lo, hi, b, D;
+			if(mine && !occ && sphere_bracket(r.o, r.d, f, g, lo, hi, b, D))
+			{
+				if(hi < tmax) occ = true;
+				else if(lo < tmax) occ = bracket_t(f.two_a, lo, hi, b, D) < tmax;
+			}
+		});
+	return occ;
+}
+
 // triangle `slot` accepted with 0 < t < tmax, not the ray's own
 SKR_DEV bool tri_before(const RayConst &r, const SceneView &sv, int slot, float tmax, int ignore)
 {
@@ -120,12 +145,21 @@ SKR_DEV bool any_triangle_before(const SceneView &sv, const RayConst &r, float t
 
 // SPH / TRI: the scene has spheres / triangles (the other search is compiled out, as skr_direct_kernel's sphere-free instance);
 // ANY: SKR_TRACE_ANY_HIT.  Lanes past n trace a ray that can hit nothing (tmax = -inf) so that the wave-wide walks stay whole.
-template <bool SPH, bool TRI, bool ANY>
-__global__ __launch_bounds__(256) void skr_ray_query_kernel(const TraceScene s, const float4 *rays, uint32_t n, void *out)
+// ST: an empty pack — the sphere searches are the loops over every sphere — or one SphereTree: they are the tree's walks (the renderer's
+// scene has the sphere tree switched on, include/skr.h skr_scene_set_sphere_tree).  The body of both kernels below.
+template <bool SPH, bool TRI, bool ANY, typename... ST>
+SKR_DEV void ray_query(const TraceScene &s, const float4 *rays, uint32_t n, void *out, const ST &...st)
 {
+	constexpr bool STREE = sizeof...(ST) > 0;
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	const bool valid = i < n;
 	float4 ra = make_float4(s.trees.ball.x, s.trees.ball.y, s.trees.ball.z, -__builtin_inff()), rb = make_float4(0.0f, 0.0f, 1.0f, __int_as_float(-1));
+	if constexpr(STREE)
+	{ // (a lane past n starts inside the sphere ball, so it never sends its wave to the loop; pick_query_tree ignores lanes that are not live,
+	  // so it need not lie in the trace ball — and a scene without a mesh has none)
+		const float4 sb = sphere_ball_of(st...);
+		ra = make_float4(sb.x, sb.y, sb.z, -__builtin_inff());
+	}
 	if(valid)
 	{
 		ra = rays[2 * (size_t) i];
@@ -139,7 +173,8 @@ __global__ __launch_bounds__(256) void skr_ray_query_kernel(const TraceScene s, 
 	if constexpr(ANY)
 	{
 		bool occ = false;
-		if(SPH) occ = any_sphere_before(sv, r, tmax);
+		if constexpr(STREE) occ = any_sphere_before_tree(st..., sv, r, tmax);
+		else if(SPH) occ = any_sphere_before(sv, r, tmax);
 		if(TRI) occ = any_triangle_before(sv, r, tmax, ignore, occ);
 		if(valid) reinterpret_cast<int32_t *>(out)[i] = occ ? 1 : 0;
 	}
@@ -147,7 +182,8 @@ __global__ __launch_bounds__(256) void skr_ray_query_kernel(const TraceScene s, 
 	{
 		float ts = __builtin_inff();
 		int sph = -1;
-		if(SPH) sph = closest_sphere(sv, r, ts);         // raytrace.h:152-165
+		if constexpr(STREE) sph = stree_closest(st..., sv, r, ts);
+		else if(SPH) sph = closest_sphere(sv, r, ts);         // raytrace.h:152-165
 		TriBest tb{__builtin_fminf(ts, tmax), -1, -1}; // the walk is cut at the sphere (it wins a tie) or at tmax, whichever is nearer
 		if(TRI) closest_triangle(sv, r, ignore, tb);
 		int kind = 0, index = -1;
@@ -178,6 +214,18 @@ __global__ __launch_bounds__(256) void skr_ray_query_kernel(const TraceScene s, 
 	}
 }
 
+template <bool SPH, bool TRI, bool ANY>
+__global__ __launch_bounds__(256) void skr_ray_query_kernel(const TraceScene s, const float4 *rays, uint32_t n, void *out)
+{
+	ray_query<SPH, TRI, ANY>(s, rays, n, out);
+}
+// the instances with the sphere tree's walks (a scene with the switch on has spheres)
+template <bool TRI, bool ANY>
+__global__ __launch_bounds__(256) void skr_ray_query_tree_kernel(const TraceScene s, const float4 *rays, uint32_t n, void *out, const SphereTree st)
+{
+	ray_query<true, TRI, ANY>(s, rays, n, out, st);
+}
+
 // The primary rays of one AA sample of a frame (include/skr.h skr_camera_rays): one lane per pixel, the direction of primary_ray().
 __global__ __launch_bounds__(256) void skr_camera_ray_kernel(const RenderParams p, float4 *rays)
 {
@@ -191,10 +239,18 @@ __global__ __launch_bounds__(256) void skr_camera_ray_kernel(const RenderParams 
 	rays[2 * i + 1] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
 }
 
-hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream)
+hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream, const SphereTree *st)
 {
 	const dim3 grid((unsigned) (((uint64_t) n + 255) / 256)), block(256);
 	const bool sph = s.ns > 0, tri = s.nt > 0;
+	if(st && sph)
+	{
+		if(tri && any_hit) hipLaunchKernelGGL((skr_ray_query_tree_kernel<true, true>), grid, block, 0, stream, s, rays, n, out, *st);
+		else if(tri) hipLaunchKernelGGL((skr_ray_query_tree_kernel<true, false>), grid, block, 0, stream, s, rays, n, out, *st);
+		else if(any_hit) hipLaunchKernelGGL((skr_ray_query_tree_kernel<false, true>), grid, block, 0, stream, s, rays, n, out, *st);
+		else hipLaunchKernelGGL((skr_ray_query_tree_kernel<false, false>), grid, block, 0, stream, s, rays, n, out, *st);
+		return hipGetLastError();
+	}
 #define SKR_TRACE_LAUNCH(S, T)                                                                                                  \
 	do                                                                                                                          \
 	{                                                                                                                           \

@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
            [--adaptive T [--adaptive-min K] [--adaptive-max N]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
@@ -13,6 +13,7 @@ The framebuffer is cut into interleaved row tiles (tile t -> rank t mod G), ever
 `skr_render_tiles` launch sequence, ONE RCCL all-gather brings the u8 tiles to every rank and rank 0 de-interleaves
 and writes the PPM (distributed.py).  The image does not depend on G: random numbers are keyed by the global pixel.
 --triangle-shadows (triangles cast shadows) needs --shade-triangles and --shadow to have an effect; it is accepted without them.
+--sphere-tree renders on the culled sphere walk (spheres in HBM, any sphere count; include/skr.h skr_scene_set_sphere_tree): the same image.
 Flags are matched like the reference does — by `strcmp` anywhere in argv, unknown tokens ignored — and usage errors
 print the reference's messages and exit with status 0 (main.cpp:381-391).  There is no CPU path.
 """
@@ -89,6 +90,8 @@ def _parse(argv):
             opt["shade_triangles"] = True
         elif a == "--triangle-shadows":
             opt["triangle_shadows"] = True
+        elif a == "--sphere-tree":
+            opt["sphere_tree"] = True
         elif a == "--legacy-reflect":
             opt["legacy_reflect"] = True
         elif a == "--progressive":
@@ -155,7 +158,8 @@ def main(argv=None):
         else:
             dist.init_process_group("nccl", device_id=dev)  # RCCL over xGMI
     try:
-        scene = skr.parse_scene(o["path"], strict=bool(o.get("strict_scn")), fog=bool(o.get("scn_fog")), triangle_shadows=bool(o.get("triangle_shadows")))
+        scene = skr.parse_scene(o["path"], strict=bool(o.get("strict_scn")), fog=bool(o.get("scn_fog")), triangle_shadows=bool(o.get("triangle_shadows")),
+                                sphere_tree=bool(o.get("sphere_tree")))
     except skr.SkrError as e:
         if rank == 0:
             print(str(e))  # scene.cpp:24: "Can't open file" on stdout, exit(0)
