@@ -30,6 +30,7 @@ extern "C" {
 #define SKR_HAS_SHADE_RAYS 1
 #define SKR_HAS_DENOISE 1    /* skr_denoise, skr_render_denoised_host: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ADAPTIVE 1   /* skr_adaptive, skr_render_adaptive(_host): an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_ADAPTIVE_DENOISE 1 /* skr_render_adaptive_var, skr_denoise_var, skr_render_adaptive_denoised_host: additions, likewise */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -538,6 +539,38 @@ int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adapt
 /* The same into HOST memory (h_rgb W*H*3 bytes, h_rgbf W*H*3 floats, h_passes W*H uint32; any may be NULL, not all three).
  * kernel_ms: device time of the whole sequence, as skr_render_progressive_host reports it. */
 int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *h_rgb, float *h_rgbf, uint32_t *h_passes, float *kernel_ms);
+
+/* ---- adaptive frames, denoised under each pixel's measured variance (new) ----
+ * The adaptive sampler knows the variance of every pixel's mean luminance; the denoiser takes it in place of its spatial estimate,
+ * which cannot tell noise from signal.  The rule (normative), all binary32 + - * / max, not contracted, divides correctly rounded,
+ * in the order written:
+ *   - Variance of the mean, of a pixel with final state S1, S2, n: n < 2: var_p = -1.0f ("not measured").  Otherwise the
+ *     expressions of the convergence test: nf = (float) n, m = S1 / nf, d = S2 / nf - m * m, v = d > 0 ? d : 0,
+ *     var_p = v / (nf - 1): the e2 the pixel was stopped on.  A NaN pass gives 0, as the stopping rule does.
+ *   - Denoiser init with a variance image d_var[H][W]: pixel q is measured iff d_var[q] >= 0 (false for NaN and negatives).  An
+ *     unmeasured pixel p takes skr_denoise's init value, the same-class 3x3 max(0, m2 - m1 * m1), unchanged.  A measured p takes
+ *     var0_p = (sum g * d_var[q]) / (sum g) over the in-image, same-class, measured q of the 3x3 window in row-major order,
+ *     g = {1/16, 1/8, 1/16; 1/8, 1/4, 1/8; 1/16, 1/8, 1/16}: each term sum += g * d_var[q], then one divide (the centre is always
+ *     in: sum g > 0).  SVGF's 3x3 variance pre-filter, applied once.
+ *   - Iterations, output and iterations == 0: skr_denoise's, with SIGMA_L = SKR_DENOISE_VAR_SIGMA_L (SIGMA_Z, EPS and the taps
+ *     are skr_denoise's).  The two sigmas are equal, so d_var == NULL or an image with no measured pixel gives skr_denoise's
+ *     output bit for bit.  A +inf entry is measured: that pixel keeps its value (no positive weight). */
+#define SKR_DENOISE_VAR_SIGMA_L 4.0f
+/* skr_render_adaptive plus d_var float[H][W], the variance of each pixel's mean luminance under the rule above; any output may be
+ * NULL, not all four.  skr_render_adaptive is this with d_var = NULL. */
+int skr_render_adaptive_var(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes, float *d_var,
+                            void *stream);
+/* skr_denoise with the DEVICE variance image d_var float[height][width] (4-byte aligned; NULL: skr_denoise itself).  skr_denoise's
+ * contract and errors; d_var must not overlap an output either.  Touches no work counter, no kernel timing and not
+ * skr_kernel_variant(). */
+int skr_denoise_var(skr_renderer *r, uint32_t width, uint32_t height, const float *d_rgbf, const skr_hit *d_hits, const float *d_var, uint32_t iterations,
+                    float *d_out_rgbf, uint8_t *d_out_rgb, void *stream);
+/* The whole sequence into HOST memory: skr_render_adaptive_var (the float means, the variance, the pass counts), the guides exactly
+ * as skr_render_denoised_host takes them (skr_trace_rays(skr_camera_rays(opt with grid_size = 0, sample 0))), then skr_denoise_var.
+ * h_rgb W*H*3 bytes and h_rgbf W*H*3 floats: the filtered frame; h_passes W*H uint32: the adaptive pass counts; any may be NULL,
+ * not all three.  The option and argument errors of both halves apply.  Synchronous.  kernel_ms: device time of the whole sequence. */
+int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf,
+                                      uint32_t *h_passes, float *kernel_ms);
 
 /* ---- image file: replaces the inline writer main.cpp:199-211 ---- */
 int skr_write_ppm(const char *path, uint32_t width, uint32_t height, const uint8_t *rgb);

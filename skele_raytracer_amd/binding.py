@@ -18,6 +18,7 @@ EXPORTED_SYMBOLS = [
     "skr_shard_tiles_per_rank", "skr_shard_deinterleave_host", "skr_shard_lpt", "skr_shard_by_cost", "skr_shard_plan", "skr_shard_deinterleave_map_host", "skr_multi_render_frame_async", "skr_multi_flush",
     "skr_trace_rays", "skr_camera_rays", "skr_shade_rays", "skr_denoise", "skr_render_denoised_host",
     "skr_adaptive_default", "skr_render_adaptive", "skr_render_adaptive_host",
+    "skr_render_adaptive_var", "skr_denoise_var", "skr_render_adaptive_denoised_host",
 ]
 
 DENOISE_ITERATIONS = 5  # include/skr.h SKR_DENOISE_ITERATIONS: Renderer.denoise's default
@@ -27,6 +28,7 @@ ADAPTIVE_MAX_PASSES = 64
 ADAPTIVE_THRESHOLD = 0.05
 ADAPTIVE_LUM_FLOOR = 0.00390625
 ADAPTIVE_PASS_LIMIT = 65535
+DENOISE_VAR_SIGMA_L = 4.0  # include/skr.h SKR_DENOISE_VAR_SIGMA_L: the luminance sigma of denoise(variance=...)
 
 
 class SkrError(RuntimeError):
@@ -167,6 +169,9 @@ def lib():
     L.skr_adaptive_default.restype = None
     L.skr_render_adaptive.argtypes = [vp, C.POINTER(COptions), C.POINTER(CAdaptive), vp, vp, vp, vp]
     L.skr_render_adaptive_host.argtypes = [vp, C.POINTER(COptions), C.POINTER(CAdaptive), vp, vp, vp, C.POINTER(C.c_float)]
+    L.skr_render_adaptive_var.argtypes = [vp, C.POINTER(COptions), C.POINTER(CAdaptive), vp, vp, vp, vp, vp]
+    L.skr_denoise_var.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp]
+    L.skr_render_adaptive_denoised_host.argtypes = [vp, C.POINTER(COptions), C.POINTER(CAdaptive), C.c_uint32, vp, vp, vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -658,11 +663,13 @@ class Renderer:
                                         out.data_ptr(), stream), "skr_shade_rays")
         return out
 
-    def denoise(self, rgbf, hits, iterations=DENOISE_ITERATIONS):
+    def denoise(self, rgbf, hits, iterations=DENOISE_ITERATIONS, variance=None):
         """The edge-aware denoiser (include/skr.h skr_denoise) on torch's current stream: rgbf float32 [H, W, 3] on this device, hits the
         guides — a Hits or its float32 raw buffer ([H * W, 8] or [H, W, 8]) of the pixel-centre camera rays of the frame's options:
         r.trace(r.camera_rays(opt_with_grid_0).view(-1, 8)), with opt_with_grid_0 = opt with jsample 0.  Returns (rgb uint8 [H, W, 3],
-        rgbf float32 [H, W, 3]) device tensors; iterations 0 .. 16, 0 = the input itself."""
+        rgbf float32 [H, W, 3]) device tensors; iterations 0 .. 16, 0 = the input itself.  variance: a float32 [H, W] tensor of each pixel's
+        measured variance of its mean luminance (render_adaptive(want_variance=True)), taken in place of the spatial estimate wherever it
+        is >= 0 (include/skr.h skr_denoise_var); None: the spatial estimate everywhere."""
         import torch
         dev = torch.device("cuda", self.device)
         if rgbf.dtype != torch.float32 or rgbf.dim() != 3 or rgbf.shape[2] != 3 or rgbf.device != dev:
@@ -671,19 +678,29 @@ class Renderer:
         raw = hits.raw if isinstance(hits, Hits) else hits
         if raw.dtype != torch.float32 or raw.device != dev or raw.numel() != h * w * 8:
             raise SkrError("denoise: hits must be the [%d, 8] float32 guides of the frame on %s (Renderer.trace)" % (h * w, dev))
+        if variance is not None and (variance.dtype != torch.float32 or variance.device != dev or tuple(variance.shape) != (h, w)):
+            raise SkrError("denoise: variance must be a float32 [%d, %d] tensor on %s" % (h, w, dev))
         rgbf, raw = rgbf.contiguous(), raw.contiguous()
         out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
         rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib().skr_denoise(self.h, w, h, rgbf.data_ptr(), raw.data_ptr(), int(iterations), out.data_ptr(), rgb.data_ptr(), stream), "skr_denoise")
+            if variance is None:
+                _check(lib().skr_denoise(self.h, w, h, rgbf.data_ptr(), raw.data_ptr(), int(iterations), out.data_ptr(), rgb.data_ptr(), stream), "skr_denoise")
+            else:
+                variance = variance.contiguous()
+                _check(lib().skr_denoise_var(self.h, w, h, rgbf.data_ptr(), raw.data_ptr(), variance.data_ptr(), int(iterations), out.data_ptr(), rgb.data_ptr(),
+                                             stream), "skr_denoise_var")
         return rgb, out
 
-    def render_adaptive(self, opt, threshold=ADAPTIVE_THRESHOLD, min_passes=ADAPTIVE_MIN_PASSES, max_passes=ADAPTIVE_MAX_PASSES, want_float=False):
+    def render_adaptive(self, opt, threshold=ADAPTIVE_THRESHOLD, min_passes=ADAPTIVE_MIN_PASSES, max_passes=ADAPTIVE_MAX_PASSES, want_float=False,
+                        want_variance=False):
         """Adaptive sampling (include/skr.h skr_render_adaptive): every pixel gets min_passes passes of opt (seeds seed, seed+1, ...) and
         more, up to max_passes, while the standard error of its mean luminance exceeds threshold x that mean.  Returns (rgb uint8
         [H, W, 3], rgbf float32 [H, W, 3] or None, passes uint32 [H, W]) device tensors, written on torch's current stream; the call
-        itself is synchronous (one 4-byte count is read back per round).  min_passes == max_passes == K is render(opt with progressive=K)."""
+        itself is synchronous (one 4-byte count is read back per round).  min_passes == max_passes == K is render(opt with progressive=K).
+        want_variance: a fourth tensor is appended, float32 [H, W], the variance of each pixel's mean luminance (-1 where it had fewer
+        than two passes): what denoise(variance=...) takes (include/skr.h skr_render_adaptive_var)."""
         import torch
         dev = torch.device("cuda", self.device)
         a = adaptive_params(threshold, min_passes, max_passes)
@@ -693,6 +710,11 @@ class Renderer:
         self._sync_switches()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
+            if want_variance:
+                var = torch.empty((opt.height, opt.width), dtype=torch.float32, device=dev)  # (every word is written)
+                _check(lib().skr_render_adaptive_var(self.h, C.byref(opt.c), C.byref(a), rgb.data_ptr(), rgbf.data_ptr() if want_float else None,
+                                                     passes.data_ptr(), var.data_ptr(), stream), "skr_render_adaptive_var")
+                return rgb, rgbf, passes, var
             _check(lib().skr_render_adaptive(self.h, C.byref(opt.c), C.byref(a), rgb.data_ptr(), rgbf.data_ptr() if want_float else None,
                                              passes.data_ptr(), stream), "skr_render_adaptive")
         return rgb, rgbf, passes
@@ -708,6 +730,23 @@ class Renderer:
         ms = C.c_float()
         _check(lib().skr_render_adaptive_host(self.h, C.byref(opt.c), C.byref(a), rgb.ctypes.data, rgbf.ctypes.data if want_float else None,
                                               passes.ctypes.data, C.byref(ms)), "skr_render_adaptive_host")
+        return rgb, rgbf, passes, ms.value
+
+    def render_adaptive_denoised(self, opt, threshold=ADAPTIVE_THRESHOLD, min_passes=ADAPTIVE_MIN_PASSES, max_passes=ADAPTIVE_MAX_PASSES,
+                                 iterations=DENOISE_ITERATIONS, want_float=False):
+        """include/skr.h skr_render_adaptive_denoised_host: the adaptive frame with its measured variance, its guides and the denoiser under
+        that variance, into host arrays.  Returns (rgb uint8 [H, W, 3], rgbf float32 or None, passes uint32 [H, W], device ms); the same
+        bits as render_adaptive(..., want_float=True, want_variance=True), then denoise(rgbf, trace(camera_rays(opt with jsample 0)
+        .view(-1, 8)), iterations, variance)."""
+        a = adaptive_params(threshold, min_passes, max_passes)
+        self._sync_switches()
+        rgb = np.zeros((opt.height, opt.width, 3), np.uint8)
+        rgbf = np.zeros((opt.height, opt.width, 3), np.float32) if want_float else None
+        passes = np.zeros((opt.height, opt.width), np.uint32)
+        ms = C.c_float()
+        _check(lib().skr_render_adaptive_denoised_host(self.h, C.byref(opt.c), C.byref(a), int(iterations), rgb.ctypes.data,
+                                                       rgbf.ctypes.data if want_float else None, passes.ctypes.data, C.byref(ms)),
+               "skr_render_adaptive_denoised_host")
         return rgb, rgbf, passes, ms.value
 
     def render_denoised(self, opt, iterations=DENOISE_ITERATIONS, want_float=False):

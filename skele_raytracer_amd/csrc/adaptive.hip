@@ -8,7 +8,7 @@
 //   skr_adaptive_rays_kernel     the camera rays of the listed pixels, bit for bit those of skr_camera_rays (primary_ray)
 //   skr_adaptive_sample_kernel   one AA sample of the listed pixels' shading queries: summed in sample order, divided by g^2 after
 //                                the last, then folded
-//   skr_adaptive_resolve_kernel  the mean C / n, its bytes and n
+//   skr_adaptive_resolve_kernel  the mean C / n, its bytes and n; skr_adaptive_resolve_var_kernel: and the variance of that mean
 //
 // Every list holds a pixel at most once, so each update is a plain read-modify-write of that pixel's state: no atomics, and the
 // sums are formed in pass order whatever the schedule.  Plain streams of 24 bytes of state per listed pixel (HBM-bound).
@@ -172,8 +172,9 @@ __global__ __launch_bounds__(256) void skr_adaptive_sample_kernel(const Adaptive
 	}
 }
 
-__global__ __launch_bounds__(256) void skr_adaptive_resolve_kernel(const AdaptiveScratch s, uint64_t pixels, uint8_t *__restrict__ rgb, float *__restrict__ rgbf,
-																	uint32_t *__restrict__ passes)
+// VAR: also var_p, the variance of the mean luminance (include/skr.h skr_render_adaptive_var): the e2 of adaptive_active, -1 under two passes
+template <bool VAR>
+SKR_DEV void adaptive_resolve(const AdaptiveScratch &s, uint64_t pixels, uint8_t *rgb, float *rgbf, uint32_t *passes, float *var)
 {
 	const size_t stride = (size_t) gridDim.x * 256;
 	for(size_t p = (size_t) blockIdx.x * 256 + threadIdx.x; p < pixels; p += stride)
@@ -195,7 +196,31 @@ __global__ __launch_bounds__(256) void skr_adaptive_resolve_kernel(const Adaptiv
 			rgb[3 * p + 2] = (uint8_t) quantise(b);
 		}
 		if(passes) passes[p] = n;
+		if constexpr(VAR)
+		{
+			float v = -1.0f; // not measured
+			if(n >= 2)
+			{
+				const float m = sk_divf(c.w, nf);
+				const float d = sk_divf(__uint_as_float(s.st2[p].x), nf) - m * m;
+				v = sk_divf(d > 0.0f ? d : 0.0f, nf - 1.0f);
+			}
+			var[p] = v;
+		}
 	}
+}
+
+__global__ __launch_bounds__(256) void skr_adaptive_resolve_kernel(const AdaptiveScratch s, uint64_t pixels, uint8_t *__restrict__ rgb, float *__restrict__ rgbf,
+																	uint32_t *__restrict__ passes)
+{
+	adaptive_resolve<false>(s, pixels, rgb, rgbf, passes, nullptr);
+}
+
+// the same, and var_p of every pixel (one more 4-byte store)
+__global__ __launch_bounds__(256) void skr_adaptive_resolve_var_kernel(const AdaptiveScratch s, uint64_t pixels, uint8_t *__restrict__ rgb, float *__restrict__ rgbf,
+																		uint32_t *__restrict__ passes, float *__restrict__ var)
+{
+	adaptive_resolve<true>(s, pixels, rgb, rgbf, passes, var);
 }
 
 static unsigned stream_blocks(uint64_t n)
@@ -270,9 +295,10 @@ hipError_t skr_launch_adaptive_sample(const AdaptiveScratch &s, const uint32_t *
 	return hipGetLastError();
 }
 
-hipError_t skr_launch_adaptive_resolve(const AdaptiveScratch &s, uint64_t pixels, uint8_t *rgb, float *rgbf, uint32_t *passes, hipStream_t stream)
+hipError_t skr_launch_adaptive_resolve(const AdaptiveScratch &s, uint64_t pixels, uint8_t *rgb, float *rgbf, uint32_t *passes, float *var, hipStream_t stream)
 {
 	if(pixels == 0) return hipSuccess;
-	hipLaunchKernelGGL(skr_adaptive_resolve_kernel, dim3(stream_blocks(pixels)), dim3(256), 0, stream, s, pixels, rgb, rgbf, passes);
+	if(var) hipLaunchKernelGGL(skr_adaptive_resolve_var_kernel, dim3(stream_blocks(pixels)), dim3(256), 0, stream, s, pixels, rgb, rgbf, passes, var);
+	else hipLaunchKernelGGL(skr_adaptive_resolve_kernel, dim3(stream_blocks(pixels)), dim3(256), 0, stream, s, pixels, rgb, rgbf, passes);
 	return hipGetLastError();
 }

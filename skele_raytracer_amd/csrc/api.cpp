@@ -103,8 +103,8 @@ struct skr_renderer {
 	Scratch acc;     // their AA accumulation image (LaunchPlan::acc_bytes)
 	Scratch prog;    // progressive accumulation: this pass's float frame | the running sum (progressive_scratch)
 	Scratch frame;   // the *_host entries' device frame (host_frame)
-	Scratch dn;      // skr_denoise: the ping-pong images, the guides and the classes (launch.h DenoiseScratch)
-	Scratch dnframe; // skr_render_denoised_host: the frame, its camera rays and guides, the filtered frame and its bytes
+	Scratch dn;      // skr_denoise(_var): the ping-pong images, the guides and the classes (launch.h DenoiseScratch)
+	Scratch dnframe; // skr_render_denoised_host, skr_render_adaptive_denoised_host: the frame (and its variance and passes), its camera rays and guides, the filtered frame and its bytes
 	Scratch ad;      // skr_render_adaptive: the per-pixel statistics, the active lists and the query path's rays (launch.h AdaptiveScratch)
 	unsigned long long *d_snap = nullptr; // skr_renderer_kernel_work: the work counters in front of and behind the dominant kernel of the last timed launch
 	uint32_t *h_count = nullptr; // skr_render_adaptive: the pinned word each round's active count is read back into
@@ -1140,24 +1140,27 @@ static bool overlaps(const void *a, size_t na, const void *b, size_t nb)
 	return x < y + nb && y < x + na;
 }
 
-int skr_denoise(skr_renderer *r, uint32_t width, uint32_t height, const float *d_rgbf, const skr_hit *d_hits, uint32_t iterations, float *d_out_rgbf,
-				uint8_t *d_out_rgb, void *stream)
+// skr_denoise and skr_denoise_var: d_var null, or the per-pixel variance image that replaces the spatial estimate where it is measured
+static int denoise(skr_renderer *r, const char *who, uint32_t width, uint32_t height, const float *d_rgbf, const skr_hit *d_hits, const float *d_var,
+				   uint32_t iterations, float *d_out_rgbf, uint8_t *d_out_rgb, void *stream)
 {
-	if(!r || !d_rgbf || !d_hits || (!d_out_rgbf && !d_out_rgb) || ((uintptr_t) d_rgbf & 3) || ((uintptr_t) d_hits & 15) || ((uintptr_t) d_out_rgbf & 3))
+	if(!r || !d_rgbf || !d_hits || (!d_out_rgbf && !d_out_rgb) || ((uintptr_t) d_rgbf & 3) || ((uintptr_t) d_hits & 15) || ((uintptr_t) d_out_rgbf & 3) ||
+	   ((uintptr_t) d_var & 3))
 	{
-		skr_set_error("skr_denoise: bad argument (null or misaligned array, or no output)");
+		skr_set_error("%s: bad argument (null or misaligned array, or no output)", who);
 		return SKR_ERR_ARG;
 	}
 	if(width == 0 || height == 0 || width > 65536 || height > 65536 || iterations > SKR_DENOISE_MAX_ITERATIONS)
 	{
-		skr_set_error("skr_denoise: bad size %ux%u or iterations %u (0 .. %d)", width, height, iterations, SKR_DENOISE_MAX_ITERATIONS);
+		skr_set_error("%s: bad size %ux%u or iterations %u (0 .. %d)", who, width, height, iterations, SKR_DENOISE_MAX_ITERATIONS);
 		return SKR_ERR_ARG;
 	}
 	const size_t n = (size_t) width * height;
 	if(overlaps(d_out_rgbf, n * 12, d_rgbf, n * 12) || overlaps(d_out_rgbf, n * 12, d_hits, n * sizeof(skr_hit)) || overlaps(d_out_rgb, n * 3, d_rgbf, n * 12) ||
-	   overlaps(d_out_rgb, n * 3, d_hits, n * sizeof(skr_hit)) || overlaps(d_out_rgbf, n * 12, d_out_rgb, n * 3))
+	   overlaps(d_out_rgb, n * 3, d_hits, n * sizeof(skr_hit)) || overlaps(d_out_rgbf, n * 12, d_out_rgb, n * 3) || overlaps(d_out_rgbf, n * 12, d_var, n * 4) ||
+	   overlaps(d_out_rgb, n * 3, d_var, n * 4))
 	{
-		skr_set_error("skr_denoise: an output overlaps an input or the other output");
+		skr_set_error("%s: an output overlaps an input or the other output", who);
 		return SKR_ERR_ARG;
 	}
 	SKR_HIP(hipSetDevice(r->scene->device));
@@ -1166,8 +1169,21 @@ int skr_denoise(skr_renderer *r, uint32_t width, uint32_t height, const float *d
 	const int rc = r->dn.grow(L.off);
 	if(rc != SKR_OK) return rc;
 	const DenoiseScratch b{{r->dn.at<float4>(o_img0), r->dn.at<float4>(o_img1)}, r->dn.at<float4>(o_guide), r->dn.at<uint32_t>(o_cls)};
-	SKR_HIP(skr_launch_denoise(b, width, height, d_rgbf, reinterpret_cast<const float4 *>(d_hits), (int) iterations, d_out_rgbf, d_out_rgb, (hipStream_t) stream));
+	SKR_HIP(skr_launch_denoise(b, width, height, d_rgbf, reinterpret_cast<const float4 *>(d_hits), d_var, (int) iterations, d_out_rgbf, d_out_rgb,
+							   (hipStream_t) stream));
 	return SKR_OK;
+}
+
+int skr_denoise(skr_renderer *r, uint32_t width, uint32_t height, const float *d_rgbf, const skr_hit *d_hits, uint32_t iterations, float *d_out_rgbf,
+				uint8_t *d_out_rgb, void *stream)
+{
+	return denoise(r, "skr_denoise", width, height, d_rgbf, d_hits, nullptr, iterations, d_out_rgbf, d_out_rgb, stream);
+}
+
+int skr_denoise_var(skr_renderer *r, uint32_t width, uint32_t height, const float *d_rgbf, const skr_hit *d_hits, const float *d_var, uint32_t iterations,
+					float *d_out_rgbf, uint8_t *d_out_rgb, void *stream)
+{
+	return denoise(r, "skr_denoise_var", width, height, d_rgbf, d_hits, d_var, iterations, d_out_rgbf, d_out_rgb, stream);
 }
 
 int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf, float *kernel_ms)
@@ -1233,14 +1249,15 @@ static int check_adaptive(const skr_options *opt, const skr_adaptive *a, const c
 	return SKR_OK;
 }
 
-int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes, void *stream)
+static int render_adaptive(skr_renderer *r, const char *who, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes,
+						   float *d_var, void *stream)
 {
-	if(!r || !opt || !a || (!d_rgb && !d_rgbf && !d_passes) || ((uintptr_t) d_rgbf & 3) || ((uintptr_t) d_passes & 3))
+	if(!r || !opt || !a || (!d_rgb && !d_rgbf && !d_passes && !d_var) || ((uintptr_t) d_rgbf & 3) || ((uintptr_t) d_passes & 3) || ((uintptr_t) d_var & 3))
 	{
-		skr_set_error("skr_render_adaptive: bad argument (null or misaligned array, or no output)");
+		skr_set_error("%s: bad argument (null or misaligned array, or no output)", who);
 		return SKR_ERR_ARG;
 	}
-	int rc = check_adaptive(opt, a, "skr_render_adaptive");
+	int rc = check_adaptive(opt, a, who);
 	if(rc != SKR_OK) return rc;
 	SKR_HIP(hipSetDevice(r->scene->device));
 	const hipStream_t st = (hipStream_t) stream;
@@ -1295,8 +1312,24 @@ int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adapt
 			SKR_HIP(skr_launch_adaptive_sample(s, in, m, aa, samples, st));
 		}
 	}
-	SKR_HIP(skr_launch_adaptive_resolve(s, pixels, d_rgb, d_rgbf, d_passes, st));
+	SKR_HIP(skr_launch_adaptive_resolve(s, pixels, d_rgb, d_rgbf, d_passes, d_var, st));
 	return SKR_OK;
+}
+
+int skr_render_adaptive_var(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes, float *d_var,
+							void *stream)
+{
+	return render_adaptive(r, "skr_render_adaptive_var", opt, a, d_rgb, d_rgbf, d_passes, d_var, stream);
+}
+
+int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes, void *stream)
+{
+	if(!d_rgb && !d_rgbf && !d_passes)
+	{
+		skr_set_error("skr_render_adaptive: bad argument (null or misaligned array, or no output)");
+		return SKR_ERR_ARG;
+	}
+	return render_adaptive(r, "skr_render_adaptive", opt, a, d_rgb, d_rgbf, d_passes, nullptr, stream);
 }
 
 int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *h_rgb, float *h_rgbf, uint32_t *h_passes, float *kernel_ms)
@@ -1318,6 +1351,41 @@ int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_
 	uint32_t *d_passes = h_passes ? f.passes : nullptr;
 	return timed_host(r, [&] { return skr_render_adaptive(r, opt, a, d_rgb, d_rgbf, d_passes, nullptr); },
 					  {{h_rgb, d_rgb, pixels * 3}, {h_rgbf, d_rgbf, pixels * 12}, {h_passes, d_passes, pixels * 4}}, kernel_ms);
+}
+
+int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf,
+									  uint32_t *h_passes, float *kernel_ms)
+{
+	if(!r || !opt || !a || (!h_rgb && !h_rgbf && !h_passes) || iterations > SKR_DENOISE_MAX_ITERATIONS)
+	{
+		skr_set_error("skr_render_adaptive_denoised_host: bad argument (no output, or iterations over %d)", SKR_DENOISE_MAX_ITERATIONS);
+		return SKR_ERR_ARG;
+	}
+	int rc = check_adaptive(opt, a, "skr_render_adaptive_denoised_host"); // before anything is sized from width x height
+	if(rc != SKR_OK) return rc;
+	SKR_HIP(hipSetDevice(r->scene->device));
+	const size_t n = (size_t) opt->width * opt->height;
+	ScratchLayout L; // the adaptive mean, its variance and pass counts, the camera rays and guides, the filtered frame and its bytes
+	const size_t o_frame = L.take(n * 12), o_var = L.take(n * 4), o_passes = L.take(n * 4), o_rays = L.take(n * sizeof(skr_ray)), o_hits = L.take(n * sizeof(skr_hit)),
+				 o_out = L.take(n * 12), o_rgb = L.take(n * 3);
+	rc = r->dnframe.grow(L.off);
+	if(rc != SKR_OK) return rc;
+	float *frame = r->dnframe.at<float>(o_frame), *var = r->dnframe.at<float>(o_var), *out = r->dnframe.at<float>(o_out);
+	uint32_t *passes = r->dnframe.at<uint32_t>(o_passes);
+	skr_ray *rays = r->dnframe.at<skr_ray>(o_rays);
+	skr_hit *hits = r->dnframe.at<skr_hit>(o_hits);
+	uint8_t *rgb = r->dnframe.at<uint8_t>(o_rgb);
+	skr_options guide_opt = *opt;
+	guide_opt.grid_size = 0; // the pixel centres
+	const bool filtered = h_rgb || h_rgbf; // (only the pass counts: the adaptive frame alone)
+	return timed_host(r, [&]() -> int {
+		int e = skr_render_adaptive_var(r, opt, a, nullptr, frame, h_passes ? passes : nullptr, var, nullptr);
+		if(e == SKR_OK && filtered) e = skr_camera_rays(r, &guide_opt, 0, rays, nullptr);
+		if(e == SKR_OK && filtered) e = skr_trace_rays(r, rays, (uint32_t) n, 0, hits, nullptr);
+		if(e == SKR_OK && filtered)
+			e = skr_denoise_var(r, (uint32_t) opt->width, (uint32_t) opt->height, frame, hits, var, iterations, h_rgbf ? out : nullptr, h_rgb ? rgb : nullptr, nullptr);
+		return e;
+	}, {{h_rgb, rgb, n * 3}, {h_rgbf, out, n * 12}, {h_passes, passes, n * 4}}, kernel_ms);
 }
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)

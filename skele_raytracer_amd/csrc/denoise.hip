@@ -6,6 +6,7 @@
 // Kernels, all one lane per pixel in 16x16 workgroups (a wave is a 16x4 block, so the taps of its lanes share cache lines):
 //   skr_dn_pack_kernel   guides once: {n, t} as one float4 and the pixel's class as one word; the colour as {r, g, b, l}
 //   skr_dn_init_kernel   var = max(0, m2 - m1^2) over the same-class 3x3 window; writes {r, g, b, var}
+//   skr_dn_init_var_kernel  skr_denoise_var: var = the caller's per-pixel variance, 3x3 pre-filtered, where it is measured
 //   skr_dn_iter_kernel   one a-trous step of size s = 2^i over 5x5 taps; the last one writes the float frame and its bytes
 // A tap reads 36 bytes: the {r, g, b, var} float4, the {n, t} float4 and the class.  No atomics, no LDS.
 #include <hip/hip_runtime.h>
@@ -20,6 +21,7 @@ namespace {
 constexpr uint32_t DN_MISS = 0xFFFFFFFFu, DN_MESH = 0xFFFFFFFEu; // the classes that are not a sphere index
 constexpr int DN_TILE = 16;
 constexpr float DN_SIGMA_L2 = SKR_DENOISE_SIGMA_L * SKR_DENOISE_SIGMA_L; // (16: exact)
+static_assert(SKR_DENOISE_VAR_SIGMA_L == SKR_DENOISE_SIGMA_L, "skr_denoise_var runs skr_dn_iter_kernel: another sigma needs an instance that takes sigma^2");
 
 // l = 0.2126 r + 0.7152 g + 0.0722 b, left to right
 SKR_DEV float dn_max0(float x) { return x > 0.0f ? x : 0.0f; }
@@ -51,13 +53,8 @@ __global__ __launch_bounds__(256) void skr_dn_pack_kernel(const float *__restric
 }
 
 // var_p = max(0, m2 - m1 * m1), m1 and m2 the means of l and l * l over the same-class in-image pixels of the 3x3 window (row-major)
-__global__ __launch_bounds__(256) void skr_dn_init_kernel(const float4 *__restrict__ col, const uint32_t *__restrict__ cls, uint32_t w, uint32_t h,
-														  float4 *__restrict__ out)
+SKR_DEV float dn_window_var(const float4 *col, const uint32_t *cls, uint32_t w, uint32_t h, uint32_t x, uint32_t y, uint32_t cp)
 {
-	uint32_t x, y;
-	if(!dn_pixel(w, h, x, y)) return;
-	const size_t i = (size_t) y * w + x;
-	const uint32_t cp = cls[i];
 	float s1 = 0.0f, s2 = 0.0f;
 	int n = 0;
 #pragma unroll
@@ -78,8 +75,57 @@ __global__ __launch_bounds__(256) void skr_dn_init_kernel(const float4 *__restri
 		}
 	}
 	const float m1 = s1 / (float) n, m2 = s2 / (float) n; // (n >= 1: the pixel itself)
+	return dn_max0(m2 - m1 * m1);
+}
+
+__global__ __launch_bounds__(256) void skr_dn_init_kernel(const float4 *__restrict__ col, const uint32_t *__restrict__ cls, uint32_t w, uint32_t h,
+														  float4 *__restrict__ out)
+{
+	uint32_t x, y;
+	if(!dn_pixel(w, h, x, y)) return;
+	const size_t i = (size_t) y * w + x;
+	const float v = dn_window_var(col, cls, w, h, x, y, cls[i]);
 	const float4 c = col[i];
-	out[i] = make_float4(c.x, c.y, c.z, dn_max0(m2 - m1 * m1));
+	out[i] = make_float4(c.x, c.y, c.z, v);
+}
+
+// skr_denoise_var's init.  A pixel whose var[p] >= 0 (measured: false for NaN and negatives) takes (sum g var[q]) / (sum g) over the
+// in-image same-class measured q of the 3x3 window, row-major, g = {1, 2, 1; 2, 4, 2; 1, 2, 1} / 16 (SVGF's variance pre-filter, once);
+// any other pixel takes skr_dn_init_kernel's value.
+__global__ __launch_bounds__(256) void skr_dn_init_var_kernel(const float4 *__restrict__ col, const uint32_t *__restrict__ cls, const float *__restrict__ var,
+															  uint32_t w, uint32_t h, float4 *__restrict__ out)
+{
+	uint32_t x, y;
+	if(!dn_pixel(w, h, x, y)) return;
+	const size_t i = (size_t) y * w + x;
+	const uint32_t cp = cls[i];
+	float v;
+	if(var[i] >= 0.0f)
+	{
+		float sv = 0.0f, sg = 0.0f;
+#pragma unroll
+		for(int dy = -1; dy <= 1; dy++)
+		{
+			const int yy = (int) y + dy;
+#pragma unroll
+			for(int dx = -1; dx <= 1; dx++)
+			{
+				const int xx = (int) x + dx;
+				if(yy < 0 || yy >= (int) h || xx < 0 || xx >= (int) w) continue;
+				const size_t j = (size_t) yy * w + xx;
+				if(cls[j] != cp) continue;
+				const float vq = var[j];
+				if(!(vq >= 0.0f)) continue;
+				const float g = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f); // (exact: it folds to a constant)
+				sv += g * vq;
+				sg += g;
+			}
+		}
+		v = sv / sg; // (sg >= 1/4: the pixel itself)
+	}
+	else v = dn_window_var(col, cls, w, h, x, y, cp);
+	const float4 c = col[i];
+	out[i] = make_float4(c.x, c.y, c.z, v);
 }
 
 // One a-trous step of size s.  LAST: the float frame and its bytes (either may be null) instead of the next {r, g, b, var} image.
@@ -170,8 +216,8 @@ __global__ __launch_bounds__(256) void skr_dn_copy_kernel(const float *__restric
 	}
 }
 
-hipError_t skr_launch_denoise(const DenoiseScratch &b, uint32_t w, uint32_t h, const float *rgbf, const float4 *hits, int iterations, float *out_rgbf,
-							  uint8_t *out_rgb, hipStream_t stream)
+hipError_t skr_launch_denoise(const DenoiseScratch &b, uint32_t w, uint32_t h, const float *rgbf, const float4 *hits, const float *var, int iterations,
+							  float *out_rgbf, uint8_t *out_rgb, hipStream_t stream)
 {
 	const dim3 grid((w + DN_TILE - 1) / DN_TILE, (h + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
 	if(iterations == 0)
@@ -180,7 +226,8 @@ hipError_t skr_launch_denoise(const DenoiseScratch &b, uint32_t w, uint32_t h, c
 		return hipGetLastError();
 	}
 	hipLaunchKernelGGL(skr_dn_pack_kernel, grid, block, 0, stream, rgbf, hits, w, h, b.img[1], b.guide, b.cls);
-	hipLaunchKernelGGL(skr_dn_init_kernel, grid, block, 0, stream, b.img[1], b.cls, w, h, b.img[0]);
+	if(var) hipLaunchKernelGGL(skr_dn_init_var_kernel, grid, block, 0, stream, b.img[1], b.cls, var, w, h, b.img[0]);
+	else hipLaunchKernelGGL(skr_dn_init_kernel, grid, block, 0, stream, b.img[1], b.cls, w, h, b.img[0]);
 	for(int it = 0; it < iterations; it++)
 	{
 		const float4 *src = b.img[it & 1];

@@ -200,8 +200,9 @@ struct DenoiseScratch {
 	float4 *guide;  // {n, t} of every pixel's guide hit
 	uint32_t *cls;  // its class: the sphere index, 0xFFFFFFFE for every triangle, 0xFFFFFFFF for a miss
 };
-hipError_t skr_launch_denoise(const DenoiseScratch &b, uint32_t w, uint32_t h, const float *rgbf, const float4 *hits, int iterations, float *out_rgbf,
-							  uint8_t *out_rgb, hipStream_t stream);
+// var: null, or the per-pixel variance image of skr_denoise_var (init by skr_dn_init_var_kernel)
+hipError_t skr_launch_denoise(const DenoiseScratch &b, uint32_t w, uint32_t h, const float *rgbf, const float4 *hits, const float *var, int iterations,
+							  float *out_rgbf, uint8_t *out_rgb, hipStream_t stream);
 // accumulate.hip
 hipError_t skr_launch_accumulate(float *acc, const float *frame, size_t n, int first, hipStream_t stream);
 hipError_t skr_launch_resolve_accumulated(const float *acc, uint32_t passes, uint32_t width, uint32_t out_rows, uint32_t height, uint32_t tile_rows,
@@ -229,4 +230,5 @@ hipError_t skr_launch_adaptive_fold(const AdaptiveScratch &s, const float *frame
 hipError_t skr_launch_adaptive_select(const AdaptiveScratch &s, const AdaptiveRule &rule, const uint32_t *in, uint32_t m, uint32_t *out, hipStream_t stream);
 hipError_t skr_launch_adaptive_rays(const RenderParams &p, const uint32_t *list, uint32_t m, float4 *rays, hipStream_t stream);
 hipError_t skr_launch_adaptive_sample(const AdaptiveScratch &s, const uint32_t *list, uint32_t m, uint32_t sample, uint32_t samples, hipStream_t stream);
-hipError_t skr_launch_adaptive_resolve(const AdaptiveScratch &s, uint64_t pixels, uint8_t *rgb, float *rgbf, uint32_t *passes, hipStream_t stream);
+// var: null, or the variance image of skr_render_adaptive_var (the second instance of the resolve kernel)
+hipError_t skr_launch_adaptive_resolve(const AdaptiveScratch &s, uint64_t pixels, uint8_t *rgb, float *rgbf, uint32_t *passes, float *var, hipStream_t stream);

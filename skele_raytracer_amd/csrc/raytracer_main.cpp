@@ -6,7 +6,7 @@
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
 // --scn-fog, --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
-// --adaptive T [--adaptive-min K] [--adaptive-max N].
+// --adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L].
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +35,8 @@ int main(int argc, char *argv[])
 	bool adaptive = false; // --adaptive T [--adaptive-min K] [--adaptive-max N]: passes per pixel while it is still noisy (include/skr.h skr_render_adaptive)
 	skr_adaptive adapt;
 	skr_adaptive_default(&adapt);
+	int adaptive_denoise = 0; // --adaptive-denoise L (with --adaptive): the adaptive frame filtered under its measured variance (skr_render_adaptive_denoised_host)
+	bool adaptive_denoised = false;
 	uint32_t progressive_every = 0; // --progressive-every M: the output file is rewritten after every M passes (the headless "viewer")
 	const char *format = "ppm";     // --format ppm | png | pfm (new; the reference writes P6 whatever the name says)
 
@@ -142,6 +144,7 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--adaptive") && has_next) { adapt.threshold = strtof(argv[i + 1], nullptr); adaptive = true; } // new: adaptive sampling
 		if(!strcmp(argv[i], "--adaptive-min") && has_next) adapt.min_passes = atoi(argv[i + 1]);
 		if(!strcmp(argv[i], "--adaptive-max") && has_next) adapt.max_passes = atoi(argv[i + 1]);
+		if(!strcmp(argv[i], "--adaptive-denoise") && has_next) { adaptive_denoise = atoi(argv[i + 1]); adaptive_denoised = true; } // new: the two together
 	}
 	if(!path)
 	{
@@ -201,8 +204,13 @@ int main(int argc, char *argv[])
 		return SKR_ERR_ARG;
 	}
 	if(adaptive && (option.progressive_passes > 1 || progressive_every || (sharded && gpus > 1) || denoised))
-	{ // the passes are chosen per pixel on one device; the denoiser does not take the per-pixel means (yet)
-		std::cerr << "raytracer: --adaptive cannot be combined with --progressive K > 1, --progressive-every, --gpus N > 1 or --denoise" << std::endl;
+	{ // the passes are chosen per pixel on one device; --denoise estimates its variance spatially, --adaptive-denoise takes the measured one
+		std::cerr << "raytracer: --adaptive cannot be combined with --progressive K > 1, --progressive-every, --gpus N > 1 or --denoise (--adaptive-denoise L filters an adaptive frame)" << std::endl;
+		return SKR_ERR_ARG;
+	}
+	if(adaptive_denoised && (!adaptive || denoised || adaptive_denoise < 0 || adaptive_denoise > SKR_DENOISE_MAX_ITERATIONS))
+	{
+		std::cerr << "raytracer: --adaptive-denoise takes 0 .. " << SKR_DENOISE_MAX_ITERATIONS << " iterations, needs --adaptive T and excludes --denoise" << std::endl;
 		return SKR_ERR_ARG;
 	}
 	if(denoised || adaptive) sharded = false; // (--gpus 1: the one device)
@@ -255,7 +263,10 @@ int main(int argc, char *argv[])
 		std::vector<uint32_t> passes(adaptive ? (size_t) option.width * option.height : 0);
 		if(rc == SKR_OK && adaptive)
 		{
-			rc = skr_render_adaptive_host(renderer, &option, &adapt, want_pfm ? nullptr : rgb.data(), want_pfm ? rgbf.data() : nullptr, passes.data(), &ms);
+			if(adaptive_denoised)
+				rc = skr_render_adaptive_denoised_host(renderer, &option, &adapt, (uint32_t) adaptive_denoise, want_pfm ? nullptr : rgb.data(),
+													   want_pfm ? rgbf.data() : nullptr, passes.data(), &ms);
+			else rc = skr_render_adaptive_host(renderer, &option, &adapt, want_pfm ? nullptr : rgb.data(), want_pfm ? rgbf.data() : nullptr, passes.data(), &ms);
 			if(rc == SKR_OK)
 			{ // the mean passes per pixel and the share of pixels that reached max_passes
 				uint64_t sum = 0, at_max = 0;

@@ -4,7 +4,7 @@ per GPU.
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
            [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
-           [--adaptive T [--adaptive-min K] [--adaptive-max N]]
+           [--adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
            --gillum 64 --jsample 5 --shadow            # BASELINE config 5
@@ -108,6 +108,8 @@ def _parse(argv):
             opt["adaptive_min"] = value(i, _atoi, "adaptive-min takes the number of passes every pixel gets")
         elif a == "--adaptive-max":
             opt["adaptive_max"] = value(i, _atoi, "adaptive-max takes the largest number of passes of a pixel")
+        elif a == "--adaptive-denoise":
+            opt["adaptive_denoise"] = value(i, _atoi, "adaptive-denoise takes a number of iterations")
         elif a == "--seed":
             opt["seed"] = value(i, _atoi, "seed takes an int")
         elif a == "--tile-rows":
@@ -200,16 +202,27 @@ def main(argv=None):
         return 2
     adaptive = o.get("adaptive")
     if adaptive is not None and (o.get("progressive", 1) > 1 or every or world > 1 or denoise is not None):
-        # the passes are chosen per pixel on one device; the denoiser does not take the per-pixel means (yet)
+        # the passes are chosen per pixel on one device; --denoise estimates its variance spatially, --adaptive-denoise takes the measured one
         if rank == 0:
-            print("raytracer: --adaptive cannot be combined with --progressive K > 1, --progressive-every, --gpus N > 1 or --denoise", file=sys.stderr)
+            print("raytracer: --adaptive cannot be combined with --progressive K > 1, --progressive-every, --gpus N > 1 or --denoise "
+                  "(--adaptive-denoise L filters an adaptive frame)", file=sys.stderr)
+        if world > 1:
+            dist.destroy_process_group()
+        return 2
+    adaptive_denoise = o.get("adaptive_denoise")
+    if adaptive_denoise is not None and (adaptive is None or denoise is not None or not 0 <= adaptive_denoise <= 16):
+        if rank == 0:
+            print("raytracer: --adaptive-denoise takes 0 .. 16 iterations, needs --adaptive T and excludes --denoise", file=sys.stderr)
         if world > 1:
             dist.destroy_process_group()
         return 2
     if adaptive is not None:
         try:
-            rgb, rgbf, passes, ms = r.render_adaptive_host(opt, adaptive, o.get("adaptive_min", skr.ADAPTIVE_MIN_PASSES), o.get("adaptive_max", skr.ADAPTIVE_MAX_PASSES),
-                                                           want_float=(fmt == "pfm"))
+            lo, hi = o.get("adaptive_min", skr.ADAPTIVE_MIN_PASSES), o.get("adaptive_max", skr.ADAPTIVE_MAX_PASSES)
+            if adaptive_denoise is not None:
+                rgb, rgbf, passes, ms = r.render_adaptive_denoised(opt, adaptive, lo, hi, adaptive_denoise, want_float=(fmt == "pfm"))
+            else:
+                rgb, rgbf, passes, ms = r.render_adaptive_host(opt, adaptive, lo, hi, want_float=(fmt == "pfm"))
         except skr.SkrError as e:
             print("raytracer: %s" % e, file=sys.stderr)
             return 2

@@ -1,5 +1,6 @@
 """Denoiser cost on one MI355X (include/skr.h skr_denoise): the filter on the 1080p headline frame (spheres2.scn
-`--gillum 16 --shadow`) at several iteration counts, and the guides (camera_rays + trace of the pixel centres) on spheres2.scn and
+`--gillum 16 --shadow`) at several iteration counts, the same under a per-pixel variance image (skr_denoise_var, DESIGN.md 8.11: the
+variance of a 4-pass adaptive frame), and the guides (camera_rays + trace of the pixel centres) on spheres2.scn and
 dragon.scn at 1080p.  HIP events around `--iters` back-to-back calls after `--warmup` calls; one JSON line per case.  Run it under
 `rocprofv3 --kernel-trace --stats -- python tools/denoise_rate.py` (its own process) for the per-kernel split."""
 import argparse
@@ -48,6 +49,12 @@ def main():
         for L in (1, 5) if name == "dragon.scn" else (0, 1, 2, 3, 5):
             ms = time_calls(lambda: r.denoise(rgbf, hits, L), a.warmup, a.iters)
             print(json.dumps({"scene": name, "case": "denoise_1080p", "iterations": L, "ms": round(ms, 4)}), flush=True)
+        if name == "spheres2.scn":
+            _, mean, _, var = r.render_adaptive(skr.Options(W, H, **kw), -1.0, 4, 4, want_float=True, want_variance=True)
+            torch.cuda.synchronize()
+            for L in (1, 5):
+                ms = time_calls(lambda: r.denoise(mean, hits, L, variance=var), a.warmup, a.iters)
+                print(json.dumps({"scene": name, "case": "denoise_var_1080p", "iterations": L, "ms": round(ms, 4)}), flush=True)
 
 
 if __name__ == "__main__":
