@@ -53,6 +53,21 @@ constexpr int NWIN = 4;                     // slot windows (rounds whose contri
 constexpr int WIN_FLOATS = 2 * 3 * 64;      // [child 0|1][component][lane]
 constexpr int LEAF2_WAVE_FLOATS = NQ_CAP * NQ_F + NWIN * WIN_FLOATS;
 
+// The launch constants of skr_trace_kernel, read where they are used.  A field of the by-value kernel argument is loaded once at the
+// kernel's entry and then lives in a scalar register to its last use: across the block loop, where the kernel held more scalars than
+// the register file has, 67 of them were spilled into lanes of carrier VGPRs and came back one v_readlane_b32 at a time — a VALU
+// issue slot each, plus the hazard s_nop, 137 per block of 256 pairs among 1 200 VALU instructions (tools/spill_report.py).  Through
+// this reference a field is one s_load from the kernel-argument segment (constant address space: the scalar cache) next to its use,
+// and dead after it.  Every call names the segment anew (the empty asm), so no load moves above its call.  The bytes read are the
+// bytes of the argument.  (The leaf kernel keeps its by-value argument: there the same re-reading was measured and loses)
+typedef const RenderParams __attribute__((address_space(4))) *LaunchArgs;
+SKR_DEV const RenderParams &launch_args()
+{
+	LaunchArgs k = (LaunchArgs) __builtin_amdgcn_kernarg_segment_ptr(); // (RenderParams is the kernel's one argument: offset 0)
+	asm volatile("" : "+s"(k));
+	return *(const RenderParams *) k;
+}
+
 // raytrace.h:171-186 + :189-192 / :221-224 for one traced child whose closest sphere is s: true = the child is a sphere
 // hit to be shaded; otherwise `black` says whether a triangle took it (else it left the scene)
 SKR_DEV bool classify_child(const SceneView &sv, f3 co, f3 d, float two_a, float four_a, const BestState &s, bool &black)
@@ -91,20 +106,23 @@ SKR_DEV bool classify_child(const SceneView &sv, f3 co, f3 d, float two_a, float
 #endif
 // GIM: GI masks (sphere-only scenes, p.gi_index set; wave_common.h closest_pair); the kernels without them are compiled without the walk
 template <bool TRIS, bool GIM>
-__global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams p)
+__global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
+	const RenderParams &p = launch_args(); // (the kernel's entry; every block below names the constants anew)
 	const uint32_t N = (uint32_t) p.num_path_traces, PP = (N + 1u) >> 1; // children, sibling pairs per node
 	const uint64_t n_pairs = (uint64_t) *p.nd_count * PP;
 	if((uint64_t) blockIdx.x * 256u >= n_pairs) return; // (uniform per workgroup)
-	const SceneView sv = stage_scene(p, lds4, TRIS);
+	stage_scene(p, lds4, TRIS);
 	const int tid = threadIdx.x, lane = tid & 63;
 	Counters cn{0, 0, 0};
 	// (the grid is sized for the worst case — every ray of the level above a hit — and capped: a workgroup takes every
 	// gridDim.x-th block of 256 pairs, so a launch far below the worst case does not pay for its empty workgroups)
 	for(uint32_t blk = blockIdx.x; (uint64_t) blk * 256u < n_pairs; blk += SKR_TRACE_STRIDE)
 	{
+	const RenderParams &p = launch_args(); // (this block's constants and its view of the staged scene: no scalar lives across the loop)
+	const SceneView sv = scene_view(p, lds4, TRIS);
 	const uint32_t chunk = blk * 4u + (uint32_t) (tid >> 6);
 	const uint64_t tp = (uint64_t) chunk * 64u + (uint32_t) lane;
 	const bool valid = tp < n_pairs;
@@ -168,7 +186,7 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 		p.ixh[IXH_ROWS * (size_t) chunk + 1] = make_uint4((uint32_t) m0, (uint32_t) (m0 >> 32), (uint32_t) m1, (uint32_t) (m1 >> 32));
 	}
 	}
-	add_counters(p, cn, (uint32_t) blockIdx.x * 4u + (uint32_t) (tid >> 6), lane);
+	add_counters(launch_args(), cn, (uint32_t) blockIdx.x * 4u + (uint32_t) (tid >> 6), lane);
 }
 
 // =====================================================================================================================
@@ -541,7 +559,11 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 			if(act)
 			{
 				uint32_t rnd[4];
-				philox4x32(pixel, p.aa_index, node_id, (uint32_t) j, p.seed_lo, p.seed_hi, rnd);
+				// (the seed words pass through an empty asm, so the key schedule — Philox bumps both words every round: the same wrap-around adds — is
+				// formed here by scalar adds; as a loop invariant it was hoisted out of the rounds loop and spilled: 12 v_readlane_b32 per round)
+				uint32_t k0 = p.seed_lo, k1 = p.seed_hi;
+				asm volatile("" : "+s"(k0), "+s"(k1));
+				philox4x32(pixel, p.aa_index, node_id, (uint32_t) j, k0, k1, rnd);
 				q1a = u31_to_unit(rnd[0]);
 				q1b = u31_to_unit(rnd[2]);
 				const float q2a = u31_to_unit(rnd[1]), q2b = u31_to_unit(rnd[3]);

@@ -139,6 +139,15 @@ SKR_DEV uint32_t *lc_prefix(uint32_t *ctr) { return ctr + SKR_PULL_STRIDE * (2u 
 constexpr size_t LVL_CTR_WORDS = (size_t) SKR_PULL_STRIDE * (2u * SKR_P1_REGIONS + 2u); // the whole block: counts, taken, mask, prefix
 static inline uint32_t *lc_prefix_host(uint32_t *ctr) { return ctr + SKR_PULL_STRIDE * (2u * SKR_P1_REGIONS + 1u) + 64; } // (host) lc_prefix [64]: the level's record count, for a kernel argument
 
+// the kernel's view of the scene SoA that stage_scene() staged at lds4 (a kernel may form it again from its launch constants: render_nodes.hip)
+SKR_DEV SceneView scene_view(const RenderParams &p, float4 *lds4, bool tris)
+{
+	const int ns = p.n_spheres, nl = p.n_lights;
+	float4 *s_geom = lds4, *s_amb = lds4 + ns + 1, *s_kd = s_amb + ns, *s_ks = s_kd + ns, *s_lights = s_ks + ns;
+	return SceneView{s_geom, s_amb, s_kd, s_ks, s_lights, p.tris, ns, tris ? p.n_tris : 0, nl, p.tri_chunks, p.n_tri_chunks, p.tri_chunk_size, p.tri_cones, p.tri_work, p.sph_geom,
+					 p.shadow_masks, p.shadow_reach2, p.shadow_all};
+}
+
 // the scene SoA staged into the workgroup's LDS (one __syncthreads); returns the kernel's view of it
 SKR_DEV SceneView stage_scene(const RenderParams &p, float4 *lds4, bool tris)
 {
@@ -155,8 +164,7 @@ SKR_DEV SceneView stage_scene(const RenderParams &p, float4 *lds4, bool tris)
 	for(int i = tid; i < 2 * nl; i += 256) s_lights[i] = p.lights[i];
 	if(tid == 0) s_geom[ns] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	__syncthreads();
-	return SceneView{s_geom, s_amb, s_kd, s_ks, s_lights, p.tris, ns, tris ? p.n_tris : 0, nl, p.tri_chunks, p.n_tri_chunks, p.tri_chunk_size, p.tri_cones, p.tri_work, p.sph_geom,
-					 p.shadow_masks, p.shadow_reach2, p.shadow_all};
+	return scene_view(p, lds4, tris);
 }
 
 SKR_DEV void add_counters(const RenderParams &p, const Counters &cn, uint32_t shard, int lane)
