@@ -31,6 +31,7 @@ extern "C" {
 #define SKR_HAS_DENOISE 1    /* skr_denoise, skr_render_denoised_host: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ADAPTIVE 1   /* skr_adaptive, skr_render_adaptive(_host): an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ADAPTIVE_DENOISE 1 /* skr_render_adaptive_var, skr_denoise_var, skr_render_adaptive_denoised_host: additions, likewise */
+#define SKR_HAS_SPOT_LIGHTS 1 /* SKR_SCN_SPOT, skr_scene_get/set_spot_lights, skr_scene_get_spot_cones, skr_debug_eval op 17: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -182,6 +183,43 @@ int skr_scene_get_triangle_shadows(const skr_scene *scene, int *enabled);
 #define SKR_SCN_SPHERE_TREE 8u
 int skr_scene_set_sphere_tree(skr_scene *scene, int enable);
 int skr_scene_get_sphere_tree(const skr_scene *scene, int *enabled);
+/* Spot lights (new, opt-in; no counterpart in the reference, whose parseScene answers a `spot_light` line with "WARNING. Do not know
+ * command", scene.cpp:214-217).  SKR_SCN_SPOT (`raytracer --scn-spot`; combines with the other scene flags): a line
+ *     spot_light r g b px py pz dx dy dz angle1 angle2
+ * (the field order of the format's other light lines; the angles in degrees from the axis d) is kept, in file order, and no longer
+ * counted in n_unknown.  A line with fewer than 11 numbers, a field that is not finite, a zero direction, or angles outside
+ * 0 <= angle1 <= angle2 <= 180 (or one past SKR_SPOT_MAX_LIGHTS) is warned about, skipped and still counted in n_unknown.  Without
+ * the flag everything is as it was, byte for byte; skr_scene_info does not grow.  The rule (normative):
+ *   - A spot light is a point light with a cone: a point-light row of the light table at its position, colour not clamped.  Shading
+ *     order: the point lights in file order, the spot lights in file order, then (SKR_SCN_STRICT) the directional lights.  L, the
+ *     colour lc and the intensity 1 / d^2 are the point light's (blinn_phong.h:67-72); the shadow masks treat it as the point light
+ *     it geometrically is (skr_scene_get_shadow_masks reports n_point + n_spot lights).  Spot lights count as lights wherever a
+ *     light limit exists (a workgroup's LDS holds the light table).
+ *   - The host derives once per light, in binary32 with one IEEE operation per step, the unit axis a = d * (1 / sqrt(d . d)) (the
+ *     device's normalize3), c1 = (float) cos((double) angle1 * (M_PI / 180.0)) and c2 = min(c1, (float) cos((double) angle2 *
+ *     (M_PI / 180.0))): skr_scene_get_spot_cones.  Kernels and checkers read these values; neither calls cos again.
+ *   - Cone factor at a shading point P, with L the unit vector from P to the light: c = -dot(a, L) ((x + y) + z of the products).
+ *     c >= c1: f = 1.  Else !(c > c2) (NaN included): the light is OUTSIDE.  Else u = (c - c2) / (c1 - c2) and
+ *     f = (u * u) * (3.0f - 2.0f * u), binary32, one correctly rounded operation per step, not contracted.
+ *   - A light that is not outside enters the point-light expression with the colour lc * f (per component, before anything else) and
+ *     casts its shadow ray exactly as a point light does (triangle shadows included: t < the distance to the light).  x * 1 == x:
+ *     a spot light with angle1 = 180 shades exactly as a point light.
+ *   - A light that is outside at P adds nothing, casts no shadow ray, adds nothing to the shadow-ray count or the sphere-test count
+ *     and is never tested against triangles.
+ *   - A scene with at least one spot light renders every frame and every shading query on the general level pipeline
+ *     (skr_kernel_variant() "level_pipeline_g1_spot", "level_pipeline_g1_spot_tshadow", "shade_rays_g1_spot",
+ *     "shade_rays_g1_spot_tshadow"), in every mode it has but three: skr_options.legacy_reflect, fog volumes and the sphere-tree
+ *     switch are refused with SKR_ERR_UNSUPPORTED.  A scene loaded with the flag that holds no spot light is planned and rendered
+ *     exactly as without it. */
+#define SKR_SCN_SPOT 16u
+#define SKR_SPOT_MAX_LIGHTS 8192 /* (more light rows than a workgroup's LDS holds: the LDS check refuses a scene first) */
+/* The spot lights of a scene, rows[n][11] = the file's fields in file order.  get: *n = their number, rows (if not NULL) receives
+ * them.  set: replaces them (n = 0: none) under the loader's validation — SKR_ERR_ARG on a bad row, the scene unchanged — for scenes
+ * made from arrays and for tests; a renderer takes the spot lights the scene has when it is created, as it takes the fog volumes.
+ * skr_scene_get_spot_cones: cones[n][5] = {a.xyz, c1, c2} as derived above. */
+int skr_scene_get_spot_lights(const skr_scene *scene, float *rows, int32_t *n);
+int skr_scene_set_spot_lights(skr_scene *scene, const float *rows, int32_t n);
+int skr_scene_get_spot_cones(const skr_scene *scene, float *cones);
 /* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
  * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
  * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device
@@ -616,7 +654,9 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  * Ops 13 and 14 call the very functions the two loops call per sphere, with `second` set and neither ray occluded yet.  The loops
  * themselves run in op 16 (closest_pair_deferred<false>, both occluded_pair forms, with rays on either side of `sane` in the two
  * slots) and in the frames of the same test file; the masked walks (closest_pair_deferred<true>, occluded_pair with shadow masks:
- * masked_rows) run only in those frames. */
+ * masked_rows) run only in those frames.
+ * 17 the spot-light cone (SKR_SCN_SPOT above; shade_common.h spot_cone, the function the light loop calls): (a(3), c1, c2, L(3))
+ *    -> {f, outside}: f as a float (0 where outside), outside 0 / 1.  (Ops 12..16 were taken when spot lights came.) */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

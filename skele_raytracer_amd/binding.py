@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -84,6 +84,9 @@ def lib():
     L.skr_scene_set_sphere_ior.argtypes = [vp, vp]
     L.skr_scene_get_fog.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_scene_set_fog.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_spot_lights.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.skr_scene_set_spot_lights.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_spot_cones.argtypes = [vp, vp]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
     L.skr_scene_set_sphere_tree.argtypes = [vp, C.c_int]
@@ -317,6 +320,30 @@ class Scene:
         _check(lib().skr_scene_set_fog(self.h, r.ctypes.data, len(r)), "skr_scene_set_fog")
 
     @property
+    def spot_lights(self):
+        """The spot lights [n, 11] = colour(3) position(3) direction(3) angle1 angle2, the file's fields in file order (include/skr.h
+        skr_scene_get_spot_lights)."""
+        n = C.c_int32()
+        _check(lib().skr_scene_get_spot_lights(self.h, None, C.byref(n)), "skr_scene_get_spot_lights")
+        rows = np.zeros((n.value, 11), np.float32)
+        _check(lib().skr_scene_get_spot_lights(self.h, rows.ctypes.data, C.byref(n)), "skr_scene_get_spot_lights")
+        return rows
+
+    def set_spot_lights(self, rows):
+        """Replace the spot lights (rows [n, 11] as `spot_lights` returns them; n = 0: none) under the loader's validation.  A renderer
+        takes those the scene has when it is made."""
+        r = np.ascontiguousarray(rows, np.float32).reshape(-1, 11)
+        _check(lib().skr_scene_set_spot_lights(self.h, r.ctypes.data, len(r)), "skr_scene_set_spot_lights")
+
+    @property
+    def spot_cones(self):
+        """What the host derives once per spot light, [n, 5] = unit axis(3) c1 c2 (include/skr.h skr_scene_get_spot_cones): the values the
+        kernels and the checkers read."""
+        c = np.zeros((len(self.spot_lights), 5), np.float32)
+        _check(lib().skr_scene_get_spot_cones(self.h, c.ctypes.data), "skr_scene_get_spot_cones")
+        return c
+
+    @property
     def triangle_shadows(self):
         """The scene's triangle-shadow switch (include/skr.h skr_scene_set_triangle_shadows)."""
         on = C.c_int()
@@ -383,17 +410,18 @@ class Scene:
         return sc
 
 
-SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE = 1, 2, 4, 8  # include/skr.h SKR_SCN_*
+SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT = 1, 2, 4, 8, 16  # include/skr.h SKR_SCN_*
 FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
 
 
-def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False):
+def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False):
     """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept),
     fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded), triangle_shadows = SKR_SCN_TRIANGLE_SHADOWS
     (--triangle-shadows: triangles cast shadows in frames with shade_triangles and shadow), sphere_tree = SKR_SCN_SPHERE_TREE
-    (--sphere-tree: frames and shading queries on the culled sphere walk, any sphere count)."""
+    (--sphere-tree: frames and shading queries on the culled sphere walk, any sphere count), spot = SKR_SCN_SPOT (--scn-spot: spot_light
+    lines parsed and shaded)."""
     h = C.c_void_p()
-    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0)
+    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0) | (SCN_SPOT if spot else 0)
     _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), flags, C.byref(h)), "skr_scene_create_from_scn_ex")
     return Scene(h.value)
 

@@ -42,6 +42,8 @@ struct DeviceScene {
 	size_t off_amb = 0, off_kd = 0, off_ks = 0, off_lights = 0, off_tris = 0, off_chunks = 0, off_tri_mats = 0;
 	size_t off_fog = 0;       // --scn-fog: 2 rows per fog volume (render_params.h RenderParams::fog_row)
 	int n_fog = 0;
+	size_t off_spot = 0;      // --scn-spot: 2 rows per spot light behind the fog rows (render_params.h SpotLights)
+	int n_spot = 0, spot_first = 0; // lights [spot_first, spot_first + n_spot) of the light table are spot lights
 	size_t off_smask = 0;     // the shadow masks (skr_scene::shadow_masks, 4 per row), 0 = none
 	float shadow_reach2 = 0.0f;
 	size_t off_gi = 0;        // the GI masks (skr_scene::gi_table, 4 words per row), 0 = none
@@ -158,7 +160,7 @@ void skr_copy_switches(skr_renderer *dst, const skr_renderer *src) { dst->sw = s
 int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
 							   float *d_rgbf, void *stream);
 
-// The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | shadow
+// The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | spot cones | shadow
 // masks | GI masks | trace tree | sphere tree (rows, chunks, nodes), then 16 rows of padding (the sphere loops ask for the rows of a trip ahead without a bounds test,
 // shade_common.h sphere_rows).  Sets the offsets and the scalars of `d` that go with the sections; host only, nothing is uploaded.
 static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
@@ -192,6 +194,10 @@ static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 		rows.push_back({f[3], f[8], f[7], 0.0f});
 		rows.push_back({f[4], f[5], f[6], 0.0f});
 	}
+	// the spot lights' cone rows (skr_scene spot_cones, SKR_SCN_SPOT / skr_scene_set_spot_lights): {unit axis, c1} {c2, 0, 0, 0}
+	d.n_spot = s.n_spot();
+	d.spot_first = s.info.n_point_lights;
+	d.off_spot = put4(s.spot_cones);
 	if(!s.shadow_masks.empty()) d.off_smask = put(s.shadow_masks.data(), s.shadow_masks.size() * 4);
 	d.shadow_reach2 = s.shadow_reach2;
 	if(!s.gi_table.empty())
@@ -313,6 +319,11 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	if(scene->raw_fog.size() / 9 > SKR_FOG_MAX_VOLUMES)
 	{
 		skr_set_error("scene has %zu fog volumes; at most %d are supported", scene->raw_fog.size() / 9, SKR_FOG_MAX_VOLUMES);
+		return SKR_ERR_UNSUPPORTED;
+	}
+	if(scene->n_spot() > SKR_SPOT_MAX_LIGHTS)
+	{
+		skr_set_error("scene has %d spot lights; at most %d are supported", scene->n_spot(), SKR_SPOT_MAX_LIGHTS);
 		return SKR_ERR_UNSUPPORTED;
 	}
 	auto s = std::make_shared<DeviceScene>(); // (frees what was allocated if the upload fails)
@@ -461,7 +472,7 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 	p.background = f3{s.info.background[0], s.info.background[1], s.info.background[2]};
 	p.n_spheres = s.info.n_spheres;
 	p.n_tris = s.info.n_triangles;
-	p.n_lights = s.info.n_point_lights + s.info.n_directional_lights; // (directional ones only under --strict-scn)
+	p.n_lights = s.info.n_point_lights + s.n_spot + s.info.n_directional_lights; // (spot lights only under --scn-spot, directional ones only under --strict-scn)
 	p.sph_geom = s.d_blob;
 	p.cam_ec = s.d_camec;
 	p.sph_amb = s.d_blob + s.off_amb;
@@ -534,6 +545,12 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 		skr_set_error("fog volumes (--scn-fog) cannot be combined with --legacy-reflect or --shade-triangles");
 		return SKR_ERR_UNSUPPORTED;
 	}
+	// --scn-spot: a scene with spot lights renders on the general level pipeline's instances with the cone decision
+	if(s.n_spot > 0 && (opt->legacy_reflect || p.n_fog > 0 || s.sphere_tree))
+	{
+		skr_set_error("spot lights (--scn-spot) cannot be combined with %s", opt->legacy_reflect ? "--legacy-reflect" : p.n_fog > 0 ? "fog volumes (--scn-fog)" : "the sphere tree (--sphere-tree)");
+		return SKR_ERR_UNSUPPORTED;
+	}
 	p.counters = s.d_counters;
 	p.tri_work = r->count_tri ? s.d_tri_work : nullptr;
 	p.qctr = reinterpret_cast<uint32_t *>(s.d_counters + (size_t) SKR_COUNTER_SHARDS * 4 + 8);
@@ -581,6 +598,13 @@ static QueryTrees query_trees(const skr_renderer *r)
 // was without the switch: the same kernels, the same skr_kernel_variant().
 static bool tri_shadows_in_force(const skr_renderer *r, const RenderParams &p) { return r->scene->tri_shadows && p.shade_triangles && p.use_shadows; }
 
+// the spot lights of a renderer's scene (render_params.h SpotLights)
+static SpotLights spot_lights_of(const skr_renderer *r)
+{
+	const DeviceScene &s = *r->scene;
+	return SpotLights{s.d_blob + s.off_spot, s.spot_first, s.n_spot};
+}
+
 // the sphere tree of a renderer whose scene had the switch on, under the renderer's switches (render_params.h SphereTree)
 static SphereTree sphere_tree_of(const skr_renderer *r)
 {
@@ -614,7 +638,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.rgb = d_rgb;
 	p.rgbf = d_rgbf;
 	LaunchPlan lp;
-	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp, r->scene->sphere_tree);
+	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp, r->scene->sphere_tree, r->scene->n_spot > 0);
 	rc = check_plan(r, p, fits, lp.lds_bytes, 0);
 	bool kept = false;
 	if(rc == SKR_OK && lp.path != SKR_PATH_DIRECT) rc = take_node_scratch(r, lp.scratch_bytes, &kept);
@@ -653,8 +677,9 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	{ // (shade_triangles: the general level pipeline)
 		lp.tri_shadows = true;
 		lp.shadows.trees = query_trees(r);
-		lp.variant = lp.sphere_tree ? "level_pipeline_g1_stree_tshadow" : "level_pipeline_g1_tshadow";
+		lp.variant = lp.sphere_tree ? "level_pipeline_g1_stree_tshadow" : lp.spot ? "level_pipeline_g1_spot_tshadow" : "level_pipeline_g1_tshadow";
 	}
+	if(lp.spot) lp.spots = spot_lights_of(r);
 	if(lp.sphere_tree) lp.stree = sphere_tree_of(r);
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
@@ -1127,8 +1152,10 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	if(tri_shadows) tsh.trees = q.trees;
 	const SphereTree st = stree ? sphere_tree_of(r) : SphereTree{};
 	if(stree) g_variant = tri_shadows ? "shade_rays_g1_stree_tshadow" : "shade_rays_g1_stree";
+	else if(r->scene->n_spot > 0) g_variant = tri_shadows ? "shade_rays_g1_spot_tshadow" : "shade_rays_g1_spot";
 	else g_variant = tri_shadows ? "shade_rays_g1_tshadow" : "shade_rays_g1";
-	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr, stree ? &st : nullptr));
+	const SpotLights spots = spot_lights_of(r);
+	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr, stree ? &st : nullptr, r->scene->n_spot > 0 ? &spots : nullptr));
 	return SKR_OK;
 }
 
@@ -1390,7 +1417,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {
-	if(!d_in || !d_out || op < 0 || op > 16) return SKR_ERR_ARG;
+	if(!d_in || !d_out || op < 0 || op > 17) return SKR_ERR_ARG;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(skr_launch_debug(op, d_in, d_out, n, (hipStream_t) stream));
 	return SKR_OK;

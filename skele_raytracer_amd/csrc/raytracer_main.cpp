@@ -5,7 +5,7 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --scn-fog, --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
+// --scn-fog, --scn-spot (spot_light lines parsed and shaded: include/skr.h SKR_SCN_SPOT), --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
 // --adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L].
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cstdio>
@@ -25,6 +25,7 @@ int main(int argc, char *argv[])
 	bool quiet = false;
 	int device = 0, gpus = 1;
 	bool strict_scn = false, width_given = false, height_given = false, depth_given = false; // --strict-scn (new)
+	bool scn_spot = false; // --scn-spot (new: DESIGN.md 8.12)
 	bool scn_fog = false, scn_fov = false, fov_given = false; // --scn-fog, --scn-fov (new: DESIGN.md "Spherical fog", "Camera half-angle")
 	bool triangle_shadows = false; // --triangle-shadows (new: include/skr.h SKR_SCN_TRIANGLE_SHADOWS)
 	bool sphere_tree = false;      // --sphere-tree (new: include/skr.h SKR_SCN_SPHERE_TREE)
@@ -131,6 +132,7 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--tile-rows") && has_next) tile_rows = (uint32_t) (atoi(argv[i + 1]) > 0 ? atoi(argv[i + 1]) : 8);
 		if(!strcmp(argv[i], "--quiet")) quiet = true;
 		if(!strcmp(argv[i], "--strict-scn")) strict_scn = true;
+		if(!strcmp(argv[i], "--scn-spot")) scn_spot = true;                 // new: spot_light lines parsed and shaded (include/skr.h SKR_SCN_SPOT)
 		if(!strcmp(argv[i], "--scn-fog")) scn_fog = true;                   // new: spherical_fog lines parsed and shaded (include/skr.h SKR_SCN_FOG)
 		if(!strcmp(argv[i], "--scn-fov")) scn_fov = true;                   // new: fov = 2 x the camera line's half_height_angle unless --fov is given
 		if(!strcmp(argv[i], "--shade-triangles")) option.shade_triangles = 1; // new: triangles as surfaces (include/skr.h skr_options)
@@ -158,7 +160,7 @@ int main(int argc, char *argv[])
 	}
 
 	skr_scene *scene = nullptr;
-	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u) | (triangle_shadows ? SKR_SCN_TRIANGLE_SHADOWS : 0u) | (sphere_tree ? SKR_SCN_SPHERE_TREE : 0u), &scene) != SKR_OK)
+	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u) | (triangle_shadows ? SKR_SCN_TRIANGLE_SHADOWS : 0u) | (sphere_tree ? SKR_SCN_SPHERE_TREE : 0u) | (scn_spot ? SKR_SCN_SPOT : 0u), &scene) != SKR_OK)
 	{
 		printf("%s\n", skr_last_error()); // scene.cpp:24-25: message, exit(0)
 		return 0;

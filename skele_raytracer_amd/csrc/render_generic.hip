@@ -155,6 +155,16 @@ SKR_DEV TriShadows shadows_of(const TriShadows &ts, const SphereTree &) { return
 SKR_DEV const SphereTree &stree_of(const SphereTree &st) { return st; }
 template <typename U, typename... R>
 SKR_DEV const SphereTree &stree_of(const U &, const R &...rest) { return stree_of(rest...); }
+// the packs of the instances with spot lights: [ShadeRays] [TriShadows] SpotLights
+SKR_DEV ShadeRays query_of(const ShadeRays &q, const SpotLights &) { return q; }
+SKR_DEV ShadeRays query_of(const SpotLights &) { return ShadeRays{}; }
+SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &, const SpotLights &) { return q; }
+SKR_DEV ShadeRays query_of(const TriShadows &, const SpotLights &) { return ShadeRays{}; }
+SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts, const SpotLights &) { return ts; }
+SKR_DEV TriShadows shadows_of(const TriShadows &ts, const SpotLights &) { return ts; }
+SKR_DEV const SpotLights &spots_of(const SpotLights &sp) { return sp; }
+template <typename U, typename... R>
+SKR_DEV const SpotLights &spots_of(const U &, const R &...rest) { return spots_of(rest...); }
 template <typename T, typename... Q>
 constexpr bool pack_has = (std::is_same<T, Q>::value || ...);
 
@@ -225,10 +235,12 @@ struct TriangleShadows {
 		}
 		shadow_triangles<NR>(w, s);
 	}
-	__device__ __forceinline__ void operator()(f3 P, int i, bool second, f3 L0, f3 L1, bool &occ0, bool &occ1) const
+	__device__ __forceinline__ void operator()(f3 P, int i, bool second, f3 L0, f3 L1, bool &occ0, bool &occ1) const { lights(P, i, second ? i + 1 : i, second, L0, L1, occ0, occ1); }
+	// the lights l0 and (second) l1, any two of the table (direct_light_spot walks a pair's one light inside its cone as a single)
+	__device__ __forceinline__ void lights(f3 P, int l0, int l1, bool second, f3 L0, f3 L1, bool &occ0, bool &occ1) const
 	{
 		const f3 o = add_scalar(P, 0.000001f);
-		const float far0 = reach(i, P), far1 = reach(second ? i + 1 : i, P);
+		const float far0 = reach(l0, P), far1 = reach(l1, P);
 #if SKR_SHADOW_PAIR_WALK
 		ShadowRays<2> s{o, {L0, L1}, {far0, far1}, {!occ0, second && !occ1}, own};
 		walk(s);
@@ -406,10 +418,11 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 
 // FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
 // Q: [ShadeRays: a shading query] [TriShadows: triangle shadows are in force — the instances with the shadow walk]
+//    [SpotLights: the scene has spot lights — the instances with the cone decision (never with FOG or the sphere tree: api.cpp launch_params)]
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
-	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>, SPOT = pack_has<SpotLights, Q...>;
 	const ShadeRays q = query_of(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -486,6 +499,15 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 				n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, TriangleShadows{sv, ts.trees, n.file}, ss);
 			}
 			else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, NoTriangleShadows(), ss);
+		}
+		else if constexpr(SPOT)
+		{ // the pair loop with the cone decision ahead of the shadow walk
+			if constexpr(TSHADOW)
+			{
+				const TriShadows ts = shadows_of(qs...);
+				n.direct = direct_light_spot(sv, p, spots_of(qs...), kd, ld3(ks4), ambp, n.P, n.N, cn, TriangleShadows{sv, ts.trees, n.file});
+			}
+			else n.direct = direct_light_spot(sv, p, spots_of(qs...), kd, ld3(ks4), ambp, n.P, n.N, cn);
 		}
 		else if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn);
 		else if constexpr(TSHADOW)
@@ -605,9 +627,10 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
 }
 
 hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q_in, const TriShadows *ts_in,
-							  const SphereTree *st_in)
+							  const SphereTree *st_in, const SpotLights *sp_in)
 {
 	if(ts_in && p_in.n_fog > 0) return hipErrorInvalidValue; // (triangle shadows need shade_triangles, which fog excludes: api.cpp launch_params)
+	if(sp_in && (st_in || p_in.n_fog > 0 || p_in.legacy_reflect)) return hipErrorInvalidValue; // (refused with a text of their own: api.cpp launch_params)
 	RenderParams p = p_in;
 	char *base = reinterpret_cast<char *>(p.node_scratch);
 	uint32_t *ctr0 = reinterpret_cast<uint32_t *>(base + pl.off_ctr);
@@ -667,6 +690,13 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 					else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, q, *st_in);
 					else if(p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *st_in);
 					else hipLaunchKernelGGL((skr_gactivate_kernel<false, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *st_in);
+				}
+				else if(sp_in)
+				{ // the instances with the cone decision of the spot lights
+					if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in, *sp_in);
+					else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in, *sp_in);
+					else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, q, *sp_in);
+					else hipLaunchKernelGGL((skr_gactivate_kernel<false, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, *sp_in);
 				}
 				else if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in);
 				else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in);

@@ -146,6 +146,15 @@ struct SphereTree {
 	unsigned long long *work; // HBM, or null (not counting): SKR_TRI_WORK_SHARDS x {culling-sphere tests, sphere tests} the walks executed
 };
 
+// The spot lights (include/skr.h SKR_SCN_SPOT): lights [first, first + n) of the light table are spot lights, and
+// `cones` holds what the host derived for each, 2 rows per light in file order — {unit axis, c1} {c2, 0, 0, 0} — in the scene blob behind
+// the fog rows (HBM, never written by a kernel).  Handed to the activate kernel's instances with the cone decision in a kernel argument
+// of their own, as SphereTree is: RenderParams keeps its size and every offset, and every other kernel its code.
+struct SpotLights {
+	const float4 *cones;
+	int32_t first, n;
+};
+
 // Optional timing of the dominant kernel of a launch (skr_renderer_kernel_ms): the launcher records the
 // two events right around that kernel on the launch stream — and, where `snap` is set, copies the work counters in front of the
 // first event and behind the second (stream-ordered device-to-device copies outside the timed window), so that the work of that

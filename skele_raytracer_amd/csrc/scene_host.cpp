@@ -52,7 +52,7 @@ struct Material { // material.h:9-17
 
 void skr_scene::finalize()
 {
-	const int ns = info.n_spheres, nt = info.n_triangles, nl = info.n_point_lights;
+	const int ns = info.n_spheres, nt = info.n_triangles;
 	sph_geom.resize(ns);
 	sph_amb.resize(ns);
 	sph_kd.resize(ns);
@@ -65,21 +65,7 @@ void skr_scene::finalize()
 		sph_kd[i] = {s[7], s[8], s[9], 0.0f};
 		sph_ks[i] = {s[10], s[11], s[12], (size_t) i < raw_sphere_ior.size() ? raw_sphere_ior[i] : 1.0f};
 	}
-	// point lights first, then (--strict-scn) the directional ones: the order blinn_phong.h:50-85 / :95-131 adds them in
-	const int nd = (int) (raw_directional_lights.size() / 6);
-	lights.resize((size_t) (nl + nd) * 2);
-	for(int i = 0; i < nl; i++)
-	{
-		const float *l = &raw_point_lights[(size_t) i * 6];
-		lights[2 * i] = {l[0], l[1], l[2], 0.0f};
-		lights[2 * i + 1] = {l[3], l[4], l[5], 0.0f};
-	}
-	for(int i = 0; i < nd; i++)
-	{
-		const float *l = &raw_directional_lights[(size_t) i * 6];
-		lights[2 * (nl + i)] = {l[0], l[1], l[2], 1.0f}; // .w = 1: a direction, not a position (shade_common.h light_term)
-		lights[2 * (nl + i) + 1] = {l[3], l[4], l[5], 0.0f};
-	}
+	build_lights();
 	// The triangle walk only answers "does any triangle accept this ray before tmin" (raytrace.h:168-176 turns
 	// any such hit black), so the order of tris[] is free: store the triangles along a Morton curve through the
 	// centres of their accept regions, which makes every run of tri_chunk_size triangles spatially tight.
@@ -141,6 +127,48 @@ void skr_scene::finalize()
 	build_shadow_masks();
 	build_gi_masks();
 	build_gi_surface();
+}
+
+// The light table: point lights first, then the spot lights (SKR_SCN_SPOT: point-light rows at their positions, the cone is the
+// kernels' business), then (--strict-scn) the directional ones: the order blinn_phong.h:50-85 / :95-131 adds them in.  And what the
+// host derives once per spot light (include/skr.h skr_scene_get_spot_cones), in binary32, one IEEE operation per step.
+void skr_scene::build_lights()
+{
+	const int nl = info.n_point_lights, nsp = n_spot();
+	const int nd = (int) (raw_directional_lights.size() / 6);
+	lights.resize((size_t) (nl + nsp + nd) * 2);
+	for(int i = 0; i < nl; i++)
+	{
+		const float *l = &raw_point_lights[(size_t) i * 6];
+		lights[2 * i] = {l[0], l[1], l[2], 0.0f};
+		lights[2 * i + 1] = {l[3], l[4], l[5], 0.0f};
+	}
+	spot_cones.resize((size_t) nsp * 2);
+	for(int i = 0; i < nsp; i++)
+	{
+		const float *l = &raw_spot_lights[(size_t) i * 11]; // r g b px py pz dx dy dz angle1 angle2
+		lights[2 * (nl + i)] = {l[3], l[4], l[5], 0.0f};
+		lights[2 * (nl + i) + 1] = {l[0], l[1], l[2], 0.0f}; // (not clamped: a point light with a cone)
+		const float ss = (l[6] * l[6] + l[7] * l[7]) + l[8] * l[8];
+		const float inv = 1.0f / sqrtf(ss); // the device's normalize3: v * (1 / sqrt(v . v))
+		const float c1 = (float) cos((double) l[9] * (M_PI / 180.0)), c2 = (float) cos((double) l[10] * (M_PI / 180.0));
+		spot_cones[2 * i] = {l[6] * inv, l[7] * inv, l[8] * inv, c1};
+		spot_cones[2 * i + 1] = {c2 < c1 ? c2 : c1, 0.0f, 0.0f, 0.0f};
+	}
+	for(int i = 0; i < nd; i++)
+	{
+		const float *l = &raw_directional_lights[(size_t) i * 6];
+		lights[2 * (nl + nsp + i)] = {l[0], l[1], l[2], 1.0f}; // .w = 1: a direction, not a position (shade_common.h light_term)
+		lights[2 * (nl + nsp + i) + 1] = {l[3], l[4], l[5], 0.0f};
+	}
+}
+
+bool skr_spot_row_ok(const float row[11])
+{
+	for(int k = 0; k < 11; k++)
+		if(!std::isfinite(row[k])) return false;
+	if(row[6] == 0.0f && row[7] == 0.0f && row[8] == 0.0f) return false;
+	return 0.0f <= row[9] && row[9] <= row[10] && row[10] <= 180.0f;
 }
 
 void skr_scene::build_triangle_materials()
@@ -210,14 +238,22 @@ void skr_scene::build_shadow_masks()
 {
 	shadow_masks.clear();
 	shadow_reach2 = 0.0f;
-	const int ns = info.n_spheres, nl = info.n_point_lights, nt = info.n_triangles;
+	// (a spot light is the point light it geometrically is: its table follows the point lights', in light order)
+	const int ns = info.n_spheres, nl = info.n_point_lights + n_spot(), nt = info.n_triangles;
 	if(ns < 1 || ns > SKR_SHADOW_MAX_SPHERES || nl < 1 || !raw_directional_lights.empty()) return;
+	auto light_pos = [&](int l, double lp[3]) {
+		const skr_f4 &q = lights[2 * (size_t) l];
+		lp[0] = q.x;
+		lp[1] = q.y;
+		lp[2] = q.z;
+	};
 	// reach: the farthest point of the scene (spheres, triangles with their accept regions v0 - e1, v0 + e2) from any light.  The device
 	// checks fl(|Lp - P|^2) <= reach^2 per lane, so a shading point outside it only costs that lane the plain walk.
 	double reach = 0.0;
 	for(int l = 0; l < nl; l++)
 	{
-		const double lp[3] = {raw_point_lights[6 * l], raw_point_lights[6 * l + 1], raw_point_lights[6 * l + 2]};
+		double lp[3];
+		light_pos(l, lp);
 		auto dist = [&](double x, double y, double z) { return std::sqrt((x - lp[0]) * (x - lp[0]) + (y - lp[1]) * (y - lp[1]) + (z - lp[2]) * (z - lp[2])); };
 		for(int k = 0; k < ns; k++)
 			reach = std::max(reach, dist(sph_geom[k].x, sph_geom[k].y, sph_geom[k].z) + std::sqrt((double) sph_geom[k].w));
@@ -242,7 +278,8 @@ void skr_scene::build_shadow_masks()
 	std::vector<uint32_t> masks((size_t) nl * SKR_SHADOW_TABLE_WORDS, 0u);
 	for(int l = 0; l < nl; l++)
 	{
-		const double lp[3] = {raw_point_lights[6 * l], raw_point_lights[6 * l + 1], raw_point_lights[6 * l + 2]};
+		double lp[3];
+		light_pos(l, lp);
 		const double lmax = std::max(std::fabs(lp[0]), std::max(std::fabs(lp[1]), std::fabs(lp[2])));
 		// |o - P| for o = fl(P + 1e-6f) per component, |P| <= |Lp| + D (twice over)
 		const double eps_o = 2.0 * std::sqrt(3.0) * (1e-6 + 0x1p-23 * (lmax + D + 1e-6));
@@ -1194,7 +1231,7 @@ static void set_camera(skr_scene_info &info, const float p[3], const float d[3],
 
 int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene &sc)
 {
-	const bool strict = (flags & SKR_SCN_STRICT) != 0, fog = (flags & SKR_SCN_FOG) != 0;
+	const bool strict = (flags & SKR_SCN_STRICT) != 0, fog = (flags & SKR_SCN_FOG) != 0, spot = (flags & SKR_SCN_SPOT) != 0;
 	FILE *fp = fopen(path.c_str(), "r");
 	if(!fp)
 	{
@@ -1372,6 +1409,21 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 				info.n_fog_skipped++;
 			}
 		}
+		else if(spot && cmd == "spot_light")
+		{ // SKR_SCN_SPOT (the reference does not know the command, scene.cpp:214-217): r g b px py pz dx dy dz angle1 angle2
+			float v[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+			const int got = read_floats(args, v, 11);
+			if(got == 11 && skr_spot_row_ok(v) && sc.n_spot() < SKR_SPOT_MAX_LIGHTS)
+			{
+				if(echo) printf("spot light colour (%f, %f, %f), located at (%f, %f, %f), direction (%f, %f, %f), angles %f %f\n", v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10]);
+				sc.raw_spot_lights.insert(sc.raw_spot_lights.end(), v, v + 11);
+			}
+			else
+			{
+				fprintf(stderr, "WARNING. spot_light needs 11 finite numbers (r g b px py pz dx dy dz angle1 angle2), a direction other than zero and 0 <= angle1 <= angle2 <= 180 (at most %d spot lights): line skipped\n", SKR_SPOT_MAX_LIGHTS);
+				info.n_unknown++;
+			}
+		}
 		else
 		{
 			if(echo) printf("WARNING. Do not know command: %s\n", cmd.c_str());
@@ -1476,6 +1528,45 @@ int skr_scene_get_fog(const skr_scene *scene, float *rows, int32_t *n)
 	if(!scene) return SKR_ERR_ARG;
 	if(n) *n = (int32_t) (scene->raw_fog.size() / 9);
 	if(rows && !scene->raw_fog.empty()) memcpy(rows, scene->raw_fog.data(), scene->raw_fog.size() * 4);
+	return SKR_OK;
+}
+
+int skr_scene_set_spot_lights(skr_scene *scene, const float *rows, int32_t n)
+{
+	if(!scene || n < 0 || n > SKR_SPOT_MAX_LIGHTS || (n && !rows))
+	{
+		skr_set_error("skr_scene_set_spot_lights: bad argument (at most %d spot lights)", SKR_SPOT_MAX_LIGHTS);
+		return SKR_ERR_ARG;
+	}
+	for(int32_t i = 0; i < n; i++)
+		if(!skr_spot_row_ok(rows + (size_t) i * 11))
+		{
+			skr_set_error("skr_scene_set_spot_lights: row %d is not a spot light (11 finite numbers, a direction other than zero, 0 <= angle1 <= angle2 <= 180)", i);
+			return SKR_ERR_ARG;
+		}
+	scene->raw_spot_lights.assign(rows, rows + (size_t) n * 11);
+	scene->build_lights();
+	scene->build_shadow_masks(); // (a spot light has a table like the point light it geometrically is)
+	return SKR_OK;
+}
+
+int skr_scene_get_spot_lights(const skr_scene *scene, float *rows, int32_t *n)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(n) *n = (int32_t) scene->n_spot();
+	if(rows && !scene->raw_spot_lights.empty()) memcpy(rows, scene->raw_spot_lights.data(), scene->raw_spot_lights.size() * 4);
+	return SKR_OK;
+}
+
+int skr_scene_get_spot_cones(const skr_scene *scene, float *cones)
+{
+	if(!scene) return SKR_ERR_ARG;
+	for(int i = 0; cones && i < scene->n_spot(); i++)
+	{
+		const skr_f4 a = scene->spot_cones[2 * (size_t) i], b = scene->spot_cones[2 * (size_t) i + 1];
+		const float row[5] = {a.x, a.y, a.z, a.w, b.x};
+		memcpy(cones + 5 * (size_t) i, row, sizeof row);
+	}
 	return SKR_OK;
 }
 

@@ -27,6 +27,7 @@ struct skr_scene {
 	std::vector<float> raw_point_lights; // [n][6]  position colour
 	std::vector<float> raw_directional_lights; // [n][6] direction colour — --strict-scn only (scene.cpp:139-163 drops them)
 	std::vector<float> raw_fog;          // [n][9] centre radius albedo scattering absorption — SKR_SCN_FOG / skr_scene_set_fog only (file order)
+	std::vector<float> raw_spot_lights;  // [n][11] colour position direction angle1 angle2, the file's fields in file order — SKR_SCN_SPOT / skr_scene_set_spot_lights only
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
 	bool sphere_tree = false;            // SKR_SCN_SPHERE_TREE / skr_scene_set_sphere_tree: likewise
@@ -38,6 +39,8 @@ struct skr_scene {
 	std::vector<skr_f4> sph_kd;   // material.diffuse
 	std::vector<skr_f4> sph_ks;   // material.specular, .w = index of refraction
 	std::vector<skr_f4> lights;   // [2*i] position (.w = 0) or, behind the point lights, direction (.w = 1: --strict-scn), [2*i+1] colour
+	                              // (the spot lights are point-light rows between the point lights and the directional ones: build_lights())
+	std::vector<skr_f4> spot_cones; // 2 per spot light, in file order: {unit axis, c1} {c2, 0, 0, 0} (include/skr.h skr_scene_get_spot_cones)
 	std::vector<skr_f4> tris;     // [3*i] v0, [3*i+1] v1-v0, [3*i+2] v2-v0 (utils.h:183-184 subtractions); [3*i+1].w = the triangle's index in the file (int bits)
 	std::vector<skr_f4> tri_mats; // [3*i] La*ka, power  [3*i+1] kd  [3*i+2] ks of the triangle stored at tris[3*i] (--shade-triangles)
 	// the culling data of the triangle walk: a tree, depth-first with skip links, three float4 per node — {centre, R^2}
@@ -49,6 +52,8 @@ struct skr_scene {
 	int tri_chunk_size = SKR_TRI_CHUNK_MIXED;
 
 	void finalize();
+	void build_lights(); // lights and spot_cones from the raw light arrays
+	int n_spot() const { return (int) (raw_spot_lights.size() / 11); }
 	size_t tri_chunk_stride = 0; // float4 entries per |d| level
 	int tri_node_count = 0;
 	bool tri_any_cone = false; // some chunk has a tight radius for non-grazing rays (scene_host.cpp)
@@ -99,6 +104,10 @@ struct SkrSphereTree {
 	float ball[4] = {0.0f, 0.0f, 0.0f, -1.0f};
 };
 void skr_build_sphere_tree(const skr_scene &scene, SkrSphereTree &out);
+
+// A spot-light row as the loader and skr_scene_set_spot_lights accept it (include/skr.h SKR_SCN_SPOT): every field finite, a direction
+// other than zero, 0 <= angle1 <= angle2 <= 180.
+bool skr_spot_row_ok(const float row[11]);
 
 // scene.cpp:12-227 replacement.  Returns SKR_OK or SKR_ERR_IO.
 int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene &out);

@@ -765,6 +765,88 @@ SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3
 	return total;
 }
 
+// ---- spot lights (include/skr.h SKR_SCN_SPOT; general level pipeline only) ----
+// The cone decision and factor of one light at one shading point: a, c1, c2 as the host derived them (render_params.h SpotLights), L the
+// unit vector from the point to the light (light_term).  One correctly rounded binary32 operation per step; NaN: outside.
+struct SpotCone {
+	float f;      // what the light's colour is multiplied by; 0 where outside
+	bool outside; // the light adds nothing and casts no shadow ray
+};
+SKR_DEV SpotCone spot_cone(f3 a, float c1, float c2, f3 L)
+{
+	const float c = -dot3(a, L);
+	if(c >= c1) return SpotCone{1.0f, false};
+	if(!(c > c2)) return SpotCone{0.0f, true};
+	const float u = sk_divf(c - c2, c1 - c2);
+	return SpotCone{(u * u) * (3.0f - 2.0f * u), false};
+}
+
+// direct_light_of<false>() for a scene with spot lights: the pair loop with the cone decision ahead of the shadow walk.  A pair whose
+// lights are both inside (or no spot lights) is walked as direct_light_of walks it, with the union of both shadow masks; where one
+// light is outside at P the other is walked as a single, with its own mask; where both are, the lane casts nothing.  An outside light
+// counts no shadow ray and no sphere test and meets no triangle.
+template <typename TS = NoTriangleShadows>
+SKR_DEV f3 direct_light_spot(const SceneView &sv, const RenderParams &p, const SpotLights &sp, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn,
+							 const TS &tri_shadows = TS())
+{
+	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
+	const f3 view = normalize3(p.cam_pos - P);
+	for(int i = 0; i < sv.nl; i += 2)
+	{
+		const bool second = i + 1 < sv.nl;
+		LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
+		bool in0 = true, in1 = second;
+		auto cone = [&](int l, LightTerm &t, bool &in)
+		{
+			if((uint32_t) (l - sp.first) < (uint32_t) sp.n)
+			{ // (l is wave-uniform: the rows come through the scalar cache)
+				const float4 A = load_const4(sp.cones, 2 * (l - sp.first)), B = load_const4(sp.cones, 2 * (l - sp.first) + 1);
+				const SpotCone c = spot_cone(ld3(A), A.w, B.x, t.L);
+				in = !c.outside;
+				t.lc = t.lc * c.f; // (per component, before anything else; x * 1 == x)
+			}
+		};
+		cone(i, t0, in0);
+		if(second) cone(i + 1, t1, in1);
+		bool occ0 = !in0, occ1 = !in1; // (dark: occluded, or outside its cone)
+		if(p.use_shadows && (in0 || in1))
+		{ // the rays of the lane: (a, b) = the pair, or a = the one light that is inside
+			const bool both = in0 && in1;
+			const int la = in0 ? i : i + 1;
+			const f3 La = in0 ? t0.L : t1.L;
+			cn.shadow_rays += both ? 2u : 1u;
+			uint32_t cand = 0u;
+			if(sv.smask)
+			{
+				cand = shadow_mask_of(sv, la, ld3(sv.lights[2 * la]) - P);
+				if(both) cand |= shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P);
+			}
+			bool oa, ob;
+			occluded_pair<false>(sv, P, La, t1.L, both, oa, ob, cn.shadow_tests, cand);
+			if constexpr(TS::on) tri_shadows.lights(P, la, i + 1, both, La, t1.L, oa, ob);
+			occ0 = in0 ? oa : true;
+			occ1 = both ? ob : (in1 ? oa : true);
+		}
+		auto add_light = [&](const LightTerm &t, bool lit)
+		{
+			if(lit)
+			{
+				diffuse = diffuse + ((kd * t.lc) * t.intensity) * max0(dot3(N, t.L));
+				const f3 vl = view + t.L;
+				const f3 H = vl / length3(vl);
+				specular = specular + ((ks * t.lc) * t.intensity) * powf_spec(max0(dot3(N, H)), ambp.w, p.pow_steps);
+			}
+		};
+		add_light(t0, !occ0);
+		add_light(t1, !occ1);
+	}
+	f3 total = mk3(0, 0, 0);
+	total = total + ld3(ambp);
+	total = total + diffuse;
+	total = total + specular;
+	return total;
+}
+
 template <bool COHERENT>
 SKR_DEV f3 direct_light(const SceneView &sv, const RenderParams &p, int sph, f3 P, f3 N, Counters &cn)
 {

@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--strict-scn] [--scn-fog] [--scn-spot] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
            [--adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
@@ -84,6 +84,8 @@ def _parse(argv):
             opt["strict_scn"] = True
         elif a == "--scn-fog":
             opt["scn_fog"] = True
+        elif a == "--scn-spot":
+            opt["scn_spot"] = True
         elif a == "--scn-fov":
             opt["scn_fov"] = True
         elif a == "--shade-triangles":
@@ -161,7 +163,7 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=dev)  # RCCL over xGMI
     try:
         scene = skr.parse_scene(o["path"], strict=bool(o.get("strict_scn")), fog=bool(o.get("scn_fog")), triangle_shadows=bool(o.get("triangle_shadows")),
-                                sphere_tree=bool(o.get("sphere_tree")))
+                                sphere_tree=bool(o.get("sphere_tree")), spot=bool(o.get("scn_spot")))
     except skr.SkrError as e:
         if rank == 0:
             print(str(e))  # scene.cpp:24: "Can't open file" on stdout, exit(0)
