@@ -45,6 +45,8 @@ struct DeviceScene {
 	size_t off_spot = 0;      // --scn-spot: 2 rows per spot light behind the fog rows (render_params.h SpotLights)
 	int n_spot = 0, spot_first = 0; // lights [spot_first, spot_first + n_spot) of the light table are spot lights
 	size_t off_smask = 0;     // the shadow masks (skr_scene::shadow_masks, 4 per row), 0 = none
+	size_t off_ssurf = 0;     // their surface patches (skr_scene::shadow_surface: ssurf_stride words per pair of lights), 0 = none
+	uint32_t ssurf_stride = 0;
 	float shadow_reach2 = 0.0f;
 	size_t off_gi = 0;        // the GI masks (skr_scene::gi_table, 4 words per row), 0 = none
 	SkrGiGrid gi_grid[2] = {};
@@ -147,9 +149,10 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_NO_SPHERE_CULL")) sw.no_sphere_cull = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_LEVELS_BUDGET_MB")) sw.budget_mb = atoi(e) > 0 ? atoi(e) : 1;
 	if(const char *e = getenv("SKR_FLAT")) sw.flat = atoi(e) > 0 ? 1 : -1;
-	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = atoi(e) > 0 ? 1 : 0;
+	if(const char *e = getenv("SKR_SHADOW_MASK")) sw.shadow_mask = (sw.shadow_mask & ~1) | (atoi(e) > 0 ? 1 : 0);
 	if(const char *e = getenv("SKR_GI_MASK")) sw.gi_mask = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_GI_SURFACE")) sw.gi_surface = atoi(e) > 0 ? 1 : 0;
+	if(const char *e = getenv("SKR_SHADOW_SURFACE")) sw.shadow_mask = (sw.shadow_mask & ~2) | (atoi(e) > 0 ? 2 : 0);
 	if(const char *e = getenv("SKR_PRIMARY_CACHE")) sw.primary_cache = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_ADAPTIVE_PATH")) sw.adaptive_path = !strcmp(e, "frame") ? 1 : !strcmp(e, "query") ? 2 : 0;
 }
@@ -200,6 +203,12 @@ static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 	d.off_spot = put4(s.spot_cones);
 	if(!s.shadow_masks.empty()) d.off_smask = put(s.shadow_masks.data(), s.shadow_masks.size() * 4);
 	d.shadow_reach2 = s.shadow_reach2;
+	if(!s.shadow_surface.empty())
+	{ // the surface patches of the shadow masks; a sphere's header word rides in the .w of its kd row (shadow_cells.h)
+		d.off_ssurf = put(s.shadow_surface.data(), s.shadow_surface.size() * 4);
+		d.ssurf_stride = s.shadow_surface_stride;
+		for(size_t k = 0; k < s.shadow_surface_head.size(); k++) memcpy(&rows[d.off_kd + k].w, &s.shadow_surface_head[k], 4);
+	}
 	if(!s.gi_table.empty())
 	{ // the GI masks (whole rows: scene_host.cpp build_gi_masks), with the surface patches' masks right behind the grids' masks (their
 	  // rows continue the grids' rows), then the patches' headers and index
@@ -483,11 +492,16 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 	p.tri_chunks = s.d_blob + s.off_chunks;
 	p.tri_chunk_size = s.chunk_size;
 	p.tri_cones = (s.cones && !r->sw.no_cones) ? 1 : 0;
-	if(s.off_smask && r->sw.shadow_mask)
+	if(s.off_smask && (r->sw.shadow_mask & 1))
 	{ // the level pipelines' shadow walk visits only the spheres a lane's masks name (shade_common.h occluded_pair)
 		p.shadow_masks = reinterpret_cast<const uint32_t *>(s.d_blob + s.off_smask);
 		p.shadow_reach2 = s.shadow_reach2;
 		p.shadow_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
+		if(s.off_ssurf && (r->sw.shadow_mask & 2))
+		{ // ... a hit of a sphere takes them from that sphere's surface patch (shade_common.h shadow_cands)
+			p.shadow_surface_word = (uint32_t) ((s.off_ssurf - s.off_smask) * 4); // (rows of 4 words; the patches follow the masks in the blob)
+			p.shadow_surface_stride = s.ssurf_stride;
+		}
 	}
 	if(s.off_gi && r->sw.gi_mask)
 	{ // the node pipeline's closest-hit walk of a GI child visits only the spheres its masks name (wave_common.h closest_pair)

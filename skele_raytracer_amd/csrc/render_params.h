@@ -33,7 +33,8 @@ struct SkrSwitches {
 	int8_t no_sphere_cull = 0;         // SKR_NO_SPHERE_CULL: a renderer on the sphere tree runs the loop over every sphere in every wave (the A/B arm of DESIGN.md 8.10)
 	int32_t budget_mb = 0;            // SKR_LEVELS_BUDGET_MB: scratch budget of the level pipelines (0 = default)
 	int32_t flat = 0;                 // SKR_FLAT = 1 | 0: the node pipeline's flat schedule forced on (+1) / off (-1); unset: by launch size
-	int8_t shadow_mask = 1;           // SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere
+	int8_t shadow_mask = 3;           // bit 0: SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere;
+	                                  // bit 1: SKR_SHADOW_SURFACE = 1 | 0: a shading point on a sphere takes its mask from the surface patches / the direction masks only
 	int8_t gi_mask = 1;               // SKR_GI_MASK = 1 | 0: the same for the closest-hit walk of the node pipeline's GI children
 	int8_t gi_surface = 1;            // SKR_GI_SURFACE = 1 | 0: GI origins on a sphere take their row of masks from the surface patches / the 3D grids only
 	int8_t adaptive_path = 0;         // SKR_ADAPTIVE_PATH = frame | query: the path of every adaptive round (+1 / +2); unset: by active share (four quarters of one word, as above)
@@ -64,6 +65,10 @@ struct RenderParams {
 	int32_t monte_carlo, num_path_traces, grid_size, max_depth, use_shadows;
 	uint32_t seed_lo, seed_hi;
 	int32_t pow_steps;        // bit length of the scene's largest integer phong exponent in [1, 1024] (device_math.h powf_spec): 1 .. 11
+	// the surface patches of the shadow masks (shadow_cells.h; shade_common.h shadow_cands), in the scene blob behind the shadow masks: one
+	// table of shadow_surface_stride words (below) per pair of lights, the first at word shadow_surface_word from shadow_masks; a sphere's
+	// header word is the .w of its kd row.  0 = the direction masks only.  Both words sit in alignment holes, as fog_row does.
+	uint32_t shadow_surface_word;
 	// outputs (device)
 	uint8_t *rgb;
 	float *rgbf;
@@ -85,6 +90,7 @@ struct RenderParams {
 	const float4 *ns_src;     // shading rows of the nodes whose children are summed (finalize, the depth-2 leaf kernel)
 	float4 *nd_dst, *ns_dst;  // nodes being written (primary hits; activated records)
 	uint32_t nd_src_level0;   // nd_src / ns_src hold the primary hits
+	uint32_t shadow_surface_stride; // (see shadow_surface_word)
 	const uint32_t *nd_count; // number of nodes in nd_src
 	float4 *rc;               // hit records of the level being produced (trace) or consumed (activate, leaf): [parent, sphere | child << 16, r1, r2]
 	uint32_t rc_cap;          // records per region (SKR_P1_REGIONS regions)
@@ -130,6 +136,9 @@ struct RenderParams {
 	// grids only.
 	const uint32_t *gi_surface;
 };
+// (a by-value kernel argument: the hidden arguments and every kernel's further arguments follow it, so a change of its size moves their
+// offsets in every kernel, and with them the code of kernels that no change meant to touch)
+static_assert(sizeof(RenderParams) == 624, "RenderParams keeps its size: new fields go into its alignment holes");
 
 // The sphere tree (include/skr.h skr_scene_set_sphere_tree): what the sphere walks of the general level pipeline read
 // (shade_common.h stree_walk), handed to the instances that have the walks in a kernel argument of their own — RenderParams, and with it

@@ -127,6 +127,7 @@ void skr_scene::finalize()
 	build_shadow_masks();
 	build_gi_masks();
 	build_gi_surface();
+	build_shadow_surface(); // (behind the GI patches: it takes its cell edge from theirs)
 }
 
 // The light table: point lights first, then the spot lights (SKR_SCN_SPOT: point-light rows at their positions, the cone is the
@@ -306,36 +307,58 @@ void skr_scene::build_shadow_masks()
 
 // Bit `bit` (sphere of centre C, squared radius r2) of every direction cell of a GI mask row, for origins in the ball (q, rho)
 // (build_gi_masks' margins; cth, sth: the cosine and sine of each direction cell's padded angular radius).  All in binary64.
+// (the ball of origins against one sphere: what every direction cone of ball_cone_touches shares)
+struct BallSphere {
+	double v[3], dist; // C - q and its length
+	double rk;         // the grown radius r': the slack of the binary32 discriminant
+	double behind, reach;
+	bool meets; // the grown sphere meets the ball: every direction
+};
+static BallSphere ball_sphere(const double *q, double rho, const double *C, double r2)
+{
+	BallSphere b;
+	for(int c = 0; c < 3; c++) b.v[c] = C[c] - q[c];
+	b.dist = std::sqrt(b.v[0] * b.v[0] + b.v[1] * b.v[1] + b.v[2] * b.v[2]);
+	const double E = (b.dist + rho) * (1.0 + 0x1p-20); // bounds |e| = |o - C| of the device's test
+	b.rk = std::sqrt(r2 + 0x1p-16 * (E * E + r2)) + 0x1p-20 * E; // discriminant slack (16x), the rounding of e
+	const double tol = 0x1p-30 * (b.dist + rho + b.rk);           // (this function's own rounding)
+	b.behind = rho + 0x1p-16 * E + tol;                            // b < 0 needs (C - o).d > -2^-22 |e| |d|
+	b.reach = b.rk + rho + tol;
+	b.meets = b.dist <= b.reach;
+	return b;
+}
+// The two rules of build_gi_masks for the lines along the directions of the cone of unit axis w and half-angle theta (ct, st: its
+// cosine and sine) through the points of a ball, v = C - (the ball's centre), dist = |v|.  cone_ahead: the sphere may lie ahead of
+// some origin (the half-line rule: b < 0); cone_line_touches: some line may pass within `reach` of C (the line rule: D >= 0).
+struct ConeSphere {
+	double cos_lo, min_sin; // the cosine of the smallest angle between v and a direction of the cone; the smallest sine, either sense
+};
+static ConeSphere cone_sphere(const double *v, double dist, const double *w, double ct, double st)
+{
+	const double cp = (v[0] * w[0] + v[1] * w[1] + v[2] * w[2]) / dist;
+	const double x = v[1] * w[2] - v[2] * w[1], y = v[2] * w[0] - v[0] * w[2], z = v[0] * w[1] - v[1] * w[0];
+	const double sp = std::sqrt(x * x + y * y + z * z) / dist;
+	const bool lo0 = cp >= ct;   // phi <= theta
+	const bool hipi = cp <= -ct; // phi + theta >= pi
+	const double sin_lo = lo0 ? 0.0 : sp * ct - cp * st;
+	const double sin_hi = hipi ? 0.0 : sp * ct + cp * st;
+	return ConeSphere{lo0 ? 1.0 : cp * ct + sp * st, std::max(0.0, std::min(sin_lo, sin_hi))};
+}
+static bool cone_ahead(const ConeSphere &c, double dist, double behind) { return dist * c.cos_lo + behind >= 0.0; }
+static bool cone_line_touches(const ConeSphere &c, double dist, double reach) { return dist * c.min_sin <= reach; }
+// Whether a ray from the ball along some direction of the cone may have D >= 0 and b < 0 for the sphere.
+static bool ball_cone_touches(const BallSphere &b, const double *w, double ct, double st)
+{
+	if(b.meets) return true;
+	const ConeSphere c = cone_sphere(b.v, b.dist, w, ct, st);
+	return cone_ahead(c, b.dist, b.behind) && cone_line_touches(c, b.dist, b.reach);
+}
 static void gi_ball_bits(const double *q, double rho, const double *C, double r2, uint32_t bit, const std::vector<double> &cell_dir,
 						 const std::vector<double> &cth, const std::vector<double> &sth, uint32_t *row)
 {
-	const double v[3] = {C[0] - q[0], C[1] - q[1], C[2] - q[2]};
-	const double dist = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-	const double E = (dist + rho) * (1.0 + 0x1p-20); // bounds |e| = |o - C| of the device's test
-	const double rk = std::sqrt(r2 + 0x1p-16 * (E * E + r2)) + 0x1p-20 * E; // discriminant slack (16x), the rounding of e
-	const double tol = 0x1p-30 * (dist + rho + rk);                         // (this function's own rounding)
-	const double behind = rho + 0x1p-16 * E + tol;                           // b < 0 needs (C - o).d > -2^-22 |e| |d|
-	const double reach = rk + rho + tol;
-	if(dist <= reach)
-	{ // the grown sphere meets the cell: every direction
-		for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++) row[e] |= bit;
-		return;
-	}
+	const BallSphere b = ball_sphere(q, rho, C, r2);
 	for(int e = 0; e < SKR_GI_ROW_ENTRIES; e++)
-	{
-		const double *w = &cell_dir[3 * (size_t) e];
-		const double cp = (v[0] * w[0] + v[1] * w[1] + v[2] * w[2]) / dist;
-		const double x = v[1] * w[2] - v[2] * w[1], y = v[2] * w[0] - v[0] * w[2], z = v[0] * w[1] - v[1] * w[0];
-		const double sp = std::sqrt(x * x + y * y + z * z) / dist;
-		const double ct = cth[e], st = sth[e];
-		const bool lo0 = cp >= ct;   // phi <= theta
-		const bool hipi = cp <= -ct; // phi + theta >= pi
-		const double cos_lo = lo0 ? 1.0 : cp * ct + sp * st;
-		const double sin_lo = lo0 ? 0.0 : sp * ct - cp * st;
-		const double sin_hi = hipi ? 0.0 : sp * ct + cp * st;
-		const double min_sin = std::max(0.0, std::min(sin_lo, sin_hi));
-		if(dist * cos_lo + behind >= 0.0 && dist * min_sin <= reach) row[e] |= bit;
-	}
+		if(ball_cone_touches(b, &cell_dir[3 * (size_t) e], cth[e], sth[e])) row[e] |= bit;
 }
 
 // The GI masks (shadow_cells.h; DESIGN.md "GI masks" derives every margin below).  A GI child ray starts at its node's hit point o
@@ -494,17 +517,67 @@ void skr_scene::build_gi_masks()
 // origin of the patch may see at an angle of 90 degrees or more from its own e (b >= 0 otherwise).  Patches are stored where their
 // ball meets the fine grid's box (the small spheres and the ground under them); the cells grow by 1.15x until the whole table
 // fits SKR_GI_MAX_BYTES.  A device lane off every stored patch takes the grids' row (shade_common.h gi_surface_row).  All in binary64.
+// (the shell of a sphere's surface points and the ball of one patch of it: shared with build_shadow_surface)
+struct SurfaceShell {
+	float tau;         // the radial slack: |fl(|e|^2) - r^2| <= tau; negative: no patches
+	double R_lo, R_hi; // every keyed point has R_lo <= |o - C| <= R_hi
+};
+static SurfaceShell surface_shell(double r2)
+{
+	SurfaceShell sh;
+	// |fl(|e|^2) - r^2| <= tau gives (r^2 - tau)(1 - 2^-20) <= |fl(e)|^2 <= (r^2 + tau)(1 + 2^-20) (the dot product's and the
+	// difference's rounding), and |e| is within 2^-23 |e| of |fl(e)|
+	sh.tau = std::sqrt(r2) > 1e-3 ? (float) (r2 * 0x1p-7) : -1.0f; // (|o - C| within about r / 256 of r; tiny spheres: no patches)
+	sh.R_lo = std::sqrt(std::max(0.0, (r2 - sh.tau) * (1.0 - 0x1p-20))) * (1.0 - 0x1p-22);
+	sh.R_hi = std::sqrt((r2 + std::max(0.0f, sh.tau)) * (1.0 + 0x1p-20)) * (1.0 + 0x1p-22);
+	return sh;
+}
+// The ball (q, rho) of the patch of sphere (C, rad) whose cell has the unit centre direction w and the padded angular radius th.
+static void surface_patch_ball(const double *C, double rad, const SurfaceShell &sh, const double *w, double th, double *q, double &rho)
+{
+	const double h = rad * std::cos(th);
+	for(int c = 0; c < 3; c++) q[c] = C[c] + h * w[c];
+	// the farthest point of the patch from q: |o - q|^2 = R^2 + h^2 - 2 R h cos(phi) grows with phi and is convex in R
+	double far = 0.0;
+	for(double R : {sh.R_lo, sh.R_hi}) far = std::max(far, std::sqrt(std::max(0.0, R * R + h * h - 2.0 * R * h * std::cos(th))));
+	double cmax = 0.0;
+	for(int c = 0; c < 3; c++) cmax = std::max(cmax, std::fabs(C[c]));
+	rho = far * (1.0 + 0x1p-20) + 0x1p-30 * (cmax + rad);
+}
+// The padded angular radii of a sphere's G x G x 6 cells (cube_cells) as the patches use them: + the angle between e and fl(e)
+static void surface_cells(int g, std::vector<double> &dir, std::vector<double> &theta)
+{
+	dir.clear();
+	theta.clear();
+	if(g) cube_cells(g, dir, theta);
+	for(double &t : theta) t = t * (1.0 + 0x1p-20) + 0x1p-20; // (2^-23 of each component)
+}
+// The first cell edge the GI patches try: half the one at which the small spheres' patches alone (about 24 r^2 / edge^2 each) fill a
+// table of `rows` rows.
+static double surface_first_edge(const std::vector<double> &rad, const std::vector<double> &r2, double rows)
+{
+	const int ns = (int) rad.size();
+	std::vector<double> sorted(rad);
+	std::sort(sorted.begin(), sorted.end());
+	double small_area = 0.0;
+	for(int k = 0; k < ns; k++)
+		if(rad[k] <= 4.0 * sorted[ns / 2]) small_area += 24.0 * r2[k];
+	return std::max(1e-6, 0.5 * std::sqrt(small_area / std::max(1.0, rows)));
+}
+
 void skr_scene::build_gi_surface()
 {
 	gi_surface.clear();
 	gi_surface_head = 0;
 	gi_rows = 0;
+	gi_surface_edge = 0.0;
 	if(gi_table.empty()) return;
 	const int ns = info.n_spheres;
 	const size_t row_words = (size_t) SKR_GI_ROW_ENTRIES * (gi_wide ? 4 : 2) / 4;
 	gi_rows = (uint32_t) ((gi_table.size() - gi_mask_word) / row_words); // (the table's padding is below one row)
 	std::vector<double> C((size_t) 3 * ns), r2(ns), rad(ns), R_lo(ns), R_hi(ns);
 	std::vector<float> tau(ns);
+	std::vector<SurfaceShell> shell(ns);
 	for(int k = 0; k < ns; k++)
 	{
 		C[3 * k] = sph_geom[k].x;
@@ -512,11 +585,10 @@ void skr_scene::build_gi_surface()
 		C[3 * k + 2] = sph_geom[k].z;
 		r2[k] = sph_geom[k].w;
 		rad[k] = std::sqrt(r2[k]);
-		// the radial slack: |fl(|e|^2) - r^2| <= tau gives (r^2 - tau)(1 - 2^-20) <= |fl(e)|^2 <= (r^2 + tau)(1 + 2^-20) (the dot product's
-		// and the difference's rounding), and |e| is within 2^-23 |e| of |fl(e)|
-		tau[k] = rad[k] > 1e-3 ? (float) (r2[k] * 0x1p-7) : -1.0f; // (|o - C| within about r / 256 of r; tiny spheres: no patches)
-		R_lo[k] = std::sqrt(std::max(0.0, (r2[k] - tau[k]) * (1.0 - 0x1p-20))) * (1.0 - 0x1p-22);
-		R_hi[k] = std::sqrt((r2[k] + std::max(0.0f, tau[k])) * (1.0 + 0x1p-20)) * (1.0 + 0x1p-22);
+		shell[k] = surface_shell(r2[k]);
+		tau[k] = shell[k].tau;
+		R_lo[k] = shell[k].R_lo;
+		R_hi[k] = shell[k].R_hi;
 	}
 	double blo[3], bhi[3]; // the fine grid's box
 	for(int c = 0; c < 3; c++)
@@ -533,13 +605,7 @@ void skr_scene::build_gi_surface()
 	std::vector<std::vector<double>> cdir(ns), cth(ns); // per sphere: its cells' centre directions and padded angular radii
 	size_t n_index = 0;
 	bool fits = false;
-	// the first edge tried: half the one at which the small spheres' patches alone (about 24 r^2 / edge^2 each) fill the table
-	std::vector<double> sorted(rad);
-	std::sort(sorted.begin(), sorted.end());
-	double small_area = 0.0;
-	for(int k = 0; k < ns; k++)
-		if(rad[k] <= 4.0 * sorted[ns / 2]) small_area += 24.0 * r2[k];
-	double edge = std::max(1e-6, 0.5 * std::sqrt(small_area / std::max(1.0, (double) SKR_GI_MAX_BYTES / (row_words * 4))));
+	double edge = surface_first_edge(rad, r2, (double) SKR_GI_MAX_BYTES / (row_words * 4)), used_edge = 0.0;
 	for(int attempt = 0; attempt < 200 && !fits; attempt++, edge *= 1.15)
 	{
 		patches.clear();
@@ -550,27 +616,15 @@ void skr_scene::build_gi_surface()
 			if(g != G[k])
 			{
 				G[k] = g;
-				cdir[k].clear();
-				cth[k].clear();
-				if(g) cube_cells(g, cdir[k], cth[k]);
-				// + the angle between e and fl(e) (2^-23 of each component)
-				for(double &t : cth[k]) t = t * (1.0 + 0x1p-20) + 0x1p-20;
+				surface_cells(g, cdir[k], cth[k]);
 			}
 			n_index += (size_t) 6 * g * g;
 			for(int cell = 0; cell < 6 * g * g; cell++)
 			{
-				const double *w = &cdir[k][3 * (size_t) cell];
-				const double th = cth[k][cell], h = rad[k] * std::cos(th);
 				Patch pt;
 				pt.s = k;
 				pt.cell = cell;
-				for(int c = 0; c < 3; c++) pt.q[c] = C[3 * k + c] + h * w[c];
-				// the farthest point of the patch from q: |o - q|^2 = R^2 + h^2 - 2 R h cos(phi) grows with phi and is convex in R
-				double far = 0.0;
-				for(double R : {R_lo[k], R_hi[k]}) far = std::max(far, std::sqrt(std::max(0.0, R * R + h * h - 2.0 * R * h * std::cos(th))));
-				double cmax = 0.0;
-				for(int c = 0; c < 3; c++) cmax = std::max(cmax, std::fabs(C[3 * k + c]));
-				pt.rho = far * (1.0 + 0x1p-20) + 0x1p-30 * (cmax + rad[k]);
+				surface_patch_ball(&C[3 * k], rad[k], shell[k], &cdir[k][3 * (size_t) cell], cth[k][cell], pt.q, pt.rho);
 				double gap2 = 0.0; // from q to the box
 				for(int c = 0; c < 3; c++)
 				{
@@ -581,8 +635,10 @@ void skr_scene::build_gi_surface()
 			}
 		}
 		fits = (SKR_GI_SURFACE_HEAD * (size_t) ns + n_index) * 4 + patches.size() * row_words * 4 <= SKR_GI_MAX_BYTES;
+		if(fits) used_edge = edge;
 	}
 	if(!fits || patches.empty()) return;
+	gi_surface_edge = used_edge;
 	std::vector<double> cell_dir, cell_theta;
 	cube_cells(SKR_GI_DIR_CELLS, cell_dir, cell_theta);
 	std::vector<double> dth(SKR_GI_ROW_ENTRIES), dct(SKR_GI_ROW_ENTRIES), dst(SKR_GI_ROW_ENTRIES);
@@ -635,6 +691,124 @@ void skr_scene::build_gi_surface()
 		index[head[SKR_GI_SURFACE_HEAD * patches[pi].s] - SKR_GI_SURFACE_HEAD * ns + patches[pi].cell] = (int32_t) (gi_rows + pi);
 	gi_surface_head = (uint32_t) n_mask_words;
 	gi_surface.swap(table);
+}
+
+// The surface patches of the shadow masks (shadow_cells.h; DESIGN.md "Shadow surface patches" derives every margin below).  A shading
+// point P of the level pipelines is a hit point of some sphere s, so the device keys it to the cell of e = P - C_s in a cube map on
+// that sphere, once fl(|e|^2) - r_s^2 is within the sphere's radial slack: P lies in build_gi_surface's patch ball, the shadow
+// ray's origin o = fl(P + 1e-6) within eps_o of it, and its direction in the cone about Lp - q of half-angle asin(rho / |Lp - q|),
+// + eta for the device's normalize.  Bit k of a patch's word is set unless, for both lights of the pair, sphere k fails
+// build_gi_masks' half-line rule for every such ray (from the patch's ball) or its line rule (taken from the light, which every
+// ray's line passes almost through); the patch's own sphere follows build_gi_surface's own-sphere rule (clear where every ray leaves
+// the sphere), and a light inside the ball sets every bit.  Every patch of every sphere is stored (one word each), at
+// SKR_SHADOW_SURFACE_SCALE cells per edge of a GI patch's cell, the cells growing by 1.15x until every pair's table together fits
+// SKR_SHADOW_SURFACE_MAX_BYTES.  All in binary64.
+void skr_scene::build_shadow_surface(double rho_scale, double cone_scale)
+{
+	shadow_surface.clear();
+	shadow_surface_head.clear();
+	shadow_surface_stride = 0;
+	if(shadow_masks.empty()) return;
+	const int ns = info.n_spheres, nl = (int) (shadow_masks.size() / SKR_SHADOW_TABLE_WORDS), npairs = (nl + 1) / 2;
+	std::vector<double> C((size_t) 3 * ns), r2(ns), rad(ns);
+	std::vector<SurfaceShell> shell(ns);
+	for(int k = 0; k < ns; k++)
+	{
+		C[3 * k] = sph_geom[k].x;
+		C[3 * k + 1] = sph_geom[k].y;
+		C[3 * k + 2] = sph_geom[k].z;
+		r2[k] = sph_geom[k].w;
+		rad[k] = std::sqrt(r2[k]);
+		for(int c = 0; c < 3; c++)
+			if(!(std::fabs(C[3 * k + c]) < 1e6)) return;
+		if(!(rad[k] < 1e6)) return; // (NaN, inf, out of the range the margins are derived for: the direction masks only)
+		shell[k] = surface_shell(r2[k]);
+	}
+	// the GI patches' edge, or what they would try first where the scene has none (triangles)
+	double edge = gi_surface_edge > 0.0 ? gi_surface_edge : surface_first_edge(rad, r2, (double) SKR_GI_MAX_BYTES / (SKR_GI_ROW_ENTRIES * (ns > 16 ? 4 : 2)));
+	edge /= SKR_SHADOW_SURFACE_SCALE;
+	std::vector<int> G(ns, 0);
+	size_t stride = 0;
+	for(int attempt = 0; attempt < 200; attempt++, edge *= 1.15)
+	{
+		stride = 0;
+		for(int k = 0; k < ns; k++)
+		{
+			G[k] = shell[k].tau < 0.0f ? 0 : (int) std::min((double) SKR_GI_SURFACE_MAX_CELLS, std::max(1.0, std::ceil(2.0 * rad[k] / edge)));
+			stride += (size_t) 6 * G[k] * G[k];
+		}
+		if(stride * npairs * 4 <= SKR_SHADOW_SURFACE_MAX_BYTES) break;
+	}
+	if(stride == 0 || stride * npairs * 4 > SKR_SHADOW_SURFACE_MAX_BYTES) return;
+	const uint32_t all = ns >= 32 ? 0xffffffffu : (1u << ns) - 1u;
+	const double eta = 0x1p-15; // the angle between the device's L = normalize(fl(Lp - P)) and Lp - P (2^-23 or so: far over)
+	std::vector<uint32_t> table(stride * npairs, 0u), head(ns, 0u);
+	std::vector<double> cdir, cth;
+	std::vector<BallSphere> bs(ns);
+	size_t base = 0;
+	for(int s = 0; s < ns; s++)
+	{
+		head[s] = (uint32_t) base | (uint32_t) G[s] << 24;
+		surface_cells(G[s], cdir, cth);
+		double cmax = 0.0;
+		for(int c = 0; c < 3; c++) cmax = std::max(cmax, std::fabs(C[3 * s + c]));
+		// |o - P| for o = fl(P + 1e-6f) per component (twice over, as build_shadow_masks)
+		const double eps_o = 2.0 * std::sqrt(3.0) * (1e-6 + 0x1p-23 * (cmax + shell[s].R_hi + 1e-6));
+		const double R_in = shell[s].R_lo - eps_o;                       // |o - C_s| at least
+		const double E_own = (shell[s].R_hi + eps_o) * (1.0 + 0x1p-20); // ... and at most
+		const double behind_own = 0x1p-16 * E_own + 0x1p-30 * shell[s].R_hi;
+		const double tilt = R_in > 0.0 ? std::asin(std::min(1.0, eps_o / shell[s].R_lo)) : 0.0; // the angle between o - C_s and P - C_s
+		for(int cell = 0; cell < 6 * G[s] * G[s]; cell++)
+		{
+			const double *wp = &cdir[3 * (size_t) cell];
+			double q[3], rho;
+			surface_patch_ball(&C[3 * s], rad[s], shell[s], wp, cth[cell], q, rho);
+			rho = (rho + eps_o) * rho_scale;
+			for(int k = 0; k < ns; k++)
+				if(k != s) bs[k] = ball_sphere(q, rho, &C[3 * k], r2[k]);
+			for(int l = 0; l < nl; l++)
+			{
+				uint32_t &word = table[(size_t) (l >> 1) * stride + base + cell];
+				const skr_f4 &lp = lights[2 * (size_t) l];
+				const double d[3] = {lp.x - q[0], lp.y - q[1], lp.z - q[2]};
+				const double dl = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+				if(!(dl > rho * (1.0 + 0x1p-20) + 0x1p-30 * (cmax + rad[s])))
+				{ // the light inside the ball: any direction
+					word = all;
+					continue;
+				}
+				const double w[3] = {d[0] / dl, d[1] / dl, d[2] / dl};
+				const double theta = (std::asin(std::min(1.0, rho / dl)) * (1.0 + 0x1p-20) + eta) * cone_scale;
+				const double ct = std::cos(theta), st = std::sin(theta);
+				// every ray's line passes within near_l of Lp: |o - P|, and the error of L over the way to the light
+				const double near_l = eps_o + eta * (dl + rho) * (1.0 + 0x1p-20);
+				const double lpd[3] = {lp.x, lp.y, lp.z};
+				for(int k = 0; k < ns; k++)
+				{
+					if(k == s) continue;
+					// the half-line rule from the patch's ball; the line rule from the light, where the lines (nearly) meet: the
+					// distance from C to a line grows with the distance from Lp, not with the width of the patch
+					const BallSphere &b = bs[k];
+					const bool ahead = b.meets || cone_ahead(cone_sphere(b.v, b.dist, w, ct, st), b.dist, b.behind);
+					const double vl[3] = {C[3 * k] - lpd[0], C[3 * k + 1] - lpd[1], C[3 * k + 2] - lpd[2]};
+					const double distl = std::sqrt(vl[0] * vl[0] + vl[1] * vl[1] + vl[2] * vl[2]);
+					const double reach_l = b.rk + near_l + 0x1p-30 * (distl + dl + b.rk);
+					const bool line = distl <= reach_l || cone_line_touches(cone_sphere(vl, distl, w, ct, st), distl, reach_l);
+					if(ahead && line) word |= 1u << k;
+				}
+				// sphere s: (C - o).L = -|o - C| cos(angle(o - C, L)), and that angle is at most psi + theta_patch + tilt + theta; below 90
+				// degrees b < 0 needs R_in cos(.) < 2^-16 E (the rounding of b, as in build_gi_masks)
+				const double x = wp[1] * w[2] - wp[2] * w[1], y = wp[2] * w[0] - wp[0] * w[2], z = wp[0] * w[1] - wp[1] * w[0];
+				const double psi = std::atan2(std::sqrt(x * x + y * y + z * z), wp[0] * w[0] + wp[1] * w[1] + wp[2] * w[2]);
+				const double ang = psi + cth[cell] + tilt + theta + 0x1p-30;
+				if(!(R_in > 0.0 && ang < 0.5 * M_PI && R_in * std::cos(ang) > behind_own)) word |= 1u << s;
+			}
+		}
+		base += (size_t) 6 * G[s] * G[s];
+	}
+	shadow_surface_stride = (uint32_t) stride;
+	shadow_surface.swap(table);
+	shadow_surface_head.swap(head);
 }
 
 // Exact-preserving culling data for the triangle walk (DESIGN.md "Triangle chunks").
@@ -1547,6 +1721,7 @@ int skr_scene_set_spot_lights(skr_scene *scene, const float *rows, int32_t n)
 	scene->raw_spot_lights.assign(rows, rows + (size_t) n * 11);
 	scene->build_lights();
 	scene->build_shadow_masks(); // (a spot light has a table like the point light it geometrically is)
+	scene->build_shadow_surface();
 	return SKR_OK;
 }
 
@@ -1742,6 +1917,26 @@ int skr_scene_get_gi_surface(const skr_scene *scene, int32_t *n_words, int32_t *
 	if(head_word) *head_word = (int32_t) scene->gi_surface_head;
 	if(first_row) *first_row = (int32_t) scene->gi_rows;
 	if(table && !scene->gi_surface.empty()) memcpy(table, scene->gi_surface.data(), scene->gi_surface.size() * 4);
+	return SKR_OK;
+}
+
+// Internal (not in include/skr.h: tests only): the surface patches of the shadow masks (skr_scene::shadow_surface): the pairs' tables
+// and the one header word per sphere.  skr_scene_rebuild_shadow_surface builds them again with the patch ball and the light cone
+// scaled (1, 1: the product's), for the tests that shrink the margins.
+int skr_scene_get_shadow_surface(const skr_scene *scene, int32_t *n_pairs, int32_t *stride, uint32_t *head, uint32_t *table)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(stride) *stride = (int32_t) scene->shadow_surface_stride;
+	if(n_pairs) *n_pairs = scene->shadow_surface_stride ? (int32_t) (scene->shadow_surface.size() / scene->shadow_surface_stride) : 0;
+	if(head && !scene->shadow_surface_head.empty()) memcpy(head, scene->shadow_surface_head.data(), scene->shadow_surface_head.size() * 4);
+	if(table && !scene->shadow_surface.empty()) memcpy(table, scene->shadow_surface.data(), scene->shadow_surface.size() * 4);
+	return SKR_OK;
+}
+
+int skr_scene_rebuild_shadow_surface(skr_scene *scene, double rho_scale, double cone_scale)
+{
+	if(!scene) return SKR_ERR_ARG;
+	scene->build_shadow_surface(rho_scale, cone_scale);
 	return SKR_OK;
 }
 

@@ -87,7 +87,14 @@ struct skr_scene {
 	std::vector<uint32_t> gi_surface;
 	uint32_t gi_surface_head = 0;
 	uint32_t gi_rows = 0; // rows of masks of the grids in gi_table
+	double gi_surface_edge = 0.0; // the patches' cell edge (G_s = ceil(2 r_s / edge)); 0 = no patches
 	void build_gi_surface();
+	// the surface patches of the shadow masks (shadow_cells.h, DESIGN.md "Shadow surface patches"): one table of shadow_surface_stride
+	// words per pair of lights, in pair order, and one header word per sphere (base | G << 24); empty where there are no shadow masks.
+	// rho_scale, cone_scale: the tests' shrunk margins (1 = the product's)
+	std::vector<uint32_t> shadow_surface, shadow_surface_head;
+	uint32_t shadow_surface_stride = 0;
+	void build_shadow_surface(double rho_scale = 1.0, double cone_scale = 1.0);
 };
 
 // The sphere tree (include/skr.h skr_scene_set_sphere_tree) in the layout of render_params.h SphereTree.  Built on

@@ -468,11 +468,27 @@ SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second,
 }
 
 // The union of the shadow masks of lights i and (second) i + 1 at P, for occluded_pair; 0 where it walks every sphere.  (The masks
-// exist only for scenes whose lights are all point lights.)
+// exist only for scenes whose lights are all point lights.)  `sph`: the sphere P was hit on, or -1 (not known, not a sphere).  Where
+// the launch has the surface patches (DESIGN.md "Shadow surface patches"), sph is in range and fl(|e|^2) - r^2 of e = P - C_sph is
+// within the sphere's radial slack, the mask is the one word of e's patch in the pair's table: one cell, one gather, and the spheres
+// behind P or under it are not named.  Everywhere else (NaN, a point off its sphere, no patches) the two direction masks, unchanged.
+// The index is in bounds whatever P holds.
 template <bool COHERENT>
-SKR_DEV uint32_t shadow_cands(const SceneView &sv, const RenderParams &p, int i, bool second, f3 P)
+SKR_DEV uint32_t shadow_cands(const SceneView &sv, const RenderParams &p, int i, bool second, f3 P, int sph = -1)
 {
 	if(COHERENT || !sv.smask || !p.use_shadows) return 0u;
+	if(p.shadow_surface_word != 0u && (uint32_t) sph < (uint32_t) sv.ns)
+	{
+		const float4 g = sv.geom[sph];
+		const uint32_t head = __float_as_uint(sv.kd[sph].w), n = head >> 24; // (base | G << 24: shadow_cells.h)
+		const f3 e = P - ld3(g);
+		const float c = dot3(e, e) - g.w;
+		if(n != 0u && __builtin_fabsf(c) <= g.w * SKR_SURFACE_SLACK) // (NaN: no)
+		{
+			const CubeCell cc = cube_cell_n(e, (int) n);
+			return sv.smask[p.shadow_surface_word + (uint32_t) (i >> 1) * p.shadow_surface_stride + (head & 0xffffffu) + ((uint32_t) cc.face * n + (uint32_t) cc.i) * n + (uint32_t) cc.j];
+		}
+	}
 	const uint32_t m0 = shadow_mask_of(sv, i, ld3(sv.lights[2 * i]) - P);
 	return second ? m0 | shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P) : m0;
 }
@@ -723,19 +739,20 @@ struct SphereLoopShadows {
 // raytrace.h:36-44 = bp::ambient (blinn_phong.h:13) + diffuse (:47) + specular (:90).
 // The reference casts the same shadow ray in diffuse and again in specular; one cast serves both.
 // (kd, ks, ambp = {La * ka, power}: the material rows of the surface hit)
+// sph: the sphere the point was hit on where the caller has it (shadow_cands), -1 elsewhere.
 // TS: triangle shadows (include/skr.h skr_scene_set_triangle_shadows) — `tri_shadows(P, i, second, L0, L1, occ0, occ1)` darkens the lights of a
 // pair that the spheres left lit and a triangle occludes (render_generic.hip TriangleShadows); chosen at compile time, so that the
 // instances without it keep their code.
 template <bool COHERENT, typename TS = NoTriangleShadows, typename SS = SphereLoopShadows>
 SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn, const TS &tri_shadows = TS(),
-						   const SS &sphere_shadows = SS())
+						   const SS &sphere_shadows = SS(), int sph = -1)
 {
 	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
 	const f3 view = normalize3(p.cam_pos - P); // always the camera (blinn_phong.h:93)
 	for(int i = 0; i < sv.nl; i += 2)
 	{
 		const bool second = i + 1 < sv.nl;
-		const uint32_t cand = SS::loops ? shadow_cands<COHERENT>(sv, p, i, second, P) : 0u; // (asked for ahead of the light terms)
+		const uint32_t cand = SS::loops ? shadow_cands<COHERENT>(sv, p, i, second, P, sph) : 0u; // (asked for ahead of the light terms)
 		const LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
 		bool occ0 = false, occ1 = false;
 		if(p.use_shadows)
@@ -850,7 +867,7 @@ SKR_DEV f3 direct_light_spot(const SceneView &sv, const RenderParams &p, const S
 template <bool COHERENT>
 SKR_DEV f3 direct_light(const SceneView &sv, const RenderParams &p, int sph, f3 P, f3 N, Counters &cn)
 {
-	return direct_light_of<COHERENT>(sv, p, ld3(sv.kd[sph]), ld3(sv.ks[sph]), sv.amb[sph], P, N, cn);
+	return direct_light_of<COHERENT>(sv, p, ld3(sv.kd[sph]), ld3(sv.ks[sph]), sv.amb[sph], P, N, cn, NoTriangleShadows(), SphereLoopShadows(), sph);
 }
 
 // ---- --scn-fog (DESIGN.md "Spherical fog"; general level pipeline only): blinn_phong.h:19-43 as written, rand() replaced ----

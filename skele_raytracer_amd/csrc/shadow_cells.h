@@ -15,6 +15,18 @@
 #define SKR_SHADOW_TABLE_WORDS (6 * SKR_SHADOW_CELLS * SKR_SHADOW_CELLS) /* per light */
 #define SKR_SHADOW_MAX_SPHERES 32 /* one bit per sphere; more spheres keep the plain loop */
 
+/* Surface patches of the shadow masks (DESIGN.md "Shadow surface patches"): a shading point P that is a hit of sphere s is keyed to
+ * the cell of e = P - C_s in a cube map of G_s x G_s cells per face on that sphere (the addressing above), where the device's
+ * fl(|e|^2) - r_s^2 is within the radial slack tau_s = r_s^2 * SKR_SURFACE_SLACK.  One table per pair of lights (2p, 2p + 1), `stride`
+ * words each; word base_s + (f G_s + i) G_s + j of a pair's table = the union over the pair's lights of the spheres that may be
+ * candidates of a shadow ray from any point of that patch.  The header of sphere s is one word, base_s | G_s << 24 (G_s = 0: no
+ * patches), kept in the .w of the sphere's kd row, which travels to LDS with the staged scene. */
+#define SKR_SURFACE_SLACK 0x1p-7f
+#ifndef SKR_SHADOW_SURFACE_SCALE
+#define SKR_SHADOW_SURFACE_SCALE 4 /* cells per edge of a GI surface patch's cell (SKR_GI_SURFACE_MAX_CELLS caps G_s here too); 1, 2, 4 measured: DESIGN.md */
+#endif
+#define SKR_SHADOW_SURFACE_MAX_BYTES (1u << 20) /* every pair's table together */
+
 /* GI masks (DESIGN.md "GI masks"): the node pipeline's closest-hit walk of a GI child ray visits only the spheres named by the mask
  * of (the cell of its origin, the cell of its direction).  Origins are looked up in a fine grid over the small spheres, then in a
  * coarse grid around it (SkrGiGrid: cubic cells, cell (i, j, k) of a point o = the integer parts of (o - lo) * inv, each in [0, n);
