@@ -32,6 +32,7 @@ extern "C" {
 #define SKR_HAS_ADAPTIVE 1   /* skr_adaptive, skr_render_adaptive(_host): an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ADAPTIVE_DENOISE 1 /* skr_render_adaptive_var, skr_denoise_var, skr_render_adaptive_denoised_host: additions, likewise */
 #define SKR_HAS_SPOT_LIGHTS 1 /* SKR_SCN_SPOT, skr_scene_get/set_spot_lights, skr_scene_get_spot_cones, skr_debug_eval op 17: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_SOFT_LIGHTS 1 /* skr_scene_set/get_light_radii, skr_debug_eval op 18: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -216,10 +217,42 @@ int skr_scene_get_sphere_tree(const skr_scene *scene, int *enabled);
 /* The spot lights of a scene, rows[n][11] = the file's fields in file order.  get: *n = their number, rows (if not NULL) receives
  * them.  set: replaces them (n = 0: none) under the loader's validation — SKR_ERR_ARG on a bad row, the scene unchanged — for scenes
  * made from arrays and for tests; a renderer takes the spot lights the scene has when it is created, as it takes the fog volumes.
- * skr_scene_get_spot_cones: cones[n][5] = {a.xyz, c1, c2} as derived above. */
+ * skr_scene_get_spot_cones: cones[n][5] = {a.xyz, c1, c2} as derived above.
+ * skr_scene_set_spot_lights changes the light count, so it resets every light radius (skr_scene_set_light_radii below) to 0. */
 int skr_scene_get_spot_lights(const skr_scene *scene, float *rows, int32_t *n);
 int skr_scene_set_spot_lights(skr_scene *scene, const float *rows, int32_t n);
 int skr_scene_get_spot_cones(const skr_scene *scene, float *cones);
+/* Sphere lights: point and spot lights with a radius, for soft shadows (new, opt-in; no counterpart in the reference, whose lights
+ * are points).  The rule (normative):
+ *   - Every point light and every spot light has a radius R >= 0, default 0.  Directional lights have none.  l is a light's index in
+ *     shading order: the point lights, then the spot lights, then the directional lights.
+ *   - For a light l with R > 0 a shading node — the (pixel, aa, node) of the counter RNG — takes ONE sample position Lp' on the sphere
+ *     of radius R about the light's position Lp; from then on the light is, for that node, the point light at Lp'.
+ *   - The draw: one call philox4x32(pixel, aa, node, soft_ctr3(l), seed_lo, seed_hi) with soft_ctr3(l) = 0x80000080u | (l << 8).  The
+ *     word is disjoint from every other draw: the hemisphere draws have bit 31 clear, the fog draws' word has bit 7 clear, the jitter
+ *     word is 0xFFFFFFFF and here bits 0-6 are 0.  u1 = u31_to_unit(out[0]), u2 = u31_to_unit(out[1]); out[2] and out[3] are unused.
+ *   - The position, in binary32, one correctly rounded operation per step, no libm, no binary64:
+ *         z = 1 - 2 * u1;  s = sqrt(max0(1 - z * z));  phi = 0x1.921fb6p+2f * u2  ((float) 2 pi times u2, not the hemisphere sampler's
+ *         binary64 product; phi <= (float) 2 pi, inside the range sincos_spec is exhaustively checked on);  (sn, cs) = sincos_spec(phi);
+ *         Lp' = (Lp.x + R * (s * cs), Lp.y + R * z, Lp.z + R * (s * sn)).
+ *   - Everything the point-light expression derives from the position uses Lp': to_l = Lp' - P, L and 1 / d^2; the shadow ray from
+ *     P + 1e-6 along that L (the any-hit rule is unchanged: any sphere with 1 < t < inf occludes, no closer-than-the-light test); the
+ *     far end length(Lp' - P) of the triangle-shadow walk; for a spot light the cone decision spot_cone(a, c1, c2, L) with that L (axis
+ *     and cosines unchanged; a sample outside the cone adds nothing and casts nothing).  One sample per (node, light) serves the
+ *     diffuse and the specular term, as one cast does.
+ *   - A light with R == 0 makes no draw and is the point light it was, bit for bit.  A point inside a light's ball, or at Lp', gets no
+ *     special case.  The work counters keep their meaning: shadow_rays the casts, sphere_tests the reference's loop count up to the
+ *     first occluder in file order.
+ *   - A scene with at least one R > 0 renders every frame and every shading query on the general level pipeline (skr_kernel_variant()
+ *     "level_pipeline_g1_soft", "level_pipeline_g1_soft_tshadow", "shade_rays_g1_soft", "shade_rays_g1_soft_tshadow"), in every mode
+ *     it has but three: skr_options.legacy_reflect, fog volumes and the sphere-tree switch are refused with SKR_ERR_UNSUPPORTED.  A
+ *     pair of lights in which either has R > 0 tests every sphere (the shadow masks are built for rays toward Lp).  A scene whose
+ *     radii are all 0 is planned and rendered exactly as before.
+ * set: radii[n], n == n_point + n_spot, every value finite and >= 0; otherwise SKR_ERR_ARG and the scene is unchanged.  A renderer
+ * takes the radii the scene has when it is created, as it takes the spot lights.  skr_scene_set_spot_lights resets every radius to 0
+ * (it changes the light count).  get: *n = n_point + n_spot, radii (if not NULL) receives them. */
+int skr_scene_set_light_radii(skr_scene *scene, const float *radii, int32_t n);
+int skr_scene_get_light_radii(const skr_scene *scene, float *radii, int32_t *n);
 /* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
  * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
  * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device
@@ -656,7 +689,9 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  * slots) and in the frames of the same test file; the masked walks (closest_pair_deferred<true>, occluded_pair with shadow masks:
  * masked_rows) run only in those frames.
  * 17 the spot-light cone (SKR_SCN_SPOT above; shade_common.h spot_cone, the function the light loop calls): (a(3), c1, c2, L(3))
- *    -> {f, outside}: f as a float (0 where outside), outside 0 / 1.  (Ops 12..16 were taken when spot lights came.) */
+ *    -> {f, outside}: f as a float (0 where outside), outside 0 / 1.  (Ops 12..16 were taken when spot lights came.)
+ * 18 the sample of a light with a radius (skr_scene_set_light_radii above; shade_common.h soft_sample, the function the light loop calls):
+ *    (pixel, aa, node, l, seed_lo, seed_hi, Lp(3), R), 10 words -> Lp'(3).  R == 0: Lp itself. */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

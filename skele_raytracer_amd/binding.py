@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -87,6 +87,8 @@ def lib():
     L.skr_scene_get_spot_lights.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_scene_set_spot_lights.argtypes = [vp, vp, C.c_int32]
     L.skr_scene_get_spot_cones.argtypes = [vp, vp]
+    L.skr_scene_set_light_radii.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_light_radii.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
     L.skr_scene_set_sphere_tree.argtypes = [vp, C.c_int]
@@ -344,6 +346,26 @@ class Scene:
         return c
 
     @property
+    def light_radii(self):
+        """The radius of every point and spot light, float32 [n_point + n_spot] in shading order; 0 = a point (include/skr.h
+        skr_scene_get_light_radii)."""
+        n = C.c_int32()
+        _check(lib().skr_scene_get_light_radii(self.h, None, C.byref(n)), "skr_scene_get_light_radii")
+        radii = np.zeros(n.value, np.float32)
+        _check(lib().skr_scene_get_light_radii(self.h, radii.ctypes.data, C.byref(n)), "skr_scene_get_light_radii")
+        return radii
+
+    def set_light_radii(self, radii):
+        """Give the point and spot lights a radius (soft shadows; include/skr.h skr_scene_set_light_radii): a scalar for every light, or one
+        value per light in shading order.  Finite and >= 0.  A renderer takes those the scene has when it is made; set_spot_lights
+        resets them to 0."""
+        r = np.asarray(radii, np.float32)
+        if r.ndim == 0:
+            r = np.full(len(self.light_radii), r, np.float32)
+        r = np.ascontiguousarray(r, np.float32).reshape(-1)
+        _check(lib().skr_scene_set_light_radii(self.h, r.ctypes.data, len(r)), "skr_scene_set_light_radii")
+
+    @property
     def triangle_shadows(self):
         """The scene's triangle-shadow switch (include/skr.h skr_scene_set_triangle_shadows)."""
         on = C.c_int()
@@ -385,7 +407,7 @@ class Scene:
 
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
-                    triangle_shadows=False, sphere_tree=False):
+                    triangle_shadows=False, sphere_tree=False, light_radii=None):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -407,6 +429,8 @@ class Scene:
             sc.set_triangle_shadows(True)
         if sphere_tree:
             sc.set_sphere_tree(True)
+        if light_radii is not None:  # a scalar or [n_point_lights] (soft shadows)
+            sc.set_light_radii(light_radii)
         return sc
 
 

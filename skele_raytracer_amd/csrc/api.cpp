@@ -44,6 +44,9 @@ struct DeviceScene {
 	int n_fog = 0;
 	size_t off_spot = 0;      // --scn-spot: 2 rows per spot light behind the fog rows (render_params.h SpotLights)
 	int n_spot = 0, spot_first = 0; // lights [spot_first, spot_first + n_spot) of the light table are spot lights
+	size_t off_radii = 0;     // skr_scene_set_light_radii: one float per point and spot light behind the cone rows (render_params.h SoftLights)
+	int n_radii = 0;
+	bool soft = false;        // some radius is > 0: frames and shading queries take the instances with the light sample
 	size_t off_smask = 0;     // the shadow masks (skr_scene::shadow_masks, 4 per row), 0 = none
 	size_t off_ssurf = 0;     // their surface patches (skr_scene::shadow_surface: ssurf_stride words per pair of lights), 0 = none
 	uint32_t ssurf_stride = 0;
@@ -163,7 +166,7 @@ void skr_copy_switches(skr_renderer *dst, const skr_renderer *src) { dst->sw = s
 int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
 							   float *d_rgbf, void *stream);
 
-// The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | spot cones | shadow
+// The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | spot cones | light radii | shadow
 // masks | GI masks | trace tree | sphere tree (rows, chunks, nodes), then 16 rows of padding (the sphere loops ask for the rows of a trip ahead without a bounds test,
 // shade_common.h sphere_rows).  Sets the offsets and the scalars of `d` that go with the sections; host only, nothing is uploaded.
 static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
@@ -201,6 +204,10 @@ static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 	d.n_spot = s.n_spot();
 	d.spot_first = s.info.n_point_lights;
 	d.off_spot = put4(s.spot_cones);
+	// the radii of the point and spot lights (skr_scene light_radii, skr_scene_set_light_radii), one float per light in light order
+	d.n_radii = (int) s.light_radii.size();
+	d.soft = s.soft();
+	d.off_radii = put(s.light_radii.data(), s.light_radii.size() * 4);
 	if(!s.shadow_masks.empty()) d.off_smask = put(s.shadow_masks.data(), s.shadow_masks.size() * 4);
 	d.shadow_reach2 = s.shadow_reach2;
 	if(!s.shadow_surface.empty())
@@ -565,6 +572,12 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 		skr_set_error("spot lights (--scn-spot) cannot be combined with %s", opt->legacy_reflect ? "--legacy-reflect" : p.n_fog > 0 ? "fog volumes (--scn-fog)" : "the sphere tree (--sphere-tree)");
 		return SKR_ERR_UNSUPPORTED;
 	}
+	// skr_scene_set_light_radii: a scene with a radius > 0 renders on the general level pipeline's instances with the light sample
+	if(s.soft && (opt->legacy_reflect || p.n_fog > 0 || s.sphere_tree))
+	{
+		skr_set_error("light radii (--light-radius) cannot be combined with %s", opt->legacy_reflect ? "--legacy-reflect" : p.n_fog > 0 ? "fog volumes (--scn-fog)" : "the sphere tree (--sphere-tree)");
+		return SKR_ERR_UNSUPPORTED;
+	}
 	p.counters = s.d_counters;
 	p.tri_work = r->count_tri ? s.d_tri_work : nullptr;
 	p.qctr = reinterpret_cast<uint32_t *>(s.d_counters + (size_t) SKR_COUNTER_SHARDS * 4 + 8);
@@ -619,6 +632,13 @@ static SpotLights spot_lights_of(const skr_renderer *r)
 	return SpotLights{s.d_blob + s.off_spot, s.spot_first, s.n_spot};
 }
 
+// the radii of a renderer's scene (render_params.h SoftLights)
+static SoftLights soft_lights_of(const skr_renderer *r)
+{
+	const DeviceScene &s = *r->scene;
+	return SoftLights{reinterpret_cast<const float *>(s.d_blob + s.off_radii), s.n_radii};
+}
+
 // the sphere tree of a renderer whose scene had the switch on, under the renderer's switches (render_params.h SphereTree)
 static SphereTree sphere_tree_of(const skr_renderer *r)
 {
@@ -652,7 +672,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.rgb = d_rgb;
 	p.rgbf = d_rgbf;
 	LaunchPlan lp;
-	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp, r->scene->sphere_tree, r->scene->n_spot > 0);
+	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp, r->scene->sphere_tree, r->scene->n_spot > 0, r->scene->soft);
 	rc = check_plan(r, p, fits, lp.lds_bytes, 0);
 	bool kept = false;
 	if(rc == SKR_OK && lp.path != SKR_PATH_DIRECT) rc = take_node_scratch(r, lp.scratch_bytes, &kept);
@@ -691,9 +711,10 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	{ // (shade_triangles: the general level pipeline)
 		lp.tri_shadows = true;
 		lp.shadows.trees = query_trees(r);
-		lp.variant = lp.sphere_tree ? "level_pipeline_g1_stree_tshadow" : lp.spot ? "level_pipeline_g1_spot_tshadow" : "level_pipeline_g1_tshadow";
+		lp.variant = lp.sphere_tree ? "level_pipeline_g1_stree_tshadow" : lp.soft ? "level_pipeline_g1_soft_tshadow" : lp.spot ? "level_pipeline_g1_spot_tshadow" : "level_pipeline_g1_tshadow";
 	}
-	if(lp.spot) lp.spots = spot_lights_of(r);
+	if(lp.spot || lp.soft) lp.spots = spot_lights_of(r); // (n = 0 without spot lights)
+	if(lp.soft) lp.softs = soft_lights_of(r);
 	if(lp.sphere_tree) lp.stree = sphere_tree_of(r);
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
@@ -1166,10 +1187,14 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	if(tri_shadows) tsh.trees = q.trees;
 	const SphereTree st = stree ? sphere_tree_of(r) : SphereTree{};
 	if(stree) g_variant = tri_shadows ? "shade_rays_g1_stree_tshadow" : "shade_rays_g1_stree";
+	else if(r->scene->soft) g_variant = tri_shadows ? "shade_rays_g1_soft_tshadow" : "shade_rays_g1_soft";
 	else if(r->scene->n_spot > 0) g_variant = tri_shadows ? "shade_rays_g1_spot_tshadow" : "shade_rays_g1_spot";
 	else g_variant = tri_shadows ? "shade_rays_g1_tshadow" : "shade_rays_g1";
 	const SpotLights spots = spot_lights_of(r);
-	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr, stree ? &st : nullptr, r->scene->n_spot > 0 ? &spots : nullptr));
+	const SoftLights softs = soft_lights_of(r);
+	const bool soft = r->scene->soft;
+	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr, stree ? &st : nullptr, r->scene->n_spot > 0 || soft ? &spots : nullptr,
+							   soft ? &softs : nullptr));
 	return SKR_OK;
 }
 
@@ -1431,7 +1456,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {
-	if(!d_in || !d_out || op < 0 || op > 17) return SKR_ERR_ARG;
+	if(!d_in || !d_out || op < 0 || op > 18) return SKR_ERR_ARG;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(skr_launch_debug(op, d_in, d_out, n, (hipStream_t) stream));
 	return SKR_OK;

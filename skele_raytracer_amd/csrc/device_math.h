@@ -221,6 +221,10 @@ SKR_DEV float u31_to_unit(uint32_t w) { return (float) (w >> 1) * 4.656612873077
 #define SKR_FOG_MAX 64 // == SKR_FOG_MAX_VOLUMES (include/skr.h)
 SKR_DEV uint32_t fog_ctr3(uint32_t light, uint32_t fog, uint32_t pass) { return 0x80000000u | (light << 8) | (fog << 1) | pass; }
 SKR_DEV float u31_to_pm1(uint32_t w) { return -1.0f + (float) (w >> 1) * 9.31322574615478515625e-10f; } // * 2^-30 is exact
+// The sample of a light with a radius (include/skr.h skr_scene_set_light_radii): ONE call per (node, light l), counter
+// (pixel, aa, node, soft_ctr3(l)).  Bit 31 set: disjoint from the hemisphere draws.  Bit 7 set: disjoint from fog_ctr3, whose bit 7 is
+// clear (l < 2^22, j < 64).  Bits 0-6 clear: never the jitter word 0xFFFFFFFF.  u1 = u31(out[0]), u2 = u31(out[1]); out[2], out[3] unused.
+SKR_DEV uint32_t soft_ctr3(uint32_t light) { return 0x80000080u | (light << 8); }
 
 // ------------------------------------------------------- shared math ----
 typedef float f2 __attribute__((ext_vector_type(2)));

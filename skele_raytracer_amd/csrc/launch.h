@@ -95,6 +95,8 @@ struct LaunchPlan {
 	SphereTree stree{};
 	bool spot = false;                 // the renderer's scene has spot lights (skr_plan_launch's argument; api.cpp render_pass sets `spots`)
 	SpotLights spots{};
+	bool soft = false;                 // some light of the renderer's scene has a radius (skr_plan_launch's argument; api.cpp render_pass sets `spots` and `softs`)
+	SoftLights softs{};
 };
 
 // the scene SoA every kernel stages into LDS (wave_common.h stage_scene): 4 rows per sphere, a zero row, 2 rows per light
@@ -141,7 +143,8 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
 // sphere_tree: the renderer's scene has the sphere tree switched on and at least one sphere (include/skr.h skr_scene_set_sphere_tree)
 // spot: the renderer's scene has at least one spot light (include/skr.h SKR_SCN_SPOT): the general level pipeline, as for fog
-bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree = false, bool spot = false); // false: the launch takes a level pipeline and not one band of it fits the budget
+// soft: at least one light of the renderer's scene has a radius > 0 (include/skr.h skr_scene_set_light_radii): likewise
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree = false, bool spot = false, bool soft = false); // false: the launch takes a level pipeline and not one band of it fits the budget
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook);
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream);
 // render_nodes.hip
@@ -154,8 +157,9 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree = false
 // ts: triangle shadows are in force (the activate kernel's instances with the shadow walk); null: they are not
 // st: the launch renders on the sphere tree (the instances with the sphere walks, which stage only the lights); null: it does not
 // sp: the scene has spot lights (the activate kernel's instances with the cone decision); null: it has none
+// so: some light has a radius (the activate kernel's instances with the light sample; sp is then given too, n = 0 without spot lights); null: none has
 hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q = nullptr,
-							  const TriShadows *ts = nullptr, const SphereTree *st = nullptr, const SpotLights *sp = nullptr);
+							  const TriShadows *ts = nullptr, const SphereTree *st = nullptr, const SpotLights *sp = nullptr, const SoftLights *so = nullptr);
 // render_wave.hip
 // Every value the level-0 stage of a node-pipeline launch depends on, and where it is kept: what skr_primary_kernel and plan_for
 // (render_nodes.hip) read.  A frame replays the stage only if its key equals, byte for byte, the key the scratch was last built under

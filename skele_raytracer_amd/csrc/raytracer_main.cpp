@@ -5,9 +5,10 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --scn-fog, --scn-spot (spot_light lines parsed and shaded: include/skr.h SKR_SCN_SPOT), --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
+// --scn-fog, --scn-spot (spot_light lines parsed and shaded: include/skr.h SKR_SCN_SPOT), --light-radius R (every point and spot light a sphere of radius R: include/skr.h skr_scene_set_light_radii), --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
 // --adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L].
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +27,8 @@ int main(int argc, char *argv[])
 	int device = 0, gpus = 1;
 	bool strict_scn = false, width_given = false, height_given = false, depth_given = false; // --strict-scn (new)
 	bool scn_spot = false; // --scn-spot (new: DESIGN.md 8.12)
+	bool radius_given = false; // --light-radius R (new: DESIGN.md 8.13)
+	float light_radius = 0.0f;
 	bool scn_fog = false, scn_fov = false, fov_given = false; // --scn-fog, --scn-fov (new: DESIGN.md "Spherical fog", "Camera half-angle")
 	bool triangle_shadows = false; // --triangle-shadows (new: include/skr.h SKR_SCN_TRIANGLE_SHADOWS)
 	bool sphere_tree = false;      // --sphere-tree (new: include/skr.h SKR_SCN_SPHERE_TREE)
@@ -133,6 +136,7 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--quiet")) quiet = true;
 		if(!strcmp(argv[i], "--strict-scn")) strict_scn = true;
 		if(!strcmp(argv[i], "--scn-spot")) scn_spot = true;                 // new: spot_light lines parsed and shaded (include/skr.h SKR_SCN_SPOT)
+		if(!strcmp(argv[i], "--light-radius") && has_next) { light_radius = strtof(argv[i + 1], nullptr); radius_given = true; } // new: every point and spot light a sphere of radius R
 		if(!strcmp(argv[i], "--scn-fog")) scn_fog = true;                   // new: spherical_fog lines parsed and shaded (include/skr.h SKR_SCN_FOG)
 		if(!strcmp(argv[i], "--scn-fov")) scn_fov = true;                   // new: fov = 2 x the camera line's half_height_angle unless --fov is given
 		if(!strcmp(argv[i], "--shade-triangles")) option.shade_triangles = 1; // new: triangles as surfaces (include/skr.h skr_options)
@@ -158,12 +162,28 @@ int main(int argc, char *argv[])
 		std::cerr << "no output destination was passed. Pass with --output destination_path.ppm" << std::endl;
 		return 0;
 	}
+	if(radius_given && !(std::isfinite(light_radius) && light_radius >= 0.0f))
+	{
+		std::cerr << "raytracer: --light-radius takes a finite radius >= 0" << std::endl;
+		return SKR_ERR_ARG;
+	}
 
 	skr_scene *scene = nullptr;
 	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u) | (triangle_shadows ? SKR_SCN_TRIANGLE_SHADOWS : 0u) | (sphere_tree ? SKR_SCN_SPHERE_TREE : 0u) | (scn_spot ? SKR_SCN_SPOT : 0u), &scene) != SKR_OK)
 	{
 		printf("%s\n", skr_last_error()); // scene.cpp:24-25: message, exit(0)
 		return 0;
+	}
+	if(radius_given)
+	{ // every point and spot light of the loaded scene (include/skr.h skr_scene_set_light_radii)
+		int32_t n = 0;
+		skr_scene_get_light_radii(scene, nullptr, &n);
+		const std::vector<float> radii((size_t) n, light_radius);
+		if(skr_scene_set_light_radii(scene, radii.data(), n) != SKR_OK)
+		{
+			std::cerr << "raytracer: " << skr_last_error() << std::endl;
+			return SKR_ERR_ARG;
+		}
 	}
 	if(strict_scn)
 	{ // the .scn's own film_resolution (scene.cpp:105-109) and max_depth (:192-198) hold unless the command line says otherwise

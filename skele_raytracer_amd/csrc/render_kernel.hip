@@ -34,7 +34,7 @@ static size_t direct_lds_bytes(const RenderParams &p)
 }
 
 // Which kernels render this launch, and what they need.  In this order:
-//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, and every tree
+//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, and every tree
 //     (shade() recurses: max_depth > 1; api.cpp folds --depth to 1 where it cannot, raytrace.h:208-218) the node pipeline does not;
 //   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget and its kernels
 //     fit the device's LDS;
@@ -42,10 +42,11 @@ static size_t direct_lds_bytes(const RenderParams &p)
 // A launch is refused (api.cpp render_pass: lp.lds_bytes > the device's LDS) only where no path fits.
 // SKR_PIPELINE=generic forces the general pipeline for every launch, SKR_PIPELINE=nodes keeps triangle meshes on the node pipeline
 // (tests, A/B runs).
-bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree, bool spot)
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree, bool spot, bool soft)
 {
 	lp = LaunchPlan();
 	lp.spot = spot;
+	lp.soft = soft;
 	if(sphere_tree)
 	{ // the sphere tree: every frame on the general level pipeline's instances with the sphere walks
 		lp.path = SKR_PATH_GENERIC;
@@ -57,7 +58,7 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bo
 		if(p.grid_size > 0) lp.acc_bytes = (size_t) p.width * p.out_rows * 12;
 		return true;
 	}
-	const bool generic_only = p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || spot;
+	const bool generic_only = p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || spot || soft;
 	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
 		lp.path = SKR_PATH_NODES;
@@ -70,7 +71,7 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bo
 	else if(generic_only || p.max_depth > 1 || direct_lds_bytes(p) > lds_limit)
 	{ // (a frame without a tree whose scene leaves the direct kernel no room for its tile: the general pipeline renders it as well)
 		lp.path = SKR_PATH_GENERIC;
-		lp.variant = spot ? "level_pipeline_g1_spot" : "level_pipeline_g1";
+		lp.variant = soft ? "level_pipeline_g1_soft" : spot ? "level_pipeline_g1_spot" : "level_pipeline_g1";
 		if(!skr_generic_plan(p, lp.generic)) return false;
 		lp.scratch_bytes = lp.generic.total;
 		lp.lds_bytes = skr_scene_kernels_lds(p);
@@ -88,7 +89,7 @@ hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStr
 {
 	if(lp.path == SKR_PATH_GENERIC)
 		return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook, nullptr, lp.tri_shadows ? &lp.shadows : nullptr, lp.sphere_tree ? &lp.stree : nullptr,
-												   lp.spot ? &lp.spots : nullptr)
+												   lp.spot || lp.soft ? &lp.spots : nullptr, lp.soft ? &lp.softs : nullptr)
 							  : hipErrorInvalidValue;
 	if(lp.path == SKR_PATH_NODES) return p.node_scratch ? skr_launch_nodes(p, lp.nodes, stream, hook) : hipErrorInvalidValue;
 	if(p.n_spheres >= 65536) return hipErrorInvalidValue; // (one launch, no tree: any scene the LDS holds)
@@ -101,7 +102,7 @@ hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStr
 // ------------------------------------------------------------ debug eval ----
 // Device-side evaluation of the arithmetic spec, one record per thread
 // (skr_debug_eval in include/skr.h).
-// Op 17: the spot-light cone.  Ops 12..16 (include/skr.h): the filtered predicates of device_math.h and the selection code on top of them, through the functions the
+// Op 18: the sample of a light with a radius.  Op 17: the spot-light cone.  Ops 12..16 (include/skr.h): the filtered predicates of device_math.h and the selection code on top of them, through the functions the
 // render kernels call.  `i` = the lane's record, `live` = it may write.
 #define SKR_DEBUG_TABLE_ROWS 80u // ops 15, 16: rows of the sphere table in the input (<= 64 spheres, the pad row, the rows table_rows asks for behind it)
 #define SKR_DEBUG_EC_PAD 8u      // ops 15, 16: rows behind the ns rows of a record's ec table
@@ -226,6 +227,17 @@ SKR_DEV void skr_debug_predicates(int op, const uint32_t *in, uint32_t *out, uin
 			{
 				out[2 * i] = U(c.f);
 				out[2 * i + 1] = c.outside ? 1u : 0u;
+			}
+			break;
+		}
+		case 18: { // the sample of one light with a radius for one shading node: soft_sample, the function direct_light_soft calls
+			const uint32_t *r = in + 10 * i;
+			const f3 s = soft_sample(r[0], r[1], r[2], r[3], r[4], r[5], v3(r + 6), F(r[9]));
+			if(live)
+			{
+				out[3 * i] = U(s.x);
+				out[3 * i + 1] = U(s.y);
+				out[3 * i + 2] = U(s.z);
 			}
 			break;
 		}

@@ -164,6 +164,15 @@ struct SpotLights {
 	int32_t first, n;
 };
 
+// The radii of the point and spot lights (include/skr.h skr_scene_set_light_radii): radii[l] for the lights [0, n) of
+// the light table, n = point lights + spot lights (a directional light has none), one float per light in the scene blob behind the cone
+// rows (HBM, never written by a kernel).  Handed to the activate kernel's instances with the light sample in a kernel argument of their
+// own, behind SpotLights (n = 0 where the scene has no spot light): RenderParams keeps its size and every offset.
+struct SoftLights {
+	const float *radii;
+	int32_t n;
+};
+
 // Optional timing of the dominant kernel of a launch (skr_renderer_kernel_ms): the launcher records the
 // two events right around that kernel on the launch stream — and, where `snap` is set, copies the work counters in front of the
 // first event and behind the second (stream-ordered device-to-device copies outside the timed window), so that the work of that

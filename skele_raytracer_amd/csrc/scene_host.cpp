@@ -144,6 +144,7 @@ void skr_scene::build_lights()
 		lights[2 * i] = {l[0], l[1], l[2], 0.0f};
 		lights[2 * i + 1] = {l[3], l[4], l[5], 0.0f};
 	}
+	light_radii.resize((size_t) (nl + nsp), 0.0f); // (a new light is a point; skr_scene_set_spot_lights resets them all)
 	spot_cones.resize((size_t) nsp * 2);
 	for(int i = 0; i < nsp; i++)
 	{
@@ -1719,6 +1720,7 @@ int skr_scene_set_spot_lights(skr_scene *scene, const float *rows, int32_t n)
 			return SKR_ERR_ARG;
 		}
 	scene->raw_spot_lights.assign(rows, rows + (size_t) n * 11);
+	scene->light_radii.clear(); // (the light count changes: every radius is 0 again, include/skr.h)
 	scene->build_lights();
 	scene->build_shadow_masks(); // (a spot light has a table like the point light it geometrically is)
 	scene->build_shadow_surface();
@@ -1730,6 +1732,31 @@ int skr_scene_get_spot_lights(const skr_scene *scene, float *rows, int32_t *n)
 	if(!scene) return SKR_ERR_ARG;
 	if(n) *n = (int32_t) scene->n_spot();
 	if(rows && !scene->raw_spot_lights.empty()) memcpy(rows, scene->raw_spot_lights.data(), scene->raw_spot_lights.size() * 4);
+	return SKR_OK;
+}
+
+int skr_scene_set_light_radii(skr_scene *scene, const float *radii, int32_t n)
+{
+	if(!scene || n < 0 || (n && !radii) || (size_t) n != scene->light_radii.size())
+	{
+		skr_set_error("skr_scene_set_light_radii: bad argument (one radius per point and spot light: %d)", scene ? (int) scene->light_radii.size() : 0);
+		return SKR_ERR_ARG;
+	}
+	for(int32_t i = 0; i < n; i++)
+		if(!std::isfinite(radii[i]) || !(radii[i] >= 0.0f))
+		{
+			skr_set_error("skr_scene_set_light_radii: radius %d is not a finite number >= 0", i);
+			return SKR_ERR_ARG;
+		}
+	for(int32_t i = 0; i < n; i++) scene->light_radii[i] = radii[i] + 0.0f; // (-0 -> +0)
+	return SKR_OK;
+}
+
+int skr_scene_get_light_radii(const skr_scene *scene, float *radii, int32_t *n)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(n) *n = (int32_t) scene->light_radii.size();
+	if(radii && !scene->light_radii.empty()) memcpy(radii, scene->light_radii.data(), scene->light_radii.size() * 4);
 	return SKR_OK;
 }
 

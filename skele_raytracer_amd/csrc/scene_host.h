@@ -28,6 +28,7 @@ struct skr_scene {
 	std::vector<float> raw_directional_lights; // [n][6] direction colour — --strict-scn only (scene.cpp:139-163 drops them)
 	std::vector<float> raw_fog;          // [n][9] centre radius albedo scattering absorption — SKR_SCN_FOG / skr_scene_set_fog only (file order)
 	std::vector<float> raw_spot_lights;  // [n][11] colour position direction angle1 angle2, the file's fields in file order — SKR_SCN_SPOT / skr_scene_set_spot_lights only
+	std::vector<float> light_radii;      // [n_point + n_spot] the radius of every point and spot light in light order, 0 = a point — skr_scene_set_light_radii only (build_lights() sizes it)
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
 	bool sphere_tree = false;            // SKR_SCN_SPHERE_TREE / skr_scene_set_sphere_tree: likewise
@@ -54,6 +55,12 @@ struct skr_scene {
 	void finalize();
 	void build_lights(); // lights and spot_cones from the raw light arrays
 	int n_spot() const { return (int) (raw_spot_lights.size() / 11); }
+	bool soft() const // some light has a radius > 0
+	{
+		for(float r : light_radii)
+			if(r > 0.0f) return true;
+		return false;
+	}
 	size_t tri_chunk_stride = 0; // float4 entries per |d| level
 	int tri_node_count = 0;
 	bool tri_any_cone = false; // some chunk has a tight radius for non-grazing rays (scene_host.cpp)

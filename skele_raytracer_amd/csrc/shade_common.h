@@ -864,6 +864,120 @@ SKR_DEV f3 direct_light_spot(const SceneView &sv, const RenderParams &p, const S
 	return total;
 }
 
+// ---- lights with a radius (include/skr.h skr_scene_set_light_radii; general level pipeline only) ----
+// The sample position of the light l at Lp with radius R for the shading node (pixel, aa, node): one Philox call, then binary32 with one
+// correctly rounded operation per step.  R == 0 (and NaN): no draw, Lp itself.  phi <= (float) 2 pi: inside the range sincos_spec is
+// exhaustively checked on.
+SKR_DEV f3 soft_sample(uint32_t pixel, uint32_t aa, uint32_t node, uint32_t l, uint32_t k0, uint32_t k1, f3 Lp, float R)
+{
+	if(!(R > 0.0f)) return Lp;
+	uint32_t rnd[4];
+	philox4x32(pixel, aa, node, soft_ctr3(l), k0, k1, rnd);
+	const float u1 = u31_to_unit(rnd[0]), u2 = u31_to_unit(rnd[1]);
+	const float z = 1.0f - 2.0f * u1;
+	const float s = sk_sqrtf(max0(1.0f - z * z));
+	float sn, cs;
+	sincos_spec(0x1.921fb6p+2f * u2, sn, cs); // (float) 2 pi times u2, in binary32
+	return mk3(Lp.x + R * (s * cs), Lp.y + R * z, Lp.z + R * (s * sn));
+}
+
+// One float of a table that no kernel writes, at a wave-uniform index, through the constant address space (load_const4's reason).
+SKR_DEV float load_const1(const float *base, int i)
+{
+	const float __attribute__((address_space(4))) *q = (const float __attribute__((address_space(4))) *) (unsigned long long) base;
+	return q[i];
+}
+
+// direct_light_spot() for a scene in which some light has a radius: the same pair loop with the sample ahead of the cone decision.  A
+// light with R > 0 is, for this node, the point light at its sample: L, 1 / d^2, the cone decision, the shadow ray and the far end of the
+// triangle walk all come from the sample.  A pair in which either light has R > 0 walks every sphere (the shadow masks are built for rays
+// toward Lp); a pair of two R == 0 lights is walked as direct_light_spot walks it.  (pixel, node): the node's counter words.
+// Nothing of a sample stays live across the shadow walk but its LightTerm: the triangle walk's far end draws the sample again.
+template <typename TS = NoTriangleShadows>
+SKR_DEV f3 direct_light_soft(const SceneView &sv, const RenderParams &p, const SpotLights &sp, const SoftLights &so, f3 kd, f3 ks, float4 ambp, f3 P, f3 N,
+							 uint32_t pixel, uint32_t node, Counters &cn, const TS &tri_shadows = TS())
+{
+	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
+	const f3 view = normalize3(p.cam_pos - P);
+	for(int i = 0; i < sv.nl; i += 2)
+	{
+		const bool second = i + 1 < sv.nl;
+		// (l is wave-uniform: the radius comes through the scalar cache, and the branches on it are the wave's)
+		auto radius = [&](int l) { return l < so.n ? load_const1(so.radii, l) : 0.0f; };
+		const float R0 = radius(i), R1 = second ? radius(i + 1) : 0.0f;
+		auto to_light = [&](int l, float R) { return soft_sample(pixel, p.aa_index, node, (uint32_t) l, p.seed_lo, p.seed_hi, ld3(sv.lights[2 * l]), R) - P; };
+		auto term = [&](int l, float R)
+		{
+			if(!(R > 0.0f)) return light_term(sv, l, P);
+			LightTerm t; // light_term's point light, at the sample
+			t.lc = ld3(sv.lights[2 * l + 1]);
+			const f3 to_l = to_light(l, R);
+			const LenTerms lt = len_terms<true>(sqr3(to_l));
+			t.L = to_l * lt.inv;
+			t.intensity = lt.inv2;
+			return t;
+		};
+		LightTerm t0 = term(i, R0), t1 = second ? term(i + 1, R1) : t0;
+		bool in0 = true, in1 = second;
+		auto cone = [&](int l, LightTerm &t, bool &in)
+		{
+			if((uint32_t) (l - sp.first) < (uint32_t) sp.n)
+			{
+				const float4 A = load_const4(sp.cones, 2 * (l - sp.first)), B = load_const4(sp.cones, 2 * (l - sp.first) + 1);
+				const SpotCone c = spot_cone(ld3(A), A.w, B.x, t.L);
+				in = !c.outside;
+				t.lc = t.lc * c.f;
+			}
+		};
+		cone(i, t0, in0);
+		if(second) cone(i + 1, t1, in1);
+		bool occ0 = !in0, occ1 = !in1;
+		if(p.use_shadows && (in0 || in1))
+		{
+			const bool both = in0 && in1;
+			const int la = in0 ? i : i + 1;
+			const f3 La = in0 ? t0.L : t1.L;
+			cn.shadow_rays += both ? 2u : 1u;
+			const bool soft_pair = R0 > 0.0f || R1 > 0.0f;
+			SceneView w = sv;
+			if(soft_pair) w.smask = nullptr; // every sphere
+			uint32_t cand = 0u;
+			if(w.smask)
+			{
+				cand = shadow_mask_of(sv, la, ld3(sv.lights[2 * la]) - P);
+				if(both) cand |= shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P);
+			}
+			bool oa, ob;
+			occluded_pair<false>(w, P, La, t1.L, both, oa, ob, cn.shadow_tests, cand);
+			if constexpr(TS::on)
+			{ // blinn_phong.h's `distance`, of the sample where the light has one
+				auto far = [&](int l, float R) { return R > 0.0f ? length3(to_light(l, R)) : tri_shadows.reach(l, P); };
+				const float fa = far(la, in0 ? R0 : R1), fb = both ? far(i + 1, R1) : fa;
+				tri_shadows.ends(P, both, La, t1.L, fa, fb, oa, ob);
+			}
+			occ0 = in0 ? oa : true;
+			occ1 = both ? ob : (in1 ? oa : true);
+		}
+		auto add_light = [&](const LightTerm &t, bool lit)
+		{
+			if(lit)
+			{
+				diffuse = diffuse + ((kd * t.lc) * t.intensity) * max0(dot3(N, t.L));
+				const f3 vl = view + t.L;
+				const f3 H = vl / length3(vl);
+				specular = specular + ((ks * t.lc) * t.intensity) * powf_spec(max0(dot3(N, H)), ambp.w, p.pow_steps);
+			}
+		};
+		add_light(t0, !occ0);
+		add_light(t1, !occ1);
+	}
+	f3 total = mk3(0, 0, 0);
+	total = total + ld3(ambp);
+	total = total + diffuse;
+	total = total + specular;
+	return total;
+}
+
 template <bool COHERENT>
 SKR_DEV f3 direct_light(const SceneView &sv, const RenderParams &p, int sph, f3 P, f3 N, Counters &cn)
 {

@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-spot] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
            [--adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
@@ -17,6 +17,7 @@ and writes the PPM (distributed.py).  The image does not depend on G: random num
 Flags are matched like the reference does — by `strcmp` anywhere in argv, unknown tokens ignored — and usage errors
 print the reference's messages and exit with status 0 (main.cpp:381-391).  There is no CPU path.
 """
+import math
 import os
 import sys
 import time
@@ -86,6 +87,8 @@ def _parse(argv):
             opt["scn_fog"] = True
         elif a == "--scn-spot":
             opt["scn_spot"] = True
+        elif a == "--light-radius":
+            opt["light_radius"] = value(i, _atof, "light-radius takes a float (the radius of every point and spot light)")
         elif a == "--scn-fov":
             opt["scn_fov"] = True
         elif a == "--shade-triangles":
@@ -139,6 +142,10 @@ def main(argv=None):
     if o["width"] <= 0 or o["height"] <= 0 or o["width"] > 65536 or o["height"] > 65536:
         print("raytracer: bad image size %dx%d" % (o["width"], o["height"]), file=sys.stderr)  # as bin/raytracer: before anything is sized from it
         return 2
+    radius = o.get("light_radius")
+    if radius is not None and not (math.isfinite(radius) and radius >= 0.0):
+        print("raytracer: --light-radius takes a finite radius >= 0", file=sys.stderr)  # as bin/raytracer
+        return 2
     import torch
     import torch.distributed as dist
     import skele_raytracer_amd as skr
@@ -180,6 +187,8 @@ def main(argv=None):
             o["depth"] = info.max_depth_parsed
     if o.get("scn_fov") and "fov" not in o["_given"]:  # as bin/raytracer --scn-fov: 2 x the camera line's half_height_angle unless --fov is given
         o["fov"] = skr.scene_fov(scene)
+    if radius is not None:  # as bin/raytracer --light-radius: every point and spot light of the loaded scene (include/skr.h skr_scene_set_light_radii)
+        scene.set_light_radii(radius)
     r = skr.Renderer(scene, local_rank)
     kw = dict(fov=o["fov"], depth=o["depth"], shadow=o["shadow"], seed=o["seed"], shade_triangles=bool(o.get("shade_triangles")), progressive=o.get("progressive", 1), legacy_reflect=bool(o.get("legacy_reflect")))
     if o["gillum"] is not None:
