@@ -480,7 +480,8 @@ static uint32_t sel_tiles(const skr_options *opt, uint32_t tile_rows, const Tile
 
 // Everything of a launch beyond camera_params that is not its output: the scene, the switches and masks, and the options folded and
 // checked — the depth fold, the node-id bound, the fog exclusions.  render_pass and skr_shade_rays both take it.
-static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &p)
+static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p);
+static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &p, GenericFeatures &f)
 {
 	const DeviceScene &s = *r->scene;
 	p.sw = r->sw;
@@ -561,21 +562,11 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 	// --scn-fog: a scene with fog volumes renders on the general level pipeline (render_kernel.hip skr_plan_launch)
 	p.n_fog = s.n_fog;
 	p.fog_row = (uint32_t) s.off_fog;
-	if(p.n_fog > 0 && (opt->legacy_reflect || opt->shade_triangles))
+	// what the scene and the options switch on of the general level pipeline, and whether they go together (launch.h)
+	f = generic_features(r, p);
+	if(const char *why = skr_features_conflict(f, opt->legacy_reflect != 0, opt->shade_triangles != 0, p.n_fog > 0))
 	{
-		skr_set_error("fog volumes (--scn-fog) cannot be combined with --legacy-reflect or --shade-triangles");
-		return SKR_ERR_UNSUPPORTED;
-	}
-	// --scn-spot: a scene with spot lights renders on the general level pipeline's instances with the cone decision
-	if(s.n_spot > 0 && (opt->legacy_reflect || p.n_fog > 0 || s.sphere_tree))
-	{
-		skr_set_error("spot lights (--scn-spot) cannot be combined with %s", opt->legacy_reflect ? "--legacy-reflect" : p.n_fog > 0 ? "fog volumes (--scn-fog)" : "the sphere tree (--sphere-tree)");
-		return SKR_ERR_UNSUPPORTED;
-	}
-	// skr_scene_set_light_radii: a scene with a radius > 0 renders on the general level pipeline's instances with the light sample
-	if(s.soft && (opt->legacy_reflect || p.n_fog > 0 || s.sphere_tree))
-	{
-		skr_set_error("light radii (--light-radius) cannot be combined with %s", opt->legacy_reflect ? "--legacy-reflect" : p.n_fog > 0 ? "fog volumes (--scn-fog)" : "the sphere tree (--sphere-tree)");
+		skr_set_error("%s", why);
 		return SKR_ERR_UNSUPPORTED;
 	}
 	p.counters = s.d_counters;
@@ -620,25 +611,6 @@ static QueryTrees query_trees(const skr_renderer *r)
 	return q;
 }
 
-// Triangle shadows are in force for a launch iff the renderer's scene has them switched on, the launch shades triangles (the option is
-// set and the scene has some) and casts shadow rays (include/skr.h skr_scene_set_triangle_shadows).  Otherwise the launch is the one it
-// was without the switch: the same kernels, the same skr_kernel_variant().
-static bool tri_shadows_in_force(const skr_renderer *r, const RenderParams &p) { return r->scene->tri_shadows && p.shade_triangles && p.use_shadows; }
-
-// the spot lights of a renderer's scene (render_params.h SpotLights)
-static SpotLights spot_lights_of(const skr_renderer *r)
-{
-	const DeviceScene &s = *r->scene;
-	return SpotLights{s.d_blob + s.off_spot, s.spot_first, s.n_spot};
-}
-
-// the radii of a renderer's scene (render_params.h SoftLights)
-static SoftLights soft_lights_of(const skr_renderer *r)
-{
-	const DeviceScene &s = *r->scene;
-	return SoftLights{reinterpret_cast<const float *>(s.d_blob + s.off_radii), s.n_radii};
-}
-
 // the sphere tree of a renderer whose scene had the switch on, under the renderer's switches (render_params.h SphereTree)
 static SphereTree sphere_tree_of(const skr_renderer *r)
 {
@@ -656,6 +628,25 @@ static SphereTree sphere_tree_of(const skr_renderer *r)
 	return t;
 }
 
+// The features of a launch on the general level pipeline (launch.h GenericFeatures).  Triangle shadows are in force iff the renderer's
+// scene has them switched on, the launch shades triangles (the option is set and the scene has some) and casts shadow rays (include/skr.h
+// skr_scene_set_triangle_shadows); otherwise the launch is the one it was without the switch: the same kernels, the same
+// skr_kernel_variant().
+static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p)
+{
+	const DeviceScene &s = *r->scene;
+	GenericFeatures f;
+	f.tri_shadows = s.tri_shadows && p.shade_triangles && p.use_shadows;
+	f.sphere_tree = s.sphere_tree;
+	f.spot = s.n_spot > 0;
+	f.soft = s.soft;
+	if(f.tri_shadows) f.shadows.trees = query_trees(r);
+	if(f.sphere_tree) f.stree = sphere_tree_of(r);
+	if(f.spot || f.soft) f.spots = SpotLights{s.d_blob + s.off_spot, s.spot_first, s.n_spot}; // (n = 0 without spot lights)
+	if(f.soft) f.softs = SoftLights{reinterpret_cast<const float *>(s.d_blob + s.off_radii), s.n_radii};
+	return f;
+}
+
 // one pass of the tiles `ts` selects (render_impl has checked the arguments and set the device)
 static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
 {
@@ -667,12 +658,13 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.out_rows = sel_tiles(opt, tile_rows, ts) * tile_rows;
 	p.band_row0 = 0;
 	p.band_rows = p.out_rows;
-	int rc = launch_params(r, opt, p);
+	GenericFeatures f;
+	int rc = launch_params(r, opt, p, f);
 	if(rc != SKR_OK) return rc;
 	p.rgb = d_rgb;
 	p.rgbf = d_rgbf;
 	LaunchPlan lp;
-	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp, r->scene->sphere_tree, r->scene->n_spot > 0, r->scene->soft);
+	const bool fits = skr_plan_launch(p, (size_t) r->scene->lds_limit, lp, f);
 	rc = check_plan(r, p, fits, lp.lds_bytes, 0);
 	bool kept = false;
 	if(rc == SKR_OK && lp.path != SKR_PATH_DIRECT) rc = take_node_scratch(r, lp.scratch_bytes, &kept);
@@ -707,15 +699,6 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	}
 	r->last_off_ctr = lp.off_ctr;
 	r->last_levels = lp.levels;
-	if(lp.path == SKR_PATH_GENERIC && tri_shadows_in_force(r, p))
-	{ // (shade_triangles: the general level pipeline)
-		lp.tri_shadows = true;
-		lp.shadows.trees = query_trees(r);
-		lp.variant = lp.sphere_tree ? "level_pipeline_g1_stree_tshadow" : lp.soft ? "level_pipeline_g1_soft_tshadow" : lp.spot ? "level_pipeline_g1_spot_tshadow" : "level_pipeline_g1_tshadow";
-	}
-	if(lp.spot || lp.soft) lp.spots = spot_lights_of(r); // (n = 0 without spot lights)
-	if(lp.soft) lp.softs = soft_lights_of(r);
-	if(lp.sphere_tree) lp.stree = sphere_tree_of(r);
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
 	if(r->timing) r->timed.push_back(hook);
@@ -1165,13 +1148,13 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	p.tile_stride = 1;
 	p.out_rows = (uint32_t) (((uint64_t) n + SKR_SHADE_ROW - 1) / SKR_SHADE_ROW);
 	p.band_rows = p.out_rows;
-	rc = launch_params(r, opt, p);
+	GenericFeatures f;
+	rc = launch_params(r, opt, p, f);
 	if(rc != SKR_OK) return rc;
 	p.grid_size = 0; // (one sample: `sample`)
 	GPlan pl;
-	const bool stree = r->scene->sphere_tree;
-	const bool fits = skr_generic_plan(p, pl, stree);
-	rc = check_plan(r, p, fits, stree ? skr_lights_kernels_lds(p) : skr_scene_kernels_lds(p), SKR_SHADE_ROW);
+	const bool fits = skr_generic_plan(p, pl, f.sphere_tree);
+	rc = check_plan(r, p, fits, f.sphere_tree ? skr_lights_kernels_lds(p) : skr_scene_kernels_lds(p), SKR_SHADE_ROW);
 	if(rc == SKR_OK) rc = take_node_scratch(r, pl.total);
 	if(rc != SKR_OK) return rc;
 	p.node_scratch = r->nodes.p;
@@ -1182,19 +1165,8 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	q.n = n;
 	q.trees = query_trees(r);
 	r->last_levels = 0; // (the scratch no longer holds the node pipeline's tables of the last render)
-	TriShadows tsh{};
-	const bool tri_shadows = tri_shadows_in_force(r, p);
-	if(tri_shadows) tsh.trees = q.trees;
-	const SphereTree st = stree ? sphere_tree_of(r) : SphereTree{};
-	if(stree) g_variant = tri_shadows ? "shade_rays_g1_stree_tshadow" : "shade_rays_g1_stree";
-	else if(r->scene->soft) g_variant = tri_shadows ? "shade_rays_g1_soft_tshadow" : "shade_rays_g1_soft";
-	else if(r->scene->n_spot > 0) g_variant = tri_shadows ? "shade_rays_g1_spot_tshadow" : "shade_rays_g1_spot";
-	else g_variant = tri_shadows ? "shade_rays_g1_tshadow" : "shade_rays_g1";
-	const SpotLights spots = spot_lights_of(r);
-	const SoftLights softs = soft_lights_of(r);
-	const bool soft = r->scene->soft;
-	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, &q, tri_shadows ? &tsh : nullptr, stree ? &st : nullptr, r->scene->n_spot > 0 || soft ? &spots : nullptr,
-							   soft ? &softs : nullptr));
+	g_variant = skr_generic_variant(true, f);
+	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, f, &q));
 	return SKR_OK;
 }
 

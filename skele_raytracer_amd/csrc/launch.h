@@ -69,11 +69,24 @@ struct ShadeRays {
 // the rays of one row of a shading query's plan
 constexpr uint32_t SKR_SHADE_ROW = 1024;
 
-// Triangle shadows (include/skr.h skr_scene_set_triangle_shadows): what the shadow walk of the activate kernel reads,
-// handed to the instances that have the walk in an argument of their own, behind a query's ShadeRays (render_generic.hip) — RenderParams,
-// and with it the code of every kernel that takes it, stays as it was.
+// Triangle shadows (include/skr.h skr_scene_set_triangle_shadows): what the shadow walk of the activate kernel reads.
 struct TriShadows {
 	QueryTrees trees; // the walk runs on the trace tree's first set (|L| = 1) for a wave whose shadow rays all start in the ball
+};
+
+// The optional features of a launch on the general level pipeline (render_generic.hip), decided once per launch (api.cpp
+// generic_features) and followed by the plan, the variant's name and the launcher.  Each feature that is on is a kernel argument of its
+// own behind RenderParams, in the one order render_generic.hip with_pack writes down, so that RenderParams — and with it the code of every
+// instance without the feature — stays as it was.  Which features exclude which: skr_features_conflict.
+struct GenericFeatures {
+	bool tri_shadows = false; // triangle shadows are in force: the scene has them switched on, the launch shades triangles and casts shadow rays
+	bool sphere_tree = false; // the scene has the sphere tree switched on and at least one sphere (include/skr.h skr_scene_set_sphere_tree)
+	bool spot = false;        // the scene has at least one spot light (include/skr.h SKR_SCN_SPOT)
+	bool soft = false;        // at least one light of the scene has a radius > 0 (include/skr.h skr_scene_set_light_radii)
+	TriShadows shadows{};     // (tri_shadows)
+	SphereTree stree{};       // (sphere_tree)
+	SpotLights spots{};       // (spot or soft; n = 0 where the scene has no spot light)
+	SoftLights softs{};       // (soft)
 };
 
 enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
@@ -89,14 +102,7 @@ struct LaunchPlan {
 	int levels = 0;                    // ... and how many node / record levels it counts (0 on the other paths)
 	NodePlan nodes;                    // (path == SKR_PATH_NODES)
 	GPlan generic;                     // (path == SKR_PATH_GENERIC)
-	bool tri_shadows = false;          // triangle shadows are in force for this launch (api.cpp render_pass sets it and `shadows`; the plan itself says no)
-	TriShadows shadows{};
-	bool sphere_tree = false;          // the launch renders on the sphere tree (skr_plan_launch's argument; api.cpp render_pass sets `stree`)
-	SphereTree stree{};
-	bool spot = false;                 // the renderer's scene has spot lights (skr_plan_launch's argument; api.cpp render_pass sets `spots`)
-	SpotLights spots{};
-	bool soft = false;                 // some light of the renderer's scene has a radius (skr_plan_launch's argument; api.cpp render_pass sets `spots` and `softs`)
-	SoftLights softs{};
+	GenericFeatures features;          // (path == SKR_PATH_GENERIC) what skr_plan_launch was given
 };
 
 // the scene SoA every kernel stages into LDS (wave_common.h stage_scene): 4 rows per sphere, a zero row, 2 rows per light
@@ -141,10 +147,14 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
-// sphere_tree: the renderer's scene has the sphere tree switched on and at least one sphere (include/skr.h skr_scene_set_sphere_tree)
-// spot: the renderer's scene has at least one spot light (include/skr.h SKR_SCN_SPOT): the general level pipeline, as for fog
-// soft: at least one light of the renderer's scene has a radius > 0 (include/skr.h skr_scene_set_light_radii): likewise
-bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree = false, bool spot = false, bool soft = false); // false: the launch takes a level pipeline and not one band of it fits the budget
+// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights and lights with a radius take the general level pipeline
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, const GenericFeatures &f); // false: the launch takes a level pipeline and not one band of it fits the budget
+// The features a launch cannot combine, given the options as the caller set them: spot lights and lights with a radius exclude
+// --legacy-reflect, fog volumes and the sphere tree; fog excludes --legacy-reflect and --shade-triangles, and with the latter triangle
+// shadows.  (Lights with a radius need the SpotLights argument: the record always carries it.)  The text for the user, or null.
+const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect, bool shade_triangles, bool fog);
+// what skr_kernel_variant() reports for a frame (query: a shading query) on the general level pipeline; static storage
+const char *skr_generic_variant(bool query, const GenericFeatures &f);
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook);
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream);
 // render_nodes.hip
@@ -153,13 +163,9 @@ hipError_t skr_launch_nodes(const RenderParams &p, const NodePlan &pl, hipStream
 hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level, uint32_t *n);
 // render_generic.hip
 bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree = false); // false: not one band fits the budget
+// f: the launch's features (the instances with the arguments they name); a combination skr_features_conflict refuses is an invalid value
 // q: a shading query (p.width = SKR_SHADE_ROW, p.out_rows its rows, p.aa_index its sample); null: a frame
-// ts: triangle shadows are in force (the activate kernel's instances with the shadow walk); null: they are not
-// st: the launch renders on the sphere tree (the instances with the sphere walks, which stage only the lights); null: it does not
-// sp: the scene has spot lights (the activate kernel's instances with the cone decision); null: it has none
-// so: some light has a radius (the activate kernel's instances with the light sample; sp is then given too, n = 0 without spot lights); null: none has
-hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q = nullptr,
-							  const TriShadows *ts = nullptr, const SphereTree *st = nullptr, const SpotLights *sp = nullptr, const SoftLights *so = nullptr);
+hipError_t skr_launch_generic(const RenderParams &p, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const GenericFeatures &f, const ShadeRays *q = nullptr);
 // render_wave.hip
 // Every value the level-0 stage of a node-pipeline launch depends on, and where it is kept: what skr_primary_kernel and plan_for
 // (render_nodes.hip) read.  A frame replays the stage only if its key equals, byte for byte, the key the scratch was last built under

@@ -30,9 +30,12 @@
 // (tests/test_gpu_parity.py, test_shade_triangles.py, test_legacy_reflect.py run every mode through it).
 //
 // Shading queries (include/skr.h skr_shade_rays).  The ray source of level 1 and the sink of level 0 are a compile-time
-// parameter of the three kernels: an empty pack `Q...` is the camera and the image (frames), one ShadeRays the caller's rays and
-// their float[n][3] values.  The empty pack leaves a frame instance's argument block, and so its code, as it was.  Every level below
-// level 1 works on any ray unchanged.
+// parameter of the three kernels: without a ShadeRays in the pack `Q...` the camera and the image (frames), with one the caller's rays
+// and their float[n][3] values.  Every level below level 1 works on any ray unchanged.
+//
+// Instances.  What a launch switches on (launch.h GenericFeatures) reaches the kernels as the pack `Q...` of arguments behind
+// RenderParams, each feature a type of its own, in the one order with_pack (below) writes down; a kernel asks the pack for a type
+// (pack_has, pick).  A feature that is off is not in the pack, which leaves that instance's argument block, and so its code, as it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -137,45 +140,15 @@ SKR_DEV GChild child_of(const SceneView &sv, const RenderParams &p, const GNode 
 	return ch;
 }
 
-// the query of an instance with a ShadeRays argument (the frame instances never call it)
-SKR_DEV ShadeRays query_of(const ShadeRays &q) { return q; }
-SKR_DEV ShadeRays query_of() { return ShadeRays{}; }
-// the activate kernel's pack: [ShadeRays] [TriShadows]
-SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &) { return q; }
-SKR_DEV ShadeRays query_of(const TriShadows &) { return ShadeRays{}; }
-SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts) { return ts; }
-SKR_DEV TriShadows shadows_of(const TriShadows &ts) { return ts; }
-// the packs of the instances with the sphere tree: [ShadeRays] [TriShadows] SphereTree
-SKR_DEV ShadeRays query_of(const ShadeRays &q, const SphereTree &) { return q; }
-SKR_DEV ShadeRays query_of(const SphereTree &) { return ShadeRays{}; }
-SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &, const SphereTree &) { return q; }
-SKR_DEV ShadeRays query_of(const TriShadows &, const SphereTree &) { return ShadeRays{}; }
-SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts, const SphereTree &) { return ts; }
-SKR_DEV TriShadows shadows_of(const TriShadows &ts, const SphereTree &) { return ts; }
-SKR_DEV const SphereTree &stree_of(const SphereTree &st) { return st; }
-template <typename U, typename... R>
-SKR_DEV const SphereTree &stree_of(const U &, const R &...rest) { return stree_of(rest...); }
-// the packs of the instances with spot lights: [ShadeRays] [TriShadows] SpotLights
-SKR_DEV ShadeRays query_of(const ShadeRays &q, const SpotLights &) { return q; }
-SKR_DEV ShadeRays query_of(const SpotLights &) { return ShadeRays{}; }
-SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &, const SpotLights &) { return q; }
-SKR_DEV ShadeRays query_of(const TriShadows &, const SpotLights &) { return ShadeRays{}; }
-SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts, const SpotLights &) { return ts; }
-SKR_DEV TriShadows shadows_of(const TriShadows &ts, const SpotLights &) { return ts; }
-SKR_DEV const SpotLights &spots_of(const SpotLights &sp) { return sp; }
-SKR_DEV const SpotLights &spots_of(const SpotLights &sp, const SoftLights &) { return sp; } // (the packs with a light sample, below)
-template <typename U, typename... R>
-SKR_DEV const SpotLights &spots_of(const U &, const R &...rest) { return spots_of(rest...); }
-// the packs of the instances with a light sample: [ShadeRays] [TriShadows] SpotLights SoftLights
-SKR_DEV ShadeRays query_of(const ShadeRays &q, const SpotLights &, const SoftLights &) { return q; }
-SKR_DEV ShadeRays query_of(const SpotLights &, const SoftLights &) { return ShadeRays{}; }
-SKR_DEV ShadeRays query_of(const ShadeRays &q, const TriShadows &, const SpotLights &, const SoftLights &) { return q; }
-SKR_DEV ShadeRays query_of(const TriShadows &, const SpotLights &, const SoftLights &) { return ShadeRays{}; }
-SKR_DEV TriShadows shadows_of(const ShadeRays &, const TriShadows &ts, const SpotLights &, const SoftLights &) { return ts; }
-SKR_DEV TriShadows shadows_of(const TriShadows &ts, const SpotLights &, const SoftLights &) { return ts; }
-SKR_DEV const SoftLights &soft_of(const SoftLights &so) { return so; }
-template <typename U, typename... R>
-SKR_DEV const SoftLights &soft_of(const U &, const R &...rest) { return soft_of(rest...); }
+// the argument of type T in a kernel's pack, itself; T{} where the pack has none (such an instance never reads it)
+template <typename T>
+SKR_DEV T pick() { return T{}; }
+template <typename T, typename U, typename... R>
+SKR_DEV decltype(auto) pick(const U &u, const R &...rest)
+{
+	if constexpr(std::is_same<T, U>::value) return (u);
+	else return pick<T>(rest...);
+}
 template <typename T, typename... Q>
 constexpr bool pack_has = (std::is_same<T, Q>::value || ...);
 
@@ -212,8 +185,12 @@ SKR_DEV void query_tree(SceneView &sv, const RenderParams &p, const ShadeRays &q
 #ifndef SKR_SHADOW_PAIR_WALK
 #define SKR_SHADOW_PAIR_WALK 1 // 1: one walk tests both rays of a pair of lights against every entry it loads; 0: one walk per light (DESIGN.md 8.9 has both times)
 #endif
+// ON = false means what shade_common.h NoTriangleShadows means, for an instance without the walk: nothing of it is called.  It exists beside
+// NoTriangleShadows only so that the activate kernel can build either from the same three arguments without a constructor or a function in
+// between — each of those moved instructions in instances that had none to move.
+template <bool ON>
 struct TriangleShadows {
-	static constexpr bool on = true;
+	static constexpr bool on = ON;
 	const SceneView &sv;
 	const QueryTrees &trees;
 	int own; // file index of the triangle being shaded, -1 at a sphere hit
@@ -247,9 +224,9 @@ struct TriangleShadows {
 		shadow_triangles<NR>(w, s);
 	}
 	__device__ __forceinline__ void operator()(f3 P, int i, bool second, f3 L0, f3 L1, bool &occ0, bool &occ1) const { lights(P, i, second ? i + 1 : i, second, L0, L1, occ0, occ1); }
-	// the lights l0 and (second) l1, any two of the table (direct_light_spot walks a pair's one light inside its cone as a single)
+	// the lights l0 and (second) l1, any two of the table (direct_light_cone walks a pair's one light inside its cone as a single)
 	__device__ __forceinline__ void lights(f3 P, int l0, int l1, bool second, f3 L0, f3 L1, bool &occ0, bool &occ1) const { ends(P, second, L0, L1, reach(l0, P), reach(l1, P), occ0, occ1); }
-	// two rays with the far ends the caller has (direct_light_soft: the distance to a light's sample)
+	// two rays with the far ends the caller has (direct_light_cone<true>: the distance to a light's sample)
 	__device__ __forceinline__ void ends(f3 P, bool second, f3 L0, f3 L1, float far0, float far1, bool &occ0, bool &occ1) const
 	{
 		const f3 o = add_scalar(P, 0.000001f);
@@ -268,6 +245,12 @@ struct TriangleShadows {
 	}
 };
 
+// shade_common.h SphereLoopShadows, built from what SphereTreeShadows is built from: likewise a duplicate kept for the instances' code alone
+struct SphereLoops {
+	static constexpr bool loops = true;
+	const SphereTree &st; // (never read)
+};
+
 } // namespace
 
 // =====================================================================================================================
@@ -277,7 +260,7 @@ template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, const Q... qs)
 {
 	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>;
-	const ShadeRays q = query_of(qs...);
+	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t A = p.g_arity; // children per node of the level above (1 at the camera level)
@@ -335,7 +318,7 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 			const RayConst r = make_ray(ch.o, ch.d);
 			float tmin;
 			int sph; // raytrace.h:152-165
-			if constexpr(STREE) sph = stree_closest(stree_of(qs...), sv, r, tmin);
+			if constexpr(STREE) sph = stree_closest(pick<SphereTree>(qs...), sv, r, tmin);
 			else sph = closest_sphere(sv, r, tmin);
 			float tcut = tmin;
 			if constexpr(RAYS)
@@ -429,15 +412,14 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 } // namespace
 
 // FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
-// Q: [ShadeRays: a shading query] [TriShadows: triangle shadows are in force — the instances with the shadow walk]
-//    [SpotLights: the scene has spot lights — the instances with the cone decision (never with FOG or the sphere tree: api.cpp launch_params)]
-//    [SpotLights SoftLights: some light has a radius — the instances with the light sample ahead of the cone decision (likewise)]
+// Q: TriShadows — the shadow walk behind the sphere test; SphereTree — the sphere test is the tree's pair walk; SpotLights — the pair loop with
+//    the cone decision; SpotLights SoftLights — and the light sample ahead of it (which packs exist: with_pack)
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
 	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>, SPOT = pack_has<SpotLights, Q...>,
 				   SOFT = pack_has<SoftLights, Q...>;
-	const ShadeRays q = query_of(qs...);
+	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t per_region = (p.rc_cap + 255u) / 256u;
@@ -503,42 +485,18 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		}
 		else n.N = normalize3(n.P - ld3(sv.geom[surf])); // :205
 		cn.hits++;
-		if constexpr(STREE)
-		{ // the sphere test of every pair of lights is the tree's pair walk
-			const SphereTreeShadows ss{stree_of(qs...)};
-			if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn, ss);
-			else if constexpr(TSHADOW)
-			{
-				const TriShadows ts = shadows_of(qs...);
-				n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, TriangleShadows{sv, ts.trees, n.file}, ss);
-			}
-			else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, NoTriangleShadows(), ss);
+		{ // raytrace.h:36-44: the direct light, each arm with what this instance's pack switches on
+			using Shadows = TriangleShadows<TSHADOW>; // what a pair loop calls behind its sphere test
+			using Spheres = std::conditional_t<STREE, SphereTreeShadows, SphereLoops>;  // the sphere test of every pair of lights: the tree's pair walk, or the loops
+			const TriShadows &ts = pick<TriShadows>(qs...);
+			const SphereTree &st = pick<SphereTree>(qs...);
+			const Shadows shadows{sv, ts.trees, n.file};
+			const Spheres spheres{st};
+			if constexpr(SPOT) // the pair loop with the cone decision ahead of the shadow walk (SOFT: and the light sample ahead of that)
+				n.direct = direct_light_cone<SOFT>(sv, p, pick<SpotLights>(qs...), pick<SoftLights>(qs...), kd, ld3(ks4), ambp, n.P, n.N, n.pixel, n.node_id, cn, shadows);
+			else if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn, spheres);
+			else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, shadows, spheres);
 		}
-		else if constexpr(SOFT)
-		{ // the pair loop with the light sample ahead of the cone decision
-			if constexpr(TSHADOW)
-			{
-				const TriShadows ts = shadows_of(qs...);
-				n.direct = direct_light_soft(sv, p, spots_of(qs...), soft_of(qs...), kd, ld3(ks4), ambp, n.P, n.N, n.pixel, n.node_id, cn, TriangleShadows{sv, ts.trees, n.file});
-			}
-			else n.direct = direct_light_soft(sv, p, spots_of(qs...), soft_of(qs...), kd, ld3(ks4), ambp, n.P, n.N, n.pixel, n.node_id, cn);
-		}
-		else if constexpr(SPOT)
-		{ // the pair loop with the cone decision ahead of the shadow walk
-			if constexpr(TSHADOW)
-			{
-				const TriShadows ts = shadows_of(qs...);
-				n.direct = direct_light_spot(sv, p, spots_of(qs...), kd, ld3(ks4), ambp, n.P, n.N, cn, TriangleShadows{sv, ts.trees, n.file});
-			}
-			else n.direct = direct_light_spot(sv, p, spots_of(qs...), kd, ld3(ks4), ambp, n.P, n.N, cn);
-		}
-		else if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn);
-		else if constexpr(TSHADOW)
-		{
-			const TriShadows ts = shadows_of(qs...);
-			n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, TriangleShadows{sv, ts.trees, n.file});
-		}
-		else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn);
 		n.fr = (p.legacy_reflect && !(surf & SURF_TRI)) ? legacy_fresnel(n.d, n.N, ks4.w) : 0.0f; // :46
 		if(p.g_last)
 		{ // its children are shade(depth 0) == (0,0,0): the node is finished
@@ -564,7 +522,7 @@ template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p, const Q... qs)
 {
 	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>;
-	const ShadeRays q = query_of(qs...);
+	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const uint32_t n_nodes = *p.nd_count;
@@ -649,19 +607,41 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
 	return rows > 0 && gplan_for(p, rows, pl);
 }
 
-hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const ShadeRays *q_in, const TriShadows *ts_in,
-							  const SphereTree *st_in, const SpotLights *sp_in, const SoftLights *so_in)
+// Calls `launch` with the pack of an instance: [ShadeRays] [TriShadows] [SphereTree | SpotLights [SoftLights]], the one place the order
+// is written down.  ACT: the activate kernel's pack; the trace and finalize kernels take only [ShadeRays] [SphereTree].  The
+// combinations skr_features_conflict refuses (the sphere tree with spot lights or a radius) are no instance.
+template <bool ACT, typename F>
+static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 {
-	if(so_in && (!sp_in || st_in || p_in.n_fog > 0 || p_in.legacy_reflect)) return hipErrorInvalidValue; // (refused with a text of their own: api.cpp launch_params)
-	if(ts_in && p_in.n_fog > 0) return hipErrorInvalidValue; // (triangle shadows need shade_triangles, which fog excludes: api.cpp launch_params)
-	if(sp_in && (st_in || p_in.n_fog > 0 || p_in.legacy_reflect)) return hipErrorInvalidValue; // (refused with a text of their own: api.cpp launch_params)
+	auto tail = [&](auto... head) {
+		if(f.sphere_tree) return launch(head..., f.stree);
+		if constexpr(ACT)
+		{
+			if(f.soft) return launch(head..., f.spots, f.softs);
+			if(f.spot) return launch(head..., f.spots);
+		}
+		launch(head...);
+	};
+	auto shadows = [&](auto... head) {
+		if constexpr(ACT)
+			if(f.tri_shadows) return tail(head..., f.shadows);
+		tail(head...);
+	};
+	if(q) shadows(*q);
+	else shadows();
+}
+
+hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStream_t stream, const SkrTimingHook *hook, const GenericFeatures &f, const ShadeRays *q_in)
+{
+	if(skr_features_conflict(f, p_in.legacy_reflect != 0, p_in.shade_triangles != 0, p_in.n_fog > 0)) return hipErrorInvalidValue; // (refused with a text: api.cpp launch_params)
 	RenderParams p = p_in;
 	char *base = reinterpret_cast<char *>(p.node_scratch);
 	uint32_t *ctr0 = reinterpret_cast<uint32_t *>(base + pl.off_ctr);
 	auto lvl_ctr = [&](int L) { return ctr0 + SKR_PULL_STRIDE + LVL_CTR_WORDS * (size_t) L; };
 	const int nsamp = (p.grid_size > 0 && !q_in) ? p.grid_size * p.grid_size : 1; // (a query: the one sample p.aa_index)
 	ShadeRays q = q_in ? *q_in : ShadeRays{};
-	const size_t lds = (st_in ? skr_lights_lds_bytes(p) : skr_scene_lds_bytes(p)) + 32;
+	const ShadeRays *qp = q_in ? &q : nullptr; // (q.ray0: the band's)
+	const size_t lds = (f.sphere_tree ? skr_lights_lds_bytes(p) : skr_scene_lds_bytes(p)) + 32;
 	const uint32_t A = skr_tree_arity(p);
 	const int D = pl.levels;
 	hipError_t e = hipSuccess;
@@ -698,43 +678,20 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.ixh = reinterpret_cast<uint4 *>(base + pl.off_hdr[L]);
 				const uint64_t wg_t = (pl.nodes_max[L - 1] * (uint64_t) p.g_arity + 255) / 256;
 				const unsigned grid_t = (unsigned) (wg_t < 49152u ? wg_t : 49152u);
-				if(st_in && q_in) hipLaunchKernelGGL((skr_gtrace_kernel<ShadeRays, SphereTree>), dim3(grid_t), dim3(256), lds, stream, p, q, *st_in);
-				else if(st_in) hipLaunchKernelGGL(skr_gtrace_kernel<SphereTree>, dim3(grid_t), dim3(256), lds, stream, p, *st_in);
-				else if(q_in) hipLaunchKernelGGL(skr_gtrace_kernel<ShadeRays>, dim3(grid_t), dim3(256), lds, stream, p, q);
-				else hipLaunchKernelGGL(skr_gtrace_kernel<>, dim3(grid_t), dim3(256), lds, stream, p);
+				with_pack<false>(f, qp, [&](auto... a) { hipLaunchKernelGGL((skr_gtrace_kernel<decltype(a)...>), dim3(grid_t), dim3(256), lds, stream, p, a...); });
 				p.g_arity = A; // (node ids of this level's hits: parent id * A + child + 1)
 				p.g_nodes_dst = L < D ? reinterpret_cast<float4 *>(base + pl.off_nodes[L]) : nullptr;
 				p.res_out = reinterpret_cast<float *>(base + pl.off_res[L]);
 				const unsigned grid_a = SKR_P1_REGIONS * ((pl.cap[L] + 255u) / 256u);
-				if(st_in)
-				{ // the instances with the sphere tree's pair walk
-					if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in, *st_in);
-					else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in, *st_in);
-					else if(q_in && p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, ShadeRays, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, q, *st_in);
-					else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, q, *st_in);
-					else if(p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *st_in);
-					else hipLaunchKernelGGL((skr_gactivate_kernel<false, SphereTree>), dim3(grid_a), dim3(256), lds, stream, p, *st_in);
-				}
-				else if(so_in)
-				{ // the instances with the light sample (and the cone decision: sp_in->n = 0 where the scene has no spot light)
-					if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows, SpotLights, SoftLights>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in, *sp_in, *so_in);
-					else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows, SpotLights, SoftLights>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in, *sp_in, *so_in);
-					else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, SpotLights, SoftLights>), dim3(grid_a), dim3(256), lds, stream, p, q, *sp_in, *so_in);
-					else hipLaunchKernelGGL((skr_gactivate_kernel<false, SpotLights, SoftLights>), dim3(grid_a), dim3(256), lds, stream, p, *sp_in, *so_in);
-				}
-				else if(sp_in)
-				{ // the instances with the cone decision of the spot lights
-					if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in, *sp_in);
-					else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in, *sp_in);
-					else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, q, *sp_in);
-					else hipLaunchKernelGGL((skr_gactivate_kernel<false, SpotLights>), dim3(grid_a), dim3(256), lds, stream, p, *sp_in);
-				}
-				else if(ts_in && q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, q, *ts_in);
-				else if(ts_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, TriShadows>), dim3(grid_a), dim3(256), lds, stream, p, *ts_in);
-				else if(q_in && p.n_fog > 0) hipLaunchKernelGGL((skr_gactivate_kernel<true, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
-				else if(q_in) hipLaunchKernelGGL((skr_gactivate_kernel<false, ShadeRays>), dim3(grid_a), dim3(256), lds, stream, p, q);
-				else if(p.n_fog > 0) hipLaunchKernelGGL(skr_gactivate_kernel<true>, dim3(grid_a), dim3(256), lds, stream, p);
-				else hipLaunchKernelGGL(skr_gactivate_kernel<false>, dim3(grid_a), dim3(256), lds, stream, p);
+				with_pack<true>(f, qp, [&](auto... a) { // FOG: a separate instance, and only of the packs without triangle shadows and spot lights
+					if constexpr(!pack_has<TriShadows, decltype(a)...> && !pack_has<SpotLights, decltype(a)...>)
+						if(p.n_fog > 0)
+						{
+							hipLaunchKernelGGL((skr_gactivate_kernel<true, decltype(a)...>), dim3(grid_a), dim3(256), lds, stream, p, a...);
+							return;
+						}
+					hipLaunchKernelGGL((skr_gactivate_kernel<false, decltype(a)...>), dim3(grid_a), dim3(256), lds, stream, p, a...);
+				});
 			}
 			for(int L = D - 1; L >= 0; L--)
 			{ // sums, deepest level first; level 0 writes the pixels
@@ -746,10 +703,7 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.res_in = reinterpret_cast<const float *>(base + pl.off_res[L + 1]);
 				p.res_out = L == 0 ? nullptr : reinterpret_cast<float *>(base + pl.off_res[L]);
 				const dim3 grid_f((unsigned) ((pl.nodes_max[L] + 255) / 256));
-				if(st_in && q_in) hipLaunchKernelGGL((skr_gfinalize_kernel<ShadeRays, SphereTree>), grid_f, dim3(256), lds, stream, p, q, *st_in);
-				else if(st_in) hipLaunchKernelGGL(skr_gfinalize_kernel<SphereTree>, grid_f, dim3(256), lds, stream, p, *st_in);
-				else if(q_in) hipLaunchKernelGGL(skr_gfinalize_kernel<ShadeRays>, grid_f, dim3(256), lds, stream, p, q);
-				else hipLaunchKernelGGL(skr_gfinalize_kernel<>, grid_f, dim3(256), lds, stream, p);
+				with_pack<false>(f, qp, [&](auto... a) { hipLaunchKernelGGL((skr_gfinalize_kernel<decltype(a)...>), grid_f, dim3(256), lds, stream, p, a...); });
 			}
 			if(timed) skr_hook_stop(hook, stream);
 			e = hipGetLastError();

@@ -42,23 +42,11 @@ static size_t direct_lds_bytes(const RenderParams &p)
 // A launch is refused (api.cpp render_pass: lp.lds_bytes > the device's LDS) only where no path fits.
 // SKR_PIPELINE=generic forces the general pipeline for every launch, SKR_PIPELINE=nodes keeps triangle meshes on the node pipeline
 // (tests, A/B runs).
-bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bool sphere_tree, bool spot, bool soft)
+bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, const GenericFeatures &f)
 {
 	lp = LaunchPlan();
-	lp.spot = spot;
-	lp.soft = soft;
-	if(sphere_tree)
-	{ // the sphere tree: every frame on the general level pipeline's instances with the sphere walks
-		lp.path = SKR_PATH_GENERIC;
-		lp.variant = "level_pipeline_g1_stree";
-		lp.sphere_tree = true;
-		if(!skr_generic_plan(p, lp.generic, true)) return false;
-		lp.scratch_bytes = lp.generic.total;
-		lp.lds_bytes = skr_lights_kernels_lds(p);
-		if(p.grid_size > 0) lp.acc_bytes = (size_t) p.width * p.out_rows * 12;
-		return true;
-	}
-	const bool generic_only = p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || spot || soft;
+	lp.features = f;
+	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft;
 	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
 		lp.path = SKR_PATH_NODES;
@@ -69,12 +57,13 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bo
 		lp.levels = lp.nodes.levels;
 	}
 	else if(generic_only || p.max_depth > 1 || direct_lds_bytes(p) > lds_limit)
-	{ // (a frame without a tree whose scene leaves the direct kernel no room for its tile: the general pipeline renders it as well)
+	{ // (a frame without a tree whose scene leaves the direct kernel no room for its tile: the general pipeline renders it as well;
+	  // the sphere tree, DESIGN.md 8.10: every frame, on the instances with the sphere walks, which stage only the lights)
 		lp.path = SKR_PATH_GENERIC;
-		lp.variant = soft ? "level_pipeline_g1_soft" : spot ? "level_pipeline_g1_spot" : "level_pipeline_g1";
-		if(!skr_generic_plan(p, lp.generic)) return false;
+		lp.variant = skr_generic_variant(false, f);
+		if(!skr_generic_plan(p, lp.generic, f.sphere_tree)) return false;
 		lp.scratch_bytes = lp.generic.total;
-		lp.lds_bytes = skr_scene_kernels_lds(p);
+		lp.lds_bytes = f.sphere_tree ? skr_lights_kernels_lds(p) : skr_scene_kernels_lds(p);
 	}
 	else
 	{
@@ -85,12 +74,30 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, bo
 	return true;
 }
 
+const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect, bool shade_triangles, bool fog)
+{
+	if(fog && (legacy_reflect || shade_triangles || f.tri_shadows)) return "fog volumes (--scn-fog) cannot be combined with --legacy-reflect or --shade-triangles";
+	const int with = legacy_reflect ? 0 : fog ? 1 : f.sphere_tree ? 2 : -1;
+	static const char *const spot[3] = {"spot lights (--scn-spot) cannot be combined with --legacy-reflect", "spot lights (--scn-spot) cannot be combined with fog volumes (--scn-fog)",
+										"spot lights (--scn-spot) cannot be combined with the sphere tree (--sphere-tree)"};
+	static const char *const soft[3] = {"light radii (--light-radius) cannot be combined with --legacy-reflect", "light radii (--light-radius) cannot be combined with fog volumes (--scn-fog)",
+										"light radii (--light-radius) cannot be combined with the sphere tree (--sphere-tree)"};
+	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : nullptr;
+}
+
+const char *skr_generic_variant(bool query, const GenericFeatures &f)
+{ // (fog has no name of its own)
+	static const char *const name[2][4][2] = {
+		{{"level_pipeline_g1", "level_pipeline_g1_tshadow"}, {"level_pipeline_g1_stree", "level_pipeline_g1_stree_tshadow"},
+		 {"level_pipeline_g1_spot", "level_pipeline_g1_spot_tshadow"}, {"level_pipeline_g1_soft", "level_pipeline_g1_soft_tshadow"}},
+		{{"shade_rays_g1", "shade_rays_g1_tshadow"}, {"shade_rays_g1_stree", "shade_rays_g1_stree_tshadow"},
+		 {"shade_rays_g1_spot", "shade_rays_g1_spot_tshadow"}, {"shade_rays_g1_soft", "shade_rays_g1_soft_tshadow"}}};
+	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][f.tri_shadows];
+}
+
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)
 {
-	if(lp.path == SKR_PATH_GENERIC)
-		return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook, nullptr, lp.tri_shadows ? &lp.shadows : nullptr, lp.sphere_tree ? &lp.stree : nullptr,
-												   lp.spot || lp.soft ? &lp.spots : nullptr, lp.soft ? &lp.softs : nullptr)
-							  : hipErrorInvalidValue;
+	if(lp.path == SKR_PATH_GENERIC) return p.node_scratch ? skr_launch_generic(p, lp.generic, stream, hook, lp.features) : hipErrorInvalidValue;
 	if(lp.path == SKR_PATH_NODES) return p.node_scratch ? skr_launch_nodes(p, lp.nodes, stream, hook) : hipErrorInvalidValue;
 	if(p.n_spheres >= 65536) return hipErrorInvalidValue; // (one launch, no tree: any scene the LDS holds)
 	skr_hook_start(hook, stream);
@@ -220,7 +227,7 @@ SKR_DEV void skr_debug_predicates(int op, const uint32_t *in, uint32_t *out, uin
 			}
 			break;
 		}
-		case 17: { // the cone decision and factor of one spot light at one shading point: spot_cone, the function direct_light_spot calls
+		case 17: { // the cone decision and factor of one spot light at one shading point: spot_cone, the function direct_light_cone calls
 			const uint32_t *r = in + 8 * i;
 			const SpotCone c = spot_cone(v3(r), F(r[3]), F(r[4]), v3(r + 5));
 			if(live)
@@ -230,7 +237,7 @@ SKR_DEV void skr_debug_predicates(int op, const uint32_t *in, uint32_t *out, uin
 			}
 			break;
 		}
-		case 18: { // the sample of one light with a radius for one shading node: soft_sample, the function direct_light_soft calls
+		case 18: { // the sample of one light with a radius for one shading node: soft_sample, the function direct_light_cone<true> calls
 			const uint32_t *r = in + 10 * i;
 			const f3 s = soft_sample(r[0], r[1], r[2], r[3], r[4], r[5], v3(r + 6), F(r[9]));
 			if(live)

@@ -782,6 +782,17 @@ SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3
 	return total;
 }
 
+// raytrace.h:36-44's closing sum, ambient + diffuse + specular from (0,0,0).  direct_light_cone's; direct_light_of and direct_light_fog keep
+// their own copies of it and of the Blinn-Phong terms, as does direct_light_cone of the latter.
+SKR_DEV f3 light_sum(float4 ambp, f3 diffuse, f3 specular)
+{
+	f3 total = mk3(0, 0, 0);
+	total = total + ld3(ambp);
+	total = total + diffuse;
+	total = total + specular;
+	return total;
+}
+
 // ---- spot lights (include/skr.h SKR_SCN_SPOT; general level pipeline only) ----
 // The cone decision and factor of one light at one shading point: a, c1, c2 as the host derived them (render_params.h SpotLights), L the
 // unit vector from the point to the light (light_term).  One correctly rounded binary32 operation per step; NaN: outside.
@@ -796,72 +807,6 @@ SKR_DEV SpotCone spot_cone(f3 a, float c1, float c2, f3 L)
 	if(!(c > c2)) return SpotCone{0.0f, true};
 	const float u = sk_divf(c - c2, c1 - c2);
 	return SpotCone{(u * u) * (3.0f - 2.0f * u), false};
-}
-
-// direct_light_of<false>() for a scene with spot lights: the pair loop with the cone decision ahead of the shadow walk.  A pair whose
-// lights are both inside (or no spot lights) is walked as direct_light_of walks it, with the union of both shadow masks; where one
-// light is outside at P the other is walked as a single, with its own mask; where both are, the lane casts nothing.  An outside light
-// counts no shadow ray and no sphere test and meets no triangle.
-template <typename TS = NoTriangleShadows>
-SKR_DEV f3 direct_light_spot(const SceneView &sv, const RenderParams &p, const SpotLights &sp, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn,
-							 const TS &tri_shadows = TS())
-{
-	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
-	const f3 view = normalize3(p.cam_pos - P);
-	for(int i = 0; i < sv.nl; i += 2)
-	{
-		const bool second = i + 1 < sv.nl;
-		LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
-		bool in0 = true, in1 = second;
-		auto cone = [&](int l, LightTerm &t, bool &in)
-		{
-			if((uint32_t) (l - sp.first) < (uint32_t) sp.n)
-			{ // (l is wave-uniform: the rows come through the scalar cache)
-				const float4 A = load_const4(sp.cones, 2 * (l - sp.first)), B = load_const4(sp.cones, 2 * (l - sp.first) + 1);
-				const SpotCone c = spot_cone(ld3(A), A.w, B.x, t.L);
-				in = !c.outside;
-				t.lc = t.lc * c.f; // (per component, before anything else; x * 1 == x)
-			}
-		};
-		cone(i, t0, in0);
-		if(second) cone(i + 1, t1, in1);
-		bool occ0 = !in0, occ1 = !in1; // (dark: occluded, or outside its cone)
-		if(p.use_shadows && (in0 || in1))
-		{ // the rays of the lane: (a, b) = the pair, or a = the one light that is inside
-			const bool both = in0 && in1;
-			const int la = in0 ? i : i + 1;
-			const f3 La = in0 ? t0.L : t1.L;
-			cn.shadow_rays += both ? 2u : 1u;
-			uint32_t cand = 0u;
-			if(sv.smask)
-			{
-				cand = shadow_mask_of(sv, la, ld3(sv.lights[2 * la]) - P);
-				if(both) cand |= shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P);
-			}
-			bool oa, ob;
-			occluded_pair<false>(sv, P, La, t1.L, both, oa, ob, cn.shadow_tests, cand);
-			if constexpr(TS::on) tri_shadows.lights(P, la, i + 1, both, La, t1.L, oa, ob);
-			occ0 = in0 ? oa : true;
-			occ1 = both ? ob : (in1 ? oa : true);
-		}
-		auto add_light = [&](const LightTerm &t, bool lit)
-		{
-			if(lit)
-			{
-				diffuse = diffuse + ((kd * t.lc) * t.intensity) * max0(dot3(N, t.L));
-				const f3 vl = view + t.L;
-				const f3 H = vl / length3(vl);
-				specular = specular + ((ks * t.lc) * t.intensity) * powf_spec(max0(dot3(N, H)), ambp.w, p.pow_steps);
-			}
-		};
-		add_light(t0, !occ0);
-		add_light(t1, !occ1);
-	}
-	f3 total = mk3(0, 0, 0);
-	total = total + ld3(ambp);
-	total = total + diffuse;
-	total = total + specular;
-	return total;
 }
 
 // ---- lights with a radius (include/skr.h skr_scene_set_light_radii; general level pipeline only) ----
@@ -888,23 +833,27 @@ SKR_DEV float load_const1(const float *base, int i)
 	return q[i];
 }
 
-// direct_light_spot() for a scene in which some light has a radius: the same pair loop with the sample ahead of the cone decision.  A
-// light with R > 0 is, for this node, the point light at its sample: L, 1 / d^2, the cone decision, the shadow ray and the far end of the
-// triangle walk all come from the sample.  A pair in which either light has R > 0 walks every sphere (the shadow masks are built for rays
-// toward Lp); a pair of two R == 0 lights is walked as direct_light_spot walks it.  (pixel, node): the node's counter words.
-// Nothing of a sample stays live across the shadow walk but its LightTerm: the triangle walk's far end draws the sample again.
-template <typename TS = NoTriangleShadows>
-SKR_DEV f3 direct_light_soft(const SceneView &sv, const RenderParams &p, const SpotLights &sp, const SoftLights &so, f3 kd, f3 ks, float4 ambp, f3 P, f3 N,
-							 uint32_t pixel, uint32_t node, Counters &cn, const TS &tri_shadows = TS())
+// direct_light_of<false>() for a scene with spot lights: the pair loop with the cone decision ahead of the shadow walk.  A pair whose
+// lights are both inside (or no spot lights) is walked as direct_light_of walks it, with the union of both shadow masks; where one
+// light is outside at P the other is walked as a single, with its own mask; where both are, the lane casts nothing.  An outside light
+// counts no shadow ray and no sphere test and meets no triangle.
+// SOFT: some light of the scene has a radius — the sample ahead of the cone decision.  A light with R > 0 is, for this node, the point
+// light at its sample: L, 1 / d^2, the cone decision, the shadow ray and the far end of the triangle walk all come from the sample.  A
+// pair in which either light has R > 0 walks every sphere (the shadow masks are built for rays toward Lp); a pair of two R == 0 lights
+// is walked as without SOFT.  (pixel, node): the node's counter words.  Nothing of a sample stays live across the shadow walk but its
+// LightTerm: the triangle walk's far end draws the sample again.
+template <bool SOFT, typename TS>
+SKR_DEV f3 direct_light_cone(const SceneView &sv, const RenderParams &p, const SpotLights &sp, const SoftLights &so, f3 kd, f3 ks, float4 ambp, f3 P, f3 N,
+							 uint32_t pixel, uint32_t node, Counters &cn, const TS &tri_shadows)
 {
 	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
 	const f3 view = normalize3(p.cam_pos - P);
 	for(int i = 0; i < sv.nl; i += 2)
 	{
 		const bool second = i + 1 < sv.nl;
-		// (l is wave-uniform: the radius comes through the scalar cache, and the branches on it are the wave's)
+		// (l is wave-uniform: the radius and the cone rows come through the scalar cache, and the branches on them are the wave's)
 		auto radius = [&](int l) { return l < so.n ? load_const1(so.radii, l) : 0.0f; };
-		const float R0 = radius(i), R1 = second ? radius(i + 1) : 0.0f;
+		const float R0 = SOFT ? radius(i) : 0.0f, R1 = SOFT && second ? radius(i + 1) : 0.0f;
 		auto to_light = [&](int l, float R) { return soft_sample(pixel, p.aa_index, node, (uint32_t) l, p.seed_lo, p.seed_hi, ld3(sv.lights[2 * l]), R) - P; };
 		auto term = [&](int l, float R)
 		{
@@ -917,7 +866,8 @@ SKR_DEV f3 direct_light_soft(const SceneView &sv, const RenderParams &p, const S
 			t.intensity = lt.inv2;
 			return t;
 		};
-		LightTerm t0 = term(i, R0), t1 = second ? term(i + 1, R1) : t0;
+		// (SOFT is a constant, one arm of each ?: is compiled; without it the second term is light_term at the index `second` selects, as in direct_light_of)
+		LightTerm t0 = SOFT ? term(i, R0) : light_term(sv, i, P), t1 = SOFT ? (second ? term(i + 1, R1) : t0) : light_term(sv, second ? i + 1 : i, P);
 		bool in0 = true, in1 = second;
 		auto cone = [&](int l, LightTerm &t, bool &in)
 		{
@@ -926,21 +876,25 @@ SKR_DEV f3 direct_light_soft(const SceneView &sv, const RenderParams &p, const S
 				const float4 A = load_const4(sp.cones, 2 * (l - sp.first)), B = load_const4(sp.cones, 2 * (l - sp.first) + 1);
 				const SpotCone c = spot_cone(ld3(A), A.w, B.x, t.L);
 				in = !c.outside;
-				t.lc = t.lc * c.f;
+				t.lc = t.lc * c.f; // (per component, before anything else; x * 1 == x)
 			}
 		};
 		cone(i, t0, in0);
 		if(second) cone(i + 1, t1, in1);
-		bool occ0 = !in0, occ1 = !in1;
+		bool occ0 = !in0, occ1 = !in1; // (dark: occluded, or outside its cone)
 		if(p.use_shadows && (in0 || in1))
-		{
+		{ // the rays of the lane: (a, b) = the pair, or a = the one light that is inside
 			const bool both = in0 && in1;
 			const int la = in0 ? i : i + 1;
 			const f3 La = in0 ? t0.L : t1.L;
 			cn.shadow_rays += both ? 2u : 1u;
-			const bool soft_pair = R0 > 0.0f || R1 > 0.0f;
-			SceneView w = sv;
-			if(soft_pair) w.smask = nullptr; // every sphere
+			SceneView every; // SOFT: the scene without its shadow masks, for a pair with a sample (every sphere)
+			if constexpr(SOFT)
+			{
+				every = sv;
+				if(R0 > 0.0f || R1 > 0.0f) every.smask = nullptr;
+			}
+			const SceneView &w = SOFT ? every : sv; // (two lvalues of one type: a reference to one of them, no copy; without SOFT `every` is never touched)
 			uint32_t cand = 0u;
 			if(w.smask)
 			{
@@ -949,12 +903,13 @@ SKR_DEV f3 direct_light_soft(const SceneView &sv, const RenderParams &p, const S
 			}
 			bool oa, ob;
 			occluded_pair<false>(w, P, La, t1.L, both, oa, ob, cn.shadow_tests, cand);
-			if constexpr(TS::on)
+			if constexpr(TS::on && SOFT)
 			{ // blinn_phong.h's `distance`, of the sample where the light has one
 				auto far = [&](int l, float R) { return R > 0.0f ? length3(to_light(l, R)) : tri_shadows.reach(l, P); };
 				const float fa = far(la, in0 ? R0 : R1), fb = both ? far(i + 1, R1) : fa;
 				tri_shadows.ends(P, both, La, t1.L, fa, fb, oa, ob);
 			}
+			else if constexpr(TS::on) tri_shadows.lights(P, la, i + 1, both, La, t1.L, oa, ob);
 			occ0 = in0 ? oa : true;
 			occ1 = both ? ob : (in1 ? oa : true);
 		}
@@ -971,11 +926,7 @@ SKR_DEV f3 direct_light_soft(const SceneView &sv, const RenderParams &p, const S
 		add_light(t0, !occ0);
 		add_light(t1, !occ1);
 	}
-	f3 total = mk3(0, 0, 0);
-	total = total + ld3(ambp);
-	total = total + diffuse;
-	total = total + specular;
-	return total;
+	return light_sum(ambp, diffuse, specular);
 }
 
 template <bool COHERENT>
