@@ -118,6 +118,7 @@ struct skr_renderer {
 	hipEvent_t frame_e0 = nullptr, frame_e1 = nullptr; // the *_host entries' timing (timed_host)
 	size_t last_off_ctr = 0; // the node-pipeline counters of the launch last enqueued (skr_renderer_last_*_count): where in `nodes` ...
 	int last_levels = 0;     // ... and how many levels they count (0: the launch took another path)
+	int last_leaf_shape = -1; // skr_renderer_last_leaf_shape
 	bool timing = false;
 	bool count_tri = false; // skr_renderer_count_triangle_work
 	// the node pipeline's level-0 stage kept in `nodes` (launch.h PrimaryKey, take_node_scratch)
@@ -156,6 +157,7 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_GI_MASK")) sw.gi_mask = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_GI_SURFACE")) sw.gi_surface = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_SHADOW_SURFACE")) sw.shadow_mask = (sw.shadow_mask & ~2) | (atoi(e) > 0 ? 2 : 0);
+	if(const char *e = getenv("SKR_LEAF_SHAPE")) sw.shadow_mask = (sw.shadow_mask & ~SKR_SW_LEAF_SHAPE) | (atoi(e) > 0 ? SKR_SW_LEAF_SHAPE : 0);
 	if(const char *e = getenv("SKR_PRIMARY_CACHE")) sw.primary_cache = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_ADAPTIVE_PATH")) sw.adaptive_path = !strcmp(e, "frame") ? 1 : !strcmp(e, "query") ? 2 : 0;
 }
@@ -699,6 +701,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	}
 	r->last_off_ctr = lp.off_ctr;
 	r->last_levels = lp.levels;
+	r->last_leaf_shape = (lp.path == SKR_PATH_NODES && !lp.nodes.flat) ? (int) skr_leaf_shape(p) : -1; // (what launch_leaf2, render_nodes.hip, asks too)
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
 	if(r->timing) r->timed.push_back(hook);
@@ -790,6 +793,36 @@ int skr_renderer_primary_cache_stats(skr_renderer *r, uint64_t *builds, uint64_t
 	if(builds) *builds = r->level0_builds;
 	if(replays) *replays = r->level0_replays;
 	return SKR_OK;
+}
+
+// Internal (not in include/skr.h: tests only).  The shape whose instance of the leaf kernel the launch last enqueued ran (launch.h
+// SkrLeafShape: 0 = the instance that reads every fact at run time); -1: that launch ran no leaf kernel (another path, the flat schedule).
+int skr_renderer_last_leaf_shape(const skr_renderer *r) { return r ? r->last_leaf_shape : -1; }
+
+// Internal (tests only; no device involved): skr_leaf_shape (launch.h) of the launch that a renderer of `scene` would make for `opt`
+// under the SKR_* switches of the environment as it is now — launch_params on the packed scene, nothing uploaded.  < 0: minus an error code.
+int skr_scene_leaf_shape(const skr_scene *scene, const skr_options *opt)
+{
+	if(!scene || !opt) return -SKR_ERR_ARG;
+	auto ds = std::make_shared<DeviceScene>();
+	ds->info = scene->info;
+	std::vector<skr_f4> rows = pack_scene(*scene, *ds);
+	std::vector<unsigned long long> counters((size_t) SKR_COUNTER_SHARDS * 4 + 16);
+	ds->d_blob = reinterpret_cast<float4 *>(rows.data()); // (host memory: only addresses are formed, and null-ness asked)
+	ds->d_counters = counters.data();
+	int rc;
+	{
+		skr_renderer r;
+		r.scene = ds;
+		load_switches(r.sw);
+		RenderParams p = camera_params(&r, opt, opt->seed, 0);
+		GenericFeatures f;
+		rc = launch_params(&r, opt, p, f);
+		rc = rc == SKR_OK ? (int) skr_leaf_shape(p) : -rc;
+	}
+	ds->d_blob = nullptr; // (neither is the device's: nothing for ~DeviceScene to free)
+	ds->d_counters = nullptr;
+	return rc;
 }
 
 // Per tile of `tile_rows` image rows: the work its pixels cost, counted — the tile is rendered on its own and the work counters read

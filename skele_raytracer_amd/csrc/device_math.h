@@ -401,13 +401,15 @@ SKR_DEV float pow_int_flat(float x, unsigned n)
 	}
 	return (float) r;
 }
+// LE7: the caller knows steps <= 7 (shade_common.h PointLightShape): no branch, and `steps` is not read
+template <bool LE7 = false>
 SKR_DEV float powf_spec(float x, float p, int steps)
 {
 #if SKR_FLAT_POW
 	const bool plain = (p >= 1.0f) && (p <= 1024.0f) && (p == __builtin_rintf(p)) && (x >= 0.0f);
 	if(__builtin_expect(!plain, 0)) return powf_spec_cold(x, p);
 	// (`steps` is wave-uniform: one scalar branch picks the unrolled length — exponents below 128 in every shipped scene)
-	return steps <= 7 ? pow_int_flat<7>(x, (unsigned) p) : pow_int_flat<11>(x, (unsigned) p);
+	return (LE7 || steps <= 7) ? pow_int_flat<7>(x, (unsigned) p) : pow_int_flat<11>(x, (unsigned) p);
 #else
 	return powf_spec_cold(x, p);
 #endif

@@ -145,6 +145,21 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 	return lo;
 }
 
+// The launch shape the leaf kernel (render_nodes.hip skr_leaf_kernel2) has an instance for (shade_common.h PointLightShape<1 | 2>), or
+// none: the instance that reads every fact at run time.  A shape is picked only where EVERY fact it compiles in equals the launch's value:
+// a sphere-only scene with GI masks (the instances are <false, FIRST, true, shape>) of 16-bit entries (at most 16 spheres), shadow rays
+// cast through the shadow masks — which exist only for scenes whose lights are all point lights (scene_host.cpp build_shadow_masks), so no
+// light is directional —, every integer Phong exponent below 128, and exactly one or two lights.  SKR_LEAF_SHAPE=0: never.
+enum SkrLeafShape { SKR_LEAF_RUNTIME = 0, SKR_LEAF_POINT1 = 1, SKR_LEAF_POINT2 = 2 };
+static inline SkrLeafShape skr_leaf_shape(const RenderParams &p)
+{
+	if(!(p.sw.shadow_mask & SKR_SW_LEAF_SHAPE)) return SKR_LEAF_RUNTIME;
+	if(p.n_tris != 0 || p.gi_index == nullptr || p.gi_wide != 0) return SKR_LEAF_RUNTIME;
+	if(!p.use_shadows || p.shadow_masks == nullptr) return SKR_LEAF_RUNTIME;
+	if(p.pow_steps > 7) return SKR_LEAF_RUNTIME;
+	return p.n_lights == 2 ? SKR_LEAF_POINT2 : p.n_lights == 1 ? SKR_LEAF_POINT1 : SKR_LEAF_RUNTIME;
+}
+
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
 // f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights and lights with a radius take the general level pipeline

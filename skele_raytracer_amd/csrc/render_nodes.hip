@@ -199,6 +199,8 @@ struct Activated {
 	float r1;
 };
 
+// SH: the facts of the launch that are compiled in (shade_common.h; RunTimeShape: none)
+template <typename SH = RunTimeShape>
 SKR_DEV Activated activate_record(const SceneView &sv, const RenderParams &p, bool act, uint32_t rec, Counters &cn)
 {
 	Activated a;
@@ -236,7 +238,7 @@ SKR_DEV Activated activate_record(const SceneView &sv, const RenderParams &p, bo
 		const f3 P = co0 + d * t;
 		a.N = normalize3(P - ld3(sv.geom[a.sph]));
 		cn.hits++;
-		a.direct = direct_light<false>(sv, p, (int) a.sph, P, a.N, cn);
+		a.direct = direct_light<false, SH>(sv, p, (int) a.sph, P, a.N, cn);
 		a.co = add_scalar(P, 0.00001f);
 	}
 	return a;
@@ -348,6 +350,7 @@ SKR_DEV void ring_push(Ring &q, bool pred, f3 d, uint32_t ids, float r1)
 // Shade the m <= 64 oldest queued leaf hits, one per lane: raytrace.h:194-213 with indirect = (0,0,0)/N (the leaf's own
 // children are shade(depth 0)), then its parent's accumulation term (:130) into the slot window of its round.
 // `co` = the child-ray origin of the node THIS lane holds (the hits' parents are lanes of this wave).
+template <typename SH>
 SKR_DEV void leaf_batch(const SceneView &sv, const RenderParams &p, Ring &q, float *slots, f3 co, int lane, int m, Counters &cn)
 {
 	wave_lds_fence();
@@ -376,7 +379,7 @@ SKR_DEV void leaf_batch(const SceneView &sv, const RenderParams &p, Ring &q, flo
 		const f3 P = co_k + d * t;
 		const f3 Nn = normalize3(P - ld3(sv.geom[sph]));
 		cn.hits++;
-		const f3 direct = direct_light<false>(sv, p, sph, P, Nn, cn);
+		const f3 direct = direct_light<false, SH>(sv, p, sph, P, Nn, cn);
 		const f3 total = mk3(0, 0, 0); // (0,0,0) / N with N >= 1 (skr_nodes_plan): +0 in every component, no division needed
 		const f3 colour = (div3_const(direct, SKR_DIV_PI) + total * 2.0f) * ld3(sv.kd[sph]);
 		const f3 c = div3_const(colour * r1, SKR_DIV_PDF);
@@ -391,6 +394,16 @@ SKR_DEV void leaf_batch(const SceneView &sv, const RenderParams &p, Ring &q, flo
 	q.count = uni(q.count - m);
 	wave_lds_fence();
 }
+
+// the shape a kernel is compiled for: the one it names, or none (RunTimeShape)
+template <typename... S>
+struct ShapeOf {
+	typedef RunTimeShape type;
+};
+template <typename S>
+struct ShapeOf<S> {
+	typedef S type;
+};
 
 } // namespace
 
@@ -425,15 +438,19 @@ extern "C" void skr_leaf2_times_read(unsigned long long *out)
 #ifndef SKR_LEAF2_OCC
 #define SKR_LEAF2_OCC 4 // waves per SIMD the register allocation aims at (A/B builds)
 #endif
-template <bool TRIS, bool FIRST, bool GIM>
+// SHAPE: none, or the one launch shape the instance is compiled for (shade_common.h PointLightShape; the launcher picks it only for a
+// launch that has it, launch.h skr_leaf_shape): the facts it fixes are constants of the shading and tracing code below, which then
+// holds no scalar for them and has neither the light loop nor the branches on them
+template <bool TRIS, bool FIRST, bool GIM, typename... SHAPE>
 __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const RenderParams p)
 {
+	typedef typename ShapeOf<SHAPE...>::type SH;
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
 	const SceneView sv = stage_scene(p, lds4, TRIS); // the only workgroup barrier
 	const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 	const uint32_t g = (uint32_t) blockIdx.x * 4u + (uint32_t) wave;
-	float *wbase = reinterpret_cast<float *>(lds4 + 4 * p.n_spheres + 1 + 2 * p.n_lights) + wave * LEAF2_WAVE_FLOATS;
+	float *wbase = reinterpret_cast<float *>(lds4 + 4 * p.n_spheres + 1 + 2 * (SH::lights > 0 ? SH::lights : p.n_lights)) + wave * LEAF2_WAVE_FLOATS;
 	Ring q{wbase, 0, 0};
 	float *slots = wbase + NQ_CAP * NQ_F;
 	const int N = p.num_path_traces, PP = (N + 1) >> 1;
@@ -525,7 +542,7 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 		else
 		{
 			out_idx = region * p.rc_cap + first + (uint32_t) lane;
-			const Activated a = activate_record(sv, p, act0, out_idx, cn);
+			const Activated a = activate_record<SH>(sv, p, act0, out_idx, cn);
 			co = a.co;
 			Nn = a.N;
 			direct1 = a.direct;
@@ -576,7 +593,7 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 				cn.rays += second ? 2u : 1u;
 				const RayPair rp = make_pair(d0, d1);
 				BestState s0, s1;
-				closest_pair<GIM>(sv, p, gi_row, co, d0, d1, second, rp, s0, s1);
+				closest_pair<GIM, SH>(sv, p, gi_row, co, d0, d1, second, rp, s0, s1);
 				bool black;
 				hit0 = classify_child(sv, co, d0, rp.two_a.x, rp.four_a.x, s0, black);
 				if(!hit0)
@@ -620,7 +637,7 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 				}
 				if(!go) break;
 				STAMP(4);
-				leaf_batch(sv, p, q, slots, co, lane, q.count < 64 ? q.count : 64, cn);
+				leaf_batch<SH>(sv, p, q, slots, co, lane, q.count < 64 ? q.count : 64, cn);
 				STAMP(3);
 			}
 			STAMP(4);
@@ -899,18 +916,29 @@ hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level,
 	return hipSuccess;
 }
 
+typedef void (*LeafKernel)(const RenderParams);
+// The leaf kernel's instance for a launch.  The instances with a compiled-in shape exist for sphere-only scenes with GI masks, one per
+// shape of skr_leaf_shape (launch.h), which alone decides whether a launch has one.
+template <bool FIRST>
+static LeafKernel leaf_instance(const RenderParams &p)
+{ // (GI masks exist for sphere-only scenes alone: scene_host.cpp build_gi_masks)
+	switch(skr_leaf_shape(p))
+	{
+	case SKR_LEAF_POINT2: return skr_leaf_kernel2<false, FIRST, true, PointLightShape<2>>;
+	case SKR_LEAF_POINT1: return skr_leaf_kernel2<false, FIRST, true, PointLightShape<1>>;
+	default: break;
+	}
+	if(p.n_tris > 0) return skr_leaf_kernel2<true, FIRST, false>;
+	return p.gi_index != nullptr ? skr_leaf_kernel2<false, FIRST, true> : skr_leaf_kernel2<false, FIRST, false>;
+}
+
 template <bool FIRST>
 static hipError_t launch_leaf2(const RenderParams &p, size_t lds, hipStream_t stream)
-{ // (GI masks exist for sphere-only scenes alone: scene_host.cpp build_gi_masks)
-	const bool gim = p.n_tris == 0 && p.gi_index != nullptr;
-	const void *fn = p.n_tris > 0 ? reinterpret_cast<const void *>(skr_leaf_kernel2<true, FIRST, false>)
-					 : gim        ? reinterpret_cast<const void *>(skr_leaf_kernel2<false, FIRST, true>)
-								  : reinterpret_cast<const void *>(skr_leaf_kernel2<false, FIRST, false>);
-	hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+{
+	const LeafKernel fn = leaf_instance<FIRST>(p);
+	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 	if(e != hipSuccess) return e;
-	if(p.n_tris > 0) hipLaunchKernelGGL((skr_leaf_kernel2<true, FIRST, false>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
-	else if(gim) hipLaunchKernelGGL((skr_leaf_kernel2<false, FIRST, true>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
-	else hipLaunchKernelGGL((skr_leaf_kernel2<false, FIRST, false>), dim3(LEAF2_GRID), dim3(256), lds, stream, p);
+	hipLaunchKernelGGL(fn, dim3(LEAF2_GRID), dim3(256), lds, stream, p);
 	return hipGetLastError();
 }
 

@@ -32,6 +32,34 @@ struct SceneView {
 	uint32_t smask_all;
 };
 typedef float skr_v4f __attribute__((ext_vector_type(4)));
+
+// ---- the shape of a launch, compiled in (DESIGN.md 5.2 "Launch shapes") ----
+// Facts of a launch that are the same for every lane of every wave: how many lights, whether shadow rays are cast, how long the
+// straight-line pow is, how wide a GI mask is.  Read from RenderParams / SceneView each of them holds a scalar register from the kernel's
+// entry to its last use — the leaf kernel has more of those than registers, and a spilled one comes back through v_readlane_b32, a VALU
+// slot — and costs the wave-uniform branch or loop counter that depends on it.  As constants of a type passed down the shading and
+// tracing call tree as a template argument (as SS / TS of direct_light_of are) they cost neither.  RunTimeShape reads every fact where it
+// was always read: the code of an instance on it is the code it had without the parameter.  The launcher picks a fixed shape only for a
+// launch whose every fact equals the constant (launch.h skr_leaf_shape).
+} // namespace
+// (types with external linkage: a kernel instance names its shape)
+struct RunTimeShape {
+	static constexpr int lights = 0;             // 0: sv.nl lights of any kind
+	static constexpr bool point_lights = false;  // true: no directional light (light_term)
+	static constexpr bool shadows = false;       // true: p.use_shadows != 0
+	static constexpr bool masks = false;         // true: the launch has shadow masks (sv.smask != null)
+	static constexpr bool pow7 = false;          // true: p.pow_steps <= 7
+	static constexpr bool gi_narrow = false;     // true: p.gi_wide == 0 (16-bit GI masks: at most 16 spheres)
+};
+// A sphere-only scene of LIGHTS (1 or 2) point lights with its shadow masks, shadows on, integer Phong exponents below 128 and at most
+// 16 spheres.
+template <int LIGHTS>
+struct PointLightShape {
+	static constexpr int lights = LIGHTS;
+	static constexpr bool point_lights = true, shadows = true, masks = true, pow7 = true, gi_narrow = true;
+};
+namespace {
+
 // One aligned 16-byte row of a table that no kernel writes, at a wave-uniform index, through the constant address space: that is what
 // makes the compiler take the scalar path (s_load_dwordx4 into SGPRs) — through a plain pointer it cannot prove that no store of the
 // kernel aliases the row and issues a vector load with a uniform address.
@@ -420,6 +448,7 @@ SKR_DEV int gi_surface_row(const RenderParams &p, const SceneView &sv, int s, f3
 }
 // The union of the masks of children d0 and (second) d1 from origin row `row`; every sphere where the row is -1 or a direction is not a
 // vector of moderate length (zero, tiny, huge, NaN, inf: the margins are derived for |d|^2 in [2^-40, 2^40]).
+template <typename SH = RunTimeShape>
 SKR_DEV uint32_t gi_cands(const RenderParams &p, int row, f3 d0, f3 d1, bool second)
 {
 	const float a0 = sqr3(d0), a1 = sqr3(d1);
@@ -429,8 +458,9 @@ SKR_DEV uint32_t gi_cands(const RenderParams &p, int row, f3 d0, f3 d1, bool sec
 	const uint32_t e0 = base + (uint32_t) ((c0.face * SKR_GI_DIR_CELLS + c0.i) * SKR_GI_DIR_CELLS + c0.j);
 	const uint32_t e1 = base + (uint32_t) ((c1.face * SKR_GI_DIR_CELLS + c1.i) * SKR_GI_DIR_CELLS + c1.j);
 	const uint16_t *m16 = reinterpret_cast<const uint16_t *>(p.gi_masks);
-	uint32_t m = p.gi_wide ? p.gi_masks[e0] : (uint32_t) m16[e0];
-	if(second) m |= p.gi_wide ? p.gi_masks[e1] : (uint32_t) m16[e1]; // (no second child: no second load)
+	const bool wide = !SH::gi_narrow && p.gi_wide;
+	uint32_t m = wide ? p.gi_masks[e0] : (uint32_t) m16[e0];
+	if(second) m |= wide ? p.gi_masks[e1] : (uint32_t) m16[e1]; // (no second child: no second load)
 	return ok ? m : p.gi_all;
 }
 
@@ -446,7 +476,7 @@ SKR_DEV uint32_t gi_cands(const RenderParams &p, int row, f3 d0, f3 d1, bool sec
 // With shadow masks (the level pipelines, !COHERENT): `cand` = the union of the lane's two masks (shadow_mask_of).  A sphere outside a
 // ray's mask provably fails pair_any_step's candidate test (its D < 0), so each lane walks only its own candidates, lowest index first: the first
 // occluder it finds is the one the loop over every sphere finds, and every decision and count is the same.
-template <bool COHERENT>
+template <bool COHERENT, typename SH = RunTimeShape>
 SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second, bool &occ0, bool &occ1, uint32_t &tests, uint32_t cand = 0u)
 {
 	const f3 o = add_scalar(P, 0.000001f);
@@ -456,7 +486,7 @@ SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second,
 	occ1 = !second;
 	auto test = [&](const float4 g, int i) { pair_any_step(rp, pa, o, g, i, occ0, occ1, tests); };
 	if(COHERENT) table_rows<SKR_COHERENT_TRIP>(sv.geom_u, sv.ns, test, [&] { return !__all(occ0 && occ1); }); // (the wave-wide exit, once per trip)
-	else if(sv.smask)
+	else if(SH::masks || sv.smask)
 	{
 		diag_mask_gate(19, cand, sv.ns);
 		masked_rows(sv, cand, test);
@@ -473,10 +503,10 @@ SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second,
 // within the sphere's radial slack, the mask is the one word of e's patch in the pair's table: one cell, one gather, and the spheres
 // behind P or under it are not named.  Everywhere else (NaN, a point off its sphere, no patches) the two direction masks, unchanged.
 // The index is in bounds whatever P holds.
-template <bool COHERENT>
+template <bool COHERENT, typename SH = RunTimeShape>
 SKR_DEV uint32_t shadow_cands(const SceneView &sv, const RenderParams &p, int i, bool second, f3 P, int sph = -1)
 {
-	if(COHERENT || !sv.smask || !p.use_shadows) return 0u;
+	if(COHERENT || !(SH::masks || sv.smask) || !(SH::shadows || p.use_shadows)) return 0u;
 	if(p.shadow_surface_word != 0u && (uint32_t) sph < (uint32_t) sv.ns)
 	{
 		const float4 g = sv.geom[sph];
@@ -491,6 +521,13 @@ SKR_DEV uint32_t shadow_cands(const SceneView &sv, const RenderParams &p, int i,
 	}
 	const uint32_t m0 = shadow_mask_of(sv, i, ld3(sv.lights[2 * i]) - P);
 	return second ? m0 | shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P) : m0;
+}
+// (the facts of a shape that fixes them; else what the launch says)
+template <typename SH>
+SKR_DEV int shape_lights(const SceneView &sv)
+{
+	if constexpr(SH::lights > 0) return SH::lights;
+	else return sv.nl;
 }
 
 // ---- the sphere tree (include/skr.h skr_scene_set_sphere_tree; scene_host.cpp skr_build_sphere_tree) ----
@@ -705,12 +742,13 @@ struct LightTerm { // the per-light quantities of blinn_phong.h:67-72 / :100-117
 	float intensity; // 1 / powf(|Lp - P|, 2) (== 1 / (d * d): SURVEY.md 8c); exactly 1 for a directional light
 };
 
+template <typename SH = RunTimeShape>
 SKR_DEV LightTerm light_term(const SceneView &sv, int i, f3 P)
 {
 	LightTerm t;
 	const float4 lp4 = sv.lights[2 * i];
 	t.lc = ld3(sv.lights[2 * i + 1]);
-	if(lp4.w != 0.0f)
+	if(!SH::point_lights && lp4.w != 0.0f)
 	{ // a directional light (--strict-scn only; blinn_phong.h:81-82,126-128): L = normalize(direction) and no 1/d^2 — the intensity
 	  // factor of the point-light expression is exactly 1, and x * 1 == x
 		t.L = normalize3(ld3(lp4));
@@ -743,22 +781,24 @@ struct SphereLoopShadows {
 // TS: triangle shadows (include/skr.h skr_scene_set_triangle_shadows) — `tri_shadows(P, i, second, L0, L1, occ0, occ1)` darkens the lights of a
 // pair that the spheres left lit and a triangle occludes (render_generic.hip TriangleShadows); chosen at compile time, so that the
 // instances without it keep their code.
-template <bool COHERENT, typename TS = NoTriangleShadows, typename SS = SphereLoopShadows>
+// SH: the facts of the launch that are compiled in (RunTimeShape: none).
+template <bool COHERENT, typename TS = NoTriangleShadows, typename SS = SphereLoopShadows, typename SH = RunTimeShape>
 SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3 ks, float4 ambp, f3 P, f3 N, Counters &cn, const TS &tri_shadows = TS(),
 						   const SS &sphere_shadows = SS(), int sph = -1)
 {
 	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
 	const f3 view = normalize3(p.cam_pos - P); // always the camera (blinn_phong.h:93)
-	for(int i = 0; i < sv.nl; i += 2)
+	const int nl = shape_lights<SH>(sv);
+	for(int i = 0; i < nl; i += 2)
 	{
-		const bool second = i + 1 < sv.nl;
-		const uint32_t cand = SS::loops ? shadow_cands<COHERENT>(sv, p, i, second, P, sph) : 0u; // (asked for ahead of the light terms)
-		const LightTerm t0 = light_term(sv, i, P), t1 = light_term(sv, second ? i + 1 : i, P);
+		const bool second = i + 1 < nl;
+		const uint32_t cand = SS::loops ? shadow_cands<COHERENT, SH>(sv, p, i, second, P, sph) : 0u; // (asked for ahead of the light terms)
+		const LightTerm t0 = light_term<SH>(sv, i, P), t1 = light_term<SH>(sv, second ? i + 1 : i, P);
 		bool occ0 = false, occ1 = false;
-		if(p.use_shadows)
+		if(SH::shadows || p.use_shadows)
 		{
 			cn.shadow_rays += second ? 2u : 1u;
-			if constexpr(SS::loops) occluded_pair<COHERENT>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
+			if constexpr(SS::loops) occluded_pair<COHERENT, SH>(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests, cand);
 			else sphere_shadows.pair(sv, P, t0.L, t1.L, second, occ0, occ1, cn.shadow_tests);
 			if constexpr(TS::on) tri_shadows(P, i, second, t0.L, t1.L, occ0, occ1);
 		}
@@ -769,7 +809,7 @@ SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3
 				diffuse = diffuse + ((kd * t.lc) * t.intensity) * max0(dot3(N, t.L));
 				const f3 vl = view + t.L;
 				const f3 H = vl / length3(vl);
-				specular = specular + ((ks * t.lc) * t.intensity) * powf_spec(max0(dot3(N, H)), ambp.w, p.pow_steps);
+				specular = specular + ((ks * t.lc) * t.intensity) * powf_spec<SH::pow7>(max0(dot3(N, H)), ambp.w, p.pow_steps);
 			}
 		};
 		add_light(t0, !occ0);
@@ -929,10 +969,10 @@ SKR_DEV f3 direct_light_cone(const SceneView &sv, const RenderParams &p, const S
 	return light_sum(ambp, diffuse, specular);
 }
 
-template <bool COHERENT>
+template <bool COHERENT, typename SH = RunTimeShape>
 SKR_DEV f3 direct_light(const SceneView &sv, const RenderParams &p, int sph, f3 P, f3 N, Counters &cn)
 {
-	return direct_light_of<COHERENT>(sv, p, ld3(sv.kd[sph]), ld3(sv.ks[sph]), sv.amb[sph], P, N, cn, NoTriangleShadows(), SphereLoopShadows(), sph);
+	return direct_light_of<COHERENT, NoTriangleShadows, SphereLoopShadows, SH>(sv, p, ld3(sv.kd[sph]), ld3(sv.ks[sph]), sv.amb[sph], P, N, cn, NoTriangleShadows(), SphereLoopShadows(), sph);
 }
 
 // ---- --scn-fog (DESIGN.md "Spherical fog"; general level pipeline only): blinn_phong.h:19-43 as written, rand() replaced ----

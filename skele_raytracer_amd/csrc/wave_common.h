@@ -67,11 +67,11 @@ SKR_DEV void closest_pair_deferred(const SceneView &sv, f3 o, f3 d0, f3 d1, bool
 
 
 // GIM: the kernel runs with GI masks (p.gi_index set; the launcher picks it); `row` = the lane's origin row (shade_common.h
-// gi_origin_row), -1 = none
-template <bool GIM>
+// gi_origin_row), -1 = none; SH: the facts of the launch that are compiled in (shade_common.h RunTimeShape: none)
+template <bool GIM, typename SH = RunTimeShape>
 SKR_DEV void closest_pair(const SceneView &sv, const RenderParams &p, int row, f3 o, f3 d0, f3 d1, bool second, const RayPair &rp, BestState &s0, BestState &s1)
 {
-	const uint32_t cand = GIM ? gi_cands(p, row, d0, d1, second) : 0u;
+	const uint32_t cand = GIM ? gi_cands<SH>(p, row, d0, d1, second) : 0u;
 	closest_pair_deferred<GIM>(sv, o, d0, d1, second, rp, s0, s1, cand, p.gi_all);
 }
 
