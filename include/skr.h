@@ -33,6 +33,7 @@ extern "C" {
 #define SKR_HAS_ADAPTIVE_DENOISE 1 /* skr_render_adaptive_var, skr_denoise_var, skr_render_adaptive_denoised_host: additions, likewise */
 #define SKR_HAS_SPOT_LIGHTS 1 /* SKR_SCN_SPOT, skr_scene_get/set_spot_lights, skr_scene_get_spot_cones, skr_debug_eval op 17: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_SOFT_LIGHTS 1 /* skr_scene_set/get_light_radii, skr_debug_eval op 18: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_ROOT_PAIRS 1 /* skr_debug_eval op 19: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -691,7 +692,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  * 17 the spot-light cone (SKR_SCN_SPOT above; shade_common.h spot_cone, the function the light loop calls): (a(3), c1, c2, L(3))
  *    -> {f, outside}: f as a float (0 where outside), outside 0 / 1.  (Ops 12..16 were taken when spot lights came.)
  * 18 the sample of a light with a radius (skr_scene_set_light_radii above; shade_common.h soft_sample, the function the light loop calls):
- *    (pixel, aa, node, l, seed_lo, seed_hi, Lp(3), R), 10 words -> Lp'(3).  R == 0: Lp itself. */
+ *    (pixel, aa, node, l, seed_lo, seed_hi, Lp(3), R), 10 words -> Lp'(3).  R == 0: Lp itself.
+ * 19 the hit root (device_math.h near_root, the function the kernels take a hit's t from): (2a, b, D) -> 7 words: near_root, near_root_exact (the
+ *    binary64 form of utils.h:87-110), 1 where near_root took the binary64 form (else 0), then the interval lo, hi and the pair q_h, q_l
+ *    of the binary32 form (meaningful only where the operands are in its ranges; word 2 is 1 for every record outside them). */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

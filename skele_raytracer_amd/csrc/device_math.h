@@ -18,7 +18,8 @@
 // Diagnostic build only (-DSKR_DIAG=1): event counts, 64 shards per counter (tools/diag_counts.py).  Compiles to nothing otherwise.
 // (Not together with timing: every event is a global atomic.)
 #if defined(SKR_DIAG) && SKR_DIAG
-static __device__ unsigned long long skr_diag[32 * 64];
+#define SKR_DIAG_SLOTS 36
+static __device__ unsigned long long skr_diag[SKR_DIAG_SLOTS * 64];
 #define DIAG_WAVE(i, v) do { const unsigned long long dv_ = (unsigned long long) (v); const unsigned long long dm_ = __ballot(true); if(__builtin_amdgcn_mbcnt_hi((uint32_t) (dm_ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) dm_, 0u)) == 0) atomicAdd(&skr_diag[(i) * 64 + (blockIdx.x & 63)], dv_); } while(0)
 #define DIAG_LANES(i) do { const unsigned long long dl_ = __ballot(true); DIAG_WAVE(i, __popcll(dl_)); } while(0)
 #else
@@ -426,6 +427,67 @@ SKR_DEV float near_root_exact(float two_a, float b, float D)
 	const float t2 = (float) q;
 	return (t2 >= 0.0f) ? t2 : __builtin_inff();
 }
+// The same behind a call, for the sites that reach it only where binary32 could not decide (as powf_spec_cold is)
+#ifndef SKR_COLD_ROOT
+#define SKR_COLD_ROOT 1 // 1: those sites call; 0: they expand it inline, 24 copies in the headline leaf instance (A/B builds, tools/experiments/README.md)
+#endif
+static __device__ __attribute__((noinline)) float near_root_cold(float two_a, float b, float D) { return near_root_exact(two_a, b, D); }
+SKR_DEV float near_root_fallback(float two_a, float b, float D)
+{
+#if SKR_COLD_ROOT
+	return near_root_cold(two_a, b, D);
+#else
+	return near_root_exact(two_a, b, D);
+#endif
+}
+
+// The binary64 pipeline above is 31 binary64 instructions (v_rsq_f64, v_rcp_f64, their Newton steps, v_div_*_f64) at 3.2 cycles of
+// issue each (profiles/r03_issue_rates_ubench.txt).  The same float from binary32 pairs (DESIGN.md "Filtered predicates", "The root
+// from binary32 pairs"): the root of D, the numerator -b - sqrt(D) and the quotient are each carried as a high part and a low part that
+// holds what the high part's rounding lost, which leaves q_h + q_l within 2.4 * 2^-45 (s + |n_h|) / 2a of the binary64 pipeline's
+// quotient.  With E = (s + |n_h|) / 2a * 2^-41 (a factor 6.7 to spare) that quotient lies in [q_h + (q_l - E), q_h + (q_l + E)], and
+// rounding to nearest is monotone: where both ends round to one float, that float is what the pipeline's quotient rounds to.
+// Anything else — the ends differ (1e-4 of the headline's roots), an operand outside the ranges the bound is derived for, -b < s
+// (the origin inside the sphere), NaN — takes the binary64 form.  SKR_ROOT_PAIRS=0: the binary64 form everywhere (A/B builds).
+#ifndef SKR_ROOT_PAIRS
+#define SKR_ROOT_PAIRS 1
+#endif
+struct RootPair { float lo, hi, q_h, q_l; }; // (q_h, q_l: for debug op 19)
+// false: an operand is outside 2^-40 <= 2a < 2^40, 2^-60 <= D < 2^60, s <= -b < 2^40 (every comparison false for a NaN)
+SKR_DEV bool near_root_pair(float two_a, float b, float D, RootPair &r)
+{
+	const bool in_range = (__float_as_uint(two_a) - (87u << 23) < (80u << 23)) && (__float_as_uint(D) - (67u << 23) < (120u << 23));
+	const float y = __builtin_amdgcn_rsqf(D);
+	const float s0 = D * y, h = 0.5f * y;
+	const float s = __builtin_fmaf(__builtin_fmaf(-s0, s0, D), h, s0); // sk_sqrtf's short form: RN(sqrt(D)) on this range
+	const float s_l = __builtin_fmaf(-s, s, D) * h;                    // sqrt(D) - s to 2^-22 of itself: the residual is exact
+	const float nb = -b;
+	const float n_h = nb - s;
+	const float n_l = ((nb - n_h) - s) - s_l;                          // fast two-sum (nb >= s): nb - s = n_h + ((nb - n_h) - s) exactly
+	const float y2 = __builtin_amdgcn_rcpf(two_a);
+	const float inv = __builtin_fmaf(__builtin_fmaf(-two_a, y2, 1.0f), y2, y2); // sk_rcpf's short form
+	r.q_h = n_h * inv;
+	r.q_l = (__builtin_fmaf(-r.q_h, two_a, n_h) + n_l) * inv;
+	const float E = (s + __builtin_fabsf(n_h)) * (inv * 0x1p-41f);
+	r.lo = r.q_h + (r.q_l - E);
+	r.hi = r.q_h + (r.q_l + E);
+	return in_range && (nb >= s) && (nb < 0x1p40f);
+}
+// near_root_exact's float wherever a caller wants the VALUE of the root (the hit point, the winner of a selection)
+SKR_DEV float near_root(float two_a, float b, float D)
+{
+#if SKR_FAST_EXACT && SKR_ROOT_PAIRS
+	RootPair r;
+	DIAG_LANES(32); // slots 32..35 of tools/diag_counts.py: roots asked for, roots the binary64 form gave, as lanes and as wave events
+	DIAG_WAVE(34, 1);
+	if(__builtin_expect(near_root_pair(two_a, b, D, r) && r.lo == r.hi, 1)) return r.lo;
+	DIAG_LANES(33);
+	DIAG_WAVE(35, 1);
+	return near_root_fallback(two_a, b, D);
+#else
+	return near_root_exact(two_a, b, D);
+#endif
+}
 
 // utils.h:87 + :113 for one sphere.  two_a = 2*a, four_a = 4*a are per-ray
 // invariants (exact doublings of a = dot(d,d)).
@@ -436,7 +498,7 @@ SKR_DEV float sphere_distance(f3 o, f3 d, float two_a, float four_a, float4 sph)
 	const float c = dot3(e, e) - sph.w; // sph.w = radius*radius
 	const float D = b * b - four_a * c;
 	if(D < 0) return __builtin_inff();
-	return near_root_exact(two_a, b, D);
+	return near_root(two_a, b, D);
 }
 
 // utils.h:169-179
@@ -489,14 +551,14 @@ SKR_DEV bool bracket_decide(bool sane, float two_a, float b, float D, float &lo,
 	{ // too close to call in binary32: the exact form decides
 		DIAG_WAVE(7, 1);
 		DIAG_LANES(3);
-		const float t = near_root_exact(two_a, b, D);
+		const float t = near_root_fallback(two_a, b, D);
 		if(!accept_distance(t)) return false;
 		lo = hi = t;
 	}
 	return true;
 }
 // The exact t2 of an accepted bracket, from the b, D kept with it: already there where the exact form decided.
-SKR_DEV float bracket_t(float two_a, float lo, float hi, float b, float D) { return (lo == hi) ? lo : near_root_exact(two_a, b, D); }
+SKR_DEV float bracket_t(float two_a, float lo, float hi, float b, float D) { return (lo == hi) ? lo : near_root(two_a, b, D); }
 
 // One sphere against one ray.  Returns false for a certain miss.  Otherwise
 // [lo, hi] brackets t2 (lo == hi when it had to be resolved exactly) and b, D
@@ -654,7 +716,7 @@ SKR_DEV bool any_decide(bool sane, float two_a, float quarter, float b, float D,
 	if(normal && ((m <= 0.0f) || (rej_lhs < D))) return false;
 	if(normal && (m > quarter) && (acc_lhs > D)) return true;
 	DIAG_WAVE(7, 1);
-	return accept_distance(near_root_exact(two_a, b, D));
+	return accept_distance(near_root_fallback(two_a, b, D));
 }
 SKR_DEV PairAny make_pair_any(const RayPair &rp) { return PairAny{rp.two_a, rp.two_a * 0.25f, rp.sane0, rp.sane1}; }
 // The any-hit step of one sphere row g (index i) for both shadow rays from o: the whole per-sphere body of occluded_pair.  A ray that

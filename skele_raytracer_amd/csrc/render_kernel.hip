@@ -109,7 +109,7 @@ hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStr
 // ------------------------------------------------------------ debug eval ----
 // Device-side evaluation of the arithmetic spec, one record per thread
 // (skr_debug_eval in include/skr.h).
-// Op 18: the sample of a light with a radius.  Op 17: the spot-light cone.  Ops 12..16 (include/skr.h): the filtered predicates of device_math.h and the selection code on top of them, through the functions the
+// Op 19: the hit root from binary32 pairs.  Op 18: the sample of a light with a radius.  Op 17: the spot-light cone.  Ops 12..16 (include/skr.h): the filtered predicates of device_math.h and the selection code on top of them, through the functions the
 // render kernels call.  `i` = the lane's record, `live` = it may write.
 #define SKR_DEBUG_TABLE_ROWS 80u // ops 15, 16: rows of the sphere table in the input (<= 64 spheres, the pad row, the rows table_rows asks for behind it)
 #define SKR_DEBUG_EC_PAD 8u      // ops 15, 16: rows behind the ns rows of a record's ec table
@@ -245,6 +245,19 @@ SKR_DEV void skr_debug_predicates(int op, const uint32_t *in, uint32_t *out, uin
 				out[3 * i] = U(s.x);
 				out[3 * i + 1] = U(s.y);
 				out[3 * i + 2] = U(s.z);
+			}
+			break;
+		}
+		case 19: { // the root from binary32 pairs against the binary64 form: near_root, near_root_exact and the interval near_root decides on
+			const uint32_t *r = in + 3 * i;
+			const float two_a = F(r[0]), b = F(r[1]), D = F(r[2]);
+			RootPair q{};
+			const bool short_form = SKR_FAST_EXACT && SKR_ROOT_PAIRS && near_root_pair(two_a, b, D, q) && q.lo == q.hi;
+			if(live)
+			{
+				uint32_t *w = out + 7 * i;
+				w[0] = U(near_root(two_a, b, D)); w[1] = U(near_root_exact(two_a, b, D)); w[2] = short_form ? 0u : 1u;
+				w[3] = U(q.lo); w[4] = U(q.hi); w[5] = U(q.q_h); w[6] = U(q.q_l);
 			}
 			break;
 		}

@@ -75,7 +75,7 @@ SKR_DEV bool classify_child(const SceneView &sv, f3 co, f3 d, float two_a, float
 	black = false;
 	if(sv.nt > 0)
 	{ // the triangle walk needs the sphere's exact t to compare against
-		const float tmin = (s.best >= 0) ? near_root_exact(two_a, s.b, s.D) : __builtin_inff();
+		const float tmin = (s.best >= 0) ? near_root(two_a, s.b, s.D) : __builtin_inff();
 		black = any_triangle_closer(sv, RayConst{co, d, two_a, four_a}, tmin);
 	}
 	return !black && s.best >= 0;
@@ -234,7 +234,7 @@ SKR_DEV Activated activate_record(const SceneView &sv, const RenderParams &p, bo
 		const float b = 2 * dot3(d, ec);
 		const float D = b * b - (4 * aa) * (dot3(ec, ec) - g.w);
 		const float two_a = 2 * aa;
-		const float t = near_root_exact(two_a, b, D);
+		const float t = near_root(two_a, b, D);
 		const f3 P = co0 + d * t;
 		a.N = normalize3(P - ld3(sv.geom[a.sph]));
 		cn.hits++;
@@ -375,7 +375,7 @@ SKR_DEV void leaf_batch(const SceneView &sv, const RenderParams &p, Ring &q, flo
 		const float b = 2 * dot3(d, ec);
 		const float D = b * b - (4 * a) * (dot3(ec, ec) - g.w);
 		const float two_a = 2 * a;
-		const float t = near_root_exact(two_a, b, D);
+		const float t = near_root(two_a, b, D);
 		const f3 P = co_k + d * t;
 		const f3 Nn = normalize3(P - ld3(sv.geom[sph]));
 		cn.hits++;
@@ -409,11 +409,11 @@ struct ShapeOf<S> {
 
 #if defined(SKR_DIAG) && SKR_DIAG
 extern "C" void skr_diag_read_nodes(unsigned long long *out, int reset)
-{ // this translation unit's copy of the 32 event counters (device_math.h), summed over their 64 shards
-	unsigned long long h[32 * 64];
+{ // this translation unit's copy of the SKR_DIAG_SLOTS event counters (device_math.h), summed over their 64 shards
+	unsigned long long h[SKR_DIAG_SLOTS * 64];
 	(void) hipDeviceSynchronize();
 	(void) hipMemcpyFromSymbol(h, HIP_SYMBOL(skr_diag), sizeof(h));
-	for(int i = 0; i < 32; i++)
+	for(int i = 0; i < SKR_DIAG_SLOTS; i++)
 	{
 		out[i] = 0;
 		for(int k = 0; k < 64; k++) out[i] += h[i * 64 + k];
