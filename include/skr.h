@@ -695,7 +695,12 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  *    (pixel, aa, node, l, seed_lo, seed_hi, Lp(3), R), 10 words -> Lp'(3).  R == 0: Lp itself.
  * 19 the hit root (device_math.h near_root, the function the kernels take a hit's t from): (2a, b, D) -> 7 words: near_root, near_root_exact (the
  *    binary64 form of utils.h:87-110), 1 where near_root took the binary64 form (else 0), then the interval lo, hi and the pair q_h, q_l
- *    of the binary32 form (meaningful only where the operands are in its ranges; word 2 is 1 for every record outside them). */
+ *    of the binary32 form (meaningful only where the operands are in its ranges; word 2 is 1 for every record outside them).
+ * 20 the Phong power as the kernels call it (device_math.h powf_spec, tests/test_shading_values_gpu.py): (x, p, steps as an integer)
+ *    -> {powf_spec<false>(x, p, steps), powf_spec<true>(x, p, steps)}: the instance that reads RenderParams::pow_steps and the one
+ *    the shaped leaf instances compile in, which is right only for integer p <= 127 (op 2 is the first at steps = 11).
+ * 21 (hi16 -> mismatch counts of len_terms<true>'s len, inv, inv2 and len_terms<false>'s inv against sqrtf(ss), 1.0f / len and
+ *    1.0f / (len * len) in the correctly rounded expansions, over the 65536 binary32 values with those high 16 bits; as op 9). */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

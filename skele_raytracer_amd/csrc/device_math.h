@@ -410,7 +410,11 @@ SKR_DEV float powf_spec(float x, float p, int steps)
 	const bool plain = (p >= 1.0f) && (p <= 1024.0f) && (p == __builtin_rintf(p)) && (x >= 0.0f);
 	if(__builtin_expect(!plain, 0)) return powf_spec_cold(x, p);
 	// (`steps` is wave-uniform: one scalar branch picks the unrolled length — exponents below 128 in every shipped scene)
-	return (LE7 || steps <= 7) ? pow_int_flat<7>(x, (unsigned) p) : pow_int_flat<11>(x, (unsigned) p);
+	// |x|: x = -0 is plain too, and the spec's odd powers of it are +0 where the products' would be -0.  The shading code passes
+	// max0(...), never -0, and the render kernels compile to the instructions they had without it: `make asm` before and after, compared
+	// with tools/asm_kernel_diff.py, differs in skr_debug_kernel alone (ops 2 and 20 take any x).
+	const float ax = __builtin_fabsf(x);
+	return (LE7 || steps <= 7) ? pow_int_flat<7>(ax, (unsigned) p) : pow_int_flat<11>(ax, (unsigned) p);
 #else
 	return powf_spec_cold(x, p);
 #endif

@@ -270,7 +270,7 @@ __global__ void skr_debug_kernel(int op, const uint32_t *in, uint32_t *out, uint
 	uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	auto F = [](uint32_t u) { return __uint_as_float(u); };
 	auto U = [](float f) { return __float_as_uint(f); };
-	if(op >= 12)
+	if(op >= 12 && op <= 19)
 	{ // the predicate ops run whole waves (occluded_pair<true> and table_rows vote wave-wide): a lane past the end evaluates the last record and writes nothing
 		const bool live = i < n;
 		if(!live) i = n - 1u;
@@ -365,6 +365,30 @@ __global__ void skr_debug_kernel(int op, const uint32_t *in, uint32_t *out, uint
 			float pni = 0.0f;
 			const f3 c = fog_term(a, alb, t, v3(16), v3(20), v3(24), v3(28), ctr, r[33], r[34], &pni);
 			out[4 * i] = U(c.x); out[4 * i + 1] = U(c.y); out[4 * i + 2] = U(c.z); out[4 * i + 3] = U(pni);
+			break;
+		}
+		case 20: { // powf_spec as the render kernels call it: (x, p, steps) -> {the instance that reads steps, the LE7 instance of the shaped leaf kernels}
+			const float x = F(in[3 * i]), p = F(in[3 * i + 1]);
+			const int steps = (int) in[3 * i + 2];
+			out[2 * i] = U(powf_spec<false>(x, p, steps));
+			out[2 * i + 1] = U(powf_spec<true>(x, p, steps));
+			break;
+		}
+		case 21: { // EXHAUSTIVE check of len_terms (device_math.h) against the correctly rounded expansions, in the shape of op 9: record i
+		           // covers the 65536 bit patterns in[i] << 16 ...; out = mismatches of {len_terms<true>.len, .inv, .inv2, len_terms<false>.inv}
+			uint32_t bad[4] = {0, 0, 0, 0};
+			auto same = [](float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); };
+			for(uint32_t k = 0; k < 65536u; k++)
+			{
+				const float ss = F((in[i] << 16) | k);
+				const LenTerms t = len_terms<true>(ss), u = len_terms<false>(ss);
+				const float len = __builtin_sqrtf(ss);
+				bad[0] += !same(t.len, len);
+				bad[1] += !same(t.inv, 1.0f / len);
+				bad[2] += !same(t.inv2, 1.0f / (len * len));
+				bad[3] += !same(u.inv, 1.0f / len);
+			}
+			for(int k = 0; k < 4; k++) out[4 * i + k] = bad[k];
 			break;
 		}
 		default: break;
