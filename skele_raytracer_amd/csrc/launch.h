@@ -145,6 +145,32 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 	return lo;
 }
 
+// ---- the node pipeline's trace waves, their headers and their hit regions (render_nodes.hip) ----
+// SKR_TRACE_BY_NODE 1: a trace wave holds a block of 64 consecutive nodes, one per lane, and runs over sibling pairs j; its header for
+// pair j is row (node >> 6) * PP + j and a node's bit in the ballots is node & 63.  0 (A/B builds): a lane is one sibling pair
+// tp = node * PP + j, a wave 64 consecutive pairs: row tp >> 6, bit tp & 63.  Either way a row's wave appends at most 128 hits, to
+// region row & 63.  The kernels, the plan and the tests (api.cpp skr_trace_header_map) all ask these functions.
+#ifndef SKR_TRACE_BY_NODE
+#define SKR_TRACE_BY_NODE 1
+#endif
+#ifndef SKR_TRACE_RUN
+#define SKR_TRACE_RUN 2 // sibling pairs a trace wave runs over before it takes its next block of nodes (0 = all PP of them); measured at PP, 4 and 2: DESIGN.md 5.2
+#endif
+__host__ __device__ static inline uint64_t skr_trace_header_row(uint64_t node, uint32_t j, uint32_t PP)
+{
+	return SKR_TRACE_BY_NODE ? (node >> 6) * PP + j : (node * PP + j) >> 6;
+}
+__host__ __device__ static inline uint32_t skr_trace_header_bit(uint64_t node, uint32_t j, uint32_t PP)
+{
+	return (uint32_t) (SKR_TRACE_BY_NODE ? node : node * PP + j) & 63u;
+}
+// the header rows that `nodes` nodes of PP sibling pairs use: rows 0 .. this - 1
+static inline uint64_t skr_trace_rows_used(uint64_t nodes, uint64_t PP) { return SKR_TRACE_BY_NODE ? (nodes + 63) / 64 * PP : (nodes * PP + 63) / 64; }
+// the rows their table holds (4 more: the old mapping's last workgroup writes the headers of all its four waves)
+static inline uint64_t skr_trace_rows_alloc(uint64_t nodes, uint64_t PP) { return skr_trace_rows_used(nodes, PP) + 4; }
+// records per region: region r receives the hits of the rows = r (mod 64), 128 at most from each
+static inline uint64_t skr_trace_region_cap(uint64_t nodes, uint64_t PP) { return (skr_trace_rows_used(nodes, PP) + SKR_P1_REGIONS - 1) / SKR_P1_REGIONS * 128; }
+
 // The launch shape the leaf kernel (render_nodes.hip skr_leaf_kernel2) has an instance for (shade_common.h PointLightShape<1 | 2>), or
 // none: the instance that reads every fact at run time.  A shape is picked only where EVERY fact it compiles in equals the launch's value:
 // a sphere-only scene with GI masks (the instances are <false, FIRST, true, shape>) of 16-bit entries (at most 16 spheres), shadow rays

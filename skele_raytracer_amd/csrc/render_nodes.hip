@@ -6,12 +6,14 @@
 //
 //   skr_primary_kernel   (render_wave.hip) primary rays + direct light; every sphere hit becomes a level-0 node (a 32-byte geometry
 //                        row for the kernels that trace its children, a 32-byte shading row for the one that sums them)
-//   skr_trace_kernel     one lane per sibling pair of a node: traces the two child rays (one Philox call, one (e, c)
-//                        per sphere for both); per wave (64 pairs) one 48-byte header — the first record of its hits and the
-//                        ballots of the children that hit: finalize finds a child's record from the population count of the
-//                        ballot below its pair, and draws r1 of a miss again from the same Philox counter — and per sphere
-//                        hit a 16-byte record (parent, sphere, child, the two draws) appended to one of 64 regions (ballot
-//                        ranks + one atomic per wave).  The grid is capped; a workgroup strides over the blocks of 256 pairs.
+//   skr_trace_kernel     one lane per node, a wave per block of 64 consecutive nodes: what belongs to the node (row, tangent, row
+//                        of GI masks) is formed once, then for a run of sibling pairs j the lane traces the two child rays (one
+//                        Philox call, one (e, c) per sphere for both); per wave and round one 48-byte header — the first record
+//                        of its hits and the ballots of the nodes whose children hit: finalize finds a child's record from the
+//                        population count of the ballot below its node, and draws r1 of a miss again from the same Philox
+//                        counter — and per sphere hit a 16-byte record (parent, sphere, child, the two draws) appended to one
+//                        of 64 regions (ballot ranks + one atomic per wave).  The grid is
+//                        capped; a workgroup strides over the groups of four work items.
 //   skr_activate_kernel  (depth >= 4, and the flat schedule) one lane per record: shades the hit (:194-207) and writes it as a
 //                        node of the next level, which the trace kernel then expands; forms the level's prefix sums itself
 //   skr_leaf_kernel2     persistent waves, one unit = 64 records of the last-but-one level, ONE LANE PER RECORD: the 64
@@ -40,9 +42,10 @@
 
 namespace {
 
-// One header per trace wave (64 sibling pairs) tells finalize what became of their children: [0] = {first record of the wave's
-// hits, -, -, -}, [1] = the ballots of the even and the odd children that hit a sphere (2 x 64 bits: a child's record is the
-// base + the number of set bits below its pair, the odd children's records behind the even ones'), [2] (triangle scenes only) =
+// One header per trace wave and round (64 nodes, sibling pair j of each: launch.h skr_trace_header_row) tells finalize what became of
+// their children: [0] = {first record of the wave's hits, how many are even children's, -, -}, [1] = the ballots of the even and the
+// odd children that hit a sphere (2 x 64 bits: a child's record is the base + the number of set bits below its node's, the odd
+// children's records behind the even ones'), [2] (triangle scenes only) =
 // the ballots of the children a triangle took.  r1 of a miss comes from the same Philox call the trace made.
 constexpr uint32_t PC_HIT0 = 1u, PC_HIT1 = 2u, PC_BLACK0 = 4u, PC_BLACK1 = 8u; // (finalize's per-pair flags, formed from the ballots)
 constexpr int IXH_ROWS = 3; // uint4 per header
@@ -104,41 +107,20 @@ SKR_DEV bool classify_child(const SceneView &sv, f3 co, f3 d, float two_a, float
 #else
 #define SKR_TRACE_ATTR
 #endif
+// One round of a trace lane: children 2j, 2j + 1 of its node (origin co, normal Nn, tangent nt, bitangent nb) are traced, and the wave's
+// hits are appended to the region of its header row `chunk`, which then says what became of the 64 lanes' children.
 // GIM: GI masks (sphere-only scenes, p.gi_index set; wave_common.h closest_pair); the kernels without them are compiled without the walk
 template <bool TRIS, bool GIM>
-__global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams)
+SKR_DEV void trace_round(const SceneView &sv, const RenderParams &p, bool valid, uint32_t node, uint32_t j, f3 co, f3 Nn, f3 nt, f3 nb, uint32_t pixel,
+						 uint32_t node_id, int gi_row, uint32_t chunk, int lane, Counters &cn)
 {
-	extern __shared__ __align__(16) unsigned char lds_raw[];
-	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
-	const RenderParams &p = launch_args(); // (the kernel's entry; every block below names the constants anew)
-	const uint32_t N = (uint32_t) p.num_path_traces, PP = (N + 1u) >> 1; // children, sibling pairs per node
-	const uint64_t n_pairs = (uint64_t) *p.nd_count * PP;
-	if((uint64_t) blockIdx.x * 256u >= n_pairs) return; // (uniform per workgroup)
-	stage_scene(p, lds4, TRIS);
-	const int tid = threadIdx.x, lane = tid & 63;
-	Counters cn{0, 0, 0};
-	// (the grid is sized for the worst case — every ray of the level above a hit — and capped: a workgroup takes every
-	// gridDim.x-th block of 256 pairs, so a launch far below the worst case does not pay for its empty workgroups)
-	for(uint32_t blk = blockIdx.x; (uint64_t) blk * 256u < n_pairs; blk += SKR_TRACE_STRIDE)
-	{
-	const RenderParams &p = launch_args(); // (this block's constants and its view of the staged scene: no scalar lives across the loop)
-	const SceneView sv = scene_view(p, lds4, TRIS);
-	const uint32_t chunk = blk * 4u + (uint32_t) (tid >> 6);
-	const uint64_t tp = (uint64_t) chunk * 64u + (uint32_t) lane;
-	const bool valid = tp < n_pairs;
-	const uint32_t node = valid ? (uint32_t) (tp / PP) : 0u, j = valid ? (uint32_t) (tp - (uint64_t) node * PP) : 0u;
+	const uint32_t N = (uint32_t) p.num_path_traces;
 	const bool second = valid && 2u * j + 1u < N;
 	bool hit0 = false, hit1 = false;
 	float4 rec0 = make_float4(0, 0, 0, 0), rec1 = rec0;
 	bool black0 = false, black1 = false;
 	if(valid)
 	{
-		const float4 *row = p.nd_src + (size_t) node * 2;
-		const float4 a0 = row[0], a1 = row[1];
-		const f3 co = mk3(a0.x, a0.y, a0.z), Nn = mk3(a0.w, a1.x, a1.y);
-		const uint32_t pixel = __float_as_uint(a1.z), node_id = __float_as_uint(a1.w);
-		f3 nt, nb;
-		tangent_basis(Nn, nt, nb);
 		uint32_t rnd[4];
 		philox4x32(pixel, p.aa_index, node_id, j, p.seed_lo, p.seed_hi, rnd);
 		const float q1a = u31_to_unit(rnd[0]), q2a = u31_to_unit(rnd[1]), q1b = u31_to_unit(rnd[2]), q2b = u31_to_unit(rnd[3]);
@@ -147,11 +129,6 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 		cn.rays += second ? 2u : 1u;
 		const RayPair rp = make_pair(d0, d1);
 		BestState s0, s1;
-		// the node's row of GI masks: stored with a level-0 node of a kept stage (p.gi_row0, wave-uniform: the patch row of its sphere's
-		// surface where there is one); else the grids' row, looked up here (the surface patches, with the node's sphere from its shading
-		// row, made this kernel slower — DESIGN.md §5.8)
-		int gi_row = -1;
-		if(GIM) gi_row = p.gi_row0 ? p.gi_row0[node] : gi_origin_row(p, co);
 		closest_pair<GIM>(sv, p, gi_row, co, d0, d1, second, rp, s0, s1);
 		hit0 = classify_child(sv, co, d0, rp.two_a.x, rp.four_a.x, s0, black0);
 		rec0 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s0.best & 0xffff) | ((2u * j) << 16)), q1a, q2a);
@@ -185,9 +162,125 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 		p.ixh[IXH_ROWS * (size_t) chunk] = make_uint4(rec_base, n0h, 0u, 0u);
 		p.ixh[IXH_ROWS * (size_t) chunk + 1] = make_uint4((uint32_t) m0, (uint32_t) (m0 >> 32), (uint32_t) m1, (uint32_t) (m1 >> 32));
 	}
+}
+
+// sibling pairs per work item of the trace kernel, and items per block of 64 nodes (launch.h SKR_TRACE_RUN)
+__host__ __device__ static inline uint32_t trace_run(uint32_t PP) { return SKR_TRACE_RUN > 0 && (uint32_t) SKR_TRACE_RUN < PP ? (uint32_t) SKR_TRACE_RUN : PP; }
+__host__ __device__ static inline uint32_t trace_runs_per_block(uint32_t PP) { return (PP + trace_run(PP) - 1u) / trace_run(PP); }
+
+#if SKR_TRACE_BY_NODE
+// A work item is a block of 64 consecutive nodes, one per lane, and a run of their sibling pairs [j0, j1): what belongs to the node — its
+// row, its row of GI masks, its tangent (utils.h:148-163: a square root and three divisions on either arm) — is formed once per item, and
+// no lane divides a pair index by PP.  A workgroup takes every gridDim.x-th group of four items, a wave one of them.
+template <bool TRIS, bool GIM>
+__global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams)
+{
+	extern __shared__ __align__(16) unsigned char lds_raw[];
+	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
+	const RenderParams &p = launch_args(); // (the kernel's entry; every round below names the constants anew)
+	const uint32_t PP0 = ((uint32_t) p.num_path_traces + 1u) >> 1;
+	const uint32_t items = ((*p.nd_count + 63u) >> 6) * trace_runs_per_block(PP0); // (< 2^30: plan_for)
+	if((uint64_t) blockIdx.x * 4u >= items) return; // (uniform per workgroup)
+	stage_scene(p, lds4, TRIS);
+	const int tid = threadIdx.x, lane = tid & 63;
+	const uint32_t wave = (uint32_t) uni(tid >> 6);
+	Counters cn{0, 0, 0};
+	// (the grid is sized for the worst case — every ray of the level above a hit — and capped)
+	for(uint32_t blk = blockIdx.x; (uint64_t) blk * 4u < items; blk += SKR_TRACE_STRIDE)
+	{
+		const uint32_t item = blk * 4u + wave;
+		if(item >= items) break; // (wave-uniform; the loop holds no workgroup barrier)
+		// Across the rounds a lane carries its node's index, tangent and row of GI masks; the origin, the normal and the RNG key it reads
+		// again from the node's 32-byte row every round (cache-resident after the first): they would cost the kernel its sixth wave
+		uint32_t j0, j1, node;
+		bool valid;
+		f3 nt = mk3(0, 1, 0);
+		int gi_row = -1;
+		{
+			const RenderParams &p = launch_args();
+			const uint32_t PP = ((uint32_t) p.num_path_traces + 1u) >> 1, RPB = trace_runs_per_block(PP), RUN = trace_run(PP);
+			const uint32_t B = item / RPB;
+			j0 = (item - B * RPB) * RUN;
+			j1 = j0 + RUN < PP ? j0 + RUN : PP;
+			node = B * 64u + (uint32_t) lane;
+			valid = node < *p.nd_count;
+			if(valid)
+			{
+				const float4 *row = p.nd_src + (size_t) node * 2;
+				const float4 a0 = row[0], a1 = row[1];
+				const f3 co = mk3(a0.x, a0.y, a0.z), Nn = mk3(a0.w, a1.x, a1.y);
+				f3 nb;
+				tangent_basis(Nn, nt, nb);
+				// the node's row of GI masks: stored with a level-0 node of a kept stage (p.gi_row0: the patch row of its sphere's surface where
+				// there is one); else the grids' row, looked up here (the surface patches, with the node's sphere from its shading row, made
+				// this kernel slower — DESIGN.md §5.8)
+				if(GIM) gi_row = p.gi_row0 ? p.gi_row0[node] : gi_origin_row(p, co);
+			}
+		}
+		for(uint32_t j = j0; j < j1; j++)
+		{
+			const RenderParams &p = launch_args(); // (this round's constants and its view of the staged scene: no scalar lives across the rounds)
+			const SceneView sv = scene_view(p, lds4, TRIS);
+			f3 co = mk3(0, 0, 1), Nn = mk3(0, 0, 1);
+			uint32_t pixel = 0, node_id = 0;
+			if(valid)
+			{
+				const float4 *row = p.nd_src + (size_t) node * 2;
+				const float4 a0 = row[0], a1 = row[1];
+				co = mk3(a0.x, a0.y, a0.z);
+				Nn = mk3(a0.w, a1.x, a1.y);
+				pixel = __float_as_uint(a1.z);
+				node_id = __float_as_uint(a1.w);
+			}
+			const f3 nb = cross3(Nn, nt); // (utils.h:164, as tangent_basis forms it)
+			const uint32_t chunk = (node >> 6) * (((uint32_t) p.num_path_traces + 1u) >> 1) + j;
+			trace_round<TRIS, GIM>(sv, p, valid, node, j, co, Nn, nt, nb, pixel, node_id, gi_row, (uint32_t) uni((int) chunk), lane, cn);
+		}
+	}
+	add_counters(launch_args(), cn, (uint32_t) blockIdx.x * 4u + wave, lane);
+}
+#else
+template <bool TRIS, bool GIM>
+__global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams)
+{
+	extern __shared__ __align__(16) unsigned char lds_raw[];
+	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
+	const RenderParams &p = launch_args(); // (the kernel's entry; every block below names the constants anew)
+	const uint32_t N = (uint32_t) p.num_path_traces, PP = (N + 1u) >> 1; // children, sibling pairs per node
+	const uint64_t n_pairs = (uint64_t) *p.nd_count * PP;
+	if((uint64_t) blockIdx.x * 256u >= n_pairs) return; // (uniform per workgroup)
+	stage_scene(p, lds4, TRIS);
+	const int tid = threadIdx.x, lane = tid & 63;
+	Counters cn{0, 0, 0};
+	// (the grid is sized for the worst case — every ray of the level above a hit — and capped: a workgroup takes every
+	// gridDim.x-th block of 256 pairs, so a launch far below the worst case does not pay for its empty workgroups)
+	for(uint32_t blk = blockIdx.x; (uint64_t) blk * 256u < n_pairs; blk += SKR_TRACE_STRIDE)
+	{
+	const RenderParams &p = launch_args(); // (this block's constants and its view of the staged scene: no scalar lives across the loop)
+	const SceneView sv = scene_view(p, lds4, TRIS);
+	const uint32_t chunk = blk * 4u + (uint32_t) (tid >> 6);
+	const uint64_t tp = (uint64_t) chunk * 64u + (uint32_t) lane;
+	const bool valid = tp < n_pairs;
+	const uint32_t node = valid ? (uint32_t) (tp / PP) : 0u, j = valid ? (uint32_t) (tp - (uint64_t) node * PP) : 0u;
+	f3 co = mk3(0, 0, 1), Nn = mk3(0, 0, 1), nt = mk3(0, 1, 0), nb = mk3(1, 0, 0);
+	uint32_t pixel = 0, node_id = 0;
+	int gi_row = -1;
+	if(valid)
+	{
+		const float4 *row = p.nd_src + (size_t) node * 2;
+		const float4 a0 = row[0], a1 = row[1];
+		co = mk3(a0.x, a0.y, a0.z);
+		Nn = mk3(a0.w, a1.x, a1.y);
+		pixel = __float_as_uint(a1.z);
+		node_id = __float_as_uint(a1.w);
+		tangent_basis(Nn, nt, nb);
+		if(GIM) gi_row = p.gi_row0 ? p.gi_row0[node] : gi_origin_row(p, co);
+	}
+	trace_round<TRIS, GIM>(sv, p, valid, node, j, co, Nn, nt, nb, pixel, node_id, gi_row, chunk, lane, cn);
 	}
 	add_counters(launch_args(), cn, (uint32_t) blockIdx.x * 4u + (uint32_t) (tid >> 6), lane);
 }
+#endif
 
 // =====================================================================================================================
 // activate (depth >= 4): record -> node of the next level
@@ -711,6 +804,10 @@ __global__ __launch_bounds__(256) void skr_finalize_kernel2(const RenderParams p
 	const float4 b0 = row[0], b1 = row[1];
 	const uint32_t pixel = __float_as_uint(b1.z), node_id = __float_as_uint(b1.w);
 	f3 total = mk3(0, 0, 0);
+#if SKR_TRACE_BY_NODE
+	// (a wave's 64 nodes are one block of the trace kernel's: the header of pair j is one row for all of them, read through the scalar cache)
+	const uint32_t hrow0 = (uint32_t) uni((int) (node >> 6)) * (uint32_t) PP;
+#endif
 	for(int j0 = 0; j0 < PP; j0 += 4)
 	{ // 4 sibling pairs (8 children) per trip: codes, headers and every gather issued before the first add
 		uint32_t code[4], rec[8];
@@ -718,15 +815,21 @@ __global__ __launch_bounds__(256) void skr_finalize_kernel2(const RenderParams p
 #pragma unroll
 		for(int k = 0; k < 4; k++)
 		{
+#if SKR_TRACE_BY_NODE
+			const size_t hrow = (size_t) hrow0 + (uint32_t) (j0 + k);
+			const uint32_t bit = node & 63u;
+#else
 			const uint64_t tp = (uint64_t) node * (uint32_t) PP + (uint32_t) (j0 + k);
+			const size_t hrow = (size_t) (tp >> 6);
+			const uint32_t bit = (uint32_t) tp & 63u;
+#endif
 			code[k] = 0;
 			rec[2 * k] = rec[2 * k + 1] = 0;
 			if(j0 + k < PP)
 			{
-				const uint4 *h = p.ixh + IXH_ROWS * (size_t) (tp >> 6);
+				const uint4 *h = p.ixh + IXH_ROWS * hrow;
 				const uint4 h0 = h[0], h1 = h[1];
 				const unsigned long long m0 = (unsigned long long) h1.y << 32 | h1.x, m1 = (unsigned long long) h1.w << 32 | h1.z;
-				const uint32_t bit = (uint32_t) tp & 63u;
 				const unsigned long long below = (1ull << bit) - 1ull;
 				code[k] = (uint32_t) ((m0 >> bit) & 1ull) * PC_HIT0 | (uint32_t) ((m1 >> bit) & 1ull) * PC_HIT1;
 				if(p.n_tris > 0)
@@ -817,8 +920,7 @@ static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, NodePlan &
 	pl.cap[0] = 0;
 	for(int L = 1; L < pl.levels; L++)
 	{ // a region receives at most 128 hits from each of its trace waves (64 sibling pairs)
-		const uint64_t chunks = (pl.nodes_max[L - 1] * PP + 63) / 64;
-		const uint64_t cap = (chunks + SKR_P1_REGIONS - 1) / SKR_P1_REGIONS * 128;
+		const uint64_t cap = skr_trace_region_cap(pl.nodes_max[L - 1], PP);
 		if(cap * SKR_P1_REGIONS >= (1ull << 31)) return false; // record indices carry a flag bit
 		pl.cap[L] = (uint32_t) cap;
 		pl.nodes_max[L] = cap * SKR_P1_REGIONS;
@@ -840,8 +942,8 @@ static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, NodePlan &
 			pl.off_shade[L] = s.take(n * 32);
 		}
 		if(L < pl.levels - 1)
-		{ // the children of level L: a 48-byte header per trace wave (64 sibling pairs)
-			pl.off_ixh[L] = s.take(((n * PP + 63) / 64 + 4) * IXH_ROWS * 16);
+		{ // the children of level L: a 48-byte header per trace wave and round (launch.h skr_trace_header_row)
+			pl.off_ixh[L] = s.take((size_t) skr_trace_rows_alloc(n, PP) * IXH_ROWS * 16);
 		}
 	}
 	pl.banded = s.off - (pl.off_nodes[0]); // what grows with the band; the counters are fixed
@@ -852,6 +954,27 @@ static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, NodePlan &
 	pl.off_girow = s.take((size_t) nblk * 256u * sizeof(int32_t));
 	pl.total = s.off;
 	return true;
+}
+
+// Internal (tests only; no device involved): where the trace kernel puts what finalize reads, for a level of `nodes` nodes with N children
+// each, as plan_for sizes it.  out[0] = header rows in use, [1] = rows the table holds, [2] = records per region (cap).  rows, bits (each
+// nodes x PP words, or null): the header row and the ballot bit of sibling pair j of node n at [n * PP + j].  Returns PP.
+extern "C" uint32_t skr_trace_header_map(uint32_t nodes, uint32_t N, uint64_t *out, uint32_t *rows, uint32_t *bits)
+{
+	const uint32_t PP = (N + 1u) >> 1;
+	if(out)
+	{
+		out[0] = skr_trace_rows_used(nodes, PP);
+		out[1] = skr_trace_rows_alloc(nodes, PP);
+		out[2] = skr_trace_region_cap(nodes, PP);
+	}
+	for(uint32_t n = 0; n < nodes && rows && bits; n++)
+		for(uint32_t j = 0; j < PP; j++)
+		{
+			rows[(size_t) n * PP + j] = (uint32_t) skr_trace_header_row(n, j, PP);
+			bits[(size_t) n * PP + j] = skr_trace_header_bit(n, j, PP);
+		}
+	return PP;
 }
 
 static uint64_t nodes_budget(const RenderParams &p, bool flat)
@@ -1010,7 +1133,11 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStr
 				p.rc_cap = pl.cap[L];
 				p.rc_ctr = lvl_ctr(L);
 				p.ixh = reinterpret_cast<uint4 *>(base + pl.off_ixh[L - 1]);
+#if SKR_TRACE_BY_NODE
+				const uint64_t wg_t = ((pl.nodes_max[L - 1] + 63) / 64 * trace_runs_per_block(((uint32_t) p.num_path_traces + 1u) >> 1) + 3) / 4; // four items per workgroup
+#else
 				const uint64_t wg_t = (pl.nodes_max[L - 1] * (uint64_t) ((p.num_path_traces + 1) >> 1) + 255) / 256;
+#endif
 				const unsigned grid_t = (unsigned) (wg_t < SKR_TRACE_GRID_MAX ? wg_t : SKR_TRACE_GRID_MAX);
 				if(flat && L == last && timed) skr_hook_start(hook, stream); // (flat: the last level's trace + shading are the dominant pair)
 				if(tris) hipLaunchKernelGGL((skr_trace_kernel<true, false>), dim3(grid_t), dim3(256), lds_scene, stream, p);

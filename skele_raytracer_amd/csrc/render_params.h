@@ -98,7 +98,7 @@ struct RenderParams {
 	float4 *rc;               // hit records of the level being produced (trace) or consumed (activate, leaf): [parent, sphere | child << 16, r1, r2]
 	uint32_t rc_cap;          // records per region (SKR_P1_REGIONS regions)
 	uint32_t *rc_ctr;         // that level's counters: [STRIDE r] records in region r, [STRIDE (64 + r)] units handed out, [STRIDE 128] exhausted mask, [STRIDE 129 ..] prefix sums
-	uint4 *ixh;               // per trace wave (64 sibling pairs of the nd_src nodes, pair = node * PP + j) three uint4: {first record of its hits, how many of them are even children's, -, -}, the ballots of the even / odd children that hit (64 bits each), the ballots of the children a triangle took (triangle scenes)
+	uint4 *ixh;               // per trace wave and round (64 consecutive nd_src nodes, sibling pair j of each: row (node >> 6) * PP + j, launch.h skr_trace_header_row) three uint4: {first record of its hits, how many of them are even children's, -, -}, the ballots of the even / odd children that hit (64 bits each), the ballots of the children a triangle took (triangle scenes)
 	uint32_t band_blk0, band_nblk, blocks_x; // node_layout: skr_primary_kernel covers the 16x16 pixel blocks [band_blk0, band_blk0 + band_nblk) of the launch (row-major, blocks_x per row)
 	void *node_scratch;       // (host) the pipeline's one allocation
 	const float *res_in;      // (colour r1)/pdf of every child record (finalize)
