@@ -34,6 +34,7 @@ extern "C" {
 #define SKR_HAS_SPOT_LIGHTS 1 /* SKR_SCN_SPOT, skr_scene_get/set_spot_lights, skr_scene_get_spot_cones, skr_debug_eval op 17: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_SOFT_LIGHTS 1 /* skr_scene_set/get_light_radii, skr_debug_eval op 18: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ROOT_PAIRS 1 /* skr_debug_eval op 19: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_LENS 1 /* skr_scene_set/get_lens, skr_debug_eval op 22: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -254,6 +255,42 @@ int skr_scene_get_spot_cones(const skr_scene *scene, float *cones);
  * (it changes the light count).  get: *n = n_point + n_spot, radii (if not NULL) receives them. */
 int skr_scene_set_light_radii(skr_scene *scene, const float *radii, int32_t n);
 int skr_scene_get_light_radii(const skr_scene *scene, float *radii, int32_t *n);
+/* Thin-lens camera: depth of field from an aperture and a focus (new, opt-in; no counterpart in the reference, whose camera is a
+ * pinhole).  A scene has a lens (A, F): aperture radius A >= 0, default 0, and focus parameter F > 0, default 1; both finite.  The rule
+ * (normative):
+ *   - A == 0 is the pinhole camera: no draw is made; planning, skr_kernel_variant(), frames and counters are what they are without a
+ *     lens, bit for bit.
+ *   - With A > 0 the primary sample of (pixel, aa) under seed s takes ONE lens sample.  The draw: one call philox4x32(pixel, aa, 0,
+ *     SKR_LENS_CTR3, seed_lo, seed_hi) with SKR_LENS_CTR3 = 0x800000C0u.  The word is disjoint from every other draw: the hemisphere draws
+ *     have bit 31 clear, the fog draws' word has bit 7 clear, the light samples' word (0x80000080u | (l << 8)) has bit 6 clear, the jitter
+ *     word is 0xFFFFFFFF.  u1 = u31_to_unit(out[0]), u2 = u31_to_unit(out[1]); out[2] and out[3] are unused.
+ *   - The disk point, in binary32, one correctly rounded operation per step, no libm, no binary64, not contracted:
+ *         r = sqrt(u1);  phi = 0x1.921fb6p+2f * u2  (the light sample's product, inside the range sincos_spec is exhaustively checked
+ *         on);  (sn, cs) = sincos_spec(phi);  lx = r * cs;  ly = r * sn.
+ *   - The ray: d is the pinhole direction of that pixel and sample (main.cpp:140-182: both branches and the jitter draw untouched);
+ *     k = A / F is one binary32 division, done once on the host;
+ *         o' = (cam_pos + cam_right * (A * lx)) + cam_up * (A * ly)
+ *         d' = (d - cam_right * (k * lx)) - cam_up * (k * ly)
+ *     with cam_right and cam_up as the camera holds them (not unit length, as d is not).
+ *   - Focus and the t window: the ray reaches the pinhole ray's point cam_pos + F d at t = F, so F is in units of d, as every t of the
+ *     renderer is.  d' keeps d's scale, so the sphere acceptance window 1 < t (raytrace.h:152-165) means what it means for the pinhole.
+ *   - Shading: the primary segment of (pixel, aa) is the ray (o', d'), node 0, ignore_triangle = -1, tmax = +inf.  Everything below it
+ *     is unchanged: child rays, GI draws, light samples, counters, the AA sum and its / (float) (g * g), and progressive_passes (the
+ *     seeds s .. s + K - 1 give K lens samples).  The specular view vector still points to the scene camera cam_pos, as everywhere
+ *     (blinn_phong.h:93; skr_shade_rays says the same).
+ *   - A scene with A > 0 renders every frame on the general level pipeline (skr_kernel_variant() carries one "_lens" part behind the
+ *     light part: "level_pipeline_g1_lens", "level_pipeline_g1_spot_lens_tshadow", ...), in every mode it has but three:
+ *     skr_options.legacy_reflect, fog volumes and the sphere-tree switch are refused with SKR_ERR_UNSUPPORTED, as spot lights and light
+ *     radii refuse them.  skr_render_denoised_host and skr_render_adaptive_denoised_host are refused too (their guides are pinhole
+ *     first hits, and their edge-stopping would undo the blur); skr_denoise / skr_denoise_var on caller-supplied guides are unaffected.
+ *   - skr_camera_rays under a lens returns (o', d') for (opt, sample), keyed to opt->seed: skr_shade_rays of a frame's camera rays with
+ *     keys y * width + x stays that sample of the frame, bit for bit.  skr_shade_rays and skr_trace_rays themselves are unaffected: the
+ *     rays are the caller's.
+ * set: a value that is not finite, aperture < 0 or focus <= 0: SKR_ERR_ARG and the scene is unchanged.  A renderer takes the lens the
+ * scene has when it is created, as it takes the light radii; skr_renderer_clone carries it. */
+#define SKR_LENS_CTR3 0x800000C0u
+int skr_scene_set_lens(skr_scene *scene, float aperture, float focus);
+int skr_scene_get_lens(const skr_scene *scene, float *aperture, float *focus);
 /* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
  * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
  * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device
@@ -510,7 +547,8 @@ typedef struct {              /* 32 bytes */
 int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t flags, void *d_out, void *stream);
 /* The primary rays of sample `sample` of a frame with options `opt` (the AA index, < grid_size^2; 0 with grid_size == 0, the pixel
  * centres) into a DEVICE skr_ray[height][width]: o = the camera position, d = bit for bit the direction the renderer traces for that
- * pixel and sample (main.cpp:140-182), tmax = +inf, ignore_triangle = -1.  Asynchronous on `stream`. */
+ * pixel and sample (main.cpp:140-182), tmax = +inf, ignore_triangle = -1.  Asynchronous on `stream`.  Where the renderer's scene has a
+ * lens with an aperture > 0 (skr_scene_set_lens): (o', d') of that rule for (opt, sample), keyed to opt->seed. */
 int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, skr_ray *d_rays, void *stream);
 
 /* ---- shading queries (new): the radiance of caller-supplied rays, what shade() returns for them ----
@@ -700,7 +738,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  *    -> {powf_spec<false>(x, p, steps), powf_spec<true>(x, p, steps)}: the instance that reads RenderParams::pow_steps and the one
  *    the shaped leaf instances compile in, which is right only for integer p <= 127 (op 2 is the first at steps = 11).
  * 21 (hi16 -> mismatch counts of len_terms<true>'s len, inv, inv2 and len_terms<false>'s inv against sqrtf(ss), 1.0f / len and
- *    1.0f / (len * len) in the correctly rounded expansions, over the 65536 binary32 values with those high 16 bits; as op 9). */
+ *    1.0f / (len * len) in the correctly rounded expansions, over the 65536 binary32 values with those high 16 bits; as op 9).
+ * 22 the lens sample and ray (skr_scene_set_lens above; wave_common.h lens_ray, the function the camera kernels call), laid out as op 18
+ *    is: (pixel, aa, seed_lo, seed_hi, A, k, cam_pos(3), cam_right(3), cam_up(3), d(3)), 18 words -> (lx, ly, o'(3), d'(3)), 8 words.
+ *    (Ops 20 and 21 were taken when the lens came.) */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -89,6 +89,8 @@ def lib():
     L.skr_scene_get_spot_cones.argtypes = [vp, vp]
     L.skr_scene_set_light_radii.argtypes = [vp, vp, C.c_int32]
     L.skr_scene_get_light_radii.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.skr_scene_set_lens.argtypes = [vp, C.c_float, C.c_float]
+    L.skr_scene_get_lens.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
     L.skr_scene_set_sphere_tree.argtypes = [vp, C.c_int]
@@ -366,6 +368,18 @@ class Scene:
         _check(lib().skr_scene_set_light_radii(self.h, r.ctypes.data, len(r)), "skr_scene_set_light_radii")
 
     @property
+    def lens(self):
+        """The scene's lens (aperture, focus); aperture 0 = the pinhole camera (include/skr.h skr_scene_get_lens)."""
+        a, f = C.c_float(), C.c_float()
+        _check(lib().skr_scene_get_lens(self.h, C.byref(a), C.byref(f)), "skr_scene_get_lens")
+        return a.value, f.value
+
+    def set_lens(self, aperture, focus=1.0):
+        """Give the camera a thin lens (depth of field; include/skr.h skr_scene_set_lens states the rule): aperture radius >= 0 (0: the
+        pinhole), focus > 0 in units of the primary ray directions, both finite.  A renderer takes the lens the scene has when it is made."""
+        _check(lib().skr_scene_set_lens(self.h, C.c_float(float(aperture)), C.c_float(float(focus))), "skr_scene_set_lens")
+
+    @property
     def triangle_shadows(self):
         """The scene's triangle-shadow switch (include/skr.h skr_scene_set_triangle_shadows)."""
         on = C.c_int()
@@ -407,7 +421,7 @@ class Scene:
 
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
-                    triangle_shadows=False, sphere_tree=False, light_radii=None):
+                    triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -431,6 +445,8 @@ class Scene:
             sc.set_sphere_tree(True)
         if light_radii is not None:  # a scalar or [n_point_lights] (soft shadows)
             sc.set_light_radii(light_radii)
+        if lens is not None:  # (aperture, focus) (depth of field)
+            sc.set_lens(*lens)
         return sc
 
 

@@ -142,6 +142,20 @@ __global__ __launch_bounds__(256) void skr_adaptive_rays_kernel(const RenderPara
 	rays[2 * i + 1] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
 }
 
+// The same under a lens (include/skr.h skr_scene_set_lens): (o', d') of wave_common.h lens_ray, the rays of skr_camera_ray_lens_kernel
+__global__ __launch_bounds__(256) void skr_adaptive_rays_lens_kernel(const RenderParams p, const uint32_t *__restrict__ list, uint32_t m, float4 *__restrict__ rays, const Lens lens)
+{
+	const uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+	if(i >= m) return;
+	const uint32_t pix = list[i], w = (uint32_t) p.width;
+	const uint32_t y = pix / w, x = pix - y * w;
+	f3 dir, o;
+	primary_ray(p, (int) x, y, pix, p.aa_index, dir);
+	lens_ray(p, lens, pix, p.aa_index, dir, o, dir);
+	rays[2 * i] = make_float4(o.x, o.y, o.z, __builtin_inff());
+	rays[2 * i + 1] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
+}
+
 // AA sample `a` of `samples` (0: one sample at the pixel centre, folded as it is) of the listed pixels, slot i = pixel list[i]:
 // the running sum starts at 0 and adds the samples in sample order, then / (float) samples (render_wave.hip skr_resolve_kernel)
 __global__ __launch_bounds__(256) void skr_adaptive_sample_kernel(const AdaptiveScratch s, const uint32_t *__restrict__ list, uint32_t m, uint32_t a, uint32_t samples)
@@ -281,10 +295,11 @@ hipError_t skr_launch_adaptive_select(const AdaptiveScratch &s, const AdaptiveRu
 	return hipGetLastError();
 }
 
-hipError_t skr_launch_adaptive_rays(const RenderParams &p, const uint32_t *list, uint32_t m, float4 *rays, hipStream_t stream)
+hipError_t skr_launch_adaptive_rays(const RenderParams &p, const uint32_t *list, uint32_t m, float4 *rays, hipStream_t stream, const Lens *lens)
 {
 	if(m == 0) return hipSuccess;
-	hipLaunchKernelGGL(skr_adaptive_rays_kernel, dim3((unsigned) (((uint64_t) m + 255) / 256)), dim3(256), 0, stream, p, list, m, rays);
+	if(lens) hipLaunchKernelGGL(skr_adaptive_rays_lens_kernel, dim3((unsigned) (((uint64_t) m + 255) / 256)), dim3(256), 0, stream, p, list, m, rays, *lens);
+	else hipLaunchKernelGGL(skr_adaptive_rays_kernel, dim3((unsigned) (((uint64_t) m + 255) / 256)), dim3(256), 0, stream, p, list, m, rays);
 	return hipGetLastError();
 }
 

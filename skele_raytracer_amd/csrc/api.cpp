@@ -47,6 +47,7 @@ struct DeviceScene {
 	size_t off_radii = 0;     // skr_scene_set_light_radii: one float per point and spot light behind the cone rows (render_params.h SoftLights)
 	int n_radii = 0;
 	bool soft = false;        // some radius is > 0: frames and shading queries take the instances with the light sample
+	float lens_A = 0.0f, lens_F = 1.0f, lens_k = 0.0f; // skr_scene_set_lens: the aperture, the focus and k = A / F (one binary32 division); A > 0: frames take the instances with the lens sample
 	size_t off_smask = 0;     // the shadow masks (skr_scene::shadow_masks, 4 per row), 0 = none
 	size_t off_ssurf = 0;     // their surface patches (skr_scene::shadow_surface: ssurf_stride words per pair of lights), 0 = none
 	uint32_t ssurf_stride = 0;
@@ -210,6 +211,9 @@ static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 	d.n_radii = (int) s.light_radii.size();
 	d.soft = s.soft();
 	d.off_radii = put(s.light_radii.data(), s.light_radii.size() * 4);
+	d.lens_A = s.lens_aperture;
+	d.lens_F = s.lens_focus;
+	d.lens_k = s.lens_aperture / s.lens_focus;
 	if(!s.shadow_masks.empty()) d.off_smask = put(s.shadow_masks.data(), s.shadow_masks.size() * 4);
 	d.shadow_reach2 = s.shadow_reach2;
 	if(!s.shadow_surface.empty())
@@ -482,8 +486,9 @@ static uint32_t sel_tiles(const skr_options *opt, uint32_t tile_rows, const Tile
 
 // Everything of a launch beyond camera_params that is not its output: the scene, the switches and masks, and the options folded and
 // checked — the depth fold, the node-id bound, the fog exclusions.  render_pass and skr_shade_rays both take it.
-static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p);
-static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &p, GenericFeatures &f)
+// query: a shading query — its rays are the caller's, so the scene's lens is not among its features.
+static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p, bool query);
+static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &p, GenericFeatures &f, bool query = false)
 {
 	const DeviceScene &s = *r->scene;
 	p.sw = r->sw;
@@ -565,7 +570,7 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 	p.n_fog = s.n_fog;
 	p.fog_row = (uint32_t) s.off_fog;
 	// what the scene and the options switch on of the general level pipeline, and whether they go together (launch.h)
-	f = generic_features(r, p);
+	f = generic_features(r, p, query);
 	if(const char *why = skr_features_conflict(f, opt->legacy_reflect != 0, opt->shade_triangles != 0, p.n_fog > 0))
 	{
 		skr_set_error("%s", why);
@@ -596,6 +601,23 @@ static int check_plan(const skr_renderer *r, const RenderParams &p, bool fits, s
 		return SKR_ERR_UNSUPPORTED;
 	}
 	return SKR_OK;
+}
+
+// the scene's lens for the kernels that form camera rays alone (launch.h Lens; no trees); null: the pinhole
+static const Lens *camera_lens(const skr_renderer *r, Lens &lens)
+{
+	const DeviceScene &s = *r->scene;
+	if(!(s.lens_A > 0.0f)) return nullptr;
+	lens = Lens{s.lens_A, s.lens_k, QueryTrees{}};
+	return &lens;
+}
+
+// A scene with a lens has no denoised frame (include/skr.h skr_scene_set_lens): the guides are pinhole first hits
+static int refuse_lens(const skr_renderer *r, const char *who)
+{
+	if(!(r->scene->lens_A > 0.0f)) return SKR_OK;
+	skr_set_error("%s: a lens (--aperture) cannot be combined with the denoiser (its guides are the pinhole camera's first hits)", who);
+	return SKR_ERR_UNSUPPORTED;
 }
 
 // the trees a query may walk under the renderer's switches (launch.h QueryTrees)
@@ -634,7 +656,7 @@ static SphereTree sphere_tree_of(const skr_renderer *r)
 // scene has them switched on, the launch shades triangles (the option is set and the scene has some) and casts shadow rays (include/skr.h
 // skr_scene_set_triangle_shadows); otherwise the launch is the one it was without the switch: the same kernels, the same
 // skr_kernel_variant().
-static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p)
+static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p, bool query)
 {
 	const DeviceScene &s = *r->scene;
 	GenericFeatures f;
@@ -646,6 +668,8 @@ static GenericFeatures generic_features(const skr_renderer *r, const RenderParam
 	if(f.sphere_tree) f.stree = sphere_tree_of(r);
 	if(f.spot || f.soft) f.spots = SpotLights{s.d_blob + s.off_spot, s.spot_first, s.n_spot}; // (n = 0 without spot lights)
 	if(f.soft) f.softs = SoftLights{reinterpret_cast<const float *>(s.d_blob + s.off_radii), s.n_radii};
+	f.lens = s.lens_A > 0.0f && !query;
+	if(f.lens) f.thin_lens = Lens{s.lens_A, s.lens_k, query_trees(r)};
 	return f;
 }
 
@@ -1158,7 +1182,8 @@ int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, sk
 		return SKR_ERR_ARG;
 	}
 	SKR_HIP(hipSetDevice(r->scene->device));
-	SKR_HIP(skr_launch_camera_rays(camera_params(r, opt, opt->seed, sample), reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream));
+	Lens lens;
+	SKR_HIP(skr_launch_camera_rays(camera_params(r, opt, opt->seed, sample), reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream, camera_lens(r, lens)));
 	return SKR_OK;
 }
 
@@ -1182,7 +1207,7 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	p.out_rows = (uint32_t) (((uint64_t) n + SKR_SHADE_ROW - 1) / SKR_SHADE_ROW);
 	p.band_rows = p.out_rows;
 	GenericFeatures f;
-	rc = launch_params(r, opt, p, f);
+	rc = launch_params(r, opt, p, f, true);
 	if(rc != SKR_OK) return rc;
 	p.grid_size = 0; // (one sample: `sample`)
 	GPlan pl;
@@ -1265,6 +1290,7 @@ int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t i
 		return SKR_ERR_ARG;
 	}
 	int rc = check_options(opt); // before anything is sized from width x height
+	if(rc == SKR_OK) rc = refuse_lens(r, "skr_render_denoised_host");
 	if(rc != SKR_OK) return rc;
 	SKR_HIP(hipSetDevice(r->scene->device));
 	const size_t n = (size_t) opt->width * opt->height;
@@ -1374,10 +1400,12 @@ static int render_adaptive(skr_renderer *r, const char *who, const skr_options *
 		}
 		// query path: per AA sample the listed pixels' camera rays, shaded with the pixel words as keys (skr_shade_rays)
 		RenderParams p = camera_params(r, opt, pass.seed, 0);
+		Lens lens;
+		const Lens *lp = camera_lens(r, lens);
 		for(uint32_t aa = 0; aa < (samples ? samples : 1u); aa++)
 		{
 			p.aa_index = aa;
-			SKR_HIP(skr_launch_adaptive_rays(p, in, m, s.rays, st));
+			SKR_HIP(skr_launch_adaptive_rays(p, in, m, s.rays, st, lp));
 			rc = skr_shade_rays(r, &pass, reinterpret_cast<const skr_ray *>(s.rays), m, aa, in, s.shade, stream);
 			if(rc != SKR_OK) return rc;
 			SKR_HIP(skr_launch_adaptive_sample(s, in, m, aa, samples, st));
@@ -1433,6 +1461,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 		return SKR_ERR_ARG;
 	}
 	int rc = check_adaptive(opt, a, "skr_render_adaptive_denoised_host"); // before anything is sized from width x height
+	if(rc == SKR_OK) rc = refuse_lens(r, "skr_render_adaptive_denoised_host");
 	if(rc != SKR_OK) return rc;
 	SKR_HIP(hipSetDevice(r->scene->device));
 	const size_t n = (size_t) opt->width * opt->height;
@@ -1461,7 +1490,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {
-	if(!d_in || !d_out || op < 0 || op > 21) return SKR_ERR_ARG;
+	if(!d_in || !d_out || op < 0 || op > 22) return SKR_ERR_ARG;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(skr_launch_debug(op, d_in, d_out, n, (hipStream_t) stream));
 	return SKR_OK;

@@ -226,6 +226,11 @@ SKR_DEV float u31_to_pm1(uint32_t w) { return -1.0f + (float) (w >> 1) * 9.31322
 // (pixel, aa, node, soft_ctr3(l)).  Bit 31 set: disjoint from the hemisphere draws.  Bit 7 set: disjoint from fog_ctr3, whose bit 7 is
 // clear (l < 2^22, j < 64).  Bits 0-6 clear: never the jitter word 0xFFFFFFFF.  u1 = u31(out[0]), u2 = u31(out[1]); out[2], out[3] unused.
 SKR_DEV uint32_t soft_ctr3(uint32_t light) { return 0x80000080u | (light << 8); }
+// The lens sample of a camera with an aperture (include/skr.h skr_scene_set_lens): ONE call per (pixel, aa), counter
+// (pixel, aa, 0, lens_ctr3()) = SKR_LENS_CTR3.  Bit 31 set: disjoint from the hemisphere draws.  Bit 7 set: disjoint from fog_ctr3.  Bit 6
+// set: disjoint from soft_ctr3, whose bit 6 is clear.  Bits 0-5 clear: never the jitter word 0xFFFFFFFF.  u1 = u31(out[0]),
+// u2 = u31(out[1]); out[2], out[3] unused.
+SKR_DEV uint32_t lens_ctr3() { return 0x800000C0u; }
 
 // ------------------------------------------------------- shared math ----
 typedef float f2 __attribute__((ext_vector_type(2)));

@@ -57,6 +57,15 @@ struct QueryTrees {
 	float4 ball;         // {centre, radius}: the trace tree holds for rays that start in it
 };
 
+// The lens of a scene with an aperture (include/skr.h skr_scene_set_lens; wave_common.h lens_ray): what the kernels that
+// form camera rays read — the general level pipeline's trace and activate instances for such a scene, in a kernel argument of their own
+// as every feature is, and the camera-ray kernels of the ray queries and the adaptive sampler.  k = A / F, one binary32 division on the
+// host.  Level-1 rays under a lens do not start at the scene camera: their waves pick a tree as query rays do (pick_query_tree).
+struct Lens {
+	float A, k;
+	QueryTrees trees; // (the level pipeline's instances only)
+};
+
 // A shading query (include/skr.h skr_shade_rays) on the general level pipeline: the rays are its roots, as rows of RenderParams::width
 // rays (the last row partial), banded like a frame's rows.  The kernels' second argument (render_generic.hip).
 struct ShadeRays {
@@ -83,10 +92,12 @@ struct GenericFeatures {
 	bool sphere_tree = false; // the scene has the sphere tree switched on and at least one sphere (include/skr.h skr_scene_set_sphere_tree)
 	bool spot = false;        // the scene has at least one spot light (include/skr.h SKR_SCN_SPOT)
 	bool soft = false;        // at least one light of the scene has a radius > 0 (include/skr.h skr_scene_set_light_radii)
+	bool lens = false;        // the scene has a lens with an aperture > 0 and the launch is a frame (include/skr.h skr_scene_set_lens); never with a shading query: its rays are the caller's
 	TriShadows shadows{};     // (tri_shadows)
 	SphereTree stree{};       // (sphere_tree)
 	SpotLights spots{};       // (spot or soft; n = 0 where the scene has no spot light)
 	SoftLights softs{};       // (soft)
+	Lens thin_lens{};         // (lens)
 };
 
 enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
@@ -188,9 +199,9 @@ static inline SkrLeafShape skr_leaf_shape(const RenderParams &p)
 
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
-// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights and lights with a radius take the general level pipeline
+// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius and a lens take the general level pipeline
 bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, const GenericFeatures &f); // false: the launch takes a level pipeline and not one band of it fits the budget
-// The features a launch cannot combine, given the options as the caller set them: spot lights and lights with a radius exclude
+// The features a launch cannot combine, given the options as the caller set them: spot lights, lights with a radius and a lens exclude
 // --legacy-reflect, fog volumes and the sphere tree; fog excludes --legacy-reflect and --shade-triangles, and with the latter triangle
 // shadows.  (Lights with a radius need the SpotLights argument: the record always carries it.)  The text for the user, or null.
 const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect, bool shade_triangles, bool fog);
@@ -248,7 +259,8 @@ struct TraceScene {
 };
 // st: the renderer's scene has the sphere tree switched on (the instances whose sphere searches are the tree's walks); null: it has not
 hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream, const SphereTree *st = nullptr);
-hipError_t skr_launch_camera_rays(const RenderParams &p, float4 *rays, hipStream_t stream);
+// lens: the scene's lens where its aperture is > 0 (the rays (o', d') of include/skr.h skr_scene_set_lens); null: the pinhole
+hipError_t skr_launch_camera_rays(const RenderParams &p, float4 *rays, hipStream_t stream, const Lens *lens = nullptr);
 // denoise.hip: the denoiser (include/skr.h skr_denoise).  Not a render: no plan, no counters, no timing.
 struct DenoiseScratch {
 	float4 *img[2]; // the {r, g, b, var} ping-pong images (img[1] first holds {r, g, b, l})
@@ -283,7 +295,7 @@ size_t skr_adaptive_scratch_bytes(uint64_t pixels);
 AdaptiveScratch skr_adaptive_carve(void *base, uint64_t pixels);
 hipError_t skr_launch_adaptive_fold(const AdaptiveScratch &s, const float *frame, const uint32_t *list, uint32_t m, int first, hipStream_t stream);
 hipError_t skr_launch_adaptive_select(const AdaptiveScratch &s, const AdaptiveRule &rule, const uint32_t *in, uint32_t m, uint32_t *out, hipStream_t stream);
-hipError_t skr_launch_adaptive_rays(const RenderParams &p, const uint32_t *list, uint32_t m, float4 *rays, hipStream_t stream);
+hipError_t skr_launch_adaptive_rays(const RenderParams &p, const uint32_t *list, uint32_t m, float4 *rays, hipStream_t stream, const Lens *lens = nullptr);
 hipError_t skr_launch_adaptive_sample(const AdaptiveScratch &s, const uint32_t *list, uint32_t m, uint32_t sample, uint32_t samples, hipStream_t stream);
 // var: null, or the variance image of skr_render_adaptive_var (the second instance of the resolve kernel)
 hipError_t skr_launch_adaptive_resolve(const AdaptiveScratch &s, uint64_t pixels, uint8_t *rgb, float *rgbf, uint32_t *passes, float *var, hipStream_t stream);

@@ -36,6 +36,10 @@
 // Instances.  What a launch switches on (launch.h GenericFeatures) reaches the kernels as the pack `Q...` of arguments behind
 // RenderParams, each feature a type of its own, in the one order with_pack (below) writes down; a kernel asks the pack for a type
 // (pack_has, pick).  A feature that is off is not in the pack, which leaves that instance's argument block, and so its code, as it was.
+//
+// A lens (include/skr.h skr_scene_set_lens).  With a Lens in the pack the camera rays of level 1 are (o', d') of
+// wave_common.h lens_ray: the trace kernel forms them and picks the tree of each wave as for query rays (the rays do not start at the
+// scene camera), the activate kernel forms o' again for the hit point.  Every level below works on any ray unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -259,7 +263,7 @@ struct SphereLoops {
 template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, const Q... qs)
 {
-	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, LENS = pack_has<Lens, Q...>;
 	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -302,6 +306,7 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 					{
 						ch.o = p.cam_pos;
 						primary_ray(p, (int) x, y, y * bw + x, p.aa_index, ch.d);
+						if constexpr(LENS) lens_ray(p, pick<Lens>(qs...), y * bw + x, p.aa_index, ch.d, ch.o, ch.d); // (o', d') of include/skr.h skr_scene_set_lens
 					}
 				}
 			}
@@ -309,6 +314,8 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 		}
 		SceneView svw = sv;
 		if constexpr(RAYS) query_tree(svw, p, q, ch.exists, ch.o, ch.d);
+		if constexpr(LENS) // level 1 starts on the lens, not at the scene camera: the tree of query rays; the levels below keep the renderer's
+			if(p.g_level == 1) pick_query_tree(svw, pick<Lens>(qs...).trees, p.cam_pos, false, ch.exists, ch.o, ch.d);
 		bool hit = false, black = false;
 		uint32_t surf = 0;
 		float t = 0.0f;
@@ -413,12 +420,13 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 
 // FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
 // Q: TriShadows — the shadow walk behind the sphere test; SphereTree — the sphere test is the tree's pair walk; SpotLights — the pair loop with
-//    the cone decision; SpotLights SoftLights — and the light sample ahead of it (which packs exist: with_pack)
+//    the cone decision; SpotLights SoftLights — and the light sample ahead of it; Lens — a level-1 hit's ray starts on the lens (which packs
+//    exist: with_pack)
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
 	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>, SPOT = pack_has<SpotLights, Q...>,
-				   SOFT = pack_has<SoftLights, Q...>;
+				   SOFT = pack_has<SoftLights, Q...>, LENS = pack_has<Lens, Q...>;
 	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -462,6 +470,11 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 				n.pixel = y * bw + x;
 				n.node_id = 0u;
 				o = p.cam_pos;
+				if constexpr(LENS)
+				{ // the origin the trace kernel gave the ray: the same draw, the same o' (d' is the record's)
+					f3 d2;
+					lens_ray(p, pick<Lens>(qs...), n.pixel, p.aa_index, n.d, o, d2);
+				}
 			}
 		}
 		else
@@ -607,20 +620,28 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
 	return rows > 0 && gplan_for(p, rows, pl);
 }
 
-// Calls `launch` with the pack of an instance: [ShadeRays] [TriShadows] [SphereTree | SpotLights [SoftLights]], the one place the order
-// is written down.  ACT: the activate kernel's pack; the trace and finalize kernels take only [ShadeRays] [SphereTree].  The
-// combinations skr_features_conflict refuses (the sphere tree with spot lights or a radius) are no instance.
-template <bool ACT, typename F>
+// Calls `launch` with the pack of an instance: [ShadeRays] [TriShadows] [SphereTree | SpotLights [SoftLights]] [Lens], the one place the
+// order is written down.  K: whose pack — the activate kernel's is the whole of it; the trace kernel takes only [ShadeRays] [SphereTree]
+// [Lens], the finalize kernel [ShadeRays] [SphereTree].  The combinations skr_features_conflict refuses (the sphere tree with spot
+// lights, a radius or a lens) are no instance, nor is a lens with a shading query (its rays are the caller's).
+enum PackOf { PACK_FINALIZE, PACK_TRACE, PACK_ACTIVATE };
+template <PackOf K, typename F>
 static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 {
+	constexpr bool ACT = K == PACK_ACTIVATE;
+	auto lens = [&](auto... all) {
+		if constexpr(K != PACK_FINALIZE && !pack_has<ShadeRays, decltype(all)...>)
+			if(f.lens) return launch(all..., f.thin_lens);
+		launch(all...);
+	};
 	auto tail = [&](auto... head) {
 		if(f.sphere_tree) return launch(head..., f.stree);
 		if constexpr(ACT)
 		{
-			if(f.soft) return launch(head..., f.spots, f.softs);
-			if(f.spot) return launch(head..., f.spots);
+			if(f.soft) return lens(head..., f.spots, f.softs);
+			if(f.spot) return lens(head..., f.spots);
 		}
-		launch(head...);
+		lens(head...);
 	};
 	auto shadows = [&](auto... head) {
 		if constexpr(ACT)
@@ -678,13 +699,13 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.ixh = reinterpret_cast<uint4 *>(base + pl.off_hdr[L]);
 				const uint64_t wg_t = (pl.nodes_max[L - 1] * (uint64_t) p.g_arity + 255) / 256;
 				const unsigned grid_t = (unsigned) (wg_t < 49152u ? wg_t : 49152u);
-				with_pack<false>(f, qp, [&](auto... a) { hipLaunchKernelGGL((skr_gtrace_kernel<decltype(a)...>), dim3(grid_t), dim3(256), lds, stream, p, a...); });
+				with_pack<PACK_TRACE>(f, qp, [&](auto... a) { hipLaunchKernelGGL((skr_gtrace_kernel<decltype(a)...>), dim3(grid_t), dim3(256), lds, stream, p, a...); });
 				p.g_arity = A; // (node ids of this level's hits: parent id * A + child + 1)
 				p.g_nodes_dst = L < D ? reinterpret_cast<float4 *>(base + pl.off_nodes[L]) : nullptr;
 				p.res_out = reinterpret_cast<float *>(base + pl.off_res[L]);
 				const unsigned grid_a = SKR_P1_REGIONS * ((pl.cap[L] + 255u) / 256u);
-				with_pack<true>(f, qp, [&](auto... a) { // FOG: a separate instance, and only of the packs without triangle shadows and spot lights
-					if constexpr(!pack_has<TriShadows, decltype(a)...> && !pack_has<SpotLights, decltype(a)...>)
+				with_pack<PACK_ACTIVATE>(f, qp, [&](auto... a) { // FOG: a separate instance, and only of the packs without triangle shadows, spot lights and a lens
+					if constexpr(!pack_has<TriShadows, decltype(a)...> && !pack_has<SpotLights, decltype(a)...> && !pack_has<Lens, decltype(a)...>)
 						if(p.n_fog > 0)
 						{
 							hipLaunchKernelGGL((skr_gactivate_kernel<true, decltype(a)...>), dim3(grid_a), dim3(256), lds, stream, p, a...);
@@ -703,7 +724,7 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 				p.res_in = reinterpret_cast<const float *>(base + pl.off_res[L + 1]);
 				p.res_out = L == 0 ? nullptr : reinterpret_cast<float *>(base + pl.off_res[L]);
 				const dim3 grid_f((unsigned) ((pl.nodes_max[L] + 255) / 256));
-				with_pack<false>(f, qp, [&](auto... a) { hipLaunchKernelGGL((skr_gfinalize_kernel<decltype(a)...>), grid_f, dim3(256), lds, stream, p, a...); });
+				with_pack<PACK_FINALIZE>(f, qp, [&](auto... a) { hipLaunchKernelGGL((skr_gfinalize_kernel<decltype(a)...>), grid_f, dim3(256), lds, stream, p, a...); });
 			}
 			if(timed) skr_hook_stop(hook, stream);
 			e = hipGetLastError();

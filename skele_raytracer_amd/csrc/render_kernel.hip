@@ -34,7 +34,7 @@ static size_t direct_lds_bytes(const RenderParams &p)
 }
 
 // Which kernels render this launch, and what they need.  In this order:
-//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, and every tree
+//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, a lens, and every tree
 //     (shade() recurses: max_depth > 1; api.cpp folds --depth to 1 where it cannot, raytrace.h:208-218) the node pipeline does not;
 //   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget and its kernels
 //     fit the device's LDS;
@@ -46,7 +46,7 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, co
 {
 	lp = LaunchPlan();
 	lp.features = f;
-	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft;
+	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft || f.lens;
 	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
 		lp.path = SKR_PATH_NODES;
@@ -82,17 +82,19 @@ const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect,
 										"spot lights (--scn-spot) cannot be combined with the sphere tree (--sphere-tree)"};
 	static const char *const soft[3] = {"light radii (--light-radius) cannot be combined with --legacy-reflect", "light radii (--light-radius) cannot be combined with fog volumes (--scn-fog)",
 										"light radii (--light-radius) cannot be combined with the sphere tree (--sphere-tree)"};
-	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : nullptr;
+	static const char *const lens[3] = {"a lens (--aperture) cannot be combined with --legacy-reflect", "a lens (--aperture) cannot be combined with fog volumes (--scn-fog)",
+										"a lens (--aperture) cannot be combined with the sphere tree (--sphere-tree)"};
+	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : f.lens ? lens[with] : nullptr;
 }
 
 const char *skr_generic_variant(bool query, const GenericFeatures &f)
-{ // (fog has no name of its own)
-	static const char *const name[2][4][2] = {
-		{{"level_pipeline_g1", "level_pipeline_g1_tshadow"}, {"level_pipeline_g1_stree", "level_pipeline_g1_stree_tshadow"},
-		 {"level_pipeline_g1_spot", "level_pipeline_g1_spot_tshadow"}, {"level_pipeline_g1_soft", "level_pipeline_g1_soft_tshadow"}},
-		{{"shade_rays_g1", "shade_rays_g1_tshadow"}, {"shade_rays_g1_stree", "shade_rays_g1_stree_tshadow"},
-		 {"shade_rays_g1_spot", "shade_rays_g1_spot_tshadow"}, {"shade_rays_g1_soft", "shade_rays_g1_soft_tshadow"}}};
-	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][f.tri_shadows];
+{ // (fog has no name of its own; a lens is a frame's: no shading query and no sphere-tree instance has one)
+#define SKR_VARIANT_NAMES(base) {{base, base "_tshadow"}, {base "_lens", base "_lens_tshadow"}}
+	static const char *const name[2][4][2][2] = {
+		{SKR_VARIANT_NAMES("level_pipeline_g1"), SKR_VARIANT_NAMES("level_pipeline_g1_stree"), SKR_VARIANT_NAMES("level_pipeline_g1_spot"), SKR_VARIANT_NAMES("level_pipeline_g1_soft")},
+		{SKR_VARIANT_NAMES("shade_rays_g1"), SKR_VARIANT_NAMES("shade_rays_g1_stree"), SKR_VARIANT_NAMES("shade_rays_g1_spot"), SKR_VARIANT_NAMES("shade_rays_g1_soft")}};
+#undef SKR_VARIANT_NAMES
+	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][!query && f.lens][f.tri_shadows];
 }
 
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)
@@ -395,8 +397,40 @@ __global__ void skr_debug_kernel(int op, const uint32_t *in, uint32_t *out, uint
 	}
 }
 
+// Op 22: the lens sample and ray of one record: lens_ray, the function the camera kernels call under a lens (a kernel of its own: the
+// ops above keep their code)
+__global__ void skr_debug_lens_kernel(const uint32_t *in, uint32_t *out, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	auto F = [](uint32_t u) { return __uint_as_float(u); };
+	auto U = [](float f) { return __float_as_uint(f); };
+	const uint32_t *r = in + 18 * i;
+	RenderParams p{};
+	p.seed_lo = r[2];
+	p.seed_hi = r[3];
+	p.cam_pos = mk3(F(r[6]), F(r[7]), F(r[8]));
+	p.cam_right = mk3(F(r[9]), F(r[10]), F(r[11]));
+	p.cam_up = mk3(F(r[12]), F(r[13]), F(r[14]));
+	Lens lens{};
+	lens.A = F(r[4]);
+	lens.k = F(r[5]);
+	f3 o2, d2;
+	float s[2];
+	lens_ray(p, lens, r[0], r[1], mk3(F(r[15]), F(r[16]), F(r[17])), o2, d2, s);
+	uint32_t *w = out + 8 * i;
+	w[0] = U(s[0]); w[1] = U(s[1]);
+	w[2] = U(o2.x); w[3] = U(o2.y); w[4] = U(o2.z);
+	w[5] = U(d2.x); w[6] = U(d2.y); w[7] = U(d2.z);
+}
+
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream)
 {
+	if(op == 22)
+	{
+		hipLaunchKernelGGL(skr_debug_lens_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n);
+		return hipGetLastError();
+	}
 	hipLaunchKernelGGL(skr_debug_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, op, (const uint32_t *) d_in, (uint32_t *) d_out, n);
 	return hipGetLastError();
 }

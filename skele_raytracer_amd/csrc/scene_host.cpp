@@ -1760,6 +1760,26 @@ int skr_scene_get_light_radii(const skr_scene *scene, float *radii, int32_t *n)
 	return SKR_OK;
 }
 
+int skr_scene_set_lens(skr_scene *scene, float aperture, float focus)
+{
+	if(!scene || !std::isfinite(aperture) || !std::isfinite(focus) || !(aperture >= 0.0f) || !(focus > 0.0f))
+	{
+		skr_set_error("skr_scene_set_lens: the aperture must be a finite number >= 0 and the focus a finite number > 0");
+		return SKR_ERR_ARG;
+	}
+	scene->lens_aperture = aperture + 0.0f; // (-0 -> +0)
+	scene->lens_focus = focus;
+	return SKR_OK;
+}
+
+int skr_scene_get_lens(const skr_scene *scene, float *aperture, float *focus)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(aperture) *aperture = scene->lens_aperture;
+	if(focus) *focus = scene->lens_focus;
+	return SKR_OK;
+}
+
 int skr_scene_get_spot_cones(const skr_scene *scene, float *cones)
 {
 	if(!scene) return SKR_ERR_ARG;

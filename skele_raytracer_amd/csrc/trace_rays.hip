@@ -239,6 +239,20 @@ __global__ __launch_bounds__(256) void skr_camera_ray_kernel(const RenderParams 
 	rays[2 * i + 1] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
 }
 
+// The same under a lens (include/skr.h skr_scene_set_lens): (o', d') of wave_common.h lens_ray.  A kernel of its own: the pinhole's keeps its code.
+__global__ __launch_bounds__(256) void skr_camera_ray_lens_kernel(const RenderParams p, float4 *rays, const Lens lens)
+{
+	const uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+	const uint32_t w = (uint32_t) p.width;
+	if(i >= (uint64_t) w * (uint32_t) p.height) return;
+	const uint32_t y = (uint32_t) (i / w), x = (uint32_t) (i - (uint64_t) y * w);
+	f3 dir, o;
+	primary_ray(p, (int) x, y, y * w + x, p.aa_index, dir);
+	lens_ray(p, lens, y * w + x, p.aa_index, dir, o, dir);
+	rays[2 * i] = make_float4(o.x, o.y, o.z, __builtin_inff());
+	rays[2 * i + 1] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
+}
+
 hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n, bool any_hit, void *out, hipStream_t stream, const SphereTree *st)
 {
 	const dim3 grid((unsigned) (((uint64_t) n + 255) / 256)), block(256);
@@ -265,9 +279,10 @@ hipError_t skr_launch_trace(const TraceScene &s, const float4 *rays, uint32_t n,
 	return hipGetLastError();
 }
 
-hipError_t skr_launch_camera_rays(const RenderParams &p, float4 *rays, hipStream_t stream)
+hipError_t skr_launch_camera_rays(const RenderParams &p, float4 *rays, hipStream_t stream, const Lens *lens)
 {
 	const uint64_t n = (uint64_t) (uint32_t) p.width * (uint32_t) p.height;
-	hipLaunchKernelGGL(skr_camera_ray_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, p, rays);
+	if(lens) hipLaunchKernelGGL(skr_camera_ray_lens_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, p, rays, *lens);
+	else hipLaunchKernelGGL(skr_camera_ray_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream, p, rays);
 	return hipGetLastError();
 }

@@ -103,6 +103,28 @@ SKR_DEV void primary_ray(const RenderParams &p, int x, uint32_t y, uint32_t pixe
 	dir = (p.cam_dir + p.cam_right * u) + p.cam_up * v;
 }
 
+// The lens sample of (pixel, aa) and the ray (o2, d2) it makes of the pinhole direction d (include/skr.h skr_scene_set_lens, DESIGN.md
+// 8.15): one Philox call at node 0 with the counter word SKR_LENS_CTR3, then binary32 with one correctly rounded operation per step.
+// phi <= (float) 2 pi: inside the range sincos_spec is exhaustively checked on.  Every kernel that forms a camera ray under a lens calls
+// this — the level pipeline's trace kernel, its activate kernel for the origin alone (the same draw, the same o2), the camera-ray kernels.
+SKR_DEV void lens_ray(const RenderParams &p, const Lens &lens, uint32_t pixel, uint32_t aa, f3 d, f3 &o2, f3 &d2, float *sample = nullptr)
+{
+	uint32_t rnd[4];
+	philox4x32(pixel, aa, 0u, lens_ctr3(), p.seed_lo, p.seed_hi, rnd);
+	const float u1 = u31_to_unit(rnd[0]), u2 = u31_to_unit(rnd[1]);
+	const float r = sk_sqrtf(u1);
+	float sn, cs;
+	sincos_spec(0x1.921fb6p+2f * u2, sn, cs); // (float) 2 pi times u2, in binary32
+	const float lx = r * cs, ly = r * sn;
+	o2 = (p.cam_pos + p.cam_right * (lens.A * lx)) + p.cam_up * (lens.A * ly);
+	d2 = (d - p.cam_right * (lens.k * lx)) - p.cam_up * (lens.k * ly);
+	if(sample)
+	{
+		sample[0] = lx;
+		sample[1] = ly;
+	}
+}
+
 SKR_DEV void emit_sample(const RenderParams &p, uint32_t out_pix, f3 c)
 { // one sample of one pixel is final: store it (1 spp) or add it to the running sum (AA, sample order = launch order)
 	if(p.grid_size > 0)

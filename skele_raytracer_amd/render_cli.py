@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--aperture A [--focus F]] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
            [--adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
@@ -89,6 +89,10 @@ def _parse(argv):
             opt["scn_spot"] = True
         elif a == "--light-radius":
             opt["light_radius"] = value(i, _atof, "light-radius takes a float (the radius of every point and spot light)")
+        elif a == "--aperture":
+            opt["aperture"] = value(i, _atof, "aperture takes a float (the radius of the lens)")
+        elif a == "--focus":
+            opt["focus"] = value(i, _atof, "focus takes a float (the t of the primary rays that is in focus)")
         elif a == "--scn-fov":
             opt["scn_fov"] = True
         elif a == "--shade-triangles":
@@ -146,6 +150,10 @@ def main(argv=None):
     if radius is not None and not (math.isfinite(radius) and radius >= 0.0):
         print("raytracer: --light-radius takes a finite radius >= 0", file=sys.stderr)  # as bin/raytracer
         return 2
+    aperture, focus = o.get("aperture"), o.get("focus", 1.0)
+    if aperture is not None and not (math.isfinite(aperture) and aperture >= 0.0 and math.isfinite(focus) and focus > 0.0):
+        print("raytracer: --aperture takes a finite radius >= 0 and --focus a finite distance > 0", file=sys.stderr)  # as bin/raytracer
+        return 2
     import torch
     import torch.distributed as dist
     import skele_raytracer_amd as skr
@@ -189,6 +197,8 @@ def main(argv=None):
         o["fov"] = skr.scene_fov(scene)
     if radius is not None:  # as bin/raytracer --light-radius: every point and spot light of the loaded scene (include/skr.h skr_scene_set_light_radii)
         scene.set_light_radii(radius)
+    if aperture is not None:  # as bin/raytracer --aperture A [--focus F]: a thin lens (include/skr.h skr_scene_set_lens); --focus alone has no effect
+        scene.set_lens(aperture, focus)
     r = skr.Renderer(scene, local_rank)
     kw = dict(fov=o["fov"], depth=o["depth"], shadow=o["shadow"], seed=o["seed"], shade_triangles=bool(o.get("shade_triangles")), progressive=o.get("progressive", 1), legacy_reflect=bool(o.get("legacy_reflect")))
     if o["gillum"] is not None:
