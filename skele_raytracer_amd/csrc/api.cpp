@@ -223,7 +223,7 @@ static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
 		for(size_t k = 0; k < s.shadow_surface_head.size(); k++) memcpy(&rows[d.off_kd + k].w, &s.shadow_surface_head[k], 4);
 	}
 	if(!s.gi_table.empty())
-	{ // the GI masks (whole rows: scene_host.cpp build_gi_masks), with the surface patches' masks right behind the grids' masks (their
+	{ // the GI masks (whole rows: scene_masks.cpp build_gi_masks), with the surface patches' masks right behind the grids' masks (their
 	  // rows continue the grids' rows), then the patches' headers and index
 		const size_t patch_word = s.gi_mask_word + (size_t) s.gi_rows * (SKR_GI_ROW_ENTRIES * (s.gi_wide ? 4 : 2) / 4);
 		d.gi_surface_word = s.gi_surface.empty() ? 0 : patch_word + s.gi_surface_head;

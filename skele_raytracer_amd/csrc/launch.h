@@ -185,7 +185,7 @@ static inline uint64_t skr_trace_region_cap(uint64_t nodes, uint64_t PP) { retur
 // The launch shape the leaf kernel (render_nodes.hip skr_leaf_kernel2) has an instance for (shade_common.h PointLightShape<1 | 2>), or
 // none: the instance that reads every fact at run time.  A shape is picked only where EVERY fact it compiles in equals the launch's value:
 // a sphere-only scene with GI masks (the instances are <false, FIRST, true, shape>) of 16-bit entries (at most 16 spheres), shadow rays
-// cast through the shadow masks — which exist only for scenes whose lights are all point lights (scene_host.cpp build_shadow_masks), so no
+// cast through the shadow masks — which exist only for scenes whose lights are all point lights (scene_masks.cpp build_shadow_masks), so no
 // light is directional —, every integer Phong exponent below 128, and exactly one or two lights.  SKR_LEAF_SHAPE=0: never.
 enum SkrLeafShape { SKR_LEAF_RUNTIME = 0, SKR_LEAF_POINT1 = 1, SKR_LEAF_POINT2 = 2 };
 static inline SkrLeafShape skr_leaf_shape(const RenderParams &p)

@@ -1044,7 +1044,7 @@ typedef void (*LeafKernel)(const RenderParams);
 // shape of skr_leaf_shape (launch.h), which alone decides whether a launch has one.
 template <bool FIRST>
 static LeafKernel leaf_instance(const RenderParams &p)
-{ // (GI masks exist for sphere-only scenes alone: scene_host.cpp build_gi_masks)
+{ // (GI masks exist for sphere-only scenes alone: scene_masks.cpp build_gi_masks)
 	switch(skr_leaf_shape(p))
 	{
 	case SKR_LEAF_POINT2: return skr_leaf_kernel2<false, FIRST, true, PointLightShape<2>>;

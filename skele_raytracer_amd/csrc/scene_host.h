@@ -4,6 +4,8 @@
 // kernels read.  See DESIGN.md "Data layout in HBM".
 #pragma once
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -15,6 +17,26 @@
 
 struct skr_f4 {
 	float x, y, z, w;
+};
+
+// An axis-aligned box in binary64 that grows around balls, from nothing or from a first point (which may be NaN, and then stays).
+struct SkrBox {
+	double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+	SkrBox() {}
+	SkrBox(double x, double y, double z) : lo{x, y, z}, hi{x, y, z} {}
+	void grow(double x, double y, double z, double r)
+	{
+		const double p[3] = {x, y, z};
+		for(int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], p[k] - r); hi[k] = std::max(hi[k], p[k] + r); }
+	}
+	double centre(int k) const { return 0.5 * (lo[k] + hi[k]); }
+};
+
+// One set of the triangle chunk tree (skr_scene::tri_chunks) as skr_scene::build_triangle_chunk_level returns it.
+struct SkrChunkLevel {
+	std::vector<skr_f4> rows; // the nodes, a pad node, the chunk entries, a pad entry
+	int node_count = 0;
+	bool any_cone = false; // at least a quarter of the chunks have a tight radius for non-grazing rays
 };
 
 struct skr_scene {
@@ -49,7 +71,7 @@ struct skr_scene {
 	// {axis / kappa, R_tight^2} {skip, first chunk, chunk count, height} (ints) — + one pad node, then two float4 per
 	// chunk of tri_chunk_size consecutive triangles — {centre, R^2} {axis / kappa, R_tight^2} — + one pad entry.
 	// Every inner node has SKR_TRI_SUPER children; a sphere is conservative: a line that
-	// misses it cannot pass utils.h:181-213 for any triangle of the chunk (see finalize())
+	// misses it cannot pass utils.h:181-213 for any triangle of the chunk (scene_trees.cpp build_triangle_chunks)
 	std::vector<skr_f4> tri_chunks; // SKR_CULL_LEVELS sets of them, one per bound on |d| (tri_chunks.h)
 	int tri_chunk_size = SKR_TRI_CHUNK_MIXED;
 
@@ -64,12 +86,13 @@ struct skr_scene {
 	}
 	size_t tri_chunk_stride = 0; // float4 entries per |d| level
 	int tri_node_count = 0;
-	bool tri_any_cone = false; // some chunk has a tight radius for non-grazing rays (scene_host.cpp)
-	void build_triangle_chunks();
+	bool tri_any_cone = false; // some chunk has a tight radius for non-grazing rays (scene_trees.cpp)
+	void build_triangle_chunks(); // every tri_* and trace_* member below tris: both trees, tri_chunk_size chosen here
 	std::vector<int> tri_order; // tris[3*i] holds triangle tri_order[i] of the file
 	void build_triangle_materials();
-	// origin_ball (x, y, z, radius) or null: the rays start anywhere in that ball instead of at the camera or on a sphere
-	void build_triangle_chunk_level(double d_max, std::vector<skr_f4> &out, const double *origin_ball = nullptr);
+	// one set of a tree for |d| <= d_max.  origin_ball (x, y, z, radius) or null: the rays start anywhere in that ball instead of at
+	// the camera or on a sphere
+	SkrChunkLevel build_triangle_chunk_level(double d_max, const double *origin_ball = nullptr) const;
 	// the same tree for the ray queries (skr_trace_rays): SKR_CULL_LEVELS sets of tri_chunk_stride entries that hold for rays starting
 	// anywhere in the ball trace_ball = {centre, radius} (twice the radius of a ball around the camera, the spheres and the triangles'
 	// accept regions); the kernel walks them for a wave whose rays all start inside it, and every triangle otherwise
@@ -119,6 +142,9 @@ struct SkrSphereTree {
 	float ball[4] = {0.0f, 0.0f, 0.0f, -1.0f};
 };
 void skr_build_sphere_tree(const skr_scene &scene, SkrSphereTree &out);
+
+// The order finalize() stores the first nt triangles of raw_triangles in: along a Morton curve (scene_trees.cpp).
+std::vector<int> skr_triangle_order(const std::vector<float> &raw_triangles, int nt);
 
 // A spot-light row as the loader and skr_scene_set_spot_lights accept it (include/skr.h SKR_SCN_SPOT): every field finite, a direction
 // other than zero, 0 <= angle1 <= angle2 <= 180.

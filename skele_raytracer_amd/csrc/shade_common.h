@@ -262,7 +262,7 @@ SKR_DEV void best_resolve(const SceneView &sv, f3 o, f3 d, float four_a, BestSta
 	}
 }
 
-// The conservative line-sphere test of the culling data (scene_host.cpp build_triangle_chunks): false only where
+// The conservative line-sphere test of the culling data (scene_trees.cpp build_triangle_chunks): false only where
 // no triangle below the entry can accept this lane's line.  A = {centre, R^2}; B = {axis / kappa, R_tight^2}: a ray
 // that is not grazing for the entry's (nearly coplanar) triangles, (d . axis / kappa)^2 >= d . d, is held to the
 // tight radius.  NaN anywhere => true.
@@ -530,7 +530,7 @@ SKR_DEV int shape_lights(const SceneView &sv)
 	else return sv.nl;
 }
 
-// ---- the sphere tree (include/skr.h skr_scene_set_sphere_tree; scene_host.cpp skr_build_sphere_tree) ----
+// ---- the sphere tree (include/skr.h skr_scene_set_sphere_tree; scene_trees.cpp skr_build_sphere_tree) ----
 // The conservative line test of an entry {C, R^2} with its slack factor kappa: false only where no sphere below the entry can be a
 // candidate (binary32 D >= 0) of this lane's line.  The slack of D grows with the distance of the ray's origin, so it is a factor of
 // |C - o|^2 and not a part of the radius.  NaN anywhere => true.

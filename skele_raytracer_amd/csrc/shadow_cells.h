@@ -1,4 +1,4 @@
-// Shape of the per-light shadow masks, shared by the host builder (scene_host.cpp build_shadow_masks) and the device lookup
+// Shape of the per-light shadow masks, shared by the host builder (scene_masks.cpp build_shadow_masks) and the device lookup
 // (shade_common.h shadow_mask_of).  DESIGN.md "Shadow masks" has the derivation of the margins.
 #pragma once
 

@@ -5,7 +5,7 @@
 // cache (sphere_rows), the mesh rows likewise (mesh_row).
 //
 // Culling.  The renderer's chunk tree holds for rays that start at the camera or on a sphere.  Query rays start anywhere, so the
-// scene carries a second tree built for rays that start anywhere in a ball around the scene (scene_host.cpp trace_chunks), one set
+// scene carries a second tree built for rays that start anywhere in a ball around the scene (scene_trees.cpp trace_chunks), one set
 // per bound on |d| like the renderer's.  A wave whose live rays all start at the scene camera bit for bit walks the renderer's set
 // of the smallest bound above every lane's |d| (as a shading query's camera wave does); one whose live rays all start
 // inside the ball walks the trace tree's; any other wave tests every triangle.  Either way every lane gets the exact answer.

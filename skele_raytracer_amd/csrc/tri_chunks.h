@@ -1,8 +1,8 @@
-// Shape of the triangle culling hierarchy, shared by the host builder (scene_host.cpp
+// Shape of the triangle culling hierarchy, shared by the host builder (scene_trees.cpp
 // build_triangle_chunks) and the device walk (shade_common.h any_triangle_closer).
 #pragma once
 
-/* Consecutive (Morton-ordered) triangles per chunk sphere, chosen per scene by skr_scene::finalize(): scenes
+/* Consecutive (Morton-ordered) triangles per chunk sphere, chosen per scene by skr_scene::build_triangle_chunks(): scenes
  * without spheres only ever trace camera rays, whose 8x8-pixel waves are coherent and gain from small chunks
  * (dragon 1080p under the tree walk: 1.45 / 1.35 / 1.22 / 1.19 ms at 8 / 6 / 4 / 2); scenes with spheres also trace
  * GI children whose waves touch many chunks and pay for every extra sphere test (test.scn: 1.84 / 1.58 / 1.56 /

@@ -1,9 +1,120 @@
-// Host-code sanitizer run (CPU only): loader, finalize, culling builder, array getters, PPM writer.
+// Host-code sanitizer run (CPU only): loader, finalize, every table builder, the getters, PPM writer.  Prints one 64-bit digest
+// (FNV-1a over the 32-bit words) per derived table and scene, so that two builds of the host code can be compared table by table
+// (the digests depend on the host's libm: compare builds on one machine).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include <string>
 #include "skr.h"
+#include "../skele_raytracer_amd/csrc/tri_chunks.h" // SKR_CULL_LEVELS (plain #defines)
+
+// internal exports of the library (tests only: not in include/skr.h)
+extern "C" {
+int skr_scene_get_gi_surface(const skr_scene *scene, int32_t *n_words, int32_t *head_word, int32_t *first_row, uint32_t *table);
+int skr_scene_get_shadow_surface(const skr_scene *scene, int32_t *n_pairs, int32_t *stride, uint32_t *head, uint32_t *table);
+int skr_scene_rebuild_shadow_surface(skr_scene *scene, double rho_scale, double cone_scale);
+}
+
+namespace {
+
+struct Digest {
+	uint64_t h = 0xcbf29ce484222325ull;
+	template <class T> Digest &words(const T *p, size_t n)
+	{
+		static_assert(sizeof(T) == 4, "32-bit words");
+		for(size_t i = 0; i < n; i++)
+		{
+			uint32_t w;
+			memcpy(&w, p + i, 4);
+			for(int b = 0; b < 4; b++) h = (h ^ ((w >> (8 * b)) & 0xffu)) * 0x100000001b3ull;
+		}
+		return *this;
+	}
+	template <class T> Digest &word(T v) { return words(&v, 1); }
+};
+
+void print(const char *scene, const char *stage, const char *table, const Digest &d)
+{
+	printf("%s %s %s %016llx\n", scene, stage, table, (unsigned long long) d.h);
+}
+
+// the two direction-mask tables every light change rebuilds
+void shadow_tables(const skr_scene *sc, int n_spheres, const char *name, const char *stage)
+{
+	int32_t nl = 0, cells = 0;
+	float reach2 = 0;
+	skr_scene_get_shadow_masks(sc, &nl, &cells, &reach2, nullptr);
+	std::vector<uint32_t> masks((size_t) nl * 6 * cells * cells + 1);
+	skr_scene_get_shadow_masks(sc, nullptr, nullptr, nullptr, masks.data());
+	print(name, stage, "shadow_masks", Digest().word(nl).word(cells).word(reach2).words(masks.data(), masks.size() - 1));
+	int32_t np = 0, stride = 0;
+	skr_scene_get_shadow_surface(sc, &np, &stride, nullptr, nullptr);
+	std::vector<uint32_t> head((size_t) (stride ? n_spheres : 0) + 1), table((size_t) np * stride + 1);
+	skr_scene_get_shadow_surface(sc, nullptr, nullptr, head.data(), table.data());
+	print(name, stage, "shadow_surface", Digest().word(np).word(stride).words(head.data(), head.size() - 1).words(table.data(), table.size() - 1));
+}
+
+void gi_tables(const skr_scene *sc, const char *name)
+{
+	int32_t nw = 0, mw = 0, wide = 0, dc = 0, hw = 0, fr = 0;
+	float grids[16] = {0};
+	skr_scene_get_gi_masks(sc, &nw, &mw, &wide, &dc, grids, nullptr);
+	std::vector<uint32_t> table((size_t) nw + 1);
+	skr_scene_get_gi_masks(sc, nullptr, nullptr, nullptr, nullptr, nullptr, table.data());
+	print(name, "built", "gi_masks", Digest().word(nw).word(mw).word(wide).word(dc).words(grids, 16).words(table.data(), nw));
+	skr_scene_get_gi_surface(sc, &nw, &hw, &fr, nullptr);
+	table.assign((size_t) nw + 1, 0u);
+	skr_scene_get_gi_surface(sc, nullptr, nullptr, nullptr, table.data());
+	print(name, "built", "gi_surface", Digest().word(nw).word(hw).word(fr).words(table.data(), nw));
+}
+
+void culling_tables(const skr_scene *sc, int n_triangles, const char *name)
+{
+	for(int trace = 0; trace < 2; trace++)
+		for(int level = 0; level < SKR_CULL_LEVELS; level++)
+		{
+			int32_t cs = 0, nn = 0, nc = 0;
+			float ball[4] = {0, 0, 0, 0};
+			if(trace) skr_scene_get_trace_culling(sc, level, &cs, &nn, &nc, nullptr, nullptr, nullptr, nullptr, ball);
+			else skr_scene_get_culling(sc, level, &cs, &nn, &nc, nullptr, nullptr, nullptr, nullptr);
+			std::vector<float> dt((size_t) n_triangles * 12 + 1), ns((size_t) nn * 8 + 1), ch((size_t) nc * 8 + 1);
+			std::vector<int32_t> nl((size_t) nn * 4 + 1);
+			if(trace) skr_scene_get_trace_culling(sc, level, nullptr, nullptr, nullptr, dt.data(), ns.data(), nl.data(), ch.data(), nullptr);
+			else skr_scene_get_culling(sc, level, nullptr, nullptr, nullptr, dt.data(), ns.data(), nl.data(), ch.data());
+			Digest d;
+			d.word(cs).word(nn).word(nc).words(ball, 4).words(dt.data(), dt.size() - 1).words(ns.data(), ns.size() - 1);
+			d.words(nl.data(), nl.size() - 1).words(ch.data(), ch.size() - 1);
+			const std::string table = std::string(trace ? "trace_culling" : "culling") + "[" + std::to_string(level) + "]";
+			print(name, "built", table.c_str(), d);
+		}
+}
+
+void sphere_tree_table(const skr_scene *sc, int n_spheres, const char *name)
+{
+	int32_t cs = 0, nn = 0, nc = 0, na = 0;
+	float ball[4] = {0, 0, 0, 0};
+	skr_scene_get_sphere_tree_data(sc, &cs, &nn, &nc, &na, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ball);
+	std::vector<float> rows((size_t) n_spheres * 4 + 1), nsph((size_t) nn * 5 + 1), csph((size_t) nc * 5 + 1);
+	std::vector<int32_t> file((size_t) n_spheres + 1), nlink((size_t) nn * 4 + 1), clink((size_t) nc * 3 + 1);
+	skr_scene_get_sphere_tree_data(sc, nullptr, nullptr, nullptr, nullptr, rows.data(), file.data(), nsph.data(), nlink.data(), csph.data(), clink.data(), nullptr);
+	Digest d;
+	d.word(cs).word(nn).word(nc).word(na).words(ball, 4).words(rows.data(), rows.size() - 1).words(file.data(), file.size() - 1);
+	d.words(nsph.data(), nsph.size() - 1).words(nlink.data(), nlink.size() - 1).words(csph.data(), csph.size() - 1).words(clink.data(), clink.size() - 1);
+	print(name, "built", "sphere_tree_data", d);
+}
+
+void spot_cones_table(const skr_scene *sc, const char *name, const char *stage)
+{
+	int32_t n = 0;
+	skr_scene_get_spot_lights(sc, nullptr, &n);
+	std::vector<float> cones((size_t) n * 5 + 1);
+	skr_scene_get_spot_cones(sc, cones.data());
+	print(name, stage, "spot_cones", Digest().word(n).words(cones.data(), cones.size() - 1));
+}
+
+} // namespace
+
 int main(int argc, char **argv)
 {
 	for(int a = 1; a < argc; a++)
@@ -15,15 +126,23 @@ int main(int argc, char **argv)
 		skr_scene_get_info(sc, &info);
 		std::vector<float> s((size_t) info.n_spheres * 14 + 1), t((size_t) info.n_triangles * 9 + 1), l((size_t) info.n_point_lights * 6 + 1);
 		skr_scene_get_arrays(sc, s.data(), t.data(), l.data());
-		for(int level = 0; level < 3; level++)
-		{
-			int32_t cs = 0, nn = 0, nc = 0;
-			skr_scene_get_culling(sc, level, &cs, &nn, &nc, nullptr, nullptr, nullptr, nullptr);
-			std::vector<float> dt((size_t) info.n_triangles * 12 + 1), ns((size_t) nn * 8 + 1), ch((size_t) nc * 8 + 1);
-			std::vector<int32_t> nl((size_t) nn * 4 + 1);
-			skr_scene_get_culling(sc, level, nullptr, nullptr, nullptr, dt.data(), ns.data(), nl.data(), ch.data());
-		}
 		printf("%s: %d spheres %d triangles %d lights ok\n", argv[a], info.n_spheres, info.n_triangles, info.n_point_lights);
+		shadow_tables(sc, info.n_spheres, argv[a], "built");
+		gi_tables(sc, argv[a]);
+		culling_tables(sc, info.n_triangles, argv[a]);
+		sphere_tree_table(sc, info.n_spheres, argv[a]);
+		spot_cones_table(sc, argv[a], "built");
+		// the rebuild paths: new lights, then the tests' shrunk margins
+		const float spots[2][11] = {{1.0f, 0.9f, 0.8f, 0.5f, 3.0f, 1.5f, 0.1f, -1.0f, -0.2f, 20.0f, 35.0f},
+									{0.3f, 0.4f, 2.0f, -2.0f, 1.0f, -3.0f, 1.0f, 0.5f, 1.0f, 0.0f, 90.0f}};
+		rc = skr_scene_set_spot_lights(sc, &spots[0][0], 2);
+		if(rc != 0) printf("%s: skr_scene_set_spot_lights rc %d (%s)\n", argv[a], rc, skr_last_error());
+		shadow_tables(sc, info.n_spheres, argv[a], "spots");
+		spot_cones_table(sc, argv[a], "spots");
+		skr_scene_rebuild_shadow_surface(sc, 0.5, 1.0);
+		shadow_tables(sc, info.n_spheres, argv[a], "rho/2");
+		skr_scene_rebuild_shadow_surface(sc, 1.0, 0.5);
+		shadow_tables(sc, info.n_spheres, argv[a], "cone/2");
 		skr_scene_destroy(sc);
 	}
 	std::vector<uint8_t> px(7 * 5 * 3, 200);
