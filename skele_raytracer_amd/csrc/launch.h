@@ -21,6 +21,7 @@ enum { SKR_PIX_NONE = 0, SKR_PIX_NODE, SKR_PIX_BACKGROUND, SKR_PIX_TRIANGLE }; /
 // The plan of one band of the node pipeline (render_nodes.hip): table sizes for the worst case, every pixel a node, every child a hit.
 constexpr int SKR_NODE_LEVELS_MAX = 33;
 struct NodePlan {
+	bool wide = false;       // the launch's hit records are 32 bytes and carry their ray (SKR_WIDE_RECORDS below)
 	bool flat = false;       // the flat schedule (render_nodes.hip nodes_flat_wanted): the leaves' hits are a record level of their own
 	int levels = 0;          // node / record levels 0 .. max_depth - 2 (flat: .. max_depth - 1)
 	uint32_t band_nblk = 0;  // 16x16 pixel blocks per band
@@ -167,6 +168,19 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 #ifndef SKR_TRACE_RUN
 #define SKR_TRACE_RUN 2 // sibling pairs a trace wave runs over before it takes its next block of nodes (0 = all PP of them); measured at PP, 4 and 2: DESIGN.md 5.2
 #endif
+// A hit record of the node pipeline.  SKR_WIDE_RECORDS 1: 32 bytes, {parent, sphere | child << 16, r1, D} {d.xyz, b} — the record carries
+// the ray that found the hit and its b, D of utils.h:116-118 for the sphere it hit, as the trace kernel's walk held them, and whoever
+// shades the hit (render_nodes.hip activate_record) forms neither again.  0 (A/B builds): 16 bytes, {parent, sphere | child << 16, r1, r2},
+// the ray formed again from its two draws.  Which form a launch's records have is the plan's decision (NodePlan::wide; render_nodes.hip
+// plan_bands): the wide one, except where not even one 16x16 block's tables fit the scratch budget with it — such a launch runs the
+// instances with 16-byte records, as it did before there were wide ones, and is not refused.  The kernels are compiled for either form
+// (template <bool WIDE>) and index the table in rows of skr_rec_rows(WIDE) float4; the plan sizes it with skr_records_bytes: the record
+// size is stated here alone.
+#ifndef SKR_WIDE_RECORDS
+#define SKR_WIDE_RECORDS 1
+#endif
+__host__ __device__ constexpr int skr_rec_rows(bool wide) { return wide ? 2 : 1; } // float4 per hit record
+static inline size_t skr_records_bytes(uint64_t records, bool wide) { return (size_t) records * (size_t) skr_rec_rows(wide) * 16; }
 __host__ __device__ static inline uint64_t skr_trace_header_row(uint64_t node, uint32_t j, uint32_t PP)
 {
 	return SKR_TRACE_BY_NODE ? (node >> 6) * PP + j : (node * PP + j) >> 6;

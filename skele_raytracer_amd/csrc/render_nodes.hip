@@ -11,8 +11,9 @@
 //                        Philox call, one (e, c) per sphere for both); per wave and round one 48-byte header — the first record
 //                        of its hits and the ballots of the nodes whose children hit: finalize finds a child's record from the
 //                        population count of the ballot below its node, and draws r1 of a miss again from the same Philox
-//                        counter — and per sphere hit a 16-byte record (parent, sphere, child, the two draws) appended to one
-//                        of 64 regions (ballot ranks + one atomic per wave).  The grid is
+//                        counter — and per sphere hit a 32-byte record (parent, sphere, child, r1, and the ray with its b, D
+//                        for that sphere: launch.h SKR_WIDE_RECORDS) appended to one of 64 regions (ballot ranks + one atomic
+//                        per wave).  The grid is
 //                        capped; a workgroup strides over the groups of four work items.
 //   skr_activate_kernel  (depth >= 4, and the flat schedule) one lane per record: shades the hit (:194-207) and writes it as a
 //                        node of the next level, which the trace kernel then expands; forms the level's prefix sums itself
@@ -110,7 +111,7 @@ SKR_DEV bool classify_child(const SceneView &sv, f3 co, f3 d, float two_a, float
 // One round of a trace lane: children 2j, 2j + 1 of its node (origin co, normal Nn, tangent nt, bitangent nb) are traced, and the wave's
 // hits are appended to the region of its header row `chunk`, which then says what became of the 64 lanes' children.
 // GIM: GI masks (sphere-only scenes, p.gi_index set; wave_common.h closest_pair); the kernels without them are compiled without the walk
-template <bool TRIS, bool GIM>
+template <bool TRIS, bool GIM, bool WIDE>
 SKR_DEV void trace_round(const SceneView &sv, const RenderParams &p, bool valid, uint32_t node, uint32_t j, f3 co, f3 Nn, f3 nt, f3 nb, uint32_t pixel,
 						 uint32_t node_id, int gi_row, uint32_t chunk, int lane, Counters &cn)
 {
@@ -118,6 +119,8 @@ SKR_DEV void trace_round(const SceneView &sv, const RenderParams &p, bool valid,
 	const bool second = valid && 2u * j + 1u < N;
 	bool hit0 = false, hit1 = false;
 	float4 rec0 = make_float4(0, 0, 0, 0), rec1 = rec0;
+	float4 ray0 = rec0, ray1 = rec0; // (WIDE)
+	constexpr int ROWS = skr_rec_rows(WIDE);
 	bool black0 = false, black1 = false;
 	if(valid)
 	{
@@ -131,11 +134,15 @@ SKR_DEV void trace_round(const SceneView &sv, const RenderParams &p, bool valid,
 		BestState s0, s1;
 		closest_pair<GIM>(sv, p, gi_row, co, d0, d1, second, rp, s0, s1);
 		hit0 = classify_child(sv, co, d0, rp.two_a.x, rp.four_a.x, s0, black0);
-		rec0 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s0.best & 0xffff) | ((2u * j) << 16)), q1a, q2a);
+		// a record (launch.h SKR_WIDE_RECORDS): {parent, sphere | child << 16, r1, D} {d, b} — the winner's b, D of utils.h:116-118 as the walk
+		// formed them (device_math.h pair_bD, or shade_common.h best_resolve after an overlap), for whoever shades the hit
+		rec0 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s0.best & 0xffff) | ((2u * j) << 16)), q1a, WIDE ? s0.D : q2a);
+		if(WIDE) ray0 = make_float4(d0.x, d0.y, d0.z, s0.b);
 		if(second)
 		{
 			hit1 = classify_child(sv, co, d1, rp.two_a.y, rp.four_a.y, s1, black1);
-			rec1 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s1.best & 0xffff) | ((2u * j + 1u) << 16)), q1b, q2b);
+			rec1 = make_float4(__uint_as_float(node), __uint_as_float((uint32_t) (s1.best & 0xffff) | ((2u * j + 1u) << 16)), q1b, WIDE ? s1.D : q2b);
+			if(WIDE) ray1 = make_float4(d1.x, d1.y, d1.z, s1.b);
 		}
 	}
 	// append the wave's hits to its region: rank by ballot, one atomic per wave
@@ -150,8 +157,16 @@ SKR_DEV void trace_round(const SceneView &sv, const RenderParams &p, bool valid,
 	}
 	const uint32_t rec_base = region * p.rc_cap + base; // the even children's hits first, then the odd ones
 	const uint32_t rank0 = (uint32_t) lanes_below(m0), rank1 = (uint32_t) lanes_below(m1);
-	if(hit0) p.rc[rec_base + rank0] = rec0;
-	if(hit1) p.rc[rec_base + n0h + rank1] = rec1;
+	if(hit0)
+	{
+		p.rc[(size_t) (rec_base + rank0) * ROWS] = rec0;
+		if(WIDE) p.rc[(size_t) (rec_base + rank0) * ROWS + 1] = ray0;
+	}
+	if(hit1)
+	{
+		p.rc[(size_t) (rec_base + n0h + rank1) * ROWS] = rec1;
+		if(WIDE) p.rc[(size_t) (rec_base + n0h + rank1) * ROWS + 1] = ray1;
+	}
 	if(TRIS)
 	{
 		const unsigned long long k0 = __ballot(black0), k1 = __ballot(black1);
@@ -172,7 +187,7 @@ __host__ __device__ static inline uint32_t trace_runs_per_block(uint32_t PP) { r
 // A work item is a block of 64 consecutive nodes, one per lane, and a run of their sibling pairs [j0, j1): what belongs to the node — its
 // row, its row of GI masks, its tangent (utils.h:148-163: a square root and three divisions on either arm) — is formed once per item, and
 // no lane divides a pair index by PP.  A workgroup takes every gridDim.x-th group of four items, a wave one of them.
-template <bool TRIS, bool GIM>
+template <bool TRIS, bool GIM, bool WIDE>
 __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -234,13 +249,13 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 			}
 			const f3 nb = cross3(Nn, nt); // (utils.h:164, as tangent_basis forms it)
 			const uint32_t chunk = (node >> 6) * (((uint32_t) p.num_path_traces + 1u) >> 1) + j;
-			trace_round<TRIS, GIM>(sv, p, valid, node, j, co, Nn, nt, nb, pixel, node_id, gi_row, (uint32_t) uni((int) chunk), lane, cn);
+			trace_round<TRIS, GIM, WIDE>(sv, p, valid, node, j, co, Nn, nt, nb, pixel, node_id, gi_row, (uint32_t) uni((int) chunk), lane, cn);
 		}
 	}
 	add_counters(launch_args(), cn, (uint32_t) blockIdx.x * 4u + wave, lane);
 }
 #else
-template <bool TRIS, bool GIM>
+template <bool TRIS, bool GIM, bool WIDE>
 __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const RenderParams)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -276,7 +291,7 @@ __global__ __launch_bounds__(256) SKR_TRACE_ATTR void skr_trace_kernel(const Ren
 		tangent_basis(Nn, nt, nb);
 		if(GIM) gi_row = p.gi_row0 ? p.gi_row0[node] : gi_origin_row(p, co);
 	}
-	trace_round<TRIS, GIM>(sv, p, valid, node, j, co, Nn, nt, nb, pixel, node_id, gi_row, chunk, lane, cn);
+	trace_round<TRIS, GIM, WIDE>(sv, p, valid, node, j, co, Nn, nt, nb, pixel, node_id, gi_row, chunk, lane, cn);
 	}
 	add_counters(launch_args(), cn, (uint32_t) blockIdx.x * 4u + (uint32_t) (tid >> 6), lane);
 }
@@ -293,7 +308,8 @@ struct Activated {
 };
 
 // SH: the facts of the launch that are compiled in (shade_common.h; RunTimeShape: none)
-template <typename SH = RunTimeShape>
+// WIDE: the records carry their ray (launch.h SKR_WIDE_RECORDS)
+template <bool WIDE, typename SH = RunTimeShape>
 SKR_DEV Activated activate_record(const SceneView &sv, const RenderParams &p, bool act, uint32_t rec, Counters &cn)
 {
 	Activated a;
@@ -304,28 +320,47 @@ SKR_DEV Activated activate_record(const SceneView &sv, const RenderParams &p, bo
 	if(act)
 	{
 		typedef float v4f __attribute__((ext_vector_type(4)));
-		const v4f n0 = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p.rc + rec)); // streamed once
+		const v4f n0 = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p.rc + (size_t) rec * skr_rec_rows(WIDE))); // streamed once
 		const uint32_t parent = __float_as_uint(n0.x), sc = __float_as_uint(n0.y);
 		a.r1 = n0.z;
 		a.sph = sc & 0xffffu;
 		a.child = sc >> 16;
 		const float4 *row = p.nd_src + (size_t) parent * 2; // (one aligned 32-byte sector per parent)
 		const float4 p0 = row[0], p1 = row[1];
-		const f3 co0 = mk3(p0.x, p0.y, p0.z), N0 = mk3(p0.w, p1.x, p1.y);
+		const f3 co0 = mk3(p0.x, p0.y, p0.z);
 		a.pixel = __float_as_uint(p1.z);
 		const uint32_t pnode = __float_as_uint(p1.w); // (0 at level 0)
 		a.node_id = pnode * (uint32_t) p.num_path_traces + a.child + 1u; // DESIGN.md "RNG": child c of node n
+		f3 d;
+		float b, D, aa;
+		if(WIDE)
+		{
+		// The ray that found this hit and its b, D of utils.h:116-118 for the sphere it hit, as the trace kernel's walk held them when it
+		// wrote the record (trace_round).  They are the values the narrow form below forms again from the record's two draws, bit for bit:
+		// d came from the same gi_direction_pair on the same draws and basis; b = 2 ((dx ex + dy ey) + dz ez) and D = b b - (4 a) c are
+		// the operations of the narrow form on the same operands, in the walk's packed halves (v_pk_mul_f32 / v_pk_add_f32 round
+		// each half like the scalar instruction, device_math.h RayPair) or, after an overlap, in best_resolve's scalar form, which is
+		// that text.
+		const v4f n1 = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p.rc + (size_t) rec * skr_rec_rows(WIDE) + 1));
+		d = mk3(n1.x, n1.y, n1.z);
+		b = n1.w;
+		D = n0.w;
+		aa = dot3(d, d);
+		}
+		else
+		{
 		// The ray that found this hit, formed again from its two draws exactly as the trace kernel formed it (raytrace.h:119-125:
-		// same operations on the same values, so the same direction), and utils.h:115-118 for the sphere it hit: 16 bytes per
-		// record instead of 32
+		// same operations on the same values, so the same direction), and utils.h:115-118 for the sphere it hit
+		const f3 N0 = mk3(p0.w, p1.x, p1.y);
 		f3 nt0, nb0;
 		tangent_basis(N0, nt0, nb0);
-		const f3 d = gi_direction(a.r1, n0.w, N0, nt0, nb0);
+		d = gi_direction(a.r1, n0.w, N0, nt0, nb0);
 		const float4 g = sv.geom[a.sph];
 		const f3 ec = co0 - ld3(g);
-		const float aa = dot3(d, d);
-		const float b = 2 * dot3(d, ec);
-		const float D = b * b - (4 * aa) * (dot3(ec, ec) - g.w);
+		aa = dot3(d, d);
+		b = 2 * dot3(d, ec);
+		D = b * b - (4 * aa) * (dot3(ec, ec) - g.w);
+		}
 		const float two_a = 2 * aa;
 		const float t = near_root(two_a, b, D);
 		const f3 P = co0 + d * t;
@@ -345,7 +380,7 @@ SKR_DEV Activated activate_record(const SceneView &sv, const RenderParams &p, bo
 #else
 #define SKR_SHADE_ATTR
 #endif
-template <bool TRIS>
+template <bool TRIS, bool WIDE>
 __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_activate_kernel(const RenderParams p)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
 	extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -362,7 +397,7 @@ __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_activate_kernel(const 
 	const bool act = pos < cnt;
 	const uint32_t rec = region * p.rc_cap + pos;
 	Counters cn{0, 0, 0};
-	const Activated a = activate_record(sv, p, act, rec, cn);
+	const Activated a = activate_record<WIDE>(sv, p, act, rec, cn);
 	if(act)
 	{
 		const size_t n = (size_t) (s_pre[region] + pos);
@@ -379,7 +414,7 @@ __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_activate_kernel(const 
 // == 0, raytrace.h:142-145): raytrace.h:194-213 with indirect = (0,0,0)/N, then the parent's accumulation term (:130) — the
 // arithmetic of leaf_batch() below, on records instead of ring entries.  Dense numbering through the level's prefix sums
 // (region_prefix): position i belongs to the region whose prefix range holds it.
-template <bool TRIS>
+template <bool TRIS, bool WIDE>
 __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_shade_leaf_kernel(const RenderParams p)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -402,7 +437,7 @@ __global__ __launch_bounds__(256) SKR_SHADE_ATTR void skr_shade_leaf_kernel(cons
 			else hi = mid;
 		}
 		const uint32_t rec = lo * p.rc_cap + ((act ? i : 0u) - prefix[lo]);
-		const Activated a = activate_record(sv, p, act, rec, cn);
+		const Activated a = activate_record<WIDE>(sv, p, act, rec, cn);
 		if(act)
 		{
 			const f3 tot = mk3(0, 0, 0); // (0,0,0) / N with N >= 1 (skr_nodes_plan): +0 in every component, no division needed
@@ -534,7 +569,8 @@ extern "C" void skr_leaf2_times_read(unsigned long long *out)
 // SHAPE: none, or the one launch shape the instance is compiled for (shade_common.h PointLightShape; the launcher picks it only for a
 // launch that has it, launch.h skr_leaf_shape): the facts it fixes are constants of the shading and tracing code below, which then
 // holds no scalar for them and has neither the light loop nor the branches on them
-template <bool TRIS, bool FIRST, bool GIM, typename... SHAPE>
+// WIDE: the unit's records carry their ray (launch.h SKR_WIDE_RECORDS; FIRST has no records: its instances are the <.., false, ..> ones)
+template <bool TRIS, bool FIRST, bool GIM, bool WIDE, typename... SHAPE>
 __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const RenderParams p)
 {
 	typedef typename ShapeOf<SHAPE...>::type SH;
@@ -635,7 +671,7 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 		else
 		{
 			out_idx = region * p.rc_cap + first + (uint32_t) lane;
-			const Activated a = activate_record<SH>(sv, p, act0, out_idx, cn);
+			const Activated a = activate_record<WIDE, SH>(sv, p, act0, out_idx, cn);
 			co = a.co;
 			Nn = a.N;
 			direct1 = a.direct;
@@ -757,7 +793,7 @@ __global__ __launch_bounds__(256, SKR_LEAF2_OCC) void skr_leaf_kernel2(const Ren
 			else
 			{
 				direct = direct1;
-				const float4 r1row = p.rc[out_idx]; // (asked for here, behind the window sums: asking earlier was measured and changes nothing, 1.570 / 1.569 ms)
+				const float4 r1row = p.rc[(size_t) out_idx * skr_rec_rows(WIDE)]; // (asked for here, behind the window sums: asking earlier was measured and changes nothing, 1.570 / 1.569 ms)
 				r1 = r1row.z;
 				sph = __float_as_uint(r1row.y) & 0xffffu;
 			}
@@ -909,8 +945,9 @@ static bool nodes_flat_wanted(const RenderParams &p)
 	return recs < SKR_FLAT_BELOW;
 }
 
-static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, NodePlan &pl)
+static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, bool wide, NodePlan &pl)
 {
+	pl.wide = wide;
 	const uint64_t N = (uint64_t) p.num_path_traces, PP = (N + 1) >> 1;
 	pl.flat = flat;
 	pl.levels = p.max_depth - 1 + (flat ? 1 : 0);
@@ -933,7 +970,7 @@ static bool plan_for(const RenderParams &p, uint32_t nblk, bool flat, NodePlan &
 		const size_t n = (size_t) pl.nodes_max[L];
 		if(L > 0)
 		{
-			pl.off_recs[L] = s.take(n * 16);
+			pl.off_recs[L] = s.take(skr_records_bytes(n, wide));
 			pl.off_res[L] = s.take(n * 12 + 16);
 		}
 		if(L < pl.levels - 1 || pl.levels == 1)
@@ -983,15 +1020,50 @@ static uint64_t nodes_budget(const RenderParams &p, bool flat)
 	return p.sw.budget_mb ? (uint64_t) p.sw.budget_mb << 20 : (flat ? 8ull : 4ull) << 30;
 }
 
-// the largest band (in 16x16 pixel blocks) whose worst-case tables fit the budget; false: not even one block does
+static bool plan_bands(const RenderParams &p, bool flat, NodePlan &pl);
+// Internal (tests only; no device involved): the plan of a width x rows launch with N children per node to `depth`, on the flat schedule
+// or the persistent one — nblk > 0: plan_for that band of 16x16 blocks, with wide records; nblk == 0: the band and the record form
+// plan_bands picks under budget_mb (0: the default budget).  out[0..15] = {levels, band_nblk, total, banded, off_ctr, ctr_bytes, off_cls, off_sums, off_girow, bytes per
+// hit record, 0 ...}; then 8 words per level L at out[16 + 8 L] = {nodes_max, cap, off_nodes, off_shade,
+// off_recs, off_res, off_ixh, bytes of its record table}.  out holds 16 + 8 * 33 words.  Returns 1, or 0 where there is no such plan.
+extern "C" int skr_nodes_plan_map(int32_t width, uint32_t rows, int32_t N, int32_t depth, int32_t flat, int32_t budget_mb, uint32_t nblk, uint64_t *out)
+{
+	RenderParams p{};
+	p.width = width;
+	p.out_rows = rows;
+	p.num_path_traces = N;
+	p.max_depth = depth;
+	p.sw.budget_mb = budget_mb;
+	NodePlan pl;
+	if(!(nblk ? plan_for(p, nblk, flat != 0, true, pl) : plan_bands(p, flat != 0, pl))) return 0;
+	const uint64_t head[16] = {(uint64_t) pl.levels, pl.band_nblk, pl.total, pl.banded, pl.off_ctr, pl.ctr_bytes, pl.off_cls, pl.off_sums,
+							   pl.off_girow, skr_records_bytes(1, pl.wide), 0, 0, 0, 0, 0, 0};
+	memcpy(out, head, sizeof head);
+	for(int L = 0; L < SKR_NODE_LEVELS_MAX; L++)
+	{
+		const uint64_t row[8] = {pl.nodes_max[L], pl.cap[L], pl.off_nodes[L], pl.off_shade[L], pl.off_recs[L], pl.off_res[L], pl.off_ixh[L],
+								 L < pl.levels ? skr_records_bytes(pl.nodes_max[L], pl.wide) : 0};
+		memcpy(out + 16 + 8 * L, row, sizeof row);
+	}
+	return 1;
+}
+
+// the largest band (in 16x16 pixel blocks) whose worst-case tables fit the budget; false: not even one block does.  The records are the
+// wide ones (launch.h SKR_WIDE_RECORDS) wherever a block's tables fit with them — at the price of more bands than 16-byte records
+// would take —; a launch of which not even one block does is planned with 16-byte records, as it was before there were wide ones:
+// no launch is refused that was not refused then.
 static bool plan_bands(const RenderParams &p, bool flat, NodePlan &pl)
 {
 	const uint32_t bx = (uint32_t) (p.width + 15) / 16, by = (p.out_rows + 15) / 16;
 	const uint64_t budget = nodes_budget(p, flat);
-	uint32_t nblk = skr_largest_band(bx * by, [&](uint32_t n) { return plan_for(p, n, flat, pl) && pl.banded <= budget; });
-	if(nblk == 0) return false;
-	if(nblk > bx) nblk = nblk / bx * bx; // whole block rows where possible
-	return plan_for(p, nblk, flat, pl);
+	for(int wide = SKR_WIDE_RECORDS ? 1 : 0; wide >= 0; wide--)
+	{
+		uint32_t nblk = skr_largest_band(bx * by, [&](uint32_t n) { return plan_for(p, n, flat, wide != 0, pl) && pl.banded <= budget; });
+		if(nblk == 0) continue;
+		if(nblk > bx) nblk = nblk / bx * bx; // whole block rows where possible
+		return plan_for(p, nblk, flat, wide != 0, pl);
+	}
+	return false;
 }
 
 // The node pipeline covers --gillum trees of any depth >= 2 on sphere scenes (<= 256 children per node, < 65536 spheres) whose tables
@@ -1042,23 +1114,26 @@ hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level,
 typedef void (*LeafKernel)(const RenderParams);
 // The leaf kernel's instance for a launch.  The instances with a compiled-in shape exist for sphere-only scenes with GI masks, one per
 // shape of skr_leaf_shape (launch.h), which alone decides whether a launch has one.
-template <bool FIRST>
+template <bool FIRST, bool WIDE>
 static LeafKernel leaf_instance(const RenderParams &p)
 { // (GI masks exist for sphere-only scenes alone: scene_masks.cpp build_gi_masks)
 	switch(skr_leaf_shape(p))
 	{
-	case SKR_LEAF_POINT2: return skr_leaf_kernel2<false, FIRST, true, PointLightShape<2>>;
-	case SKR_LEAF_POINT1: return skr_leaf_kernel2<false, FIRST, true, PointLightShape<1>>;
+	case SKR_LEAF_POINT2: return skr_leaf_kernel2<false, FIRST, true, WIDE, PointLightShape<2>>;
+	case SKR_LEAF_POINT1: return skr_leaf_kernel2<false, FIRST, true, WIDE, PointLightShape<1>>;
 	default: break;
 	}
-	if(p.n_tris > 0) return skr_leaf_kernel2<true, FIRST, false>;
-	return p.gi_index != nullptr ? skr_leaf_kernel2<false, FIRST, true> : skr_leaf_kernel2<false, FIRST, false>;
+	if(p.n_tris > 0) return skr_leaf_kernel2<true, FIRST, false, WIDE>;
+	return p.gi_index != nullptr ? skr_leaf_kernel2<false, FIRST, true, WIDE> : skr_leaf_kernel2<false, FIRST, false, WIDE>;
 }
 
+// wide: the plan's record form (NodePlan::wide); the depth-2 instances (FIRST) read no record
 template <bool FIRST>
-static hipError_t launch_leaf2(const RenderParams &p, size_t lds, hipStream_t stream)
+static hipError_t launch_leaf2(const RenderParams &p, bool wide, size_t lds, hipStream_t stream)
 {
-	const LeafKernel fn = leaf_instance<FIRST>(p);
+	LeafKernel fn;
+	if constexpr(FIRST) fn = leaf_instance<true, false>(p);
+	else fn = wide ? leaf_instance<false, true>(p) : leaf_instance<false, false>(p);
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
 	if(e != hipSuccess) return e;
 	hipLaunchKernelGGL(fn, dim3(LEAF2_GRID), dim3(256), lds, stream, p);
@@ -1117,7 +1192,7 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStr
 				p.nd_count = ctr0;
 				p.rc_ctr = lvl_ctr(0);
 				if(timed) skr_hook_start(hook, stream);
-				e = launch_leaf2<true>(p, pl.lds_leaf, stream);
+				e = launch_leaf2<true>(p, pl.wide, pl.lds_leaf, stream);
 				if(timed) skr_hook_stop(hook, stream);
 				if(e != hipSuccess) return e;
 				continue;
@@ -1140,16 +1215,18 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStr
 #endif
 				const unsigned grid_t = (unsigned) (wg_t < SKR_TRACE_GRID_MAX ? wg_t : SKR_TRACE_GRID_MAX);
 				if(flat && L == last && timed) skr_hook_start(hook, stream); // (flat: the last level's trace + shading are the dominant pair)
-				if(tris) hipLaunchKernelGGL((skr_trace_kernel<true, false>), dim3(grid_t), dim3(256), lds_scene, stream, p);
-				else if(p.gi_index) hipLaunchKernelGGL((skr_trace_kernel<false, true>), dim3(grid_t), dim3(256), lds_scene, stream, p);
-				else hipLaunchKernelGGL((skr_trace_kernel<false, false>), dim3(grid_t), dim3(256), lds_scene, stream, p);
+				const LeafKernel trace = tris       ? (pl.wide ? skr_trace_kernel<true, false, true> : skr_trace_kernel<true, false, false>)
+										 : p.gi_index ? (pl.wide ? skr_trace_kernel<false, true, true> : skr_trace_kernel<false, true, false>)
+													  : (pl.wide ? skr_trace_kernel<false, false, true> : skr_trace_kernel<false, false, false>);
+				hipLaunchKernelGGL(trace, dim3(grid_t), dim3(256), lds_scene, stream, p);
 				if(L < last)
 				{ // its records become the nodes of level L
 					p.nd_dst = nodes(L);
 					p.ns_dst = shade(L);
 					const unsigned grid_a = SKR_P1_REGIONS * ((pl.cap[L] + 255u) / 256u);
-					if(tris) hipLaunchKernelGGL(skr_activate_kernel<true>, dim3(grid_a), dim3(256), lds_scene, stream, p);
-					else hipLaunchKernelGGL(skr_activate_kernel<false>, dim3(grid_a), dim3(256), lds_scene, stream, p);
+					const LeafKernel activate = tris ? (pl.wide ? skr_activate_kernel<true, true> : skr_activate_kernel<true, false>)
+													 : (pl.wide ? skr_activate_kernel<false, true> : skr_activate_kernel<false, false>);
+					hipLaunchKernelGGL(activate, dim3(grid_a), dim3(256), lds_scene, stream, p);
 				}
 			}
 			p.res_out = reinterpret_cast<float *>(base + pl.off_res[last]);
@@ -1157,14 +1234,15 @@ hipError_t skr_launch_nodes(const RenderParams &p_in, const NodePlan &pl, hipStr
 			{ // the records of the last level are the leaves' hits: shaded one per lane, results into res[last]
 				const uint64_t wg = (pl.nodes_max[last] + 255) / 256;
 				const unsigned grid_s = (unsigned) (wg < 16384 ? wg : 16384);
-				if(tris) hipLaunchKernelGGL(skr_shade_leaf_kernel<true>, dim3(grid_s), dim3(256), lds_scene, stream, p);
-				else hipLaunchKernelGGL(skr_shade_leaf_kernel<false>, dim3(grid_s), dim3(256), lds_scene, stream, p);
+				const LeafKernel shade_leaf = tris ? (pl.wide ? skr_shade_leaf_kernel<true, true> : skr_shade_leaf_kernel<true, false>)
+												   : (pl.wide ? skr_shade_leaf_kernel<false, true> : skr_shade_leaf_kernel<false, false>);
+				hipLaunchKernelGGL(shade_leaf, dim3(grid_s), dim3(256), lds_scene, stream, p);
 				if(timed) skr_hook_stop(hook, stream);
 			}
 			else
 			{ // leaf kernel: the records of the last level (their parents: level last - 1), results into res[last]
 				if(timed) skr_hook_start(hook, stream);
-				e = launch_leaf2<false>(p, pl.lds_leaf, stream);
+				e = launch_leaf2<false>(p, pl.wide, pl.lds_leaf, stream);
 				if(timed) skr_hook_stop(hook, stream);
 				if(e != hipSuccess) return e;
 			}

@@ -95,7 +95,7 @@ struct RenderParams {
 	uint32_t nd_src_level0;   // nd_src / ns_src hold the primary hits
 	uint32_t shadow_surface_stride; // (see shadow_surface_word)
 	const uint32_t *nd_count; // number of nodes in nd_src
-	float4 *rc;               // hit records of the level being produced (trace) or consumed (activate, leaf): [parent, sphere | child << 16, r1, r2]
+	float4 *rc;               // hit records of the level being produced (trace) or consumed (activate, leaf): SKR_REC_ROWS float4 each (launch.h): [parent, sphere | child << 16, r1, D] [d.xyz, b]
 	uint32_t rc_cap;          // records per region (SKR_P1_REGIONS regions)
 	uint32_t *rc_ctr;         // that level's counters: [STRIDE r] records in region r, [STRIDE (64 + r)] units handed out, [STRIDE 128] exhausted mask, [STRIDE 129 ..] prefix sums
 	uint4 *ixh;               // per trace wave and round (64 consecutive nd_src nodes, sibling pair j of each: row (node >> 6) * PP + j, launch.h skr_trace_header_row) three uint4: {first record of its hits, how many of them are even children's, -, -}, the ballots of the even / odd children that hit (64 bits each), the ballots of the children a triangle took (triangle scenes)
