@@ -11,8 +11,8 @@ LIBDIR  := skele_raytracer_amd/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
             -fno-fast-math -Wall -Wno-unused-function -Wno-pass-failed -Iinclude
 KERNEL_SRCS := $(CSRC)/render_kernel.hip $(CSRC)/render_wave.hip $(CSRC)/render_nodes.hip $(CSRC)/render_generic.hip $(CSRC)/accumulate.hip $(CSRC)/trace_rays.hip $(CSRC)/denoise.hip $(CSRC)/adaptive.hip
-HOST_SRCS   := $(CSRC)/api.cpp $(CSRC)/scene_host.cpp $(CSRC)/scene_masks.cpp $(CSRC)/scene_trees.cpp $(CSRC)/multi_gpu.cpp
-HDRS        := include/skr.h $(CSRC)/launch.h $(CSRC)/device_math.h $(CSRC)/shade_common.h $(CSRC)/render_params.h $(CSRC)/scene_host.h $(CSRC)/shadow_cells.h $(CSRC)/tri_chunks.h $(CSRC)/wave_common.h
+HOST_SRCS   := $(CSRC)/api.cpp $(CSRC)/scene_host.cpp $(CSRC)/scene_masks.cpp $(CSRC)/scene_trees.cpp $(CSRC)/scene_pack.cpp $(CSRC)/multi_gpu.cpp
+HDRS        := include/skr.h $(CSRC)/launch.h $(CSRC)/device_math.h $(CSRC)/shade_common.h $(CSRC)/render_params.h $(CSRC)/scene_host.h $(CSRC)/scene_pack.h $(CSRC)/api_internal.h $(CSRC)/shadow_cells.h $(CSRC)/tri_chunks.h $(CSRC)/wave_common.h
 
 all: lib cli oracle
 
@@ -20,7 +20,7 @@ lib: $(LIBDIR)/libskr.so
 cli: bin/raytracer
 
 OBJDIR := build/obj
-OBJS   := $(OBJDIR)/render_kernel.o $(OBJDIR)/render_wave.o $(OBJDIR)/render_nodes.o $(OBJDIR)/render_generic.o $(OBJDIR)/accumulate.o $(OBJDIR)/trace_rays.o $(OBJDIR)/denoise.o $(OBJDIR)/adaptive.o $(OBJDIR)/api.o $(OBJDIR)/scene_host.o $(OBJDIR)/scene_masks.o $(OBJDIR)/scene_trees.o $(OBJDIR)/multi_gpu.o
+OBJS   := $(OBJDIR)/render_kernel.o $(OBJDIR)/render_wave.o $(OBJDIR)/render_nodes.o $(OBJDIR)/render_generic.o $(OBJDIR)/accumulate.o $(OBJDIR)/trace_rays.o $(OBJDIR)/denoise.o $(OBJDIR)/adaptive.o $(OBJDIR)/api.o $(OBJDIR)/scene_host.o $(OBJDIR)/scene_masks.o $(OBJDIR)/scene_trees.o $(OBJDIR)/scene_pack.o $(OBJDIR)/multi_gpu.o
 
 # one object per translation unit (the kernel files take a minute or two each: `make -j4 lib`)
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
@@ -30,6 +30,10 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c -o $@ -x hip $<
+
+# the object list, for tools that link a library of their own (tools/build_variant.sh)
+print-objs:
+	@echo $(OBJS)
 
 $(LIBDIR)/libskr.so: $(OBJS)
 	@mkdir -p $(LIBDIR)
@@ -57,4 +61,4 @@ clean:
 	rm -rf $(LIBDIR) bin build
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib cli oracle asm clean
+.PHONY: all lib cli oracle asm clean print-objs

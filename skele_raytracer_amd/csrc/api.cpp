@@ -11,64 +11,34 @@
 #include <memory>
 #include <vector>
 
+#include "api_internal.h"
 #include "launch.h"
-#include "scene_host.h"
+#include "scene_pack.h"
 
 static thread_local const char *g_variant = "none";
 
-#define SKR_HIP(call)                                                                                      \
-	do                                                                                                     \
-	{                                                                                                      \
-		hipError_t e_ = (call);                                                                            \
-		if(e_ != hipSuccess)                                                                               \
-		{                                                                                                  \
-			skr_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);     \
-			return SKR_ERR_HIP;                                                                            \
-		}                                                                                                  \
-	} while(0)
+// The counter block of a scene (DeviceScene::d_counters), in 64-bit words: the work counters, SKR_COUNTER_SHARDS x {radiance rays,
+// sphere hits shaded, shadow rays, sphere tests}; the 8 phase stamps of diagnostic builds (wave_common.h); then the queue counters,
+// 32-bit words SKR_PULL_STRIDE apart, and 8 reserved words behind them.  The walks' counters are allocations of their own.
+constexpr size_t CTR_WORK_WORDS = (size_t) SKR_COUNTER_SHARDS * 4, CTR_STAMP_WORDS = 8, CTR_RESERVED_WORDS = 8;
+constexpr size_t CTR_READ_WORDS = CTR_WORK_WORDS + CTR_STAMP_WORDS; // what the readers copy and reset, and where the queue counters start
+constexpr size_t CTR_BYTES = (CTR_READ_WORDS + CTR_RESERVED_WORDS) * sizeof(unsigned long long) + (SKR_PULL_QUEUES + 2 + 2 * SKR_P1_REGIONS) * SKR_PULL_STRIDE * sizeof(uint32_t);
+constexpr size_t CTR_SNAP_BYTES = 2 * CTR_WORK_WORDS * sizeof(unsigned long long); // skr_renderer::d_snap: the work counters twice (render_params.h SkrTimingHook)
+constexpr size_t WALK_SHARDS = 256; // d_tri_work, d_st_work: WALK_SHARDS x {culling-sphere tests, leaf tests} of a walk
+constexpr size_t WALK_BYTES = WALK_SHARDS * 2 * sizeof(unsigned long long);
 
-// The uploaded scene and what the launches take with it: shared by a renderer and its clones (skr_renderer_clone), freed by the last
-// of them.  The section offsets count 16-byte rows of the blob (pack_scene).
+// The uploaded scene: shared by a renderer and its clones (skr_renderer_clone), freed by the last of them.  Every pointer is null or
+// came from hipMalloc.
 struct DeviceScene {
 	int device = 0;
-	skr_scene_info info{};
 	int lds_limit = 0;
-	int pow_steps = 11; // bit length of the largest integer phong exponent in [1, 1024] among the scene's materials (device_math.h powf_spec)
-	float4 *d_blob = nullptr; // one allocation: the sections of pack_scene
-	size_t blob_bytes = 0;
-	float4 *d_camec = nullptr; // per sphere {cam_pos - centre, |.|^2 - r^2} (render_wave.hip skr_camec_kernel), + 16 rows of padding
-	unsigned long long *d_counters = nullptr;
-	unsigned long long *d_tri_work = nullptr; // 256 x {culling-sphere tests, triangle tests} executed by the triangle walks (skr_renderer_read_triangle_work)
-	size_t off_amb = 0, off_kd = 0, off_ks = 0, off_lights = 0, off_tris = 0, off_chunks = 0, off_tri_mats = 0;
-	size_t off_fog = 0;       // --scn-fog: 2 rows per fog volume (render_params.h RenderParams::fog_row)
-	int n_fog = 0;
-	size_t off_spot = 0;      // --scn-spot: 2 rows per spot light behind the fog rows (render_params.h SpotLights)
-	int n_spot = 0, spot_first = 0; // lights [spot_first, spot_first + n_spot) of the light table are spot lights
-	size_t off_radii = 0;     // skr_scene_set_light_radii: one float per point and spot light behind the cone rows (render_params.h SoftLights)
-	int n_radii = 0;
-	bool soft = false;        // some radius is > 0: frames and shading queries take the instances with the light sample
-	float lens_A = 0.0f, lens_F = 1.0f, lens_k = 0.0f; // skr_scene_set_lens: the aperture, the focus and k = A / F (one binary32 division); A > 0: frames take the instances with the lens sample
-	size_t off_smask = 0;     // the shadow masks (skr_scene::shadow_masks, 4 per row), 0 = none
-	size_t off_ssurf = 0;     // their surface patches (skr_scene::shadow_surface: ssurf_stride words per pair of lights), 0 = none
-	uint32_t ssurf_stride = 0;
-	float shadow_reach2 = 0.0f;
-	size_t off_gi = 0;        // the GI masks (skr_scene::gi_table, 4 words per row), 0 = none
-	SkrGiGrid gi_grid[2] = {};
-	uint32_t gi_mask_word = 0;
-	int gi_wide = 0;
-	size_t gi_surface_word = 0; // the surface patches' headers (skr_scene::gi_surface), in words from off_gi; 0 = none
-	int n_chunks = 0, chunk_size = 0, cones = 0;
-	size_t chunk_stride = 0;
-	size_t off_trace = 0;     // the ray queries' tree (skr_scene::trace_chunks, SKR_CULL_LEVELS sets of chunk_stride rows), 0 = none
-	float4 trace_ball{};
-	int trace_cones = 0;
-	bool tri_shadows = false; // the scene's triangle-shadow switch when the renderer was made (include/skr.h skr_scene_set_triangle_shadows)
-	// the sphere tree (include/skr.h skr_scene_set_sphere_tree; render_params.h SphereTree), uploaded where the scene had the switch on
-	bool sphere_tree = false;
-	size_t off_st_rows = 0, off_st_chunks = 0, off_st_nodes = 0;
-	int st_nodes = 0, st_chunks = 0, st_always = 0;
-	float4 st_ball{};
-	unsigned long long *d_st_work = nullptr; // 256 x {culling-sphere tests, sphere tests} its walks executed (skr_renderer_read_sphere_tree_work)
+	skr_scene_info info{};
+	SceneLayout layout; // where the sections of d_blob lie (scene_pack.h)
+	float4 *d_blob = nullptr;
+	float4 *d_camec = nullptr; // per sphere {cam_pos - centre, |.|^2 - r^2} (render_wave.hip skr_camec_kernel), + SKR_BLOB_PAD_ROWS rows of padding
+	unsigned long long *d_counters = nullptr; // CTR_BYTES
+	unsigned long long *d_tri_work = nullptr; // the triangle walks' counters (skr_renderer_read_triangle_work)
+	unsigned long long *d_st_work = nullptr;  // the sphere tree's (skr_renderer_read_sphere_tree_work); null without a sphere tree
 
 	DeviceScene() = default;
 	DeviceScene(const DeviceScene &) = delete;
@@ -163,108 +133,7 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_ADAPTIVE_PATH")) sw.adaptive_path = !strcmp(e, "frame") ? 1 : !strcmp(e, "query") ? 2 : 0;
 }
 
-// (multi_gpu.cpp) a clone follows its source's development switches: tests change them between frames
 void skr_copy_switches(skr_renderer *dst, const skr_renderer *src) { dst->sw = src->sw; }
-// (multi_gpu.cpp) skr_render_tile_list for a table the caller owns and never rewrites in place: table_id (not 0) names its contents
-int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
-							   float *d_rgbf, void *stream);
-
-// The scene blob, in this order: sphere geom | amb | kd | ks | lights | tris | chunk trees | triangle materials | fog volumes | spot cones | light radii | shadow
-// masks | GI masks | trace tree | sphere tree (rows, chunks, nodes), then 16 rows of padding (the sphere loops ask for the rows of a trip ahead without a bounds test,
-// shade_common.h sphere_rows).  Sets the offsets and the scalars of `d` that go with the sections; host only, nothing is uploaded.
-static std::vector<skr_f4> pack_scene(const skr_scene &s, DeviceScene &d)
-{
-	std::vector<skr_f4> rows;
-	auto put = [&](const void *src, size_t bytes) { // `bytes` of `src` (null: zeros) as whole rows; returns the first
-		const size_t at = rows.size();
-		rows.resize(at + (bytes + 15) / 16, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
-		if(src && bytes) memcpy(&rows[at], src, bytes);
-		return at;
-	};
-	auto put4 = [&](const std::vector<skr_f4> &v) { return put(v.data(), v.size() * 16); };
-	put4(s.sph_geom);
-	d.off_amb = put4(s.sph_amb);
-	d.off_kd = put4(s.sph_kd);
-	d.off_ks = put4(s.sph_ks);
-	d.off_lights = put4(s.lights);
-	d.off_tris = put4(s.tris);
-	d.off_chunks = put4(s.tri_chunks);
-	d.chunk_size = s.tri_chunk_size;
-	d.chunk_stride = s.tri_chunk_stride;
-	d.cones = s.tri_any_cone ? 1 : 0;
-	d.n_chunks = s.info.n_triangles ? s.tri_node_count : 0; // nodes of the chunk tree (scene_host.h)
-	d.off_tri_mats = put4(s.tri_mats);
-	// the fog volumes (skr_scene raw_fog, SKR_SCN_FOG / skr_scene_set_fog): [radius absorption scattering 0] [albedo 0]
-	d.off_fog = rows.size();
-	d.n_fog = (int) (s.raw_fog.size() / 9);
-	for(int j = 0; j < d.n_fog; j++)
-	{
-		const float *f = &s.raw_fog[9 * j]; // x y z radius r g b scattering absorption
-		rows.push_back({f[3], f[8], f[7], 0.0f});
-		rows.push_back({f[4], f[5], f[6], 0.0f});
-	}
-	// the spot lights' cone rows (skr_scene spot_cones, SKR_SCN_SPOT / skr_scene_set_spot_lights): {unit axis, c1} {c2, 0, 0, 0}
-	d.n_spot = s.n_spot();
-	d.spot_first = s.info.n_point_lights;
-	d.off_spot = put4(s.spot_cones);
-	// the radii of the point and spot lights (skr_scene light_radii, skr_scene_set_light_radii), one float per light in light order
-	d.n_radii = (int) s.light_radii.size();
-	d.soft = s.soft();
-	d.off_radii = put(s.light_radii.data(), s.light_radii.size() * 4);
-	d.lens_A = s.lens_aperture;
-	d.lens_F = s.lens_focus;
-	d.lens_k = s.lens_aperture / s.lens_focus;
-	if(!s.shadow_masks.empty()) d.off_smask = put(s.shadow_masks.data(), s.shadow_masks.size() * 4);
-	d.shadow_reach2 = s.shadow_reach2;
-	if(!s.shadow_surface.empty())
-	{ // the surface patches of the shadow masks; a sphere's header word rides in the .w of its kd row (shadow_cells.h)
-		d.off_ssurf = put(s.shadow_surface.data(), s.shadow_surface.size() * 4);
-		d.ssurf_stride = s.shadow_surface_stride;
-		for(size_t k = 0; k < s.shadow_surface_head.size(); k++) memcpy(&rows[d.off_kd + k].w, &s.shadow_surface_head[k], 4);
-	}
-	if(!s.gi_table.empty())
-	{ // the GI masks (whole rows: scene_masks.cpp build_gi_masks), with the surface patches' masks right behind the grids' masks (their
-	  // rows continue the grids' rows), then the patches' headers and index
-		const size_t patch_word = s.gi_mask_word + (size_t) s.gi_rows * (SKR_GI_ROW_ENTRIES * (s.gi_wide ? 4 : 2) / 4);
-		d.gi_surface_word = s.gi_surface.empty() ? 0 : patch_word + s.gi_surface_head;
-		d.off_gi = put(nullptr, std::max(s.gi_table.size(), s.gi_surface.empty() ? 0 : patch_word + s.gi_surface.size()) * 4);
-		uint32_t *words = reinterpret_cast<uint32_t *>(&rows[d.off_gi]);
-		memcpy(words, s.gi_table.data(), s.gi_table.size() * 4);
-		if(d.gi_surface_word) memcpy(words + patch_word, s.gi_surface.data(), s.gi_surface.size() * 4);
-	}
-	d.gi_grid[0] = s.gi_grid[0];
-	d.gi_grid[1] = s.gi_grid[1];
-	d.gi_mask_word = s.gi_mask_word;
-	d.gi_wide = s.gi_wide;
-	if(s.info.n_triangles && !s.trace_chunks.empty()) d.off_trace = put4(s.trace_chunks);
-	d.trace_ball = make_float4(s.trace_ball[0], s.trace_ball[1], s.trace_ball[2], s.trace_ball[3]);
-	d.trace_cones = s.trace_any_cone ? 1 : 0;
-	d.tri_shadows = s.triangle_shadows;
-	d.sphere_tree = s.sphere_tree && !s.sph_geom.empty();
-	if(d.sphere_tree)
-	{ // (the walk asks for the rows of a whole chunk, up to 3 behind the last sphere: the chunks follow)
-		SkrSphereTree t;
-		skr_build_sphere_tree(s, t);
-		d.off_st_rows = put4(t.rows);
-		d.off_st_chunks = put4(t.chunks);
-		d.off_st_nodes = put4(t.nodes);
-		d.st_nodes = t.n_nodes;
-		d.st_chunks = t.n_chunks;
-		d.st_always = t.n_always;
-		d.st_ball = make_float4(t.ball[0], t.ball[1], t.ball[2], t.ball[3]);
-	}
-	rows.resize(rows.size() + 16, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
-	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
-		float top = 1.0f;
-		auto look = [&](float pw) { if(pw >= 1.0f && pw <= 1024.0f && pw == rintf(pw) && pw > top) top = pw; };
-		for(const skr_f4 &a : s.sph_amb) look(a.w);
-		for(size_t i = 0; i + 2 < s.tri_mats.size(); i += 3) look(s.tri_mats[i].w);
-		int bits = 0;
-		for(unsigned v = (unsigned) top; v; v >>= 1) bits++;
-		d.pow_steps = bits < 1 ? 1 : bits;
-	}
-	return rows;
-}
 
 // The device frame of a *_host entry, kept in the renderer: its bytes, its floats and, with `passes`, the adaptive sampler's pass counts
 struct HostFrame {
@@ -352,20 +221,18 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	s->device = device;
 	s->info = scene->info;
 	s->lds_limit = (int) prop.sharedMemPerBlock;
-	const std::vector<skr_f4> blob = pack_scene(*scene, *s);
-	s->blob_bytes = blob.size() * 16;
-	const size_t ns = scene->sph_geom.size();
-	const size_t counter_bytes = (SKR_COUNTER_SHARDS * 4 + 16) * sizeof(unsigned long long) + (SKR_PULL_QUEUES + 2 + 2 * SKR_P1_REGIONS) * SKR_PULL_STRIDE * sizeof(uint32_t);
-	hipError_t e = hipMalloc((void **) &s->d_blob, s->blob_bytes);
-	if(e == hipSuccess) e = hipMemcpy(s->d_blob, blob.data(), s->blob_bytes, hipMemcpyHostToDevice);
-	if(e == hipSuccess) e = hipMalloc((void **) &s->d_counters, counter_bytes);
-	if(e == hipSuccess) e = hipMemset(s->d_counters, 0, counter_bytes);
-	if(e == hipSuccess) e = hipMalloc((void **) &s->d_tri_work, 256 * 2 * sizeof(unsigned long long));
-	if(e == hipSuccess) e = hipMemset(s->d_tri_work, 0, 256 * 2 * sizeof(unsigned long long));
-	if(e == hipSuccess && s->sphere_tree) e = hipMalloc((void **) &s->d_st_work, 256 * 2 * sizeof(unsigned long long));
-	if(e == hipSuccess && s->sphere_tree) e = hipMemset(s->d_st_work, 0, 256 * 2 * sizeof(unsigned long long));
-	if(e == hipSuccess) e = hipMalloc((void **) &s->d_camec, (ns + 16) * 16);
-	if(e == hipSuccess) e = hipMemset(s->d_camec, 0, (ns + 16) * 16);
+	const std::vector<skr_f4> blob = skr_pack_scene(*scene, s->layout);
+	const size_t ns = scene->sph_geom.size(), camec_bytes = (ns + SKR_BLOB_PAD_ROWS) * 16;
+	auto zeroed = [](auto **p, size_t bytes) { // a device allocation of zeros
+		const hipError_t e = hipMalloc((void **) p, bytes);
+		return e == hipSuccess ? hipMemset(*p, 0, bytes) : e;
+	};
+	hipError_t e = hipMalloc((void **) &s->d_blob, blob.size() * 16);
+	if(e == hipSuccess) e = hipMemcpy(s->d_blob, blob.data(), blob.size() * 16, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = zeroed(&s->d_counters, CTR_BYTES);
+	if(e == hipSuccess) e = zeroed(&s->d_tri_work, WALK_BYTES);
+	if(e == hipSuccess && s->layout.sphere_tree) e = zeroed(&s->d_st_work, WALK_BYTES);
+	if(e == hipSuccess) e = zeroed(&s->d_camec, camec_bytes);
 	if(e == hipSuccess)
 	{ // the camera belongs to the scene: its (e, c) rows are formed once, on the device, by the operations every ray would perform
 		const float *c = scene->info.camera;
@@ -448,7 +315,7 @@ static int check_options(const skr_options *opt)
 // What every launch starts from, and all the camera rays need (skr_launch_camera_rays, skr_launch_adaptive_rays): the size of the frame
 // of opt, AA sample `sample` of it under `seed`, and the camera of camera.h:8-32 (what primary_ray() reads) with main.cpp:134-137
 // hoisted (identical float/double expressions evaluated once)
-static RenderParams camera_params(const skr_renderer *r, const skr_options *opt, uint64_t seed, uint32_t sample)
+static RenderParams camera_params(const skr_scene_info &info, const skr_options *opt, uint64_t seed, uint32_t sample)
 {
 	RenderParams p{};
 	p.width = opt->width;
@@ -461,7 +328,7 @@ static RenderParams camera_params(const skr_renderer *r, const skr_options *opt,
 	p.inv_height = 1 / float(opt->height);
 	p.aspect = opt->width / float(opt->height);
 	p.angle = (float) tan(M_PI * 0.5 * opt->fov / 180.);
-	const float *c = r->scene->info.camera;
+	const float *c = info.camera;
 	p.cam_pos = f3{c[0], c[1], c[2]};
 	p.cam_dir = f3{c[3], c[4], c[5]};
 	p.cam_up = f3{c[6], c[7], c[8]};
@@ -484,49 +351,68 @@ static uint32_t sel_tiles(const skr_options *opt, uint32_t tile_rows, const Tile
 	return n > ts.max_tiles ? ts.max_tiles : n;
 }
 
+// What the launch helpers below read of a renderer, and all they read: the scene's facts and layout, where its tables start, the
+// switches and whether the walks count their work.  It owns nothing: a renderer's addresses are its DeviceScene's allocations,
+// skr_scene_leaf_shape's are host arrays nobody dereferences.
+struct LaunchScene {
+	const skr_scene_info &info;
+	const SceneLayout &layout;
+	const float4 *blob, *camec;
+	unsigned long long *counters, *tri_work, *st_work;
+	const SkrSwitches &sw;
+	bool count_tri;
+	const float4 *sec(SkrBlobSection k) const { return blob + layout.first[k]; } // where a section starts
+};
+static LaunchScene launch_scene(const skr_renderer *r)
+{
+	const DeviceScene &s = *r->scene;
+	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri};
+}
+static float4 ball4(const skr_f4 &b) { return make_float4(b.x, b.y, b.z, b.w); }
+
 // Everything of a launch beyond camera_params that is not its output: the scene, the switches and masks, and the options folded and
 // checked — the depth fold, the node-id bound, the fog exclusions.  render_pass and skr_shade_rays both take it.
 // query: a shading query — its rays are the caller's, so the scene's lens is not among its features.
-static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p, bool query);
-static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &p, GenericFeatures &f, bool query = false)
+static GenericFeatures generic_features(const LaunchScene &v, const RenderParams &p, bool query);
+static int launch_params(const LaunchScene &v, const skr_options *opt, RenderParams &p, GenericFeatures &f, bool query = false)
 {
-	const DeviceScene &s = *r->scene;
-	p.sw = r->sw;
-	const float *c = s.info.camera;
-	p.background = f3{s.info.background[0], s.info.background[1], s.info.background[2]};
-	p.n_spheres = s.info.n_spheres;
-	p.n_tris = s.info.n_triangles;
-	p.n_lights = s.info.n_point_lights + s.n_spot + s.info.n_directional_lights; // (spot lights only under --scn-spot, directional ones only under --strict-scn)
-	p.sph_geom = s.d_blob;
-	p.cam_ec = s.d_camec;
-	p.sph_amb = s.d_blob + s.off_amb;
-	p.sph_kd = s.d_blob + s.off_kd;
-	p.sph_ks = s.d_blob + s.off_ks;
-	p.lights = s.d_blob + s.off_lights;
-	p.tris = s.d_blob + s.off_tris;
-	p.tri_chunks = s.d_blob + s.off_chunks;
+	const SceneLayout &s = v.layout;
+	p.sw = v.sw;
+	const float *c = v.info.camera;
+	p.background = f3{v.info.background[0], v.info.background[1], v.info.background[2]};
+	p.n_spheres = v.info.n_spheres;
+	p.n_tris = v.info.n_triangles;
+	p.n_lights = v.info.n_point_lights + s.n_spot + v.info.n_directional_lights; // (spot lights only under --scn-spot, directional ones only under --strict-scn)
+	p.sph_geom = v.blob;
+	p.cam_ec = v.camec;
+	p.sph_amb = v.sec(SKR_SEC_amb);
+	p.sph_kd = v.sec(SKR_SEC_kd);
+	p.sph_ks = v.sec(SKR_SEC_ks);
+	p.lights = v.sec(SKR_SEC_lights);
+	p.tris = v.sec(SKR_SEC_tris);
+	p.tri_chunks = v.sec(SKR_SEC_chunks);
 	p.tri_chunk_size = s.chunk_size;
-	p.tri_cones = (s.cones && !r->sw.no_cones) ? 1 : 0;
-	if(s.off_smask && (r->sw.shadow_mask & 1))
+	p.tri_cones = (s.cones && !v.sw.no_cones) ? 1 : 0;
+	if(s.has(SKR_SEC_smask) && (v.sw.shadow_mask & 1))
 	{ // the level pipelines' shadow walk visits only the spheres a lane's masks name (shade_common.h occluded_pair)
-		p.shadow_masks = reinterpret_cast<const uint32_t *>(s.d_blob + s.off_smask);
+		p.shadow_masks = reinterpret_cast<const uint32_t *>(v.sec(SKR_SEC_smask));
 		p.shadow_reach2 = s.shadow_reach2;
 		p.shadow_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
-		if(s.off_ssurf && (r->sw.shadow_mask & 2))
+		if(s.has(SKR_SEC_ssurf) && (v.sw.shadow_mask & 2))
 		{ // ... a hit of a sphere takes them from that sphere's surface patch (shade_common.h shadow_cands)
-			p.shadow_surface_word = (uint32_t) ((s.off_ssurf - s.off_smask) * 4); // (rows of 4 words; the patches follow the masks in the blob)
+			p.shadow_surface_word = (uint32_t) ((s.first[SKR_SEC_ssurf] - s.first[SKR_SEC_smask]) * 4); // (rows of 4 words; the patches follow the masks in the blob)
 			p.shadow_surface_stride = s.ssurf_stride;
 		}
 	}
-	if(s.off_gi && r->sw.gi_mask)
+	if(s.has(SKR_SEC_gi) && v.sw.gi_mask)
 	{ // the node pipeline's closest-hit walk of a GI child visits only the spheres its masks name (wave_common.h closest_pair)
-		p.gi_index = reinterpret_cast<const int32_t *>(s.d_blob + s.off_gi);
-		p.gi_masks = reinterpret_cast<const uint32_t *>(s.d_blob + s.off_gi) + s.gi_mask_word;
+		p.gi_index = reinterpret_cast<const int32_t *>(v.sec(SKR_SEC_gi));
+		p.gi_masks = reinterpret_cast<const uint32_t *>(v.sec(SKR_SEC_gi)) + s.gi_mask_word;
 		p.gi_grid[0] = s.gi_grid[0];
 		p.gi_grid[1] = s.gi_grid[1];
 		p.gi_wide = s.gi_wide;
 		p.gi_all = p.n_spheres >= 32 ? ~0u : (1u << p.n_spheres) - 1u;
-		if(s.gi_surface_word && r->sw.gi_surface) p.gi_surface = reinterpret_cast<const uint32_t *>(s.d_blob + s.off_gi) + s.gi_surface_word;
+		if(s.gi_surface_word && v.sw.gi_surface) p.gi_surface = reinterpret_cast<const uint32_t *>(v.sec(SKR_SEC_gi)) + s.gi_surface_word;
 	}
 	{ // pick the tightest set of chunk spheres whose |d| bound covers this frame's camera rays (GI children stay below 4,
 	  // the smallest bound): primary directions are dir + u right + v up (main.cpp:154-155)
@@ -536,7 +422,7 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 		const double bound[SKR_CULL_LEVELS] = SKR_CULL_DMAX_LIST;
 		int level = 0;
 		while(level < SKR_CULL_LEVELS && !(dmax < bound[level])) level++;
-		p.n_tri_chunks = (level < SKR_CULL_LEVELS && !r->sw.no_cull) ? s.n_chunks : 0;
+		p.n_tri_chunks = (level < SKR_CULL_LEVELS && !v.sw.no_cull) ? s.n_chunks : 0;
 		if(p.n_tri_chunks) p.tri_chunks += (size_t) level * s.chunk_stride;
 	}
 	p.monte_carlo = opt->monte_carlo ? 1 : 0;
@@ -548,7 +434,7 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 	// child to recurse into: every --depth is then the depth-1 image
 	// (--shade-triangles: a triangle hit recurses too)
 	p.shade_triangles = (opt->shade_triangles && p.n_tris > 0) ? 1 : 0;
-	p.tri_mats = s.d_blob + s.off_tri_mats;
+	p.tri_mats = v.sec(SKR_SEC_tri_mats);
 	// Only a sphere hit has the terms of raytrace.h:45-103, so a scene without spheres has nothing to add — but the flag also sets the
 	// arity of the counter RNG's node ids (N + 2 L, include/skr.h), and a tree over triangle surfaces (--shade-triangles --gillum) has
 	// nodes whatever the scene holds: there the flag stays, the legacy children simply never exist (found by tests/fuzz_parity.py:
@@ -568,17 +454,17 @@ static int launch_params(skr_renderer *r, const skr_options *opt, RenderParams &
 	}
 	// --scn-fog: a scene with fog volumes renders on the general level pipeline (render_kernel.hip skr_plan_launch)
 	p.n_fog = s.n_fog;
-	p.fog_row = (uint32_t) s.off_fog;
+	p.fog_row = (uint32_t) s.first[SKR_SEC_fog];
 	// what the scene and the options switch on of the general level pipeline, and whether they go together (launch.h)
-	f = generic_features(r, p, query);
+	f = generic_features(v, p, query);
 	if(const char *why = skr_features_conflict(f, opt->legacy_reflect != 0, opt->shade_triangles != 0, p.n_fog > 0))
 	{
 		skr_set_error("%s", why);
 		return SKR_ERR_UNSUPPORTED;
 	}
-	p.counters = s.d_counters;
-	p.tri_work = r->count_tri ? s.d_tri_work : nullptr;
-	p.qctr = reinterpret_cast<uint32_t *>(s.d_counters + (size_t) SKR_COUNTER_SHARDS * 4 + 8);
+	p.counters = v.counters;
+	p.tri_work = v.count_tri ? v.tri_work : nullptr;
+	p.qctr = reinterpret_cast<uint32_t *>(v.counters + CTR_READ_WORDS);
 	return SKR_OK;
 }
 
@@ -597,58 +483,49 @@ static int check_plan(const skr_renderer *r, const RenderParams &p, bool fits, s
 	if(lds > (size_t) r->scene->lds_limit)
 	{
 		skr_set_error("scene needs %zu bytes of LDS (%d spheres, %d lights); the device allows %d per workgroup%s", lds, p.n_spheres, p.n_lights,
-					  r->scene->lds_limit, r->scene->sphere_tree ? "" : " (the sphere tree, skr_scene_set_sphere_tree / --sphere-tree, keeps the spheres out of LDS)");
+					  r->scene->lds_limit, r->scene->layout.sphere_tree ? "" : " (the sphere tree, skr_scene_set_sphere_tree / --sphere-tree, keeps the spheres out of LDS)");
 		return SKR_ERR_UNSUPPORTED;
 	}
 	return SKR_OK;
 }
 
 // the scene's lens for the kernels that form camera rays alone (launch.h Lens; no trees); null: the pinhole
-static const Lens *camera_lens(const skr_renderer *r, Lens &lens)
+static const Lens *camera_lens(const SceneLayout &s, Lens &lens)
 {
-	const DeviceScene &s = *r->scene;
 	if(!(s.lens_A > 0.0f)) return nullptr;
 	lens = Lens{s.lens_A, s.lens_k, QueryTrees{}};
 	return &lens;
 }
 
-// A scene with a lens has no denoised frame (include/skr.h skr_scene_set_lens): the guides are pinhole first hits
-static int refuse_lens(const skr_renderer *r, const char *who)
-{
-	if(!(r->scene->lens_A > 0.0f)) return SKR_OK;
-	skr_set_error("%s: a lens (--aperture) cannot be combined with the denoiser (its guides are the pinhole camera's first hits)", who);
-	return SKR_ERR_UNSUPPORTED;
-}
-
 // the trees a query may walk under the renderer's switches (launch.h QueryTrees)
-static QueryTrees query_trees(const skr_renderer *r)
+static QueryTrees query_trees(const LaunchScene &v)
 {
-	const DeviceScene &s = *r->scene;
+	const SceneLayout &s = v.layout;
 	QueryTrees q{};
-	q.tree = s.d_blob + s.off_chunks;
-	q.trace = s.off_trace ? s.d_blob + s.off_trace : nullptr;
+	q.tree = v.sec(SKR_SEC_chunks);
+	q.trace = s.has(SKR_SEC_trace) ? v.sec(SKR_SEC_trace) : nullptr;
 	q.stride = (uint32_t) s.chunk_stride;
-	q.nchunks = r->sw.no_cull ? 0 : s.n_chunks;
-	q.cones = (s.cones && !r->sw.no_cones) ? 1 : 0;
-	q.trace_cones = (s.trace_cones && !r->sw.no_cones) ? 1 : 0;
-	q.ball = s.trace_ball;
+	q.nchunks = v.sw.no_cull ? 0 : s.n_chunks;
+	q.cones = (s.cones && !v.sw.no_cones) ? 1 : 0;
+	q.trace_cones = (s.trace_cones && !v.sw.no_cones) ? 1 : 0;
+	q.ball = ball4(s.trace_ball);
 	return q;
 }
 
 // the sphere tree of a renderer whose scene had the switch on, under the renderer's switches (render_params.h SphereTree)
-static SphereTree sphere_tree_of(const skr_renderer *r)
+static SphereTree sphere_tree_of(const LaunchScene &v)
 {
-	const DeviceScene &s = *r->scene;
+	const SceneLayout &s = v.layout;
 	SphereTree t{};
-	t.nodes = s.d_blob + s.off_st_nodes;
-	t.chunks = s.d_blob + s.off_st_chunks;
-	t.rows = s.d_blob + s.off_st_rows;
+	t.nodes = v.sec(SKR_SEC_st_nodes);
+	t.chunks = v.sec(SKR_SEC_st_chunks);
+	t.rows = v.sec(SKR_SEC_st_rows);
 	t.n_nodes = s.st_nodes;
 	t.n_chunks = s.st_chunks;
 	t.n_always = s.st_always;
-	t.cull = (r->sw.no_sphere_cull || !(s.st_ball.w >= 0.0f)) ? 0 : 1; // (a ball of radius -1: the tree's bounds do not hold, no wave walks it)
-	t.ball = s.st_ball;
-	t.work = r->count_tri ? s.d_st_work : nullptr;
+	t.cull = (v.sw.no_sphere_cull || !(s.st_ball.w >= 0.0f)) ? 0 : 1; // (a ball of radius -1: the tree's bounds do not hold, no wave walks it)
+	t.ball = ball4(s.st_ball);
+	t.work = v.count_tri ? v.st_work : nullptr;
 	return t;
 }
 
@@ -656,27 +533,27 @@ static SphereTree sphere_tree_of(const skr_renderer *r)
 // scene has them switched on, the launch shades triangles (the option is set and the scene has some) and casts shadow rays (include/skr.h
 // skr_scene_set_triangle_shadows); otherwise the launch is the one it was without the switch: the same kernels, the same
 // skr_kernel_variant().
-static GenericFeatures generic_features(const skr_renderer *r, const RenderParams &p, bool query)
+static GenericFeatures generic_features(const LaunchScene &v, const RenderParams &p, bool query)
 {
-	const DeviceScene &s = *r->scene;
+	const SceneLayout &s = v.layout;
 	GenericFeatures f;
 	f.tri_shadows = s.tri_shadows && p.shade_triangles && p.use_shadows;
 	f.sphere_tree = s.sphere_tree;
 	f.spot = s.n_spot > 0;
 	f.soft = s.soft;
-	if(f.tri_shadows) f.shadows.trees = query_trees(r);
-	if(f.sphere_tree) f.stree = sphere_tree_of(r);
-	if(f.spot || f.soft) f.spots = SpotLights{s.d_blob + s.off_spot, s.spot_first, s.n_spot}; // (n = 0 without spot lights)
-	if(f.soft) f.softs = SoftLights{reinterpret_cast<const float *>(s.d_blob + s.off_radii), s.n_radii};
+	if(f.tri_shadows) f.shadows.trees = query_trees(v);
+	if(f.sphere_tree) f.stree = sphere_tree_of(v);
+	if(f.spot || f.soft) f.spots = SpotLights{v.sec(SKR_SEC_spot), s.spot_first, s.n_spot}; // (n = 0 without spot lights)
+	if(f.soft) f.softs = SoftLights{reinterpret_cast<const float *>(v.sec(SKR_SEC_radii)), s.n_radii};
 	f.lens = s.lens_A > 0.0f && !query;
-	if(f.lens) f.thin_lens = Lens{s.lens_A, s.lens_k, query_trees(r)};
+	if(f.lens) f.thin_lens = Lens{s.lens_A, s.lens_k, query_trees(v)};
 	return f;
 }
 
 // one pass of the tiles `ts` selects (render_impl has checked the arguments and set the device)
 static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
 {
-	RenderParams p = camera_params(r, opt, opt->seed, 0);
+	RenderParams p = camera_params(r->scene->info, opt, opt->seed, 0);
 	p.tile_rows = tile_rows;
 	p.first_tile = ts.first;
 	p.tile_table = ts.d_table;
@@ -685,7 +562,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	p.band_row0 = 0;
 	p.band_rows = p.out_rows;
 	GenericFeatures f;
-	int rc = launch_params(r, opt, p, f);
+	int rc = launch_params(launch_scene(r), opt, p, f);
 	if(rc != SKR_OK) return rc;
 	p.rgb = d_rgb;
 	p.rgbf = d_rgbf;
@@ -717,8 +594,8 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 		}
 		if(!r->d_snap)
 		{
-			SKR_HIP(hipMalloc((void **) &r->d_snap, (size_t) 2 * SKR_COUNTER_SHARDS * 4 * sizeof(unsigned long long)));
-			SKR_HIP(hipMemset(r->d_snap, 0, (size_t) 2 * SKR_COUNTER_SHARDS * 4 * sizeof(unsigned long long)));
+			SKR_HIP(hipMalloc((void **) &r->d_snap, CTR_SNAP_BYTES));
+			SKR_HIP(hipMemset(r->d_snap, 0, CTR_SNAP_BYTES));
 		}
 		hook.snap = r->d_snap;
 		hook.counters = r->scene->d_counters;
@@ -747,6 +624,15 @@ static int progressive_scratch(skr_renderer *r, size_t n, float *&frame, float *
 	return rc;
 }
 
+// the options of pass k of a multi-pass render: one frame under the seed s + k
+static skr_options pass_options(const skr_options *opt, uint64_t k)
+{
+	skr_options pass = *opt;
+	pass.progressive_passes = 1;
+	pass.seed = opt->seed + k;
+	return pass;
+}
+
 // skr_options.progressive_passes: K frames under the seeds s, s+1, ..., s+K-1, summed in binary32 in pass
 // order, divided by K once and quantised like a single frame (accumulate.hip).  K <= 1 is the single frame itself.
 static int render_impl(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const TileSel &ts, uint8_t *d_rgb, float *d_rgbf, void *stream)
@@ -767,11 +653,9 @@ static int render_impl(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	float *frame, *acc;
 	rc = progressive_scratch(r, n, frame, acc);
 	if(rc != SKR_OK) return rc;
-	skr_options pass = *opt;
-	pass.progressive_passes = 1;
 	for(int32_t k = 0; k < opt->progressive_passes; k++)
 	{
-		pass.seed = opt->seed + (uint64_t) k;
+		const skr_options pass = pass_options(opt, (uint64_t) k);
 		rc = render_pass(r, &pass, tile_rows, ts, nullptr, frame, stream);
 		if(rc != SKR_OK) return rc;
 		SKR_HIP(skr_launch_accumulate(acc, frame, n, k == 0, (hipStream_t) stream));
@@ -790,25 +674,9 @@ int skr_render_tiles(skr_renderer *r, const skr_options *opt, uint32_t tile_rows
 	return render_impl(r, opt, tile_rows, ts, d_rgb, d_rgbf, stream);
 }
 
-// table_id: the identity of the table's present contents, from its owner (0: unknown — such a launch never replays a level-0 stage)
-static int render_tile_list(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
-							float *d_rgbf, void *stream)
-{
-	if(!d_tiles)
-	{
-		skr_set_error("skr_render_tile_list: no tile table");
-		return SKR_ERR_ARG;
-	}
-	TileSel ts;
-	ts.d_table = d_tiles;
-	ts.n_slots = n_slots;
-	ts.table_id = table_id;
-	return render_impl(r, opt, tile_rows, ts, d_rgb, d_rgbf, stream);
-}
-
 int skr_render_tile_list(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint8_t *d_rgb, float *d_rgbf, void *stream)
 {
-	return render_tile_list(r, opt, tile_rows, d_tiles, n_slots, 0, d_rgb, d_rgbf, stream);
+	return skr_render_tile_list_owned(r, opt, tile_rows, d_tiles, n_slots, 0, d_rgb, d_rgbf, stream); // (0: contents unknown — such a launch never replays a level-0 stage)
 }
 
 int skr_renderer_primary_cache_stats(skr_renderer *r, uint64_t *builds, uint64_t *replays)
@@ -828,25 +696,16 @@ int skr_renderer_last_leaf_shape(const skr_renderer *r) { return r ? r->last_lea
 int skr_scene_leaf_shape(const skr_scene *scene, const skr_options *opt)
 {
 	if(!scene || !opt) return -SKR_ERR_ARG;
-	auto ds = std::make_shared<DeviceScene>();
-	ds->info = scene->info;
-	std::vector<skr_f4> rows = pack_scene(*scene, *ds);
-	std::vector<unsigned long long> counters((size_t) SKR_COUNTER_SHARDS * 4 + 16);
-	ds->d_blob = reinterpret_cast<float4 *>(rows.data()); // (host memory: only addresses are formed, and null-ness asked)
-	ds->d_counters = counters.data();
-	int rc;
-	{
-		skr_renderer r;
-		r.scene = ds;
-		load_switches(r.sw);
-		RenderParams p = camera_params(&r, opt, opt->seed, 0);
-		GenericFeatures f;
-		rc = launch_params(&r, opt, p, f);
-		rc = rc == SKR_OK ? (int) skr_leaf_shape(p) : -rc;
-	}
-	ds->d_blob = nullptr; // (neither is the device's: nothing for ~DeviceScene to free)
-	ds->d_counters = nullptr;
-	return rc;
+	SceneLayout layout;
+	const std::vector<skr_f4> rows = skr_pack_scene(*scene, layout);
+	std::vector<unsigned long long> counters(CTR_READ_WORDS + CTR_RESERVED_WORDS);
+	SkrSwitches sw;
+	load_switches(sw);
+	RenderParams p = camera_params(scene->info, opt, opt->seed, 0);
+	GenericFeatures f; // (host memory: only addresses are formed, and null-ness asked)
+	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false};
+	const int rc = launch_params(v, opt, p, f);
+	return rc == SKR_OK ? (int) skr_leaf_shape(p) : -rc;
 }
 
 // Per tile of `tile_rows` image rows: the work its pixels cost, counted — the tile is rendered on its own and the work counters read
@@ -862,7 +721,7 @@ int skr_tile_costs(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, 
 	SKR_HIP(hipSetDevice(r->scene->device));
 	const uint32_t T = ((uint32_t) opt->height + tile_rows - 1) / tile_rows;
 	SKR_HIP(hipDeviceSynchronize()); // (frames still in flight on other streams add to the counters this probe borrows)
-	std::vector<unsigned long long> saved((size_t) SKR_COUNTER_SHARDS * 4 + 8);
+	std::vector<unsigned long long> saved(CTR_READ_WORDS);
 	SKR_HIP(hipMemcpy(saved.data(), r->scene->d_counters, saved.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	SKR_HIP(hipMemset(r->scene->d_counters, 0, saved.size() * sizeof(unsigned long long)));
 	std::vector<uint32_t> tiles(T);
@@ -872,8 +731,9 @@ int skr_tile_costs(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, 
 	hipError_t e = hipMalloc((void **) &d_tiles, (size_t) T * sizeof(uint32_t));
 	if(e == hipSuccess) e = hipMalloc((void **) &d_rgb, (size_t) tile_rows * (size_t) opt->width * 3);
 	if(e == hipSuccess) e = hipMemcpy(d_tiles, tiles.data(), (size_t) T * sizeof(uint32_t), hipMemcpyHostToDevice);
-	const bool was_timing = r->count_tri;
+	const bool was_counting = r->count_tri, was_timing = r->timing; // the probe's launches are not the caller's: they count no walk work and are not timed
 	r->count_tri = false;
+	r->timing = false;
 	for(uint32_t t = 0; t < T && e == hipSuccess && rc == SKR_OK; t++)
 	{
 		rc = skr_render_tile_list(r, opt, tile_rows, d_tiles + t, 1, d_rgb, nullptr, nullptr);
@@ -882,7 +742,8 @@ int skr_tile_costs(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, 
 		const uint64_t mesh = r->scene->info.n_triangles > 64 ? (uint64_t) (6 * 19 + 5 * 46) : (uint64_t) r->scene->info.n_triangles * 46;
 		h_cost[t] = 34 * w[3] + 150 * w[1] + (20 + mesh) * (w[0] + w[2]);
 	}
-	r->count_tri = was_timing;
+	r->count_tri = was_counting;
+	r->timing = was_timing;
 	if(d_tiles) (void) hipFree(d_tiles);
 	if(d_rgb) (void) hipFree(d_rgb);
 	if(e == hipSuccess) e = hipMemcpy(r->scene->d_counters, saved.data(), saved.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
@@ -991,15 +852,15 @@ static int read_work(skr_renderer *r, uint64_t *out, int n_out, int reset)
 {
 	if(!r || !out) return SKR_ERR_ARG;
 	SKR_HIP(hipSetDevice(r->scene->device));
-	// the work counters and (diagnostic builds) the 8 phase stamps behind them; the queue counters that follow are not touched
-	std::vector<unsigned long long> h((size_t) SKR_COUNTER_SHARDS * 4 + 8);
+	// the work counters and (diagnostic builds) the phase stamps behind them; the queue counters that follow are not touched
+	std::vector<unsigned long long> h(CTR_READ_WORDS);
 	SKR_HIP(hipMemcpy(h.data(), r->scene->d_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost)); // synchronises with prior launches
 	for(int k = 0; k < n_out; k++) out[k] = 0;
-	for(size_t s = 0; s < SKR_COUNTER_SHARDS; s++)
-		for(int k = 0; k < n_out; k++) out[k] += h[4 * s + k];
+	for(size_t s = 0; s < CTR_WORK_WORDS; s += 4)
+		for(int k = 0; k < n_out; k++) out[k] += h[s + k];
 	if(getenv("SKR_PRINT_STAMPS"))
 	{ // diagnostic builds (-DSKR_STAMPS=1) only: per-phase cycle sums
-		for(int k = 0; k < 8; k++) fprintf(stderr, "stamp[%d] = %llu\n", k, h[(size_t) SKR_COUNTER_SHARDS * 4 + k]);
+		for(size_t k = 0; k < CTR_STAMP_WORDS; k++) fprintf(stderr, "stamp[%zu] = %llu\n", k, h[CTR_WORK_WORDS + k]);
 	}
 	// (null stream: callers read the counters between frames, after synchronising their render stream)
 	if(reset) SKR_HIP(hipMemset(r->scene->d_counters, 0, h.size() * sizeof(unsigned long long)));
@@ -1030,33 +891,37 @@ int skr_renderer_kernel_work(skr_renderer *r, uint64_t out[4])
 	for(int k = 0; k < 4; k++) out[k] = 0;
 	if(!r->d_snap) return SKR_OK;
 	SKR_HIP(hipSetDevice(r->scene->device));
-	std::vector<unsigned long long> h((size_t) 2 * SKR_COUNTER_SHARDS * 4);
-	SKR_HIP(hipMemcpy(h.data(), r->d_snap, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost)); // synchronises with prior launches
-	const size_t half = (size_t) SKR_COUNTER_SHARDS * 4;
-	for(size_t s = 0; s < SKR_COUNTER_SHARDS; s++)
-		for(int k = 0; k < 4; k++) out[k] += h[half + 4 * s + k] - h[4 * s + k];
+	std::vector<unsigned long long> h(2 * CTR_WORK_WORDS);
+	SKR_HIP(hipMemcpy(h.data(), r->d_snap, CTR_SNAP_BYTES, hipMemcpyDeviceToHost)); // synchronises with prior launches
+	for(size_t s = 0; s < CTR_WORK_WORDS; s += 4)
+		for(int k = 0; k < 4; k++) out[k] += h[CTR_WORK_WORDS + s + k] - h[s + k];
 	out[3] += out[0] * (uint64_t) r->scene->info.n_spheres; // (as skr_renderer_read_work)
+	return SKR_OK;
+}
+
+// the counters of a walk (d_tri_work, d_st_work), summed over their shards: {culling-sphere tests, leaf tests}
+static int read_walk_work(unsigned long long *d_work, uint64_t out[2], int reset)
+{
+	unsigned long long h[WALK_SHARDS * 2];
+	SKR_HIP(hipMemcpy(h, d_work, WALK_BYTES, hipMemcpyDeviceToHost)); // synchronises with prior launches
+	for(size_t s = 0; s < WALK_SHARDS; s++)
+	{
+		out[0] += h[2 * s];
+		out[1] += h[2 * s + 1];
+	}
+	if(reset) SKR_HIP(hipMemset(d_work, 0, WALK_BYTES));
 	return SKR_OK;
 }
 
 int skr_renderer_read_triangle_work(skr_renderer *r, uint64_t out[3], int reset)
 {
 	if(!r || !out) return SKR_ERR_ARG;
-	SKR_HIP(hipSetDevice(r->scene->device));
-	unsigned long long h[256 * 2];
-	SKR_HIP(hipMemcpy(h, r->scene->d_tri_work, sizeof(h), hipMemcpyDeviceToHost)); // synchronises with prior launches
-	out[0] = out[1] = 0;
-	for(int s = 0; s < 256; s++)
-	{
-		out[0] += h[2 * s];
-		out[1] += h[2 * s + 1];
-	}
 	uint64_t w[4];
 	const int rc = read_work(r, w, 4, 0);
 	if(rc != SKR_OK) return rc;
+	out[0] = out[1] = 0;
 	out[2] = w[0] * (uint64_t) r->scene->info.n_triangles; // raytrace.h:171-186: every radiance ray tests every triangle
-	if(reset) SKR_HIP(hipMemset(r->scene->d_tri_work, 0, sizeof(h)));
-	return SKR_OK;
+	return read_walk_work(r->scene->d_tri_work, out, reset);
 }
 
 int skr_renderer_read_sphere_tree_work(skr_renderer *r, uint64_t out[2], int reset)
@@ -1065,15 +930,7 @@ int skr_renderer_read_sphere_tree_work(skr_renderer *r, uint64_t out[2], int res
 	out[0] = out[1] = 0;
 	if(!r->scene->d_st_work) return SKR_OK; // (no sphere tree: no walks)
 	SKR_HIP(hipSetDevice(r->scene->device));
-	unsigned long long h[256 * 2];
-	SKR_HIP(hipMemcpy(h, r->scene->d_st_work, sizeof(h), hipMemcpyDeviceToHost)); // synchronises with prior launches
-	for(int s = 0; s < 256; s++)
-	{
-		out[0] += h[2 * s];
-		out[1] += h[2 * s + 1];
-	}
-	if(reset) SKR_HIP(hipMemset(r->scene->d_st_work, 0, sizeof(h)));
-	return SKR_OK;
+	return read_walk_work(r->scene->d_st_work, out, reset);
 }
 
 int skr_render_progressive_host(skr_renderer *r, const skr_options *opt, uint32_t every, uint8_t *h_rgb, float *h_rgbf, skr_progress_fn progress, void *user,
@@ -1105,12 +962,10 @@ int skr_render_progressive_host(skr_renderer *r, const skr_options *opt, uint32_
 	float *frame, *acc;
 	rc = progressive_scratch(r, n, frame, acc);
 	if(rc != SKR_OK) return rc;
-	skr_options pass = *opt;
-	pass.progressive_passes = 1;
 	float total_ms = 0;
 	for(uint32_t k = 0; k < passes; k++)
 	{
-		pass.seed = opt->seed + (uint64_t) k;
+		const skr_options pass = pass_options(opt, k);
 		const bool show = (k + 1) % every == 0 || k + 1 == passes;
 		const uint32_t h = (uint32_t) opt->height;
 		float ms = 0;
@@ -1150,20 +1005,21 @@ int skr_trace_rays(skr_renderer *r, const skr_ray *d_rays, uint32_t n, uint32_t 
 	const DeviceScene &sc = *r->scene;
 	SKR_HIP(hipSetDevice(sc.device));
 	TraceScene s{};
-	s.geom = sc.d_blob;
-	s.tris = sc.d_blob + sc.off_tris;
+	const LaunchScene v = launch_scene(r);
+	s.geom = v.blob;
+	s.tris = v.sec(SKR_SEC_tris);
 	s.ns = sc.info.n_spheres;
 	s.nt = sc.info.n_triangles;
-	s.chunk = sc.chunk_size;
+	s.chunk = sc.layout.chunk_size;
 	s.cam = f3{sc.info.camera[0], sc.info.camera[1], sc.info.camera[2]};
-	s.trees = query_trees(r);
+	s.trees = query_trees(v);
 	SphereTree st{};
-	if(sc.sphere_tree)
+	if(sc.layout.sphere_tree)
 	{ // the sphere searches walk the tree (a query counts nothing)
-		st = sphere_tree_of(r);
+		st = sphere_tree_of(v);
 		st.work = nullptr;
 	}
-	SKR_HIP(skr_launch_trace(s, reinterpret_cast<const float4 *>(d_rays), n, any_hit, d_out, (hipStream_t) stream, sc.sphere_tree ? &st : nullptr));
+	SKR_HIP(skr_launch_trace(s, reinterpret_cast<const float4 *>(d_rays), n, any_hit, d_out, (hipStream_t) stream, sc.layout.sphere_tree ? &st : nullptr));
 	return SKR_OK;
 }
 
@@ -1183,7 +1039,7 @@ int skr_camera_rays(skr_renderer *r, const skr_options *opt, uint32_t sample, sk
 	}
 	SKR_HIP(hipSetDevice(r->scene->device));
 	Lens lens;
-	SKR_HIP(skr_launch_camera_rays(camera_params(r, opt, opt->seed, sample), reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream, camera_lens(r, lens)));
+	SKR_HIP(skr_launch_camera_rays(camera_params(r->scene->info, opt, opt->seed, sample), reinterpret_cast<float4 *>(d_rays), (hipStream_t) stream, camera_lens(r->scene->layout, lens)));
 	return SKR_OK;
 }
 
@@ -1200,14 +1056,15 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	if(rc != SKR_OK) return rc;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(hipSetDevice(r->scene->device));
-	RenderParams p = camera_params(r, opt, opt->seed, sample);
+	RenderParams p = camera_params(r->scene->info, opt, opt->seed, sample);
 	p.width = (int32_t) SKR_SHADE_ROW; // the plan's rows: SKR_SHADE_ROW rays each, the last one partial
 	p.tile_rows = 1;
 	p.tile_stride = 1;
 	p.out_rows = (uint32_t) (((uint64_t) n + SKR_SHADE_ROW - 1) / SKR_SHADE_ROW);
 	p.band_rows = p.out_rows;
 	GenericFeatures f;
-	rc = launch_params(r, opt, p, f, true);
+	const LaunchScene v = launch_scene(r);
+	rc = launch_params(v, opt, p, f, true);
 	if(rc != SKR_OK) return rc;
 	p.grid_size = 0; // (one sample: `sample`)
 	GPlan pl;
@@ -1221,7 +1078,7 @@ int skr_shade_rays(skr_renderer *r, const skr_options *opt, const skr_ray *d_ray
 	q.keys = d_keys;
 	q.out = d_rgbf;
 	q.n = n;
-	q.trees = query_trees(r);
+	q.trees = query_trees(v);
 	r->last_levels = 0; // (the scratch no longer holds the node pipeline's tables of the last render)
 	g_variant = skr_generic_variant(true, f);
 	SKR_HIP(skr_launch_generic(p, pl, (hipStream_t) stream, nullptr, f, &q));
@@ -1282,37 +1139,6 @@ int skr_denoise_var(skr_renderer *r, uint32_t width, uint32_t height, const floa
 	return denoise(r, "skr_denoise_var", width, height, d_rgbf, d_hits, d_var, iterations, d_out_rgbf, d_out_rgb, stream);
 }
 
-int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf, float *kernel_ms)
-{
-	if(!r || !opt || (!h_rgb && !h_rgbf) || iterations > SKR_DENOISE_MAX_ITERATIONS)
-	{
-		skr_set_error("skr_render_denoised_host: bad argument");
-		return SKR_ERR_ARG;
-	}
-	int rc = check_options(opt); // before anything is sized from width x height
-	if(rc == SKR_OK) rc = refuse_lens(r, "skr_render_denoised_host");
-	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(r->scene->device));
-	const size_t n = (size_t) opt->width * opt->height;
-	ScratchLayout L; // the frame, its camera rays and guides, the filtered frame and its bytes
-	const size_t o_frame = L.take(n * 12), o_rays = L.take(n * sizeof(skr_ray)), o_hits = L.take(n * sizeof(skr_hit)), o_out = L.take(n * 12), o_rgb = L.take(n * 3);
-	rc = r->dnframe.grow(L.off);
-	if(rc != SKR_OK) return rc;
-	float *frame = r->dnframe.at<float>(o_frame), *out = r->dnframe.at<float>(o_out);
-	skr_ray *rays = r->dnframe.at<skr_ray>(o_rays);
-	skr_hit *hits = r->dnframe.at<skr_hit>(o_hits);
-	uint8_t *rgb = r->dnframe.at<uint8_t>(o_rgb);
-	skr_options guide_opt = *opt;
-	guide_opt.grid_size = 0; // the pixel centres
-	return timed_host(r, [&]() -> int {
-		int e = skr_render_tiles(r, opt, (uint32_t) opt->height, 0, 1, nullptr, frame, nullptr); // (the K-pass mean under progressive_passes)
-		if(e == SKR_OK) e = skr_camera_rays(r, &guide_opt, 0, rays, nullptr);
-		if(e == SKR_OK) e = skr_trace_rays(r, rays, (uint32_t) n, 0, hits, nullptr);
-		if(e == SKR_OK) e = skr_denoise(r, (uint32_t) opt->width, (uint32_t) opt->height, frame, hits, iterations, h_rgbf ? out : nullptr, h_rgb ? rgb : nullptr, nullptr);
-		return e;
-	}, {{h_rgb, rgb, n * 3}, {h_rgbf, out, n * 12}}, kernel_ms);
-}
-
 // ---- adaptive sampling (adaptive.hip): extra passes only for the pixels whose estimate is still noisy ----
 void skr_adaptive_default(skr_adaptive *a)
 {
@@ -1365,12 +1191,10 @@ static int render_adaptive(skr_renderer *r, const char *who, const skr_options *
 	if(rc != SKR_OK) return rc;
 	if(!r->h_count) SKR_HIP(hipHostMalloc((void **) &r->h_count, sizeof(uint32_t), hipHostMallocDefault));
 	const AdaptiveScratch s = skr_adaptive_carve(r->ad.p, pixels);
-	skr_options pass = *opt;
-	pass.progressive_passes = 1;
 	// the first min_passes passes: whole frames
 	for(int32_t k = 0; k < a->min_passes; k++)
 	{
-		pass.seed = opt->seed + (uint64_t) k;
+		const skr_options pass = pass_options(opt, (uint64_t) k);
 		rc = render_pass(r, &pass, (uint32_t) opt->height, TileSel(), nullptr, frame, stream);
 		if(rc != SKR_OK) return rc;
 		SKR_HIP(skr_launch_adaptive_fold(s, frame, nullptr, (uint32_t) pixels, k == 0, st));
@@ -1389,7 +1213,7 @@ static int render_adaptive(skr_renderer *r, const char *who, const skr_options *
 		m = *r->h_count;
 		in = out;
 		if(m == 0) break;
-		pass.seed = opt->seed + (uint64_t) n;
+		const skr_options pass = pass_options(opt, n);
 		const bool whole = r->sw.adaptive_path == 1 || (r->sw.adaptive_path == 0 && (double) m >= (double) SKR_ADAPTIVE_CROSSOVER * (double) pixels);
 		if(whole)
 		{ // frame path: the whole frame, its listed pixels gathered
@@ -1399,9 +1223,9 @@ static int render_adaptive(skr_renderer *r, const char *who, const skr_options *
 			continue;
 		}
 		// query path: per AA sample the listed pixels' camera rays, shaded with the pixel words as keys (skr_shade_rays)
-		RenderParams p = camera_params(r, opt, pass.seed, 0);
+		RenderParams p = camera_params(r->scene->info, opt, pass.seed, 0);
 		Lens lens;
-		const Lens *lp = camera_lens(r, lens);
+		const Lens *lp = camera_lens(r->scene->layout, lens);
 		for(uint32_t aa = 0; aa < (samples ? samples : 1u); aa++)
 		{
 			p.aa_index = aa;
@@ -1423,12 +1247,7 @@ int skr_render_adaptive_var(skr_renderer *r, const skr_options *opt, const skr_a
 
 int skr_render_adaptive(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *d_rgb, float *d_rgbf, uint32_t *d_passes, void *stream)
 {
-	if(!d_rgb && !d_rgbf && !d_passes)
-	{
-		skr_set_error("skr_render_adaptive: bad argument (null or misaligned array, or no output)");
-		return SKR_ERR_ARG;
-	}
-	return render_adaptive(r, "skr_render_adaptive", opt, a, d_rgb, d_rgbf, d_passes, nullptr, stream);
+	return render_adaptive(r, "skr_render_adaptive", opt, a, d_rgb, d_rgbf, d_passes, nullptr, stream); // (no variance image: an output of the three is needed)
 }
 
 int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint8_t *h_rgb, float *h_rgbf, uint32_t *h_passes, float *kernel_ms)
@@ -1452,6 +1271,55 @@ int skr_render_adaptive_host(skr_renderer *r, const skr_options *opt, const skr_
 					  {{h_rgb, d_rgb, pixels * 3}, {h_rgbf, d_rgbf, pixels * 12}, {h_passes, d_passes, pixels * 4}}, kernel_ms);
 }
 
+// The two denoised host entries: the frame — `a` null: opt's own (the K-pass mean under progressive_passes), else the adaptive mean
+// with its variance and pass counts — then its guides (the pixel centres' camera rays, traced) and the filter.  Only the pass counts
+// wanted: the adaptive frame alone.  The entries have checked their arguments.
+static int denoised_host(skr_renderer *r, const char *who, const skr_options *opt, const skr_adaptive *a, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf,
+						 uint32_t *h_passes, float *kernel_ms)
+{
+	if(r->scene->layout.lens_A > 0.0f)
+	{ // a scene with a lens has no denoised frame (include/skr.h skr_scene_set_lens)
+		skr_set_error("%s: a lens (--aperture) cannot be combined with the denoiser (its guides are the pinhole camera's first hits)", who);
+		return SKR_ERR_UNSUPPORTED;
+	}
+	SKR_HIP(hipSetDevice(r->scene->device));
+	const size_t n = (size_t) opt->width * opt->height;
+	ScratchLayout L; // the frame, (adaptive) its variance and pass counts, the camera rays and guides, the filtered frame and its bytes
+	const size_t o_frame = L.take(n * 12), o_var = a ? L.take(n * 4) : 0, o_passes = a ? L.take(n * 4) : 0, o_rays = L.take(n * sizeof(skr_ray)),
+				 o_hits = L.take(n * sizeof(skr_hit)), o_out = L.take(n * 12), o_rgb = L.take(n * 3);
+	const int rc = r->dnframe.grow(L.off);
+	if(rc != SKR_OK) return rc;
+	float *frame = r->dnframe.at<float>(o_frame), *var = a ? r->dnframe.at<float>(o_var) : nullptr, *out = r->dnframe.at<float>(o_out);
+	uint32_t *passes = a ? r->dnframe.at<uint32_t>(o_passes) : nullptr;
+	skr_ray *rays = r->dnframe.at<skr_ray>(o_rays);
+	skr_hit *hits = r->dnframe.at<skr_hit>(o_hits);
+	uint8_t *rgb = r->dnframe.at<uint8_t>(o_rgb);
+	skr_options guide_opt = *opt;
+	guide_opt.grid_size = 0; // the pixel centres
+	const bool filtered = h_rgb || h_rgbf;
+	return timed_host(r, [&]() -> int {
+		int e = a ? skr_render_adaptive_var(r, opt, a, nullptr, frame, h_passes ? passes : nullptr, var, nullptr)
+				  : skr_render_tiles(r, opt, (uint32_t) opt->height, 0, 1, nullptr, frame, nullptr);
+		if(e == SKR_OK && filtered) e = skr_camera_rays(r, &guide_opt, 0, rays, nullptr);
+		if(e == SKR_OK && filtered) e = skr_trace_rays(r, rays, (uint32_t) n, 0, hits, nullptr);
+		if(e == SKR_OK && filtered)
+			e = denoise(r, a ? "skr_denoise_var" : "skr_denoise", (uint32_t) opt->width, (uint32_t) opt->height, frame, hits, var, iterations, h_rgbf ? out : nullptr,
+						h_rgb ? rgb : nullptr, nullptr);
+		return e;
+	}, {{h_rgb, rgb, n * 3}, {h_rgbf, out, n * 12}, {h_passes, passes, n * 4}}, kernel_ms);
+}
+
+int skr_render_denoised_host(skr_renderer *r, const skr_options *opt, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf, float *kernel_ms)
+{
+	if(!r || !opt || (!h_rgb && !h_rgbf) || iterations > SKR_DENOISE_MAX_ITERATIONS)
+	{
+		skr_set_error("skr_render_denoised_host: bad argument");
+		return SKR_ERR_ARG;
+	}
+	const int rc = check_options(opt); // before anything is sized from width x height
+	return rc != SKR_OK ? rc : denoised_host(r, "skr_render_denoised_host", opt, nullptr, iterations, h_rgb, h_rgbf, nullptr, kernel_ms);
+}
+
 int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, const skr_adaptive *a, uint32_t iterations, uint8_t *h_rgb, float *h_rgbf,
 									  uint32_t *h_passes, float *kernel_ms)
 {
@@ -1460,32 +1328,8 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 		skr_set_error("skr_render_adaptive_denoised_host: bad argument (no output, or iterations over %d)", SKR_DENOISE_MAX_ITERATIONS);
 		return SKR_ERR_ARG;
 	}
-	int rc = check_adaptive(opt, a, "skr_render_adaptive_denoised_host"); // before anything is sized from width x height
-	if(rc == SKR_OK) rc = refuse_lens(r, "skr_render_adaptive_denoised_host");
-	if(rc != SKR_OK) return rc;
-	SKR_HIP(hipSetDevice(r->scene->device));
-	const size_t n = (size_t) opt->width * opt->height;
-	ScratchLayout L; // the adaptive mean, its variance and pass counts, the camera rays and guides, the filtered frame and its bytes
-	const size_t o_frame = L.take(n * 12), o_var = L.take(n * 4), o_passes = L.take(n * 4), o_rays = L.take(n * sizeof(skr_ray)), o_hits = L.take(n * sizeof(skr_hit)),
-				 o_out = L.take(n * 12), o_rgb = L.take(n * 3);
-	rc = r->dnframe.grow(L.off);
-	if(rc != SKR_OK) return rc;
-	float *frame = r->dnframe.at<float>(o_frame), *var = r->dnframe.at<float>(o_var), *out = r->dnframe.at<float>(o_out);
-	uint32_t *passes = r->dnframe.at<uint32_t>(o_passes);
-	skr_ray *rays = r->dnframe.at<skr_ray>(o_rays);
-	skr_hit *hits = r->dnframe.at<skr_hit>(o_hits);
-	uint8_t *rgb = r->dnframe.at<uint8_t>(o_rgb);
-	skr_options guide_opt = *opt;
-	guide_opt.grid_size = 0; // the pixel centres
-	const bool filtered = h_rgb || h_rgbf; // (only the pass counts: the adaptive frame alone)
-	return timed_host(r, [&]() -> int {
-		int e = skr_render_adaptive_var(r, opt, a, nullptr, frame, h_passes ? passes : nullptr, var, nullptr);
-		if(e == SKR_OK && filtered) e = skr_camera_rays(r, &guide_opt, 0, rays, nullptr);
-		if(e == SKR_OK && filtered) e = skr_trace_rays(r, rays, (uint32_t) n, 0, hits, nullptr);
-		if(e == SKR_OK && filtered)
-			e = skr_denoise_var(r, (uint32_t) opt->width, (uint32_t) opt->height, frame, hits, var, iterations, h_rgbf ? out : nullptr, h_rgb ? rgb : nullptr, nullptr);
-		return e;
-	}, {{h_rgb, rgb, n * 3}, {h_rgbf, out, n * 12}, {h_passes, passes, n * 4}}, kernel_ms);
+	const int rc = check_adaptive(opt, a, "skr_render_adaptive_denoised_host"); // before anything is sized from width x height
+	return rc != SKR_OK ? rc : denoised_host(r, "skr_render_adaptive_denoised_host", opt, a, iterations, h_rgb, h_rgbf, h_passes, kernel_ms);
 }
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
@@ -1501,5 +1345,14 @@ int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stre
 int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
 							   float *d_rgbf, void *stream)
 {
-	return render_tile_list(r, opt, tile_rows, d_tiles, n_slots, table_id, d_rgb, d_rgbf, stream);
+	if(!d_tiles)
+	{
+		skr_set_error("skr_render_tile_list: no tile table");
+		return SKR_ERR_ARG;
+	}
+	TileSel ts;
+	ts.d_table = d_tiles;
+	ts.n_slots = n_slots;
+	ts.table_id = table_id;
+	return render_impl(r, opt, tile_rows, ts, d_rgb, d_rgbf, stream);
 }

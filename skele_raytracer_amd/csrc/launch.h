@@ -161,7 +161,7 @@ static uint32_t skr_largest_band(uint32_t all, Fits fits)
 // SKR_TRACE_BY_NODE 1: a trace wave holds a block of 64 consecutive nodes, one per lane, and runs over sibling pairs j; its header for
 // pair j is row (node >> 6) * PP + j and a node's bit in the ballots is node & 63.  0 (A/B builds): a lane is one sibling pair
 // tp = node * PP + j, a wave 64 consecutive pairs: row tp >> 6, bit tp & 63.  Either way a row's wave appends at most 128 hits, to
-// region row & 63.  The kernels, the plan and the tests (api.cpp skr_trace_header_map) all ask these functions.
+// region row & 63.  The kernels, the plan and the tests (render_nodes.hip skr_trace_header_map) all ask these functions.
 #ifndef SKR_TRACE_BY_NODE
 #define SKR_TRACE_BY_NODE 1
 #endif

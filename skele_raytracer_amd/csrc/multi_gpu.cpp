@@ -33,12 +33,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/skr.h"
-
-void skr_set_error(const char *fmt, ...);
-void skr_copy_switches(skr_renderer *dst, const skr_renderer *src); // api.cpp
-int skr_render_tile_list_owned(skr_renderer *r, const skr_options *opt, uint32_t tile_rows, const uint32_t *d_tiles, uint32_t n_slots, uint64_t table_id, uint8_t *d_rgb,
-							   float *d_rgbf, void *stream); // api.cpp
+#include "api_internal.h"
 
 namespace {
 
@@ -79,16 +74,6 @@ Rccl &rccl()
 	return r;
 }
 
-#define SKR_HIP(call)                                                                                   \
-	do                                                                                                  \
-	{                                                                                                   \
-		hipError_t e_ = (call);                                                                         \
-		if(e_ != hipSuccess)                                                                            \
-		{                                                                                               \
-			skr_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);  \
-			return SKR_ERR_HIP;                                                                         \
-		}                                                                                               \
-	} while(0)
 #define SKR_NCCL(call)                                                                                          \
 	do                                                                                                          \
 	{                                                                                                           \

@@ -8,7 +8,7 @@ FILES=${@:-render_nodes}
 make -j4 lib > /dev/null
 mkdir -p build/var_$NAME skele_raytracer_amd/lib/var
 OBJS=""
-for o in render_kernel render_wave render_nodes render_generic accumulate trace_rays denoise adaptive api scene_host scene_masks scene_trees multi_gpu; do
+for o in $(make -s print-objs | xargs -n1 basename -s .o); do # (the Makefile's list: a copy here has drifted before)
   if echo " $FILES " | grep -q " $o "; then
     src=skele_raytracer_amd/csrc/$o.hip; x=""
     [ -f $src ] || { src=skele_raytracer_amd/csrc/$o.cpp; x="-x hip"; }

@@ -1,4 +1,4 @@
-// Host-code sanitizer run (CPU only): loader, finalize, every table builder, the getters, PPM writer.  Prints one 64-bit digest
+// Host-code sanitizer run (CPU only): loader, finalize, every table builder, the getters, the scene blob's packer, PPM writer.  Prints one 64-bit digest
 // (FNV-1a over the 32-bit words) per derived table and scene, so that two builds of the host code can be compared table by table
 // (the digests depend on the host's libm: compare builds on one machine).
 #include <cstdio>
@@ -8,6 +8,7 @@
 #include <string>
 #include "skr.h"
 #include "../skele_raytracer_amd/csrc/tri_chunks.h" // SKR_CULL_LEVELS (plain #defines)
+#include "../skele_raytracer_amd/csrc/scene_pack.h" // skr_scene_pack, the blob's section table
 
 // internal exports of the library (tests only: not in include/skr.h)
 extern "C" {
@@ -113,6 +114,19 @@ void spot_cones_table(const skr_scene *sc, const char *name, const char *stage)
 	print(name, stage, "spot_cones", Digest().word(n).words(cones.data(), cones.size() - 1));
 }
 
+// the scene as a renderer would upload it (scene_pack.h): the rows and the section table
+void blob_table(const skr_scene *sc, const char *name, const char *stage)
+{
+	int64_t first[SKR_BLOB_SECTION_COUNT], count[SKR_BLOB_SECTION_COUNT], scalars[2];
+	const int64_t n = skr_scene_pack(sc, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+	std::vector<uint32_t> rows((size_t) n * 4 + 1);
+	skr_scene_pack(sc, first, count, rows.data(), n, nullptr, scalars);
+	Digest d;
+	d.words(rows.data(), rows.size() - 1);
+	for(int k = 0; k < SKR_BLOB_SECTION_COUNT; k++) d.word((uint32_t) first[k]).word((uint32_t) count[k]);
+	print(name, stage, "blob", d.word((uint32_t) scalars[0]).word((uint32_t) scalars[1]));
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -132,6 +146,7 @@ int main(int argc, char **argv)
 		culling_tables(sc, info.n_triangles, argv[a]);
 		sphere_tree_table(sc, info.n_spheres, argv[a]);
 		spot_cones_table(sc, argv[a], "built");
+		blob_table(sc, argv[a], "built");
 		// the rebuild paths: new lights, then the tests' shrunk margins
 		const float spots[2][11] = {{1.0f, 0.9f, 0.8f, 0.5f, 3.0f, 1.5f, 0.1f, -1.0f, -0.2f, 20.0f, 35.0f},
 									{0.3f, 0.4f, 2.0f, -2.0f, 1.0f, -3.0f, 1.0f, 0.5f, 1.0f, 0.0f, 90.0f}};
@@ -139,10 +154,15 @@ int main(int argc, char **argv)
 		if(rc != 0) printf("%s: skr_scene_set_spot_lights rc %d (%s)\n", argv[a], rc, skr_last_error());
 		shadow_tables(sc, info.n_spheres, argv[a], "spots");
 		spot_cones_table(sc, argv[a], "spots");
+		blob_table(sc, argv[a], "spots");
 		skr_scene_rebuild_shadow_surface(sc, 0.5, 1.0);
 		shadow_tables(sc, info.n_spheres, argv[a], "rho/2");
+		blob_table(sc, argv[a], "rho/2");
 		skr_scene_rebuild_shadow_surface(sc, 1.0, 0.5);
 		shadow_tables(sc, info.n_spheres, argv[a], "cone/2");
+		blob_table(sc, argv[a], "cone/2");
+		skr_scene_set_sphere_tree(sc, 1);
+		blob_table(sc, argv[a], "sphere_tree");
 		skr_scene_destroy(sc);
 	}
 	std::vector<uint8_t> px(7 * 5 * 3, 200);

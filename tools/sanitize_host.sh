@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 mkdir -p build
 CSRC=skele_raytracer_amd/csrc
 FLAGS=${SANITIZE_HOST_FLAGS:--g -O1 -fsanitize=address,undefined,float-cast-overflow -fno-omit-frame-pointer}
-SRCS=${SANITIZE_HOST_SRCS:-$CSRC/scene_host.cpp $CSRC/scene_masks.cpp $CSRC/scene_trees.cpp}
+SRCS=${SANITIZE_HOST_SRCS:-$CSRC/scene_host.cpp $CSRC/scene_masks.cpp $CSRC/scene_trees.cpp $CSRC/scene_pack.cpp}
 rm -rf build/sanitize_obj && mkdir -p build/sanitize_obj
 pids=""
 for f in tools/sanitize_host.cpp $SRCS; do # (side by side)
