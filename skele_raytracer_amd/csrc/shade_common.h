@@ -262,12 +262,15 @@ SKR_DEV void best_resolve(const SceneView &sv, f3 o, f3 d, float four_a, BestSta
 	}
 }
 
-// The conservative line-sphere test of the culling data (scene_trees.cpp build_triangle_chunks): false only where
-// no triangle below the entry can accept this lane's line.  A = {centre, R^2}; B = {axis / kappa, R_tight^2}: a ray
-// that is not grazing for the entry's (nearly coplanar) triangles, (d . axis / kappa)^2 >= d . d, is held to the
-// tight radius.  NaN anywhere => true.
+// The line part of the culling tests (scene_trees.cpp build_triangle_chunks), for an entry A = {centre, R^2}, B = {axis / kappa,
+// R_tight^2}: e = C - o, |e x d|^2 and R^2 |d|^2.  A ray that is not grazing for the entry's (nearly coplanar) triangles,
+// (d . axis / kappa)^2 >= d . d, is held to the tight radius.
+struct LinePart {
+	f3 e;
+	float cr2, lim;
+};
 template <bool CONES>
-SKR_DEV bool line_touches(const RayConst &r, float dd, float4 A, float4 B)
+SKR_DEV LinePart line_part(const RayConst &r, float dd, float4 A, float4 B)
 {
 	const f3 e = ld3(A) - r.o;
 	const f3 cr = cross3(e, r.d);
@@ -277,17 +280,55 @@ SKR_DEV bool line_touches(const RayConst &r, float dd, float4 A, float4 B)
 		const float gb = dot3(r.d, ld3(B));
 		R2 = (gb * gb >= dd) ? B.w : A.w;
 	}
-	return !(dot3(cr, cr) > R2 * dd); // |e x d|^2 <= R^2 |d|^2
+	return LinePart{e, dot3(cr, cr), R2 * dd};
 }
 
-// A line that misses a conservative sphere cannot pass the test for any triangle below it, so a node or chunk that
-// no lane's line touches is skipped whole.  The levels above the chunks are stored depth-first with skip links:
-// one wave-uniform index, no stack; both possible successors are fetched (scalar loads: mesh_row) while the sphere is tested.
-template <bool CONES, bool COUNT>
-SKR_DEV bool tree_walk(const SceneView &sv, const RayConst &r, float tmin)
+// The conservative line-sphere test of the culling data: false only where no triangle below the entry can accept this lane's line,
+// |e x d|^2 > R^2 |d|^2.  NaN anywhere => true.
+template <bool CONES>
+SKR_DEV bool line_touches(const RayConst &r, float dd, float4 A, float4 B)
 {
-	bool hit = false;
-	const float dd = r.two_a * 0.5f; // dot(d, d)
+	const LinePart p = line_part<CONES>(r, dd, A, B);
+	return !(p.cr2 > p.lim);
+}
+
+// lanes x rays of a mask of up to two rays per lane (wave-uniform: scalar registers)
+SKR_DEV uint32_t lanes_of(uint32_t mask) { return (uint32_t) __popcll(__ballot((mask & 1u) != 0u)) + (uint32_t) __popcll(__ballot((mask & 2u) != 0u)); }
+
+// The instance of a mesh walk a scene view asks for: f(cones, count) with the types of two compile-time flags — the entries' tight
+// radii are tested (sv.cones), the walk counts its work (counting costs the dragon walk 19 %: the counting instances run only while
+// sv.tri_work is set — skr_renderer_count_triangle_work).
+template <bool V>
+struct Flag {
+	static constexpr bool value = V;
+};
+template <typename F>
+SKR_DEV void mesh_instance(const SceneView &sv, F f)
+{
+	if(__builtin_expect(sv.tri_work != nullptr, 0))
+	{
+		if(sv.cones) f(Flag<true>{}, Flag<true>{});
+		else f(Flag<false>{}, Flag<true>{});
+	}
+	else if(sv.cones) f(Flag<true>{}, Flag<false>{});
+	else f(Flag<false>{}, Flag<false>{});
+}
+
+// The walk over the triangle tree `sv.chunks` (sv.nchunks > 0 nodes).  A line that misses a conservative sphere cannot pass the test
+// for any triangle below it, so a node or chunk that no lane wants is skipped whole.  The levels above the chunks are stored
+// depth-first with skip links: one wave-uniform index, no stack, rows through the scalar cache (mesh_row); both successors of a node
+// are fetched while its sphere is tested.  The chunk entries of a height-1 node are contiguous: a tight loop, entries and triangles
+// loaded where they are used (asked for one ahead, the walks of any_triangle_closer and shadow_triangles were the slower ones: dragon
+// 0.915 against 0.860 ms, the shadowed dragon 14.4 against 13.1 ms; 20 scalar registers less).  `live()` = the rays of the lane (a bit
+// each, or a bool) that still want tests; `touch(A, B)` = those of them that want this entry: an entry is entered when any lane wants
+// it, and `tri(v0, e1, e2, slot, mine)` sees every triangle of a chunk some lane wants, as its three rows, with the bits of its own
+// lane.  The wave leaves after a height-1 node once no lane is live.  Counted: an entry per live ray that it is tested for, a
+// triangle per ray that is live and wants its chunk.
+// Reads past the end: only the successors of the last node, which are the pad node behind the nodes of every set of both trees
+// (scene_trees.cpp build_triangle_chunk_level), at every bound on |d|.
+template <bool COUNT, typename V, typename T, typename S>
+SKR_DEV void mesh_walk(const SceneView &sv, V live, T touch, S tri)
+{
 	int i = 0;
 	uint32_t n_cull = 0, n_tri = 0; // (wave-uniform: scalar registers)
 	const float4 *chunk_ent = sv.chunks + 3 * (sv.nchunks + 1); // behind the nodes and their pad
@@ -298,39 +339,31 @@ SKR_DEV bool tree_walk(const SceneView &sv, const RayConst &r, float tmin)
 		// first child (or the next node after a height-1 node) and next sibling (padded past the end)
 		const float4 A_in = mesh_row(sv.chunks, 3 * i + 3), B_in = mesh_row(sv.chunks, 3 * i + 4), lk_in = mesh_row(sv.chunks, 3 * i + 5);
 		const float4 A_out = mesh_row(sv.chunks, 3 * i_out), B_out = mesh_row(sv.chunks, 3 * i_out + 1), lk_out = mesh_row(sv.chunks, 3 * i_out + 2);
-		if(COUNT) n_cull += (uint32_t) __popcll(__ballot(!hit));
-		const bool enter = __any(!hit && line_touches<CONES>(r, dd, A, B));
+		if(COUNT) n_cull += lanes_of(live());
+		const bool enter = __any(touch(A, B) != 0);
 		const int count = __float_as_int(lk.z);
 		if(enter && count > 0)
-		{ // height 1: its chunk entries are contiguous — tight loop, next entry prefetched
+		{ // height 1: its chunk entries are contiguous
 			const int c0 = __float_as_int(lk.y), c1 = c0 + count;
-			float4 cA_next = mesh_row(chunk_ent, 2 * c0), cB_next = mesh_row(chunk_ent, 2 * c0 + 1);
 			for(int c = c0; c < c1; c++)
 			{
-				const float4 cA = cA_next, cB = cB_next;
-				cA_next = mesh_row(chunk_ent, 2 * c + 2);
-				cB_next = mesh_row(chunk_ent, 2 * c + 3);
-				if(COUNT) n_cull += (uint32_t) __popcll(__ballot(!hit));
-				const bool mine = !hit && line_touches<CONES>(r, dd, cA, cB);
-				if(__any(mine))
+				const float4 cA = mesh_row(chunk_ent, 2 * c), cB = mesh_row(chunk_ent, 2 * c + 1);
+				if(COUNT) n_cull += lanes_of(live());
+				const auto mine = touch(cA, cB);
+				if(__any(mine != 0))
 				{
 					const int i0 = c * sv.chunk, i1 = (i0 + sv.chunk < sv.nt) ? i0 + sv.chunk : sv.nt;
-					// (one triangle per scalar-cache round trip, the next one asked for meanwhile; a whole 4-triangle chunk asked for at once was measured
+					// (one triangle per scalar-cache round trip; a whole 4-triangle chunk asked for at once was measured
 					// slower: dragon 1.19 -> 1.27 ms, 48 more SGPRs live)
-					float4 n0 = mesh_row(sv.tris, 3 * i0), n1 = mesh_row(sv.tris, 3 * i0 + 1), n2 = mesh_row(sv.tris, 3 * i0 + 2);
 					for(int k = i0; k < i1; k++)
 					{
-						const f3 v0 = ld3(n0), e1 = ld3(n1), e2 = ld3(n2);
-						n0 = mesh_row(sv.tris, 3 * k + 3);
-						n1 = mesh_row(sv.tris, 3 * k + 4);
-						n2 = mesh_row(sv.tris, 3 * k + 5);
-						float t;
-						if(COUNT) n_tri += (uint32_t) __popcll(__ballot(mine && !hit));
-						if(mine && !hit && triangle_hit(r.o, r.d, v0, e1, e2, t) && t < tmin) hit = true;
+						const float4 v0 = mesh_row(sv.tris, 3 * k), e1 = mesh_row(sv.tris, 3 * k + 1), e2 = mesh_row(sv.tris, 3 * k + 2);
+						if(COUNT) n_tri += lanes_of(mine & live());
+						tri(v0, e1, e2, k, mine);
 					}
 				}
 			}
-			if(__all(hit)) break;
+			if(!__any(live() != 0)) break;
 		}
 		i = enter ? i + 1 : i_out;
 		A = enter ? A_in : A_out;
@@ -338,37 +371,51 @@ SKR_DEV bool tree_walk(const SceneView &sv, const RayConst &r, float tmin)
 		lk = enter ? lk_in : lk_out;
 	}
 	if(COUNT) tri_work_add(sv, n_cull, n_tri);
-	return hit;
+}
+
+// mesh_walk() where the wave has no tree (sv.nchunks == 0: SKR_NO_CULL, directions longer than the bounds were built for, a query ray
+// that starts outside the tree's ball): `tri` sees every triangle with the lane's live rays.  Triangle k + 1 is fetched while k is
+// tested (tris[] carries one pad triangle so the prefetch needs no bounds test); the wave looks every eighth triangle whether a lane
+// is still live.  The tests are counted while sv.tri_work is set.
+template <typename V, typename S>
+SKR_DEV void mesh_all(const SceneView &sv, V live, S tri)
+{
+	uint32_t n_tri = 0;
+	float4 n0 = mesh_row(sv.tris, 0), n1 = mesh_row(sv.tris, 1), n2 = mesh_row(sv.tris, 2);
+	for(int k = 0; k < sv.nt; k++)
+	{
+		const float4 v0 = n0, e1 = n1, e2 = n2;
+		n0 = mesh_row(sv.tris, 3 * k + 3);
+		n1 = mesh_row(sv.tris, 3 * k + 4);
+		n2 = mesh_row(sv.tris, 3 * k + 5);
+		if(sv.tri_work) n_tri += lanes_of(live());
+		tri(v0, e1, e2, k, live());
+		if((k & 7) == 7 && !__any(live() != 0)) break;
+	}
+	tri_work_add(sv, 0u, n_tri);
 }
 
 // raytrace.h:171-186.  The outcome is binary: once a triangle passes with
 // t < min_distance the sample is black (:221-224) whatever comes later, so a
 // lane stops testing at its first accepted triangle and the wave leaves the
-// loop when every active lane has.
+// walk when every active lane has.  (No t > 0 test: the reference has none.)
 SKR_DEV bool any_triangle_closer(const SceneView &sv, const RayConst &r, float tmin)
 {
-	if(sv.nchunks > 0)
-	{ // (counting costs the dragon walk 19 %: the counting instantiation runs only while sv.tri_work is set — skr_renderer_count_triangle_work)
-		if(__builtin_expect(sv.tri_work != nullptr, 0)) return sv.cones ? tree_walk<true, true>(sv, r, tmin) : tree_walk<false, true>(sv, r, tmin);
-		return sv.cones ? tree_walk<true, false>(sv, r, tmin) : tree_walk<false, false>(sv, r, tmin);
-	}
 	bool hit = false;
-	uint32_t n_tri = 0;
-	// wave-uniform addresses => scalar loads; triangle i+1 is fetched while i is tested
-	// (tris[] carries one pad triangle so the prefetch needs no bounds test)
-	float4 n0 = mesh_row(sv.tris, 0), n1 = mesh_row(sv.tris, 1), n2 = mesh_row(sv.tris, 2);
-	for(int i = 0; i < sv.nt; i++)
+	const float dd = r.two_a * 0.5f; // dot(d, d)
+	auto live = [&] { return !hit; };
+	auto tri = [&](const float4 v0, const float4 e1, const float4 e2, int, bool mine)
 	{
-		const f3 v0 = ld3(n0), e1 = ld3(n1), e2 = ld3(n2);
-		n0 = mesh_row(sv.tris, 3 * i + 3);
-		n1 = mesh_row(sv.tris, 3 * i + 4);
-		n2 = mesh_row(sv.tris, 3 * i + 5);
 		float t;
-		if(sv.tri_work) n_tri += (uint32_t) __popcll(__ballot(!hit));
-		if(!hit && triangle_hit(r.o, r.d, v0, e1, e2, t) && t < tmin) hit = true;
-		if((i & 7) == 7 && __all(hit)) break;
-	}
-	tri_work_add(sv, 0u, n_tri);
+		if(mine && !hit && triangle_hit(r.o, r.d, ld3(v0), ld3(e1), ld3(e2), t) && t < tmin) hit = true;
+	};
+	if(sv.nchunks > 0)
+		mesh_instance(sv, [&](auto cones, auto count)
+		{
+			constexpr bool CONES = decltype(cones)::value;
+			mesh_walk<decltype(count)::value>(sv, live, [&](const float4 A, const float4 B) { return !hit && line_touches<CONES>(r, dd, A, B); }, tri);
+		});
+	else mesh_all(sv, live, tri);
 	return hit;
 }
 
@@ -554,10 +601,8 @@ SKR_DEV void sphere_work_add(const SphereTree &st, uint32_t n_cull, uint32_t n_s
 		}
 	}
 }
-// lanes x rays of a mask of up to two rays per lane (wave-uniform: scalar registers)
-SKR_DEV uint32_t lanes_of(uint32_t mask) { return (uint32_t) __popcll(__ballot((mask & 1u) != 0u)) + (uint32_t) __popcll(__ballot((mask & 2u) != 0u)); }
 
-// The walk of tree_walk() over the sphere tree: one wave-uniform index over the depth-first nodes, no stack, rows through the scalar
+// The walk of mesh_walk() over the sphere tree: one wave-uniform index over the depth-first nodes, no stack, rows through the scalar
 // cache; both successors of a node are fetched while its culling sphere is tested.  `live()` = the rays of the lane (a bit each) that
 // still want tests; `touch(A, kappa, smallest file index below)` = those of them that want this entry: an entry is entered when any
 // lane wants it, and `sphere(row, file index, mine)` sees every sphere of a chunk some lane wants, with the bits of its own lane.
@@ -1108,22 +1153,16 @@ SKR_DEV void tri_consider(const RayConst &r, bool mine, f3 v0, float4 n1, float4
 template <bool CONES>
 SKR_DEV bool entry_may_hold_nearer(const RayConst &r, float dd, float4 A, float4 B, float t_best)
 {
-	const f3 e = ld3(A) - r.o;
-	const f3 cr = cross3(e, r.d);
-	float R2 = A.w;
-	if constexpr(CONES)
-	{
-		const float gb = dot3(r.d, ld3(B));
-		R2 = (gb * gb >= dd) ? B.w : A.w;
-	}
-	const float lim = R2 * dd;
-	if(dot3(cr, cr) > lim) return false; // the line misses the sphere (NaN: falls through, "enter")
-	const float lhs = dot3(r.d, e) - t_best * dd;
-	return !(lhs > 0.0f && lhs * lhs > lim * 1.27f);
+	const LinePart p = line_part<CONES>(r, dd, A, B);
+	if(p.cr2 > p.lim) return false; // the line misses the sphere (NaN: falls through, "enter")
+	const float lhs = dot3(r.d, p.e) - t_best * dd;
+	return !(lhs > 0.0f && lhs * lhs > p.lim * 1.27f);
 }
 
-// The walk of tree_walk() as a closest-hit walk: every chunk whose conservative sphere this lane's line touches in front of its
-// running best is tested to the end (the spheres bound the accept test itself, whatever t comes out).
+// The closest-hit walk: every chunk whose conservative sphere this lane's line touches in front of its running best is tested to the
+// end (the spheres bound the accept test itself, whatever t comes out).  mesh_walk() written out by hand: as its visitor the ray
+// queries' 2^22 random rays on dragon.scn took 21.11 against 21.02 ms (spreads 0.02 and 0.04; with entries and triangles asked for
+// one ahead 24.3 ms), the frame and the camera rays what they take here.
 template <bool CONES>
 SKR_DEV void tree_walk_closest(const SceneView &sv, const RayConst &r, int from_tri, TriBest &b)
 {
@@ -1160,7 +1199,7 @@ SKR_DEV void tree_walk_closest(const SceneView &sv, const RayConst &r, int from_
 		B = enter ? B_in : B_out;
 		lk = enter ? lk_in : lk_out;
 	}
-	tri_work_add(sv, n_cull, n_tri);
+	if(sv.tri_work) tri_work_add(sv, n_cull, n_tri);
 }
 
 SKR_DEV void closest_triangle(const SceneView &sv, const RayConst &r, int from_tri, TriBest &b)
@@ -1192,124 +1231,50 @@ SKR_DEV bool shadow_triangle_hit(f3 o, f3 d, f3 v0, f3 e1, f3 e2, int file, int 
 	return triangle_hit(o, d, v0, e1, e2, t) && t > 0.0f && t < tmax && file != own;
 }
 
-// tree_walk() for shadow rays: one wave-uniform index over the tree `sv.chunks`, every entry that is loaded is tested against all NR
-// rays of the lane (the walk is bound by its scalar loads, which the rays of a pair share).  A ray leaves at its first occluder, the
-// wave when no ray of any lane is live.  The line test only: the tree proves nothing about the segment between o and the light.
-template <int NR, bool CONES, bool COUNT>
-SKR_DEV void tree_walk_shadow(const SceneView &sv, ShadowRays<NR> &s)
-{
-	RayConst r[NR];
-	float dd[NR];
-#pragma unroll
-	for(int k = 0; k < NR; k++)
-	{
-		r[k] = make_ray(s.o, s.d[k]);
-		dd[k] = dot3(s.d[k], s.d[k]);
-	}
-	int i = 0;
-	uint32_t n_cull = 0, n_tri = 0; // (wave-uniform: scalar registers)
-	const float4 *chunk_ent = sv.chunks + 3 * (sv.nchunks + 1); // behind the nodes and their pad
-	float4 A = mesh_row(sv.chunks, 0), B = mesh_row(sv.chunks, 1), lk = mesh_row(sv.chunks, 2);
-	while(i < sv.nchunks)
-	{
-		const int i_out = __float_as_int(lk.x);
-		const float4 A_in = mesh_row(sv.chunks, 3 * i + 3), B_in = mesh_row(sv.chunks, 3 * i + 4), lk_in = mesh_row(sv.chunks, 3 * i + 5);
-		const float4 A_out = mesh_row(sv.chunks, 3 * i_out), B_out = mesh_row(sv.chunks, 3 * i_out + 1), lk_out = mesh_row(sv.chunks, 3 * i_out + 2);
-		bool touch = false;
-#pragma unroll
-		for(int k = 0; k < NR; k++)
-		{
-			if(COUNT) n_cull += (uint32_t) __popcll(__ballot(s.live[k]));
-			touch = touch || (s.live[k] && line_touches<CONES>(r[k], dd[k], A, B));
-		}
-		const bool enter = __any(touch);
-		const int count = __float_as_int(lk.z);
-		if(enter && count > 0)
-		{ // height 1: its chunk entries are contiguous
-			const int c0 = __float_as_int(lk.y), c1 = c0 + count;
-			float4 cA_next = mesh_row(chunk_ent, 2 * c0), cB_next = mesh_row(chunk_ent, 2 * c0 + 1);
-			for(int c = c0; c < c1; c++)
-			{
-				const float4 cA = cA_next, cB = cB_next;
-				cA_next = mesh_row(chunk_ent, 2 * c + 2);
-				cB_next = mesh_row(chunk_ent, 2 * c + 3);
-				bool mine[NR], some = false;
-#pragma unroll
-				for(int k = 0; k < NR; k++)
-				{
-					if(COUNT) n_cull += (uint32_t) __popcll(__ballot(s.live[k]));
-					mine[k] = s.live[k] && line_touches<CONES>(r[k], dd[k], cA, cB);
-					some = some || mine[k];
-				}
-				if(__any(some))
-				{
-					const int i0 = c * sv.chunk, i1 = (i0 + sv.chunk < sv.nt) ? i0 + sv.chunk : sv.nt;
-					float4 n0 = mesh_row(sv.tris, 3 * i0), n1 = mesh_row(sv.tris, 3 * i0 + 1), n2 = mesh_row(sv.tris, 3 * i0 + 2);
-					for(int t = i0; t < i1; t++)
-					{
-						const f3 v0 = ld3(n0), e1 = ld3(n1), e2 = ld3(n2);
-						const int file = __float_as_int(n1.w);
-						n0 = mesh_row(sv.tris, 3 * t + 3);
-						n1 = mesh_row(sv.tris, 3 * t + 4);
-						n2 = mesh_row(sv.tris, 3 * t + 5);
-#pragma unroll
-						for(int k = 0; k < NR; k++)
-						{
-							if(COUNT) n_tri += (uint32_t) __popcll(__ballot(mine[k] && s.live[k]));
-							if(mine[k] && s.live[k] && shadow_triangle_hit(s.o, s.d[k], v0, e1, e2, file, s.own, s.tmax[k])) s.live[k] = false;
-						}
-					}
-				}
-			}
-			bool some_live = false;
-#pragma unroll
-			for(int k = 0; k < NR; k++) some_live = some_live || s.live[k];
-			if(!__any(some_live)) break;
-		}
-		i = enter ? i + 1 : i_out;
-		A = enter ? A_in : A_out;
-		B = enter ? B_in : B_out;
-		lk = enter ? lk_in : lk_out;
-	}
-	if(COUNT) tri_work_add(sv, n_cull, n_tri);
-}
-
-// The shadow walk of a lane's NR rays: the tree in sv.chunks (sv.nchunks nodes), or every triangle where the wave has none
-// (sv.nchunks == 0: SKR_NO_CULL, a ray that starts outside the tree's ball).  Both give the same answers.
+// The shadow visitor of mesh_walk() for a lane's NR rays: every entry that is loaded is tested against all of them (the walk is bound
+// by its scalar loads, which the rays of a pair share).  A ray leaves at its first occluder, the wave when no ray of any lane is live.
+// The line test only: the tree proves nothing about the segment between o and the light.  Without a tree (SKR_NO_CULL, a ray that
+// starts outside the tree's ball) every triangle is tested; both give the same answers.
 template <int NR>
 SKR_DEV void shadow_triangles(const SceneView &sv, ShadowRays<NR> &s)
 {
-	if(sv.nchunks > 0)
-	{ // (the counting instantiation runs only while sv.tri_work is set, as in any_triangle_closer)
-		if(__builtin_expect(sv.tri_work != nullptr, 0))
-		{
-			if(sv.cones) tree_walk_shadow<NR, true, true>(sv, s);
-			else tree_walk_shadow<NR, false, true>(sv, s);
-		}
-		else if(sv.cones) tree_walk_shadow<NR, true, false>(sv, s);
-		else tree_walk_shadow<NR, false, false>(sv, s);
-		return;
-	}
-	uint32_t n_tri = 0;
-	float4 n0 = mesh_row(sv.tris, 0), n1 = mesh_row(sv.tris, 1), n2 = mesh_row(sv.tris, 2); // (tris[] carries one pad triangle)
-	for(int t = 0; t < sv.nt; t++)
+	static_assert(NR <= 2, "a ray is a bit of the masks lanes_of() counts: two per lane");
+	auto live = [&]
+	{
+		uint32_t m = 0;
+#pragma unroll
+		for(int k = 0; k < NR; k++) m |= s.live[k] ? 1u << k : 0u;
+		return m;
+	};
+	auto tri = [&](const float4 n0, const float4 n1, const float4 n2, int, uint32_t mine)
 	{
 		const f3 v0 = ld3(n0), e1 = ld3(n1), e2 = ld3(n2);
 		const int file = __float_as_int(n1.w);
-		n0 = mesh_row(sv.tris, 3 * t + 3);
-		n1 = mesh_row(sv.tris, 3 * t + 4);
-		n2 = mesh_row(sv.tris, 3 * t + 5);
-		bool some_live = false;
 #pragma unroll
 		for(int k = 0; k < NR; k++)
+			if((mine >> k & 1u) && s.live[k] && shadow_triangle_hit(s.o, s.d[k], v0, e1, e2, file, s.own, s.tmax[k])) s.live[k] = false;
+	};
+	if(sv.nchunks > 0)
+		mesh_instance(sv, [&](auto cones, auto count)
 		{
-			if(sv.tri_work) n_tri += (uint32_t) __popcll(__ballot(s.live[k]));
-			if(s.live[k] && shadow_triangle_hit(s.o, s.d[k], v0, e1, e2, file, s.own, s.tmax[k])) s.live[k] = false;
-			some_live = some_live || s.live[k];
-		}
-		if((t & 7) == 7 && !__any(some_live)) break;
-	}
-	tri_work_add(sv, 0u, n_tri);
+			constexpr bool CONES = decltype(cones)::value;
+			RayConst r[NR];
+			float dd[NR];
+#pragma unroll
+			for(int k = 0; k < NR; k++)
+			{
+				r[k] = make_ray(s.o, s.d[k]);
+				dd[k] = dot3(s.d[k], s.d[k]);
+			}
+			mesh_walk<decltype(count)::value>(sv, live, [&](const float4 A, const float4 B)
+			{
+				uint32_t m = 0;
+#pragma unroll
+				for(int k = 0; k < NR; k++) m |= (s.live[k] && line_touches<CONES>(r[k], dd[k], A, B)) ? 1u << k : 0u;
+				return m;
+			}, tri);
+		});
+	else mesh_all(sv, live, tri);
 }
 
 // ---- --legacy-reflect: the leaf functions of raytrace.h:45-103 ----

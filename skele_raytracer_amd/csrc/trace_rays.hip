@@ -91,6 +91,8 @@ SKR_DEV bool tri_before(const RayConst &r, const SceneView &sv, int slot, float 
 
 // Any accepted triangle with t < tmax: the walk of tree_walk_closest() with the running best fixed at tmax (an entry that can only
 // hold hits behind tmax is skipped), a lane done at its first hit, the wave at the first chunk after which every lane is.
+// shade_common.h mesh_walk() written out by hand: as its visitor the any-hit queries on dragon.scn took 2.85 against 2.39 ms for
+// camera rays and 34.4 against 25.8 ms for 2^22 random rays (with entries and triangles asked for one ahead 2.60 and 31.2 ms).
 template <bool CONES>
 SKR_DEV bool tree_walk_any(const SceneView &sv, const RayConst &r, float tmax, int ignore, bool hit)
 {

@@ -1,5 +1,5 @@
 // Shape of the triangle culling hierarchy, shared by the host builder (scene_trees.cpp
-// build_triangle_chunks) and the device walk (shade_common.h any_triangle_closer).
+// build_triangle_chunks) and the device walk (shade_common.h mesh_walk).
 #pragma once
 
 /* Consecutive (Morton-ordered) triangles per chunk sphere, chosen per scene by skr_scene::build_triangle_chunks(): scenes
