@@ -741,7 +741,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  *    1.0f / (len * len) in the correctly rounded expansions, over the 65536 binary32 values with those high 16 bits; as op 9).
  * 22 the lens sample and ray (skr_scene_set_lens above; wave_common.h lens_ray, the function the camera kernels call), laid out as op 18
  *    is: (pixel, aa, seed_lo, seed_hi, A, k, cam_pos(3), cam_right(3), cam_up(3), d(3)), 18 words -> (lx, ly, o'(3), d'(3)), 8 words.
- *    (Ops 20 and 21 were taken when the lens came.) */
+ *    (Ops 20 and 21 were taken when the lens came.)
+ * 23 the Phong power of the shaped leaf instance compiled for an exponent mask (device_math.h pow_int_sparse; csrc/launch.h
+ *    SKR_LEAF_POW_MASKS): (x, p, mask as an integer) -> one word, right for every integer p inside the mask and for every p that is
+ *    not plain; 0xFFFFFFFF for a mask that has no instance. */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

@@ -90,6 +90,7 @@ struct skr_renderer {
 	size_t last_off_ctr = 0; // the node-pipeline counters of the launch last enqueued (skr_renderer_last_*_count): where in `nodes` ...
 	int last_levels = 0;     // ... and how many levels they count (0: the launch took another path)
 	int last_leaf_shape = -1; // skr_renderer_last_leaf_shape
+	int last_leaf_pow = -1;   // skr_renderer_last_leaf_pow
 	bool timing = false;
 	bool count_tri = false; // skr_renderer_count_triangle_work
 	// the node pipeline's level-0 stage kept in `nodes` (launch.h PrimaryKey, take_node_scratch)
@@ -129,6 +130,7 @@ static void load_switches(SkrSwitches &sw)
 	if(const char *e = getenv("SKR_GI_SURFACE")) sw.gi_surface = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_SHADOW_SURFACE")) sw.shadow_mask = (sw.shadow_mask & ~2) | (atoi(e) > 0 ? 2 : 0);
 	if(const char *e = getenv("SKR_LEAF_SHAPE")) sw.shadow_mask = (sw.shadow_mask & ~SKR_SW_LEAF_SHAPE) | (atoi(e) > 0 ? SKR_SW_LEAF_SHAPE : 0);
+	if(const char *e = getenv("SKR_LEAF_POW")) sw.shadow_mask = (sw.shadow_mask & ~SKR_SW_LEAF_POW) | (atoi(e) > 0 ? SKR_SW_LEAF_POW : 0);
 	if(const char *e = getenv("SKR_PRIMARY_CACHE")) sw.primary_cache = atoi(e) > 0 ? 1 : 0;
 	if(const char *e = getenv("SKR_ADAPTIVE_PATH")) sw.adaptive_path = !strcmp(e, "frame") ? 1 : !strcmp(e, "query") ? 2 : 0;
 }
@@ -430,6 +432,7 @@ static int launch_params(const LaunchScene &v, const skr_options *opt, RenderPar
 	p.max_depth = opt->max_depth;
 	p.use_shadows = opt->use_shadows ? 1 : 0;
 	p.pow_steps = s.pow_steps;
+	p.sw.pow_any = (uint16_t) s.pow_any; // (host side: what skr_leaf_pow_plan reads)
 	// shade() only recurses under --gillum and only below a sphere hit (raytrace.h:208-218), and with N = 0 there is no
 	// child to recurse into: every --depth is then the depth-1 image
 	// (--shade-triangles: a triangle hit recurses too)
@@ -603,6 +606,7 @@ static int render_pass(skr_renderer *r, const skr_options *opt, uint32_t tile_ro
 	r->last_off_ctr = lp.off_ctr;
 	r->last_levels = lp.levels;
 	r->last_leaf_shape = (lp.path == SKR_PATH_NODES && !lp.nodes.flat) ? (int) skr_leaf_shape(p) : -1; // (what launch_leaf2, render_nodes.hip, asks too)
+	r->last_leaf_pow = r->last_leaf_shape >= 0 ? (int) skr_leaf_pow_plan(p) : -1;
 	g_variant = lp.variant;
 	SKR_HIP(skr_launch_render(p, lp, (hipStream_t) stream, r->timing ? &hook : nullptr));
 	if(r->timing) r->timed.push_back(hook);
@@ -690,10 +694,13 @@ int skr_renderer_primary_cache_stats(skr_renderer *r, uint64_t *builds, uint64_t
 // Internal (not in include/skr.h: tests only).  The shape whose instance of the leaf kernel the launch last enqueued ran (launch.h
 // SkrLeafShape: 0 = the instance that reads every fact at run time); -1: that launch ran no leaf kernel (another path, the flat schedule).
 int skr_renderer_last_leaf_shape(const skr_renderer *r) { return r ? r->last_leaf_shape : -1; }
+// ... and the exponent mask of that instance (launch.h skr_leaf_pow_plan: 0 = the run-time instance, which has none); -1 as above
+int skr_renderer_last_leaf_pow(const skr_renderer *r) { return r ? r->last_leaf_pow : -1; }
 
 // Internal (tests only; no device involved): skr_leaf_shape (launch.h) of the launch that a renderer of `scene` would make for `opt`
 // under the SKR_* switches of the environment as it is now — launch_params on the packed scene, nothing uploaded.  < 0: minus an error code.
-int skr_scene_leaf_shape(const skr_scene *scene, const skr_options *opt)
+// what: 0 = skr_leaf_shape, 1 = skr_leaf_pow_plan
+static int scene_leaf_plan(const skr_scene *scene, const skr_options *opt, int what)
 {
 	if(!scene || !opt) return -SKR_ERR_ARG;
 	SceneLayout layout;
@@ -705,8 +712,12 @@ int skr_scene_leaf_shape(const skr_scene *scene, const skr_options *opt)
 	GenericFeatures f; // (host memory: only addresses are formed, and null-ness asked)
 	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false};
 	const int rc = launch_params(v, opt, p, f);
-	return rc == SKR_OK ? (int) skr_leaf_shape(p) : -rc;
+	return rc != SKR_OK ? -rc : what ? (int) skr_leaf_pow_plan(p) : (int) skr_leaf_shape(p);
 }
+int skr_scene_leaf_shape(const skr_scene *scene, const skr_options *opt) { return scene_leaf_plan(scene, opt, 0); }
+// Internal (tests only; no device involved), as skr_scene_leaf_shape: the exponent mask of the leaf kernel's instance for that launch
+// (launch.h skr_leaf_pow_plan): 0 where the launch gets the run-time instance.  < 0: minus an error code.
+int skr_scene_leaf_pow(const skr_scene *scene, const skr_options *opt) { return scene_leaf_plan(scene, opt, 1); }
 
 // Per tile of `tile_rows` image rows: the work its pixels cost, counted — the tile is rendered on its own and the work counters read
 // (radiance rays, shaded hits, ray-sphere tests as the reference's loops run them), priced in flops like bench.py prices a frame
@@ -1334,7 +1345,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {
-	if(!d_in || !d_out || op < 0 || op > 22) return SKR_ERR_ARG;
+	if(!d_in || !d_out || op < 0 || op > 23) return SKR_ERR_ARG;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(skr_launch_debug(op, d_in, d_out, n, (hipStream_t) stream));
 	return SKR_OK;

@@ -407,8 +407,34 @@ SKR_DEV float pow_int_flat(float x, unsigned n)
 	}
 	return (float) r;
 }
+// The same for a caller that knows more than the bit length: ANY, the OR of every integer exponent a lane can hold (a fact of the launch,
+// launch.h skr_leaf_pow_plan).  The squarings run up to ANY's top bit; a product and its select exist only at ANY's bits — a step below
+// ANY's lowest bit multiplies nothing into r for any such n, and the first product, 1.0 * base, is the base itself.  For every n inside
+// ANY these are the spec's products in the spec's order, so the double that is rounded is the same double; an n outside ANY is out of
+// contract (it raises to n & ANY).  ANY = 0x7F is pow_int_flat<7> step for step.
+constexpr int pow_mask_steps(unsigned any) { return any ? 1 + pow_mask_steps(any >> 1) : 0; }
+template <unsigned ANY>
+SKR_DEV float pow_int_sparse(float x, unsigned n)
+{
+	static_assert(ANY != 0u && ANY <= 0x7FFu, "a mask of exponent bits 0 .. 10");
+	constexpr int STEPS = pow_mask_steps(ANY);
+	double r = 1.0, base = (double) x;
+#pragma unroll
+	for(int k = 0; k < STEPS; k++)
+	{
+		if((ANY >> k) & 1u)
+		{
+			const double rb = r * base;
+			r = ((n >> k) & 1u) ? rb : r;
+		}
+		if(k + 1 < STEPS) base *= base;
+	}
+	return (float) r;
+}
+constexpr unsigned SKR_POW_FULL7 = 0x7Fu; // every exponent below 128
 // LE7: the caller knows steps <= 7 (shade_common.h PointLightShape): no branch, and `steps` is not read
-template <bool LE7 = false>
+// ANY (with LE7): the caller knows that every integer exponent lies inside this mask; the full mask is the seven steps themselves
+template <bool LE7 = false, unsigned ANY = SKR_POW_FULL7>
 SKR_DEV float powf_spec(float x, float p, int steps)
 {
 #if SKR_FLAT_POW
@@ -419,6 +445,7 @@ SKR_DEV float powf_spec(float x, float p, int steps)
 	// max0(...), never -0, and the render kernels compile to the instructions they had without it: `make asm` before and after, compared
 	// with tools/asm_kernel_diff.py, differs in skr_debug_kernel alone (ops 2 and 20 take any x).
 	const float ax = __builtin_fabsf(x);
+	if constexpr(LE7 && ANY != SKR_POW_FULL7) return pow_int_sparse<ANY>(ax, (unsigned) p);
 	return (LE7 || steps <= 7) ? pow_int_flat<7>(ax, (unsigned) p) : pow_int_flat<11>(ax, (unsigned) p);
 #else
 	return powf_spec_cold(x, p);

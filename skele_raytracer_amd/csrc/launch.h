@@ -211,6 +211,30 @@ static inline SkrLeafShape skr_leaf_shape(const RenderParams &p)
 	return p.n_lights == 2 ? SKR_LEAF_POINT2 : p.n_lights == 1 ? SKR_LEAF_POINT1 : SKR_LEAF_RUNTIME;
 }
 
+// The exponent masks the shaped instances are compiled for (shade_common.h PointLightShape<L, ANY>; device_math.h pow_int_sparse): the
+// straight-line pow of an instance forms a product only at the bits of its mask.  SKR_LEAF_POW_FULL, all seven steps, comes first and
+// serves every launch with a shape; 0x30 is the exponents 16, 32 and 48 (spheres1.scn, spheres2.scn).  One instance per mask, shape,
+// FIRST and record form: a mask is worth its code only for exponents that scenes in use have.
+#define SKR_LEAF_POW_MASKS(X) X(0x7Fu) X(0x30u)
+constexpr unsigned SKR_LEAF_POW_FULL = 0x7Fu;
+// The mask of the instance a launch gets: of the listed masks that cover the OR of its scene's integer exponents (SkrSwitches::pow_any)
+// the one with the fewest bits, else the full one; 0: the launch has no shape, and the run-time instance no mask.  SKR_LEAF_POW=0: the
+// full mask always.
+static inline unsigned skr_leaf_pow_plan(const RenderParams &p)
+{
+	if(skr_leaf_shape(p) == SKR_LEAF_RUNTIME) return 0u;
+	unsigned best = SKR_LEAF_POW_FULL;
+	if(!(p.sw.shadow_mask & SKR_SW_LEAF_POW)) return best;
+	const unsigned list[] = {
+#define X(m) m,
+		SKR_LEAF_POW_MASKS(X)
+#undef X
+	};
+	for(unsigned m : list)
+		if(((unsigned) p.sw.pow_any & ~m) == 0u && __builtin_popcount(m) < __builtin_popcount(best)) best = m;
+	return best;
+}
+
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
 // f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius and a lens take the general level pipeline

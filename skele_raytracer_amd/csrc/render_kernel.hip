@@ -424,8 +424,32 @@ __global__ void skr_debug_lens_kernel(const uint32_t *in, uint32_t *out, uint32_
 	w[5] = U(d2.x); w[6] = U(d2.y); w[7] = U(d2.z);
 }
 
+// Op 23: powf_spec as the shaped leaf instance of an exponent mask calls it (launch.h SKR_LEAF_POW_MASKS): (x, p, mask) -> one word; a
+// mask that is not listed gives 0xFFFFFFFF (a kernel of its own: the ops above keep their code)
+__global__ void skr_debug_pow_kernel(const uint32_t *in, uint32_t *out, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	const float x = __uint_as_float(in[3 * i]), p = __uint_as_float(in[3 * i + 1]);
+	uint32_t r = 0xFFFFFFFFu;
+	switch(in[3 * i + 2])
+	{
+#define X(m) \
+	case m: r = __float_as_uint(powf_spec<true, m>(x, p, 7)); break;
+		SKR_LEAF_POW_MASKS(X)
+#undef X
+	default: break;
+	}
+	out[i] = r;
+}
+
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream)
 {
+	if(op == 23)
+	{
+		hipLaunchKernelGGL(skr_debug_pow_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n);
+		return hipGetLastError();
+	}
 	if(op == 22)
 	{
 		hipLaunchKernelGGL(skr_debug_lens_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n);

@@ -1114,15 +1114,22 @@ hipError_t skr_nodes_level_count(const void *scratch, size_t off_ctr, int level,
 typedef void (*LeafKernel)(const RenderParams);
 // The leaf kernel's instance for a launch.  The instances with a compiled-in shape exist for sphere-only scenes with GI masks, one per
 // shape of skr_leaf_shape (launch.h), which alone decides whether a launch has one.
+// The shaped instances exist once per exponent mask of launch.h SKR_LEAF_POW_MASKS; skr_leaf_pow_plan alone decides which one a shaped
+// launch gets.
+static_assert(SKR_LEAF_POW_FULL == SKR_POW_FULL7, "the full mask of the plan is the one PointLightShape defaults to");
 template <bool FIRST, bool WIDE>
 static LeafKernel leaf_instance(const RenderParams &p)
 { // (GI masks exist for sphere-only scenes alone: scene_masks.cpp build_gi_masks)
-	switch(skr_leaf_shape(p))
-	{
-	case SKR_LEAF_POINT2: return skr_leaf_kernel2<false, FIRST, true, WIDE, PointLightShape<2>>;
-	case SKR_LEAF_POINT1: return skr_leaf_kernel2<false, FIRST, true, WIDE, PointLightShape<1>>;
-	default: break;
-	}
+	const SkrLeafShape shape = skr_leaf_shape(p);
+	if(shape != SKR_LEAF_RUNTIME)
+		switch(skr_leaf_pow_plan(p))
+		{
+#define X(m) \
+	case m: return shape == SKR_LEAF_POINT2 ? skr_leaf_kernel2<false, FIRST, true, WIDE, PointLightShape<2, m>> : skr_leaf_kernel2<false, FIRST, true, WIDE, PointLightShape<1, m>>;
+			SKR_LEAF_POW_MASKS(X)
+#undef X
+		default: break; // (no such plan: every mask skr_leaf_pow_plan names is listed)
+		}
 	if(p.n_tris > 0) return skr_leaf_kernel2<true, FIRST, false, WIDE>;
 	return p.gi_index != nullptr ? skr_leaf_kernel2<false, FIRST, true, WIDE> : skr_leaf_kernel2<false, FIRST, false, WIDE>;
 }

@@ -26,23 +26,28 @@ struct f3 {
 // skr_renderer_reload_switches) — the launch path never calls getenv.
 enum SkrPipeline { SKR_PIPE_AUTO = 0, SKR_PIPE_NODES, SKR_PIPE_GENERIC, SKR_PIPE_OTHER };
 struct SkrSwitches {
-	int32_t pipeline = SKR_PIPE_AUTO; // SKR_PIPELINE = nodes | generic: which level pipeline takes a --gillum tree (tests, A/B runs)
+	int16_t pipeline = SKR_PIPE_AUTO; // SKR_PIPELINE = nodes | generic: which level pipeline takes a --gillum tree (tests, A/B runs)
+	uint16_t pow_any = 0x7FF;         // no switch but a host fact of the launch's scene, in the spare half of this word (api.cpp launch_params): the OR of its
+	                                  // integer Phong exponents in [1, 1024] (scene_pack.h SceneLayout::pow_any; launch.h skr_leaf_pow_plan)
 	int8_t no_cones = 0, no_cull = 0;  // SKR_NO_CONES, SKR_NO_CULL: triangle-walk culling off  (four quarters of one word: the struct stays 20 bytes, so that
 	                                   // every field of RenderParams behind it keeps its offset and the kernels that never read the switches their code)
 	int8_t primary_cache = 1;          // SKR_PRIMARY_CACHE = 1 | 0: frames of one camera replay the node pipeline's level-0 stage / every frame runs skr_primary_kernel
 	int8_t no_sphere_cull = 0;         // SKR_NO_SPHERE_CULL: a renderer on the sphere tree runs the loop over every sphere in every wave (the A/B arm of DESIGN.md 8.10)
 	int32_t budget_mb = 0;            // SKR_LEVELS_BUDGET_MB: scratch budget of the level pipelines (0 = default)
 	int32_t flat = 0;                 // SKR_FLAT = 1 | 0: the node pipeline's flat schedule forced on (+1) / off (-1); unset: by launch size
-	int8_t shadow_mask = 7;           // bit 0: SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere;
+	int8_t shadow_mask = 15;          // bit 0: SKR_SHADOW_MASK = 1 | 0: the shadow walk of the level pipelines visits only the spheres the masks name / every sphere;
 	                                  // bit 1: SKR_SHADOW_SURFACE = 1 | 0: a shading point on a sphere takes its mask from the surface patches / the direction masks only;
 	                                  // bit 2 (SKR_SW_LEAF_SHAPE, a spare bit of this byte): SKR_LEAF_SHAPE = 1 | 0: the leaf kernel's instance with the launch's shape
 	                                  // compiled in where there is one (launch.h skr_leaf_shape) / always the instance that reads it at run time (A/B runs, tests)
+	                                  // bit 3 (SKR_SW_LEAF_POW): SKR_LEAF_POW = 1 | 0: the shaped instance for the scene's exponent bits (launch.h skr_leaf_pow_plan) /
+	                                  // always the one with all seven pow steps (A/B runs, tests)
 	int8_t gi_mask = 1;               // SKR_GI_MASK = 1 | 0: the same for the closest-hit walk of the node pipeline's GI children
 	int8_t gi_surface = 1;            // SKR_GI_SURFACE = 1 | 0: GI origins on a sphere take their row of masks from the surface patches / the 3D grids only
 	int8_t adaptive_path = 0;         // SKR_ADAPTIVE_PATH = frame | query: the path of every adaptive round (+1 / +2); unset: by active share (four quarters of one word, as above)
 };
 
 constexpr int SKR_SW_LEAF_SHAPE = 4;
+constexpr int SKR_SW_LEAF_POW = 8;
 static_assert(sizeof(SkrSwitches) == 20, "SkrSwitches keeps its 20 bytes");
 
 struct RenderParams {

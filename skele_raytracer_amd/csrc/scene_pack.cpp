@@ -85,13 +85,20 @@ std::vector<skr_f4> skr_pack_scene(const skr_scene &s, SceneLayout &d)
 	}
 	put(SKR_SEC_pad, nullptr, SKR_BLOB_PAD_ROWS * 16);
 	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
+		// ... and needs a product only at a bit that some integer exponent has set (pow_any; the others take powf_spec_cold lane by lane)
 		float top = 1.0f;
-		auto look = [&](float pw) { if(pw >= 1.0f && pw <= 1024.0f && pw == rintf(pw) && pw > top) top = pw; };
+		unsigned any = 0;
+		auto look = [&](float pw) {
+			if(!(pw >= 1.0f && pw <= 1024.0f && pw == rintf(pw))) return;
+			any |= (unsigned) pw;
+			if(pw > top) top = pw;
+		};
 		for(const skr_f4 &a : s.sph_amb) look(a.w);
 		for(size_t i = 0; i + 2 < s.tri_mats.size(); i += 3) look(s.tri_mats[i].w);
 		int bits = 0;
 		for(unsigned v = (unsigned) top; v; v >>= 1) bits++;
 		d.pow_steps = bits < 1 ? 1 : bits;
+		d.pow_any = any;
 	}
 	return rows;
 }

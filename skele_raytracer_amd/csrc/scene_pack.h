@@ -32,6 +32,7 @@ struct SceneLayout {
 	size_t first[SKR_BLOB_SECTION_COUNT] = {}, rows[SKR_BLOB_SECTION_COUNT] = {}; // per section its first row and its rows; 0 rows: absent
 	bool has(SkrBlobSection s) const { return rows[s] != 0; }
 	int pow_steps = 11; // bit length of the largest integer phong exponent in [1, 1024] among the scene's materials (device_math.h powf_spec)
+	unsigned pow_any = 0x7FF; // the OR of those exponents (0: the scene has none): the bits at which the straight-line pow needs a product (launch.h skr_leaf_pow_plan)
 	int n_chunks = 0, chunk_size = 0, cones = 0; // nodes of the chunk tree (scene_host.h)
 	size_t chunk_stride = 0;
 	int n_fog = 0;

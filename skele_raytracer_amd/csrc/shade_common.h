@@ -49,14 +49,16 @@ struct RunTimeShape {
 	static constexpr bool shadows = false;       // true: p.use_shadows != 0
 	static constexpr bool masks = false;         // true: the launch has shadow masks (sv.smask != null)
 	static constexpr bool pow7 = false;          // true: p.pow_steps <= 7
+	static constexpr unsigned pow_any = SKR_POW_FULL7; // (pow7) every integer Phong exponent of the scene lies inside this mask of bits
 	static constexpr bool gi_narrow = false;     // true: p.gi_wide == 0 (16-bit GI masks: at most 16 spheres)
 };
-// A sphere-only scene of LIGHTS (1 or 2) point lights with its shadow masks, shadows on, integer Phong exponents below 128 and at most
-// 16 spheres.
-template <int LIGHTS>
+// A sphere-only scene of LIGHTS (1 or 2) point lights with its shadow masks, shadows on, integer Phong exponents below 128 — all of them
+// inside the bits of ANY (device_math.h pow_int_sparse; 0x7F: any of them) — and at most 16 spheres.
+template <int LIGHTS, unsigned ANY = SKR_POW_FULL7>
 struct PointLightShape {
 	static constexpr int lights = LIGHTS;
 	static constexpr bool point_lights = true, shadows = true, masks = true, pow7 = true, gi_narrow = true;
+	static constexpr unsigned pow_any = ANY;
 };
 namespace {
 
@@ -854,7 +856,7 @@ SKR_DEV f3 direct_light_of(const SceneView &sv, const RenderParams &p, f3 kd, f3
 				diffuse = diffuse + ((kd * t.lc) * t.intensity) * max0(dot3(N, t.L));
 				const f3 vl = view + t.L;
 				const f3 H = vl / length3(vl);
-				specular = specular + ((ks * t.lc) * t.intensity) * powf_spec<SH::pow7>(max0(dot3(N, H)), ambp.w, p.pow_steps);
+				specular = specular + ((ks * t.lc) * t.intensity) * powf_spec<SH::pow7, SH::pow_any>(max0(dot3(N, H)), ambp.w, p.pow_steps);
 			}
 		};
 		add_light(t0, !occ0);

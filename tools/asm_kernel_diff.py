@@ -32,7 +32,8 @@ def kernels(path):
 
 def demangle(names):
     res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return {n: re.sub(r"^void ", "", d).replace("<>", "") for n, d in zip(names, res)}
+    # (PointLightShape<L> became PointLightShape<L, ANY = 0x7F>: the instance of the full mask is the old one under a longer name)
+    return {n: re.sub(r"(PointLightShape<\d+), 127u>", r"\1>", re.sub(r"^void ", "", d).replace("<>", "")) for n, d in zip(names, res)}
 
 
 def main():
