@@ -35,6 +35,7 @@ extern "C" {
 #define SKR_HAS_SOFT_LIGHTS 1 /* skr_scene_set/get_light_radii, skr_debug_eval op 18: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ROOT_PAIRS 1 /* skr_debug_eval op 19: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_LENS 1 /* skr_scene_set/get_lens, skr_debug_eval op 22: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_MOTION 1 /* SKR_SCN_MOTION, skr_scene_set/get_sphere_velocities, skr_scene_set/get_shutter, skr_debug_eval op 24: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -291,6 +292,48 @@ int skr_scene_get_light_radii(const skr_scene *scene, float *radii, int32_t *n);
 #define SKR_LENS_CTR3 0x800000C0u
 int skr_scene_set_lens(skr_scene *scene, float aperture, float focus);
 int skr_scene_get_lens(const skr_scene *scene, float *aperture, float *focus);
+/* Motion blur: moving spheres, one shutter time per sample (new, opt-in; no counterpart in the reference, whose spheres are frozen).  A
+ * scene carries one velocity v_i (3 floats) per sphere, default (0, 0, 0), and a shutter S, default 1; every value finite, S >= 0.
+ * SKR_SCN_MOTION (`raytracer --scn-motion`; combines with the other scene flags): a line
+ *     velocity vx vy vz
+ * sets the velocity in force for the `sphere` lines that follow, stateful exactly as `material` is; the initial value is 0 0 0.  A line
+ * without 3 finite numbers is warned about, skipped and counted in n_unknown.  Without the flag the line stays "WARNING. Do not know
+ * command" and everything is as it was, byte for byte; skr_scene_info does not grow.  The rule (normative):
+ *   - In force.  Motion is in force for a launch iff S > 0 and some component of some v_i is != 0.  Otherwise no draw is made:
+ *     planning, skr_kernel_variant(), frames, floats and all work counters are exactly what they are without velocities.
+ *   - The draw: one call per (pixel, aa), philox4x32(pixel, aa, 0, SKR_SHUTTER_CTR3, seed_lo, seed_hi) with SKR_SHUTTER_CTR3 =
+ *     0x800000E0u.  The word is disjoint from every other draw: bit 31 is set (the hemisphere draws have it clear), bit 7 is set (the
+ *     fog word has it clear), bit 6 is set (the light samples' word 0x80000080u | (l << 8) has it clear), bit 5 is set (SKR_LENS_CTR3 =
+ *     0x800000C0u has it clear), bits 0-4 are clear (never the jitter word 0xFFFFFFFF).  u = u31_to_unit(out[0]); tau = S * u is one
+ *     binary32 multiply; out[1..3] are unused.
+ *   - The displaced centres: for this sample sphere i has the centre
+ *         c'_i = (fmaf(tau, v_i.x, c_i.x), fmaf(tau, v_i.y, c_i.y), fmaf(tau, v_i.z, c_i.z)),
+ *     one correctly rounded fused multiply-add per component — a stated exception to "not contracted", as fma2 is where the spec names
+ *     it.  r^2 is unchanged.  A sphere with v_i = 0 keeps c_i up to the sign of a zero.
+ *   - The sample: the radiance of sample (pixel, aa) is what the renderer returns for that pixel, aa and seed on the static scene whose
+ *     sphere i has the centre c'_i.  Untouched: the primary ray and its jitter draw; child rays, GI draws, light samples, cone
+ *     decisions and triangle shadows; the specular view vector toward cam_pos; the acceptance window 1 < t; "origin inside a sphere =>
+ *     miss"; the shadow rule "any sphere with 1 < t < inf"; the AA sum and its divide, and progressive_passes.  The whole tree under
+ *     one primary sample sees one tau.  Triangles, lights and the camera do not move.
+ *   - Keys: tau depends only on (pixel word, aa, seed), and the pixel word of a query ray is its key.  So skr_shade_rays with keys
+ *     y * width + x and sample = aa on a scene with motion in force gives that sample of the frame, bit for bit.  skr_camera_rays is
+ *     unchanged.  skr_trace_rays answers for the scene at rest (tau = 0).
+ *   - Where it runs: a launch with motion in force always takes the general level pipeline; skr_kernel_variant() carries one "_motion"
+ *     part behind the light part ("level_pipeline_g1_motion", "level_pipeline_g1_soft_motion_tshadow", "shade_rays_g1_motion", ...).
+ *     It combines with use_shadows, grid_size, num_path_traces at any depth, SKR_SCN_STRICT, shade_triangles with or without triangle
+ *     shadows, spot lights, light radii, tiles and strides, clones, skr_multi / skr_comm, progressive and adaptive frames.
+ *   - Refused with SKR_ERR_UNSUPPORTED where motion is in force (and only there): skr_options.legacy_reflect, fog volumes, the
+ *     sphere-tree switch, a lens with A > 0, and skr_render_denoised_host / skr_render_adaptive_denoised_host (guides at rest would
+ *     sharpen what the shutter blurs, as under a lens).
+ * set: a value that is not finite, S < 0, or n != the sphere count: SKR_ERR_ARG and the scene is unchanged.  get: *n = the sphere
+ * count, v (if not NULL) receives v[n][3].  A renderer takes velocities and shutter when it is created; skr_renderer_clone and the
+ * multi-GPU frame steps carry them. */
+#define SKR_SCN_MOTION 32u
+#define SKR_SHUTTER_CTR3 0x800000E0u
+int skr_scene_set_sphere_velocities(skr_scene *scene, const float *v, int32_t n);
+int skr_scene_get_sphere_velocities(const skr_scene *scene, float *v, int32_t *n);
+int skr_scene_set_shutter(skr_scene *scene, float shutter);
+int skr_scene_get_shutter(const skr_scene *scene, float *shutter);
 /* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
  * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
  * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device
@@ -744,7 +787,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  *    (Ops 20 and 21 were taken when the lens came.)
  * 23 the Phong power of the shaped leaf instance compiled for an exponent mask (device_math.h pow_int_sparse; csrc/launch.h
  *    SKR_LEAF_POW_MASKS): (x, p, mask as an integer) -> one word, right for every integer p inside the mask and for every p that is
- *    not plain; 0xFFFFFFFF for a mask that has no instance. */
+ *    not plain; 0xFFFFFFFF for a mask that has no instance.
+ * 24 the shutter time and a displaced centre (skr_scene_set_sphere_velocities above; wave_common.h shutter_time and shade_common.h
+ *    MovingCentres::centre, the functions the kernels of a launch with motion call): (pixel, aa, seed_lo, seed_hi, S, c(3), v(3)),
+ *    11 words -> (tau, c'(3)), 4 words. */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_sphere_velocities", "skr_scene_get_sphere_velocities", "skr_scene_set_shutter", "skr_scene_get_shutter", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -91,6 +91,10 @@ def lib():
     L.skr_scene_get_light_radii.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_scene_set_lens.argtypes = [vp, C.c_float, C.c_float]
     L.skr_scene_get_lens.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.skr_scene_set_sphere_velocities.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_sphere_velocities.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.skr_scene_set_shutter.argtypes = [vp, C.c_float]
+    L.skr_scene_get_shutter.argtypes = [vp, C.POINTER(C.c_float)]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
     L.skr_scene_set_sphere_tree.argtypes = [vp, C.c_int]
@@ -374,6 +378,34 @@ class Scene:
         _check(lib().skr_scene_get_lens(self.h, C.byref(a), C.byref(f)), "skr_scene_get_lens")
         return a.value, f.value
 
+    @property
+    def velocities(self):
+        """The velocity of every sphere, [n_spheres][3]; all 0 = a scene at rest (include/skr.h skr_scene_get_sphere_velocities)."""
+        n = C.c_int32(0)
+        _check(lib().skr_scene_get_sphere_velocities(self.h, None, C.byref(n)), "skr_scene_get_sphere_velocities")
+        v = np.zeros((n.value, 3), np.float32)
+        _check(lib().skr_scene_get_sphere_velocities(self.h, v.ctypes.data, C.byref(n)), "skr_scene_get_sphere_velocities")
+        return v
+
+    def set_velocities(self, velocities):
+        """Give every sphere a velocity (motion blur; include/skr.h skr_scene_set_sphere_velocities states the rule): [n_spheres][3], every
+        value finite.  A renderer takes the velocities the scene has when it is made."""
+        v = np.ascontiguousarray(velocities, np.float32).reshape(-1)
+        if len(v) % 3:
+            raise ValueError("velocities: 3 floats per sphere")
+        _check(lib().skr_scene_set_sphere_velocities(self.h, v.ctypes.data, len(v) // 3), "skr_scene_set_sphere_velocities")
+
+    @property
+    def shutter(self):
+        """The scene's shutter S (default 1): a sample's spheres are where they are at a time in [0, S) (include/skr.h skr_scene_get_shutter)."""
+        s = C.c_float(0)
+        _check(lib().skr_scene_get_shutter(self.h, C.byref(s)), "skr_scene_get_shutter")
+        return s.value
+
+    def set_shutter(self, shutter):
+        """Set the shutter S, finite and >= 0; 0 = closed: the scene at rest (include/skr.h skr_scene_set_shutter)."""
+        _check(lib().skr_scene_set_shutter(self.h, C.c_float(float(shutter))), "skr_scene_set_shutter")
+
     def set_lens(self, aperture, focus=1.0):
         """Give the camera a thin lens (depth of field; include/skr.h skr_scene_set_lens states the rule): aperture radius >= 0 (0: the
         pinhole), focus > 0 in units of the primary ray directions, both finite.  A renderer takes the lens the scene has when it is made."""
@@ -421,7 +453,7 @@ class Scene:
 
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
-                    triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None):
+                    triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None, velocities=None, shutter=None):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -447,21 +479,25 @@ class Scene:
             sc.set_light_radii(light_radii)
         if lens is not None:  # (aperture, focus) (depth of field)
             sc.set_lens(*lens)
+        if velocities is not None:  # [n_spheres][3] (motion blur)
+            sc.set_velocities(velocities)
+        if shutter is not None:
+            sc.set_shutter(shutter)
         return sc
 
 
-SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT = 1, 2, 4, 8, 16  # include/skr.h SKR_SCN_*
+SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT, SCN_MOTION = 1, 2, 4, 8, 16, 32  # include/skr.h SKR_SCN_*
 FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
 
 
-def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False):
+def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False, motion=False):
     """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept),
     fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded), triangle_shadows = SKR_SCN_TRIANGLE_SHADOWS
     (--triangle-shadows: triangles cast shadows in frames with shade_triangles and shadow), sphere_tree = SKR_SCN_SPHERE_TREE
     (--sphere-tree: frames and shading queries on the culled sphere walk, any sphere count), spot = SKR_SCN_SPOT (--scn-spot: spot_light
-    lines parsed and shaded)."""
+    lines parsed and shaded), motion = SKR_SCN_MOTION (--scn-motion: velocity lines parsed, the spheres that follow move)."""
     h = C.c_void_p()
-    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0) | (SCN_SPOT if spot else 0)
+    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0) | (SCN_SPOT if spot else 0) | (SCN_MOTION if motion else 0)
     _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), flags, C.byref(h)), "skr_scene_create_from_scn_ex")
     return Scene(h.value)
 

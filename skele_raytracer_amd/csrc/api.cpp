@@ -39,13 +39,14 @@ struct DeviceScene {
 	unsigned long long *d_counters = nullptr; // CTR_BYTES
 	unsigned long long *d_tri_work = nullptr; // the triangle walks' counters (skr_renderer_read_triangle_work)
 	unsigned long long *d_st_work = nullptr;  // the sphere tree's (skr_renderer_read_sphere_tree_work); null without a sphere tree
+	float4 *d_vel = nullptr; // the spheres' velocities {v.xyz, 0} in file order, + SKR_BLOB_PAD_ROWS rows of zeros (launch.h Motion); null unless motion is in force
 
 	DeviceScene() = default;
 	DeviceScene(const DeviceScene &) = delete;
 	DeviceScene &operator=(const DeviceScene &) = delete;
 	~DeviceScene()
 	{
-		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work})
+		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work, (void *) d_vel})
 			if(p) (void) hipFree(p);
 	}
 };
@@ -235,6 +236,13 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 	if(e == hipSuccess) e = zeroed(&s->d_tri_work, WALK_BYTES);
 	if(e == hipSuccess && s->layout.sphere_tree) e = zeroed(&s->d_st_work, WALK_BYTES);
 	if(e == hipSuccess) e = zeroed(&s->d_camec, camec_bytes);
+	if(e == hipSuccess && s->layout.motion)
+	{ // the velocities travel beside the blob, whose section table they are no part of (scene_pack.h)
+		std::vector<skr_f4> vel(ns + SKR_BLOB_PAD_ROWS, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
+		for(size_t i = 0; i < ns && 3 * i + 2 < scene->velocities.size(); i++) vel[i] = skr_f4{scene->velocities[3 * i], scene->velocities[3 * i + 1], scene->velocities[3 * i + 2], 0.0f};
+		e = hipMalloc((void **) &s->d_vel, vel.size() * 16);
+		if(e == hipSuccess) e = hipMemcpy(s->d_vel, vel.data(), vel.size() * 16, hipMemcpyHostToDevice);
+	}
 	if(e == hipSuccess)
 	{ // the camera belongs to the scene: its (e, c) rows are formed once, on the device, by the operations every ray would perform
 		const float *c = scene->info.camera;
@@ -363,12 +371,13 @@ struct LaunchScene {
 	unsigned long long *counters, *tri_work, *st_work;
 	const SkrSwitches &sw;
 	bool count_tri;
+	const float4 *vel; // the velocity rows where motion is in force (DeviceScene::d_vel)
 	const float4 *sec(SkrBlobSection k) const { return blob + layout.first[k]; } // where a section starts
 };
 static LaunchScene launch_scene(const skr_renderer *r)
 {
 	const DeviceScene &s = *r->scene;
-	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri};
+	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri, s.d_vel};
 }
 static float4 ball4(const skr_f4 &b) { return make_float4(b.x, b.y, b.z, b.w); }
 
@@ -550,6 +559,13 @@ static GenericFeatures generic_features(const LaunchScene &v, const RenderParams
 	if(f.soft) f.softs = SoftLights{reinterpret_cast<const float *>(v.sec(SKR_SEC_radii)), s.n_radii};
 	f.lens = s.lens_A > 0.0f && !query;
 	if(f.lens) f.thin_lens = Lens{s.lens_A, s.lens_k, query_trees(v)};
+	f.motion = s.motion && p.n_spheres > 0; // (frames and shading queries alike: the shutter time of a query ray is its key's)
+	if(f.motion)
+	{ // such a launch always carries the spot and radius tables, n = 0 where the scene has none (render_generic.hip with_pack)
+		f.mot = Motion{v.vel, s.shutter, query_trees(v)};
+		f.spots = SpotLights{v.sec(SKR_SEC_spot), s.spot_first, s.n_spot};
+		f.softs = SoftLights{reinterpret_cast<const float *>(v.sec(SKR_SEC_radii)), s.n_radii};
+	}
 	return f;
 }
 
@@ -710,7 +726,7 @@ static int scene_leaf_plan(const skr_scene *scene, const skr_options *opt, int w
 	load_switches(sw);
 	RenderParams p = camera_params(scene->info, opt, opt->seed, 0);
 	GenericFeatures f; // (host memory: only addresses are formed, and null-ness asked)
-	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false};
+	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false, reinterpret_cast<const float4 *>(rows.data())};
 	const int rc = launch_params(v, opt, p, f);
 	return rc != SKR_OK ? -rc : what ? (int) skr_leaf_pow_plan(p) : (int) skr_leaf_shape(p);
 }
@@ -1293,6 +1309,11 @@ static int denoised_host(skr_renderer *r, const char *who, const skr_options *op
 		skr_set_error("%s: a lens (--aperture) cannot be combined with the denoiser (its guides are the pinhole camera's first hits)", who);
 		return SKR_ERR_UNSUPPORTED;
 	}
+	if(r->scene->layout.motion)
+	{ // nor has a scene in motion (include/skr.h skr_scene_set_sphere_velocities)
+		skr_set_error("%s: motion blur (sphere velocities under --shutter) cannot be combined with the denoiser (its guides are first hits of the scene at rest)", who);
+		return SKR_ERR_UNSUPPORTED;
+	}
 	SKR_HIP(hipSetDevice(r->scene->device));
 	const size_t n = (size_t) opt->width * opt->height;
 	ScratchLayout L; // the frame, (adaptive) its variance and pass counts, the camera rays and guides, the filtered frame and its bytes
@@ -1345,7 +1366,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {
-	if(!d_in || !d_out || op < 0 || op > 23) return SKR_ERR_ARG;
+	if(!d_in || !d_out || op < 0 || op > 24) return SKR_ERR_ARG;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(skr_launch_debug(op, d_in, d_out, n, (hipStream_t) stream));
 	return SKR_OK;

@@ -231,6 +231,10 @@ SKR_DEV uint32_t soft_ctr3(uint32_t light) { return 0x80000080u | (light << 8); 
 // set: disjoint from soft_ctr3, whose bit 6 is clear.  Bits 0-5 clear: never the jitter word 0xFFFFFFFF.  u1 = u31(out[0]),
 // u2 = u31(out[1]); out[2], out[3] unused.
 SKR_DEV uint32_t lens_ctr3() { return 0x800000C0u; }
+// The shutter time of a scene in motion (include/skr.h skr_scene_set_sphere_velocities): ONE call per (pixel, aa), counter
+// (pixel, aa, 0, shutter_ctr3()) = SKR_SHUTTER_CTR3.  Bits 31, 7 and 6 as lens_ctr3; bit 5 set: disjoint from lens_ctr3, whose bit 5 is
+// clear.  Bits 0-4 clear: never the jitter word 0xFFFFFFFF.  u = u31(out[0]); out[1..3] unused.
+SKR_DEV uint32_t shutter_ctr3() { return 0x800000E0u; }
 
 // ------------------------------------------------------- shared math ----
 typedef float f2 __attribute__((ext_vector_type(2)));

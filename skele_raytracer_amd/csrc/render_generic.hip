@@ -40,6 +40,13 @@
 // A lens (include/skr.h skr_scene_set_lens).  With a Lens in the pack the camera rays of level 1 are (o', d') of
 // wave_common.h lens_ray: the trace kernel forms them and picks the tree of each wave as for query rays (the rays do not start at the
 // scene camera), the activate kernel forms o' again for the hit point.  Every level below works on any ray unchanged.
+//
+// Motion (include/skr.h skr_scene_set_sphere_velocities).  With a Motion in the pack every lane forms the shutter time of
+// its sample from the pixel word of its tree's root (wave_common.h shutter_time) and searches the spheres where they are at that time
+// (shade_common.h MovingCentres): the closest-hit search of the trace kernel, the normal and the shadow rays of the activate kernel.
+// Such an instance consults no table built from the centres at rest — its view of the scene has no shadow masks, and this pipeline reads
+// neither GI masks nor the camera's (e, c) rows — and, where its rays start on displaced surfaces (below level 1), picks the tree of
+// each wave as for query rays.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -263,7 +270,7 @@ struct SphereLoops {
 template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, const Q... qs)
 {
-	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, LENS = pack_has<Lens, Q...>;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, LENS = pack_has<Lens, Q...>, MOTION = pack_has<Motion, Q...>;
 	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -284,12 +291,14 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 		ch.o = ch.d = mk3(0, 0, 1);
 		ch.from_tri = -1;
 		float tmax = __builtin_inff();
+		uint32_t root = 0u; // MOTION: the pixel word of the ray's tree, what its shutter time is drawn from
 		if(valid)
 		{
 			if(p.g_level == 1)
 			{
 				if constexpr(RAYS)
 				{ // the caller's ray {o, tmax} {d, ignore_triangle} (include/skr.h skr_ray); ignore_triangle only where a ray can carry one
+					if constexpr(MOTION) root = q.keys ? q.keys[q.ray0 + node] : q.ray0 + node; // (the activate kernel's n.pixel)
 					const float4 ra = q.rays[2 * (size_t) (q.ray0 + node)], rb = q.rays[2 * (size_t) (q.ray0 + node) + 1];
 					ch.exists = true;
 					ch.o = mk3(ra.x, ra.y, ra.z);
@@ -306,14 +315,23 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 					{
 						ch.o = p.cam_pos;
 						primary_ray(p, (int) x, y, y * bw + x, p.aa_index, ch.d);
+						if constexpr(MOTION) root = y * bw + x;
 						if constexpr(LENS) lens_ray(p, pick<Lens>(qs...), y * bw + x, p.aa_index, ch.d, ch.o, ch.d); // (o', d') of include/skr.h skr_scene_set_lens
 					}
 				}
 			}
-			else ch = child_of(sv, p, load_node(p.g_nodes_src + (size_t) node * GNODE_ROWS), c);
+			else
+			{
+				const GNode pn = load_node(p.g_nodes_src + (size_t) node * GNODE_ROWS);
+				ch = child_of(sv, p, pn, c);
+				if constexpr(MOTION) root = pn.pixel;
+			}
 		}
 		SceneView svw = sv;
-		if constexpr(RAYS) query_tree(svw, p, q, ch.exists, ch.o, ch.d);
+		if constexpr(RAYS && MOTION) pick_query_tree(svw, q.trees, p.cam_pos, false, ch.exists, ch.o, ch.d); // (below level 1 too: origins on displaced surfaces)
+		else if constexpr(RAYS) query_tree(svw, p, q, ch.exists, ch.o, ch.d);
+		else if constexpr(MOTION) // level 1 starts at the scene camera and keeps the renderer's tree; below it the origins lie on displaced surfaces, which that tree is not built for
+			if(p.g_level != 1) pick_query_tree(svw, pick<Motion>(qs...).trees, p.cam_pos, false, ch.exists, ch.o, ch.d);
 		if constexpr(LENS) // level 1 starts on the lens, not at the scene camera: the tree of query rays; the levels below keep the renderer's
 			if(p.g_level == 1) pick_query_tree(svw, pick<Lens>(qs...).trees, p.cam_pos, false, ch.exists, ch.o, ch.d);
 		bool hit = false, black = false;
@@ -326,6 +344,11 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 			float tmin;
 			int sph; // raytrace.h:152-165
 			if constexpr(STREE) sph = stree_closest(pick<SphereTree>(qs...), sv, r, tmin);
+			else if constexpr(MOTION)
+			{ // the spheres where they are at the sample's shutter time
+				const Motion &mo = pick<Motion>(qs...);
+				sph = closest_sphere(sv, r, tmin, MovingCentres{mo.vel, shutter_time(p, root, p.aa_index, mo.S)});
+			}
 			else sph = closest_sphere(sv, r, tmin);
 			float tcut = tmin;
 			if constexpr(RAYS)
@@ -420,13 +443,14 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 
 // FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
 // Q: TriShadows — the shadow walk behind the sphere test; SphereTree — the sphere test is the tree's pair walk; SpotLights — the pair loop with
-//    the cone decision; SpotLights SoftLights — and the light sample ahead of it; Lens — a level-1 hit's ray starts on the lens (which packs
-//    exist: with_pack)
+//    the cone decision; SpotLights SoftLights — and the light sample ahead of it; Lens — a level-1 hit's ray starts on the lens; Motion —
+//    the normal and the shadow rays meet the spheres where they are at the sample's shutter time (which packs exist: with_pack)
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
 	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>, SPOT = pack_has<SpotLights, Q...>,
-				   SOFT = pack_has<SoftLights, Q...>, LENS = pack_has<Lens, Q...>;
+				   SOFT = pack_has<SoftLights, Q...>, LENS = pack_has<Lens, Q...>, MOTION = pack_has<Motion, Q...>;
+	static_assert(!MOTION || (SPOT && SOFT && !FOG && !STREE && !LENS), "a launch with motion carries SpotLights and SoftLights (with_pack)");
 	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -486,6 +510,8 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 			o = c < N ? add_scalar(pn.P, 0.00001f) : pn.P; // raytrace.h:128 / :66, :73
 		}
 		n.P = o + n.d * t; // raytrace.h:204 (t of the winner == the loop's minimum)
+		MovingCentres at{nullptr, 0.0f}; // MOTION: where the spheres are at the shutter time of the node's sample (the draw the trace kernel made for the ray)
+		if constexpr(MOTION) at = MovingCentres{pick<Motion>(qs...).vel, shutter_time(p, n.pixel, p.aa_index, pick<Motion>(qs...).S)};
 		float4 ambp, ks4;
 		f3 kd;
 		surface_material(sv, p, surf, ambp, kd, ks4);
@@ -496,6 +522,7 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 			if(dot3(n.N, n.d) > 0.0f) n.N = mk3(-n.N.x, -n.N.y, -n.N.z);
 			n.file = __float_as_int(sv.tris[3 * slot + 1].w);
 		}
+		else if constexpr(MOTION) n.N = normalize3(n.P - ld3(at.row(sv.geom[surf], (int) surf))); // :205, the centre the trace kernel's search met
 		else n.N = normalize3(n.P - ld3(sv.geom[surf])); // :205
 		cn.hits++;
 		{ // raytrace.h:36-44: the direct light, each arm with what this instance's pack switches on
@@ -505,7 +532,13 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 			const SphereTree &st = pick<SphereTree>(qs...);
 			const Shadows shadows{sv, ts.trees, n.file};
 			const Spheres spheres{st};
-			if constexpr(SPOT) // the pair loop with the cone decision ahead of the shadow walk (SOFT: and the light sample ahead of that)
+			if constexpr(MOTION)
+			{ // the same pair loop on the spheres of the sample; the shadow masks are built from the centres at rest: a view without them (the precedent: direct_light_cone's `every`)
+				SceneView moved = sv;
+				moved.smask = nullptr;
+				n.direct = direct_light_cone<SOFT>(moved, p, pick<SpotLights>(qs...), pick<SoftLights>(qs...), kd, ld3(ks4), ambp, n.P, n.N, n.pixel, n.node_id, cn, shadows, at);
+			}
+			else if constexpr(SPOT) // the pair loop with the cone decision ahead of the shadow walk (SOFT: and the light sample ahead of that)
 				n.direct = direct_light_cone<SOFT>(sv, p, pick<SpotLights>(qs...), pick<SoftLights>(qs...), kd, ld3(ks4), ambp, n.P, n.N, n.pixel, n.node_id, cn, shadows);
 			else if(FOG && !(surf & SURF_TRI)) n.direct = direct_light_fog(sv, p, kd, ld3(ks4), ambp, n.P, n.N, ld3(sv.geom[surf]), n.pixel, n.node_id, cn, spheres);
 			else n.direct = direct_light_of<false>(sv, p, kd, ld3(ks4), ambp, n.P, n.N, cn, shadows, spheres);
@@ -620,10 +653,12 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
 	return rows > 0 && gplan_for(p, rows, pl);
 }
 
-// Calls `launch` with the pack of an instance: [ShadeRays] [TriShadows] [SphereTree | SpotLights [SoftLights]] [Lens], the one place the
-// order is written down.  K: whose pack — the activate kernel's is the whole of it; the trace kernel takes only [ShadeRays] [SphereTree]
-// [Lens], the finalize kernel [ShadeRays] [SphereTree].  The combinations skr_features_conflict refuses (the sphere tree with spot
-// lights, a radius or a lens) are no instance, nor is a lens with a shading query (its rays are the caller's).
+// Calls `launch` with the pack of an instance: [ShadeRays] [TriShadows] [SphereTree | SpotLights [SoftLights]] [Lens | Motion], the one
+// place the order is written down.  K: whose pack — the activate kernel's is the whole of it; the trace kernel takes only [ShadeRays]
+// [SphereTree] [Lens | Motion], the finalize kernel [ShadeRays] [SphereTree].  The combinations skr_features_conflict refuses (the sphere
+// tree with spot lights, a radius, a lens or motion; a lens with motion) are no instance, nor is a lens with a shading query (its rays are
+// the caller's).  A launch with motion always carries SpotLights SoftLights (their tables have n = 0 where the scene has none), so motion
+// adds two trace and four activate instances.
 enum PackOf { PACK_FINALIZE, PACK_TRACE, PACK_ACTIVATE };
 template <PackOf K, typename F>
 static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
@@ -638,9 +673,12 @@ static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 		if(f.sphere_tree) return launch(head..., f.stree);
 		if constexpr(ACT)
 		{
+			if(f.motion) return launch(head..., f.spots, f.softs, f.mot);
 			if(f.soft) return lens(head..., f.spots, f.softs);
 			if(f.spot) return lens(head..., f.spots);
 		}
+		else if constexpr(K == PACK_TRACE)
+			if(f.motion) return launch(head..., f.mot);
 		lens(head...);
 	};
 	auto shadows = [&](auto... head) {

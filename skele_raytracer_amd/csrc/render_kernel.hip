@@ -34,7 +34,7 @@ static size_t direct_lds_bytes(const RenderParams &p)
 }
 
 // Which kernels render this launch, and what they need.  In this order:
-//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, a lens, and every tree
+//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, a lens, motion, and every tree
 //     (shade() recurses: max_depth > 1; api.cpp folds --depth to 1 where it cannot, raytrace.h:208-218) the node pipeline does not;
 //   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget and its kernels
 //     fit the device's LDS;
@@ -46,7 +46,7 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, co
 {
 	lp = LaunchPlan();
 	lp.features = f;
-	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft || f.lens;
+	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft || f.lens || f.motion;
 	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
 		lp.path = SKR_PATH_NODES;
@@ -84,17 +84,20 @@ const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect,
 										"light radii (--light-radius) cannot be combined with the sphere tree (--sphere-tree)"};
 	static const char *const lens[3] = {"a lens (--aperture) cannot be combined with --legacy-reflect", "a lens (--aperture) cannot be combined with fog volumes (--scn-fog)",
 										"a lens (--aperture) cannot be combined with the sphere tree (--sphere-tree)"};
-	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : f.lens ? lens[with] : nullptr;
+	static const char *const motion[3] = {"motion blur (sphere velocities under --shutter) cannot be combined with --legacy-reflect", "motion blur (sphere velocities under --shutter) cannot be combined with fog volumes (--scn-fog)",
+										  "motion blur (sphere velocities under --shutter) cannot be combined with the sphere tree (--sphere-tree)"};
+	if(f.motion && f.lens) return "motion blur (sphere velocities under --shutter) cannot be combined with a lens (--aperture)";
+	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : f.lens ? lens[with] : f.motion ? motion[with] : nullptr;
 }
 
 const char *skr_generic_variant(bool query, const GenericFeatures &f)
-{ // (fog has no name of its own; a lens is a frame's: no shading query and no sphere-tree instance has one)
-#define SKR_VARIANT_NAMES(base) {{base, base "_tshadow"}, {base "_lens", base "_lens_tshadow"}}
-	static const char *const name[2][4][2][2] = {
+{ // (fog has no name of its own; a lens is a frame's: no shading query and no sphere-tree instance has one; motion excludes both)
+#define SKR_VARIANT_NAMES(base) {{base, base "_tshadow"}, {base "_lens", base "_lens_tshadow"}, {base "_motion", base "_motion_tshadow"}}
+	static const char *const name[2][4][3][2] = {
 		{SKR_VARIANT_NAMES("level_pipeline_g1"), SKR_VARIANT_NAMES("level_pipeline_g1_stree"), SKR_VARIANT_NAMES("level_pipeline_g1_spot"), SKR_VARIANT_NAMES("level_pipeline_g1_soft")},
 		{SKR_VARIANT_NAMES("shade_rays_g1"), SKR_VARIANT_NAMES("shade_rays_g1_stree"), SKR_VARIANT_NAMES("shade_rays_g1_spot"), SKR_VARIANT_NAMES("shade_rays_g1_soft")}};
 #undef SKR_VARIANT_NAMES
-	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][!query && f.lens][f.tri_shadows];
+	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][f.motion ? 2 : !query && f.lens][f.tri_shadows];
 }
 
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)
@@ -443,8 +446,32 @@ __global__ void skr_debug_pow_kernel(const uint32_t *in, uint32_t *out, uint32_t
 	out[i] = r;
 }
 
+// Op 24: the shutter time and the displaced centre of one record: (pixel, aa, seed_lo, seed_hi, S, c(3), v(3)) -> (tau, c'(3)), through
+// shutter_time and MovingCentres::centre, the functions the kernels of a launch with motion call (a kernel of its own: the ops above
+// keep their code)
+__global__ void skr_debug_motion_kernel(const uint32_t *in, uint32_t *out, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	auto F = [](uint32_t u) { return __uint_as_float(u); };
+	auto U = [](float f) { return __float_as_uint(f); };
+	const uint32_t *r = in + 11 * i;
+	RenderParams p{};
+	p.seed_lo = r[2];
+	p.seed_hi = r[3];
+	const float tau = shutter_time(p, r[0], r[1], F(r[4]));
+	const float4 c = MovingCentres::centre(make_float4(F(r[5]), F(r[6]), F(r[7]), 0.0f), make_float4(F(r[8]), F(r[9]), F(r[10]), 0.0f), tau);
+	uint32_t *w = out + 4 * i;
+	w[0] = U(tau); w[1] = U(c.x); w[2] = U(c.y); w[3] = U(c.z);
+}
+
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream)
 {
+	if(op == 24)
+	{
+		hipLaunchKernelGGL(skr_debug_motion_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n);
+		return hipGetLastError();
+	}
 	if(op == 23)
 	{
 		hipLaunchKernelGGL(skr_debug_pow_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n);

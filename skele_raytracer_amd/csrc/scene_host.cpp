@@ -166,6 +166,9 @@ static void set_camera(skr_scene_info &info, const float p[3], const float d[3],
 int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene &sc)
 {
 	const bool strict = (flags & SKR_SCN_STRICT) != 0, fog = (flags & SKR_SCN_FOG) != 0, spot = (flags & SKR_SCN_SPOT) != 0;
+	const bool motion = (flags & SKR_SCN_MOTION) != 0;
+	float vel[3] = {0.0f, 0.0f, 0.0f}; // SKR_SCN_MOTION: the velocity in force for the sphere lines that follow, stateful as `material` is
+	std::vector<float> vels;
 	FILE *fp = fopen(path.c_str(), "r");
 	if(!fp)
 	{
@@ -207,6 +210,7 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 								   mat.diffuse[0], mat.diffuse[1], mat.diffuse[2], mat.specular[0], mat.specular[1], mat.specular[2], mat.power};
 			sc.raw_spheres.insert(sc.raw_spheres.end(), rec, rec + 14);
 			sc.raw_sphere_ior.push_back(mat.ior);
+			vels.insert(vels.end(), vel, vel + 3);
 			info.n_spheres++;
 		}
 		else if(cmd == "vertex")
@@ -358,6 +362,21 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 				info.n_unknown++;
 			}
 		}
+		else if(motion && cmd == "velocity")
+		{ // SKR_SCN_MOTION (the reference does not know the command): vx vy vz
+			float v[3] = {0, 0, 0};
+			const int got = read_floats(args, v, 3);
+			if(got == 3 && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]))
+			{
+				if(echo) printf("velocity (%f, %f, %f)\n", v[0], v[1], v[2]);
+				memcpy(vel, v, sizeof vel);
+			}
+			else
+			{
+				fprintf(stderr, "WARNING. velocity needs 3 finite numbers (vx vy vz): line skipped\n");
+				info.n_unknown++;
+			}
+		}
 		else
 		{
 			if(echo) printf("WARNING. Do not know command: %s\n", cmd.c_str());
@@ -366,6 +385,7 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 	}
 	fclose(fp);
 	sc.finalize();
+	if(motion) sc.velocities = vels;
 	return SKR_OK;
 }
 
@@ -536,6 +556,50 @@ int skr_scene_get_lens(const skr_scene *scene, float *aperture, float *focus)
 	if(!scene) return SKR_ERR_ARG;
 	if(aperture) *aperture = scene->lens_aperture;
 	if(focus) *focus = scene->lens_focus;
+	return SKR_OK;
+}
+
+int skr_scene_set_sphere_velocities(skr_scene *scene, const float *v, int32_t n)
+{
+	if(!scene || n < 0 || n != scene->info.n_spheres || (n && !v))
+	{
+		skr_set_error("skr_scene_set_sphere_velocities: bad argument (one velocity of 3 floats per sphere: %d)", scene ? scene->info.n_spheres : 0);
+		return SKR_ERR_ARG;
+	}
+	for(size_t i = 0; i < (size_t) n * 3; i++)
+		if(!std::isfinite(v[i]))
+		{
+			skr_set_error("skr_scene_set_sphere_velocities: velocity %zu has a component that is not finite", i / 3);
+			return SKR_ERR_ARG;
+		}
+	scene->velocities.assign(v, v + (size_t) n * 3);
+	return SKR_OK;
+}
+
+int skr_scene_get_sphere_velocities(const skr_scene *scene, float *v, int32_t *n)
+{
+	if(!scene) return SKR_ERR_ARG;
+	const size_t ns = (size_t) scene->info.n_spheres;
+	if(n) *n = (int32_t) ns;
+	for(size_t i = 0; v && i < ns * 3; i++) v[i] = i < scene->velocities.size() ? scene->velocities[i] : 0.0f;
+	return SKR_OK;
+}
+
+int skr_scene_set_shutter(skr_scene *scene, float shutter)
+{
+	if(!scene || !std::isfinite(shutter) || !(shutter >= 0.0f))
+	{
+		skr_set_error("skr_scene_set_shutter: the shutter must be a finite number >= 0");
+		return SKR_ERR_ARG;
+	}
+	scene->shutter = shutter + 0.0f; // (-0 -> +0)
+	return SKR_OK;
+}
+
+int skr_scene_get_shutter(const skr_scene *scene, float *shutter)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(shutter) *shutter = scene->shutter;
 	return SKR_OK;
 }
 

@@ -52,6 +52,15 @@ struct skr_scene {
 	std::vector<float> raw_spot_lights;  // [n][11] colour position direction angle1 angle2, the file's fields in file order — SKR_SCN_SPOT / skr_scene_set_spot_lights only
 	std::vector<float> light_radii;      // [n_point + n_spot] the radius of every point and spot light in light order, 0 = a point — skr_scene_set_light_radii only (build_lights() sizes it)
 	float lens_aperture = 0.0f, lens_focus = 1.0f; // the lens (A, F), A = 0: the pinhole — skr_scene_set_lens only (include/skr.h)
+	std::vector<float> velocities;       // [n][3] the velocity of every sphere in file order; empty = every sphere at rest — SKR_SCN_MOTION / skr_scene_set_sphere_velocities only (include/skr.h)
+	float shutter = 1.0f;                // the shutter S >= 0 — skr_scene_set_shutter only
+	bool motion() const                  // motion is in force: S > 0 and some velocity component is not 0
+	{
+		if(!(shutter > 0.0f)) return false;
+		for(float v : velocities)
+			if(v != 0.0f) return true;
+		return false;
+	}
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
 	bool sphere_tree = false;            // SKR_SCN_SPHERE_TREE / skr_scene_set_sphere_tree: likewise

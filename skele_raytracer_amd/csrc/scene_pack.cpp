@@ -83,6 +83,8 @@ std::vector<skr_f4> skr_pack_scene(const skr_scene &s, SceneLayout &d)
 		d.st_always = t.n_always;
 		d.st_ball = skr_f4{t.ball[0], t.ball[1], t.ball[2], t.ball[3]};
 	}
+	d.motion = s.motion();
+	d.shutter = s.shutter;
 	put(SKR_SEC_pad, nullptr, SKR_BLOB_PAD_ROWS * 16);
 	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
 		// ... and needs a product only at a bit that some integer exponent has set (pow_any; the others take powf_spec_cold lane by lane)

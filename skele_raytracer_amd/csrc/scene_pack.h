@@ -52,6 +52,8 @@ struct SceneLayout {
 	bool sphere_tree = false; // the sphere tree (include/skr.h skr_scene_set_sphere_tree), packed where the scene had the switch on
 	int st_nodes = 0, st_chunks = 0, st_always = 0;
 	skr_f4 st_ball{};
+	bool motion = false;  // motion is in force (skr_scene::motion(), include/skr.h skr_scene_set_sphere_velocities): frames and shading queries take the instances with the shutter draw.
+	float shutter = 1.0f; // The velocities are no section of the blob: the renderer uploads them beside it (api.cpp DeviceScene::d_vel)
 };
 
 // The blob of `s` and its layout; nothing is uploaded.

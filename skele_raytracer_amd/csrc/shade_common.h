@@ -72,6 +72,28 @@ SKR_DEV float4 load_const4(const float4 *base, int i)
 	return make_float4(v.x, v.y, v.z, v.w);
 }
 
+// ---- where a sphere is during a sample (include/skr.h skr_scene_set_sphere_velocities) ----
+// The centre policy of the sphere searches: `row(g, i)` is the row {centre, r^2} of sphere i as a search tests it, g the row at rest.
+// AtRest is the scene as it lies — no code, as NoTriangleShadows and SphereLoopShadows are none — and what every instance without a
+// Motion in its pack is compiled with.  MovingCentres is the sample at shutter time tau of the lane: c' = fma(tau, v_i, c_i), one
+// correctly rounded fused multiply-add per component (the stated exception to "not contracted"), r^2 unchanged.  The velocity rows
+// {v.xyz, 0} are the renderer's own allocation (launch.h Motion), read through the constant address space: at the wave-uniform index of a
+// sphere loop one scalar load beside the sphere row's, at a lane's own index (the normal of a hit) a vector load.
+struct AtRest {
+	static constexpr bool moving = false;
+	__device__ __forceinline__ float4 row(float4 g, int) const { return g; }
+};
+struct MovingCentres {
+	static constexpr bool moving = true;
+	const float4 *vel;
+	float tau;
+	static __device__ __forceinline__ float4 centre(float4 g, float4 v, float tau)
+	{
+		return make_float4(__builtin_fmaf(tau, v.x, g.x), __builtin_fmaf(tau, v.y, g.y), __builtin_fmaf(tau, v.z, g.z), g.w);
+	}
+	__device__ __forceinline__ float4 row(float4 g, int i) const { return centre(g, load_const4(vel, i), tau); }
+};
+
 // The sphere loops of the level pipelines (closest_pair_deferred, occluded_pair<false>): `test(row, index)` for every sphere in order,
 // SKR_SPHERE_TRIP spheres per trip, the rows of the next trip asked for a trip ahead with ONE scalar load (s_load_dwordx8 / x16: the rows
 // are consecutive).  The rows come through the scalar cache into SGPRs (geom_u), so the spheres in flight cost no vector register for
@@ -179,14 +201,15 @@ SKR_DEV RayConst make_ray(f3 o, f3 d)
 
 // raytrace.h:152-165: closest accepted sphere (strict <, first index wins ties),
 // evaluated exactly as written: the binary64 root for every sphere with D >= 0.
-SKR_DEV int closest_sphere_exact(const SceneView &sv, const RayConst &r, float &tmin)
+template <typename M = AtRest>
+SKR_DEV int closest_sphere_exact(const SceneView &sv, const RayConst &r, float &tmin, const M &m = M())
 {
 	int best = -1;
 	tmin = __builtin_inff();
 	float4 g_next = sv.geom[0];
 	for(int i = 0; i < sv.ns; i++)
 	{
-		const float4 g = g_next;
+		const float4 g = m.row(g_next, i);
 		g_next = sv.geom[i + 1]; // software prefetch; geom[] carries one pad entry
 		const float t = sphere_distance(r.o, r.d, r.two_a, r.four_a, g);
 		if(accept_distance(t) && t < tmin)
@@ -202,9 +225,10 @@ SKR_DEV int closest_sphere_exact(const SceneView &sv, const RayConst &r, float &
 // known as soon as its bracket lies strictly below every other accepted
 // sphere's; its exact t2 is then formed once.  Overlapping brackets (two
 // surfaces within ~1e-6 relative of each other along the ray) fall back to the
-// exact loop for that lane.  The rows of `table`, K per trip; `bracket(row, f, lo, hi, b, D)` is the test of one row.
-template <int K, typename B>
-SKR_DEV int closest_of_rows(const SceneView &sv, const float4 *table, const RayConst &r, float &tmin, B bracket)
+// exact loop for that lane.  The rows of `table`, K per trip; `bracket(row, f, lo, hi, b, D)` is the test of one row.  M: where the
+// spheres are (AtRest, MovingCentres; sphere rows only).
+template <int K, typename B, typename M = AtRest>
+SKR_DEV int closest_of_rows(const SceneView &sv, const float4 *table, const RayConst &r, float &tmin, B bracket, const M &m = M())
 {
 	const RayFilt f = make_filt(r.d);
 	int best = -1;
@@ -213,20 +237,21 @@ SKR_DEV int closest_of_rows(const SceneView &sv, const float4 *table, const RayC
 	table_rows<K>(table, sv.ns, [&](const float4 row, int i)
 	{
 		float lo, hi, b, D;
-		if(bracket(row, f, lo, hi, b, D)) best_update(best_hi, others_lo, best_lo, best, best_b, best_D, i, lo, hi, b, D);
+		if(bracket(m.row(row, i), f, lo, hi, b, D)) best_update(best_hi, others_lo, best_lo, best, best_b, best_D, i, lo, hi, b, D);
 	}, [] { return true; });
 	tmin = __builtin_inff();
 	if(best >= 0)
 	{
 		if(others_lo > best_hi) tmin = bracket_t(f.two_a, best_lo, best_hi, best_b, best_D);
-		else best = closest_sphere_exact(sv, r, tmin);
+		else best = closest_sphere_exact(sv, r, tmin, m);
 	}
 	return best;
 }
-SKR_DEV int closest_sphere(const SceneView &sv, const RayConst &r, float &tmin)
+template <typename M = AtRest>
+SKR_DEV int closest_sphere(const SceneView &sv, const RayConst &r, float &tmin, const M &m = M())
 {
 	return closest_of_rows<SKR_SPHERE_TRIP>(sv, sv.geom_u, r, tmin, // (the rows of sphere_rows)
-		[&](const float4 g, const RayFilt &f, float &lo, float &hi, float &b, float &D) { return sphere_bracket(r.o, r.d, f, g, lo, hi, b, D); });
+		[&](const float4 g, const RayFilt &f, float &lo, float &hi, float &b, float &D) { return sphere_bracket(r.o, r.d, f, g, lo, hi, b, D); }, m);
 }
 
 // closest_sphere() for rays that all start at ONE point (the camera: main.cpp:140-182), with e = o - C and c = e.e - r^2 of utils.h:115-118
@@ -525,15 +550,16 @@ SKR_DEV uint32_t gi_cands(const RenderParams &p, int row, f3 d0, f3 d1, bool sec
 // With shadow masks (the level pipelines, !COHERENT): `cand` = the union of the lane's two masks (shadow_mask_of).  A sphere outside a
 // ray's mask provably fails pair_any_step's candidate test (its D < 0), so each lane walks only its own candidates, lowest index first: the first
 // occluder it finds is the one the loop over every sphere finds, and every decision and count is the same.
-template <bool COHERENT, typename SH = RunTimeShape>
-SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second, bool &occ0, bool &occ1, uint32_t &tests, uint32_t cand = 0u)
+// M: where the spheres are (AtRest, MovingCentres).
+template <bool COHERENT, typename SH = RunTimeShape, typename M = AtRest>
+SKR_DEV void occluded_pair(const SceneView &sv, f3 P, f3 L0, f3 L1, bool second, bool &occ0, bool &occ1, uint32_t &tests, uint32_t cand = 0u, const M &m = M())
 {
 	const f3 o = add_scalar(P, 0.000001f);
 	const RayPair rp = make_pair(L0, L1);
 	const PairAny pa = make_pair_any(rp);
 	occ0 = false;
 	occ1 = !second;
-	auto test = [&](const float4 g, int i) { pair_any_step(rp, pa, o, g, i, occ0, occ1, tests); };
+	auto test = [&](const float4 g, int i) { pair_any_step(rp, pa, o, m.row(g, i), i, occ0, occ1, tests); };
 	if(COHERENT) table_rows<SKR_COHERENT_TRIP>(sv.geom_u, sv.ns, test, [&] { return !__all(occ0 && occ1); }); // (the wave-wide exit, once per trip)
 	else if(SH::masks || sv.smask)
 	{
@@ -929,9 +955,10 @@ SKR_DEV float load_const1(const float *base, int i)
 // pair in which either light has R > 0 walks every sphere (the shadow masks are built for rays toward Lp); a pair of two R == 0 lights
 // is walked as without SOFT.  (pixel, node): the node's counter words.  Nothing of a sample stays live across the shadow walk but its
 // LightTerm: the triangle walk's far end draws the sample again.
-template <bool SOFT, typename TS>
+// M: where the spheres are for the shadow rays (AtRest, MovingCentres; a caller with MovingCentres hands in a view without shadow masks).
+template <bool SOFT, typename TS, typename M = AtRest>
 SKR_DEV f3 direct_light_cone(const SceneView &sv, const RenderParams &p, const SpotLights &sp, const SoftLights &so, f3 kd, f3 ks, float4 ambp, f3 P, f3 N,
-							 uint32_t pixel, uint32_t node, Counters &cn, const TS &tri_shadows)
+							 uint32_t pixel, uint32_t node, Counters &cn, const TS &tri_shadows, const M &m = M())
 {
 	f3 diffuse = mk3(0, 0, 0), specular = mk3(0, 0, 0);
 	const f3 view = normalize3(p.cam_pos - P);
@@ -989,7 +1016,7 @@ SKR_DEV f3 direct_light_cone(const SceneView &sv, const RenderParams &p, const S
 				if(both) cand |= shadow_mask_of(sv, i + 1, ld3(sv.lights[2 * i + 2]) - P);
 			}
 			bool oa, ob;
-			occluded_pair<false>(w, P, La, t1.L, both, oa, ob, cn.shadow_tests, cand);
+			occluded_pair<false, RunTimeShape, M>(w, P, La, t1.L, both, oa, ob, cn.shadow_tests, cand, m);
 			if constexpr(TS::on && SOFT)
 			{ // blinn_phong.h's `distance`, of the sample where the light has one
 				auto far = [&](int l, float R) { return R > 0.0f ? length3(to_light(l, R)) : tri_shadows.reach(l, P); };

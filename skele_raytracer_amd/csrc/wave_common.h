@@ -125,6 +125,18 @@ SKR_DEV void lens_ray(const RenderParams &p, const Lens &lens, uint32_t pixel, u
 	}
 }
 
+// The shutter time of sample (pixel, aa) of a scene in motion (include/skr.h skr_scene_set_sphere_velocities): one Philox
+// call at node 0 with the counter word SKR_SHUTTER_CTR3, tau = S * u in one binary32 multiply.  The one copy of the draw: every lane that
+// searches the spheres of a sample or forms a normal on one calls this with the pixel word of its tree's root — a trace lane with
+// y * width + x, the query ray's key or its parent node's pixel word, an activate lane with its node's — so nothing of the draw is
+// carried in a record or a node (as direct_light_cone draws a light's sample again).
+SKR_DEV float shutter_time(const RenderParams &p, uint32_t pixel, uint32_t aa, float S)
+{
+	uint32_t rnd[4];
+	philox4x32(pixel, aa, 0u, shutter_ctr3(), p.seed_lo, p.seed_hi, rnd);
+	return S * u31_to_unit(rnd[0]);
+}
+
 SKR_DEV void emit_sample(const RenderParams &p, uint32_t out_pix, f3 c)
 { // one sample of one pixel is final: store it (1 spp) or add it to the running sum (AA, sample order = launch order)
 	if(p.grid_size > 0)

@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--aperture A [--focus F]] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--aperture A [--focus F]] [--scn-motion] [--shutter S] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
            [--adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
@@ -89,6 +89,10 @@ def _parse(argv):
             opt["scn_spot"] = True
         elif a == "--light-radius":
             opt["light_radius"] = value(i, _atof, "light-radius takes a float (the radius of every point and spot light)")
+        elif a == "--scn-motion":
+            opt["scn_motion"] = True
+        elif a == "--shutter":
+            opt["shutter"] = value(i, _atof, "shutter takes a float (how long the shutter is open)")
         elif a == "--aperture":
             opt["aperture"] = value(i, _atof, "aperture takes a float (the radius of the lens)")
         elif a == "--focus":
@@ -176,9 +180,13 @@ def main(argv=None):
             dist.init_process_group("gloo")
         else:
             dist.init_process_group("nccl", device_id=dev)  # RCCL over xGMI
+    shutter = o.get("shutter")
+    if shutter is not None and not (math.isfinite(shutter) and shutter >= 0.0):
+        print("raytracer: --shutter takes a finite number >= 0", file=sys.stderr)  # as bin/raytracer
+        return 2
     try:
         scene = skr.parse_scene(o["path"], strict=bool(o.get("strict_scn")), fog=bool(o.get("scn_fog")), triangle_shadows=bool(o.get("triangle_shadows")),
-                                sphere_tree=bool(o.get("sphere_tree")), spot=bool(o.get("scn_spot")))
+                                sphere_tree=bool(o.get("sphere_tree")), spot=bool(o.get("scn_spot")), motion=bool(o.get("scn_motion")))
     except skr.SkrError as e:
         if rank == 0:
             print(str(e))  # scene.cpp:24: "Can't open file" on stdout, exit(0)
@@ -199,6 +207,8 @@ def main(argv=None):
         scene.set_light_radii(radius)
     if aperture is not None:  # as bin/raytracer --aperture A [--focus F]: a thin lens (include/skr.h skr_scene_set_lens); --focus alone has no effect
         scene.set_lens(aperture, focus)
+    if shutter is not None:  # as bin/raytracer --shutter S (include/skr.h skr_scene_set_shutter); without velocities it has no effect
+        scene.set_shutter(shutter)
     r = skr.Renderer(scene, local_rank)
     kw = dict(fov=o["fov"], depth=o["depth"], shadow=o["shadow"], seed=o["seed"], shade_triangles=bool(o.get("shade_triangles")), progressive=o.get("progressive", 1), legacy_reflect=bool(o.get("legacy_reflect")))
     if o["gillum"] is not None:

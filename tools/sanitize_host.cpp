@@ -164,6 +164,26 @@ int main(int argc, char **argv)
 		skr_scene_set_sphere_tree(sc, 1);
 		blob_table(sc, argv[a], "sphere_tree");
 		skr_scene_destroy(sc);
+		// motion: the loader under its flag, the setters with good and bad arguments, the getters; the velocities are no section of the blob
+		skr_scene *mv = nullptr;
+		if(skr_scene_create_from_scn_ex(argv[a], 0, SKR_SCN_MOTION, &mv) == 0)
+		{
+			const int32_t ns = info.n_spheres;
+			std::vector<float> v((size_t) ns * 3 + 3, 0.5f), back((size_t) ns * 3 + 3, -1.0f);
+			int32_t n = -1;
+			skr_scene_get_sphere_velocities(mv, back.data(), &n);
+			const int ok = skr_scene_set_sphere_velocities(mv, v.data(), ns);
+			const int wrong_n = skr_scene_set_sphere_velocities(mv, v.data(), ns + 1);
+			v[0] = NAN;
+			const int not_finite = skr_scene_set_sphere_velocities(mv, v.data(), ns);
+			skr_scene_get_sphere_velocities(mv, back.data(), &n);
+			float S = -1.0f;
+			const int s_ok = skr_scene_set_shutter(mv, 0.25f), s_bad = skr_scene_set_shutter(mv, -1.0f);
+			skr_scene_get_shutter(mv, &S);
+			printf("%s: motion %d spheres, set %d %d %d, v0 %g, shutter %d %d %g\n", argv[a], n, ok, wrong_n, not_finite, ns > 0 ? back[0] : 0.0f, s_ok, s_bad, S);
+			blob_table(mv, argv[a], "motion");
+			skr_scene_destroy(mv);
+		}
 	}
 	std::vector<uint8_t> px(7 * 5 * 3, 200);
 	skr_write_ppm("build/asan_out.ppm", 7, 5, px.data());

@@ -17,7 +17,7 @@ for f in tools/sanitize_host.cpp $SRCS; do # (side by side)
 done
 for p in $pids; do wait "$p"; done # (set -e: the script stops at the first file that did not compile)
 g++ $FLAGS -o build/sanitize_host build/sanitize_obj/*.o
-printf 'sphere 1 2\nvertex 1 2\ntriangle 0 1 999999\ntriangle -5 0 1\nmaterial 1\ncamera\npoint_light 1 2 3\nvertex nan inf -inf\nvertex 1e39 0 0\ntriangle 0 0 0\ntriangle 1.7 0.2 2.9\n' > build/bad1.scn
+printf 'sphere 1 2\nvertex 1 2\ntriangle 0 1 999999\ntriangle -5 0 1\nmaterial 1\ncamera\npoint_light 1 2 3\nvertex nan inf -inf\nvertex 1e39 0 0\ntriangle 0 0 0\ntriangle 1.7 0.2 2.9\nvelocity 1 nan 3\nvelocity 1 2\nvelocity 1 2 3\nsphere 0 0 0 1\n' > build/bad1.scn
 : > build/empty.scn
 rm -f build/gen_*.scn
 python3 - <<'PY'
