@@ -36,6 +36,7 @@ extern "C" {
 #define SKR_HAS_ROOT_PAIRS 1 /* skr_debug_eval op 19: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_LENS 1 /* skr_scene_set/get_lens, skr_debug_eval op 22: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_MOTION 1 /* SKR_SCN_MOTION, skr_scene_set/get_sphere_velocities, skr_scene_set/get_shutter, skr_debug_eval op 24: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_ENVIRONMENT 1 /* skr_scene_set/get_environment, skr_read_pfm, skr_debug_eval op 25: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -334,6 +335,42 @@ int skr_scene_set_sphere_velocities(skr_scene *scene, const float *v, int32_t n)
 int skr_scene_get_sphere_velocities(const skr_scene *scene, float *v, int32_t *n);
 int skr_scene_set_shutter(skr_scene *scene, float shutter);
 int skr_scene_get_shutter(const skr_scene *scene, float *shutter);
+/* Environment map: an image-based background and GI light (new, opt-in; no counterpart in the reference, whose misses return one
+ * constant colour).  A scene may carry an environment: a square image of E x E RGB binary32 texels T[j][i], 1 <= E <= SKR_ENV_MAX_EDGE,
+ * every texel finite.  The environment is in force iff the scene has one.  The rule (normative):
+ *   - Where it is read.  With the environment in force every ray for which shade() would return scene.background (raytrace.h:189-192)
+ *     returns env(d) instead, d that ray's direction as traced: a frame's primary ray (under a lens: d'), a --gillum child ray at any
+ *     level, a shading query's ray, including one whose winner lies at or beyond tmax.  A ray that a triangle blackens
+ *     (raytrace.h:221-224) stays black.  Shadow rays and the direct light loop do not read the environment: it lights surfaces only
+ *     through --gillum children.  All work counters are those of the same frame with a constant background.
+ *   - env(d): an octahedral map with world +y at the centre of the square, filtered bilinearly, clamped at the square's border.
+ *     Everything is binary32, each step one correctly rounded operation, nothing contracted, no transcendental function:
+ *       1. s = (|dx| + |dy|) + |dz|.  If !(s > 0) or s is not finite, env(d) is the scene's background (a zero direction, a NaN, an
+ *          overflow, infinities).
+ *       2. px = dx / s, pz = dz / s.
+ *       3. If dy < 0 (a -0 is not < 0): qx = (1 - |pz|) * sgn(px), qz = (1 - |px|) * sgn(pz), sgn(x) = x < 0 ? -1 : +1.  Otherwise
+ *          qx = px, qz = pz.
+ *       4. u = qx * 0.5f + 0.5f, v = qz * 0.5f + 0.5f.
+ *       5. x = u * (float) E - 0.5f, x0 = floorf(x), fx = x - x0, i0 = clamp((int) x0, 0, E - 1), i1 = clamp((int) x0 + 1, 0, E - 1);
+ *          likewise y, y0, fy, j0, j1 from v.
+ *       6. Per channel: top = T[j0][i0] + fx * (T[j0][i1] - T[j0][i0]); bot the same on row j1; env = top + fy * (bot - top).
+ *     So env depends on d only up to a power-of-two scale; a map whose texels all equal a finite colour c returns c exactly (c = -0
+ *     gives +0), and a map holding the scene's background is the frame it was; with E = 1 every lookup is texel (0, 0).
+ *   - Where it runs: a launch with the environment in force always takes the general level pipeline, frames the direct kernel or the
+ *     node pipeline would otherwise render included; skr_kernel_variant() carries one "_env" part at its end
+ *     ("level_pipeline_g1_env", "level_pipeline_g1_soft_lens_tshadow_env", "shade_rays_g1_env", ...).  It combines with use_shadows,
+ *     grid_size, num_path_traces at any depth, SKR_SCN_STRICT, shade_triangles with or without triangle shadows, spot lights, light
+ *     radii, motion, a lens, tiles and strides, bands, clones, skr_multi / skr_comm, progressive and adaptive frames, shading queries.
+ *   - Refused with SKR_ERR_UNSUPPORTED where the environment is in force (and only there): skr_options.legacy_reflect, fog volumes,
+ *     the sphere-tree switch, and skr_render_denoised_host / skr_render_adaptive_denoised_host (their guides hold one class for every
+ *     miss: the filter would smear the backdrop).  skr_denoise on caller-supplied guides stays as it is.
+ * set: texels float[edge][edge][3], row j first; edge == 0 or NULL texels clears the environment; an edge outside
+ * [1, SKR_ENV_MAX_EDGE] or a texel that is not finite: SKR_ERR_ARG and the scene is unchanged.  get: *edge = E (0: none), texels (if
+ * not NULL) receives float[E][E][3].  A renderer takes the environment when it is created (an allocation of its own beside the scene
+ * blob); skr_renderer_clone and the multi-GPU frame steps share it. */
+#define SKR_ENV_MAX_EDGE 4096
+int skr_scene_set_environment(skr_scene *scene, const float *texels, int32_t edge);
+int skr_scene_get_environment(const skr_scene *scene, float *texels, int32_t *edge);
 /* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
  * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
  * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device
@@ -732,6 +769,12 @@ int skr_write_ppm(const char *path, uint32_t width, uint32_t height, const uint8
  * first; rgbf is top row first like every buffer of this interface. */
 int skr_write_png(const char *path, uint32_t width, uint32_t height, const uint8_t *rgb);
 int skr_write_pfm(const char *path, uint32_t width, uint32_t height, const float *rgbf);
+/* The inverse of skr_write_pfm (new; `raytracer --envmap FILE.pfm`): a colour "PF" file, either sign of the scale line (negative:
+ * little-endian, positive: big-endian; its magnitude is not applied).  *width, *height: the sizes; rgbf (if not NULL) receives
+ * height * width * 3 floats, TOP row first, so that reading what skr_write_pfm wrote gives the buffer back bit for bit; NULL: the
+ * sizes only.  A file that is no colour PFM, has a size < 1, a scale of 0 or not finite, or ends early: SKR_ERR_IO with a text.
+ * Row j of an environment (skr_scene_set_environment) is row j of this array. */
+int skr_read_pfm(const char *path, uint32_t *width, uint32_t *height, float *rgbf);
 
 /* ---- diagnostics ---- */
 const char *skr_last_error(void);      /* thread-local text of the last failure */
@@ -790,7 +833,10 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  *    not plain; 0xFFFFFFFF for a mask that has no instance.
  * 24 the shutter time and a displaced centre (skr_scene_set_sphere_velocities above; wave_common.h shutter_time and shade_common.h
  *    MovingCentres::centre, the functions the kernels of a launch with motion call): (pixel, aa, seed_lo, seed_hi, S, c(3), v(3)),
- *    11 words -> (tau, c'(3)), 4 words. */
+ *    11 words -> (tau, c'(3)), 4 words.
+ * 25 the environment lookup's taps (skr_scene_set_environment above; wave_common.h env_taps, the index code env_lookup itself runs):
+ *    (d(3), E as an integer), 4 words -> (flag: 1 = the background arm, i0, i1, j0, j1 as integers, fx, fy), 7 words; the six
+ *    behind a flag of 1 are 0. */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

@@ -12,9 +12,9 @@ There is no CPU fallback: every render entry point raises if libskr.so or a
 gfx950 device is missing.
 """
 from .binding import (Options, Renderer, Scene, SkrError, lib, lib_path, parse_scene, scene_fov, radiance_ray_count,
-                      write_ppm, write_png, write_pfm, EXPORTED_SYMBOLS, Hits, make_rays, TRACE_ANY_HIT, adaptive_params, ADAPTIVE_MIN_PASSES,
+                      write_ppm, write_png, write_pfm, read_pfm, EXPORTED_SYMBOLS, Hits, make_rays, TRACE_ANY_HIT, adaptive_params, ADAPTIVE_MIN_PASSES,
                       ADAPTIVE_MAX_PASSES, ADAPTIVE_THRESHOLD, ADAPTIVE_LUM_FLOOR, ADAPTIVE_PASS_LIMIT, DENOISE_VAR_SIGMA_L)
 
 __all__ = ["Options", "Renderer", "Scene", "SkrError", "lib", "lib_path", "parse_scene", "scene_fov", "radiance_ray_count",
-           "write_ppm", "write_png", "write_pfm", "EXPORTED_SYMBOLS", "Hits", "make_rays", "TRACE_ANY_HIT",
+           "write_ppm", "write_png", "write_pfm", "read_pfm", "EXPORTED_SYMBOLS", "Hits", "make_rays", "TRACE_ANY_HIT",
            "adaptive_params", "ADAPTIVE_MIN_PASSES", "ADAPTIVE_MAX_PASSES", "ADAPTIVE_THRESHOLD", "ADAPTIVE_LUM_FLOOR", "ADAPTIVE_PASS_LIMIT", "DENOISE_VAR_SIGMA_L"]

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_sphere_velocities", "skr_scene_get_sphere_velocities", "skr_scene_set_shutter", "skr_scene_get_shutter", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_sphere_velocities", "skr_scene_get_sphere_velocities", "skr_scene_set_shutter", "skr_scene_get_shutter", "skr_scene_set_environment", "skr_scene_get_environment", "skr_read_pfm", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -95,6 +95,9 @@ def lib():
     L.skr_scene_get_sphere_velocities.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_scene_set_shutter.argtypes = [vp, C.c_float]
     L.skr_scene_get_shutter.argtypes = [vp, C.POINTER(C.c_float)]
+    L.skr_scene_set_environment.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_environment.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.skr_read_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
     L.skr_scene_set_sphere_tree.argtypes = [vp, C.c_int]
@@ -406,6 +409,29 @@ class Scene:
         """Set the shutter S, finite and >= 0; 0 = closed: the scene at rest (include/skr.h skr_scene_set_shutter)."""
         _check(lib().skr_scene_set_shutter(self.h, C.c_float(float(shutter))), "skr_scene_set_shutter")
 
+    @property
+    def environment(self):
+        """The scene's environment, float32 [E, E, 3] with row j first, or None (include/skr.h skr_scene_get_environment)."""
+        e = C.c_int32(0)
+        _check(lib().skr_scene_get_environment(self.h, None, C.byref(e)), "skr_scene_get_environment")
+        if e.value == 0:
+            return None
+        t = np.zeros((e.value, e.value, 3), np.float32)
+        _check(lib().skr_scene_get_environment(self.h, t.ctypes.data, C.byref(e)), "skr_scene_get_environment")
+        return t
+
+    def set_environment(self, texels):
+        """Give the scene an environment map (include/skr.h skr_scene_set_environment states the rule): [E, E, 3] finite floats, an
+        octahedral map with world +y at the centre; rays that miss return it.  None clears it.  A renderer takes the environment the
+        scene has when it is made."""
+        if texels is None:
+            _check(lib().skr_scene_set_environment(self.h, None, 0), "skr_scene_set_environment")
+            return
+        t = np.ascontiguousarray(texels, np.float32)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 3 or t.shape[0] == 0:
+            raise ValueError("environment: a square [E, E, 3] array")
+        _check(lib().skr_scene_set_environment(self.h, t.ctypes.data, t.shape[0]), "skr_scene_set_environment")
+
     def set_lens(self, aperture, focus=1.0):
         """Give the camera a thin lens (depth of field; include/skr.h skr_scene_set_lens states the rule): aperture radius >= 0 (0: the
         pinhole), focus > 0 in units of the primary ray directions, both finite.  A renderer takes the lens the scene has when it is made."""
@@ -453,7 +479,7 @@ class Scene:
 
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
-                    triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None, velocities=None, shutter=None):
+                    triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None, velocities=None, shutter=None, environment=None):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -483,11 +509,14 @@ class Scene:
             sc.set_velocities(velocities)
         if shutter is not None:
             sc.set_shutter(shutter)
+        if environment is not None:  # [E, E, 3] (an image-based background and GI light)
+            sc.set_environment(environment)
         return sc
 
 
 SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT, SCN_MOTION = 1, 2, 4, 8, 16, 32  # include/skr.h SKR_SCN_*
 FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
+ENV_MAX_EDGE = 4096         # include/skr.h SKR_ENV_MAX_EDGE
 
 
 def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False, motion=False):
@@ -525,6 +554,15 @@ def write_pfm(path, rgbf):
     rgbf = np.ascontiguousarray(rgbf, np.float32)
     h, w, _ = rgbf.shape
     _check(lib().skr_write_pfm(os.fsencode(path), w, h, rgbf.ctypes.data), "skr_write_pfm")
+
+
+def read_pfm(path):
+    """A colour PFM file as float32 [H, W, 3], top row first: the inverse of write_pfm, bit for bit (include/skr.h skr_read_pfm)."""
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().skr_read_pfm(os.fsencode(path), C.byref(w), C.byref(h), None), "skr_read_pfm")
+    a = np.zeros((h.value, w.value, 3), np.float32)
+    _check(lib().skr_read_pfm(os.fsencode(path), C.byref(w), C.byref(h), a.ctypes.data), "skr_read_pfm")
+    return a
 
 
 class Renderer:

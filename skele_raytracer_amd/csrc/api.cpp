@@ -41,12 +41,14 @@ struct DeviceScene {
 	unsigned long long *d_st_work = nullptr;  // the sphere tree's (skr_renderer_read_sphere_tree_work); null without a sphere tree
 	float4 *d_vel = nullptr; // the spheres' velocities {v.xyz, 0} in file order, + SKR_BLOB_PAD_ROWS rows of zeros (launch.h Motion); null unless motion is in force
 
+	float4 *d_env = nullptr; // the environment's texels {r, g, b, 0}, edge * edge rows, row j first (launch.h EnvMap); null unless the scene has an environment
+
 	DeviceScene() = default;
 	DeviceScene(const DeviceScene &) = delete;
 	DeviceScene &operator=(const DeviceScene &) = delete;
 	~DeviceScene()
 	{
-		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work, (void *) d_vel})
+		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work, (void *) d_vel, (void *) d_env})
 			if(p) (void) hipFree(p);
 	}
 };
@@ -243,6 +245,14 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		e = hipMalloc((void **) &s->d_vel, vel.size() * 16);
 		if(e == hipSuccess) e = hipMemcpy(s->d_vel, vel.data(), vel.size() * 16, hipMemcpyHostToDevice);
 	}
+	if(e == hipSuccess && s->layout.env_edge > 0)
+	{ // the environment travels beside the blob too: one allocation per device scene, shared by its clones
+		const size_t n = (size_t) s->layout.env_edge * (size_t) s->layout.env_edge;
+		std::vector<skr_f4> tex(n);
+		for(size_t i = 0; i < n; i++) tex[i] = skr_f4{scene->env_texels[3 * i], scene->env_texels[3 * i + 1], scene->env_texels[3 * i + 2], 0.0f};
+		e = hipMalloc((void **) &s->d_env, n * 16);
+		if(e == hipSuccess) e = hipMemcpy(s->d_env, tex.data(), n * 16, hipMemcpyHostToDevice);
+	}
 	if(e == hipSuccess)
 	{ // the camera belongs to the scene: its (e, c) rows are formed once, on the device, by the operations every ray would perform
 		const float *c = scene->info.camera;
@@ -372,12 +382,13 @@ struct LaunchScene {
 	const SkrSwitches &sw;
 	bool count_tri;
 	const float4 *vel; // the velocity rows where motion is in force (DeviceScene::d_vel)
+	const float4 *env; // the environment's texels where the scene has one (DeviceScene::d_env)
 	const float4 *sec(SkrBlobSection k) const { return blob + layout.first[k]; } // where a section starts
 };
 static LaunchScene launch_scene(const skr_renderer *r)
 {
 	const DeviceScene &s = *r->scene;
-	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri, s.d_vel};
+	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri, s.d_vel, s.d_env};
 }
 static float4 ball4(const skr_f4 &b) { return make_float4(b.x, b.y, b.z, b.w); }
 
@@ -566,6 +577,8 @@ static GenericFeatures generic_features(const LaunchScene &v, const RenderParams
 		f.spots = SpotLights{v.sec(SKR_SEC_spot), s.spot_first, s.n_spot};
 		f.softs = SoftLights{reinterpret_cast<const float *>(v.sec(SKR_SEC_radii)), s.n_radii};
 	}
+	f.env = s.env_edge > 0; // (frames and shading queries alike)
+	if(f.env) f.envmap = EnvMap{v.env, s.env_edge};
 	return f;
 }
 
@@ -726,7 +739,7 @@ static int scene_leaf_plan(const skr_scene *scene, const skr_options *opt, int w
 	load_switches(sw);
 	RenderParams p = camera_params(scene->info, opt, opt->seed, 0);
 	GenericFeatures f; // (host memory: only addresses are formed, and null-ness asked)
-	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false, reinterpret_cast<const float4 *>(rows.data())};
+	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false, reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data())};
 	const int rc = launch_params(v, opt, p, f);
 	return rc != SKR_OK ? -rc : what ? (int) skr_leaf_pow_plan(p) : (int) skr_leaf_shape(p);
 }
@@ -1314,6 +1327,11 @@ static int denoised_host(skr_renderer *r, const char *who, const skr_options *op
 		skr_set_error("%s: motion blur (sphere velocities under --shutter) cannot be combined with the denoiser (its guides are first hits of the scene at rest)", who);
 		return SKR_ERR_UNSUPPORTED;
 	}
+	if(r->scene->layout.env_edge > 0)
+	{ // nor has a scene with an environment (include/skr.h skr_scene_set_environment)
+		skr_set_error("%s: an environment map (--envmap) cannot be combined with the denoiser (its guides hold one class for every miss: the filter would smear the backdrop)", who);
+		return SKR_ERR_UNSUPPORTED;
+	}
 	SKR_HIP(hipSetDevice(r->scene->device));
 	const size_t n = (size_t) opt->width * opt->height;
 	ScratchLayout L; // the frame, (adaptive) its variance and pass counts, the camera rays and guides, the filtered frame and its bytes
@@ -1366,7 +1384,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {
-	if(!d_in || !d_out || op < 0 || op > 24) return SKR_ERR_ARG;
+	if(!d_in || !d_out || op < 0 || op > 25) return SKR_ERR_ARG;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(skr_launch_debug(op, d_in, d_out, n, (hipStream_t) stream));
 	return SKR_OK;

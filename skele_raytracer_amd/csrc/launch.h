@@ -79,6 +79,15 @@ struct Motion {
 	QueryTrees trees;
 };
 
+// The environment of a scene that has one (include/skr.h skr_scene_set_environment; wave_common.h env_lookup): what the
+// general level pipeline's finalize instances for a launch with the environment in force read — the only kernel that decides a miss — in
+// a kernel argument of its own as every feature is.  texels: edge * edge rows {r, g, b, 0}, row j first, an allocation of the
+// renderer's beside the scene blob (the blob's section table stays as it is).
+struct EnvMap {
+	const float4 *texels;
+	int32_t edge;
+};
+
 // A shading query (include/skr.h skr_shade_rays) on the general level pipeline: the rays are its roots, as rows of RenderParams::width
 // rays (the last row partial), banded like a frame's rows.  The kernels' second argument (render_generic.hip).
 struct ShadeRays {
@@ -113,6 +122,8 @@ struct GenericFeatures {
 	Lens thin_lens{};         // (lens)
 	bool motion = false;      // motion is in force: the shutter is > 0 and some sphere has a velocity other than 0 (include/skr.h skr_scene_set_sphere_velocities); frames and shading queries
 	Motion mot{};             // (motion; such a launch always carries spots and softs, n = 0 where the scene has none)
+	bool env = false;         // the environment is in force: the scene has one (include/skr.h skr_scene_set_environment); frames and shading queries
+	EnvMap envmap{};          // (env; with it the finalize kernel also takes thin_lens where lens is set: a primary miss looks up d')
 };
 
 enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
@@ -251,12 +262,12 @@ static inline unsigned skr_leaf_pow_plan(const RenderParams &p)
 
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
-// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius, a lens and motion take the general level pipeline
+// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius, a lens, motion and the environment take the general level pipeline
 bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, const GenericFeatures &f); // false: the launch takes a level pipeline and not one band of it fits the budget
 // The features a launch cannot combine, given the options as the caller set them: spot lights, lights with a radius and a lens exclude
 // --legacy-reflect, fog volumes and the sphere tree; fog excludes --legacy-reflect and --shade-triangles, and with the latter triangle
-// shadows; motion excludes what they exclude, and a lens.  (Lights with a radius need the SpotLights argument: the record always carries
-// it.)  The text for the user, or null.
+// shadows; motion excludes what they exclude, and a lens; the environment excludes --legacy-reflect, fog volumes and the sphere tree.
+// (Lights with a radius need the SpotLights argument: the record always carries it.)  The text for the user, or null.
 const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect, bool shade_triangles, bool fog);
 // what skr_kernel_variant() reports for a frame (query: a shading query) on the general level pipeline; static storage
 const char *skr_generic_variant(bool query, const GenericFeatures &f);

@@ -5,7 +5,7 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --scn-fog, --scn-spot (spot_light lines parsed and shaded: include/skr.h SKR_SCN_SPOT), --light-radius R (every point and spot light a sphere of radius R: include/skr.h skr_scene_set_light_radii), --aperture A [--focus F] (a thin lens: depth of field, include/skr.h skr_scene_set_lens; --focus alone has no effect), --scn-motion [--shutter S] (velocity lines parsed, the spheres move while the shutter is open: motion blur, include/skr.h skr_scene_set_sphere_velocities; --shutter without velocities has no effect), --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
+// --scn-fog, --scn-spot (spot_light lines parsed and shaded: include/skr.h SKR_SCN_SPOT), --light-radius R (every point and spot light a sphere of radius R: include/skr.h skr_scene_set_light_radii), --aperture A [--focus F] (a thin lens: depth of field, include/skr.h skr_scene_set_lens; --focus alone has no effect), --scn-motion [--shutter S] (velocity lines parsed, the spheres move while the shutter is open: motion blur, include/skr.h skr_scene_set_sphere_velocities; --shutter without velocities has no effect), --envmap FILE.pfm (a square colour PFM as the scene's environment: rays that miss return it, an image-based background and GI light, include/skr.h skr_scene_set_environment), --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
 // --adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L].
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cmath>
@@ -34,6 +34,7 @@ int main(int argc, char *argv[])
 	bool scn_motion = false;     // --scn-motion (new: DESIGN.md 8.16; include/skr.h SKR_SCN_MOTION)
 	bool shutter_given = false;  // --shutter S
 	float shutter = 1.0f;
+	const char *envmap = nullptr; // --envmap FILE.pfm (new: DESIGN.md 8.17; include/skr.h skr_scene_set_environment)
 	bool scn_fog = false, scn_fov = false, fov_given = false; // --scn-fog, --scn-fov (new: DESIGN.md "Spherical fog", "Camera half-angle")
 	bool triangle_shadows = false; // --triangle-shadows (new: include/skr.h SKR_SCN_TRIANGLE_SHADOWS)
 	bool sphere_tree = false;      // --sphere-tree (new: include/skr.h SKR_SCN_SPHERE_TREE)
@@ -144,6 +145,7 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--light-radius") && has_next) { light_radius = strtof(argv[i + 1], nullptr); radius_given = true; } // new: every point and spot light a sphere of radius R
 		if(!strcmp(argv[i], "--scn-motion")) scn_motion = true;             // new: velocity lines parsed, the spheres move while the shutter is open (include/skr.h SKR_SCN_MOTION)
 		if(!strcmp(argv[i], "--shutter") && has_next) { shutter = strtof(argv[i + 1], nullptr); shutter_given = true; } // new: the shutter S (default 1); no effect without velocities
+		if(!strcmp(argv[i], "--envmap") && has_next) envmap = argv[i + 1];     // new: the scene's environment, a square colour PFM
 		if(!strcmp(argv[i], "--aperture") && has_next) { aperture = strtof(argv[i + 1], nullptr); aperture_given = true; } // new: a thin lens of aperture radius A
 		if(!strcmp(argv[i], "--focus") && has_next) focus = strtof(argv[i + 1], nullptr);                                 // ... in focus at t = F of the primary rays
 		if(!strcmp(argv[i], "--scn-fog")) scn_fog = true;                   // new: spherical_fog lines parsed and shaded (include/skr.h SKR_SCN_FOG)
@@ -203,6 +205,26 @@ int main(int argc, char *argv[])
 	{
 		std::cerr << "raytracer: --shutter takes a finite number >= 0" << std::endl;
 		return SKR_ERR_ARG;
+	}
+	if(envmap)
+	{
+		uint32_t ew = 0, eh = 0;
+		if(skr_read_pfm(envmap, &ew, &eh, nullptr) != SKR_OK)
+		{
+			std::cerr << "raytracer: --envmap " << envmap << ": " << skr_last_error() << std::endl;
+			return SKR_ERR_IO;
+		}
+		if(ew != eh || ew > (uint32_t) SKR_ENV_MAX_EDGE)
+		{
+			std::cerr << "raytracer: --envmap " << envmap << ": the environment must be square with an edge of at most " << SKR_ENV_MAX_EDGE << ", the file is " << ew << " x " << eh << std::endl;
+			return SKR_ERR_ARG;
+		}
+		std::vector<float> tex((size_t) ew * eh * 3);
+		if(skr_read_pfm(envmap, &ew, &eh, tex.data()) != SKR_OK || skr_scene_set_environment(scene, tex.data(), (int32_t) ew) != SKR_OK)
+		{
+			std::cerr << "raytracer: --envmap " << envmap << ": " << skr_last_error() << std::endl;
+			return SKR_ERR_ARG;
+		}
 	}
 	if(strict_scn)
 	{ // the .scn's own film_resolution (scene.cpp:105-109) and max_depth (:192-198) hold unless the command line says otherwise

@@ -47,6 +47,11 @@
 // Such an instance consults no table built from the centres at rest — its view of the scene has no shadow masks, and this pipeline reads
 // neither GI masks nor the camera's (e, c) rows — and, where its rays start on displaced surfaces (below level 1), picks the tree of
 // each wave as for query rays.
+//
+// The environment (include/skr.h skr_scene_set_environment).  Only the finalize kernel decides a miss, and its tables
+// carry nothing for one: with an EnvMap in the pack it forms the missed ray's direction again, by the function that formed it for the
+// trace kernel — child_of on its own node below level 0, primary_ray (then lens_ray: a Lens rides behind the EnvMap) or the caller's d at
+// level 0 — and returns wave_common.h env_lookup of it.  Trace and activate instances, records and nodes are as they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -567,7 +572,9 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p, const Q... qs)
 {
-	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, ENV = pack_has<EnvMap, Q...>, LENS = pack_has<Lens, Q...>;
+	static_assert(!ENV || !STREE, "the environment excludes the sphere tree (skr_features_conflict)");
+	static_assert(!LENS || (ENV && !RAYS), "the finalize kernel takes a Lens only behind an EnvMap, and only for frames (with_pack)");
 	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -577,7 +584,31 @@ __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p
 	const uint32_t node = (uint32_t) blockIdx.x * 256u + threadIdx.x;
 	if(node >= n_nodes) return;
 	const uint32_t A = p.g_arity;
-	// the value of child c: its record's (a hit), (0,0,0) (a triangle took it: raytrace.h:221-224) or the background (:189-192)
+	const GNode *own = nullptr; // ENV: the lane's node below level 0, whose child rays value_of may have to form again
+	// the direction of child c as the trace kernel formed it (ENV: what a miss looks up)
+	auto direction_of = [&](uint32_t c) -> f3 {
+		if(p.g_level != 0) return child_of(sv, p, *own, c).d;
+		if constexpr(RAYS)
+		{
+			const float4 rb = q.rays[2 * (size_t) (q.ray0 + node) + 1];
+			return mk3(rb.x, rb.y, rb.z);
+		}
+		else
+		{
+			const uint32_t bw = (uint32_t) p.width, row = p.band_row0 + node / bw, x = node - (node / bw) * bw;
+			const uint32_t y = image_row(p, row);
+			f3 d;
+			primary_ray(p, (int) x, y, y * bw + x, p.aa_index, d);
+			if constexpr(LENS)
+			{
+				f3 o2;
+				lens_ray(p, pick<Lens>(qs...), y * bw + x, p.aa_index, d, o2, d);
+			}
+			return d;
+		}
+	};
+	// the value of child c: its record's (a hit), (0,0,0) (a triangle took it: raytrace.h:221-224) or the background (:189-192; ENV:
+	// the environment in the ray's direction)
 	auto value_of = [&](uint32_t c) -> f3 {
 		const uint64_t ri = (uint64_t) node * A + c;
 		const uint4 *h = p.ixh + GHDR_ROWS * (size_t) (ri >> 6);
@@ -589,7 +620,12 @@ __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p
 			const float *r = p.res_in + (size_t) (h0.x + (uint32_t) __popcll(mh & ((1ull << bit) - 1ull))) * 3;
 			return mk3(r[0], r[1], r[2]);
 		}
-		return ((mb >> bit) & 1ull) ? mk3(0, 0, 0) : p.background;
+		if constexpr(ENV)
+		{
+			if((mb >> bit) & 1ull) return mk3(0, 0, 0);
+			return env_lookup(pick<EnvMap>(qs...), direction_of(c), p.background);
+		}
+		else return ((mb >> bit) & 1ull) ? mk3(0, 0, 0) : p.background;
 	};
 	if(p.g_level == 0)
 	{
@@ -605,6 +641,7 @@ __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p
 	}
 	const GNode n = load_node(p.g_nodes_src + (size_t) node * GNODE_ROWS);
 	GNode m = n;
+	if constexpr(ENV) own = &m;
 	// a child that does not exist (no legacy terms for this surface; fr >= 1) is never asked for by node_value()
 	store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of));
 }
@@ -655,10 +692,11 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
 
 // Calls `launch` with the pack of an instance: [ShadeRays] [TriShadows] [SphereTree | SpotLights [SoftLights]] [Lens | Motion], the one
 // place the order is written down.  K: whose pack — the activate kernel's is the whole of it; the trace kernel takes only [ShadeRays]
-// [SphereTree] [Lens | Motion], the finalize kernel [ShadeRays] [SphereTree].  The combinations skr_features_conflict refuses (the sphere
+// [SphereTree] [Lens | Motion], the finalize kernel [ShadeRays] [SphereTree] [EnvMap [Lens]].  The combinations skr_features_conflict refuses (the sphere
 // tree with spot lights, a radius, a lens or motion; a lens with motion) are no instance, nor is a lens with a shading query (its rays are
 // the caller's).  A launch with motion always carries SpotLights SoftLights (their tables have n = 0 where the scene has none), so motion
-// adds two trace and four activate instances.
+// adds two trace and four activate instances.  The environment excludes the sphere tree too and adds three finalize instances:
+// <EnvMap>, <ShadeRays, EnvMap>, <EnvMap, Lens>.
 enum PackOf { PACK_FINALIZE, PACK_TRACE, PACK_ACTIVATE };
 template <PackOf K, typename F>
 static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
@@ -678,7 +716,15 @@ static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 			if(f.spot) return lens(head..., f.spots);
 		}
 		else if constexpr(K == PACK_TRACE)
+		{
 			if(f.motion) return launch(head..., f.mot);
+		}
+		else if(f.env)
+		{ // the finalize kernel: the lookup, and under a lens the draw that made the primary ray (a frame's only)
+			if constexpr(!pack_has<ShadeRays, decltype(head)...>)
+				if(f.lens) return launch(head..., f.envmap, f.thin_lens);
+			return launch(head..., f.envmap);
+		}
 		lens(head...);
 	};
 	auto shadows = [&](auto... head) {

@@ -34,7 +34,7 @@ static size_t direct_lds_bytes(const RenderParams &p)
 }
 
 // Which kernels render this launch, and what they need.  In this order:
-//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, a lens, motion, and every tree
+//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, a lens, motion, the environment, and every tree
 //     (shade() recurses: max_depth > 1; api.cpp folds --depth to 1 where it cannot, raytrace.h:208-218) the node pipeline does not;
 //   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget and its kernels
 //     fit the device's LDS;
@@ -46,7 +46,7 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, co
 {
 	lp = LaunchPlan();
 	lp.features = f;
-	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft || f.lens || f.motion;
+	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft || f.lens || f.motion || f.env;
 	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
 		lp.path = SKR_PATH_NODES;
@@ -86,18 +86,23 @@ const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect,
 										"a lens (--aperture) cannot be combined with the sphere tree (--sphere-tree)"};
 	static const char *const motion[3] = {"motion blur (sphere velocities under --shutter) cannot be combined with --legacy-reflect", "motion blur (sphere velocities under --shutter) cannot be combined with fog volumes (--scn-fog)",
 										  "motion blur (sphere velocities under --shutter) cannot be combined with the sphere tree (--sphere-tree)"};
+	static const char *const env[3] = {"an environment map (--envmap) cannot be combined with --legacy-reflect", "an environment map (--envmap) cannot be combined with fog volumes (--scn-fog)",
+									   "an environment map (--envmap) cannot be combined with the sphere tree (--sphere-tree)"};
 	if(f.motion && f.lens) return "motion blur (sphere velocities under --shutter) cannot be combined with a lens (--aperture)";
-	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : f.lens ? lens[with] : f.motion ? motion[with] : nullptr;
+	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : f.lens ? lens[with] : f.motion ? motion[with] : f.env ? env[with] : nullptr;
 }
 
 const char *skr_generic_variant(bool query, const GenericFeatures &f)
-{ // (fog has no name of its own; a lens is a frame's: no shading query and no sphere-tree instance has one; motion excludes both)
-#define SKR_VARIANT_NAMES(base) {{base, base "_tshadow"}, {base "_lens", base "_lens_tshadow"}, {base "_motion", base "_motion_tshadow"}}
-	static const char *const name[2][4][3][2] = {
+{ // (fog has no name of its own; a lens is a frame's: no shading query and no sphere-tree instance has one; motion excludes both; the
+  // environment's part comes last)
+#define SKR_VARIANT_ENV(name) {name, name "_env"}
+#define SKR_VARIANT_NAMES(base) {{SKR_VARIANT_ENV(base), SKR_VARIANT_ENV(base "_tshadow")}, {SKR_VARIANT_ENV(base "_lens"), SKR_VARIANT_ENV(base "_lens_tshadow")}, {SKR_VARIANT_ENV(base "_motion"), SKR_VARIANT_ENV(base "_motion_tshadow")}}
+	static const char *const name[2][4][3][2][2] = {
 		{SKR_VARIANT_NAMES("level_pipeline_g1"), SKR_VARIANT_NAMES("level_pipeline_g1_stree"), SKR_VARIANT_NAMES("level_pipeline_g1_spot"), SKR_VARIANT_NAMES("level_pipeline_g1_soft")},
 		{SKR_VARIANT_NAMES("shade_rays_g1"), SKR_VARIANT_NAMES("shade_rays_g1_stree"), SKR_VARIANT_NAMES("shade_rays_g1_spot"), SKR_VARIANT_NAMES("shade_rays_g1_soft")}};
 #undef SKR_VARIANT_NAMES
-	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][f.motion ? 2 : !query && f.lens][f.tri_shadows];
+#undef SKR_VARIANT_ENV
+	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][f.motion ? 2 : !query && f.lens][f.tri_shadows][f.env];
 }
 
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)
@@ -465,8 +470,28 @@ __global__ void skr_debug_motion_kernel(const uint32_t *in, uint32_t *out, uint3
 	w[0] = U(tau); w[1] = U(c.x); w[2] = U(c.y); w[3] = U(c.z);
 }
 
+// Op 25: the taps of the environment lookup of one record: (d(3), E) -> (flag, i0, i1, j0, j1, fx, fy), through env_taps, the index
+// code env_lookup runs (a kernel of its own: the ops above keep their code)
+__global__ void skr_debug_env_kernel(const uint32_t *in, uint32_t *out, uint32_t n)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	const uint32_t *r = in + 4 * i;
+	EnvTaps t{0, 0, 0, 0, 0.0f, 0.0f};
+	const bool ok = env_taps(mk3(__uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2])), (int32_t) r[3], t);
+	uint32_t *w = out + 7 * i;
+	w[0] = ok ? 0u : 1u;
+	w[1] = ok ? (uint32_t) t.i0 : 0u; w[2] = ok ? (uint32_t) t.i1 : 0u; w[3] = ok ? (uint32_t) t.j0 : 0u; w[4] = ok ? (uint32_t) t.j1 : 0u;
+	w[5] = ok ? __float_as_uint(t.fx) : 0u; w[6] = ok ? __float_as_uint(t.fy) : 0u;
+}
+
 hipError_t skr_launch_debug(int op, const void *d_in, void *d_out, uint32_t n, hipStream_t stream)
 {
+	if(op == 25)
+	{
+		hipLaunchKernelGGL(skr_debug_env_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n);
+		return hipGetLastError();
+	}
 	if(op == 24)
 	{
 		hipLaunchKernelGGL(skr_debug_motion_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n);

@@ -603,6 +603,44 @@ int skr_scene_get_shutter(const skr_scene *scene, float *shutter)
 	return SKR_OK;
 }
 
+int skr_scene_set_environment(skr_scene *scene, const float *texels, int32_t edge)
+{
+	if(!scene)
+	{
+		skr_set_error("skr_scene_set_environment: null scene");
+		return SKR_ERR_ARG;
+	}
+	if(edge == 0 || !texels)
+	{ // cleared: misses return the background again
+		scene->env_texels.clear();
+		scene->env_edge = 0;
+		return SKR_OK;
+	}
+	if(edge < 1 || edge > SKR_ENV_MAX_EDGE)
+	{
+		skr_set_error("skr_scene_set_environment: the edge must be in [1, %d] (0 clears the environment): %d", SKR_ENV_MAX_EDGE, edge);
+		return SKR_ERR_ARG;
+	}
+	const size_t n = (size_t) edge * (size_t) edge * 3;
+	for(size_t i = 0; i < n; i++)
+		if(!std::isfinite(texels[i]))
+		{
+			skr_set_error("skr_scene_set_environment: texel (row %zu, column %zu) has a channel that is not finite", i / 3 / (size_t) edge, i / 3 % (size_t) edge);
+			return SKR_ERR_ARG;
+		}
+	scene->env_texels.assign(texels, texels + n);
+	scene->env_edge = edge;
+	return SKR_OK;
+}
+
+int skr_scene_get_environment(const skr_scene *scene, float *texels, int32_t *edge)
+{
+	if(!scene) return SKR_ERR_ARG;
+	if(edge) *edge = scene->env_edge;
+	if(texels && scene->env_edge > 0) memcpy(texels, scene->env_texels.data(), scene->env_texels.size() * sizeof(float));
+	return SKR_OK;
+}
+
 int skr_scene_get_spot_cones(const skr_scene *scene, float *cones)
 {
 	if(!scene) return SKR_ERR_ARG;
@@ -875,6 +913,80 @@ int skr_write_pfm(const char *path, uint32_t width, uint32_t height, const float
 	for(uint32_t y = height; y-- > 0;) ofs.write(reinterpret_cast<const char *>(rgbf + (size_t) y * width * 3), (std::streamsize) width * 12);
 	ofs.close();
 	return ofs ? SKR_OK : SKR_ERR_IO;
+}
+
+// The inverse of skr_write_pfm (include/skr.h): "PF", W H, the scale line (its sign is the byte order), one whitespace byte, then
+// H rows of W*3 binary32 values, bottom row first; rgbf receives them top row first.
+int skr_read_pfm(const char *path, uint32_t *width, uint32_t *height, float *rgbf)
+{
+	if(!path || !width || !height)
+	{
+		skr_set_error("skr_read_pfm: null argument");
+		return SKR_ERR_ARG;
+	}
+	*width = *height = 0;
+	FILE *fp = fopen(path, "rb");
+	if(!fp)
+	{
+		skr_set_error("cannot open '%s' for reading", path);
+		return SKR_ERR_IO;
+	}
+	auto fail = [&](const char *why) {
+		fclose(fp);
+		skr_set_error("'%s' is not a colour PFM file this reader takes: %s", path, why);
+		return SKR_ERR_IO;
+	};
+	auto token = [&](char *buf, size_t cap) { // the next whitespace-delimited token of the header; the ONE whitespace byte behind it is consumed
+		int c = fgetc(fp);
+		while(c == ' ' || c == '\t' || c == '\n' || c == '\r') c = fgetc(fp);
+		size_t n = 0;
+		while(c != EOF && c != ' ' && c != '\t' && c != '\n' && c != '\r')
+		{
+			if(n + 1 < cap) buf[n++] = (char) c;
+			c = fgetc(fp);
+		}
+		buf[n] = 0;
+		return n > 0 && c != EOF;
+	};
+	char tok[64], *end = nullptr;
+	if(!token(tok, sizeof tok) || strcmp(tok, "PF") != 0) return fail("the magic is not PF");
+	if(!token(tok, sizeof tok)) return fail("no width");
+	const long long w = strtoll(tok, &end, 10);
+	if(*end || w < 1 || w > 0x7FFFFFFFll) return fail("bad width");
+	if(!token(tok, sizeof tok)) return fail("no height");
+	const long long h = strtoll(tok, &end, 10);
+	if(*end || h < 1 || h > 0x7FFFFFFFll) return fail("bad height");
+	if(!token(tok, sizeof tok)) return fail("no scale line");
+	const double scale = strtod(tok, &end);
+	if(*end || !std::isfinite(scale) || scale == 0.0) return fail("bad scale");
+	const bool big = scale > 0.0;
+	*width = (uint32_t) w;
+	*height = (uint32_t) h;
+	const size_t row = (size_t) w * 3;
+	if(!rgbf)
+	{ // the sizes only — of a file that holds its pixels
+		const long at = ftell(fp);
+		if(at < 0 || fseek(fp, 0, SEEK_END) != 0) return fail("cannot seek");
+		const long len = ftell(fp);
+		if(len < 0 || (unsigned long long) (len - at) < (unsigned long long) row * 4ull * (unsigned long long) h) return fail("the pixel data ends early");
+		fclose(fp);
+		return SKR_OK;
+	}
+	for(long long y = h; y-- > 0;)
+	{
+		float *dst = rgbf + (size_t) y * row;
+		if(fread(dst, 4, row, fp) != row) return fail("the pixel data ends early");
+		if(big)
+			for(size_t i = 0; i < row; i++)
+			{
+				uint32_t u;
+				memcpy(&u, dst + i, 4);
+				u = (u >> 24) | ((u >> 8) & 0xFF00u) | ((u << 8) & 0xFF0000u) | (u << 24);
+				memcpy(dst + i, &u, 4);
+			}
+	}
+	fclose(fp);
+	return SKR_OK;
 }
 
 // PNG, 8-bit RGB, the bytes of the PPM: filter 0 on every row, zlib stream of stored (uncompressed) deflate blocks — no

@@ -61,6 +61,8 @@ struct skr_scene {
 			if(v != 0.0f) return true;
 		return false;
 	}
+	std::vector<float> env_texels;       // [E][E][3] the environment's texels, row j first; empty = none — skr_scene_set_environment only (include/skr.h)
+	int32_t env_edge = 0;                // E; 0 = no environment (then misses return info.background, as ever)
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
 	bool sphere_tree = false;            // SKR_SCN_SPHERE_TREE / skr_scene_set_sphere_tree: likewise

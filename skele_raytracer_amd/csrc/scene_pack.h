@@ -54,6 +54,8 @@ struct SceneLayout {
 	skr_f4 st_ball{};
 	bool motion = false;  // motion is in force (skr_scene::motion(), include/skr.h skr_scene_set_sphere_velocities): frames and shading queries take the instances with the shutter draw.
 	float shutter = 1.0f; // The velocities are no section of the blob: the renderer uploads them beside it (api.cpp DeviceScene::d_vel)
+	int env_edge = 0;     // the environment's edge E, 0 = none (include/skr.h skr_scene_set_environment): in force, frames and shading queries take the finalize instances
+	                      // with the lookup.  The texels are no section of the blob either (api.cpp DeviceScene::d_env)
 };
 
 // The blob of `s` and its layout; nothing is uploaded.

@@ -137,6 +137,55 @@ SKR_DEV float shutter_time(const RenderParams &p, uint32_t pixel, uint32_t aa, f
 	return S * u31_to_unit(rnd[0]);
 }
 
+// The environment lookup (include/skr.h skr_scene_set_environment): the one copy of the rule.  env_taps is its steps 1-5
+// — the octahedral fold of d and the four bilinear taps — in binary32 with one correctly rounded operation per step (the unit is
+// compiled without contraction); false: the background arm (!(s > 0) or s not finite).  Behind a finite s > 0 every |component| <= s,
+// so px, pz lie in [-1, 1], u, v in [0, 1] and x, y in [-0.5, E - 0.5]: the int conversions are exact and small, and the indices are
+// clamped to [0, E - 1] before any address is formed.
+struct EnvTaps {
+	int32_t i0, i1, j0, j1;
+	float fx, fy;
+};
+SKR_DEV bool env_taps(f3 d, int32_t E, EnvTaps &t)
+{
+	const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+	const float s = (ax + ay) + az;
+	if(!(s > 0.0f) || !(s < __builtin_inff())) return false;
+	const float px = d.x / s, pz = d.z / s;
+	float qx = px, qz = pz;
+	if(d.y < 0.0f)
+	{
+		qx = (1.0f - __builtin_fabsf(pz)) * (px < 0.0f ? -1.0f : 1.0f);
+		qz = (1.0f - __builtin_fabsf(px)) * (pz < 0.0f ? -1.0f : 1.0f);
+	}
+	const float u = qx * 0.5f + 0.5f, v = qz * 0.5f + 0.5f;
+	const float fe = (float) E;
+	const float x = u * fe - 0.5f, y = v * fe - 0.5f;
+	const float x0 = __builtin_floorf(x), y0 = __builtin_floorf(y);
+	t.fx = x - x0;
+	t.fy = y - y0;
+	auto clamp = [E](int32_t i) { return i < 0 ? 0 : i > E - 1 ? E - 1 : i; };
+	const int32_t ix = (int32_t) x0, iy = (int32_t) y0;
+	t.i0 = clamp(ix);
+	t.i1 = clamp(ix + 1);
+	t.j0 = clamp(iy);
+	t.j1 = clamp(iy + 1);
+	return true;
+}
+// env(d): four clamped float4 gathers {r, g, b, 0}, then step 6 per channel.  A lane's taps are its own (divergent directions): vector
+// loads, two neighbouring texels of a row side by side.
+SKR_DEV f3 env_lookup(const EnvMap &e, f3 d, f3 background)
+{
+	EnvTaps t;
+	if(!env_taps(d, e.edge, t)) return background;
+	const float4 *r0 = e.texels + (size_t) t.j0 * (size_t) e.edge, *r1 = e.texels + (size_t) t.j1 * (size_t) e.edge;
+	const float4 a = r0[t.i0], b = r0[t.i1], c = r1[t.i0], g = r1[t.i1];
+	const f3 a3 = mk3(a.x, a.y, a.z), c3 = mk3(c.x, c.y, c.z);
+	const f3 top = a3 + (mk3(b.x, b.y, b.z) - a3) * t.fx;
+	const f3 bot = c3 + (mk3(g.x, g.y, g.z) - c3) * t.fx;
+	return top + (bot - top) * t.fy;
+}
+
 SKR_DEV void emit_sample(const RenderParams &p, uint32_t out_pix, f3 c)
 { // one sample of one pixel is final: store it (1 spp) or add it to the running sum (AA, sample order = launch order)
 	if(p.grid_size > 0)

@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--aperture A [--focus F]] [--scn-motion] [--shutter S] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--aperture A [--focus F]] [--scn-motion] [--shutter S] [--envmap FILE.pfm] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
            [--adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
@@ -93,6 +93,8 @@ def _parse(argv):
             opt["scn_motion"] = True
         elif a == "--shutter":
             opt["shutter"] = value(i, _atof, "shutter takes a float (how long the shutter is open)")
+        elif a == "--envmap":
+            opt["envmap"] = value(i, str, "envmap takes the path of a square colour PFM file (the scene's environment)")
         elif a == "--aperture":
             opt["aperture"] = value(i, _atof, "aperture takes a float (the radius of the lens)")
         elif a == "--focus":
@@ -158,9 +160,18 @@ def main(argv=None):
     if aperture is not None and not (math.isfinite(aperture) and aperture >= 0.0 and math.isfinite(focus) and focus > 0.0):
         print("raytracer: --aperture takes a finite radius >= 0 and --focus a finite distance > 0", file=sys.stderr)  # as bin/raytracer
         return 2
+    import skele_raytracer_amd as skr
+    env = None
+    if o.get("envmap") is not None:  # --envmap FILE.pfm: read and checked on the host before anything touches the GPU, as bin/raytracer does
+        try:
+            env = skr.read_pfm(o["envmap"])
+            if env.shape[0] != env.shape[1] or env.shape[0] > skr.binding.ENV_MAX_EDGE:
+                raise skr.SkrError("the environment must be square with an edge of at most %d, the file is %d x %d" % (skr.binding.ENV_MAX_EDGE, env.shape[1], env.shape[0]))
+        except skr.SkrError as e:
+            print("raytracer: --envmap %s: %s" % (o["envmap"], e), file=sys.stderr)
+            return 2
     import torch
     import torch.distributed as dist
-    import skele_raytracer_amd as skr
     from .distributed import FrameSharder
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -209,6 +220,15 @@ def main(argv=None):
         scene.set_lens(aperture, focus)
     if shutter is not None:  # as bin/raytracer --shutter S (include/skr.h skr_scene_set_shutter); without velocities it has no effect
         scene.set_shutter(shutter)
+    if env is not None:  # as bin/raytracer --envmap FILE.pfm: the scene's environment (include/skr.h skr_scene_set_environment)
+        try:
+            scene.set_environment(env)
+        except skr.SkrError as e:  # (a texel that is not finite)
+            if rank == 0:
+                print("raytracer: --envmap %s: %s" % (o["envmap"], e), file=sys.stderr)
+            if world > 1:
+                dist.destroy_process_group()
+            return 2
     r = skr.Renderer(scene, local_rank)
     kw = dict(fov=o["fov"], depth=o["depth"], shadow=o["shadow"], seed=o["seed"], shade_triangles=bool(o.get("shade_triangles")), progressive=o.get("progressive", 1), legacy_reflect=bool(o.get("legacy_reflect")))
     if o["gillum"] is not None:

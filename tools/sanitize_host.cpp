@@ -187,5 +187,41 @@ int main(int argc, char **argv)
 	}
 	std::vector<uint8_t> px(7 * 5 * 3, 200);
 	skr_write_ppm("build/asan_out.ppm", 7, 5, px.data());
+	{ // the PFM reader on what the writer wrote, on short, malformed and absurd files; the environment's setter and getter with good and bad arguments
+		std::vector<float> f(7 * 5 * 3), back(7 * 5 * 3, -1.0f);
+		for(size_t i = 0; i < f.size(); i++) f[i] = 0.25f * (float) i;
+		skr_write_pfm("build/asan_out.pfm", 7, 5, f.data());
+		uint32_t w = 0, h = 0;
+		const int sizes = skr_read_pfm("build/asan_out.pfm", &w, &h, nullptr), whole = skr_read_pfm("build/asan_out.pfm", &w, &h, back.data());
+		printf("pfm: sizes %d whole %d %u x %u same %d\n", sizes, whole, w, h, (int) (back == f));
+		const char *const bad[] = {"PF\n7 5\n-1.0\n", "PF\n7 5\n", "PF\n7", "PF\n4294967295 4294967295\n-1.0\nxxxx", "PF\n-3 5\n-1.0\n", "Pf\n7 5\n-1.0\n", "PF\n7 5\n0.0\n", "PF\n7 5\nnan\n", "", "PF",
+								   "PF\n99999999999999999999999 1\n1\n", "PF\n1 1\n1\n\1\2\3\4\5\6\7\1\2\3\4"};
+		for(const char *text : bad)
+		{
+			FILE *fp = fopen("build/asan_bad.pfm", "wb");
+			if(!fp) break;
+			fputs(text, fp);
+			fclose(fp);
+			const int a = skr_read_pfm("build/asan_bad.pfm", &w, &h, nullptr);
+			const int b = (a == 0 && (size_t) w * h * 3 <= back.size()) ? skr_read_pfm("build/asan_bad.pfm", &w, &h, back.data()) : -1;
+			printf("pfm: bad file rc %d %d\n", a, b);
+		}
+		skr_scene *sc = nullptr;
+		if(skr_scene_create_from_scn("build/empty.scn", 0, &sc) == 0)
+		{
+			std::vector<float> tex(5 * 5 * 3, 0.5f), got(5 * 5 * 3 + 3, -1.0f);
+			int32_t e = -1;
+			const int ok = skr_scene_set_environment(sc, tex.data(), 5), neg = skr_scene_set_environment(sc, tex.data(), -1), big = skr_scene_set_environment(sc, tex.data(), SKR_ENV_MAX_EDGE + 1);
+			tex[74] = INFINITY;
+			const int not_finite = skr_scene_set_environment(sc, tex.data(), 5);
+			skr_scene_get_environment(sc, got.data(), &e);
+			printf("env: set %d %d %d %d, edge %d, last %g guard %g\n", ok, neg, big, not_finite, e, got[74], got[75]);
+			blob_table(sc, "env", "set");
+			const int cleared = skr_scene_set_environment(sc, nullptr, 5);
+			skr_scene_get_environment(sc, got.data(), &e);
+			printf("env: cleared %d edge %d\n", cleared, e);
+			skr_scene_destroy(sc);
+		}
+	}
 	return 0;
 }
