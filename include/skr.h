@@ -37,6 +37,7 @@ extern "C" {
 #define SKR_HAS_LENS 1 /* skr_scene_set/get_lens, skr_debug_eval op 22: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_MOTION 1 /* SKR_SCN_MOTION, skr_scene_set/get_sphere_velocities, skr_scene_set/get_shutter, skr_debug_eval op 24: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ENVIRONMENT 1 /* skr_scene_set/get_environment, skr_read_pfm, skr_debug_eval op 25: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_TEXTURES 1 /* SKR_SCN_TEXTURE, skr_scene_add/get_texture, skr_scene_texture_count, skr_scene_set/get_sphere_textures, skr_scene_clear_textures, skr_debug_eval op 26: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -371,6 +372,50 @@ int skr_scene_get_shutter(const skr_scene *scene, float *shutter);
 #define SKR_ENV_MAX_EDGE 4096
 int skr_scene_set_environment(skr_scene *scene, const float *texels, int32_t edge);
 int skr_scene_get_environment(const skr_scene *scene, float *texels, int32_t *edge);
+/* Sphere textures: an image albedo on an octahedral map of the shading normal (new, opt-in; no counterpart in the reference, whose
+ * `material` line gives every sphere one flat colour).  A scene holds 0 <= n_tex <= SKR_TEX_MAX textures; texture k is a square image of
+ * E_k x E_k RGB binary32 texels, 1 <= E_k <= SKR_TEX_MAX_EDGE, every texel finite, row j first as for the environment.  Every sphere
+ * has a texture index x_i in [-1, n_tex), -1 (the default) = none.  Textures are in force for a launch iff some x_i >= 0; otherwise
+ * planning, skr_kernel_variant(), frames, floats and all work counters are exactly what they are without this section.  The rule
+ * (normative):
+ *   - tex_k(N) is steps 1-6 of the environment rule above applied to d = N with E = E_k and T = texture k: the axes are the world's,
+ *     +y at the centre of the square, the map turns with nothing.  Where step 1 fails (!(s > 0) or s not finite: a zero or NaN
+ *     normal) tex_k(N) = (1, 1, 1).  The kernels compute it by the environment's own index code (wave_common.h env_taps).
+ *   - Where it is read.  At a node whose surface is sphere i with x_i = k >= 0, c = tex_k(N), N the node's shading normal as the
+ *     kernel holds it: normalize3(P - centre), under motion the displaced centre.  The material rows of that node become
+ *     kd' = (kd.x c.x, kd.y c.y, kd.z c.z) and ambp' = (ambp.x c.x, ambp.y c.y, ambp.z c.z, ambp.w), ambp = {La * ka, power}: one
+ *     binary32 multiply each.  ks, the exponent and the ior are unchanged.  Every use of that node's kd and ambp takes the primed
+ *     values: the diffuse and ambient terms of the light loop, and the final `* kd` of raytrace.h:213.  Triangles have no texture.
+ *     Rays, hits, child rays, draws, shadow rays and all work counters are those of the same scene without textures.
+ *   - Where it runs: a launch with textures in force always takes the general level pipeline; skr_kernel_variant() carries one "_tex"
+ *     part at its very end, behind "_env" where that is present ("level_pipeline_g1_tex", "level_pipeline_g1_soft_lens_tshadow_env_tex",
+ *     "shade_rays_g1_env_tex", ...).  It combines with use_shadows, grid_size,
+ *     num_path_traces at any depth, SKR_SCN_STRICT, shade_triangles with or without triangle shadows, spot lights, light radii,
+ *     motion, a lens, the environment, tiles and strides, bands, clones, skr_multi / skr_comm, progressive and adaptive frames,
+ *     shading queries.  skr_trace_rays is unaffected.
+ *   - Refused with SKR_ERR_UNSUPPORTED where textures are in force (and only there): skr_options.legacy_reflect, fog volumes, the
+ *     sphere-tree switch, and skr_render_denoised_host / skr_render_adaptive_denoised_host (their guides hold one class per sphere:
+ *     the filter would smear the pattern).
+ * SKR_SCN_TEXTURE (`raytracer --scn-texture`; combines with the other scene flags): a line `texture NAME` sets the texture in force
+ * for the `sphere` lines that follow, stateful exactly as `velocity` and `material` are; `texture none` clears it; the initial state
+ * is none.  NAME is a colour PFM read by skr_read_pfm, a relative name resolved against the scene file's directory; the same NAME
+ * twice is one texture.  A line without a name, whose file cannot be read, is not square, has an edge above the limit or a texel that
+ * is not finite, or that would be a 17th distinct texture, is warned about, skipped and counted in n_unknown, the texture in force
+ * unchanged.  Without the flag the line stays "WARNING. Do not know command" and everything is byte for byte as it was.
+ * add: texels float[edge][edge][3]; returns the new texture's index, or -SKR_ERR_ARG (a bad edge, a texel that is not finite, a 17th
+ * texture), the scene unchanged.  get: *edge = E_k, texels (if not NULL) receives float[E_k][E_k][3].  set_sphere_textures: n must be
+ * the sphere count and every index in [-1, n_tex), else SKR_ERR_ARG and the scene is unchanged.  get_sphere_textures: *n = the sphere
+ * count, idx (if not NULL) receives it.  clear: every index back to -1 (the textures stay).  A renderer takes textures and indices
+ * when it is created (an allocation of its own beside the scene blob); skr_renderer_clone and the multi-GPU frame steps share it. */
+#define SKR_SCN_TEXTURE 64u
+#define SKR_TEX_MAX 16
+#define SKR_TEX_MAX_EDGE 1024
+int skr_scene_add_texture(skr_scene *scene, const float *texels, int32_t edge);
+int skr_scene_get_texture(const skr_scene *scene, int32_t k, float *texels, int32_t *edge);
+int skr_scene_texture_count(const skr_scene *scene);
+int skr_scene_set_sphere_textures(skr_scene *scene, const int32_t *idx, int32_t n);
+int skr_scene_get_sphere_textures(const skr_scene *scene, int32_t *idx, int32_t *n);
+int skr_scene_clear_textures(skr_scene *scene);
 /* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
  * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
  * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device
@@ -836,7 +881,11 @@ const char *skr_kernel_variant(void);  /* name of the kernel the last render lau
  *    11 words -> (tau, c'(3)), 4 words.
  * 25 the environment lookup's taps (skr_scene_set_environment above; wave_common.h env_taps, the index code env_lookup itself runs):
  *    (d(3), E as an integer), 4 words -> (flag: 1 = the background arm, i0, i1, j0, j1 as integers, fx, fy), 7 words; the six
- *    behind a flag of 1 are 0. */
+ *    behind a flag of 1 are 0.
+ * 26 the texture colour of a normal (skr_scene_add_texture above; render_generic.hip texture_colour, the function textured_material
+ *    multiplies the material rows by): (N(3), texture index k), 4 words -> c(3), 3 words, on the op's own fixed textures: texture k
+ *    (0 <= k < 4) has the edge (1, 2, 3, 64)[k] and the texel (row j, column i) = (i + 1, j + 1, 0.5 (i + j) + 0.25); any other k is
+ *    no texture, c = (1, 1, 1). */
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream);
 
 #ifdef __cplusplus

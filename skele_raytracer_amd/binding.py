@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_sphere_velocities", "skr_scene_get_sphere_velocities", "skr_scene_set_shutter", "skr_scene_get_shutter", "skr_scene_set_environment", "skr_scene_get_environment", "skr_read_pfm", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_sphere_velocities", "skr_scene_get_sphere_velocities", "skr_scene_set_shutter", "skr_scene_get_shutter", "skr_scene_set_environment", "skr_scene_get_environment", "skr_read_pfm", "skr_scene_add_texture", "skr_scene_get_texture", "skr_scene_texture_count", "skr_scene_set_sphere_textures", "skr_scene_get_sphere_textures", "skr_scene_clear_textures", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -97,6 +97,12 @@ def lib():
     L.skr_scene_get_shutter.argtypes = [vp, C.POINTER(C.c_float)]
     L.skr_scene_set_environment.argtypes = [vp, vp, C.c_int32]
     L.skr_scene_get_environment.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.skr_scene_add_texture.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_texture.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_int32)]
+    L.skr_scene_texture_count.argtypes = [vp]
+    L.skr_scene_set_sphere_textures.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_sphere_textures.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.skr_scene_clear_textures.argtypes = [vp]
     L.skr_read_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
@@ -432,6 +438,51 @@ class Scene:
             raise ValueError("environment: a square [E, E, 3] array")
         _check(lib().skr_scene_set_environment(self.h, t.ctypes.data, t.shape[0]), "skr_scene_set_environment")
 
+    @property
+    def textures(self):
+        """The scene's textures, a list of float32 [E_k, E_k, 3] arrays with row j first (include/skr.h skr_scene_get_texture)."""
+        n = lib().skr_scene_texture_count(self.h)
+        if n < 0:
+            _check(-n, "skr_scene_texture_count")
+        out = []
+        for k in range(n):
+            e = C.c_int32(0)
+            _check(lib().skr_scene_get_texture(self.h, k, None, C.byref(e)), "skr_scene_get_texture")
+            t = np.zeros((e.value, e.value, 3), np.float32)
+            _check(lib().skr_scene_get_texture(self.h, k, t.ctypes.data, C.byref(e)), "skr_scene_get_texture")
+            out.append(t)
+        return out
+
+    def add_texture(self, texels):
+        """Add a texture (include/skr.h skr_scene_add_texture states the rule): [E, E, 3] finite floats, an octahedral map of a sphere's
+        normal with world +y at the centre.  Returns its index, what set_sphere_textures names it by."""
+        t = np.ascontiguousarray(texels, np.float32)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 3 or t.shape[0] == 0:
+            raise ValueError("texture: a square [E, E, 3] array")
+        k = lib().skr_scene_add_texture(self.h, t.ctypes.data, t.shape[0])
+        if k < 0:
+            _check(-k, "skr_scene_add_texture")
+        return k
+
+    @property
+    def sphere_textures(self):
+        """The texture index of every sphere, int32 [n_spheres], -1 = none (include/skr.h skr_scene_get_sphere_textures)."""
+        n = C.c_int32(0)
+        _check(lib().skr_scene_get_sphere_textures(self.h, None, C.byref(n)), "skr_scene_get_sphere_textures")
+        x = np.full(n.value, -1, np.int32)
+        _check(lib().skr_scene_get_sphere_textures(self.h, x.ctypes.data, C.byref(n)), "skr_scene_get_sphere_textures")
+        return x
+
+    def set_sphere_textures(self, indices):
+        """Name the texture of every sphere: int [n_spheres], each -1 (none) or the index of a texture the scene holds.  A renderer takes
+        the textures and indices the scene has when it is made."""
+        x = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        _check(lib().skr_scene_set_sphere_textures(self.h, x.ctypes.data, len(x)), "skr_scene_set_sphere_textures")
+
+    def clear_textures(self):
+        """Every sphere's texture index back to -1 (the textures stay; include/skr.h skr_scene_clear_textures)."""
+        _check(lib().skr_scene_clear_textures(self.h), "skr_scene_clear_textures")
+
     def set_lens(self, aperture, focus=1.0):
         """Give the camera a thin lens (depth of field; include/skr.h skr_scene_set_lens states the rule): aperture radius >= 0 (0: the
         pinhole), focus > 0 in units of the primary ray directions, both finite.  A renderer takes the lens the scene has when it is made."""
@@ -479,7 +530,8 @@ class Scene:
 
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
-                    triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None, velocities=None, shutter=None, environment=None):
+                    triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None, velocities=None, shutter=None, environment=None, textures=None,
+                    sphere_textures=None):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -511,22 +563,28 @@ class Scene:
             sc.set_shutter(shutter)
         if environment is not None:  # [E, E, 3] (an image-based background and GI light)
             sc.set_environment(environment)
+        for t in (textures or ()):  # [E, E, 3] each, indexed in this order
+            sc.add_texture(t)
+        if sphere_textures is not None:  # one index per sphere, -1 = none
+            sc.set_sphere_textures(sphere_textures)
         return sc
 
 
-SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT, SCN_MOTION = 1, 2, 4, 8, 16, 32  # include/skr.h SKR_SCN_*
+SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT, SCN_MOTION, SCN_TEXTURE = 1, 2, 4, 8, 16, 32, 64  # include/skr.h SKR_SCN_*
 FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
 ENV_MAX_EDGE = 4096         # include/skr.h SKR_ENV_MAX_EDGE
+TEX_MAX, TEX_MAX_EDGE = 16, 1024  # include/skr.h SKR_TEX_MAX, SKR_TEX_MAX_EDGE
 
 
-def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False, motion=False):
+def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False, motion=False, texture=False):
     """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept),
     fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded), triangle_shadows = SKR_SCN_TRIANGLE_SHADOWS
     (--triangle-shadows: triangles cast shadows in frames with shade_triangles and shadow), sphere_tree = SKR_SCN_SPHERE_TREE
     (--sphere-tree: frames and shading queries on the culled sphere walk, any sphere count), spot = SKR_SCN_SPOT (--scn-spot: spot_light
-    lines parsed and shaded), motion = SKR_SCN_MOTION (--scn-motion: velocity lines parsed, the spheres that follow move)."""
+    lines parsed and shaded), motion = SKR_SCN_MOTION (--scn-motion: velocity lines parsed, the spheres that follow move),
+    texture = SKR_SCN_TEXTURE (--scn-texture: texture lines parsed, the spheres that follow carry the image)."""
     h = C.c_void_p()
-    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0) | (SCN_SPOT if spot else 0) | (SCN_MOTION if motion else 0)
+    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0) | (SCN_SPOT if spot else 0) | (SCN_MOTION if motion else 0) | (SCN_TEXTURE if texture else 0)
     _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), flags, C.byref(h)), "skr_scene_create_from_scn_ex")
     return Scene(h.value)
 

@@ -43,12 +43,16 @@ struct DeviceScene {
 
 	float4 *d_env = nullptr; // the environment's texels {r, g, b, 0}, edge * edge rows, row j first (launch.h EnvMap); null unless the scene has an environment
 
+	float4 *d_tex = nullptr; // the textures: one row pair {texel offset, edge} per sphere in file order (edge 0: none), padded to whole 16-byte rows, then every texture's texels
+	                         // {r, g, b, 0}, row j first (launch.h Textures); null unless textures are in force
+	size_t tex_rows = 0;     // the float4 rows the per-sphere pairs take: the texels start behind them
+
 	DeviceScene() = default;
 	DeviceScene(const DeviceScene &) = delete;
 	DeviceScene &operator=(const DeviceScene &) = delete;
 	~DeviceScene()
 	{
-		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work, (void *) d_vel, (void *) d_env})
+		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work, (void *) d_vel, (void *) d_env, (void *) d_tex})
 			if(p) (void) hipFree(p);
 	}
 };
@@ -253,6 +257,30 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		e = hipMalloc((void **) &s->d_env, n * 16);
 		if(e == hipSuccess) e = hipMemcpy(s->d_env, tex.data(), n * 16, hipMemcpyHostToDevice);
 	}
+	if(e == hipSuccess && s->layout.textured)
+	{ // so do the textures: the per-sphere rows, then the texels of every texture some sphere names
+		s->tex_rows = (ns * 8 + 15) / 16;
+		std::vector<skr_f4> tex(s->tex_rows, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
+		std::vector<uint32_t> first(scene->textures.size(), 0xFFFFFFFFu); // where texture k's texels start, once some sphere names it
+		std::vector<uint32_t> pairs(s->tex_rows * 4, 0u);
+		for(size_t i = 0; i < ns && i < scene->sphere_textures.size(); i++)
+		{
+			const int32_t k = scene->sphere_textures[i];
+			if(k < 0 || (size_t) k >= scene->textures.size()) continue;
+			const size_t E = (size_t) scene->texture_edges[(size_t) k];
+			if(first[(size_t) k] == 0xFFFFFFFFu)
+			{
+				first[(size_t) k] = (uint32_t) (tex.size() - s->tex_rows);
+				const std::vector<float> &t = scene->textures[(size_t) k];
+				for(size_t j = 0; j < E * E; j++) tex.push_back(skr_f4{t[3 * j], t[3 * j + 1], t[3 * j + 2], 0.0f});
+			}
+			pairs[2 * i] = first[(size_t) k];
+			pairs[2 * i + 1] = (uint32_t) E;
+		}
+		memcpy(tex.data(), pairs.data(), s->tex_rows * 16);
+		e = hipMalloc((void **) &s->d_tex, tex.size() * 16);
+		if(e == hipSuccess) e = hipMemcpy(s->d_tex, tex.data(), tex.size() * 16, hipMemcpyHostToDevice);
+	}
 	if(e == hipSuccess)
 	{ // the camera belongs to the scene: its (e, c) rows are formed once, on the device, by the operations every ray would perform
 		const float *c = scene->info.camera;
@@ -383,12 +411,14 @@ struct LaunchScene {
 	bool count_tri;
 	const float4 *vel; // the velocity rows where motion is in force (DeviceScene::d_vel)
 	const float4 *env; // the environment's texels where the scene has one (DeviceScene::d_env)
+	const float4 *tex; // the textures' rows and texels where textures are in force (DeviceScene::d_tex) ...
+	size_t tex_rows;   // ... and how many rows the per-sphere pairs take
 	const float4 *sec(SkrBlobSection k) const { return blob + layout.first[k]; } // where a section starts
 };
 static LaunchScene launch_scene(const skr_renderer *r)
 {
 	const DeviceScene &s = *r->scene;
-	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri, s.d_vel, s.d_env};
+	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri, s.d_vel, s.d_env, s.d_tex, s.tex_rows};
 }
 static float4 ball4(const skr_f4 &b) { return make_float4(b.x, b.y, b.z, b.w); }
 
@@ -579,6 +609,13 @@ static GenericFeatures generic_features(const LaunchScene &v, const RenderParams
 	}
 	f.env = s.env_edge > 0; // (frames and shading queries alike)
 	if(f.env) f.envmap = EnvMap{v.env, s.env_edge};
+	f.tex = s.textured && p.n_spheres > 0; // (frames and shading queries alike)
+	if(f.tex)
+	{ // such a launch carries the spot and radius tables too, as one with motion does (render_generic.hip with_pack)
+		f.textures = Textures{v.tex + v.tex_rows, reinterpret_cast<const uint2 *>(v.tex)};
+		f.spots = SpotLights{v.sec(SKR_SEC_spot), s.spot_first, s.n_spot};
+		f.softs = SoftLights{reinterpret_cast<const float *>(v.sec(SKR_SEC_radii)), s.n_radii};
+	}
 	return f;
 }
 
@@ -739,7 +776,7 @@ static int scene_leaf_plan(const skr_scene *scene, const skr_options *opt, int w
 	load_switches(sw);
 	RenderParams p = camera_params(scene->info, opt, opt->seed, 0);
 	GenericFeatures f; // (host memory: only addresses are formed, and null-ness asked)
-	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false, reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data())};
+	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false, reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data()), 0};
 	const int rc = launch_params(v, opt, p, f);
 	return rc != SKR_OK ? -rc : what ? (int) skr_leaf_pow_plan(p) : (int) skr_leaf_shape(p);
 }
@@ -1332,6 +1369,11 @@ static int denoised_host(skr_renderer *r, const char *who, const skr_options *op
 		skr_set_error("%s: an environment map (--envmap) cannot be combined with the denoiser (its guides hold one class for every miss: the filter would smear the backdrop)", who);
 		return SKR_ERR_UNSUPPORTED;
 	}
+	if(r->scene->layout.textured)
+	{ // nor has a scene with textures (include/skr.h skr_scene_add_texture)
+		skr_set_error("%s: sphere textures (--scn-texture) cannot be combined with the denoiser (its guides hold one class per sphere: the filter would smear the pattern)", who);
+		return SKR_ERR_UNSUPPORTED;
+	}
 	SKR_HIP(hipSetDevice(r->scene->device));
 	const size_t n = (size_t) opt->width * opt->height;
 	ScratchLayout L; // the frame, (adaptive) its variance and pass counts, the camera rays and guides, the filtered frame and its bytes
@@ -1384,7 +1426,7 @@ int skr_render_adaptive_denoised_host(skr_renderer *r, const skr_options *opt, c
 
 int skr_debug_eval(int op, const void *d_in, void *d_out, uint32_t n, void *stream)
 {
-	if(!d_in || !d_out || op < 0 || op > 25) return SKR_ERR_ARG;
+	if(!d_in || !d_out || op < 0 || op > 26) return SKR_ERR_ARG;
 	if(n == 0) return SKR_OK;
 	SKR_HIP(skr_launch_debug(op, d_in, d_out, n, (hipStream_t) stream));
 	return SKR_OK;

@@ -88,6 +88,16 @@ struct EnvMap {
 	int32_t edge;
 };
 
+// The textures of a scene some sphere of which has one (include/skr.h skr_scene_add_texture; render_generic.hip
+// textured_material): what the general level pipeline's activate and finalize instances for a launch with textures in force read, in a
+// kernel argument of their own as every feature is.  texels: one allocation for all textures, rows {r, g, b, 0} so that a tap is one
+// 16-byte gather, each texture row j first; rows: per sphere in file order {where its texture's texels start, its edge}, edge 0 = none,
+// read by per-lane index as the material rows are.  An allocation of the renderer's beside the scene blob.
+struct Textures {
+	const float4 *texels;
+	const uint2 *rows;
+};
+
 // A shading query (include/skr.h skr_shade_rays) on the general level pipeline: the rays are its roots, as rows of RenderParams::width
 // rays (the last row partial), banded like a frame's rows.  The kernels' second argument (render_generic.hip).
 struct ShadeRays {
@@ -124,6 +134,8 @@ struct GenericFeatures {
 	Motion mot{};             // (motion; such a launch always carries spots and softs, n = 0 where the scene has none)
 	bool env = false;         // the environment is in force: the scene has one (include/skr.h skr_scene_set_environment); frames and shading queries
 	EnvMap envmap{};          // (env; with it the finalize kernel also takes thin_lens where lens is set: a primary miss looks up d')
+	bool tex = false;         // textures are in force: some sphere has a texture (include/skr.h skr_scene_add_texture); frames and shading queries
+	Textures textures{};      // (tex; such a launch always carries spots and softs, n = 0 where the scene has none)
 };
 
 enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
@@ -262,11 +274,12 @@ static inline unsigned skr_leaf_pow_plan(const RenderParams &p)
 
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
-// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius, a lens, motion and the environment take the general level pipeline
+// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius, a lens, motion, the environment and textures take the general level pipeline
 bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, const GenericFeatures &f); // false: the launch takes a level pipeline and not one band of it fits the budget
 // The features a launch cannot combine, given the options as the caller set them: spot lights, lights with a radius and a lens exclude
 // --legacy-reflect, fog volumes and the sphere tree; fog excludes --legacy-reflect and --shade-triangles, and with the latter triangle
-// shadows; motion excludes what they exclude, and a lens; the environment excludes --legacy-reflect, fog volumes and the sphere tree.
+// shadows; motion excludes what they exclude, and a lens; the environment excludes --legacy-reflect, fog volumes and the sphere tree, and so do
+// textures.
 // (Lights with a radius need the SpotLights argument: the record always carries it.)  The text for the user, or null.
 const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect, bool shade_triangles, bool fog);
 // what skr_kernel_variant() reports for a frame (query: a shading query) on the general level pipeline; static storage

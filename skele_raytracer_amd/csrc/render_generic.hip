@@ -52,6 +52,12 @@
 // carry nothing for one: with an EnvMap in the pack it forms the missed ray's direction again, by the function that formed it for the
 // trace kernel — child_of on its own node below level 0, primary_ray (then lens_ray: a Lens rides behind the EnvMap) or the caller's d at
 // level 0 — and returns wave_common.h env_lookup of it.  Trace and activate instances, records and nodes are as they were.
+//
+// Textures (include/skr.h skr_scene_add_texture).  With a Textures in the pack — the last argument, behind everything —
+// the two places that take a node's material rows, the activate kernel and node_value, hand them to textured_material with the node's
+// shading normal: at a sphere with a texture kd and the ambient row are multiplied by wave_common.h env_lookup of N on that texture.
+// The finalize kernel finds N in the node's rows with the bits the activate kernel had.  Trace instances, records and nodes are as they
+// were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -115,6 +121,33 @@ SKR_DEV void surface_material(const SceneView &sv, const RenderParams &p, uint32
 		ks4 = sv.ks[surf];
 	}
 }
+
+// tex_k(N) of include/skr.h skr_scene_add_texture on the texture whose texels start at row `first` and whose edge is E >= 1: the
+// environment's lookup of N — env_taps and the four clamped gathers — with (1, 1, 1) where its first step fails
+SKR_DEV f3 texture_colour(const Textures &tx, uint32_t first, uint32_t E, f3 N)
+{
+	return env_lookup(EnvMap{tx.texels + first, (int32_t) E}, N, mk3(1, 1, 1));
+}
+
+// The one statement of the texture rule: the material rows of a node on sphere `surf` with the shading normal N.  kd' = kd c and
+// ambp' = {ambp.xyz c, ambp.w}, one multiply per component; a triangle, and a sphere without a texture, keep their rows.
+SKR_DEV void textured_material(const Textures &tx, uint32_t surf, f3 N, float4 &ambp, f3 &kd)
+{
+	if(surf & SURF_TRI) return;
+	const uint2 row = tx.rows[surf];
+	if(row.y == 0u) return;
+	const f3 c = texture_colour(tx, row.x, row.y, N);
+	kd = kd * c;
+	ambp = make_float4(ambp.x * c.x, ambp.y * c.y, ambp.z * c.z, ambp.w);
+}
+// what node_value is handed where the launch has no textures: nothing, and no code
+struct NoTextures {
+	static constexpr bool on = false;
+};
+struct WithTextures {
+	static constexpr bool on = true;
+	const Textures &tx;
+};
 
 // does the node spawn the legacy children (raytrace.h:52: a specular colour other than (0,0,0); only a sphere hit has these terms)
 SKR_DEV bool legacy_children(const RenderParams &p, const SceneView &sv, uint32_t surf)
@@ -409,12 +442,14 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 namespace {
 
 // the value of a node whose children's values are known — or all (0,0,0): shade(depth 0), raytrace.h:142-145.  `value_of(c)`: child c.
-template <typename F>
-SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n, F value_of)
+// TX: the launch's textures (WithTextures), or none
+template <typename F, typename TX = NoTextures>
+SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n, F value_of, const TX &tex = TX())
 {
 	float4 ambp, ks4;
 	f3 kd;
 	surface_material(sv, p, n.surf, ambp, kd, ks4);
+	if constexpr(TX::on) textured_material(tex.tx, n.surf, n.N, ambp, kd);
 	const uint32_t N = (uint32_t) (p.monte_carlo ? p.num_path_traces : 0);
 	f3 direct = n.direct;
 	if(p.legacy_reflect && !(n.surf & SURF_TRI))
@@ -449,13 +484,15 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 // FOG: the scene has fog volumes (a separate instance: the fog term's registers would cost every other frame a wave per SIMD)
 // Q: TriShadows — the shadow walk behind the sphere test; SphereTree — the sphere test is the tree's pair walk; SpotLights — the pair loop with
 //    the cone decision; SpotLights SoftLights — and the light sample ahead of it; Lens — a level-1 hit's ray starts on the lens; Motion —
-//    the normal and the shadow rays meet the spheres where they are at the sample's shutter time (which packs exist: with_pack)
+//    the normal and the shadow rays meet the spheres where they are at the sample's shutter time; Textures — the material rows of a
+//    sphere with a texture are multiplied by its colour at the normal (which packs exist: with_pack)
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
 	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>, SPOT = pack_has<SpotLights, Q...>,
-				   SOFT = pack_has<SoftLights, Q...>, LENS = pack_has<Lens, Q...>, MOTION = pack_has<Motion, Q...>;
+				   SOFT = pack_has<SoftLights, Q...>, LENS = pack_has<Lens, Q...>, MOTION = pack_has<Motion, Q...>, TEX = pack_has<Textures, Q...>;
 	static_assert(!MOTION || (SPOT && SOFT && !FOG && !STREE && !LENS), "a launch with motion carries SpotLights and SoftLights (with_pack)");
+	static_assert(!TEX || (SPOT && SOFT && !FOG && !STREE), "a launch with textures carries SpotLights and SoftLights (with_pack)");
 	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -529,6 +566,7 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		}
 		else if constexpr(MOTION) n.N = normalize3(n.P - ld3(at.row(sv.geom[surf], (int) surf))); // :205, the centre the trace kernel's search met
 		else n.N = normalize3(n.P - ld3(sv.geom[surf])); // :205
+		if constexpr(TEX) textured_material(pick<Textures>(qs...), surf, n.N, ambp, kd); // (ahead of the light loop: the taps are dead when it starts)
 		cn.hits++;
 		{ // raytrace.h:36-44: the direct light, each arm with what this instance's pack switches on
 			using Shadows = TriangleShadows<TSHADOW>; // what a pair loop calls behind its sphere test
@@ -551,7 +589,8 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		n.fr = (p.legacy_reflect && !(surf & SURF_TRI)) ? legacy_fresnel(n.d, n.N, ks4.w) : 0.0f; // :46
 		if(p.g_last)
 		{ // its children are shade(depth 0) == (0,0,0): the node is finished
-			store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }));
+			if constexpr(TEX) store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }, WithTextures{pick<Textures>(qs...)}));
+			else store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }));
 		}
 		else
 		{
@@ -572,7 +611,8 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p, const Q... qs)
 {
-	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, ENV = pack_has<EnvMap, Q...>, LENS = pack_has<Lens, Q...>;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, ENV = pack_has<EnvMap, Q...>, LENS = pack_has<Lens, Q...>, TEX = pack_has<Textures, Q...>;
+	static_assert(!TEX || !STREE, "textures exclude the sphere tree (skr_features_conflict)");
 	static_assert(!ENV || !STREE, "the environment excludes the sphere tree (skr_features_conflict)");
 	static_assert(!LENS || (ENV && !RAYS), "the finalize kernel takes a Lens only behind an EnvMap, and only for frames (with_pack)");
 	const ShadeRays q = pick<ShadeRays>(qs...);
@@ -643,7 +683,8 @@ __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p
 	GNode m = n;
 	if constexpr(ENV) own = &m;
 	// a child that does not exist (no legacy terms for this surface; fr >= 1) is never asked for by node_value()
-	store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of));
+	if constexpr(TEX) store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of, WithTextures{pick<Textures>(qs...)}));
+	else store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of));
 }
 
 // =====================================================================================================================
@@ -696,23 +737,32 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
 // tree with spot lights, a radius, a lens or motion; a lens with motion) are no instance, nor is a lens with a shading query (its rays are
 // the caller's).  A launch with motion always carries SpotLights SoftLights (their tables have n = 0 where the scene has none), so motion
 // adds two trace and four activate instances.  The environment excludes the sphere tree too and adds three finalize instances:
-// <EnvMap>, <ShadeRays, EnvMap>, <EnvMap, Lens>.
+// <EnvMap>, <ShadeRays, EnvMap>, <EnvMap, Lens>.  Textures come last, in the activate and the finalize kernel's pack: [...] Textures.
+// They exclude the sphere tree, and a launch with them always carries SpotLights SoftLights as one with motion does, so they add ten
+// activate instances — [ShadeRays] [TriShadows] SpotLights SoftLights [Lens | Motion] Textures, a Lens never behind ShadeRays — and five
+// finalize instances: <Textures>, <EnvMap, Textures>, <EnvMap, Lens, Textures>, <ShadeRays, Textures>, <ShadeRays, EnvMap, Textures>.
+// No trace instance takes them.
 enum PackOf { PACK_FINALIZE, PACK_TRACE, PACK_ACTIVATE };
 template <PackOf K, typename F>
 static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 {
 	constexpr bool ACT = K == PACK_ACTIVATE;
+	auto last = [&](auto... all) { // (the activate kernel's Textures only behind SoftLights: no other pack of it is ever asked for them)
+		if constexpr(K == PACK_FINALIZE || (ACT && pack_has<SoftLights, decltype(all)...>))
+			if(f.tex) return launch(all..., f.textures);
+		launch(all...);
+	};
 	auto lens = [&](auto... all) {
 		if constexpr(K != PACK_FINALIZE && !pack_has<ShadeRays, decltype(all)...>)
-			if(f.lens) return launch(all..., f.thin_lens);
-		launch(all...);
+			if(f.lens) return last(all..., f.thin_lens);
+		last(all...);
 	};
 	auto tail = [&](auto... head) {
 		if(f.sphere_tree) return launch(head..., f.stree);
 		if constexpr(ACT)
 		{
-			if(f.motion) return launch(head..., f.spots, f.softs, f.mot);
-			if(f.soft) return lens(head..., f.spots, f.softs);
+			if(f.motion) return last(head..., f.spots, f.softs, f.mot);
+			if(f.soft || f.tex) return lens(head..., f.spots, f.softs);
 			if(f.spot) return lens(head..., f.spots);
 		}
 		else if constexpr(K == PACK_TRACE)
@@ -722,8 +772,8 @@ static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 		else if(f.env)
 		{ // the finalize kernel: the lookup, and under a lens the draw that made the primary ray (a frame's only)
 			if constexpr(!pack_has<ShadeRays, decltype(head)...>)
-				if(f.lens) return launch(head..., f.envmap, f.thin_lens);
-			return launch(head..., f.envmap);
+				if(f.lens) return last(head..., f.envmap, f.thin_lens);
+			return last(head..., f.envmap);
 		}
 		lens(head...);
 	};
@@ -817,4 +867,57 @@ hipError_t skr_launch_generic(const RenderParams &p_in, const GPlan &pl, hipStre
 	}
 	if(p.grid_size > 0 && !q_in) return skr_launch_resolve(p, stream);
 	return hipSuccess;
+}
+
+// =====================================================================================================================
+// skr_debug_eval op 26 (include/skr.h): the texture colour of a normal, through texture_colour as textured_material calls it
+// =====================================================================================================================
+namespace {
+constexpr uint32_t DEBUG_TEX_EDGES[4] = {1u, 2u, 3u, 64u};
+}
+__global__ void skr_debug_texture_kernel(const uint32_t *in, uint32_t *out, uint32_t n, const Textures tx)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	const uint32_t *r = in + 4 * i;
+	f3 c = mk3(1, 1, 1);
+	if(r[3] < 4u)
+	{ // (the op's rows are per texture, not per sphere)
+		const uint2 row = tx.rows[r[3]];
+		c = texture_colour(tx, row.x, row.y, mk3(__uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2])));
+	}
+	uint32_t *w = out + 3 * i;
+	w[0] = __float_as_uint(c.x); w[1] = __float_as_uint(c.y); w[2] = __float_as_uint(c.z);
+}
+
+hipError_t skr_launch_debug_texture(const void *d_in, void *d_out, uint32_t n, hipStream_t stream)
+{ // the op's own textures: edges (1, 2, 3, 64), texel (row j, column i) = (i + 1, j + 1, 0.5 (i + j) + 0.25); two rows of pairs, then the texels
+	const size_t rows = 2;
+	size_t total = rows;
+	for(uint32_t E : DEBUG_TEX_EDGES) total += (size_t) E * E;
+	float4 *host = (float4 *) calloc(total, sizeof(float4));
+	if(!host) return hipErrorOutOfMemory;
+	uint32_t *pairs = reinterpret_cast<uint32_t *>(host);
+	size_t at = rows;
+	for(int k = 0; k < 4; k++)
+	{
+		const uint32_t E = DEBUG_TEX_EDGES[k];
+		pairs[2 * k] = (uint32_t) (at - rows);
+		pairs[2 * k + 1] = E;
+		for(uint32_t j = 0; j < E; j++)
+			for(uint32_t i = 0; i < E; i++) host[at++] = make_float4((float) (i + 1u), (float) (j + 1u), 0.5f * (float) (i + j) + 0.25f, 0.0f);
+	}
+	float4 *dev = nullptr;
+	hipError_t e = hipMalloc((void **) &dev, total * sizeof(float4));
+	if(e == hipSuccess) e = hipMemcpy(dev, host, total * sizeof(float4), hipMemcpyHostToDevice);
+	free(host);
+	if(e == hipSuccess)
+	{
+		hipLaunchKernelGGL(skr_debug_texture_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const uint32_t *) d_in, (uint32_t *) d_out, n,
+						   Textures{dev + rows, reinterpret_cast<const uint2 *>(dev)});
+		e = hipGetLastError();
+		if(e == hipSuccess) e = hipStreamSynchronize(stream); // (the textures are freed below)
+	}
+	if(dev) (void) hipFree(dev);
+	return e;
 }

@@ -169,6 +169,10 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 	const bool motion = (flags & SKR_SCN_MOTION) != 0;
 	float vel[3] = {0.0f, 0.0f, 0.0f}; // SKR_SCN_MOTION: the velocity in force for the sphere lines that follow, stateful as `material` is
 	std::vector<float> vels;
+	const bool texture = (flags & SKR_SCN_TEXTURE) != 0;
+	int32_t tex = -1; // SKR_SCN_TEXTURE: the texture in force for the sphere lines that follow (-1: none), stateful as `material` is
+	std::vector<int32_t> texs;
+	std::vector<std::string> tex_names; // the resolved name of texture k: the same name twice is one texture
 	FILE *fp = fopen(path.c_str(), "r");
 	if(!fp)
 	{
@@ -211,6 +215,7 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 			sc.raw_spheres.insert(sc.raw_spheres.end(), rec, rec + 14);
 			sc.raw_sphere_ior.push_back(mat.ior);
 			vels.insert(vels.end(), vel, vel + 3);
+			texs.push_back(tex);
 			info.n_spheres++;
 		}
 		else if(cmd == "vertex")
@@ -377,6 +382,62 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 				info.n_unknown++;
 			}
 		}
+		else if(texture && cmd == "texture")
+		{ // SKR_SCN_TEXTURE (the reference does not know the command): NAME, a square colour PFM, or `none`
+			const char *a = args;
+			while(*a == ' ' || *a == '\t' || *a == '\r' || *a == '\n' || *a == '\v' || *a == '\f') a++;
+			const char *b = a;
+			while(*b && !(*b == ' ' || *b == '\t' || *b == '\r' || *b == '\n' || *b == '\v' || *b == '\f')) b++;
+			std::string name(a, b);
+			const char *why = nullptr;
+			if(name.empty()) why = "needs the name of a square colour PFM file, or none";
+			else if(name == "none")
+			{
+				if(echo) printf("texture none\n");
+				tex = -1;
+			}
+			else
+			{
+				if(name[0] != '/')
+				{ // a relative name is the scene file's neighbour
+					const size_t slash = path.find_last_of('/');
+					if(slash != std::string::npos) name = path.substr(0, slash + 1) + name;
+				}
+				int32_t k = 0;
+				while(k < (int32_t) tex_names.size() && tex_names[(size_t) k] != name) k++;
+				if(k == (int32_t) tex_names.size())
+				{
+					uint32_t tw = 0, th = 0;
+					std::vector<float> texels;
+					if(k >= SKR_TEX_MAX) why = "would be one texture too many";
+					else if(skr_read_pfm(name.c_str(), &tw, &th, nullptr) != SKR_OK) why = "names a file that cannot be read as a colour PFM";
+					else if(tw != th || tw > (uint32_t) SKR_TEX_MAX_EDGE) why = "names a file that is not square or has too long an edge";
+					else
+					{
+						texels.resize((size_t) tw * th * 3);
+						if(skr_read_pfm(name.c_str(), &tw, &th, texels.data()) != SKR_OK) why = "names a file that cannot be read as a colour PFM";
+						for(size_t i = 0; !why && i < texels.size(); i++)
+							if(!std::isfinite(texels[i])) why = "names a file with a texel that is not finite";
+					}
+					if(!why)
+					{
+						sc.textures.push_back(std::move(texels));
+						sc.texture_edges.push_back((int32_t) tw);
+						tex_names.push_back(name);
+					}
+				}
+				if(!why)
+				{
+					if(echo) printf("texture %d: %s (%d x %d)\n", k, name.c_str(), sc.texture_edges[(size_t) k], sc.texture_edges[(size_t) k]);
+					tex = k;
+				}
+			}
+			if(why)
+			{
+				fprintf(stderr, "WARNING. texture %s (at most %d textures, edges up to %d): line skipped\n", why, SKR_TEX_MAX, SKR_TEX_MAX_EDGE);
+				info.n_unknown++;
+			}
+		}
 		else
 		{
 			if(echo) printf("WARNING. Do not know command: %s\n", cmd.c_str());
@@ -386,6 +447,7 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 	fclose(fp);
 	sc.finalize();
 	if(motion) sc.velocities = vels;
+	if(texture) sc.sphere_textures = texs;
 	return SKR_OK;
 }
 
@@ -638,6 +700,82 @@ int skr_scene_get_environment(const skr_scene *scene, float *texels, int32_t *ed
 	if(!scene) return SKR_ERR_ARG;
 	if(edge) *edge = scene->env_edge;
 	if(texels && scene->env_edge > 0) memcpy(texels, scene->env_texels.data(), scene->env_texels.size() * sizeof(float));
+	return SKR_OK;
+}
+
+int skr_scene_add_texture(skr_scene *scene, const float *texels, int32_t edge)
+{
+	if(!scene || !texels)
+	{
+		skr_set_error("skr_scene_add_texture: null argument");
+		return -SKR_ERR_ARG;
+	}
+	if(edge < 1 || edge > SKR_TEX_MAX_EDGE)
+	{
+		skr_set_error("skr_scene_add_texture: the edge must be in [1, %d]: %d", SKR_TEX_MAX_EDGE, edge);
+		return -SKR_ERR_ARG;
+	}
+	if((int) scene->textures.size() >= SKR_TEX_MAX)
+	{
+		skr_set_error("skr_scene_add_texture: the scene holds %d textures already", SKR_TEX_MAX);
+		return -SKR_ERR_ARG;
+	}
+	const size_t n = (size_t) edge * (size_t) edge * 3;
+	for(size_t i = 0; i < n; i++)
+		if(!std::isfinite(texels[i]))
+		{
+			skr_set_error("skr_scene_add_texture: texel (row %zu, column %zu) has a channel that is not finite", i / 3 / (size_t) edge, i / 3 % (size_t) edge);
+			return -SKR_ERR_ARG;
+		}
+	scene->textures.emplace_back(texels, texels + n);
+	scene->texture_edges.push_back(edge);
+	return (int) scene->textures.size() - 1;
+}
+
+int skr_scene_texture_count(const skr_scene *scene) { return scene ? (int) scene->textures.size() : -SKR_ERR_ARG; }
+
+int skr_scene_get_texture(const skr_scene *scene, int32_t k, float *texels, int32_t *edge)
+{
+	if(!scene || k < 0 || k >= (int32_t) scene->textures.size())
+	{
+		skr_set_error("skr_scene_get_texture: bad argument (the scene holds %d textures: %d)", scene ? (int) scene->textures.size() : 0, k);
+		return SKR_ERR_ARG;
+	}
+	if(edge) *edge = scene->texture_edges[(size_t) k];
+	if(texels) memcpy(texels, scene->textures[(size_t) k].data(), scene->textures[(size_t) k].size() * sizeof(float));
+	return SKR_OK;
+}
+
+int skr_scene_set_sphere_textures(skr_scene *scene, const int32_t *idx, int32_t n)
+{
+	if(!scene || n != scene->info.n_spheres || (n > 0 && !idx))
+	{
+		skr_set_error("skr_scene_set_sphere_textures: bad argument (one texture index per sphere: %d)", scene ? scene->info.n_spheres : 0);
+		return SKR_ERR_ARG;
+	}
+	for(int32_t i = 0; i < n; i++)
+		if(idx[i] < -1 || idx[i] >= (int32_t) scene->textures.size())
+		{
+			skr_set_error("skr_scene_set_sphere_textures: sphere %d names texture %d, outside [-1, %d)", i, idx[i], (int) scene->textures.size());
+			return SKR_ERR_ARG;
+		}
+	scene->sphere_textures.assign(idx, idx + n);
+	return SKR_OK;
+}
+
+int skr_scene_get_sphere_textures(const skr_scene *scene, int32_t *idx, int32_t *n)
+{
+	if(!scene) return SKR_ERR_ARG;
+	const size_t ns = (size_t) scene->info.n_spheres;
+	if(n) *n = (int32_t) ns;
+	for(size_t i = 0; idx && i < ns; i++) idx[i] = i < scene->sphere_textures.size() ? scene->sphere_textures[i] : -1;
+	return SKR_OK;
+}
+
+int skr_scene_clear_textures(skr_scene *scene)
+{
+	if(!scene) return SKR_ERR_ARG;
+	scene->sphere_textures.clear(); // (shorter than the sphere count: -1)
 	return SKR_OK;
 }
 

@@ -63,6 +63,15 @@ struct skr_scene {
 	}
 	std::vector<float> env_texels;       // [E][E][3] the environment's texels, row j first; empty = none — skr_scene_set_environment only (include/skr.h)
 	int32_t env_edge = 0;                // E; 0 = no environment (then misses return info.background, as ever)
+	std::vector<std::vector<float>> textures; // texture k: [E_k][E_k][3] texels, row j first — SKR_SCN_TEXTURE / skr_scene_add_texture only (include/skr.h)
+	std::vector<int32_t> texture_edges;  // E_k
+	std::vector<int32_t> sphere_textures; // [n] the texture index of every sphere in file order, -1 = none; shorter than n = -1 — skr_scene_set_sphere_textures
+	bool textured() const                // textures are in force: some sphere has a texture
+	{
+		for(int32_t x : sphere_textures)
+			if(x >= 0) return true;
+		return false;
+	}
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
 	bool sphere_tree = false;            // SKR_SCN_SPHERE_TREE / skr_scene_set_sphere_tree: likewise

@@ -56,6 +56,8 @@ struct SceneLayout {
 	float shutter = 1.0f; // The velocities are no section of the blob: the renderer uploads them beside it (api.cpp DeviceScene::d_vel)
 	int env_edge = 0;     // the environment's edge E, 0 = none (include/skr.h skr_scene_set_environment): in force, frames and shading queries take the finalize instances
 	                      // with the lookup.  The texels are no section of the blob either (api.cpp DeviceScene::d_env)
+	bool textured = false; // textures are in force (skr_scene::textured(), include/skr.h skr_scene_add_texture): frames and shading queries take the activate and finalize
+	                       // instances with the lookup.  Rows and texels are no section of the blob either (api.cpp DeviceScene::d_tex)
 };
 
 // The blob of `s` and its layout; nothing is uploaded.

@@ -223,5 +223,90 @@ int main(int argc, char **argv)
 			skr_scene_destroy(sc);
 		}
 	}
+	{ // sphere textures: add, get, the per-sphere indices with good and bad arguments, and the parser's `texture` lines on good, missing, malformed and too many files
+		std::vector<float> t2(2 * 2 * 3), t3(3 * 3 * 3, 0.25f);
+		for(size_t i = 0; i < t2.size(); i++) t2[i] = 0.5f * (float) i;
+		skr_write_pfm("build/asan_t2.pfm", 2, 2, t2.data());
+		skr_write_pfm("build/asan_t3.pfm", 3, 3, t3.data());
+		skr_write_pfm("build/asan_wide.pfm", 3, 2, t3.data());
+		t3[7] = INFINITY;
+		skr_write_pfm("build/asan_inf.pfm", 3, 3, t3.data());
+		t3[7] = 0.25f;
+		FILE *fp = fopen("build/asan_tex.scn", "w");
+		if(fp)
+		{
+			fputs("sphere 0 0 0 1\ntexture asan_t2.pfm\nsphere 1 0 0 1\ntexture\ntexture  \t \ntexture asan_missing.pfm\ntexture asan_wide.pfm\ntexture asan_inf.pfm\ntexture asan_bad.pfm\n"
+				  "sphere 2 0 0 1\ntexture asan_t3.pfm trailing words\nsphere 3 0 0 1\ntexture none\nsphere 4 0 0 1\ntexture asan_t2.pfm\nsphere 5 0 0 1\n", fp);
+			for(int k = 0; k < SKR_TEX_MAX + 2; k++)
+			{ // more distinct names than a scene holds: copies of one file
+				char name[64];
+				snprintf(name, sizeof name, "build/asan_many%02d.pfm", k);
+				skr_write_pfm(name, 1, 1, t2.data());
+				fprintf(fp, "texture asan_many%02d.pfm\nsphere %d 0 0 1\n", k, 6 + k);
+			}
+			fclose(fp);
+		}
+		for(uint32_t flags : {0u, (uint32_t) SKR_SCN_TEXTURE, (uint32_t) (SKR_SCN_TEXTURE | SKR_SCN_MOTION | SKR_SCN_STRICT)})
+		{
+			skr_scene *sc = nullptr;
+			if(skr_scene_create_from_scn_ex("build/asan_tex.scn", 0, flags, &sc) != 0) continue;
+			skr_scene_info info;
+			skr_scene_get_info(sc, &info);
+			int32_t n = -1;
+			skr_scene_get_sphere_textures(sc, nullptr, &n);
+			std::vector<int32_t> idx((size_t) (n > 0 ? n : 0) + 1, 77);
+			skr_scene_get_sphere_textures(sc, idx.data(), &n);
+			printf("tex: flags %u spheres %d unknown %d textures %d, indices", flags, n, info.n_unknown, skr_scene_texture_count(sc));
+			for(int32_t i = 0; i < n; i++) printf(" %d", idx[(size_t) i]);
+			printf(", guard %d\n", idx[(size_t) n]);
+			for(int k = 0; k < skr_scene_texture_count(sc); k++)
+			{
+				int32_t e = -1;
+				skr_scene_get_texture(sc, k, nullptr, &e);
+				std::vector<float> got((size_t) e * e * 3 + 1, -1.0f);
+				skr_scene_get_texture(sc, k, got.data(), &e);
+				if(k < 2) printf("tex: texture %d edge %d first %g last %g guard %g\n", k, e, got[0], got[got.size() - 2], got.back());
+			}
+			blob_table(sc, "tex", "parsed");
+			skr_scene_destroy(sc);
+		}
+		skr_scene *sc = nullptr;
+		if(skr_scene_create_from_scn("build/bad1.scn", 0, &sc) == 0)
+		{
+			skr_scene_info info;
+			skr_scene_get_info(sc, &info);
+			const int a = skr_scene_add_texture(sc, t2.data(), 2), b = skr_scene_add_texture(sc, t3.data(), 3);
+			const int zero = skr_scene_add_texture(sc, t2.data(), 0), neg = skr_scene_add_texture(sc, t2.data(), -3), big = skr_scene_add_texture(sc, t2.data(), SKR_TEX_MAX_EDGE + 1),
+					  null = skr_scene_add_texture(sc, nullptr, 2);
+			t3[26] = NAN;
+			const int not_finite = skr_scene_add_texture(sc, t3.data(), 3);
+			printf("tex: add %d %d, refused %d %d %d %d %d, count %d\n", a, b, zero, neg, big, null, not_finite, skr_scene_texture_count(sc));
+			std::vector<int32_t> idx((size_t) info.n_spheres, 1), back((size_t) info.n_spheres + 1, 77);
+			if(!idx.empty()) idx[0] = -1;
+			const int set = skr_scene_set_sphere_textures(sc, idx.data(), info.n_spheres), shorter = skr_scene_set_sphere_textures(sc, idx.data(), info.n_spheres - 1),
+					  longer = skr_scene_set_sphere_textures(sc, idx.data(), info.n_spheres + 1), null_idx = skr_scene_set_sphere_textures(sc, nullptr, info.n_spheres);
+			if(!idx.empty()) idx.back() = 2;
+			const int outside = skr_scene_set_sphere_textures(sc, idx.data(), info.n_spheres);
+			if(!idx.empty()) idx.back() = -2;
+			const int below = skr_scene_set_sphere_textures(sc, idx.data(), info.n_spheres);
+			int32_t n = -1;
+			skr_scene_get_sphere_textures(sc, back.data(), &n);
+			printf("tex: set %d, refused %d %d %d %d %d, n %d first %d last %d guard %d\n", set, shorter, longer, null_idx, outside, below, n, back[0], n > 0 ? back[(size_t) n - 1] : 0, back[(size_t) n]);
+			int32_t e = -1;
+			printf("tex: get outside %d %d\n", skr_scene_get_texture(sc, -1, nullptr, &e), skr_scene_get_texture(sc, 2, nullptr, &e));
+			blob_table(sc, "tex", "set");
+			const int cleared = skr_scene_clear_textures(sc);
+			skr_scene_get_sphere_textures(sc, back.data(), &n);
+			printf("tex: cleared %d first %d count %d\n", cleared, back[0], skr_scene_texture_count(sc));
+			for(int k = 2; k < SKR_TEX_MAX + 1; k++)
+			{
+				const int rc = skr_scene_add_texture(sc, t2.data(), 1);
+				if(k >= SKR_TEX_MAX - 1) printf("tex: add %d -> %d\n", k, rc);
+			}
+			skr_scene_destroy(sc);
+		}
+		printf("tex: null scene %d %d %d %d %d %d\n", skr_scene_add_texture(nullptr, t2.data(), 2), skr_scene_texture_count(nullptr), skr_scene_get_texture(nullptr, 0, nullptr, nullptr),
+			   skr_scene_set_sphere_textures(nullptr, nullptr, 0), skr_scene_get_sphere_textures(nullptr, nullptr, nullptr), skr_scene_clear_textures(nullptr));
+	}
 	return 0;
 }
