@@ -38,6 +38,7 @@ extern "C" {
 #define SKR_HAS_MOTION 1 /* SKR_SCN_MOTION, skr_scene_set/get_sphere_velocities, skr_scene_set/get_shutter, skr_debug_eval op 24: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_ENVIRONMENT 1 /* skr_scene_set/get_environment, skr_read_pfm, skr_debug_eval op 25: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TEXTURES 1 /* SKR_SCN_TEXTURE, skr_scene_add/get_texture, skr_scene_texture_count, skr_scene_set/get_sphere_textures, skr_scene_clear_textures, skr_debug_eval op 26: an addition that leaves every existing entry point and struct as it was */
+#define SKR_HAS_EMISSION 1 /* SKR_SCN_EMISSION, skr_scene_set/get_sphere_emission: an addition that leaves every existing entry point and struct as it was */
 #define SKR_HAS_TRIANGLE_SHADOWS 1 /* SKR_SCN_TRIANGLE_SHADOWS, skr_scene_set/get_triangle_shadows, skr_scene_get_trace_culling: an addition that leaves every existing entry point and struct as it was */
 
 typedef enum {
@@ -416,6 +417,39 @@ int skr_scene_texture_count(const skr_scene *scene);
 int skr_scene_set_sphere_textures(skr_scene *scene, const int32_t *idx, int32_t n);
 int skr_scene_get_sphere_textures(const skr_scene *scene, int32_t *idx, int32_t *n);
 int skr_scene_clear_textures(skr_scene *scene);
+/* Emissive spheres: surfaces that glow (new, opt-in; no counterpart in the reference, whose `material` line holds no such term).
+ * Every sphere has an emission e_i = (r, g, b), default (0, 0, 0); every component is finite and >= 0.0f (-0.0f passes that test and is
+ * stored as given: x + (-0) = x).  Emission is in force for a launch iff some component of some sphere is > 0; otherwise planning,
+ * skr_kernel_variant(), frames, floats and all work counters are exactly what they are without this section.  The rule (normative):
+ *   - Where it is added.  With emission in force every shade() whose winner is sphere i, at depth > 0, returns v + e_i, v what it
+ *     returned before: raytrace.h:213 under num_path_traces > 0 (--gillum), :218 without.  The add is one correctly rounded binary32 add
+ *     per component, after the multiply by kd and not contracted with it.  It applies to primary rays, under a lens and under motion
+ *     (emission belongs to the sphere index, not to a place), to --gillum children at any level, and to shading queries.
+ *     shade(depth 0) stays (0, 0, 0) (:142-145).  A triangle has no emission.  A texture on the sphere primes kd and the ambient row as
+ *     before and leaves e_i alone.
+ *   - What emission is not.  The light loop and shadow rays do not know emitters: an emitter lights other surfaces only through
+ *     --gillum children that hit it, and is itself shaded and casts shadows like any sphere.  Rays, hits, child rays, draws, shadow
+ *     rays and all four work counters are those of the same scene without emission.
+ *   - Where it runs: a launch with emission in force always takes the general level pipeline; skr_kernel_variant() carries one "_emit"
+ *     part at its very end, behind "_env" and "_tex" where those are present ("level_pipeline_g1_emit",
+ *     "level_pipeline_g1_soft_lens_tshadow_env_tex_emit", "shade_rays_g1_emit", ...).  It combines with everything textures combine
+ *     with: use_shadows, grid_size, num_path_traces at any depth, SKR_SCN_STRICT, shade_triangles with or without triangle shadows, spot
+ *     lights, light radii, motion, a lens, the environment, textures, tiles and strides, bands, clones, skr_multi / skr_comm,
+ *     progressive and adaptive frames, shading queries — and with skr_render_denoised_host / skr_render_adaptive_denoised_host
+ *     (emission is constant per sphere: the guides' one class per sphere still describes the surface).  skr_trace_rays is unaffected.
+ *   - Refused with SKR_ERR_UNSUPPORTED where emission is in force (and only there): skr_options.legacy_reflect, fog volumes and the
+ *     sphere-tree switch.
+ * SKR_SCN_EMISSION (`raytracer --scn-emission`; combines with the other scene flags): a line `emission r g b` sets the emission in
+ * force for the `sphere` lines that follow, stateful exactly as `velocity` and `material` are; `emission 0 0 0` ends it; the initial
+ * state is (0, 0, 0).  A line without three finite numbers >= 0 is warned about, skipped and counted in n_unknown, the emission in force
+ * unchanged.  Without the flag the line stays "WARNING. Do not know command" and everything is byte for byte as it was.
+ * set: rgb float[n][3], n the sphere count; a wrong n, a value that is not finite or a negative value returns SKR_ERR_ARG and leaves
+ * the scene unchanged; rgb == NULL or n == 0 clears the emission.  get: *n = the sphere count, rgb (if not NULL) receives
+ * float[n][3], zeros where none was set.  skr_scene_create_from_arrays scenes start with no emission.  A renderer takes the emission
+ * when it is created (an allocation of its own beside the scene blob); skr_renderer_clone and the multi-GPU frame steps share it. */
+#define SKR_SCN_EMISSION 128u
+int skr_scene_set_sphere_emission(skr_scene *scene, const float *rgb, int32_t n);
+int skr_scene_get_sphere_emission(const skr_scene *scene, float *rgb, int32_t *n);
 /* The sphere tree as a renderer uploads it (built on demand, whatever the switch says).  chunk_size spheres at most per chunk; the
  * first *n_always chunks hold the always-tested spheres (no culling sphere); the other chunks hold consecutive spheres of the Morton
  * order and lie under a depth-first, skip-linked 8-ary tree of *n_nodes nodes.  device_spheres[n_spheres][4] = {centre, r^2} in device

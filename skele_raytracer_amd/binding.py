@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # every symbol include/skr.h declares (tests/test_abi.py checks the library exports them)
 EXPORTED_SYMBOLS = [
-    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_sphere_velocities", "skr_scene_get_sphere_velocities", "skr_scene_set_shutter", "skr_scene_get_shutter", "skr_scene_set_environment", "skr_scene_get_environment", "skr_read_pfm", "skr_scene_add_texture", "skr_scene_get_texture", "skr_scene_texture_count", "skr_scene_set_sphere_textures", "skr_scene_get_sphere_textures", "skr_scene_clear_textures", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
+    "skr_scene_create_from_scn", "skr_scene_create_from_scn_ex", "skr_scene_create_from_arrays", "skr_scene_set_triangle_materials", "skr_scene_set_sphere_ior", "skr_scene_get_fog", "skr_scene_set_fog", "skr_scene_get_spot_lights", "skr_scene_set_spot_lights", "skr_scene_get_spot_cones", "skr_scene_set_light_radii", "skr_scene_get_light_radii", "skr_scene_set_lens", "skr_scene_get_lens", "skr_scene_set_sphere_velocities", "skr_scene_get_sphere_velocities", "skr_scene_set_shutter", "skr_scene_get_shutter", "skr_scene_set_environment", "skr_scene_get_environment", "skr_read_pfm", "skr_scene_add_texture", "skr_scene_get_texture", "skr_scene_texture_count", "skr_scene_set_sphere_textures", "skr_scene_get_sphere_textures", "skr_scene_clear_textures", "skr_scene_set_sphere_emission", "skr_scene_get_sphere_emission", "skr_scene_set_triangle_shadows", "skr_scene_get_triangle_shadows", "skr_scene_set_sphere_tree", "skr_scene_get_sphere_tree", "skr_scene_get_sphere_tree_data", "skr_renderer_read_sphere_tree_work", "skr_scene_destroy", "skr_scene_get_info",
     "skr_scene_get_arrays", "skr_scene_get_culling", "skr_scene_get_trace_culling", "skr_scene_get_shadow_masks", "skr_scene_get_gi_masks", "skr_options_default", "skr_radiance_ray_count", "skr_device_count",
     "skr_renderer_create", "skr_renderer_clone", "skr_renderer_destroy", "skr_render_tiles", "skr_render_tile_list", "skr_tile_costs", "skr_tile_count", "skr_render_rows",
     "skr_renderer_read_counters", "skr_renderer_read_work", "skr_renderer_read_triangle_work", "skr_renderer_count_triangle_work", "skr_renderer_kernel_work", "skr_renderer_reload_switches", "skr_renderer_kernel_timing", "skr_renderer_kernel_ms", "skr_renderer_last_parent_count", "skr_renderer_last_level1_count", "skr_renderer_primary_cache_stats", "skr_render_frame_host", "skr_render_progressive_host", "skr_accumulate", "skr_resolve_accumulated", "skr_write_png", "skr_write_pfm", "skr_write_ppm", "skr_last_error",
@@ -103,6 +103,8 @@ def lib():
     L.skr_scene_set_sphere_textures.argtypes = [vp, vp, C.c_int32]
     L.skr_scene_get_sphere_textures.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_scene_clear_textures.argtypes = [vp]
+    L.skr_scene_set_sphere_emission.argtypes = [vp, vp, C.c_int32]
+    L.skr_scene_get_sphere_emission.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     L.skr_read_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
     L.skr_scene_set_triangle_shadows.argtypes = [vp, C.c_int]
     L.skr_scene_get_triangle_shadows.argtypes = [vp, C.POINTER(C.c_int)]
@@ -483,6 +485,25 @@ class Scene:
         """Every sphere's texture index back to -1 (the textures stay; include/skr.h skr_scene_clear_textures)."""
         _check(lib().skr_scene_clear_textures(self.h), "skr_scene_clear_textures")
 
+    @property
+    def emission(self):
+        """The emission of every sphere, float32 [n_spheres, 3], zeros where none was set (include/skr.h skr_scene_get_sphere_emission)."""
+        n = C.c_int32(0)
+        _check(lib().skr_scene_get_sphere_emission(self.h, None, C.byref(n)), "skr_scene_get_sphere_emission")
+        e = np.zeros((n.value, 3), np.float32)
+        _check(lib().skr_scene_get_sphere_emission(self.h, e.ctypes.data, C.byref(n)), "skr_scene_get_sphere_emission")
+        return e
+
+    def set_emission(self, rgb):
+        """Make spheres glow (include/skr.h skr_scene_set_sphere_emission states the rule): [n_spheres, 3] finite floats >= 0, added to
+        what shade() returns at that sphere; None clears it.  An emitter lights other surfaces only through --gillum.  A renderer takes
+        the emission the scene has when it is made."""
+        if rgb is None:
+            _check(lib().skr_scene_set_sphere_emission(self.h, None, 0), "skr_scene_set_sphere_emission")
+            return
+        e = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+        _check(lib().skr_scene_set_sphere_emission(self.h, e.ctypes.data, len(e)), "skr_scene_set_sphere_emission")
+
     def set_lens(self, aperture, focus=1.0):
         """Give the camera a thin lens (depth of field; include/skr.h skr_scene_set_lens states the rule): aperture radius >= 0 (0: the
         pinhole), focus > 0 in units of the primary ray directions, both finite.  A renderer takes the lens the scene has when it is made."""
@@ -531,7 +552,7 @@ class Scene:
     @staticmethod
     def from_arrays(spheres, triangles, point_lights, camera, background=(0, 0, 0), ambient=(0, 0, 0), triangle_materials=None, sphere_ior=None,
                     triangle_shadows=False, sphere_tree=False, light_radii=None, lens=None, velocities=None, shutter=None, environment=None, textures=None,
-                    sphere_textures=None):
+                    sphere_textures=None, emission=None):
         s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 14)
         t = np.ascontiguousarray(triangles, np.float32).reshape(-1, 9)
         l = np.ascontiguousarray(point_lights, np.float32).reshape(-1, 6)
@@ -567,24 +588,27 @@ class Scene:
             sc.add_texture(t)
         if sphere_textures is not None:  # one index per sphere, -1 = none
             sc.set_sphere_textures(sphere_textures)
+        if emission is not None:  # [n_spheres, 3], >= 0
+            sc.set_emission(emission)
         return sc
 
 
-SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT, SCN_MOTION, SCN_TEXTURE = 1, 2, 4, 8, 16, 32, 64  # include/skr.h SKR_SCN_*
+SCN_STRICT, SCN_FOG, SCN_TRIANGLE_SHADOWS, SCN_SPHERE_TREE, SCN_SPOT, SCN_MOTION, SCN_TEXTURE, SCN_EMISSION = 1, 2, 4, 8, 16, 32, 64, 128  # include/skr.h SKR_SCN_*
 FOG_MAX_VOLUMES = 64        # include/skr.h SKR_FOG_MAX_VOLUMES
 ENV_MAX_EDGE = 4096         # include/skr.h SKR_ENV_MAX_EDGE
 TEX_MAX, TEX_MAX_EDGE = 16, 1024  # include/skr.h SKR_TEX_MAX, SKR_TEX_MAX_EDGE
 
 
-def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False, motion=False, texture=False):
+def parse_scene(path, echo=False, strict=False, fog=False, triangle_shadows=False, sphere_tree=False, spot=False, motion=False, texture=False, emission=False):
     """Reference `Scene parseScene(std::string)` (scene.cpp:12); strict = SKR_SCN_STRICT (--strict-scn: directional lights kept),
     fog = SKR_SCN_FOG (--scn-fog: spherical_fog lines parsed and shaded), triangle_shadows = SKR_SCN_TRIANGLE_SHADOWS
     (--triangle-shadows: triangles cast shadows in frames with shade_triangles and shadow), sphere_tree = SKR_SCN_SPHERE_TREE
     (--sphere-tree: frames and shading queries on the culled sphere walk, any sphere count), spot = SKR_SCN_SPOT (--scn-spot: spot_light
     lines parsed and shaded), motion = SKR_SCN_MOTION (--scn-motion: velocity lines parsed, the spheres that follow move),
-    texture = SKR_SCN_TEXTURE (--scn-texture: texture lines parsed, the spheres that follow carry the image)."""
+    texture = SKR_SCN_TEXTURE (--scn-texture: texture lines parsed, the spheres that follow carry the image),
+    emission = SKR_SCN_EMISSION (--scn-emission: emission lines parsed, the spheres that follow glow)."""
     h = C.c_void_p()
-    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0) | (SCN_SPOT if spot else 0) | (SCN_MOTION if motion else 0) | (SCN_TEXTURE if texture else 0)
+    flags = (SCN_STRICT if strict else 0) | (SCN_FOG if fog else 0) | (SCN_TRIANGLE_SHADOWS if triangle_shadows else 0) | (SCN_SPHERE_TREE if sphere_tree else 0) | (SCN_SPOT if spot else 0) | (SCN_MOTION if motion else 0) | (SCN_TEXTURE if texture else 0) | (SCN_EMISSION if emission else 0)
     _check(lib().skr_scene_create_from_scn_ex(os.fsencode(path), int(echo), flags, C.byref(h)), "skr_scene_create_from_scn_ex")
     return Scene(h.value)
 

@@ -47,12 +47,15 @@ struct DeviceScene {
 	                         // {r, g, b, 0}, row j first (launch.h Textures); null unless textures are in force
 	size_t tex_rows = 0;     // the float4 rows the per-sphere pairs take: the texels start behind them
 
+	float4 *d_emit = nullptr; // the spheres' emission {r, g, b, 0} in file order (launch.h Emission); null unless emission is in force.  With it d_tex exists too, every edge 0
+	                          // where the scene has no texture: a launch with emission carries Textures (render_generic.hip with_pack)
+
 	DeviceScene() = default;
 	DeviceScene(const DeviceScene &) = delete;
 	DeviceScene &operator=(const DeviceScene &) = delete;
 	~DeviceScene()
 	{
-		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work, (void *) d_vel, (void *) d_env, (void *) d_tex})
+		for(void *p : {(void *) d_blob, (void *) d_camec, (void *) d_counters, (void *) d_tri_work, (void *) d_st_work, (void *) d_vel, (void *) d_env, (void *) d_tex, (void *) d_emit})
 			if(p) (void) hipFree(p);
 	}
 };
@@ -257,8 +260,8 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		e = hipMalloc((void **) &s->d_env, n * 16);
 		if(e == hipSuccess) e = hipMemcpy(s->d_env, tex.data(), n * 16, hipMemcpyHostToDevice);
 	}
-	if(e == hipSuccess && s->layout.textured)
-	{ // so do the textures: the per-sphere rows, then the texels of every texture some sphere names
+	if(e == hipSuccess && (s->layout.textured || s->layout.emissive))
+	{ // so do the textures: the per-sphere rows, then the texels of every texture some sphere names (emission alone: the rows, every edge 0)
 		s->tex_rows = (ns * 8 + 15) / 16;
 		std::vector<skr_f4> tex(s->tex_rows, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
 		std::vector<uint32_t> first(scene->textures.size(), 0xFFFFFFFFu); // where texture k's texels start, once some sphere names it
@@ -280,6 +283,13 @@ int skr_renderer_create(const skr_scene *scene, int device, skr_renderer **out)
 		memcpy(tex.data(), pairs.data(), s->tex_rows * 16);
 		e = hipMalloc((void **) &s->d_tex, tex.size() * 16);
 		if(e == hipSuccess) e = hipMemcpy(s->d_tex, tex.data(), tex.size() * 16, hipMemcpyHostToDevice);
+	}
+	if(e == hipSuccess && s->layout.emissive)
+	{ // and the emission: one row per sphere
+		std::vector<skr_f4> emi(ns > 0 ? ns : 1, skr_f4{0.0f, 0.0f, 0.0f, 0.0f});
+		for(size_t i = 0; i < ns && 3 * i + 2 < scene->emission.size(); i++) emi[i] = skr_f4{scene->emission[3 * i], scene->emission[3 * i + 1], scene->emission[3 * i + 2], 0.0f};
+		e = hipMalloc((void **) &s->d_emit, emi.size() * 16);
+		if(e == hipSuccess) e = hipMemcpy(s->d_emit, emi.data(), emi.size() * 16, hipMemcpyHostToDevice);
 	}
 	if(e == hipSuccess)
 	{ // the camera belongs to the scene: its (e, c) rows are formed once, on the device, by the operations every ray would perform
@@ -413,12 +423,13 @@ struct LaunchScene {
 	const float4 *env; // the environment's texels where the scene has one (DeviceScene::d_env)
 	const float4 *tex; // the textures' rows and texels where textures are in force (DeviceScene::d_tex) ...
 	size_t tex_rows;   // ... and how many rows the per-sphere pairs take
+	const float4 *emit; // the emission rows where emission is in force (DeviceScene::d_emit)
 	const float4 *sec(SkrBlobSection k) const { return blob + layout.first[k]; } // where a section starts
 };
 static LaunchScene launch_scene(const skr_renderer *r)
 {
 	const DeviceScene &s = *r->scene;
-	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri, s.d_vel, s.d_env, s.d_tex, s.tex_rows};
+	return {s.info, s.layout, s.d_blob, s.d_camec, s.d_counters, s.d_tri_work, s.d_st_work, r->sw, r->count_tri, s.d_vel, s.d_env, s.d_tex, s.tex_rows, s.d_emit};
 }
 static float4 ball4(const skr_f4 &b) { return make_float4(b.x, b.y, b.z, b.w); }
 
@@ -610,8 +621,10 @@ static GenericFeatures generic_features(const LaunchScene &v, const RenderParams
 	f.env = s.env_edge > 0; // (frames and shading queries alike)
 	if(f.env) f.envmap = EnvMap{v.env, s.env_edge};
 	f.tex = s.textured && p.n_spheres > 0; // (frames and shading queries alike)
-	if(f.tex)
-	{ // such a launch carries the spot and radius tables too, as one with motion does (render_generic.hip with_pack)
+	f.emit = s.emissive && p.n_spheres > 0; // (frames and shading queries alike)
+	if(f.emit) f.emission = Emission{v.emit};
+	if(f.tex || f.emit)
+	{ // such a launch carries the spot and radius tables too, as one with motion does (render_generic.hip with_pack); one with emission the texture rows
 		f.textures = Textures{v.tex + v.tex_rows, reinterpret_cast<const uint2 *>(v.tex)};
 		f.spots = SpotLights{v.sec(SKR_SEC_spot), s.spot_first, s.n_spot};
 		f.softs = SoftLights{reinterpret_cast<const float *>(v.sec(SKR_SEC_radii)), s.n_radii};
@@ -776,7 +789,7 @@ static int scene_leaf_plan(const skr_scene *scene, const skr_options *opt, int w
 	load_switches(sw);
 	RenderParams p = camera_params(scene->info, opt, opt->seed, 0);
 	GenericFeatures f; // (host memory: only addresses are formed, and null-ness asked)
-	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false, reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data()), 0};
+	const LaunchScene v{scene->info, layout, reinterpret_cast<const float4 *>(rows.data()), nullptr, counters.data(), nullptr, nullptr, sw, false, reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data()), reinterpret_cast<const float4 *>(rows.data()), 0, reinterpret_cast<const float4 *>(rows.data())};
 	const int rc = launch_params(v, opt, p, f);
 	return rc != SKR_OK ? -rc : what ? (int) skr_leaf_pow_plan(p) : (int) skr_leaf_shape(p);
 }

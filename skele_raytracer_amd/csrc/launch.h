@@ -98,6 +98,14 @@ struct Textures {
 	const uint2 *rows;
 };
 
+// The emission of a scene some sphere of which glows (include/skr.h skr_scene_set_sphere_emission; render_generic.hip
+// node_value): what the activate and finalize instances for a launch with emission in force read, in a kernel argument of their own as
+// every feature is, the last of the pack.  rows: one row {r, g, b, 0} per sphere in file order, read by per-lane index as the texture
+// rows are.  An allocation of the renderer's beside the scene blob.
+struct Emission {
+	const float4 *rows;
+};
+
 // A shading query (include/skr.h skr_shade_rays) on the general level pipeline: the rays are its roots, as rows of RenderParams::width
 // rays (the last row partial), banded like a frame's rows.  The kernels' second argument (render_generic.hip).
 struct ShadeRays {
@@ -135,7 +143,9 @@ struct GenericFeatures {
 	bool env = false;         // the environment is in force: the scene has one (include/skr.h skr_scene_set_environment); frames and shading queries
 	EnvMap envmap{};          // (env; with it the finalize kernel also takes thin_lens where lens is set: a primary miss looks up d')
 	bool tex = false;         // textures are in force: some sphere has a texture (include/skr.h skr_scene_add_texture); frames and shading queries
-	Textures textures{};      // (tex; such a launch always carries spots and softs, n = 0 where the scene has none)
+	Textures textures{};      // (tex or emit; such a launch always carries spots and softs, n = 0 where the scene has none)
+	bool emit = false;        // emission is in force: some sphere has an emission component > 0 (include/skr.h skr_scene_set_sphere_emission); frames and shading queries
+	Emission emission{};      // (emit; such a launch always carries textures, every row's edge 0 where the scene has none, and with them spots and softs)
 };
 
 enum SkrPath { SKR_PATH_DIRECT = 0, SKR_PATH_NODES, SKR_PATH_GENERIC };
@@ -274,12 +284,12 @@ static inline unsigned skr_leaf_pow_plan(const RenderParams &p)
 
 // render_kernel.hip
 // lds_limit: the device's workgroup LDS.  A path whose kernels need more is not taken; lp.lds_bytes > lds_limit: no path fits.
-// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius, a lens, motion, the environment and textures take the general level pipeline
+// f: the features of the renderer's scene under this launch's options; the sphere tree, spot lights, lights with a radius, a lens, motion, the environment, textures and emission take the general level pipeline
 bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, const GenericFeatures &f); // false: the launch takes a level pipeline and not one band of it fits the budget
 // The features a launch cannot combine, given the options as the caller set them: spot lights, lights with a radius and a lens exclude
 // --legacy-reflect, fog volumes and the sphere tree; fog excludes --legacy-reflect and --shade-triangles, and with the latter triangle
 // shadows; motion excludes what they exclude, and a lens; the environment excludes --legacy-reflect, fog volumes and the sphere tree, and so do
-// textures.
+// textures and emission.
 // (Lights with a radius need the SpotLights argument: the record always carries it.)  The text for the user, or null.
 const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect, bool shade_triangles, bool fog);
 // what skr_kernel_variant() reports for a frame (query: a shading query) on the general level pipeline; static storage

@@ -5,7 +5,7 @@
 // messages and the exit-status-0 convention follow the reference.  New,
 // non-colliding flags: --seed u64 (counter-RNG key; the reference seeds rand()
 // with time(0)), --device i, --quiet (no per-line scene echo), --gpus N, --strict-scn,
-// --scn-fog, --scn-spot (spot_light lines parsed and shaded: include/skr.h SKR_SCN_SPOT), --light-radius R (every point and spot light a sphere of radius R: include/skr.h skr_scene_set_light_radii), --aperture A [--focus F] (a thin lens: depth of field, include/skr.h skr_scene_set_lens; --focus alone has no effect), --scn-motion [--shutter S] (velocity lines parsed, the spheres move while the shutter is open: motion blur, include/skr.h skr_scene_set_sphere_velocities; --shutter without velocities has no effect), --envmap FILE.pfm (a square colour PFM as the scene's environment: rays that miss return it, an image-based background and GI light, include/skr.h skr_scene_set_environment), --scn-texture (texture lines parsed, the spheres that follow carry the image as their albedo: include/skr.h SKR_SCN_TEXTURE), --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
+// --scn-fog, --scn-spot (spot_light lines parsed and shaded: include/skr.h SKR_SCN_SPOT), --light-radius R (every point and spot light a sphere of radius R: include/skr.h skr_scene_set_light_radii), --aperture A [--focus F] (a thin lens: depth of field, include/skr.h skr_scene_set_lens; --focus alone has no effect), --scn-motion [--shutter S] (velocity lines parsed, the spheres move while the shutter is open: motion blur, include/skr.h skr_scene_set_sphere_velocities; --shutter without velocities has no effect), --envmap FILE.pfm (a square colour PFM as the scene's environment: rays that miss return it, an image-based background and GI light, include/skr.h skr_scene_set_environment), --scn-texture (texture lines parsed, the spheres that follow carry the image as their albedo: include/skr.h SKR_SCN_TEXTURE), --scn-emission (emission lines parsed, the spheres that follow glow: include/skr.h SKR_SCN_EMISSION), --scn-fov, --shade-triangles, --sphere-tree (the culled sphere walk, spheres in HBM: any sphere count), --triangle-shadows (needs --shade-triangles and --shadow to have an effect; accepted without them), --legacy-reflect, --progressive K [--progressive-every M], --format ppm|png|pfm, --denoise L,
 // --adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L].
 // The frame itself is rendered by libskr on the GPU; there is no CPU path here.
 #include <cmath>
@@ -33,6 +33,7 @@ int main(int argc, char *argv[])
 	float aperture = 0.0f, focus = 1.0f;
 	bool scn_motion = false;     // --scn-motion (new: DESIGN.md 8.16; include/skr.h SKR_SCN_MOTION)
 	bool scn_texture = false;    // --scn-texture (new: DESIGN.md 8.18; include/skr.h SKR_SCN_TEXTURE)
+	bool scn_emission = false;   // --scn-emission (new: DESIGN.md 8.19; include/skr.h SKR_SCN_EMISSION)
 	bool shutter_given = false;  // --shutter S
 	float shutter = 1.0f;
 	const char *envmap = nullptr; // --envmap FILE.pfm (new: DESIGN.md 8.17; include/skr.h skr_scene_set_environment)
@@ -146,6 +147,7 @@ int main(int argc, char *argv[])
 		if(!strcmp(argv[i], "--light-radius") && has_next) { light_radius = strtof(argv[i + 1], nullptr); radius_given = true; } // new: every point and spot light a sphere of radius R
 		if(!strcmp(argv[i], "--scn-motion")) scn_motion = true;             // new: velocity lines parsed, the spheres move while the shutter is open (include/skr.h SKR_SCN_MOTION)
 		if(!strcmp(argv[i], "--scn-texture")) scn_texture = true;           // new: texture lines parsed, the spheres that follow carry the image (include/skr.h SKR_SCN_TEXTURE)
+		if(!strcmp(argv[i], "--scn-emission")) scn_emission = true;         // new: emission lines parsed, the spheres that follow glow (include/skr.h SKR_SCN_EMISSION)
 		if(!strcmp(argv[i], "--shutter") && has_next) { shutter = strtof(argv[i + 1], nullptr); shutter_given = true; } // new: the shutter S (default 1); no effect without velocities
 		if(!strcmp(argv[i], "--envmap") && has_next) envmap = argv[i + 1];     // new: the scene's environment, a square colour PFM
 		if(!strcmp(argv[i], "--aperture") && has_next) { aperture = strtof(argv[i + 1], nullptr); aperture_given = true; } // new: a thin lens of aperture radius A
@@ -182,7 +184,7 @@ int main(int argc, char *argv[])
 	}
 
 	skr_scene *scene = nullptr;
-	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u) | (triangle_shadows ? SKR_SCN_TRIANGLE_SHADOWS : 0u) | (sphere_tree ? SKR_SCN_SPHERE_TREE : 0u) | (scn_spot ? SKR_SCN_SPOT : 0u) | (scn_motion ? SKR_SCN_MOTION : 0u) | (scn_texture ? SKR_SCN_TEXTURE : 0u), &scene) != SKR_OK)
+	if(skr_scene_create_from_scn_ex(path, quiet ? 0 : 1, (strict_scn ? SKR_SCN_STRICT : 0u) | (scn_fog ? SKR_SCN_FOG : 0u) | (triangle_shadows ? SKR_SCN_TRIANGLE_SHADOWS : 0u) | (sphere_tree ? SKR_SCN_SPHERE_TREE : 0u) | (scn_spot ? SKR_SCN_SPOT : 0u) | (scn_motion ? SKR_SCN_MOTION : 0u) | (scn_texture ? SKR_SCN_TEXTURE : 0u) | (scn_emission ? SKR_SCN_EMISSION : 0u), &scene) != SKR_OK)
 	{
 		printf("%s\n", skr_last_error()); // scene.cpp:24-25: message, exit(0)
 		return 0;

@@ -58,6 +58,10 @@
 // shading normal: at a sphere with a texture kd and the ambient row are multiplied by wave_common.h env_lookup of N on that texture.
 // The finalize kernel finds N in the node's rows with the bits the activate kernel had.  Trace instances, records and nodes are as they
 // were.
+//
+// Emission (include/skr.h skr_scene_set_sphere_emission).  With an Emission in the pack — behind the Textures such a
+// launch always carries — node_value adds the sphere's row to the value it returns: the activate kernel's last-level arm and the
+// finalize kernel, nothing else.  Trace instances, records and nodes are as they were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -147,6 +151,23 @@ struct NoTextures {
 struct WithTextures {
 	static constexpr bool on = true;
 	const Textures &tx;
+};
+
+// The one statement of the emission rule: what shade() returns at surface `surf`, v the value it had.  v + e_i at sphere i, one add per
+// component; a triangle has no emission.
+SKR_DEV f3 emitted(const Emission &em, uint32_t surf, f3 v)
+{
+	if(surf & SURF_TRI) return v;
+	const float4 e = em.rows[surf];
+	return mk3(v.x + e.x, v.y + e.y, v.z + e.z);
+}
+// what node_value is handed where the launch has no emission: nothing, and no code
+struct NoEmission {
+	static constexpr bool on = false;
+};
+struct WithEmission {
+	static constexpr bool on = true;
+	const Emission &em;
 };
 
 // does the node spawn the legacy children (raytrace.h:52: a specular colour other than (0,0,0); only a sphere hit has these terms)
@@ -442,9 +463,11 @@ __global__ __launch_bounds__(256) void skr_gtrace_kernel(const RenderParams p, c
 namespace {
 
 // the value of a node whose children's values are known — or all (0,0,0): shade(depth 0), raytrace.h:142-145.  `value_of(c)`: child c.
-// TX: the launch's textures (WithTextures), or none
-template <typename F, typename TX = NoTextures>
-SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n, F value_of, const TX &tex = TX())
+// TX: the launch's textures (WithTextures), or none.  EM: its emission (WithEmission), or none: both returns go through emitted(), behind
+// the multiply by kd (nothing here is contracted).  EM travels by value: an empty NoEmission is then no argument at all, and the
+// instances without emission keep their instructions (by reference four activate instances had two loads change places)
+template <typename F, typename TX = NoTextures, typename EM = NoEmission>
+SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n, F value_of, const TX &tex = TX(), EM emi = EM())
 {
 	float4 ambp, ks4;
 	f3 kd;
@@ -466,7 +489,11 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 		}
 		direct = (direct + refraction_colour) + reflection_colour; // :102
 	}
-	if(!p.monte_carlo) return direct; // :218
+	if(!p.monte_carlo)
+	{ // :218
+		if constexpr(EM::on) return emitted(emi.em, n.surf, direct);
+		else return direct;
+	}
 	f3 total = mk3(0, 0, 0);
 	uint32_t rnd[4] = {0, 0, 0, 0};
 	for(uint32_t c = 0; c < N; c++)
@@ -476,7 +503,8 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 		total = total + div3_const(value_of(c) * r1, SKR_DIV_PDF);
 	}
 	total = total / (float) p.num_path_traces;                              // :133 (N == 0: 0/0, as in the reference)
-	return (div3_const(direct, SKR_DIV_PI) + total * 2.0f) * kd; // :213
+	if constexpr(EM::on) return emitted(emi.em, n.surf, (div3_const(direct, SKR_DIV_PI) + total * 2.0f) * kd);
+	else return (div3_const(direct, SKR_DIV_PI) + total * 2.0f) * kd; // :213
 }
 
 } // namespace
@@ -485,14 +513,16 @@ SKR_DEV f3 node_value(const SceneView &sv, const RenderParams &p, const GNode &n
 // Q: TriShadows — the shadow walk behind the sphere test; SphereTree — the sphere test is the tree's pair walk; SpotLights — the pair loop with
 //    the cone decision; SpotLights SoftLights — and the light sample ahead of it; Lens — a level-1 hit's ray starts on the lens; Motion —
 //    the normal and the shadow rays meet the spheres where they are at the sample's shutter time; Textures — the material rows of a
-//    sphere with a texture are multiplied by its colour at the normal (which packs exist: with_pack)
+//    sphere with a texture are multiplied by its colour at the normal; Emission — a last-level sphere hit's value takes the sphere's
+//    emission (which packs exist: with_pack)
 template <bool FOG, typename... Q>
 __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p, const Q... qs)
 { // a workgroup covers 256 consecutive positions of one region; positions past the region's count exit
 	constexpr bool RAYS = pack_has<ShadeRays, Q...>, TSHADOW = pack_has<TriShadows, Q...>, STREE = pack_has<SphereTree, Q...>, SPOT = pack_has<SpotLights, Q...>,
-				   SOFT = pack_has<SoftLights, Q...>, LENS = pack_has<Lens, Q...>, MOTION = pack_has<Motion, Q...>, TEX = pack_has<Textures, Q...>;
+				   SOFT = pack_has<SoftLights, Q...>, LENS = pack_has<Lens, Q...>, MOTION = pack_has<Motion, Q...>, TEX = pack_has<Textures, Q...>, EMIT = pack_has<Emission, Q...>;
 	static_assert(!MOTION || (SPOT && SOFT && !FOG && !STREE && !LENS), "a launch with motion carries SpotLights and SoftLights (with_pack)");
 	static_assert(!TEX || (SPOT && SOFT && !FOG && !STREE), "a launch with textures carries SpotLights and SoftLights (with_pack)");
+	static_assert(!EMIT || TEX, "a launch with emission carries Textures (with_pack)");
 	const ShadeRays q = pick<ShadeRays>(qs...);
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	float4 *lds4 = reinterpret_cast<float4 *>(lds_raw);
@@ -589,8 +619,10 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 		n.fr = (p.legacy_reflect && !(surf & SURF_TRI)) ? legacy_fresnel(n.d, n.N, ks4.w) : 0.0f; // :46
 		if(p.g_last)
 		{ // its children are shade(depth 0) == (0,0,0): the node is finished
-			if constexpr(TEX) store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }, WithTextures{pick<Textures>(qs...)}));
-			else store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }));
+			if constexpr(TEX && !EMIT) store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }, WithTextures{pick<Textures>(qs...)}));
+			else if constexpr(!TEX) store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }));
+			else // (the new arm last: the closure types of the two above keep the numbers they had in the instances without emission)
+				store3(p.res_out + (size_t) rec * 3, node_value(sv, p, n, [](uint32_t) { return mk3(0, 0, 0); }, WithTextures{pick<Textures>(qs...)}, WithEmission{pick<Emission>(qs...)}));
 		}
 		else
 		{
@@ -611,8 +643,10 @@ __global__ __launch_bounds__(256) void skr_gactivate_kernel(const RenderParams p
 template <typename... Q>
 __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p, const Q... qs)
 {
-	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, ENV = pack_has<EnvMap, Q...>, LENS = pack_has<Lens, Q...>, TEX = pack_has<Textures, Q...>;
+	constexpr bool RAYS = pack_has<ShadeRays, Q...>, STREE = pack_has<SphereTree, Q...>, ENV = pack_has<EnvMap, Q...>, LENS = pack_has<Lens, Q...>, TEX = pack_has<Textures, Q...>,
+				   EMIT = pack_has<Emission, Q...>;
 	static_assert(!TEX || !STREE, "textures exclude the sphere tree (skr_features_conflict)");
+	static_assert(!EMIT || TEX, "a launch with emission carries Textures (with_pack)");
 	static_assert(!ENV || !STREE, "the environment excludes the sphere tree (skr_features_conflict)");
 	static_assert(!LENS || (ENV && !RAYS), "the finalize kernel takes a Lens only behind an EnvMap, and only for frames (with_pack)");
 	const ShadeRays q = pick<ShadeRays>(qs...);
@@ -683,7 +717,8 @@ __global__ __launch_bounds__(256) void skr_gfinalize_kernel(const RenderParams p
 	GNode m = n;
 	if constexpr(ENV) own = &m;
 	// a child that does not exist (no legacy terms for this surface; fr >= 1) is never asked for by node_value()
-	if constexpr(TEX) store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of, WithTextures{pick<Textures>(qs...)}));
+	if constexpr(EMIT) store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of, WithTextures{pick<Textures>(qs...)}, WithEmission{pick<Emission>(qs...)}));
+	else if constexpr(TEX) store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of, WithTextures{pick<Textures>(qs...)}));
 	else store3(p.res_out + (size_t) n.rec * 3, node_value(sv, p, m, value_of));
 }
 
@@ -741,7 +776,9 @@ bool skr_generic_plan(const RenderParams &p, GPlan &pl, bool sphere_tree)
 // They exclude the sphere tree, and a launch with them always carries SpotLights SoftLights as one with motion does, so they add ten
 // activate instances — [ShadeRays] [TriShadows] SpotLights SoftLights [Lens | Motion] Textures, a Lens never behind ShadeRays — and five
 // finalize instances: <Textures>, <EnvMap, Textures>, <EnvMap, Lens, Textures>, <ShadeRays, Textures>, <ShadeRays, EnvMap, Textures>.
-// No trace instance takes them.
+// No trace instance takes them.  Emission comes behind Textures, the last of the pack, in the same two kernels: [...] Textures Emission.
+// A launch with emission always carries Textures (every row's edge 0 where the scene has none) and with them SpotLights SoftLights, so
+// emission mirrors the Textures instances one for one: ten activate and five finalize instances more, and no trace instance.
 enum PackOf { PACK_FINALIZE, PACK_TRACE, PACK_ACTIVATE };
 template <PackOf K, typename F>
 static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
@@ -749,7 +786,10 @@ static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 	constexpr bool ACT = K == PACK_ACTIVATE;
 	auto last = [&](auto... all) { // (the activate kernel's Textures only behind SoftLights: no other pack of it is ever asked for them)
 		if constexpr(K == PACK_FINALIZE || (ACT && pack_has<SoftLights, decltype(all)...>))
+		{
+			if(f.emit) return launch(all..., f.textures, f.emission);
 			if(f.tex) return launch(all..., f.textures);
+		}
 		launch(all...);
 	};
 	auto lens = [&](auto... all) {
@@ -762,7 +802,7 @@ static void with_pack(const GenericFeatures &f, const ShadeRays *q, F launch)
 		if constexpr(ACT)
 		{
 			if(f.motion) return last(head..., f.spots, f.softs, f.mot);
-			if(f.soft || f.tex) return lens(head..., f.spots, f.softs);
+			if(f.soft || f.tex || f.emit) return lens(head..., f.spots, f.softs);
 			if(f.spot) return lens(head..., f.spots);
 		}
 		else if constexpr(K == PACK_TRACE)

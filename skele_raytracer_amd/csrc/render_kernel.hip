@@ -34,7 +34,7 @@ static size_t direct_lds_bytes(const RenderParams &p)
 }
 
 // Which kernels render this launch, and what they need.  In this order:
-//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, a lens, motion, the environment, textures, and every tree
+//   * the general level pipeline takes the two modes only it knows (--shade-triangles, --legacy-reflect), fog volumes, spot lights, lights with a radius, a lens, motion, the environment, textures, emission, and every tree
 //     (shade() recurses: max_depth > 1; api.cpp folds --depth to 1 where it cannot, raytrace.h:208-218) the node pipeline does not;
 //   * the node pipeline takes the trees it selects (render_nodes.hip skr_nodes_plan), if a band of it fits the budget and its kernels
 //     fit the device's LDS;
@@ -46,7 +46,7 @@ bool skr_plan_launch(const RenderParams &p, size_t lds_limit, LaunchPlan &lp, co
 {
 	lp = LaunchPlan();
 	lp.features = f;
-	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft || f.lens || f.motion || f.env || f.tex;
+	const bool generic_only = f.sphere_tree || p.sw.pipeline == SKR_PIPE_GENERIC || p.shade_triangles || p.legacy_reflect || p.n_fog > 0 || f.spot || f.soft || f.lens || f.motion || f.env || f.tex || f.emit;
 	if(!generic_only && skr_nodes_plan(p, lds_limit, lp.nodes))
 	{
 		lp.path = SKR_PATH_NODES;
@@ -90,21 +90,25 @@ const char *skr_features_conflict(const GenericFeatures &f, bool legacy_reflect,
 									   "an environment map (--envmap) cannot be combined with the sphere tree (--sphere-tree)"};
 	static const char *const tex[3] = {"sphere textures (--scn-texture) cannot be combined with --legacy-reflect", "sphere textures (--scn-texture) cannot be combined with fog volumes (--scn-fog)",
 									   "sphere textures (--scn-texture) cannot be combined with the sphere tree (--sphere-tree)"};
+	static const char *const emit[3] = {"sphere emission (--scn-emission) cannot be combined with --legacy-reflect", "sphere emission (--scn-emission) cannot be combined with fog volumes (--scn-fog)",
+										"sphere emission (--scn-emission) cannot be combined with the sphere tree (--sphere-tree)"};
 	if(f.motion && f.lens) return "motion blur (sphere velocities under --shutter) cannot be combined with a lens (--aperture)";
-	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : f.lens ? lens[with] : f.motion ? motion[with] : f.env ? env[with] : f.tex ? tex[with] : nullptr;
+	return with < 0 ? nullptr : f.spot ? spot[with] : f.soft ? soft[with] : f.lens ? lens[with] : f.motion ? motion[with] : f.env ? env[with] : f.tex ? tex[with] : f.emit ? emit[with] : nullptr;
 }
 
 const char *skr_generic_variant(bool query, const GenericFeatures &f)
 { // (fog has no name of its own; a lens is a frame's: no shading query and no sphere-tree instance has one; motion excludes both; the
-  // environment's part comes last but for the textures' "_tex")
-#define SKR_VARIANT_ENV(name) {{name, name "_tex"}, {name "_env", name "_env_tex"}}
+  // environment's part comes last but for the textures' "_tex" and, behind that, the emission's "_emit")
+#define SKR_VARIANT_TEX(name) {{name, name "_emit"}, {name "_tex", name "_tex_emit"}}
+#define SKR_VARIANT_ENV(name) {SKR_VARIANT_TEX(name), SKR_VARIANT_TEX(name "_env")}
 #define SKR_VARIANT_NAMES(base) {{SKR_VARIANT_ENV(base), SKR_VARIANT_ENV(base "_tshadow")}, {SKR_VARIANT_ENV(base "_lens"), SKR_VARIANT_ENV(base "_lens_tshadow")}, {SKR_VARIANT_ENV(base "_motion"), SKR_VARIANT_ENV(base "_motion_tshadow")}}
-	static const char *const name[2][4][3][2][2][2] = {
+	static const char *const name[2][4][3][2][2][2][2] = {
 		{SKR_VARIANT_NAMES("level_pipeline_g1"), SKR_VARIANT_NAMES("level_pipeline_g1_stree"), SKR_VARIANT_NAMES("level_pipeline_g1_spot"), SKR_VARIANT_NAMES("level_pipeline_g1_soft")},
 		{SKR_VARIANT_NAMES("shade_rays_g1"), SKR_VARIANT_NAMES("shade_rays_g1_stree"), SKR_VARIANT_NAMES("shade_rays_g1_spot"), SKR_VARIANT_NAMES("shade_rays_g1_soft")}};
 #undef SKR_VARIANT_NAMES
 #undef SKR_VARIANT_ENV
-	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][f.motion ? 2 : !query && f.lens][f.tri_shadows][f.env][f.tex];
+#undef SKR_VARIANT_TEX
+	return name[query][f.sphere_tree ? 1 : f.soft ? 3 : f.spot ? 2 : 0][f.motion ? 2 : !query && f.lens][f.tri_shadows][f.env][f.tex][f.emit];
 }
 
 hipError_t skr_launch_render(const RenderParams &p, const LaunchPlan &lp, hipStream_t stream, const SkrTimingHook *hook)

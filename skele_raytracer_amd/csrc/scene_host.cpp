@@ -173,6 +173,9 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 	int32_t tex = -1; // SKR_SCN_TEXTURE: the texture in force for the sphere lines that follow (-1: none), stateful as `material` is
 	std::vector<int32_t> texs;
 	std::vector<std::string> tex_names; // the resolved name of texture k: the same name twice is one texture
+	const bool emission = (flags & SKR_SCN_EMISSION) != 0;
+	float emi[3] = {0.0f, 0.0f, 0.0f}; // SKR_SCN_EMISSION: the emission in force for the sphere lines that follow, stateful as `material` is
+	std::vector<float> emis;
 	FILE *fp = fopen(path.c_str(), "r");
 	if(!fp)
 	{
@@ -216,6 +219,7 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 			sc.raw_sphere_ior.push_back(mat.ior);
 			vels.insert(vels.end(), vel, vel + 3);
 			texs.push_back(tex);
+			emis.insert(emis.end(), emi, emi + 3);
 			info.n_spheres++;
 		}
 		else if(cmd == "vertex")
@@ -382,6 +386,21 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 				info.n_unknown++;
 			}
 		}
+		else if(emission && cmd == "emission")
+		{ // SKR_SCN_EMISSION (the reference does not know the command): r g b
+			float v[3] = {0, 0, 0};
+			const int got = read_floats(args, v, 3);
+			if(got == 3 && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && v[0] >= 0.0f && v[1] >= 0.0f && v[2] >= 0.0f)
+			{
+				if(echo) printf("emission (%f, %f, %f)\n", v[0], v[1], v[2]);
+				memcpy(emi, v, sizeof emi);
+			}
+			else
+			{
+				fprintf(stderr, "WARNING. emission needs 3 finite numbers that are not negative (r g b): line skipped\n");
+				info.n_unknown++;
+			}
+		}
 		else if(texture && cmd == "texture")
 		{ // SKR_SCN_TEXTURE (the reference does not know the command): NAME, a square colour PFM, or `none`
 			const char *a = args;
@@ -448,6 +467,7 @@ int skr_parse_scn(const std::string &path, bool echo, uint32_t flags, skr_scene 
 	sc.finalize();
 	if(motion) sc.velocities = vels;
 	if(texture) sc.sphere_textures = texs;
+	if(emission) sc.emission = emis;
 	return SKR_OK;
 }
 
@@ -776,6 +796,42 @@ int skr_scene_clear_textures(skr_scene *scene)
 {
 	if(!scene) return SKR_ERR_ARG;
 	scene->sphere_textures.clear(); // (shorter than the sphere count: -1)
+	return SKR_OK;
+}
+
+int skr_scene_set_sphere_emission(skr_scene *scene, const float *rgb, int32_t n)
+{
+	if(!scene)
+	{
+		skr_set_error("skr_scene_set_sphere_emission: null scene");
+		return SKR_ERR_ARG;
+	}
+	if(!rgb || n == 0)
+	{ // no emission
+		scene->emission.clear();
+		return SKR_OK;
+	}
+	if(n != scene->info.n_spheres)
+	{
+		skr_set_error("skr_scene_set_sphere_emission: bad argument (one emission of 3 floats per sphere: %d)", scene->info.n_spheres);
+		return SKR_ERR_ARG;
+	}
+	for(size_t i = 0; i < (size_t) n * 3; i++)
+		if(!std::isfinite(rgb[i]) || !(rgb[i] >= 0.0f))
+		{
+			skr_set_error("skr_scene_set_sphere_emission: emission %zu has a component that is not finite or is negative", i / 3);
+			return SKR_ERR_ARG;
+		}
+	scene->emission.assign(rgb, rgb + (size_t) n * 3);
+	return SKR_OK;
+}
+
+int skr_scene_get_sphere_emission(const skr_scene *scene, float *rgb, int32_t *n)
+{
+	if(!scene) return SKR_ERR_ARG;
+	const size_t ns = (size_t) scene->info.n_spheres;
+	if(n) *n = (int32_t) ns;
+	for(size_t i = 0; rgb && i < ns * 3; i++) rgb[i] = i < scene->emission.size() ? scene->emission[i] : 0.0f;
 	return SKR_OK;
 }
 

@@ -72,6 +72,13 @@ struct skr_scene {
 			if(x >= 0) return true;
 		return false;
 	}
+	std::vector<float> emission;         // [n][3] the emission of every sphere in file order, each finite and >= 0; empty = none — SKR_SCN_EMISSION / skr_scene_set_sphere_emission only (include/skr.h)
+	bool emissive() const                // emission is in force: some component of some sphere is > 0
+	{
+		for(float v : emission)
+			if(v > 0.0f) return true;
+		return false;
+	}
 	bool strict = false;                 // parsed with SKR_SCN_STRICT
 	bool triangle_shadows = false;       // SKR_SCN_TRIANGLE_SHADOWS / skr_scene_set_triangle_shadows: a renderer made from the scene takes it (include/skr.h)
 	bool sphere_tree = false;            // SKR_SCN_SPHERE_TREE / skr_scene_set_sphere_tree: likewise

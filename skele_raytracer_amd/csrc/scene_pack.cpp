@@ -87,6 +87,7 @@ std::vector<skr_f4> skr_pack_scene(const skr_scene &s, SceneLayout &d)
 	d.shutter = s.shutter;
 	d.env_edge = s.env_edge;
 	d.textured = s.textured();
+	d.emissive = s.emissive();
 	put(SKR_SEC_pad, nullptr, SKR_BLOB_PAD_ROWS * 16);
 	{ // the straight-line pow runs as many squarings as the scene's largest integer exponent has bits
 		// ... and needs a product only at a bit that some integer exponent has set (pow_any; the others take powf_spec_cold lane by lane)

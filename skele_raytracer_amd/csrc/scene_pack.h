@@ -58,6 +58,8 @@ struct SceneLayout {
 	                      // with the lookup.  The texels are no section of the blob either (api.cpp DeviceScene::d_env)
 	bool textured = false; // textures are in force (skr_scene::textured(), include/skr.h skr_scene_add_texture): frames and shading queries take the activate and finalize
 	                       // instances with the lookup.  Rows and texels are no section of the blob either (api.cpp DeviceScene::d_tex)
+	bool emissive = false; // emission is in force (skr_scene::emissive(), include/skr.h skr_scene_set_sphere_emission): frames and shading queries take the activate and finalize
+	                       // instances with the add.  The rows are no section of the blob either (api.cpp DeviceScene::d_emit)
 };
 
 // The blob of `s` and its layout; nothing is uploaded.

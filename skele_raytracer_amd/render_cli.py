@@ -3,7 +3,7 @@ per GPU.
 
     python -m skele_raytracer_amd.render_cli --path S.scn --output O.ppm [--width i] [--height i] [--fov f]
            [--gillum n] [--jsample g] [--depth d] [--parallel true|false] [--shadow] [--seed N] [--tile-rows r]
-           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--aperture A [--focus F]] [--scn-motion] [--shutter S] [--envmap FILE.pfm] [--scn-texture] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
+           [--strict-scn] [--scn-fog] [--scn-spot] [--light-radius R] [--aperture A [--focus F]] [--scn-motion] [--shutter S] [--envmap FILE.pfm] [--scn-texture] [--scn-emission] [--scn-fov] [--shade-triangles] [--triangle-shadows] [--sphere-tree] [--legacy-reflect] [--progressive K [--progressive-every M]] [--format ppm|png|pfm] [--denoise L]
            [--adaptive T [--adaptive-min K] [--adaptive-max N] [--adaptive-denoise L]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
            -m skele_raytracer_amd.render_cli --path spheres2.scn --output out.ppm --width 3840 --height 2160 \\
@@ -93,6 +93,8 @@ def _parse(argv):
             opt["scn_motion"] = True
         elif a == "--scn-texture":
             opt["scn_texture"] = True
+        elif a == "--scn-emission":
+            opt["scn_emission"] = True
         elif a == "--shutter":
             opt["shutter"] = value(i, _atof, "shutter takes a float (how long the shutter is open)")
         elif a == "--envmap":
@@ -199,7 +201,8 @@ def main(argv=None):
         return 2
     try:
         scene = skr.parse_scene(o["path"], strict=bool(o.get("strict_scn")), fog=bool(o.get("scn_fog")), triangle_shadows=bool(o.get("triangle_shadows")),
-                                sphere_tree=bool(o.get("sphere_tree")), spot=bool(o.get("scn_spot")), motion=bool(o.get("scn_motion")), texture=bool(o.get("scn_texture")))
+                                sphere_tree=bool(o.get("sphere_tree")), spot=bool(o.get("scn_spot")), motion=bool(o.get("scn_motion")), texture=bool(o.get("scn_texture")),
+                                emission=bool(o.get("scn_emission")))
     except skr.SkrError as e:
         if rank == 0:
             print(str(e))  # scene.cpp:24: "Can't open file" on stdout, exit(0)

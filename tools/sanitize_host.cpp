@@ -308,5 +308,60 @@ int main(int argc, char **argv)
 		printf("tex: null scene %d %d %d %d %d %d\n", skr_scene_add_texture(nullptr, t2.data(), 2), skr_scene_texture_count(nullptr), skr_scene_get_texture(nullptr, 0, nullptr, nullptr),
 			   skr_scene_set_sphere_textures(nullptr, nullptr, 0), skr_scene_get_sphere_textures(nullptr, nullptr, nullptr), skr_scene_clear_textures(nullptr));
 	}
+	{ // sphere emission: the setter and the getter with good and bad arguments, and the parser's `emission` lines, valid, malformed, negative and not finite
+		FILE *fp = fopen("build/asan_emit.scn", "w");
+		if(fp)
+		{
+			fputs("sphere 0 0 0 1\nemission 1 0.5 0.25\nsphere 1 0 0 1\nemission\nemission  \t \nemission 1 2\nemission 1 -2 3\nemission nan 0 0\nemission 0 inf 0\nemission 0 0 -inf\nemission a b c\n"
+				  "emission 1e39 0 0\nsphere 2 0 0 1\nemission 0 0 7 trailing words\nsphere 3 0 0 1\nemission 0 0 0\nsphere 4 0 0 1\nemission -0 -0 -0\nsphere 5 0 0 1\nemission 1e-46 3 3\nsphere 6 0 0 1\n", fp);
+			fclose(fp);
+		}
+		for(uint32_t flags : {0u, (uint32_t) SKR_SCN_EMISSION, (uint32_t) (SKR_SCN_EMISSION | SKR_SCN_TEXTURE | SKR_SCN_MOTION | SKR_SCN_STRICT)})
+		{
+			skr_scene *sc = nullptr;
+			if(skr_scene_create_from_scn_ex("build/asan_emit.scn", 0, flags, &sc) != 0) continue;
+			skr_scene_info info;
+			skr_scene_get_info(sc, &info);
+			int32_t n = -1;
+			skr_scene_get_sphere_emission(sc, nullptr, &n);
+			std::vector<float> e((size_t) (n > 0 ? n : 0) * 3 + 1, 77.0f);
+			skr_scene_get_sphere_emission(sc, e.data(), &n);
+			printf("emit: flags %u spheres %d unknown %d, emission", flags, n, info.n_unknown);
+			for(int32_t i = 0; i < 3 * n; i++) printf(" %g", e[(size_t) i]);
+			printf(", guard %g\n", e[(size_t) n * 3]);
+			blob_table(sc, "emit", "parsed");
+			skr_scene_destroy(sc);
+		}
+		skr_scene *sc = nullptr;
+		if(skr_scene_create_from_scn("build/bad1.scn", 0, &sc) == 0)
+		{
+			skr_scene_info info;
+			skr_scene_get_info(sc, &info);
+			const int32_t ns = info.n_spheres;
+			std::vector<float> e((size_t) ns * 3 + 3, 0.5f), back((size_t) ns * 3 + 1, 77.0f);
+			if(ns > 0) e[1] = -0.0f;
+			const int set = skr_scene_set_sphere_emission(sc, e.data(), ns), shorter = skr_scene_set_sphere_emission(sc, e.data(), ns - 1), longer = skr_scene_set_sphere_emission(sc, e.data(), ns + 1),
+					  negative_n = skr_scene_set_sphere_emission(sc, e.data(), -ns);
+			int refused[4] = {0, 0, 0, 0};
+			const float bad[4] = {NAN, INFINITY, -INFINITY, -1.0f};
+			for(int k = 0; k < 4 && ns > 0; k++)
+			{ // the last component of the last sphere: the whole array is read before anything is stored
+				e[(size_t) ns * 3 - 1] = bad[k];
+				refused[k] = skr_scene_set_sphere_emission(sc, e.data(), ns);
+			}
+			int32_t n = -1;
+			skr_scene_get_sphere_emission(sc, back.data(), &n);
+			printf("emit: set %d, refused %d %d %d, %d %d %d %d, n %d first %g %g last %g guard %g\n", set, shorter, longer, negative_n, refused[0], refused[1], refused[2], refused[3], n,
+				   n > 0 ? back[0] : 0.0f, n > 0 ? back[1] : 0.0f, n > 0 ? back[(size_t) n * 3 - 1] : 0.0f, back[(size_t) n * 3]);
+			blob_table(sc, "emit", "set");
+			const int cleared = skr_scene_set_sphere_emission(sc, nullptr, ns);
+			skr_scene_get_sphere_emission(sc, back.data(), &n);
+			e[(size_t) ns * 3 - (ns > 0 ? 1 : 0)] = 0.5f;
+			const int again = skr_scene_set_sphere_emission(sc, e.data(), ns), zero_n = skr_scene_set_sphere_emission(sc, e.data(), 0);
+			printf("emit: cleared %d first %g, set %d, n = 0 clears %d\n", cleared, n > 0 ? back[0] : 0.0f, again, zero_n);
+			skr_scene_destroy(sc);
+		}
+		printf("emit: null scene %d %d\n", skr_scene_set_sphere_emission(nullptr, nullptr, 0), skr_scene_get_sphere_emission(nullptr, nullptr, nullptr));
+	}
 	return 0;
 }
